@@ -16,6 +16,13 @@ N > 1: weak scaling -- every rank draws its own n_mc-sample shard of ONE estimat
 (csrc/kernels_p2p.hip; RCCL when the areas cannot be mapped), the exchange of estimate t overlapped with the kernels of
 estimate t+1; `value` counts n_mc-sample estimate units processed by all ranks per second; `dist` holds the route taken and the
 per-stage times {partials, exchange, serial, pipelined}.
+
+A plain run does only what the headline needs: set-up, warm-up (+ pre-heat), the K timed steps, the result line.  `--full` adds every
+other measurement and check on top of the same timed region: repeats of it, the roofline / per-kernel figures, the concurrent-streams leg,
+the steady-state leg, the other BASELINE configurations and precisions (`also`), parity against the fp64 oracle and the CPU baseline, and
+for N > 1 the per-rank exchange diagnostics, the estimate-sharded line and the per-stage times.
+`--dump-outputs DIR` writes what the timed path returned in its last step (the estimate's `value` and `grad`, float32) as DIR/<name>.npy;
+the timed steps' estimate indices are fixed by the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -52,10 +59,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="ns", choices=sorted(WORKLOADS))
     ap.add_argument("--graph-chunk", type=int, default=100, help="estimates per hipGraph replay (N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the other BASELINE configurations (c2, ns_dense, ns_stl, c5, c3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every non-headline measurement and check (rooflines, other configurations, parity, CPU baseline, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (value, grad) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip parity against the oracle and the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the other BASELINE configurations (c2, ns_dense, ns_stl, c5, c3)")
     ap.add_argument("--concurrent", type=int, default=4,
-                    help="extra (non-headline) leg: this many independent estimator contexts on separate HIP streams")
+                    help="with --full, extra (non-headline) leg: this many independent estimator contexts on separate HIP streams")
     args = ap.parse_args()
 
     # A/B switches select in-library REFERENCE routes: a bench line measured under one is not the product's number.  Refuse to run.
@@ -241,13 +252,16 @@ def main():
         # -- 0.2 ms for the driver's --steps 20 -- does not sit on the clock ramp of a GPU that was idle a moment ago (measured in one
         # process, same call: 16-24 us per estimate in its first tens of milliseconds of GPU work, 11-13 us after a few hundred)
         t_heat, heat_calls = time.perf_counter(), 0
-        idx_t = W + chunk          # the estimate index walks on, so the timed call continues the device-side counter (no counter-setting launch)
+        idx_h = 1 << 32            # the pre-heat's own estimate indices: its call count follows the clock, the timed steps' indices must not
         while time.perf_counter() - t_heat < 0.3 or heat_calls < 3:
-            run(idx_t, max(chunk, 1))
-            idx_t += max(chunk, 1)
+            run(idx_h, max(chunk, 1))
+            idx_h += max(chunk, 1)
             heat_calls += 1
             if heat_calls % 8 == 0:
                 stream.synchronize()
+        # the three calls below walk the indices on from a point fixed by the arguments, so the timed steps (and --dump-outputs) see the same
+        # inputs in every run and the timed call continues the device-side counter (no counter-setting launch)
+        idx_t = W + chunk
         for _ in range(3):   # ... ending on the timed region's own rhythm: one call, device-wide synchronize (the first isolated call behind a
             stream.synchronize()   # queue of back-to-back ones measured 1.2 us per estimate slower than the ones after it: `repeat_ms_per_step`)
             torch.cuda.synchronize()
@@ -263,8 +277,12 @@ def main():
         if dist:
             dist.barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:   # what the caller of the timed path holds after its last step (the legs below reuse the buffers)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, t in (("value", value), ("grad", grad)):
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().cpu().numpy().astype(np.float32))
         repeats = []
-        if single:   # the same timed region again, back to back (diagnostic: what a longer-running process sees for the same K steps)
+        if single and args.full:   # the same timed region again, back to back (diagnostic: what a longer-running process sees for the same K steps)
             for r in range(5):
                 torch.cuda.synchronize()
                 tr = time.perf_counter()
@@ -277,7 +295,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
 
-        if not single:
+        if not single and args.full:
             # per-rank diagnostics of the timed region's exchange (route p2p): what the exchange kernel waited for -- the own compute chain,
             # the peers' pushes, the owners' reduced chunks -- and the bytes stored into every peer: one line tells a slow link from a slow rank
             try:
@@ -415,7 +433,7 @@ def main():
             # ---- roofline leg: hipEvent-timed launches of the dominant kernel on the launch stream ----------
             roof = None
             stages = {}
-            if single and w["target"] in ("iso", "dense"):
+            if args.full and single and w["target"] in ("iso", "dense"):
                 reps = 300
                 if w["family"] == 0:
                     roof, stages = mf_roofline(ctx, params, cost)
@@ -430,9 +448,9 @@ def main():
                 stages = {k: round(v * 1e3, 3) for k, v in stages.items()}   # us
                 if w["family"] == 1 and w["entropy"] in (3, 4):
                     roof["stl_term"] = stl_block(ctx, params, w)
-            elif single:
+            elif args.full and single:
                 roof = other_roofline(ctx, params, w, dt / K)
-            elif w["family"] == 1 and w["target"] in ("iso", "dense"):
+            elif args.full and w["family"] == 1 and w["target"] in ("iso", "dense"):
                 # N > 1: the dominant kernel is the same per-rank product kernel on this rank's shard (no collective inside these launches)
                 try:
                     roof, stages = fr_roofline(ctx, params, cost, w)
@@ -448,7 +466,7 @@ def main():
             # star's family / target: the batch engine, three launches per step of up to 80 estimates -- config.launch).  What an optimiser
             # loop sees -- every estimate behind the previous update, one dependent chain -- is `also.ns_adam_loop`.
             conc = None
-            if single and args.concurrent > 1 and w["target"] in ("iso", "dense"):
+            if args.full and single and args.concurrent > 1 and w["target"] in ("iso", "dense"):
                 S = args.concurrent
                 streams = [torch.cuda.Stream(device=local_rank) for _ in range(S)]
                 ctxs, bufs = [], []
@@ -480,7 +498,7 @@ def main():
             # the driver's --steps, and its own roofline block
             also = None
             steady = None
-            if single:
+            if args.full and single:
                 n_ss = 1000
                 run(idx_t + K, chunk)          # (graph already instantiated)
                 t_h = time.perf_counter()      # the legs above left the GPU idle between their synchronisations: back to full clocks first
@@ -492,7 +510,7 @@ def main():
                 stream.synchronize()
                 tss = time.perf_counter() - t0s
                 steady = dict(estimates=n_ss, us_per_step=tss / n_ss * 1e6, estimates_per_s=n_ss / tss)
-            if single and args.workload == "ns" and not args.no_also:
+            if args.full and single and args.workload == "ns" and not args.no_also:
                 also = {}
                 for wn in ("c2", "ns_dense", "ns_stl", "c5") + (() if os.environ.get("MIVI_BENCH_SKIP_C3") else ("c3",)):
                     w2 = WORKLOADS[wn]
@@ -816,7 +834,7 @@ def main():
             rel = None
             parity_head = None
             cpub = None
-            if single and not args.no_cpu_baseline:
+            if args.full and single and not args.no_cpu_baseline:
                 from oracle import c_oracle as CO
                 if w["target"] == "iso":
                     cpub = cpu_baseline(w, params_h)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B: XCD-affine product / draw tables (FBX_AFF bit 0) and write-back plane stores (bit 1)
-line() { python bench.py --no-cpu-baseline --no-also "$@" 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.readline()); print(j['value'], j['ms_per_step'])"; }
+line() { python bench.py --full --no-cpu-baseline --no-also "$@" 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.readline()); print(j['value'], j['ms_per_step'])"; }
 for r in 1 2; do
   for v in 0 1 2 3; do
     echo "FBX_AFF=$v round $r: driver $(FBX_AFF=$v line --steps 20 --warmup 5) | ns $(FBX_AFF=$v line) | stl $(FBX_AFF=$v line --workload ns_stl)"

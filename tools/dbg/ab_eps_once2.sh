@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B: the draws in both orientations (e0) against the draws once + transposing VJP reads (e1)
-line() { python bench.py --no-cpu-baseline --no-also "$@" 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.readline()); print(j['value'], j['ms_per_step'])"; }
+line() { python bench.py --full --no-cpu-baseline --no-also "$@" 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.readline()); print(j['value'], j['ms_per_step'])"; }
 for r in 1 2 3; do
   for v in e0 e1; do
     cp tools/bin/libmivi_$v.so advancedvi.jl_amd/libmivi.so

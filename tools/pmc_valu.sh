@@ -7,8 +7,8 @@ TAG=${1:-r0x}
 REPO=$(pwd); OUT=$REPO/gpurun_out/summ; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 for w in c2 c5; do
   rm -rf /tmp/pmc_valu_$w
-  { echo "# $TAG: rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU -- python bench.py --workload $w --steps 2000 --warmup 200 --no-cpu-baseline --no-also --concurrent 1"; echo; } > $OUT/${TAG}_${w}_pmc_valu.md
-  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU -d /tmp/pmc_valu_$w -o run -- python $REPO/bench.py --workload $w --steps 2000 --warmup 200 --no-cpu-baseline --no-also --concurrent 1 > /tmp/pmc_valu_$w.log 2>&1
+  { echo "# $TAG: rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU -- python bench.py --full --workload $w --steps 2000 --warmup 200 --no-cpu-baseline --no-also --concurrent 1"; echo; } > $OUT/${TAG}_${w}_pmc_valu.md
+  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU -d /tmp/pmc_valu_$w -o run -- python $REPO/bench.py --full --workload $w --steps 2000 --warmup 200 --no-cpu-baseline --no-also --concurrent 1 > /tmp/pmc_valu_$w.log 2>&1
   db=$(find /tmp/pmc_valu_$w -name '*.db' | head -1)
   if [ -n "$db" ]; then python $REPO/tools/rocpd_pmc.py $db | grep -E "k_mf_|^\| kernel|^\|---" >> $OUT/${TAG}_${w}_pmc_valu.md; else echo "(no database: $(tail -2 /tmp/pmc_valu_$w.log))" >> $OUT/${TAG}_${w}_pmc_valu.md; fi
 done

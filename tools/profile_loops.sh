@@ -12,5 +12,5 @@ db=$(find /tmp/prof_lr -name '*.db' | head -1)
 { echo "# $TAG: rocprofv3 --kernel-trace --stats -- python tools/logreg_loop_bench.py 1,208,61,1 0,208,61,1 0,1000,33,16 (README-sized: k_lr_small_loop; BASELINE configs[0]: the hipGraph of launches)"; echo;
   python $REPO/tools/rocpd_stats.py $db | head -24; echo; echo '```'; grep "^family" /tmp/prof_lr.log; echo '```'; } > $OUT/${TAG}_logreg_loops_kernel_stats.md
 cd $REPO
-python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${TAG}_bench_driver_protocol.json
-python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench_ns_default.json
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${TAG}_bench_driver_protocol.json
+python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_ns_default.json
