@@ -2,26 +2,6 @@
 // third-generation batch engine (kernels_fullrank_batch.hip): mivi_estimate_gradient_n / _each.
 #include "api_common.h"
 
-// ---------------------------------------------------------------------------------------------
-// hipGraph-batched estimates and the device-resident optimisation loop
-// ---------------------------------------------------------------------------------------------
-// The null stream cannot be captured: record on an internal stream, replay on the context's stream.
-mivi_status_t begin_capture(mivi_ctx *c, hipStream_t *saved) {
-  if (!c->cap_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
-
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // pending memsets / uploads on the launch stream
-  *saved = c->stream;
-  c->stream = c->cap_stream;
-  hipError_t e = hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) { c->stream = *saved; c->err = std::string("hipStreamBeginCapture: ") + hipGetErrorString(e); return MIVI_ERR_HIP; }
-  return MIVI_OK;
-}
-hipError_t end_capture(mivi_ctx *c, hipStream_t saved, hipGraph_t *graph) {
-  hipError_t e = hipStreamEndCapture(c->cap_stream, graph);
-  c->stream = saved;
-  return e;
-}
-
 bool graph_capturable(const mivi_ctx *c) {   // every device-resident target (the host callback is not)
   return c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS || c->target == TGT_FUNNEL || c->target == TGT_LOGREG;
 }
@@ -29,6 +9,33 @@ bool graph_capturable(const mivi_ctx *c) {   // every device-resident target (th
 mivi_status_t reserve_target(mivi_ctx *c, int M) {
   if (c->target == TGT_LOGREG && !logreg_reserve(c, M)) return fail(c, MIVI_ERR_HIP, "logistic regression: scratch allocation failed");
   return MIVI_OK;
+}
+
+// `cnt` chained estimates of context k at fixed parameters: indices first, first + stride, ... -- by value (idx_ptr = nullptr: an eager
+// chain) or relative to the device-side counter *idx_ptr (a recording).  Every estimate but the last writes its result where the last one
+// does; the chain's closing value launch is flush_chain's.
+// The eps speculation is off afterwards.  (run_estimate clears pre_valid on entry and sets it only on its `spec` branches, which a
+// chained gradient estimate never takes: the second-generation route has spec = !chained, and the first-generation route is chained
+// exactly when hetero_ok holds, which spec needs too.  So the flag can only have survived an estimate that failed before it got there.)
+static mivi_status_t record_chain(mivi_ctx *k, const void *params, uint64_t first, uint64_t stride, int cnt, const uint64_t *idx_ptr, void *value,
+                                  void *grad) {
+  Chain chn;
+  chn.on = true;
+  chn.estimates_only = true;
+  mivi_status_t s = MIVI_OK;
+  for (int i = 0; i < cnt && s == MIVI_OK; ++i) {
+    RngArgs r = rng_of(k, first + (uint64_t)i * stride);
+    if (idx_ptr) r.idx_ptr = idx_ptr;
+    k->cur = i & 1;
+    chn.has_next = (i + 1 < cnt);
+    chn.next_rng = rng_of(k, first + ((uint64_t)i + 1) * stride);
+    chn.next_rng.idx_ptr = r.idx_ptr;
+    s = run_estimate(k, params, r, k->cfg.n_mc, 1, final_out(k, value, grad), &chn);
+  }
+  if (s == MIVI_OK) flush_chain(k, params, &chn);
+  k->cur = 0;
+  k->pre_valid = false;
+  return s;
 }
 
 static mivi_status_t estimate_gradient_chain(mivi_ctx *c, const void *params, uint64_t idx0, int32_t count, void *value, void *grad) {
@@ -78,58 +85,21 @@ static mivi_status_t estimate_gradient_chain(mivi_ctx *c, const void *params, ui
   // smallest batch that is captured.
   static const int graph_min = getenv("MIVI_GRAPH_MIN") ? atoi(getenv("MIVI_GRAPH_MIN")) : 6;
   if (count < graph_min && c->cfg.family == MIVI_FULLRANK) {
-    Chain chn;
-    chn.on = true;
-    chn.estimates_only = true;
-    for (int i = 0; i < count && s == MIVI_OK; ++i) {
-      c->cur = i & 1;
-      chn.has_next = (i + 1 < count);
-      chn.next_rng = rng_of(c, idx0 + ((uint64_t)i + 1) * st);
-      s = run_estimate(c, params, rng_of(c, idx0 + (uint64_t)i * st), c->cfg.n_mc, 1, final_out(c, value, grad), &chn);
-    }
-    if (s == MIVI_OK) flush_chain(c, params, &chn);
-    c->cur = 0;
-    c->pre_valid = false;
-    if (s) return s;
+    if ((s = record_chain(c, params, idx0, st, count, nullptr, value, grad))) return s;
     HIPCHK(c, hipGetLastError());
     return MIVI_OK;
   }
-  GraphCache &g = c->graph;
-  if (!(g.exec && g.kind == 1 && g.count == count && g.params == params && g.value == value && g.grad == grad)) {
+  const GraphKey key{GRAPH_CHAIN, count, params, value, grad};
+  if (!c->graph.matches(key)) {
     invalidate_graph(c);
-    hipGraph_t graph = nullptr;
-    hipStream_t saved;
-    if ((s = begin_capture(c, &saved))) return s;
-    Chain chn;
-    chn.on = true;
-    chn.estimates_only = true;
-    for (int i = 0; i < count && s == MIVI_OK; ++i) {
-      RngArgs r = rng_of(c, (uint64_t)i * st);
-      r.idx_ptr = (const uint64_t *)c->d_idx.p;
-      c->cur = i & 1;
-      chn.has_next = (i + 1 < count);
-      chn.next_rng = rng_of(c, ((uint64_t)i + 1) * st);
-      chn.next_rng.idx_ptr = r.idx_ptr;
-      s = run_estimate(c, params, r, c->cfg.n_mc, 1, final_out(c, value, grad), &chn);
-    }
-    if (s == MIVI_OK) flush_chain(c, params, &chn);
-    // the graph leaves the device-side estimate counter at idx0 + count * st: a caller that walks the indices in order (an SGD-style
-    // driver does) needs no counter-setting launch in front of the next replay
-    if (s == MIVI_OK) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count * st);
-    c->cur = 0;
-    hipError_t e = end_capture(c, saved, &graph);
-    if (s) { if (graph) (void)hipGraphDestroy(graph); return s; }
-    HIPCHK(c, e);
-    HIPCHK(c, hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    g.kind = 1; g.count = count; g.params = params; g.value = value; g.grad = grad;
+    s = graph_record(c, key, [&]() -> mivi_status_t {
+      const mivi_status_t rs = record_chain(c, params, 0, st, count, (const uint64_t *)c->d_idx.p, value, grad);
+      if (rs == MIVI_OK) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count * st);
+      return rs;
+    });
+    if (s) return s;
   }
-  if (!(c->d_idx_valid && c->d_idx_expect == idx0))
-    hipLaunchKernelGGL(k_set_u64x2, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, idx0, 0ull, 1);
-  HIPCHK(c, hipGraphLaunch(g.exec, c->stream));
-  c->d_idx_valid = true;
-  c->d_idx_expect = idx0 + (uint64_t)count * st;
-  return MIVI_OK;
+  return graph_replay(c, idx0, (uint64_t)count * st);
 }
 
 // ---- interleaved chains ------------------------------------------------------------------------------------------------------------
@@ -172,6 +142,37 @@ mivi_status_t ensure_kids(mivi_ctx *c, int lanes) {
     }
     c->kids[c->n_kids++] = k;
   }
+  return MIVI_OK;
+}
+
+// On a cache miss, before a recording that spans the children: invalidate_graph has just bumped the generation the children were synced
+// to (sync_kid), so re-stamp it; and their streams carry their table uploads, which have to be done before the capture (not on every replay).
+mivi_status_t kids_before_capture(mivi_ctx *c, int lanes) {
+  for (int j = 0; j < lanes - 1; ++j) {
+    c->kids[j]->kid_gen = c->target_gen;
+    HIPCHK(c, hipStreamSynchronize(c->kids[j]->stream));
+  }
+  return MIVI_OK;
+}
+
+// The fork / join of a recording with B parallel branches (at most four: see kMaxKids): branch 0 is the context's own stream; branch b > 0
+// runs on the stream of child b E - 1, which joins the capture behind ONE fork event and is joined back through its own event.  The
+// recording closes by advancing the device-side estimate counter by `count`.
+template <class Branch> static mivi_status_t record_branches(mivi_ctx *c, int B, int E, int count, Branch &branch) {
+  mivi_status_t s = MIVI_OK;
+  hipError_t he = hipEventRecord(c->ev_fork, c->stream);
+  for (int b = 1; b < B && s == MIVI_OK && he == hipSuccess; ++b) {
+    hipStream_t bs = c->kids[b * E - 1]->stream;
+    he = hipStreamWaitEvent(bs, c->ev_fork, 0);   // the branch's stream joins the capture
+    if (he != hipSuccess) break;
+    s = branch(b);
+    if (s == MIVI_OK) he = hipEventRecord(c->ev_join[b * E - 1], bs);
+  }
+  if (s == MIVI_OK && he == hipSuccess) s = branch(0);
+  for (int b = 1; b < B && s == MIVI_OK && he == hipSuccess; ++b) he = hipStreamWaitEvent(c->stream, c->ev_join[b * E - 1], 0);
+  if (s == MIVI_OK && he == hipSuccess) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count);
+  if (s) return s;
+  HIPCHK(c, he);
   return MIVI_OK;
 }
 
@@ -472,23 +473,16 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
     if (!lds_prepare(k, k->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");
   }
   if (!lds_prepare(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");
-  GraphCache &g = c->graph;
   // LANE-BATCHED contexts: the launchers of the two kernels record their arguments into a sink instead of launching
   // (kernels_fullrank_lds.hip: launch_lanes_*), the driver issues one launch per kernel and branch.
   if (lane_e > 0) {
-    const int lane_mode = lane_e;
-    const int E = lane_mode, B = lanes / E;
-    if (!(g.exec && g.kind == 3 && g.count == count && g.params == params && g.value == value && g.grad == grad && g.p0 == (double)(lanes * 16 + E))) {
+    const int E = lane_e, B = lanes / E;
+    GraphKey key{GRAPH_LANE_BRANCHES, count, params, value, grad};
+    key.lanes = lanes;
+    key.per_branch = E;
+    if (!c->graph.matches(key)) {
       invalidate_graph(c);
-      c->idx_stride = lanes;
-      for (int j = 0; j < lanes - 1; ++j) {
-        c->kids[j]->kid_gen = c->target_gen;
-        HIPCHK(c, hipStreamSynchronize(c->kids[j]->stream));
-      }
-      hipGraph_t graph = nullptr;
-      hipStream_t saved;
-      if ((s = begin_capture(c, &saved))) return s;
-      hipError_t he = hipEventRecord(c->ev_fork, c->stream);
+      if ((s = kids_before_capture(c, lanes))) return s;
       mivi_ctx *ctxs[1 + mivi_ctx::kMaxKids];
       ctxs[0] = c;
       for (int l = 1; l < lanes; ++l) ctxs[l] = c->kids[l - 1];
@@ -561,90 +555,26 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
         eps_sink_free(esink);
         return st;
       };
-      for (int b = 1; b < B && s == MIVI_OK && he == hipSuccess; ++b) {
-        mivi_ctx *k = ctxs[b * E];
-        he = hipStreamWaitEvent(k->stream, c->ev_fork, 0);   // the branch's stream joins the capture
-        if (he != hipSuccess) break;
-        s = branch(b);
-        if (s == MIVI_OK) he = hipEventRecord(c->ev_join[b * E - 1], k->stream);
-      }
-      if (s == MIVI_OK && he == hipSuccess) s = branch(0);
-      for (int b = 1; b < B && s == MIVI_OK && he == hipSuccess; ++b) he = hipStreamWaitEvent(c->stream, c->ev_join[b * E - 1], 0);
-      if (s == MIVI_OK && he == hipSuccess) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count);
-      hipError_t e = end_capture(c, saved, &graph);
-      if (s) { if (graph) (void)hipGraphDestroy(graph); return s; }
-      HIPCHK(c, he);
-      HIPCHK(c, e);
-      HIPCHK(c, hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-      (void)hipGraphDestroy(graph);
-      g.kind = 3; g.count = count; g.params = params; g.value = value; g.grad = grad; g.p0 = (double)(lanes * 16 + E);
+      if ((s = graph_record(c, key, [&]() { return record_branches(c, B, E, count, branch); }))) return s;
     }
-    if (!(c->d_idx_valid && c->d_idx_expect == idx0))
-      hipLaunchKernelGGL(k_set_u64x2, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, idx0, 0ull, 1);
-    HIPCHK(c, hipGraphLaunch(g.exec, c->stream));
-    c->d_idx_valid = true;
-    c->d_idx_expect = idx0 + (uint64_t)count;
-    return MIVI_OK;
+    return graph_replay(c, idx0, (uint64_t)count);
   }
-  if (!(g.exec && g.kind == 2 && g.count == count && g.params == params && g.value == value && g.grad == grad && g.p0 == (double)lanes)) {
+  GraphKey key{GRAPH_FORKED_CHAINS, count, params, value, grad};
+  key.lanes = lanes;
+  if (!c->graph.matches(key)) {
     invalidate_graph(c);
-    c->idx_stride = lanes;   // (invalidate_graph leaves it; the children were synced above: re-stamp their generation)
-    for (int j = 0; j < lanes - 1; ++j) {
-      c->kids[j]->kid_gen = c->target_gen;
-      HIPCHK(c, hipStreamSynchronize(c->kids[j]->stream));   // (their table uploads, before the capture -- not on every replay)
-    }
-    hipGraph_t graph = nullptr;
-    hipStream_t saved;
-    if ((s = begin_capture(c, &saved))) return s;
-    hipError_t he = hipEventRecord(c->ev_fork, c->stream);
-    auto chain_body = [&](mivi_ctx *k, int q, int cnt, void *v, void *gr) -> mivi_status_t {
-      Chain chn;
-      chn.on = true;
-      chn.estimates_only = true;
-      mivi_status_t st = MIVI_OK;
-      for (int i = 0; i < cnt && st == MIVI_OK; ++i) {
-        RngArgs r = rng_of(k, (uint64_t)q + (uint64_t)i * lanes);
-        r.idx_ptr = (const uint64_t *)c->d_idx.p;   // ONE device counter (the parent's) for all chains
-        k->cur = i & 1;
-        chn.has_next = (i + 1 < cnt);
-        chn.next_rng = rng_of(k, (uint64_t)q + ((uint64_t)i + 1) * lanes);
-        chn.next_rng.idx_ptr = r.idx_ptr;
-        st = run_estimate(k, params, r, k->cfg.n_mc, 1, final_out(k, v, gr), &chn);
-      }
-      if (st == MIVI_OK) flush_chain(k, params, &chn);
-      k->cur = 0;
-      k->pre_valid = false;
-      return st;
+    if ((s = kids_before_capture(c, lanes))) return s;
+    auto chain = [&](int q) -> mivi_status_t {   // chain q: this context (q = 0) or child q - 1, estimates q, q + lanes, ... relative to ONE device counter (the parent's)
+      mivi_ctx *k = q ? c->kids[q - 1] : c;
+      char *ko = q ? (char *)c->kid_out[q - 1].p : (char *)c->tmp_out.p;
+      const mivi_status_t cs = record_chain(k, params, (uint64_t)q, (uint64_t)lanes, (count - q + lanes - 1) / lanes, (const uint64_t *)c->d_idx.p,
+                                            q == q_last ? value : (void *)ko, q == q_last ? grad : (void *)(ko + 16));
+      if (cs && q) c->err = k->err;
+      return cs;
     };
-    for (int q = 1; q < lanes && s == MIVI_OK && he == hipSuccess; ++q) {
-      mivi_ctx *k = c->kids[q - 1];
-      char *ko = (char *)c->kid_out[q - 1].p;
-      he = hipStreamWaitEvent(k->stream, c->ev_fork, 0);   // the child's stream joins the capture
-      if (he != hipSuccess) break;
-      s = chain_body(k, q, (count - q + lanes - 1) / lanes, q == q_last ? value : (void *)ko, q == q_last ? grad : (void *)(ko + 16));
-      if (s) c->err = k->err;
-      if (s == MIVI_OK) he = hipEventRecord(c->ev_join[q - 1], k->stream);
-    }
-    if (s == MIVI_OK && he == hipSuccess) {
-      char *ko = (char *)c->tmp_out.p;
-      s = chain_body(c, 0, (count + lanes - 1) / lanes, q_last == 0 ? value : (void *)ko, q_last == 0 ? grad : (void *)(ko + 16));
-    }
-    for (int q = 1; q < lanes && s == MIVI_OK && he == hipSuccess; ++q) he = hipStreamWaitEvent(c->stream, c->ev_join[q - 1], 0);
-    if (s == MIVI_OK && he == hipSuccess) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count);
-    hipError_t e = end_capture(c, saved, &graph);
-    if (s) { if (graph) (void)hipGraphDestroy(graph); return s; }
-    HIPCHK(c, he);
-    HIPCHK(c, e);
-    HIPCHK(c, hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    g.kind = 2; g.count = count; g.params = params; g.value = value; g.grad = grad; g.p0 = (double)lanes;
+    if ((s = graph_record(c, key, [&]() { return record_branches(c, lanes, 1, count, chain); }))) return s;
   }
-  if (!(c->d_idx_valid && c->d_idx_expect == idx0))
-    hipLaunchKernelGGL(k_set_u64x2, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, idx0, 0ull, 1);
-  HIPCHK(c, hipGraphLaunch(g.exec, c->stream));
-  c->d_idx_valid = true;
-  c->d_idx_expect = idx0 + (uint64_t)count;
   // (the children's sticky status flags are folded in by mivi_synchronize / read_status)
-  return MIVI_OK;
+  return graph_replay(c, idx0, (uint64_t)count);
 }
 

@@ -2,7 +2,8 @@
 // Reference call stack being replaced: SURVEY.md section 3.2 (estimate_gradient! -> _value_and_gradient! -> AD of
 // estimate_repgradelbo_ad_forward).  The other parts: api_estimate.hip (one estimate), api_batch.hip (estimates at fixed
 // parameters), api_objective.hip (estimate_objective, the Gaussian-expectation gradient / Hessian), api_dist.hip (sharded
-// estimates), api_optimize.hip (update rules, the device-resident loop), api_profile.hip (per-kernel timing entries).
+// estimates), api_optimize.hip (update rules, the device-resident loop), api_profile.hip (per-kernel timing entries),
+// api_graph.hip (hipGraph capture, the context's graph cache and its replay).
 #include "api_common.h"
 
 // ---- one-thread kernels shared by the api_*.hip units (declared in api_common.h) ----
@@ -67,7 +68,7 @@ namespace mivi {
 void invalidate_graph(mivi_ctx *c) {
   c->pre_valid = false;
   ++c->target_gen;
-  if (c->graph.exec) { (void)hipGraphExecDestroy(c->graph.exec); c->graph = GraphCache{}; }
+  c->graph.drop();
 }
 }  // namespace mivi
 
@@ -188,7 +189,7 @@ mivi_status_t mivi_destroy(mivi_ctx_t *c) {
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->is_child) c->t_mean = c->t_istd = c->t_prec = c->status = mivi::DevBuf{};   // borrowed from the parent
   (void)mivi_comm_destroy(c);
-  if (c->graph.exec) (void)hipGraphExecDestroy(c->graph.exec);
+  c->graph.drop();
   DevBuf *bufs[] = {&c->t_mean, &c->t_istd, &c->t_prec, &c->lr_X_own, &c->lr_y_own, &c->lr_scratch, &c->lr_part, &c->lr_Xrm,
                     &c->eps[0], &c->eps[1], &c->epsT[0], &c->epsT[1], &c->Z, &c->W, &c->RT, &c->ell, &c->X,
                     &c->ell_part[0], &c->ell_part[1], &c->he_part[0], &c->he_part[1], &c->row_part,
@@ -228,7 +229,7 @@ mivi_status_t mivi_set_stream(mivi_ctx_t *c, void *s) {
   if (c->own_stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); c->own_stream = false; }
   c->stream = (hipStream_t)s;   // NULL = the null stream
   c->pre_valid = false;
-  if (c->graph.exec) { (void)hipGraphExecDestroy(c->graph.exec); c->graph = GraphCache{}; }
+  c->graph.drop();   // (not invalidate_graph: the children's generation stays)
   return MIVI_OK;
 }
 

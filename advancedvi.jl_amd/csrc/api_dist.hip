@@ -761,7 +761,6 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
       HIPCHK(c, hipEventCreateWithFlags(&c->ev_comm[k], hipEventDisableTiming));
     }
   }
-  GraphCache &g = c->graph;
   const int route = mivi_comm_route(c);
   // Peer-to-peer route, pipelined: the exchange is ONE persistent kernel on comm_stream for the whole batch (kernels_p2p.hip), the compute
   // chain is a single-stream graph of {partial kernels, hand-over} per estimate; the two talk through two device words.
@@ -792,33 +791,27 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
       }
     }
   }
-  const int kind = 20 + mode;
+  GraphKey key{GRAPH_SHARDED, count, params, value, grad};
+  key.route = route;
+  key.mode = mode;
   bool &capture_refused = c->dist_capture_refused;   // (a collective library that cannot be captured: do not retry on every call of THIS context)
-  if (!(g.exec && g.kind == kind && g.count == count && g.params == params && g.value == value && g.grad == grad && g.p0 == (double)route) && !capture_refused) {
+  if (!c->graph.matches(key) && !capture_refused) {
     invalidate_graph(c);
-    if (c->dist_lane4) {
-      for (int j = 0; j < kGroup - 1; ++j) {
-        c->kids[j]->kid_gen = c->target_gen;
-        HIPCHK(c, hipStreamSynchronize(c->kids[j]->stream));   // (their table uploads, before the capture)
-      }
-    }
-    hipGraph_t graph = nullptr;
-    hipStream_t saved;
-    if ((s = begin_capture(c, &saved))) return s;
-    s = dist_sequence(c, params, true, 0, count, value, grad, mode);
-    if (s == MIVI_OK && mode != 3) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count);
-    c->cur = 0;
-    c->pre_valid = false;
-    hipError_t e = end_capture(c, saved, &graph);
-    if (s == MIVI_OK && e == hipSuccess && graph) e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (s != MIVI_OK || e != hipSuccess) {
+    if (c->dist_lane4 && (s = kids_before_capture(c, kGroup))) return s;
+    bool begun = false;
+    s = graph_record(c, key, [&]() -> mivi_status_t {
+      begun = true;
+      const mivi_status_t rs = dist_sequence(c, params, true, 0, count, value, grad, mode);
+      if (rs == MIVI_OK && mode != 3) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count);
+      c->cur = 0;
+      c->pre_valid = false;
+      return rs;
+    });
+    if (s && !begun) return s;   // (the capture never started: the stream's error, not a refusal)
+    if (s) {   // refused (or the sequence failed): the same sequence is issued eagerly below, from now on
       (void)hipGetLastError();
-      g = GraphCache{};
       capture_refused = true;
       (void)hipStreamSynchronize(c->comm_stream);
-    } else {
-      g.kind = kind; g.count = count; g.params = params; g.value = value; g.grad = grad; g.p0 = (double)route;
     }
   }
   auto p2p_front = [&]() -> mivi_status_t {   // hand-over words reset, then the persistent exchange kernels (one per lane) on their own streams
@@ -844,16 +837,12 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_comm[0], 0));
     return MIVI_OK;
   };
-  if (g.exec && g.kind == kind && g.count == count && g.params == params && g.value == value && g.grad == grad && g.p0 == (double)route) {
-    if (!(c->d_idx_valid && c->d_idx_expect == idx0))
-      hipLaunchKernelGGL(k_set_u64x2, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, idx0, 0ull, 1);
+  if (c->graph.matches(key)) {
+    graph_seek(c, idx0);
     if (p2p_pipe && (s = p2p_front())) return s;
-    const hipError_t ge = hipGraphLaunch(g.exec, c->stream);
+    const mivi_status_t gs = graph_launch(c, idx0, (uint64_t)count, mode != 3);   // (mode 3, exchange only: the recording does not move the counter)
     if (p2p_pipe && (s = p2p_back())) return s;   // (also behind a failed launch: the exchange kernel's waits are bounded, the caller's stream joins it)
-    HIPCHK(c, ge);
-    c->d_idx_valid = mode != 3;
-    c->d_idx_expect = idx0 + (uint64_t)count;
-    return MIVI_OK;
+    return gs;
   }
   // eager: the same sequence with by-value indices
   c->pre_valid = false;

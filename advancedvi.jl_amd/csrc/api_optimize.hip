@@ -76,12 +76,6 @@ static mivi_status_t deliver_elbo(mivi_ctx *c, const double *rec, int n_steps, v
   return MIVI_OK;
 }
 
-static bool same_loop(const mivi_loop_t &a, const mivi_loop_t &b) {   // everything baked into a captured loop
-  return a.rule == b.rule && a.op == b.op && a.averager == b.averager && a.n_steps == b.n_steps && a.eta == b.eta &&
-         a.beta1 == b.beta1 && a.beta2 == b.beta2 && a.adam_eps == b.adam_eps && a.clip_epsilon == b.clip_epsilon &&
-         a.avg_eta == b.avg_eta && a.opt_state_dev == b.opt_state_dev && a.avg_params_dev == b.avg_params_dev;
-}
-
 // One call's steps on the best route.  allow_exchange = false: the launch-free loops whose workgroups exchange partials grid-wide every step are
 // skipped (their graph-of-launches equivalents run instead); *used_exchange: one of them was launched.
 static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_loop_t *lp, bool allow_exchange, bool *used_exchange) {
@@ -207,12 +201,9 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
       return read_status(c);
     }
   }
-  GraphCache &g = c->graph;
-  if (!(g.exec && g.kind == 9 && g.params == params && g.value == (void *)vbuf && same_loop(g.loop, l))) {
-    invalidate_graph(c);
-    hipGraph_t graph = nullptr;
-    hipStream_t saved;
-    if ((s = begin_capture(c, &saved))) return s;
+  // every other configuration: the steps as a graph of launches, recorded once per loop configuration
+  auto record_steps = [&]() -> mivi_status_t {
+    mivi_status_t s = MIVI_OK;
     Chain chn;
     chn.on = true;
     const long long *t_ptr = (const long long *)c->d_idx.p + 1;   // iterations done before this call
@@ -262,18 +253,18 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
     }
     if (s == MIVI_OK) flush_chain(c, params, &chn);
     c->cur = 0;
-    hipError_t e = end_capture(c, saved, &graph);
-    if (s) { if (graph) (void)hipGraphDestroy(graph); return s; }
-    HIPCHK(c, e);
-    HIPCHK(c, hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    g.kind = 9; g.count = n_steps; g.params = params; g.value = vbuf;
-    g.loop = l;
+    return s;
+  };
+  GraphKey key{GRAPH_LOOP, n_steps, params, vbuf};
+  key.loop = l;
+  if (!c->graph.matches(key)) {
+    invalidate_graph(c);
+    if ((s = graph_record(c, key, record_steps))) return s;
   }
   c->d_idx_valid = false;
   hipLaunchKernelGGL(k_set_u64x2, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, l.estimate_idx0, (uint64_t)l.t0, 2);
   HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));   // a stale flag of earlier estimates (this context's word or a child context's: read_status folds them all in) is not this run's
-  HIPCHK(c, hipGraphLaunch(g.exec, c->stream));
+  HIPCHK(c, hipGraphLaunch(c->graph.exec, c->stream));
   if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
   return read_status(c);
 }

@@ -31,7 +31,7 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
     if (!(lds && lds_use_prod32(c, M)) || c->is_child || c->target != TGT_DIAG_GAUSS) return fail(c, MIVI_ERR_UNSUPPORTED, "which = 10 / 11: full-rank second-generation kernels, diagonal-Gaussian target");
     if ((s = mivi_estimate_gradient_n(c, params, 1, 8, o, o + 16))) return s;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!(c->graph.exec && c->graph.kind == 3)) return fail(c, MIVI_ERR_UNSUPPORTED, "which = 10 / 11: this configuration does not take the lane-batched route");
+    if (!(c->graph.exec && c->graph.key.kind == GRAPH_LANE_BRANCHES)) return fail(c, MIVI_ERR_UNSUPPORTED, "which = 10 / 11: this configuration does not take the lane-batched route");
     psink = lane_sinks_alloc(4);
     for (int l = 0; l < 4 && s == MIVI_OK; ++l) {
       mivi_ctx *k = l ? c->kids[l - 1] : c;
@@ -125,16 +125,13 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
   const bool graphed = which != 0 && which != 5 && !c->dbg;
   if (graphed) {
     invalidate_graph(c);
-    hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    hipStream_t saved;
-    if ((s = begin_capture(c, &saved))) return s;
-    for (int r = 0; r < reps && s == MIVI_OK; ++r) s = one(r);
-    hipError_t e = end_capture(c, saved, &graph);
-    if (s) { if (graph) (void)hipGraphDestroy(graph); return s; }
-    HIPCHK(c, e);
-    HIPCHK(c, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
+    s = capture_graph(c, &exec, [&]() -> mivi_status_t {
+      mivi_status_t rs = MIVI_OK;
+      for (int r = 0; r < reps && rs == MIVI_OK; ++r) rs = one(r);
+      return rs;
+    });
+    if (s) return s;
     HIPCHK(c, hipGraphLaunch(exec, c->stream));   // warm replay
     HIPCHK(c, hipEventRecord(e0, c->stream));
     HIPCHK(c, hipGraphLaunch(exec, c->stream));

@@ -240,16 +240,30 @@ struct FbStep {
   void *parts; long long part_stride;     // sharded batches: the VJP leaves lane l's UNNORMALISED partial vector at parts + l part_stride instead of a gradient
 };
 
-struct GraphCache {
-  hipGraphExec_t exec = nullptr;
+// What a cached hipGraphExec was recorded for (api_graph.hip): a call replays it only if every field matches.
+enum GraphKind {
+  GRAPH_NONE = 0,
+  GRAPH_CHAIN,           // `count` chained estimates on one stream
+  GRAPH_FORKED_CHAINS,   // one chain per context (`lanes` of them) behind a fork event
+  GRAPH_LANE_BRANCHES,   // branches of `per_branch` lane-batched contexts, `lanes` contexts in all
+  GRAPH_LOOP,            // the optimisation loop as a graph of launches (`loop`)
+  GRAPH_SHARDED,         // a sharded batch (`mode`, `route`)
+};
+struct GraphKey {
+  GraphKind kind = GRAPH_NONE;
   int count = 0;
   const void *params = nullptr;
   void *value = nullptr;
   void *grad = nullptr;
-  int kind = 0;
-  double p0 = 0, p1 = 0;
-  void *aux0 = nullptr, *aux1 = nullptr;
-  mivi_loop_t loop{};   // kind 9: the configuration the captured loop was built for
+  int lanes = 0, per_branch = 0;   // GRAPH_FORKED_CHAINS / GRAPH_LANE_BRANCHES
+  int route = 0, mode = 0;         // GRAPH_SHARDED: mivi_comm_route, the sequence (api_dist.hip dist_sequence)
+  mivi_loop_t loop{};              // GRAPH_LOOP: the configuration the captured loop was built for
+};
+struct GraphCache {
+  hipGraphExec_t exec = nullptr;
+  GraphKey key;
+  bool matches(const GraphKey &k) const;
+  void drop();   // destroys the cached hipGraphExec, if any, and empties the slot
 };
 
 }  // namespace mivi

@@ -160,6 +160,33 @@ def test_product_never_imports_the_oracle():
                 assert "libmivi_oracle" not in txt and "mivi_oracle.c" not in txt, f
 
 
+def test_graph_capture_has_one_owner():
+    """Stream capture, instantiation and the intermediate hipGraph_t live in ONE translation unit (csrc/api_graph.hip); the routes name
+    neither them nor the capture stream, and the cache key is typed (no integer kinds, nothing packed into a double)."""
+    csrc = os.path.join(ROOT, "advancedvi.jl_amd", "csrc")
+    hip = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+    owners = {tok: [f for f, txt in hip.items() if tok in txt]
+              for tok in ("hipStreamBeginCapture", "hipStreamEndCapture", "hipGraphInstantiate", "hipGraphDestroy(")}
+    assert all(len(fs) == 1 for fs in owners.values()), owners
+    assert len({fs[0] for fs in owners.values()}) == 1, owners
+    owner = owners["hipStreamBeginCapture"][0]
+    for f, txt in hip.items():
+        lines = [ln for ln in txt.splitlines() if "cap_stream" in ln]
+        if f == owner:
+            assert lines, f
+        elif f == "api_core.hip":   # mivi_destroy releases it
+            assert len(lines) == 1 and "hipStreamDestroy(c->cap_stream)" in lines[0], lines
+        else:
+            assert not lines, (f, lines)
+    abi = [(f, txt) for f, txt in hip.items() if f.startswith("api_")]   # (the kernels have `kind`s of their own)
+    for f, txt in abi + [(h, open(os.path.join(csrc, h)).read()) for h in ("api_common.h", "mivi_internal.h")]:
+        assert not re.search(r"\bkind\s*(==|!=|=)\s*\d", txt), f
+        assert not re.search(r"\bbegin_capture\b|\bend_capture\b", txt), f
+    internal = open(os.path.join(csrc, "mivi_internal.h")).read()
+    cache = re.search(r"struct GraphKey \{.*?\n\};.*?struct GraphCache \{.*?\n\};", internal, flags=re.S).group(0)
+    assert not re.search(r"\b(p0|p1|aux0|aux1)\b", cache), cache
+
+
 def test_host_philox_matches_oracle_bit_exact(lib):
     rng = np.random.default_rng(0)
     for _ in range(50):
