@@ -7,13 +7,13 @@ from ._lib import LIB_PATH, MiviError, load as load_library
 from .families import MvLocationScale, MeanFieldGaussian, FullRankGaussian, destructure, MEANFIELD, FULLRANK
 from .problems import (LogDensityOrder, DiagNormalProblem, DenseNormalProblem, LogRegProblem, FunnelProblem,
                        dimension, capabilities)
-from .objectives import (RepGradELBO, RepGradELBOState, ClosedFormEntropy, ClosedFormEntropyZeroGradient,
+from .objectives import (RepGradELBO, RepGradELBOState, ScoreGradELBO, ScoreGradELBOState, ClosedFormEntropy, ClosedFormEntropyZeroGradient,
                          MonteCarloEntropy, StickingTheLandingEntropy, StickingTheLandingEntropyZeroGradient,
                          AutoMIVI, PhiloxRNG, DiffResult, set_objective_state_problem, rand,
                          gaussian_expectation_gradient_and_hessian_)
 from . import objectives as _objectives
 from . import optimize as _optimize
-from .optimize import (KLMinRepGradDescent, KLMinRepGradProxDescent, ADVI, ClipScale, IdentityOperator,
+from .optimize import (KLMinRepGradDescent, KLMinRepGradProxDescent, ADVI, KLMinScoreGradDescent, BBVI, ClipScale, IdentityOperator,
                        ProximalLocationScaleEntropy, Descent, Adam, DoG, DoWG, COCOB, NoAveraging,
                        PolynomialAveraging, optimize, step, output)
 from .context import MiviContext
@@ -28,7 +28,7 @@ from . import distributed
 def estimate_objective(*args, **kwargs):
     """Dispatches like the reference: (rng, alg|obj, q, prob) or (alg|obj, q, prob)."""
     head = args[1] if isinstance(args[0], PhiloxRNG) else args[0]
-    if isinstance(head, KLMinRepGradDescent):
+    if isinstance(head, _optimize.PARAM_SPACE_SGD):
         return _optimize.estimate_objective(*args, **kwargs)
     if isinstance(head, SubsampledObjective):
         return _subsampling.estimate_objective(*args, **kwargs)
@@ -36,7 +36,7 @@ def estimate_objective(*args, **kwargs):
 
 
 def estimate_gradient_(rng, obj, *args, **kwargs):
-    """`estimate_gradient!(rng, obj, adtype, out, state, params, restructure)` for RepGradELBO or SubsampledObjective."""
+    """`estimate_gradient!(rng, obj, adtype, out, state, params, restructure)` for RepGradELBO, ScoreGradELBO or SubsampledObjective."""
     if isinstance(obj, SubsampledObjective):
         return _subsampling.estimate_gradient_(rng, obj, *args, **kwargs)
     return _objectives.estimate_gradient_(rng, obj, *args, **kwargs)
@@ -44,7 +44,7 @@ def estimate_gradient_(rng, obj, *args, **kwargs):
 
 def init(*args, **kwargs):
     """init(rng, alg, q_init, prob)  or  init(rng, obj, adtype, q, prob, params, restructure)."""
-    if isinstance(args[1], KLMinRepGradDescent):
+    if isinstance(args[1], _optimize.PARAM_SPACE_SGD):
         return _optimize.init(*args, **kwargs)
     if isinstance(args[1], SubsampledObjective):
         return _subsampling.init(*args, **kwargs)

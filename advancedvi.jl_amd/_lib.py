@@ -44,6 +44,9 @@ SIGNATURES = {
     "mivi_set_target_logreg": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int32]),
     "mivi_set_target_funnel": (C.c_int32, [C.c_void_p, C.c_double]),
     "mivi_set_target_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_AND_GRADIENT_FN, LOGDENSITY_FN, C.c_void_p]),
+    "mivi_set_target_value_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_FN, C.c_void_p]),
+    "mivi_estimate_score_gradient": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mivi_estimate_score_gradient_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mivi_sample": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "mivi_estimate_gradient": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "mivi_estimate_gradient_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -92,12 +92,14 @@ class MiviContext:
         return C.c_void_p(t.data_ptr())
 
     # -- targets ----------------------------------------------------------------------------------
-    def set_problem(self, prob):
+    def set_problem(self, prob, values_only=False):
+        """values_only: the caller evaluates nothing but `logdensity` (ScoreGradELBO) -- a generic problem without a gradient is then
+        registered through mivi_set_target_value_callback instead of a gradient callback that raises."""
         if P.dimension(prob) != self.d:
             raise ValueError("dimension(prob) does not match the variational family")
         dt = self.np_dtype
         if isinstance(prob, P.TransformedProblem):   # inner target first, then the Stacked bijector around it
-            self.set_problem(prob.prob)
+            self.set_problem(prob.prob, values_only=values_only)
             self.set_bijector(prob.bijector)
             self.problem = prob
             return
@@ -138,7 +140,7 @@ class MiviContext:
         elif isinstance(prob, P.FunnelConstrainedProblem):
             self._chk(self.lib.mivi_set_target_funnel_constrained(self.h, prob.sigma_v))
         else:
-            self._set_callback(prob)
+            self._set_callback(prob, values_only=values_only)
         self.problem = prob
 
     def set_bijector(self, bij):
@@ -150,7 +152,7 @@ class MiviContext:
         kinds = np.ascontiguousarray([P.StackedBijector.KINDS[k] for _, _, k in bij.blocks], dtype=np.int32)
         self._chk(self.lib.mivi_set_bijector_stacked(self.h, len(bij.blocks), rng.ctypes.data, kinds.ctypes.data))
 
-    def _set_callback(self, prob):
+    def _set_callback(self, prob, values_only=False):
         has_grad = hasattr(prob, "logdensity_and_gradient") or hasattr(prob, "logdensity_and_gradient_batch")
         if not has_grad and not hasattr(prob, "logdensity"):
             raise TypeError("generic targets must implement logdensity (LogDensityOrder 0: values only -- estimate_objective) or "
@@ -218,6 +220,9 @@ class MiviContext:
                else C.cast(None, _lib.LOGDENSITY_GRADIENT_AND_HESSIAN_FN))
         self._keep += [cfg, cfv, cfh]
         self._cb_error = None
+        if values_only and hasattr(prob, "logdensity") and (not has_grad or P.capabilities(prob) < P.LogDensityOrder(1)):
+            self._chk(self.lib.mivi_set_target_value_callback(self.h, cfv, None))   # order 0: no gradient function behind the ABI at all
+            return
         self._chk(self.lib.mivi_set_target_callback(self.h, cfg, cfv, None))
         self._chk(self.lib.mivi_set_target_hess_callback(self.h, cfh, None))
 
@@ -244,6 +249,15 @@ class MiviContext:
         grad = self.empty(self.params_len) if grad is None else grad
         self._raise_cb(self.lib.mivi_estimate_gradient(self.h, self._p(p), idx, self._p(value), self._p(grad)))
         return value, grad
+
+    def estimate_score_gradient(self, params, idx, value=None, elbo=None, grad=None):
+        """mivi_estimate_score_gradient: (value = the VarGrad objective, elbo = mean(log pi - log q), gradient) of estimate `idx`."""
+        p = self.to_device(params)
+        value = self.empty(1) if value is None else value
+        elbo = self.empty(1) if elbo is None else elbo
+        grad = self.empty(self.params_len) if grad is None else grad
+        self._raise_cb(self.lib.mivi_estimate_score_gradient(self.h, self._p(p), idx, self._p(value), self._p(elbo), self._p(grad)))
+        return value, elbo, grad
 
     def estimate_gradient_n(self, params, idx0, count, value, grad):
         self._chk(self.lib.mivi_estimate_gradient_n(self.h, self._p(params), idx0, int(count), self._p(value), self._p(grad)))

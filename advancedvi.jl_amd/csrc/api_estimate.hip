@@ -5,7 +5,12 @@
 // ---------------------------------------------------------------------------------------------
 // estimate driver
 // ---------------------------------------------------------------------------------------------
-static mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
+// a target registered with mivi_set_target_value_callback (LogDensityOrder 0) asked for its gradient
+static const char *const kValueOnlyTarget =
+    "the target has only a value callback (mivi_set_target_value_callback): this entry needs the target's gradient -- use "
+    "mivi_estimate_score_gradient / mivi_estimate_objective, or register mivi_set_target_callback";
+
+mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
   switch (c->target) {
     case TGT_DIAG_GAUSS:
     case TGT_FUNNEL:
@@ -15,6 +20,7 @@ static mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
       if (!launch_logreg_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "logistic regression: scratch allocation failed");
       return MIVI_OK;
     case TGT_CALLBACK: {
+      if (want_grad && !c->cb_grad) return fail(c, MIVI_ERR_UNSUPPORTED, kValueOnlyTarget);
       const size_t es = c->esize, d = c->cfg.d;
       c->h_Z.resize(d * M * es);
       c->h_G.resize(d * M * es);
@@ -22,7 +28,7 @@ static mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
       HIPCHK(c, hipMemcpyAsync(c->h_Z.data(), c->Z.p, d * M * es, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
       int rc;
-      if (!want_grad && c->cb_value)
+      if ((!want_grad && c->cb_value) || !c->cb_grad)
         rc = c->cb_value(c->cb_user, c->h_Z.data(), (int)d, M, c->h_ell.data());
       else
         rc = c->cb_grad(c->cb_user, c->h_Z.data(), (int)d, M, c->h_ell.data(), c->h_G.data());
@@ -174,6 +180,7 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
                                   OutArgs out, Chain *ch, const FusedUpdate *upd,
                                   bool stop_after_target) {
   if (c->target == TGT_NONE) return fail(c, MIVI_ERR_NO_TARGET, "no target set");
+  if (want_grad && c->target == TGT_CALLBACK && !c->cb_grad) return fail(c, MIVI_ERR_UNSUPPORTED, kValueOnlyTarget);
   mivi_status_t s = ensure_work(c, M);
   if (s) return s;
   out.M_local = M;

@@ -367,6 +367,8 @@ struct mivi_ctx {
   mivi::DevBuf row_part, status, d_idx, acc, tmp_params, tmp_out;
   mivi::DevBuf obj_vals;   // mivi_estimate_objective on the batch engine: the lanes' values
   mivi::DevBuf stein_A, stein_g;   // Stein estimator: eps G^T accumulator (dP x dP, T) and the f64 column sums of G
+  mivi::DevBuf sg_S, sg_d;         // score-gradient estimator (kernels_score.hip): -E diag(f - mean f) laid out like eps (full-rank); f64 [|eps_m|^2; dense ell_m; f_m - mean f] (3 x cap_M)
+  int sg_cap = 0;                  // samples sg_d is sized for
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
   const uint64_t *idx_src = nullptr;   // mivi_set_index_source
@@ -539,6 +541,13 @@ int logreg_kernel_bits(const mivi_ctx *c, int M);         // mivi_logreg_kernels
 bool logreg_uses_mfma(const mivi_ctx *c, int M);          // the matrix-core route (needs Z^T staged in RT)
 bool logreg_reserve(mivi_ctx *c, int M);                        // size the scratch ahead of a graph capture
 bool logreg_prepare_f32(mivi_ctx *c);   // row-major padded copy of X for the MFMA route (false: allocation failed)
+
+// kernels_score.hip: the score-gradient (VarGrad) estimator's own kernels (api_score.hip drives them)
+void launch_sg_dense_ell(mivi_ctx *c, int M);                          // sg_d[cap + m] = 0.5 r_m' g_m from Z and W = G = -P R (dense-Gaussian target)
+void launch_sg_norms(mivi_ctx *c, const RngArgs &rng, int M);         // sg_d[m] = |eps_m|^2 (full-rank: from eps[0]; mean-field: redrawn from Philox)
+void launch_sg_stats(mivi_ctx *c, const void *params, int M, bool ell_f64, void *value, void *elbo);   // f, mean f, weights, value, elbo, status flags
+void launch_sg_scale(mivi_ctx *c, int M);                              // full-rank: sg_S = -eps diag(f - mean f) (pads zero), W = 0
+void launch_sg_mf_grad(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *grad);   // mean-field: [d/dmu; d/dsigma]
 
 // kernels_p2p.hip: phases bit 0 push, 1 reduce + finalise, 2 unpack (7 = the whole exchange in one launch)
 void launch_p2p_handover4(mivi_ctx *c, unsigned *ready, unsigned ready_val, const unsigned *const *freed, const unsigned *freed_min, int n);

@@ -12,7 +12,7 @@ module MIVI
 
 using AdvancedVI, ADTypes, AbstractPPL, DiffResults, LogDensityProblems, Optimisers, Random, LinearAlgebra
 using Distributions: Normal
-using AdvancedVI: MvLocationScale, RepGradELBO, KLMinRepGradDescent, ClosedFormEntropy, ClosedFormEntropyZeroGradient,
+using AdvancedVI: MvLocationScale, RepGradELBO, ScoreGradELBO, KLMinRepGradDescent, ClosedFormEntropy, ClosedFormEntropyZeroGradient,
                   MonteCarloEntropy, StickingTheLandingEntropy, StickingTheLandingEntropyZeroGradient
 
 const libmivi = get(ENV, "LIBMIVI", "libmivi.so")
@@ -154,6 +154,84 @@ function AdvancedVI.estimate_objective(rng::Random.AbstractRNG, obj::RepGradELBO
     value = Ref{T}(zero(T))
     check(st.ctx, ccall((:mivi_estimate_objective_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, UInt64, Int32, Int32, Ref{T}),
                         st.ctx, params, UInt64(0), n_samples, entropy_code(obj.entropy), value))
+    return value[]
+end
+
+# ---- ScoreGradELBO (src/algorithms/scoregradelbo.jl; KLMinScoreGradDescent = BBVI, src/algorithms/constructors.jl:199-233) ----------
+# The score-gradient estimator evaluates nothing but `logdensity`: no capability dispatch, no AD of the target, no @info.  An order-0
+# problem registers the value-only callback; an order >= 1 problem keeps its gradient callback (only the values it returns are used).
+function value_callback(user::Ptr{Cvoid}, Zp::Ptr{Cvoid}, d::Int32, M::Int32, ellp::Ptr{Cvoid})::Int32
+    st = unsafe_pointer_to_objref(user)::MIVIState
+    T = st.T
+    Z = unsafe_wrap(Array, Ptr{T}(Zp), (Int(d), Int(M)))
+    ell = unsafe_wrap(Array, Ptr{T}(ellp), (Int(M),))
+    try
+        for m in 1:M
+            ell[m] = LogDensityProblems.logdensity(st.problem, view(Z, :, m))
+        end
+        return Int32(0)
+    catch
+        return Int32(1)
+    end
+end
+
+function AdvancedVI.init(rng::Random.AbstractRNG, obj::ScoreGradELBO, ad::AutoMIVI, q::MvLocationScale, prob, params, restructure)
+    T = eltype(params)
+    cfg = Ref(MiviConfig(dtype_code(T), family_code(q), length(q), obj.n_samples, entropy_code(MonteCarloEntropy()),
+                         ad.device, rand(rng, UInt64), 0, 0, C_NULL, 1, 0))
+    ctx = Ref{Ptr{Cvoid}}(C_NULL)
+    status = ccall((:mivi_create, libmivi), Int32, (Ref{MiviConfig}, Ref{Ptr{Cvoid}}), cfg, ctx)
+    status == 0 || error("mivi_create failed with status $status (no HIP device?)")
+    st = MIVIState(prob, T, ctx[], UInt64(0), nothing, false, nothing, false, nothing)
+    finalizer(s -> ccall((:mivi_destroy, libmivi), Int32, (Ptr{Cvoid},), s.ctx), st)
+    if prob isa NativeTarget
+        set_native_target!(st, prob)
+        return st
+    end
+    vcb = @cfunction(value_callback, Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}))
+    if LogDensityProblems.capabilities(typeof(prob)) < LogDensityProblems.LogDensityOrder{1}()
+        st.cb = vcb
+        check(st.ctx, ccall((:mivi_set_target_value_callback, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Any), st.ctx, vcb, st))
+    else
+        gcb = @cfunction(target_callback, Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}))
+        st.cb = (gcb, vcb)
+        check(st.ctx, ccall((:mivi_set_target_callback, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Any), st.ctx, gcb, vcb, st))
+    end
+    return st
+end
+
+# scoregradelbo.jl:96-117: `out` receives the VarGrad objective and its gradient, the statistic is the ELBO estimate itself
+function AdvancedVI.estimate_gradient!(rng::Random.AbstractRNG, obj::ScoreGradELBO, ::AutoMIVI,
+                                       out::DiffResults.MutableDiffResult, state::MIVIState, params, restructure)
+    T = eltype(params)
+    value = Ref{T}(zero(T))
+    elbo = Ref{T}(zero(T))
+    grad = DiffResults.gradient(out)
+    status = ccall((:mivi_estimate_score_gradient_host, libmivi), Int32,
+                   (Ptr{Cvoid}, Ptr{T}, UInt64, Ref{T}, Ref{T}, Ptr{T}), state.ctx, params, state.estimate_idx, value, elbo, grad)
+    state.estimate_idx += 1
+    status == 2 || check(state.ctx, status)   # (non-finite: `step` raises the reference's own ErrorException, common.jl:83-89)
+    DiffResults.value!(out, value[])
+    return out, state, (elbo = elbo[],)
+end
+
+# the same estimate with device-resident buffers (asynchronous for native targets): value_dev / elbo_dev T[1], grad_dev T[params_len]
+function estimate_score_gradient_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, value_dev::Ptr{Cvoid}, elbo_dev::Ptr{Cvoid}, grad_dev::Ptr{Cvoid})
+    check(state.ctx, ccall((:mivi_estimate_score_gradient, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                           state.ctx, params_dev, state.estimate_idx, value_dev, elbo_dev, grad_dev))
+    state.estimate_idx += 1
+    return state
+end
+
+# scoregradelbo.jl:58-65: -mean(log pi - log q), the value route with the Monte-Carlo entropy
+function AdvancedVI.estimate_objective(rng::Random.AbstractRNG, obj::ScoreGradELBO, q::MvLocationScale, prob, ad::AutoMIVI;
+                                       n_samples::Int = obj.n_samples)
+    params, re = Optimisers.destructure(q)
+    st = AdvancedVI.init(rng, ScoreGradELBO(min(n_samples, 16384)), ad, q, prob, params, re)
+    T = eltype(params)
+    value = Ref{T}(zero(T))
+    check(st.ctx, ccall((:mivi_estimate_objective_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, UInt64, Int32, Int32, Ref{T}),
+                        st.ctx, params, UInt64(0), n_samples, entropy_code(MonteCarloEntropy()), value))
     return value[]
 end
 
@@ -522,5 +600,5 @@ end
 # ProximalLocationScaleEntropy on the host arrays works unchanged (src/optimization/proximal_location_scale_entropy.jl);
 # the device-resident variant for a parameter vector that lives in HBM is mivi_prox_scale_entropy.
 
-export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!
+export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!
 end # module

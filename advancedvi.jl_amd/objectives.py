@@ -127,6 +127,27 @@ class RepGradELBOState:
         self.obj_ad_prep = ctx
 
 
+class ScoreGradELBO:
+    """ScoreGradELBO(n_samples): scoregradelbo.jl:15-17 -- the score-function gradient of the ELBO with the VarGrad (leave-one-out) control
+    variate.  It evaluates the target's `logdensity` only, so it is the objective for targets without a gradient."""
+
+    def __init__(self, n_samples: int):
+        if not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
+            raise ValueError("n_samples must be a positive Int")
+        self.n_samples = int(n_samples)
+
+    def __repr__(self):  # Base.show, scoregradelbo.jl:52-56
+        return f"ScoreGradELBO(n_samples={self.n_samples})"
+
+
+class ScoreGradELBOState:
+    """ScoreGradELBOState(problem, obj_ad_prep): scoregradelbo.jl:19-22; `obj_ad_prep` is the libmivi context."""
+
+    def __init__(self, problem, ctx: MiviContext):
+        self.problem = problem
+        self.obj_ad_prep = ctx
+
+
 def _order0(prob) -> bool:
     """capability < LogDensityOrder{1}() (repgradelbo.jl:50-51), looking through a TransformedProblem like README.md:115-119."""
     inner = prob.prob if isinstance(prob, P.TransformedProblem) else prob
@@ -166,21 +187,41 @@ def _make_ctx(rng, obj, adtype, q, prob, n_mc=None, entropy=None):
     return ctx
 
 
-def init(rng, obj: RepGradELBO, adtype, q, prob, params, restructure) -> RepGradELBOState:
+def _make_score_ctx(rng, obj, adtype, q, prob):
+    if not isinstance(q, MvLocationScale):
+        raise TypeError("libmivi implements the ScoreGradELBO path for MvLocationScale families only")
+    ctx = MiviContext(q.eltype, q.family, len(q), obj.n_samples, MonteCarloEntropy.code, rng.seed, device=getattr(adtype, "device", 0))
+    ctx.set_problem(prob, values_only=True)
+    return ctx
+
+
+def init(rng, obj, adtype, q, prob, params, restructure):
     """AdvancedVI.init(rng, obj::RepGradELBO, adtype, q, prob, params, restructure): repgradelbo.jl:41-70.
     The capability dispatch of :50-62: order >= 1 problems are used through `logdensity_and_gradient`; an order-0 problem (only
     `logdensity`: the README model, README.md:64-66, and the benchmark target, bench/benchmarks.jl:39-41) is differentiated on the host
     by `adtype.target_ad` with the reference's @info -- see `_ad_problem`."""
     if not isinstance(adtype, AutoMIVI):
         raise TypeError("adtype must be AutoMIVI() for the libmivi path")
+    if isinstance(obj, ScoreGradELBO):
+        # scoregradelbo.jl:34-50: no capability dispatch, no ADgradient wrapping, no @info -- only `logdensity` is ever evaluated, so an
+        # order-0 problem is used as it is (the value-only callback)
+        st = ScoreGradELBOState(prob, _make_score_ctx(rng, obj, adtype, q, prob))
+        st.adtype = adtype
+        return st
     ad_prob = _ad_problem(adtype, prob)
     st = RepGradELBOState(ad_prob, _make_ctx(rng, obj, adtype, q, ad_prob))
     st.adtype = adtype
     return st
 
 
-def set_objective_state_problem(state: RepGradELBOState, prob) -> RepGradELBOState:
-    """repgradelbo.jl:31-39 (the same capability dispatch as `init`, without the @info)."""
+def set_objective_state_problem(state, prob):
+    """repgradelbo.jl:31-39 (the same capability dispatch as `init`, without the @info); scoregradelbo.jl:24-32 for a ScoreGradELBOState
+    (the problem is used as it is)."""
+    if isinstance(state, ScoreGradELBOState):
+        state.obj_ad_prep.set_problem(prob, values_only=True)
+        st = ScoreGradELBOState(prob, state.obj_ad_prep)
+        st.adtype = getattr(state, "adtype", None)
+        return st
     adtype = getattr(state, "adtype", None)
     ad_prob = _ad_problem(adtype, prob, announce=False) if adtype is not None else prob
     state.obj_ad_prep.set_problem(ad_prob)
@@ -189,22 +230,32 @@ def set_objective_state_problem(state: RepGradELBOState, prob) -> RepGradELBOSta
     return st
 
 
-def estimate_gradient_(rng, obj: RepGradELBO, adtype, out: DiffResult, state: RepGradELBOState, params, restructure,
+def estimate_gradient_(rng, obj, adtype, out: DiffResult, state, params, restructure,
                        *args):
     """`estimate_gradient!`: repgradelbo.jl:151-177.  Writes -elbo and its gradient into `out`
     (both device resident), returns (out, state, info) with info = {"elbo": -value}.  `info["elbo"]`
-    is a 0-dim device tensor so the call stays asynchronous; `float()` it to synchronise."""
+    is a 0-dim device tensor so the call stays asynchronous; `float()` it to synchronise.
+    obj::ScoreGradELBO (scoregradelbo.jl:96-117): `out.value` is the VarGrad objective, `info["elbo"]` the separate scalar
+    mean(log pi - log q) over the same samples."""
     ctx = state.obj_ad_prep
+    if isinstance(obj, ScoreGradELBO):
+        elbo = ctx.empty(1)
+        ctx.estimate_score_gradient(params, rng.next_index(), out.value_t, elbo, out.gradient_t)
+        return out, state, {"elbo": elbo[0]}
     ctx.estimate_gradient(params, rng.next_index(), out.value_t, out.gradient_t)
     info = {"elbo": -out.value_t[0]}
     return out, state, info
 
 
-def estimate_objective(rng, obj: RepGradELBO, q, prob, n_samples: int = None, adtype=None, _ctx_cache={}):
+def estimate_objective(rng, obj, q, prob=None, n_samples: int = None, adtype=None, _ctx_cache={}):
     """estimate_objective(rng, obj::RepGradELBO, q, prob; n_samples): repgradelbo.jl:112-118 (q_stop := q).
     Returns the NEGATIVE elbo as a Python float."""
-    if isinstance(rng, RepGradELBO):  # estimate_objective(obj, q, prob): default rng, repgradelbo.jl:120-122
+    if isinstance(rng, (RepGradELBO, ScoreGradELBO)):  # estimate_objective(obj, q, prob): default rng, repgradelbo.jl:120-122
         rng, obj, q, prob = default_rng(), rng, obj, q
+    if isinstance(obj, ScoreGradELBO):
+        # scoregradelbo.jl:58-65: -mean(log pi - log q) -- the value route with the Monte-Carlo entropy (values of the target only)
+        n = int(n_samples) if n_samples is not None else obj.n_samples
+        return estimate_objective(rng, RepGradELBO(n, entropy=MonteCarloEntropy()), q, prob, adtype=adtype)
     n = int(n_samples) if n_samples is not None else obj.n_samples
     ctx = _make_ctx(rng, obj, adtype or AutoMIVI(), q, prob, n_mc=min(n, 16384))
     try:

@@ -185,6 +185,27 @@ class KLMinRepGradProxDescent(KLMinRepGradDescent):
         self.operator = ProximalLocationScaleEntropy()
 
 
+class KLMinScoreGradDescent:
+    """KLMinScoreGradDescent(adtype; optimizer, n_samples, averager, operator): constructors.jl:199-233 -- stochastic gradient descent
+    on the score-gradient ELBO (ScoreGradELBO), also known as black-box variational inference.  Needs only `logdensity` of the target."""
+
+    def __init__(self, adtype, optimizer=None, n_samples: int = 1, averager=None, operator=None, **kwargs):
+        if "subsampling" in kwargs:   # constructors.jl:222-226 composes with SubsampledObjective
+            raise TypeError("KLMinScoreGradDescent(subsampling=...) is not implemented: ScoreGradELBO does not compose with "
+                            "SubsampledObjective in this library")
+        if kwargs:
+            raise TypeError(f"KLMinScoreGradDescent() got an unexpected keyword argument {next(iter(kwargs))!r}")
+        self.objective = O.ScoreGradELBO(n_samples)
+        self.adtype = adtype
+        self.optimizer = optimizer if optimizer is not None else DoWG()
+        self.averager = averager if averager is not None else PolynomialAveraging()
+        self.operator = operator if operator is not None else IdentityOperator()
+
+
+BBVI = KLMinScoreGradDescent
+PARAM_SPACE_SGD = (KLMinRepGradDescent, KLMinScoreGradDescent)   # the ParamSpaceSGD algorithms: what init / step / optimize accept
+
+
 def _obj_init(rng, obj, *a):
     return (S.init if isinstance(obj, S.SubsampledObjective) else O.init)(rng, obj, *a)
 
@@ -197,11 +218,13 @@ def _ctx_of(obj_st):
     return obj_st.obj_st.obj_ad_prep if isinstance(obj_st, S.SubsampledObjectiveState) else obj_st.obj_ad_prep
 
 
-def estimate_objective(rng, alg, q, prob, n_samples=None, entropy=None):
+def estimate_objective(rng, alg, q, prob=None, n_samples=None, entropy=None):
     """estimate_objective([rng,] alg, q, prob; n_samples, entropy=MonteCarloEntropy()): common.jl:29-38."""
-    if isinstance(rng, KLMinRepGradDescent):
+    if isinstance(rng, PARAM_SPACE_SGD):
         rng, alg, q, prob = O.default_rng(), rng, alg, q
     n = n_samples if n_samples is not None else alg.objective.n_samples
+    if isinstance(alg.objective, O.ScoreGradELBO):   # scoregradelbo.jl:58-65 (its own estimator: no entropy choice)
+        return O.estimate_objective(rng, alg.objective, q, prob, n_samples=n, adtype=alg.adtype)
     ent = entropy if entropy is not None else O.MonteCarloEntropy()
     if isinstance(alg.objective, S.SubsampledObjective):
         sub = S.SubsampledObjective(O.RepGradELBO(n, entropy=ent), alg.objective.subsampling)
@@ -209,7 +232,7 @@ def estimate_objective(rng, alg, q, prob, n_samples=None, entropy=None):
     return O.estimate_objective(rng, O.RepGradELBO(n, entropy=ent), q, prob, adtype=alg.adtype)
 
 
-def init(rng, alg: KLMinRepGradDescent, q_init, prob):
+def init(rng, alg, q_init, prob):
     """init(rng, alg::ParamSpaceSGD, q_init, prob): common.jl:40-61."""
     if isinstance(q_init, MvLocationScale) and isinstance(alg.operator, IdentityOperator):
         warnings.warn(
@@ -251,7 +274,10 @@ def step(rng, alg, state, callback, *objargs):
     state["avg_st"] = alg.averager.apply(ctx, state["avg_st"], params)
     state["params"] = params
     state["q"] = None  # materialised lazily by `output` / callbacks (params are device resident)
-    info = {**{k: v for k, v in info.items() if k != "elbo"}, "elbo": -value}   # subsampling adds (epoch, step)
+    if isinstance(alg.objective, O.ScoreGradELBO):   # its value is the VarGrad objective; the elbo is the objective's own statistic
+        info = {**info, "elbo": float(info["elbo"])}
+    else:
+        info = {**{k: v for k, v in info.items() if k != "elbo"}, "elbo": -value}   # subsampling adds (epoch, step)
     if callback is not None:
         extra = callback(rng=rng, iteration=t, restructure=re, params=params,
                          averaged_params=alg.averager.value(state["avg_st"]), gradient=grad, state=state)
@@ -366,7 +392,7 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
     Returns (output, info, state).  Without a callback and with a device-resident target every iteration runs inside
     mivi_optimize_loop (`device_loop=False` forces the host-driven `step` loop; both give the same result -- bitwise or to rounding, see
     _optimize_on_device)."""
-    if isinstance(rng, KLMinRepGradDescent):   # default-rng overload, optimize.jl:83-94
+    if isinstance(rng, PARAM_SPACE_SGD):   # default-rng overload, optimize.jl:83-94
         extra = (q_init,) if q_init is not None else ()
         rng, algorithm, max_iter, prob, q_init = O.default_rng(), rng, algorithm, max_iter, prob
         objargs = extra + objargs

@@ -151,6 +151,12 @@ typedef int32_t (*mivi_logdensity_fn)(void *user, const void *Z_host, int32_t d,
 mivi_status_t mivi_set_target_callback(mivi_ctx_t *ctx, mivi_logdensity_and_gradient_fn fn_grad,
                                        mivi_logdensity_fn fn_value, void *user);
 
+/* A target that has ONLY a batched `logdensity` (LogDensityProblems.LogDensityOrder{0}(): not differentiable, or no gradient at hand) --
+ * what the score-gradient estimator is for (src/algorithms/scoregradelbo.jl:44,108 evaluates nothing but `logdensity`).  The score
+ * entries and mivi_estimate_objective accept it; every entry that needs the target's gradient returns MIVI_ERR_UNSUPPORTED on it.
+ * fn_value must not be NULL (mivi_set_target_callback keeps rejecting a NULL gradient function). */
+mivi_status_t mivi_set_target_value_callback(mivi_ctx_t *ctx, mivi_logdensity_fn fn_value, void *user);
+
 /* ---- the hot path ----------------------------------------------------------------------------- */
 /* rand(rng, q, n_mc): src/families/location_scale.jl:71-87 (exposes the sample kernel for parity).
  * Z_dev: T[d*n_mc]; eps_dev: T[d*n_mc] or NULL. */
@@ -183,6 +189,24 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *ctx, const void *params_dev, 
  * rounding (value 1e-6, gradient relative l2 2e-6) on the batch engine (full-rank f32, d and n_mc multiples of 32, Gaussian targets). */
 mivi_status_t mivi_estimate_gradient_each(mivi_ctx_t *ctx, const void *params_dev, uint64_t estimate_idx0,
                                           int32_t count, void *values_dev, void *grads_dev);
+
+/* estimate_gradient!(rng, obj::ScoreGradELBO, adtype, out, state, params, restructure): src/algorithms/scoregradelbo.jl:96-117
+ * with AD of estimate_scoregradelbo_ad_forward (:87-94) replaced by its closed form (DESIGN.md "Score-gradient estimator").
+ * With f_m = log q(z_m) - log pi(z_m) over the cfg.n_mc samples of `estimate_idx` -- the draws mivi_sample returns for that index:
+ *   value_dev T[1] <- mean((f - mean f)^2) / 2   (the VarGrad objective, biased variance as :93)
+ *   elbo_dev  T[1] <- mean(log pi - log q)       (the `stat` of :113-115; may be NULL)
+ *   grad_dev  T[params_len] <- the gradient through log q alone, fully overwritten (full-rank: exact zeros above the diagonal)
+ * Only VALUES of the target are used: every built-in target, the gradient callback (fn_value when set, otherwise the values fn_grad
+ * returns) and the value-only callback, with or without a Stacked bijector (log pi gains logabsdetjac).  cfg.entropy is ignored.
+ * n_mc = 1 gives value = 0 and a zero gradient exactly.  Asynchronous for built-in targets, synchronous for callback targets; a
+ * non-finite value / elbo or a non-positive scale diagonal sets the sticky device flag like mivi_estimate_gradient.
+ * MIVI_ERR_UNSUPPORTED: a sharded context (m_offset != 0 or m_total not in {0, n_mc}: the centring needs every sample); a full-rank d
+ * beyond the LDS-resident triangular solve (the limit of the sticking-the-landing estimators). */
+mivi_status_t mivi_estimate_score_gradient(mivi_ctx_t *ctx, const void *params_dev, uint64_t estimate_idx,
+                                           void *value_dev, void *elbo_dev, void *grad_dev);
+/* Same, host buffers, synchronous; returns MIVI_ERR_NONFINITE / MIVI_ERR_NONPOSITIVE_SCALE (src/algorithms/common.jl:83-89). */
+mivi_status_t mivi_estimate_score_gradient_host(mivi_ctx_t *ctx, const void *params_host, uint64_t estimate_idx,
+                                                void *value_host, void *elbo_host, void *grad_host);
 
 /* estimate_objective(rng, obj::RepGradELBO, q, prob; n_samples): src/algorithms/repgradelbo.jl:112-118;
  * `entropy` override mirrors the algorithm-level wrapper src/algorithms/common.jl:29-38 (default there:
