@@ -295,3 +295,64 @@ def test_second_order_branch_needs_a_hessian():
     with pytest.raises(avi.MiviError, match="no Hessian"):
         ctx.gauss_expected_grad_hess(avi.destructure(q)[0], 0, second_order=True)
     ctx.close()
+
+
+# ---- the second-order logistic-regression Hessian over the DATA axis ---------------------------------------------------------------------
+H2_DATA = [(1, 4), (63, 33), (65, 32), (300, 63), (20000, 40)]   # (n, p): below / around the 64-row tiles of k_h2_lr_wsum and k_h2_lr_gram,
+#                                                                  one to two 32-column Gram tiles, three row splits of 6720 (the last ragged)
+H2_F32_FACTOR = 8.0                                               # tests/test_gpu_scoregrad.py F32_FACTOR
+
+
+def _h2_units(p):
+    """the Gram kernel's units of H: every 32 x 32 tile of H[:p, :p] (a lower tile and its mirror are two units), the border row, the border column"""
+    cuts = list(range(0, p, 32))
+    units = [(f"tile({a // 32},{b // 32})", np.s_[a:min(a + 32, p), b:min(b + 32, p)]) for a in cuts for b in cuts]
+    return units + [("border row", np.s_[p, :]), ("border column", np.s_[:, p])]
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("M", [3, 8])
+@pytest.mark.parametrize("n,p", H2_DATA)
+def test_second_order_logreg_hessian_over_the_data_axis(n, p, M, dtype):
+    """csrc/kernels_hess2.hip with data the parametrised tests above never give it (make_problem: n = 64, one full row tile): n below, just
+    around and far beyond a row tile, several column tiles, several row splits, both variants, likeadj 1 and 1.7.  X ~ N(0, 1) / sqrt(p) puts
+    the Gram block on the order of the -mean(sigma^-2) I diagonal that dominates a global norm, and beside the global check every unit of
+    the Gram kernel is held on its own: f64 to 1e-10 of the unit's norm; f32 to 8 x the distance of the float32 restatement
+    (solve_ref.logreg_hessian_order2, floor 2^-24 of the unit's norm) from the float64 one on the f32-stored inputs and the device's draws.
+    Measured on the MI355X, worst unit over all cases: f32 3.66 x the yardstick (the border row at n = 65, p = 32, M = 8), f64 7.7e-16."""
+    from tests import solve_ref as S
+    d, idx = p + 1, 6
+    rng = np.random.default_rng(1000 * n + p)
+    X = (rng.normal(size=(n, p)) / np.sqrt(p)).astype(dtype)
+    y = (rng.uniform(size=n) < 0.5).astype(np.uint8)
+    q, q_o = make_family(rng, d, avi.FULLRANK, dtype, mu_scale=0.2)
+    params, _ = avi.destructure(q)
+    ctx = avi.MiviContext(dtype, avi.FULLRANK, d, M, 0, SEED)
+    tv, tg, th = TOL[dtype]
+    for variant in ("logsigma_normal", "lognormal_exp_bijector"):
+        for likeadj in (1.0, 1.7):
+            ctx.set_problem(avi.LogRegProblem(X, y, variant, likeadj, order=2))
+            _, eps = ctx.sample(params, idx)
+            eps = eps.cpu().numpy().copy()
+            logpi, g, H = ctx.gauss_expected_grad_hess(params, idx, second_order=True)
+            logpi, g, H = float(logpi.item()), g.cpu().numpy().astype(np.float64), H.cpu().numpy().astype(np.float64)
+            lp_ref, g_ref, H_ref = O.gaussian_expectation_gradient_and_hessian_order2(q_o, O.LogRegTarget(X, y, variant, likeadj), eps.astype(np.float64))
+            assert abs(logpi - lp_ref) <= tv * max(abs(lp_ref), 1.0)
+            assert np.linalg.norm(g - g_ref) <= tg * max(np.linalg.norm(g_ref), 1.0)
+            assert np.linalg.norm(H - H_ref) <= th * max(np.linalg.norm(H_ref), 1.0)
+            ref = S.logreg_hessian_order2(params, d, X, y, variant, likeadj, eps, np.float64)
+            assert np.linalg.norm(ref - H_ref) <= 1e-12 * np.linalg.norm(H_ref)
+            yard = S.logreg_hessian_order2(params, d, X, y, variant, likeadj, eps, np.float32) if dtype == np.float32 else None
+            worst = (0.0, "")
+            for name, sl in _h2_units(p):
+                err, scale = np.linalg.norm(H[sl] - ref[sl]), np.linalg.norm(ref[sl])
+                if dtype == np.float64:
+                    worst = max(worst, (err / scale, name))
+                    assert err <= 1e-10 * scale, (variant, likeadj, name, err / scale)
+                else:
+                    bound = max(np.linalg.norm(yard[sl].astype(np.float64) - ref[sl]), S.F32_FLOOR * scale)
+                    worst = max(worst, (err / bound, name))
+                    assert err <= H2_F32_FACTOR * bound, (variant, likeadj, name, err / bound)
+            print(f"[logreg hess2] n={n} p={p} M={M} {np.dtype(dtype).name} {variant} likeadj={likeadj}: worst unit {worst[1]} "
+                  + (f"{worst[0]:.2f} x the float32 yardstick" if dtype == np.float32 else f"{worst[0]:.2e} relative"))
+    ctx.close()
