@@ -289,6 +289,32 @@ class MiviContext:
         self._raise_cb(fn(self.h, self._p(p), idx, int(n_samples), self._p(logpi), self._p(grad), self._p(hess)))
         return logpi, grad, hess.view(self.d, self.d).t()   # column-major d x d
 
+    def sqrt_ngd_update(self, params, grad, hess, stepsize, entropy=None):
+        """mivi_sqrt_ngd_update: the square-root natural-gradient update of the device tensor `params` ([m; vec C]) in place from
+        grad (d) and hess (d*d column-major, as gauss_expected_grad_hess fills it); returns entropy(q') as a 1-element device tensor."""
+        entropy = self.empty(1) if entropy is None else entropy
+        hess = hess.t() if hess.dim() == 2 else hess   # the (d, d) matrix view gauss_expected_grad_hess returns -> its column-major storage
+        if not hess.is_contiguous():
+            hess = hess.contiguous()
+        self._chk(self.lib.mivi_sqrt_ngd_update(self.h, self._p(params), self._p(grad), self._p(hess), float(stepsize), self._p(entropy)))
+        return entropy
+
+    def sqrt_ngd_update_host(self, params, grad, hess, stepsize):
+        """mivi_sqrt_ngd_update_host on numpy arrays: params ([m; vec C]), grad (d), hess ((d, d) matrix); returns (params', entropy(q'))."""
+        p = np.array(params, dtype=self.np_dtype, copy=True)
+        g = np.ascontiguousarray(grad, dtype=self.np_dtype)
+        H = np.asfortranarray(hess, dtype=self.np_dtype)
+        ent = np.zeros(1, dtype=self.np_dtype)
+        self._chk(self.lib.mivi_sqrt_ngd_update_host(self.h, p.ctypes.data, g.ctypes.data, H.ctypes.data, float(stepsize), ent.ctypes.data))
+        return p, ent[0]
+
+    def sqrt_ngd_steps(self, params, idx0, count, stepsize, n_samples=0, second_order=False, elbo=None):
+        """mivi_sqrt_ngd_steps: `count` iterations {estimator (index idx0 + t), update} on the device tensor `params`; returns elbo (count)."""
+        elbo = self.empty(int(count)) if elbo is None else elbo
+        self._raise_cb(self.lib.mivi_sqrt_ngd_steps(self.h, self._p(params), idx0, int(count), int(n_samples), 1 if second_order else 0,
+                                                    float(stepsize), self._p(elbo)))
+        return elbo
+
     def estimate_partials(self, params, idx, partials=None):
         p = self.to_device(params)
         partials = self.empty(self.partials_len) if partials is None else partials

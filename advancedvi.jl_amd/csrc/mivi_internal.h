@@ -369,6 +369,7 @@ struct mivi_ctx {
   mivi::DevBuf stein_A, stein_g;   // Stein estimator: eps G^T accumulator (dP x dP, T) and the f64 column sums of G
   mivi::DevBuf sg_S, sg_d;         // score-gradient estimator (kernels_score.hip): -E diag(f - mean f) laid out like eps (full-rank); f64 [|eps_m|^2; dense ell_m; f_m - mean f] (3 x cap_M)
   int sg_cap = 0;                  // samples sg_d is sized for
+  mivi::DevBuf ngd_work, ngd_part, ngd_est;   // square-root natural-gradient update (kernels_ngd.hip): [Cc; G; T; v] padded to whole tiles; the diagonal tiles' f64 partials + the ticket; [logpi_avg (16 bytes); grad (d); hess (d x d)] of mivi_sqrt_ngd_steps
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
   const uint64_t *idx_src = nullptr;   // mivi_set_index_source
@@ -548,6 +549,11 @@ void launch_sg_norms(mivi_ctx *c, const RngArgs &rng, int M);         // sg_d[m]
 void launch_sg_stats(mivi_ctx *c, const void *params, int M, bool ell_f64, void *value, void *elbo);   // f, mean f, weights, value, elbo, status flags
 void launch_sg_scale(mivi_ctx *c, int M);                              // full-rank: sg_S = -eps diag(f - mean f) (pads zero), W = 0
 void launch_sg_mf_grad(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *grad);   // mean-field: [d/dmu; d/dsigma]
+
+// kernels_ngd.hip: KLMinSqrtNaturalGradDescent's update (klminsqrtnaturalgraddescent.jl:108-119) on [m; vec C] in place
+size_t ngd_work_bytes(const mivi_ctx *c);    // c->ngd_work (0: the one-workgroup kernel needs none)
+size_t ngd_part_bytes(const mivi_ctx *c);    // c->ngd_part: the diagonal tiles' partials + their ticket (0: the one-workgroup kernel needs none)
+void launch_ngd_update(mivi_ctx *c, void *params, const void *grad, const void *hess, double eta, const void *logpi, void *entropy, void *elbo);
 
 // kernels_p2p.hip: phases bit 0 push, 1 reduce + finalise, 2 unpack (7 = the whole exchange in one launch)
 void launch_p2p_handover4(mivi_ctx *c, unsigned *ready, unsigned ready_val, const unsigned *const *freed, const unsigned *freed_min, int n);

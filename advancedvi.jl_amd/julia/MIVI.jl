@@ -536,6 +536,31 @@ function AdvancedVI.gaussian_expectation_gradient_and_hessian!(
     return logpi[], grad_buf, hess_buf
 end
 
+# KLMinSqrtNaturalGradDescent (src/algorithms/klminsqrtnaturalgraddescent.jl): the update of `step` (:108-112) on [m; vec(C)] from the
+# buffers gaussian_expectation_gradient_and_hessian! filled -- `params = first(Optimisers.destructure(q))` is updated in place, entropy(q')
+# (the term of :119) is returned -- and, on device pointers, whole iterations {estimator, update} without a host round trip
+# (mivi_sqrt_ngd_steps: params_dev T[d + d^2] in HBM, elbo_dev T[count] or C_NULL; second_order as the reference's capability test :31-32).
+function sqrt_ngd_update!(state::MIVIState, params::Vector{T}, grad_buf::Vector{T}, hess_buf::Matrix{T}, stepsize::Real) where {T<:Real}
+    entropy = Ref{T}(zero(T))
+    check(state.ctx, ccall((:mivi_sqrt_ngd_update_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, Ptr{T}, Ptr{T}, Float64, Ref{T}),
+                           state.ctx, params, grad_buf, hess_buf, Float64(stepsize), entropy))
+    return params, entropy[]
+end
+function sqrt_ngd_update_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, grad_dev::Ptr{Cvoid}, hess_dev::Ptr{Cvoid}, stepsize::Real,
+                              entropy_dev::Ptr{Cvoid}=C_NULL)
+    check(state.ctx, ccall((:mivi_sqrt_ngd_update, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}),
+                           state.ctx, params_dev, grad_dev, hess_dev, Float64(stepsize), entropy_dev))
+    return state
+end
+function sqrt_ngd_steps!(state::MIVIState, params_dev::Ptr{Cvoid}, count::Integer, n_samples::Integer, second_order::Bool, stepsize::Real,
+                         elbo_dev::Ptr{Cvoid}=C_NULL)
+    check(state.ctx, ccall((:mivi_sqrt_ngd_steps, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Int32, Int32, Int32, Float64, Ptr{Cvoid}),
+                           state.ctx, params_dev, state.estimate_idx, Int32(count), Int32(n_samples), Int32(second_order), Float64(stepsize), elbo_dev))
+    state.estimate_idx += count
+    check(state.ctx, ccall((:mivi_synchronize, libmivi), Int32, (Ptr{Cvoid},), state.ctx))
+    return state
+end
+
 # Constrained supports (README.md:76-82, 91-119; docs/src/tutorials/constrained.md:154-196): a Bijectors.Stacked of identity / exp
 # blocks is applied by the library around whatever target is set.  `ranges` are the Stacked's UnitRanges (1-based, as Bijectors
 # stores them), `kinds[i]` is :identity or :exp.  An empty list removes the constraint.
@@ -600,5 +625,5 @@ end
 # ProximalLocationScaleEntropy on the host arrays works unchanged (src/optimization/proximal_location_scale_entropy.jl);
 # the device-resident variant for a parameter vector that lives in HBM is mivi_prox_scale_entropy.
 
-export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!
+export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!
 end # module

@@ -1,0 +1,155 @@
+"""Measure-space algorithms: KLMinSqrtNaturalGradDescent, the host-side mirror of
+src/algorithms/klminsqrtnaturalgraddescent.jl (AdvancedVI.jl v0.7.0) over libmivi.
+
+    KLMinSqrtNaturalGradDescent(stepsize, n_samples=1, subsampling=None)     :39-44
+    init(rng, alg, q_init, prob)                                             :55-75
+    step(rng, alg, state, callback) -> (state, False, info)                  :79-127
+    output(alg, state) = state.q, the last iterate                           :77
+    estimate_objective([rng,] alg, q, prob; n_samples)                       :146-165
+
+The variational parameters [m; vec(C)] stay resident in HBM between steps.  A step is the tuned inner estimator
+(mivi_gauss_expected_grad_hess / _hess2, chosen by the target's capability like gauss_expected_grad_hess.jl:31-32) followed by
+mivi_sqrt_ngd_update; `optimize` without a callback and without subsampling runs whole chunks of steps inside mivi_sqrt_ngd_steps, with
+bitwise the same iterates as the host-driven `step` loop."""
+from __future__ import annotations
+
+from . import objectives as O
+from . import problems as P
+from . import subsampling as S
+from .context import MiviContext
+from .families import FULLRANK, MvLocationScale, destructure
+
+
+class KLMinSqrtNaturalGradDescent:
+    """KL minimisation by discretising the natural-gradient flow under the square-root parameterisation
+    (klminsqrtnaturalgraddescent.jl:2-44).  Needs a full-rank Gaussian family and a target with at least first-order capability; a target
+    with second-order capability has its Hessians used, otherwise the Stein identity on gradients."""
+
+    def __init__(self, stepsize, n_samples: int = 1, subsampling=None, device: int = 0):
+        if not isinstance(n_samples, int) or n_samples < 1:
+            raise ValueError("n_samples must be a positive Int")
+        self.stepsize = float(stepsize)
+        self.n_samples = int(n_samples)
+        self.subsampling = subsampling
+        self.device = int(device)
+
+    def __repr__(self):
+        return f"KLMinSqrtNaturalGradDescent(stepsize={self.stepsize}, n_samples={self.n_samples}, subsampling={self.subsampling})"
+
+
+def _second_order(prob) -> bool:
+    """LogDensityOrder{1}() < capabilities(prob): the branch test of gauss_expected_grad_hess.jl:31-32."""
+    return P.LogDensityOrder(1) < P.capabilities(prob)
+
+
+def init(rng, alg: KLMinSqrtNaturalGradDescent, q_init, prob):
+    """klminsqrtnaturalgraddescent.jl:55-75."""
+    if not isinstance(q_init, MvLocationScale) or q_init.family != FULLRANK:
+        raise TypeError("`KLMinSqrtNaturalGradDescent` expects a Gaussian with a lower-triangular scale (FullRankGaussian) as q_init")
+    capability = P.capabilities(prob)
+    if capability < P.LogDensityOrder(1):   # :64-70 (ArgumentError)
+        raise ValueError("`KLMinSqrtNaturalGradDescent` requires at least first-order differentiation capability. The capability of the "
+                         f"supplied `LogDensityProblem` is {capability}.")
+    sub_st = None if alg.subsampling is None else S.init_subsampling(rng, alg.subsampling)
+    params_h, re = destructure(q_init)
+    ctx = MiviContext(q_init.eltype, FULLRANK, len(q_init), min(alg.n_samples, 16384), O.ClosedFormEntropy.code, rng.seed, device=alg.device)
+    ctx.set_problem(prob)
+    d = len(q_init)
+    return dict(q=q_init, prob=prob, iteration=0, sub_st=sub_st, ctx=ctx, params=ctx.to_device(params_h).clone(), restructure=re,
+                grad_buf=ctx.empty(d), hess_buf=ctx.empty(d * d))
+
+
+def _q_of(state):
+    if state["q"] is None:
+        state["q"] = state["restructure"](state["params"].cpu().numpy())
+    return state["q"]
+
+
+def output(alg, state):
+    """output(::KLMinSqrtNaturalGradDescent, state) = state.q: the last iterate, no averaging (:77)."""
+    return _q_of(state)
+
+
+def step(rng, alg: KLMinSqrtNaturalGradDescent, state, callback, *objargs):
+    """klminsqrtnaturalgraddescent.jl:79-127.  The parameters live in ONE device buffer that the update advances in place: the state passed in is
+    consumed by the call (use the returned one; `optimize(state=...)` works on a copy of the buffer and leaves its argument as it was)."""
+    state = dict(state)
+    ctx, params = state["ctx"], state["params"]
+    state["iteration"] += 1
+    prob_sub, sub_inf = state["prob"], {}
+    if alg.subsampling is not None:   # :96-102
+        batch, state["sub_st"], sub_inf = S.step_subsampling(rng, alg.subsampling, state["sub_st"])
+        prob_sub = P.subsample(state["prob"], batch)
+        ctx.set_problem(prob_sub)
+    logpi, grad, _ = ctx.gauss_expected_grad_hess(params, rng.next_index(), alg.n_samples, state["grad_buf"], state["hess_buf"],
+                                                  second_order=_second_order(prob_sub))
+    entropy = ctx.sqrt_ngd_update(params, grad, state["hess_buf"], alg.stepsize)
+    elbo = float((logpi + entropy).item())   # (one addition in the context's dtype: what mivi_sqrt_ngd_steps records)
+    ctx.synchronize()                        # a scale diagonal that left the positive numbers raises here (MIVI_ERR_NONPOSITIVE_SCALE)
+    state["q"] = None                        # materialised lazily by `output` / callbacks (the parameters are device resident)
+    info = {"elbo": elbo, **sub_inf}
+    if callback is not None:
+        extra = callback(rng=rng, iteration=state["iteration"], q=_q_of(state), info=info)
+        if extra is not None:
+            info = {**extra, **info}
+    return state, False, info
+
+
+def estimate_objective(rng, alg, q=None, prob=None, n_samples=None):
+    """estimate_objective([rng,] alg, q, prob; n_samples): klminsqrtnaturalgraddescent.jl:146-165 -- the negative ELBO with the Monte-Carlo
+    entropy; with subsampling, the average over one pass through the batches."""
+    if isinstance(rng, KLMinSqrtNaturalGradDescent):
+        rng, alg, q, prob = O.default_rng(), rng, alg, q
+    n = int(n_samples) if n_samples is not None else alg.n_samples
+    obj = O.RepGradELBO(n, entropy=O.MonteCarloEntropy())
+    adtype = O.AutoMIVI(device=alg.device)
+    if alg.subsampling is None:
+        return O.estimate_objective(rng, obj, q, prob, adtype=adtype)
+    return S.estimate_objective(rng, S.SubsampledObjective(obj, alg.subsampling), q, prob, adtype=adtype)
+
+
+def _steps_on_device(rng, alg, max_iter, state, show_progress):
+    from .optimize import DEVICE_LOOP_CHUNK
+    ctx, params = state["ctx"], state["params"]
+    second = _second_order(state["prob"])
+    info_total, done = [], 0
+    while done < max_iter:
+        n = min(DEVICE_LOOP_CHUNK, max_iter - done)
+        elbo = ctx.sqrt_ngd_steps(params, rng.counter, n, alg.stepsize, n_samples=alg.n_samples, second_order=second)
+        ctx.synchronize()
+        for _ in range(n):
+            rng.next_index()
+        vals = elbo.cpu().numpy()
+        info_total += [{"elbo": float(vals[i]), "iteration": done + i + 1} for i in range(n)]
+        state["iteration"] += n
+        state["q"] = None
+        done += n
+        if show_progress:
+            print(f"\rOptimizing {done}/{max_iter} elbo={info_total[-1]['elbo']:.6g}", end="" if done < max_iter else "\n")
+    return info_total
+
+
+def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, show_progress=False, state=None, callback=None,
+             device_loop=True):
+    """optimize([rng,] algorithm, max_iter, prob, q_init; show_progress, state, callback): src/optimize.jl:42-94 for this algorithm.
+    Returns (output, info, state)."""
+    if isinstance(rng, KLMinSqrtNaturalGradDescent):   # default-rng overload, optimize.jl:83-94
+        rng, algorithm, max_iter, prob, q_init = O.default_rng(), rng, algorithm, max_iter, prob
+    if state is None:
+        state = init(rng, algorithm, q_init, prob)
+    else:   # a warm start: the caller's state (its parameter buffer and cached q) stays what it was
+        state = dict(state, params=state["params"].clone())
+    if device_loop and callback is None and algorithm.subsampling is None and not objargs and max_iter > 0:
+        state = dict(state)
+        info_total = _steps_on_device(rng, algorithm, max_iter, state, show_progress)
+        return output(algorithm, state), info_total, state
+    info_total = []
+    for t in range(1, max_iter + 1):
+        state, terminate, info = step(rng, algorithm, state, callback, *objargs)
+        info = {**info, "iteration": t}
+        if terminate:
+            break
+        if show_progress:
+            print(f"\rOptimizing {t}/{max_iter} elbo={info['elbo']:.6g}", end="" if t < max_iter else "\n")
+        info_total.append(info)
+    return output(algorithm, state), info_total, state

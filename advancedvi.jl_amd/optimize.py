@@ -206,6 +206,13 @@ BBVI = KLMinScoreGradDescent
 PARAM_SPACE_SGD = (KLMinRepGradDescent, KLMinScoreGradDescent)   # the ParamSpaceSGD algorithms: what init / step / optimize accept
 
 
+def _measure_space(*heads):
+    """The measure_space module when one of `heads` is a measure-space algorithm (KLMinSqrtNaturalGradDescent: it has a loop of its own,
+    no objective / optimiser / averager), else None."""
+    from . import measure_space as M
+    return M if any(isinstance(h, M.KLMinSqrtNaturalGradDescent) for h in heads) else None
+
+
 def _obj_init(rng, obj, *a):
     return (S.init if isinstance(obj, S.SubsampledObjective) else O.init)(rng, obj, *a)
 
@@ -220,6 +227,9 @@ def _ctx_of(obj_st):
 
 def estimate_objective(rng, alg, q, prob=None, n_samples=None, entropy=None):
     """estimate_objective([rng,] alg, q, prob; n_samples, entropy=MonteCarloEntropy()): common.jl:29-38."""
+    M = _measure_space(rng, alg)
+    if M is not None:
+        return M.estimate_objective(rng, alg, q, prob, n_samples=n_samples)
     if isinstance(rng, PARAM_SPACE_SGD):
         rng, alg, q, prob = O.default_rng(), rng, alg, q
     n = n_samples if n_samples is not None else alg.objective.n_samples
@@ -234,6 +244,9 @@ def estimate_objective(rng, alg, q, prob=None, n_samples=None, entropy=None):
 
 def init(rng, alg, q_init, prob):
     """init(rng, alg::ParamSpaceSGD, q_init, prob): common.jl:40-61."""
+    M = _measure_space(alg)
+    if M is not None:
+        return M.init(rng, alg, q_init, prob)
     if isinstance(q_init, MvLocationScale) and isinstance(alg.operator, IdentityOperator):
         warnings.warn(
             "IdentityOperator is used with a variational family <:MvLocationScale. Optimization can easily fail under "
@@ -252,11 +265,17 @@ def init(rng, alg, q_init, prob):
 
 def output(alg, state):
     """output(alg, state) = re(value(averager, avg_st)): common.jl:63-67."""
+    M = _measure_space(alg)
+    if M is not None:
+        return M.output(alg, state)
     return state["restructure"](alg.averager.value(state["avg_st"]).cpu().numpy())
 
 
 def step(rng, alg, state, callback, *objargs):
     """step(rng, alg::ParamSpaceSGD, state, callback): common.jl:69-120."""
+    M = _measure_space(alg)
+    if M is not None:
+        return M.step(rng, alg, state, callback, *objargs)
     state = dict(state)
     state["iteration"] += 1
     t = state["iteration"]
@@ -392,6 +411,10 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
     Returns (output, info, state).  Without a callback and with a device-resident target every iteration runs inside
     mivi_optimize_loop (`device_loop=False` forces the host-driven `step` loop; both give the same result -- bitwise or to rounding, see
     _optimize_on_device)."""
+    M = _measure_space(rng, algorithm)
+    if M is not None:
+        return M.optimize(rng, algorithm, max_iter, prob, q_init, *objargs, show_progress=show_progress, state=state, callback=callback,
+                          device_loop=device_loop)
     if isinstance(rng, PARAM_SPACE_SGD):   # default-rng overload, optimize.jl:83-94
         extra = (q_init,) if q_init is not None else ()
         rng, algorithm, max_iter, prob, q_init = O.default_rng(), rng, algorithm, max_iter, prob

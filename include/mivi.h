@@ -251,6 +251,30 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *ctx, const void *params
 mivi_status_t mivi_gauss_expected_grad_hess2_host(mivi_ctx_t *ctx, const void *params_host, uint64_t estimate_idx,
                                                   int32_t n_samples, void *logpi_avg_host, void *grad_host, void *hess_host);
 
+/* KLMinSqrtNaturalGradDescent: the update of `step` (src/algorithms/klminsqrtnaturalgraddescent.jl:108-112) on the device-resident
+ * parameters [m; vec(C)] of a full-rank context, IN PLACE, from grad (T[d]) and hess (T[d*d], column-major) as the estimator entries above
+ * leave them -- both read-only, hess used as it comes (not symmetrised, not transposed; only the lower triangle of A is formed):
+ *   A = C' (-hess) C - I     T = tril(A) - diag(A)/2     m' = m - stepsize C (C' (-grad))     C' = C - stepsize C T   (exact zeros above the diagonal)
+ *   entropy_dev T[1] <- entropy(q') = d/2 (1 + log 2 pi) + sum_i log C'_ii  (src/families/location_scale.jl:52-57; the term of :119); may be NULL
+ * d <= 48: one workgroup, one launch; above: three launches of 64 x 64 tiles on the matrix cores (csrc/kernels_ngd.hip), C' assembled from a
+ * context-owned copy of C.  The update is bitwise repeatable (no floating-point atomics, one summation order).  A C'_ii that is not a positive finite number or a non-finite entropy sets the sticky device flag
+ * (mivi_synchronize); the _host form (host buffers, synchronous) returns MIVI_ERR_NONPOSITIVE_SCALE / MIVI_ERR_NONFINITE itself.  Any d >= 1.
+ * MIVI_ERR_UNSUPPORTED: a mean-field context. */
+mivi_status_t mivi_sqrt_ngd_update(mivi_ctx_t *ctx, void *params_dev, const void *grad_dev, const void *hess_dev, double stepsize,
+                                   void *entropy_dev);
+mivi_status_t mivi_sqrt_ngd_update_host(mivi_ctx_t *ctx, void *params_host, const void *grad_host, const void *hess_host, double stepsize,
+                                        void *entropy_host);
+/* `count` whole iterations of step(rng, alg::KLMinSqrtNaturalGradDescent, ...) (src/algorithms/klminsqrtnaturalgraddescent.jl:79-127, without
+ * subsampling and callback) with the parameters resident in HBM and no host round trip: iteration t estimates with index estimate_idx0 + t
+ * (:104; second_order = 0: mivi_gauss_expected_grad_hess, the Stein branch; != 0: mivi_gauss_expected_grad_hess2; n_samples <= 0: cfg.n_mc), then
+ * updates (:108-112); elbo_dev T[count] (or NULL) <- logpi_avg_t + entropy(q'_t) (:119).  The same launches and arithmetic as `count` calls of the estimator entry followed by
+ * mivi_sqrt_ngd_update: bitwise equal to them and bitwise repeatable wherever the estimator entry is (the second-order branch of the built-in logistic-regression and
+ * funnel targets sums with f64 atomics, csrc/kernels_hess2.hip: those steps repeat to the rounding of a reordered f64 sum).  Asynchronous for built-in targets, synchronous per step for callback targets; a non-finite elbo or a C'_ii that is
+ * not positive sets the sticky device flag.  MIVI_ERR_UNSUPPORTED: a mean-field context (:58 takes a LowerTriangular scale); a sharded context; what
+ * the chosen estimator entry refuses (second_order without a Hessian or under a Stacked bijector; d beyond the first-order entry's solve). */
+mivi_status_t mivi_sqrt_ngd_steps(mivi_ctx_t *ctx, void *params_dev, uint64_t estimate_idx0, int32_t count, int32_t n_samples,
+                                  int32_t second_order, double stepsize, void *elbo_dev);
+
 /* ---- multi-GPU: shard the MC batch, all-reduce the partials, finalize -------------------------- *
  * No counterpart in the reference (single task).  partials_dev: T[partials_len] un-normalised sums over
  * this context's samples; the caller all-reduces (RCCL sum) and calls mivi_finalize on every rank. */
