@@ -308,6 +308,42 @@ class MiviContext:
         self._chk(self.lib.mivi_sqrt_ngd_update_host(self.h, p.ctypes.data, g.ctypes.data, H.ctypes.data, float(stepsize), ent.ctypes.data))
         return p, ent[0]
 
+    # the _host entries (what julia/MIVI.jl calls on every step): numpy arrays in, numpy arrays out, synchronous
+    def estimate_gradient_host(self, params, idx):
+        """mivi_estimate_gradient_host: (value, grad (params_len)) of estimate `idx` at the host vector `params`."""
+        p = np.ascontiguousarray(params, dtype=self.np_dtype)
+        value = np.zeros(1, dtype=self.np_dtype)
+        grad = np.zeros(self.params_len, dtype=self.np_dtype)
+        self._raise_cb(self.lib.mivi_estimate_gradient_host(self.h, p.ctypes.data, idx, value.ctypes.data, grad.ctypes.data))
+        return value[0], grad
+
+    def estimate_objective_host(self, params, idx, n_samples=0, entropy=-1):
+        """mivi_estimate_objective_host: the objective value; a non-finite one is returned as it is (only a non-positive scale raises)."""
+        p = np.ascontiguousarray(params, dtype=self.np_dtype)
+        value = np.zeros(1, dtype=self.np_dtype)
+        self._raise_cb(self.lib.mivi_estimate_objective_host(self.h, p.ctypes.data, idx, int(n_samples), int(entropy), value.ctypes.data))
+        return value[0]
+
+    def gauss_expected_grad_hess_host(self, params, idx, n_samples=0, second_order=False):
+        """mivi_gauss_expected_grad_hess_host / _hess2_host: (logpi_avg, grad (d), hess (d, d)); `hess[i, j]` is the matrix entry."""
+        p = np.ascontiguousarray(params, dtype=self.np_dtype)
+        logpi = np.zeros(1, dtype=self.np_dtype)
+        grad = np.zeros(self.d, dtype=self.np_dtype)
+        hess = np.zeros((self.d, self.d), dtype=self.np_dtype, order="F")   # column-major d x d
+        fn = self.lib.mivi_gauss_expected_grad_hess2_host if second_order else self.lib.mivi_gauss_expected_grad_hess_host
+        self._raise_cb(fn(self.h, p.ctypes.data, idx, int(n_samples), logpi.ctypes.data, grad.ctypes.data, hess.ctypes.data))
+        return logpi[0], grad, hess
+
+    def estimate_score_gradient_host(self, params, idx, want_elbo=True):
+        """mivi_estimate_score_gradient_host: (value, elbo, grad (params_len)); want_elbo False passes NULL for elbo_h and returns None there."""
+        p = np.ascontiguousarray(params, dtype=self.np_dtype)
+        value = np.zeros(1, dtype=self.np_dtype)
+        elbo = np.zeros(1, dtype=self.np_dtype) if want_elbo else None
+        grad = np.zeros(self.params_len, dtype=self.np_dtype)
+        self._raise_cb(self.lib.mivi_estimate_score_gradient_host(self.h, p.ctypes.data, idx, value.ctypes.data,
+                                                                  elbo.ctypes.data if want_elbo else None, grad.ctypes.data))
+        return value[0], (elbo[0] if want_elbo else None), grad
+
     def sqrt_ngd_steps(self, params, idx0, count, stepsize, n_samples=0, second_order=False, elbo=None):
         """mivi_sqrt_ngd_steps: `count` iterations {estimator (index idx0 + t), update} on the device tensor `params`; returns elbo (count)."""
         elbo = self.empty(int(count)) if elbo is None else elbo

@@ -14,7 +14,7 @@ mivi_status_t reserve_target(mivi_ctx *c, int M) {
 // `cnt` chained estimates of context k at fixed parameters: indices first, first + stride, ... -- by value (idx_ptr = nullptr: an eager
 // chain) or relative to the device-side counter *idx_ptr (a recording).  Every estimate but the last writes its result where the last one
 // does; the chain's closing value launch is flush_chain's.
-// The eps speculation is off afterwards.  (run_estimate clears pre_valid on entry and sets it only on its `spec` branches, which a
+// The eps speculation is off afterwards.  (run_estimate clears c->pre on entry and sets it only on its `spec` branches, which a
 // chained gradient estimate never takes: the second-generation route has spec = !chained, and the first-generation route is chained
 // exactly when hetero_ok holds, which spec needs too.  So the flag can only have survived an estimate that failed before it got there.)
 static mivi_status_t record_chain(mivi_ctx *k, const void *params, uint64_t first, uint64_t stride, int cnt, const uint64_t *idx_ptr, void *value,
@@ -34,7 +34,7 @@ static mivi_status_t record_chain(mivi_ctx *k, const void *params, uint64_t firs
   }
   if (s == MIVI_OK) flush_chain(k, params, &chn);
   k->cur = 0;
-  k->pre_valid = false;
+  k->pre.clear();
   return s;
 }
 
@@ -545,7 +545,7 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
           if (st == MIVI_OK) flush_chain(k, params, &chn[l]);
           k->value_sink = nullptr;
           k->cur = 0;
-          k->pre_valid = false;
+          k->pre.clear();
         }
         if (st == MIVI_OK) launch_lanes_value(lead, params, vsink);
         value_sink_free(vsink);

@@ -66,7 +66,7 @@ mivi_status_t ensure(mivi_ctx *c, DevBuf &b, size_t bytes, bool zero) {
 // parity.  Anything that reallocates or rewrites those calls this.
 namespace mivi {
 void invalidate_graph(mivi_ctx *c) {
-  c->pre_valid = false;
+  c->pre.clear();
   ++c->target_gen;
   c->graph.drop();
 }
@@ -228,7 +228,7 @@ mivi_status_t mivi_set_stream(mivi_ctx_t *c, void *s) {
   if (!c) return MIVI_ERR_BAD_ARG;
   if (c->own_stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); c->own_stream = false; }
   c->stream = (hipStream_t)s;   // NULL = the null stream
-  c->pre_valid = false;
+  c->pre.clear();
   c->graph.drop();   // (not invalidate_graph: the children's generation stays)
   return MIVI_OK;
 }

@@ -633,7 +633,7 @@ static mivi_status_t dist_sequence_lanes(mivi_ctx *c, const void *params, bool c
     ctxs[l]->eps_sink = nullptr;
     ctxs[l]->stream = kept[l];
     ctxs[l]->cur = 0;
-    ctxs[l]->pre_valid = false;
+    ctxs[l]->pre.clear();
   }
   lane_sinks_free(sink);
   eps_sink_free(esink);
@@ -804,7 +804,7 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
       const mivi_status_t rs = dist_sequence(c, params, true, 0, count, value, grad, mode);
       if (rs == MIVI_OK && mode != 3) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count);
       c->cur = 0;
-      c->pre_valid = false;
+      c->pre.clear();
       return rs;
     });
     if (s && !begun) return s;   // (the capture never started: the stream's error, not a refusal)
@@ -845,7 +845,7 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
     return gs;
   }
   // eager: the same sequence with by-value indices
-  c->pre_valid = false;
+  c->pre.clear();
   if (p2p_pipe && (s = p2p_front())) return s;
   s = dist_sequence(c, params, false, idx0, count, value, grad, mode);
   if (p2p_pipe) {   // join the exchange stream whatever happened: after a failed sequence its kernel gives up at its bounded waits (status bit 8)
@@ -853,7 +853,7 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
     if (s == MIVI_OK) s = sb;
   }
   c->cur = 0;
-  c->pre_valid = false;
+  c->pre.clear();
   return s;
 }
 

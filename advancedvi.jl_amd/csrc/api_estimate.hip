@@ -67,6 +67,87 @@ bool lds_route(const mivi_ctx *c, const void *params, int M, int want_grad, cons
   return true;
 }
 
+// ---- the eps speculation (c->pre): "the VJP of estimate idx also draws eps of idx + 1, and the next call skips its eps kernel" ----
+EpsLookup eps_spec_lookup(mivi_ctx *c, const RngArgs &rng, int M) {
+  EpsLookup lk{};
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamGetCaptureInfo(c->stream, &cs, &lk.cap_id) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+  lk.capturing = cs == hipStreamCaptureStatusActive;
+  if (!lk.capturing) lk.cap_id = 0;
+  const EpsSpec &s = c->pre;
+  lk.hit = s.valid && s.M == M && s.rng.seed == rng.seed && s.rng.idx_base == rng.idx_base && s.rng.idx_ptr == rng.idx_ptr &&
+           s.rng.m_offset == rng.m_offset && s.capturing == lk.capturing && s.capture_id == lk.cap_id;
+  return lk;
+}
+
+void eps_spec_publish(mivi_ctx *c, const RngArgs &next_rng, int M, int parity, const EpsLookup &lk) {
+  c->pre.valid = true;
+  c->pre.rng = next_rng;
+  c->pre.M = M;
+  c->pre.parity = parity;
+  c->pre.capturing = lk.capturing;
+  c->pre.capture_id = lk.cap_id;
+}
+
+void eps_spec_drop(mivi_ctx *c) {
+  c->cur = 0;
+  c->pre.clear();
+}
+
+// ---- steps the two drivers share ----
+// The eps job that rides in this estimate's kernels: the chain's next estimate, the speculated one, or none.
+static const EpsJob *next_eps_job(EpsJob &nx, const RngArgs &rng, int p, const Chain *ch, bool chained, bool spec) {
+  if (chained && ch->has_next) {
+    nx.rng = ch->next_rng;
+  } else if (spec) {   // speculate that the caller asks for estimate idx + 1 next (an SGD loop does)
+    nx.rng = rng;
+    nx.rng.idx_base = rng.idx_base + 1ull;   // (a single call: the NEXT index, whatever stride an earlier batched call left on this context)
+  } else {
+    return nullptr;
+  }
+  nx.parity = p ^ 1;
+  return &nx;
+}
+
+// Z (behind the bijector, if one is set) is in memory: evaluate the target on it and wire what it leaves into vin.
+mivi_status_t target_on_z(mivi_ctx *c, int M, int want_grad, int p, ValueIn &vin) {
+  if (c->target == TGT_DENSE_GAUSS) {
+    launch_rt_from_z(c, M);
+    launch_fr_dense_target(c, M, want_grad);
+    vin.ell_part = (const double *)c->ell_part[p].p;
+    vin.n_ell_part = fr_dense_blocks(c, M);
+    if (c->bij_on) { vin.ell = c->bij_ld.p; vin.n_ell = M; }   // + logabsdetjac per sample
+    return MIVI_OK;
+  }
+  if (logreg_uses_mfma(c, M)) launch_rt_from_z(c, M);   // Z^T for the MFMA route
+  const mivi_status_t s = eval_generic_target(c, M, want_grad);
+  if (s) return s;
+  vin.ell = c->ell.p;
+  vin.n_ell = M;
+  return MIVI_OK;
+}
+
+// The sticking-the-landing term W += C^-T eps of a full-rank gradient estimate (nothing for the other estimators).
+// dinv_done: the product kernel's riders have already inverted the diagonal blocks of C.
+static mivi_status_t stl_term(mivi_ctx *c, const void *params, int M, const OutArgs &out, bool dinv_done) {
+  if (out.ent_kind != MIVI_ENT_STL && out.ent_kind != MIVI_ENT_STL_ZERO_GRAD) return MIVI_OK;
+  if (!stl_lds_fits(c, c->dP) && !c->stl_CT.p) return fail(c, MIVI_ERR_UNSUPPORTED, "full-rank STL: d too large for the LDS-resident solve");
+  if (stl2_shape_ok(c, M)) launch_stl2(c, params, M, dinv_done);
+  else launch_fr_stl(c, params, M);
+  return MIVI_OK;
+}
+
+// The mean-field kernel's partials: [ell | 0.5 eps^2 | log-det], mf_nblk each, in sc_part[p].
+static void wire_mf_partials(const mivi_ctx *c, int p, ValueIn &vin) {
+  const double *sc = (const double *)c->sc_part[p].p;
+  vin.ell_part2 = sc;
+  vin.n_ell_part2 = c->mf_nblk;
+  vin.he_part = sc + c->mf_nblk;
+  vin.n_he_part = c->mf_nblk;
+  vin.ld_part = sc + 2 * (size_t)c->mf_nblk;
+  vin.n_ld_part = c->mf_nblk;
+}
+
 // One estimate on the second-generation route:
 //   [k_eps unless the previous estimate's product kernel already drew this eps]
 //   k_fr_prod32 / k_fr_prod64 <SAMPLE> (z, fused target, ell / log-det partials, riders: eps of the next estimate, STL operands)
@@ -79,38 +160,17 @@ static mivi_status_t run_estimate_lds(mivi_ctx *c, const void *params, const Rng
   const bool grad_stage = want_grad && !stop_after_target;
   const bool chained = ch && ch->on && grad_stage && !out.partials_mode;
   const bool spec = !chained && want_grad;   // (also the Stein estimator's calls: stop_after_target)
-  bool hit = false;
-  int capturing = 0;
-  unsigned long long cap_id = 0;
-  if (spec) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamGetCaptureInfo(c->stream, &cs, &cap_id) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    capturing = cs == hipStreamCaptureStatusActive;
-    if (!capturing) cap_id = 0;
-    hit = c->pre_valid && c->pre_M == M && c->pre_rng.seed == rng.seed && c->pre_rng.idx_base == rng.idx_base &&
-          c->pre_rng.idx_ptr == rng.idx_ptr && c->pre_rng.m_offset == rng.m_offset && c->pre_capturing == capturing &&
-          c->pre_capture_id == cap_id;
-  }
-  c->pre_valid = false;
-  if (!chained) c->cur = hit ? c->pre_parity : 0;
+  const EpsLookup lk = spec ? eps_spec_lookup(c, rng, M) : EpsLookup{};
+  c->pre.clear();
+  if (!chained) c->cur = lk.hit ? c->pre.parity : 0;
   const int p = c->cur;
-  if (chained ? ch->first : !hit) {
-    c->he_n[p] = launch_eps(c, rng, M);
+  if (chained ? ch->first : !lk.hit) {
+    c->he_n[p] = launch_eps(c, rng, M);   // (kept: on this route the product kernel's riders draw eps in blocks of their own, see below)
   }
   vin.he_part = (const double *)c->he_part[p].p;
   vin.n_he_part = c->he_n[p];
   EpsJob nx{};
-  const EpsJob *next = nullptr;
-  if (chained && ch->has_next) {
-    nx.rng = ch->next_rng;
-    nx.parity = p ^ 1;
-    next = &nx;
-  } else if (spec) {   // speculate that the caller asks for estimate idx + 1 next (an SGD loop does)
-    nx.rng = rng;
-    nx.rng.idx_base = rng.idx_base + 1ull;   // (a single call: the NEXT index, whatever stride an earlier batched call left on this context)
-    nx.parity = p ^ 1;
-    next = &nx;
-  }
+  const EpsJob *next = next_eps_job(nx, rng, p, ch, chained, spec);
   const bool dense = c->target == TGT_DENSE_GAUSS;
   const bool p32 = lds_use_prod32(c, M);
   bool dinv_done = false;
@@ -136,35 +196,17 @@ static mivi_status_t run_estimate_lds(mivi_ctx *c, const void *params, const Rng
   }
   if (ch) { ch->have_prev = false; ch->first = !chained; }
   if (grad_stage) {
-    if (out.ent_kind == MIVI_ENT_STL || out.ent_kind == MIVI_ENT_STL_ZERO_GRAD) {
-      const size_t sh = (8 * (size_t)c->dP + 32 * 33) * c->esize;
-      if (sh > 160 * 1024 && !c->stl_CT.p) return fail(c, MIVI_ERR_UNSUPPORTED, "full-rank STL: d too large for the LDS-resident solve");
-      if (stl2_shape_ok(c, M)) launch_stl2(c, params, M, dinv_done);
-      else launch_fr_stl(c, params, M);
-    }
+    const mivi_status_t s = stl_term(c, params, M, out, dinv_done);
+    if (s) return s;
     vin.ld_part = (const double *)c->ld_part[p].p;   // left by the reduce kernel (the VJP kernel may already be updating C)
     vin.n_ld_part = p32 ? fr_ld_blocks(c) : lds_ld_blocks(c);
     ValueJob self{vin, out};
     launch_lds_vjp(c, params, M, out, &self, chained ? upd : nullptr);
-    if (spec) {
-      c->pre_valid = true;
-      c->pre_rng = nx.rng;
-      c->pre_M = M;
-      c->pre_parity = p ^ 1;
-      c->pre_capturing = capturing;
-      c->pre_capture_id = cap_id;
-    }
+    if (spec) eps_spec_publish(c, nx.rng, M, p ^ 1, lk);
     HIPCHK(c, hipGetLastError());
     return MIVI_OK;
   }
-  if (spec) {
-    c->pre_valid = true;
-    c->pre_rng = nx.rng;
-    c->pre_M = M;
-    c->pre_parity = p ^ 1;
-    c->pre_capturing = capturing;
-    c->pre_capture_id = cap_id;
-  }
+  if (spec) eps_spec_publish(c, nx.rng, M, p ^ 1, lk);   // (the Stein path too: its product kernel carried the draw of idx + 1 as well)
   if (c->defer_value) {   // (Stein estimator: its accumulation kernel assembles the value partials in one of its own workgroups)
     *c->defer_value = ValueJob{vin, out};
     c->value_deferred = true;
@@ -192,21 +234,11 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
   const int d = c->cfg.d, d4 = (d + 3) / 4;
   const bool chained = ch && ch->on && hetero_ok(c, want_grad, ch) && !out.partials_mode;
   // single calls on the MFMA full-rank path: did the previous call's VJP kernel already generate this estimate's eps?
+  // (not the Stein estimator's calls: here the draw of idx + 1 rides in the VJP kernel, which stop_after_target never launches)
   const bool spec = !chained && c->cfg.family == MIVI_FULLRANK && hetero_ok(c, want_grad) && !stop_after_target;
-  bool hit = false;
-  int capturing = 0;
-  unsigned long long cap_id = 0;
-  if (spec) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamGetCaptureInfo(c->stream, &cs, &cap_id) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    capturing = cs == hipStreamCaptureStatusActive;
-    if (!capturing) cap_id = 0;
-    hit = c->pre_valid && c->pre_M == M && c->pre_rng.seed == rng.seed && c->pre_rng.idx_base == rng.idx_base &&
-          c->pre_rng.idx_ptr == rng.idx_ptr && c->pre_rng.m_offset == rng.m_offset && c->pre_capturing == capturing &&
-          c->pre_capture_id == cap_id;
-  }
-  c->pre_valid = false;
-  if (!chained) c->cur = hit ? c->pre_parity : 0;
+  const EpsLookup lk = spec ? eps_spec_lookup(c, rng, M) : EpsLookup{};
+  c->pre.clear();
+  if (!chained) c->cur = lk.hit ? c->pre.parity : 0;
   const int p = c->cur;
   const ValueJob *prev = (chained && ch->have_prev) ? &ch->prev : nullptr;
 
@@ -223,61 +255,28 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
         vin.fn.M = M;
         vin.fn.sigma_v = c->funnel_sigma_v;
       }
-      vin.ell_part2 = (const double *)c->sc_part[p].p;
-      vin.n_ell_part2 = c->mf_nblk;
-      vin.he_part = (const double *)c->sc_part[p].p + c->mf_nblk;
-      vin.n_he_part = c->mf_nblk;
-      vin.ld_part = (const double *)c->sc_part[p].p + 2 * (size_t)c->mf_nblk;
-      vin.n_ld_part = c->mf_nblk;
+      wire_mf_partials(c, p, vin);
     } else {
       launch_sample_mf(c, params, rng, M, c->Z.p, nullptr, 0, want_grad ? nullptr : (double *)c->he_part[p].p);
       if (bij) launch_bij_forward(c, M);   // the target sees binv(z)
-      if (c->target == TGT_DENSE_GAUSS) {
-        launch_rt_from_z(c, M);
-        launch_fr_dense_target(c, M, want_grad);
-        vin.ell_part = (const double *)c->ell_part[p].p;
-        vin.n_ell_part = fr_dense_blocks(c, M);
-        if (bij) { vin.ell = c->bij_ld.p; vin.n_ell = M; }   // + logabsdetjac per sample
-      } else {
-        if (logreg_uses_mfma(c, M)) launch_rt_from_z(c, M);   // Z^T for the MFMA route
-        if ((s = eval_generic_target(c, M, want_grad))) return s;
-        vin.ell = c->ell.p;
-        vin.n_ell = M;
-      }
+      if ((s = target_on_z(c, M, want_grad, p, vin))) return s;
       if (bij) launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
       if (want_grad) {
         launch_mf_main(c, params, rng, M, 1, c->W.p, vin, out);
-        vin.ell_part2 = (const double *)c->sc_part[p].p;   // zeros for the non-fused target; he / logdet live here
-        vin.n_ell_part2 = c->mf_nblk;
-        vin.he_part = (const double *)c->sc_part[p].p + c->mf_nblk;
-        vin.n_he_part = c->mf_nblk;
-        vin.ld_part = (const double *)c->sc_part[p].p + 2 * (size_t)c->mf_nblk;
-        vin.n_ld_part = c->mf_nblk;
+        wire_mf_partials(c, p, vin);   // (ell_part2: zeros for the non-fused target; he / logdet live here)
       } else {
         vin.he_part = (const double *)c->he_part[p].p;
         vin.n_he_part = ((d4 + 255) / 256) * M;
       }
     }
   } else {
-    if (chained ? ch->first : !hit) launch_eps(c, rng, M);   // otherwise generated inside the previous VJP kernel
+    if (chained ? ch->first : !lk.hit) launch_eps(c, rng, M);   // otherwise generated inside the previous VJP kernel
     vin.he_part = (const double *)c->he_part[p].p;
-    vin.n_he_part = eps_blocks(c, M);
+    vin.n_he_part = eps_blocks(c, M);   // (not he_n: on this route every producer of eps leaves eps_blocks partials)
     if (c->bij_on) {   // Stacked bijector: explicit samples, transformed in place around whatever target is set
       launch_fr_sample(c, params, M, TGT_NONE, c->Z.p);
       launch_bij_forward(c, M);
-      if (c->target == TGT_DENSE_GAUSS) {
-        launch_rt_from_z(c, M);
-        launch_fr_dense_target(c, M, want_grad);
-        vin.ell_part = (const double *)c->ell_part[p].p;
-        vin.n_ell_part = fr_dense_blocks(c, M);
-        vin.ell = c->bij_ld.p;
-        vin.n_ell = M;
-      } else {
-        if (logreg_uses_mfma(c, M)) launch_rt_from_z(c, M);
-        if ((s = eval_generic_target(c, M, want_grad))) return s;
-        vin.ell = c->ell.p;
-        vin.n_ell = M;
-      }
+      if ((s = target_on_z(c, M, want_grad, p, vin))) return s;
       launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
     } else if (c->target == TGT_DIAG_GAUSS) {
       launch_fr_sample(c, params, M, TGT_DIAG_GAUSS, nullptr, prev);
@@ -296,33 +295,13 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
       vin.n_ell = M;
     }
     if (want_grad && !stop_after_target) {   // (the Stein estimator stops here: eps, W = grad log pi and the ell sums are ready)
-      if (out.ent_kind == MIVI_ENT_STL || out.ent_kind == MIVI_ENT_STL_ZERO_GRAD) {
-        const size_t sh = (8 * (size_t)c->dP + 32 * 33) * c->esize;
-        if (sh > 160 * 1024 && !c->stl_CT.p) return fail(c, MIVI_ERR_UNSUPPORTED, "full-rank STL: d too large for the LDS-resident solve");
-        if (stl2_shape_ok(c, M)) launch_stl2(c, params, M);
-        else launch_fr_stl(c, params, M);
-      }
+      if ((s = stl_term(c, params, M, out, false))) return s;
       EpsJob nx{};
-      const EpsJob *next = nullptr;
-      if (chained && ch->has_next) {
-        nx.rng = ch->next_rng;
-        nx.parity = p ^ 1;
-        next = &nx;
-      } else if (spec) {   // speculate that the caller asks for estimate idx + 1 next (an SGD loop does)
-        nx.rng = rng;
-        nx.rng.idx_base = rng.idx_base + 1ull;   // (a single call: the NEXT index, whatever stride an earlier batched call left on this context)
-        nx.parity = p ^ 1;
-        next = &nx;
-      }
+      const EpsJob *next = next_eps_job(nx, rng, p, ch, chained, spec);
       if (spec) {          // this estimate's value rides in the same kernel: no separate value launch
         ValueJob self{vin, out};
         launch_fr_vjp(c, params, M, out, next, &self);
-        c->pre_valid = true;
-        c->pre_rng = nx.rng;
-        c->pre_M = M;
-        c->pre_parity = p ^ 1;
-        c->pre_capturing = capturing;
-        c->pre_capture_id = cap_id;
+        eps_spec_publish(c, nx.rng, M, p ^ 1, lk);
         if (ch) { ch->have_prev = false; ch->first = true; }
         HIPCHK(c, hipGetLastError());
         return MIVI_OK;
@@ -381,8 +360,7 @@ mivi_status_t mivi_sample(mivi_ctx_t *c, const void *params, uint64_t idx, void 
   if (c->cfg.family == MIVI_MEANFIELD) {
     launch_sample_mf(c, params, rng_of(c, idx), M, Z, eps, d, nullptr);
   } else {
-    c->cur = 0;
-    c->pre_valid = false;
+    eps_spec_drop(c);
     launch_eps(c, rng_of(c, idx), M);
     launch_fr_sample(c, params, M, TGT_NONE, Z);
     if (eps)
@@ -416,17 +394,28 @@ mivi_status_t read_status(mivi_ctx *c) {
   return MIVI_OK;
 }
 
+// ---- the _host boundary: parameters up into tmp_params, the device entry, results down out of tmp_out, wait ----
+mivi_status_t stage_params(mivi_ctx *c, const void *params_h) {
+  HIPCHK(c, hipMemcpyAsync(c->tmp_params.p, params_h, (size_t)mivi_params_len(c) * c->esize, hipMemcpyHostToDevice, c->stream));
+  return MIVI_OK;
+}
+
+mivi_status_t fetch_results(mivi_ctx *c, std::initializer_list<HostCopy> res, bool with_status) {
+  for (const HostCopy &r : res)
+    if (r.host) HIPCHK(c, hipMemcpyAsync(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost, c->stream));
+  if (with_status) return read_status(c);   // waits; MIVI_ERR_NONPOSITIVE_SCALE / MIVI_ERR_NONFINITE
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MIVI_OK;
+}
+
 mivi_status_t mivi_estimate_gradient_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, void *value_h, void *grad_h) {
   if (!c || !params_h || !value_h || !grad_h) return MIVI_ERR_BAD_ARG;
   (void)hipSetDevice(c->cfg.device);
-  const size_t plen = (size_t)mivi_params_len(c), es = c->esize;
-  HIPCHK(c, hipMemcpyAsync(c->tmp_params.p, params_h, plen * es, hipMemcpyHostToDevice, c->stream));
-  char *o = (char *)c->tmp_out.p;
-  mivi_status_t s = run_estimate(c, c->tmp_params.p, rng_of(c, idx), c->cfg.n_mc, 1, final_out(c, o, o + 16));
+  mivi_status_t s = stage_params(c, params_h);
   if (s) return s;
-  HIPCHK(c, hipMemcpyAsync(value_h, o, es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(grad_h, o + 16, plen * es, hipMemcpyDeviceToHost, c->stream));
-  return read_status(c);
+  char *o = (char *)c->tmp_out.p;
+  if ((s = run_estimate(c, c->tmp_params.p, rng_of(c, idx), c->cfg.n_mc, 1, final_out(c, o, o + 16)))) return s;
+  return fetch_results(c, {{value_h, o, c->esize}, {grad_h, o + 16, (size_t)mivi_params_len(c) * c->esize}}, true);
 }
 
 mivi_status_t mivi_estimate_partials(mivi_ctx_t *c, const void *params, uint64_t idx, void *partials) {

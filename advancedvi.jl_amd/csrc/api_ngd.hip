@@ -14,6 +14,17 @@ static mivi_status_t ngd_update(mivi_ctx *c, void *params, const void *grad, con
   return MIVI_OK;
 }
 
+// c->ngd_est, sized: [scalar (16 bytes: entropy or logpi_avg); grad (d); hess (d x d), 16-byte aligned behind grad]
+struct NgdEst { char *scalar, *grad, *hess; };
+static mivi_status_t ngd_est(mivi_ctx *c, NgdEst *e) {
+  const size_t es = c->esize, d = (size_t)c->cfg.d, goff = (d * es + 15) / 16 * 16;
+  const mivi_status_t s = ensure(c, c->ngd_est, 16 + goff + d * d * es, false);
+  if (s) return s;
+  char *b = (char *)c->ngd_est.p;
+  *e = NgdEst{b, b + 16, b + 16 + goff};
+  return MIVI_OK;
+}
+
 extern "C" {
 
 mivi_status_t mivi_sqrt_ngd_update(mivi_ctx_t *c, void *params, const void *grad, const void *hess, double stepsize, void *entropy) {
@@ -29,17 +40,14 @@ mivi_status_t mivi_sqrt_ngd_update_host(mivi_ctx_t *c, void *params_h, const voi
   if (c->cfg.family != MIVI_FULLRANK)
     return fail(c, MIVI_ERR_UNSUPPORTED, "sqrt_ngd_update takes a triangular scale (full-rank family)");
   (void)hipSetDevice(c->cfg.device);
-  const size_t plen = (size_t)mivi_params_len(c), es = c->esize, d = (size_t)c->cfg.d, goff = (d * es + 15) / 16 * 16;   // hess 16-byte aligned behind grad
+  const size_t es = c->esize, d = (size_t)c->cfg.d;
+  NgdEst e;   // (its scalar: the entropy)
   mivi_status_t s;
-  if ((s = ensure(c, c->ngd_est, 16 + goff + d * d * es, false))) return s;
-  char *e = (char *)c->ngd_est.p;   // [entropy (16 bytes); grad; hess]
-  HIPCHK(c, hipMemcpyAsync(c->tmp_params.p, params_h, plen * es, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(e + 16, grad_h, d * es, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(e + 16 + goff, hess_h, d * d * es, hipMemcpyHostToDevice, c->stream));
-  if ((s = ngd_update(c, c->tmp_params.p, e + 16, e + 16 + goff, stepsize, nullptr, e, nullptr))) return s;
-  HIPCHK(c, hipMemcpyAsync(params_h, c->tmp_params.p, plen * es, hipMemcpyDeviceToHost, c->stream));
-  if (entropy_h) HIPCHK(c, hipMemcpyAsync(entropy_h, e, es, hipMemcpyDeviceToHost, c->stream));
-  return read_status(c);   // waits; MIVI_ERR_NONPOSITIVE_SCALE / MIVI_ERR_NONFINITE
+  if ((s = ngd_est(c, &e)) || (s = stage_params(c, params_h))) return s;
+  HIPCHK(c, hipMemcpyAsync(e.grad, grad_h, d * es, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(e.hess, hess_h, d * d * es, hipMemcpyHostToDevice, c->stream));
+  if ((s = ngd_update(c, c->tmp_params.p, e.grad, e.hess, stepsize, nullptr, e.scalar, nullptr))) return s;
+  return fetch_results(c, {{params_h, c->tmp_params.p, (size_t)mivi_params_len(c) * es}, {entropy_h, e.scalar, es}}, true);
 }
 
 mivi_status_t mivi_sqrt_ngd_steps(mivi_ctx_t *c, void *params, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
@@ -51,17 +59,16 @@ mivi_status_t mivi_sqrt_ngd_steps(mivi_ctx_t *c, void *params, uint64_t idx0, in
     return fail(c, MIVI_ERR_UNSUPPORTED, "sqrt_ngd_steps: a sharded context is not supported (the update needs the whole estimate)");
   if (c->target == TGT_NONE) return fail(c, MIVI_ERR_NO_TARGET, "no target set");
   (void)hipSetDevice(c->cfg.device);
-  const size_t es = c->esize, d = (size_t)c->cfg.d, goff = (d * es + 15) / 16 * 16;   // hess 16-byte aligned behind grad
+  NgdEst e;   // (its scalar: logpi_avg)
   mivi_status_t s;
-  if ((s = ensure(c, c->ngd_est, 16 + goff + d * d * es, false))) return s;
-  char *e = (char *)c->ngd_est.p;   // [logpi_avg (16 bytes); grad; hess]
+  if ((s = ngd_est(c, &e))) return s;
   for (int32_t t = 0; t < count; ++t) {
     // (the estimator entries refuse what they cannot do -- no Hessian / a Stacked bijector for the second-order branch, d beyond the solve --
     // before they launch anything, so a refused call leaves the parameters untouched)
-    s = second_order ? mivi_gauss_expected_grad_hess2(c, params, idx0 + (uint64_t)t, n_samples, e, e + 16, e + 16 + goff)
-                     : mivi_gauss_expected_grad_hess(c, params, idx0 + (uint64_t)t, n_samples, e, e + 16, e + 16 + goff);
+    s = second_order ? mivi_gauss_expected_grad_hess2(c, params, idx0 + (uint64_t)t, n_samples, e.scalar, e.grad, e.hess)
+                     : mivi_gauss_expected_grad_hess(c, params, idx0 + (uint64_t)t, n_samples, e.scalar, e.grad, e.hess);
     if (s) return s;
-    if ((s = ngd_update(c, params, e + 16, e + 16 + goff, stepsize, e, nullptr, elbo ? (char *)elbo + (size_t)t * es : nullptr))) return s;
+    if ((s = ngd_update(c, params, e.grad, e.hess, stepsize, e.scalar, nullptr, elbo ? (char *)elbo + (size_t)t * c->esize : nullptr))) return s;
   }
   return MIVI_OK;
 }

@@ -2,6 +2,33 @@
 // gaussian_expectation_gradient_and_hessian! (src/algorithms/gauss_expected_grad_hess.jl).
 #include "api_common.h"
 
+// ---- chunk bookkeeping: c->acc (f64) collects what the chunks of samples leave, element type by the context's dtype ----
+// acc = (first ? 0 : acc) + w * src, for the leading scalars of a chunk's result
+static void acc_chunk_value(mivi_ctx *c, const void *src, double w, int first) {
+  if (c->cfg.dtype == MIVI_F32)
+    hipLaunchKernelGGL(k_acc_value_f32, dim3(1), dim3(1), 0, c->stream, (double *)c->acc.p, (const float *)src, w, first);
+  else
+    hipLaunchKernelGGL(k_acc_value_f64, dim3(1), dim3(1), 0, c->stream, (double *)c->acc.p, (const double *)src, w, first);
+}
+
+static void store_acc_value(mivi_ctx *c, void *dst) {
+  if (c->cfg.dtype == MIVI_F32)
+    hipLaunchKernelGGL(k_store_value_f32, dim3(1), dim3(1), 0, c->stream, (float *)dst, (const double *)c->acc.p);
+  else
+    hipLaunchKernelGGL(k_store_value_f64, dim3(1), dim3(1), 0, c->stream, (double *)dst, (const double *)c->acc.p);
+}
+
+// a chunk of Mc samples leaves only its two scalar partials [sum ell, sum 0.5 eps^2] in `part`
+static OutArgs chunk_partials_out(mivi_ctx *c, void *part, int Mc) {
+  OutArgs o = final_out(c, nullptr, nullptr);
+  o.partials = part;
+  o.partials_mode = 1;
+  o.scalars_off = 0;
+  o.ent_kind = MIVI_ENT_CLOSED_FORM;
+  o.M_total = Mc;
+  return o;
+}
+
 mivi_status_t mivi_estimate_objective(mivi_ctx_t *c, const void *params, uint64_t idx, int32_t n_samples, int32_t entropy,
                                       void *value) {
   if (!c || !params || !value) return MIVI_ERR_BAD_ARG;
@@ -50,16 +77,9 @@ mivi_status_t mivi_estimate_objective(mivi_ctx_t *c, const void *params, uint64_
     r.m_offset += off;
     mivi_status_t s = run_estimate(c, params, r, Mc, 0, o);
     if (s) return s;
-    const double w = (double)Mc / (double)n_samples;
-    if (c->cfg.dtype == MIVI_F32)
-      hipLaunchKernelGGL(k_acc_value_f32, dim3(1), dim3(1), 0, c->stream, (double *)c->acc.p, (const float *)tmpv, w, first);
-    else
-      hipLaunchKernelGGL(k_acc_value_f64, dim3(1), dim3(1), 0, c->stream, (double *)c->acc.p, (const double *)tmpv, w, first);
+    acc_chunk_value(c, tmpv, (double)Mc / (double)n_samples, first);
   }
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_store_value_f32, dim3(1), dim3(1), 0, c->stream, (float *)value, (const double *)c->acc.p);
-  else
-    hipLaunchKernelGGL(k_store_value_f64, dim3(1), dim3(1), 0, c->stream, (double *)value, (const double *)c->acc.p);
+  store_acc_value(c, value);
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
 }
@@ -68,13 +88,12 @@ mivi_status_t mivi_estimate_objective_host(mivi_ctx_t *c, const void *params_h, 
                                            int32_t entropy, void *value_h) {
   if (!c || !params_h || !value_h) return MIVI_ERR_BAD_ARG;
   (void)hipSetDevice(c->cfg.device);
-  const size_t plen = (size_t)mivi_params_len(c), es = c->esize;
-  HIPCHK(c, hipMemcpyAsync(c->tmp_params.p, params_h, plen * es, hipMemcpyHostToDevice, c->stream));
-  char *o = (char *)c->tmp_out.p + 16;
-  mivi_status_t s = mivi_estimate_objective(c, c->tmp_params.p, idx, n_samples, entropy, o);
+  mivi_status_t s = stage_params(c, params_h);
   if (s) return s;
-  HIPCHK(c, hipMemcpyAsync(value_h, o, es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  char *o = (char *)c->tmp_out.p + 16;
+  if ((s = mivi_estimate_objective(c, c->tmp_params.p, idx, n_samples, entropy, o))) return s;
+  if ((s = fetch_results(c, {{value_h, o, c->esize}}, false))) return s;
+  // its own status read, not read_status: word 0 only, and only the non-positive scale is an error
   int st = 0;
   HIPCHK(c, hipMemcpy(&st, c->status.p, sizeof(int), hipMemcpyDeviceToHost));
   if (st) HIPCHK(c, hipMemset(c->status.p, 0, sizeof(int)));
@@ -95,7 +114,7 @@ mivi_status_t mivi_gauss_expected_grad_hess(mivi_ctx_t *c, const void *params, u
   (void)hipSetDevice(c->cfg.device);
   const int d = c->cfg.d, dP = round_up(d, 64);
   const size_t es = c->esize;
-  if ((8 * (size_t)dP + 32 * 33) * es > 160 * 1024 && ((size_t)dP * 16 + 8 * 8 * 64) * es > 160 * 1024)
+  if (!stl_lds_fits(c, dP) && !stl16_lds_fits(c, dP))
     return fail(c, MIVI_ERR_UNSUPPORTED, "gauss_expected_grad_hess: d too large for the LDS-resident solve");
   mivi_status_t s;
   if ((s = ensure(c, c->stein_A, (size_t)dP * dP * es, true)) || (s = ensure(c, c->stein_g, (size_t)(d + 8) * sizeof(double), true)) ||
@@ -109,12 +128,7 @@ mivi_status_t mivi_gauss_expected_grad_hess(mivi_ctx_t *c, const void *params, u
   char *part = (char *)c->tmp_out.p;   // [sum ell, sum 0.5 eps^2] of a chunk
   for (int off = 0, first = 1; off < n_samples; off += CH, first = 0) {
     const int Mc = n_samples - off < CH ? n_samples - off : CH;
-    OutArgs o = final_out(c, nullptr, nullptr);
-    o.partials = part;
-    o.partials_mode = 1;
-    o.scalars_off = 0;
-    o.ent_kind = MIVI_ENT_CLOSED_FORM;
-    o.M_total = Mc;
+    const OutArgs o = chunk_partials_out(c, part, Mc);
     RngArgs r = rng_of(c, idx);
     r.m_offset += off;
     c->want_stl_pack = stl2 && first;   // the solve's parameter-only preparation rides in the first chunk's sampling kernel
@@ -132,12 +146,8 @@ mivi_status_t mivi_gauss_expected_grad_hess(mivi_ctx_t *c, const void *params, u
     const bool fused_tail = c->value_deferred;
     c->value_deferred = false;
     if (first) pack_done = c->stl_pack_done;
-    if (single_chunk) {
-      // (its partial is read by the finishing kernel directly: no accumulation launch)
-    } else if (c->cfg.dtype == MIVI_F32)
-      hipLaunchKernelGGL(k_acc_value_f32, dim3(1), dim3(1), 0, c->stream, (double *)c->acc.p, (const float *)part, 1.0, first);
-    else
-      hipLaunchKernelGGL(k_acc_value_f64, dim3(1), dim3(1), 0, c->stream, (double *)c->acc.p, (const double *)part, 1.0, first);
+    // (a single chunk's partial is read by the finishing kernel directly: no accumulation launch)
+    if (!single_chunk) acc_chunk_value(c, part, 1.0, first);
     const bool last = off + CH >= n_samples;
     const double scale = last ? 1.0 / (double)n_samples : 1.0;
     if (st2) {
@@ -197,8 +207,7 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, 
       if ((s = ensure_work(c, Mc))) return s;
       RngArgs r = rng_of(c, idx);
       r.m_offset += off;
-      c->cur = 0;
-      c->pre_valid = false;
+      eps_spec_drop(c);
       launch_eps(c, r, Mc);
       launch_fr_sample(c, params, Mc, TGT_NONE, c->Z.p);
       c->h_Z.resize((size_t)d * Mc * es);
@@ -238,21 +247,11 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, 
   char *part = (char *)c->tmp_out.p;   // [sum ell, sum 0.5 eps^2] of a chunk
   for (int off = 0, first = 1; off < n_samples; off += CH, first = 0) {
     const int Mc = n_samples - off < CH ? n_samples - off : CH;
-    OutArgs o = final_out(c, nullptr, nullptr);
-    o.partials = part;
-    o.partials_mode = 1;
-    o.scalars_off = 0;
-    o.ent_kind = MIVI_ENT_CLOSED_FORM;
-    o.M_total = Mc;
+    const OutArgs o = chunk_partials_out(c, part, Mc);
     RngArgs r = rng_of(c, idx);
     r.m_offset += off;
     if ((s = run_estimate(c, params, r, Mc, 1, o, nullptr, nullptr, true))) return s;   // sampling + target: W = grad logpi(z), the chunk's value partials
-    if (!single_chunk) {
-      if (c->cfg.dtype == MIVI_F32)
-        hipLaunchKernelGGL(k_acc_value_f32, dim3(1), dim3(1), 0, c->stream, (double *)c->acc.p, (const float *)part, 1.0, first);
-      else
-        hipLaunchKernelGGL(k_acc_value_f64, dim3(1), dim3(1), 0, c->stream, (double *)c->acc.p, (const double *)part, 1.0, first);
-    }
+    if (!single_chunk) acc_chunk_value(c, part, 1.0, first);
     launch_stein_gsum(c, Mc, (double *)c->stein_g.p, first);
     if (sampled) target_hess2_accumulate(c, Mc);   // (the chunk's samples are still in c->Z)
   }
@@ -263,40 +262,29 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, 
   return MIVI_OK;
 }
 
-mivi_status_t mivi_gauss_expected_grad_hess_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, int32_t n_samples,
-                                                 void *logpi_avg_h, void *grad_h, void *hess_h) {
+// the two _host forms of gaussian_expectation_gradient_and_hessian!: one body, `entry` is the device entry
+using GradHessEntry = mivi_status_t (*)(mivi_ctx_t *, const void *, uint64_t, int32_t, void *, void *, void *);
+static mivi_status_t grad_hess_host(mivi_ctx *c, GradHessEntry entry, const void *params_h, uint64_t idx, int32_t n_samples, void *logpi_avg_h,
+                                    void *grad_h, void *hess_h) {
   if (!c || !params_h || !logpi_avg_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
   if (c->cfg.family != MIVI_FULLRANK)
     return fail(c, MIVI_ERR_UNSUPPORTED, "gauss_expected_grad_hess takes a triangular scale (full-rank family)");
   (void)hipSetDevice(c->cfg.device);
-  const size_t plen = (size_t)mivi_params_len(c), es = c->esize, d = (size_t)c->cfg.d;
-  HIPCHK(c, hipMemcpyAsync(c->tmp_params.p, params_h, plen * es, hipMemcpyHostToDevice, c->stream));
+  const size_t es = c->esize, d = (size_t)c->cfg.d;
+  mivi_status_t s = stage_params(c, params_h);
+  if (s) return s;
   // the chunk partials use tmp_out[0..1]; results go behind them: [.., logpi (slot 2), grad (d), hess (d*d)] <= params_len + 16
   char *o = (char *)c->tmp_out.p + 2 * 8;
-  mivi_status_t s = mivi_gauss_expected_grad_hess(c, c->tmp_params.p, idx, n_samples, o, o + 8, o + 8 + d * es);
-  if (s) return s;
-  HIPCHK(c, hipMemcpyAsync(logpi_avg_h, o, es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(grad_h, o + 8, d * es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(hess_h, o + 8 + d * es, d * d * es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MIVI_OK;
+  if ((s = entry(c, c->tmp_params.p, idx, n_samples, o, o + 8, o + 8 + d * es))) return s;
+  return fetch_results(c, {{logpi_avg_h, o, es}, {grad_h, o + 8, d * es}, {hess_h, o + 8 + d * es, d * d * es}}, false);
+}
+
+mivi_status_t mivi_gauss_expected_grad_hess_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, int32_t n_samples,
+                                                 void *logpi_avg_h, void *grad_h, void *hess_h) {
+  return grad_hess_host(c, mivi_gauss_expected_grad_hess, params_h, idx, n_samples, logpi_avg_h, grad_h, hess_h);
 }
 
 mivi_status_t mivi_gauss_expected_grad_hess2_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, int32_t n_samples,
                                                   void *logpi_avg_h, void *grad_h, void *hess_h) {
-  if (!c || !params_h || !logpi_avg_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
-  if (c->cfg.family != MIVI_FULLRANK)
-    return fail(c, MIVI_ERR_UNSUPPORTED, "gauss_expected_grad_hess takes a triangular scale (full-rank family)");
-  (void)hipSetDevice(c->cfg.device);
-  const size_t plen = (size_t)mivi_params_len(c), es = c->esize, d = (size_t)c->cfg.d;
-  HIPCHK(c, hipMemcpyAsync(c->tmp_params.p, params_h, plen * es, hipMemcpyHostToDevice, c->stream));
-  char *o = (char *)c->tmp_out.p + 2 * 8;   // (behind the chunk partials, as the first-order _host entry)
-  mivi_status_t s = mivi_gauss_expected_grad_hess2(c, c->tmp_params.p, idx, n_samples, o, o + 8, o + 8 + d * es);
-  if (s) return s;
-  HIPCHK(c, hipMemcpyAsync(logpi_avg_h, o, es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(grad_h, o + 8, d * es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(hess_h, o + 8 + d * es, d * d * es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MIVI_OK;
+  return grad_hess_host(c, mivi_gauss_expected_grad_hess2, params_h, idx, n_samples, logpi_avg_h, grad_h, hess_h);
 }
-

@@ -8,10 +8,10 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
   char *o = (char *)c->tmp_out.p;
   OutArgs out = final_out(c, o, o + 16);
   RngArgs rng = rng_of(c, 0);
-  c->pre_valid = false;
+  c->pre.clear();
   mivi_status_t s = run_estimate(c, params, rng, M, 1, out);   // warm + populate eps / W / partial buffers
   if (s) return s;
-  if (which != 0) c->pre_valid = false;                        // the stage launches below work on parity 0
+  if (which != 0) c->pre.clear();                              // the stage launches below work on parity 0
   out.M_local = M;
   ValueIn vin{};
   vin.ell_const = c->t_const;
@@ -148,7 +148,7 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  if (which != 0) c->pre_valid = false;
+  if (which != 0) c->pre.clear();
   if (s) return s;
   *ms_out = (double)ms / reps;
   return MIVI_OK;

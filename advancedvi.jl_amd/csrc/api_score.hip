@@ -30,7 +30,7 @@ static mivi_status_t run_score_estimate(mivi_ctx *c, const void *params, uint64_
   const bool stl2 = full && stl2_shape_ok(c, M);
   if (full) {
     const int dP = c->dP;
-    if ((8 * (size_t)dP + 32 * 33) * es > 160 * 1024 && ((size_t)dP * 16 + 8 * 8 * 64) * es > 160 * 1024)
+    if (!stl_lds_fits(c, dP) && !stl16_lds_fits(c, dP))
       return fail(c, MIVI_ERR_UNSUPPORTED, "score gradient: d too large for the LDS-resident solve");
     // the solve's operands, as ensure_work sizes them for the sticking-the-landing estimators (no-ops on such a context)
     if ((s = ensure(c, c->stl_CT, (size_t)dP * dP * es, true)) || (s = ensure(c, c->stl_Dinv, (size_t)((d + 63) / 64) * 4096 * es, false))) return s;
@@ -44,8 +44,7 @@ static mivi_status_t run_score_estimate(mivi_ctx *c, const void *params, uint64_
     c->sg_cap = c->cap_M;
   }
   const RngArgs rng = rng_of(c, idx);
-  c->cur = 0;            // (as mivi_sample: this estimate's draw goes to parity 0 and no speculative draw survives it)
-  c->pre_valid = false;
+  eps_spec_drop(c);   // (as mivi_sample)
   if (full) {
     c->he_n[0] = launch_eps(c, rng, M);
     launch_fr_sample(c, params, M, TGT_NONE, c->Z.p);
@@ -54,14 +53,9 @@ static mivi_status_t run_score_estimate(mivi_ctx *c, const void *params, uint64_
   }
   if (c->bij_on) launch_bij_forward(c, M);   // the target sees binv(z); its logabsdetjac per sample joins log pi in k_sg_stats
   const bool dense = c->target == TGT_DENSE_GAUSS;
-  if (dense) {
-    launch_rt_from_z(c, M);
-    launch_fr_dense_target(c, M, 1);        // W = G = -P R
-    launch_sg_dense_ell(c, M);              // ell_m = r_m' g_m / 2
-  } else {
-    if (logreg_uses_mfma(c, M)) launch_rt_from_z(c, M);   // Z^T for the matrix-core route
-    if ((s = eval_generic_target(c, M, 0))) return s;
-  }
+  ValueIn unused{};   // (this estimator reads the per-sample values themselves -- c->ell, or sg_d for the dense target -- not their partials)
+  if ((s = target_on_z(c, M, dense ? 1 : 0, 0, unused))) return s;   // dense: W = G = -P R is what it has; everything else: values only
+  if (dense) launch_sg_dense_ell(c, M);   // ell_m = r_m' g_m / 2
   launch_sg_norms(c, rng, M);
   launch_sg_stats(c, params, M, dense, value, elbo);
   if (full) {
@@ -89,13 +83,10 @@ mivi_status_t mivi_estimate_score_gradient(mivi_ctx_t *c, const void *params, ui
 mivi_status_t mivi_estimate_score_gradient_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, void *value_h, void *elbo_h, void *grad_h) {
   if (!c || !params_h || !value_h || !grad_h) return MIVI_ERR_BAD_ARG;
   (void)hipSetDevice(c->cfg.device);
-  const size_t plen = (size_t)mivi_params_len(c), es = c->esize;
-  HIPCHK(c, hipMemcpyAsync(c->tmp_params.p, params_h, plen * es, hipMemcpyHostToDevice, c->stream));
-  char *o = (char *)c->tmp_out.p;   // [value | elbo | gradient]
-  mivi_status_t s = run_score_estimate(c, c->tmp_params.p, idx, o, o + 8, o + 16);
+  const size_t es = c->esize;
+  mivi_status_t s = stage_params(c, params_h);
   if (s) return s;
-  HIPCHK(c, hipMemcpyAsync(value_h, o, es, hipMemcpyDeviceToHost, c->stream));
-  if (elbo_h) HIPCHK(c, hipMemcpyAsync(elbo_h, o + 8, es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(grad_h, o + 16, plen * es, hipMemcpyDeviceToHost, c->stream));
-  return read_status(c);
+  char *o = (char *)c->tmp_out.p;   // [value | elbo | gradient]
+  if ((s = run_score_estimate(c, c->tmp_params.p, idx, o, o + 8, o + 16))) return s;
+  return fetch_results(c, {{value_h, o, es}, {elbo_h, o + 8, es}, {grad_h, o + 16, (size_t)mivi_params_len(c) * es}}, true);
 }

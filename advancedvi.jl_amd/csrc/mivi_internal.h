@@ -184,6 +184,17 @@ struct EpsJob {        // eps generation for the next estimate
   RngArgs rng;
   int parity;
 };
+// speculative eps prefetch across single calls: the VJP kernel of estimate (seed, idx) also generates eps of
+// (seed, idx + 1) into the other parity; a following call for exactly that estimate skips its eps kernel.
+// Looked up, published and dropped by api_estimate.hip (eps_spec_*); everyone else may only clear() it.
+struct EpsSpec {
+  bool valid = false;
+  RngArgs rng{};
+  int M = 0, parity = 0;
+  int capturing = 0;
+  unsigned long long capture_id = 0;
+  void clear() { valid = false; }
+};
 
 template <typename T>
 struct ColTargetArgs {  // standalone per-column targets: Z -> (ell, G)
@@ -373,13 +384,7 @@ struct mivi_ctx {
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
   const uint64_t *idx_src = nullptr;   // mivi_set_index_source
-  // speculative eps prefetch across single calls: the VJP kernel of estimate (seed, idx) also generates eps of
-  // (seed, idx + 1) into the other parity; a following call for exactly that estimate skips its eps kernel
-  bool pre_valid = false;
-  mivi::RngArgs pre_rng{};
-  int pre_M = 0, pre_parity = 0;
-  int pre_capturing = 0;
-  unsigned long long pre_capture_id = 0;
+  mivi::EpsSpec pre;   // the eps speculation across single calls
   long long *dbg = nullptr;   // timeline buffer supplied through mivi_debug_timeline (tools only)
   int dP = 0, MP = 0;
 
