@@ -192,7 +192,7 @@ static bool fb_stl_on() {   // MIVI_FB_STL=0: the sticking-the-landing estimator
   return !off;
 }
 static bool fb_route(const mivi_ctx *c, const void *params, const void *grad_last, const void *grads_all) {
-  const bool stl = c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD;
+  const bool stl = stl_entropy(c);
   return !c->is_child && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && !c->bij_on && !c->idx_src && !c->dbg &&
          (c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS) && (!stl || (fb_stl_on() && stl2_shape_ok(c, c->cfg.d))) &&
          fb_shape_ok(c, c->cfg.n_mc) && ((!stl && c->target == TGT_DIAG_GAUSS) || fb_whole_tiles(c, c->cfg.n_mc)) &&   // (padded geometry: the diagonal target, no STL term)
@@ -258,7 +258,7 @@ static mivi_status_t fb_batch(mivi_ctx *c, const void *params, uint64_t idx0, in
     }
   }
   const bool values_only = obj_ent >= 0 || (!grads_all && !grad_last);
-  const bool stl = !values_only && (c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD);   // (a value needs no gradient term)
+  const bool stl = !values_only && stl_entropy(c);   // (a value needs no gradient term)
   if (stl) {
     // W += C^-T eps: inside a call the parameters are fixed, so C^-T is formed ONCE -- the solve kernels (kernels_stl.hip) on the identity's d
     // columns -- and the term is one more triangular product per lane (k_fb_prod<FB_STL_U>)
@@ -373,7 +373,7 @@ mivi_status_t mivi_profile_batch(mivi_ctx_t *c, const void *params, int32_t lane
   fs.rng = rng_of(c, 1);
   fs.grads = c->fb.grads.p; fs.grad_stride = (long long)mivi_params_len(c); fs.values = c->fb.values.p; fs.value_stride = 1; fs.lane_last = -1;
   fs.dense = c->target == TGT_DENSE_GAUSS ? 1 : 0;
-  fs.stl = (c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD) ? 1 : 0;
+  fs.stl = stl_entropy(c) ? 1 : 0;
   us_out[3] = us_out[4] = 0.0;
   hipEvent_t e0, e1;
   HIPCHK(c, hipEventCreate(&e0));
@@ -418,10 +418,12 @@ mivi_status_t mivi_estimate_gradient_each(mivi_ctx_t *c, const void *params, uin
   return s;
 }
 
-mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64_t idx0, int32_t count, void *value, void *grad) {
-  if (!c || !params || !value || !grad || count <= 0) return MIVI_ERR_BAD_ARG;
-  (void)hipSetDevice(c->cfg.device);
-  if (count >= 2 && fb_route(c, params, grad, nullptr)) return fb_batch(c, params, idx0, count, value, grad, nullptr, nullptr);
+// How mivi_estimate_gradient_n deals a batch that the engine does not take onto contexts (it only reads the context).
+struct LanePlan {
+  int lanes = 1;        // contexts: 1 = a single chain on the context itself
+  int per_branch = 0;   // 0: forked chains, every context on a graph branch of its own; E > 0: lanes / E branches of E lane-batched contexts
+};
+static LanePlan lane_plan(const mivi_ctx *c, const void *params, const void *grad, int count) {
   // Several interleaved chains pay when an estimate is a short chain of latency-bound launches (the second-generation full-rank
   // kernels at the BASELINE sizes: two launches of 6-8 us that leave most CUs idle half of the time).  One chain otherwise.
   int lanes = 1;
@@ -436,11 +438,11 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
   // short batch (4 contexts, one branch: isolated 20-estimate calls 10.6 -> 9.7 us per estimate), two branches of four from twelve estimates on
   // (since the lane-batched launches are kernels of their own -- k_fr_prod32q, k_fr_vjp32s: one product + one VJP workgroup fit a CU -- the second
   // branch pays for 20-estimate calls too: 9.0 -> 8.1 us; 100-estimate calls back to back 7.0 us; 8, 12 and 16 contexts agree there).
-  // MIVI_LANE_BATCH=0 keeps every context on a branch of its own (A/B reference; the STL estimators always do); MIVI_CHAINS = contexts.
+  // MIVI_LANE_BATCH=0 keeps every context on a branch of its own (A/B reference; the STL estimators do where their solve is not the
+  // second-generation one); MIVI_CHAINS = contexts.
   static const int lane_env = getenv("MIVI_LANE_BATCH") ? atoi(getenv("MIVI_LANE_BATCH")) : -1;
-  const bool stl_ent = c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD;
   int lane_e = 0;   // contexts per branch (0: one each)
-  if (lanes > 1 && (!stl_ent || stl2_shape_ok(c, c->cfg.n_mc)) && lds_use_prod32(c, c->cfg.n_mc) && lds_bf16x3() && ((uintptr_t)params & 15) == 0 &&
+  if (lanes > 1 && (!stl_entropy(c) || stl2_shape_ok(c, c->cfg.n_mc)) && lds_use_prod32(c, c->cfg.n_mc) && lds_bf16x3() && ((uintptr_t)params & 15) == 0 &&
       ((uintptr_t)grad & 15) == 0 && lane_env != 0) {
     lane_e = lane_env > 0 ? (lane_env > 4 ? 4 : lane_env) : 4;
     lanes = count < 12 ? 4 : 8;   // (isolated batches at the north star, 4 vs 8 contexts, us per estimate: 8: 10.8 / 10.4, 10: 11.0 / 11.5, 12: 9.9 / 9.4, 20: 9.1 / 8.1, 48: 8.3 / 7.2)
@@ -450,6 +452,55 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
   if (lane_e <= 0 && lanes > 4) lanes = 4;          // (as graph BRANCHES: at most four -- see kMaxKids)
   if (lane_e > 0 && lanes / lane_e > 4) lanes = 4 * lane_e;
   while (lanes > 1 && count < 4 * lanes && lane_e <= 0) --lanes;   // (short batches: not worth the fork / join)
+  LanePlan plan;
+  plan.lanes = lanes;
+  plan.per_branch = lanes > 1 ? lane_e : 0;
+  return plan;
+}
+
+// Branch b of a lane-batched recording: contexts ctxs[b E .. b E + E) of `lanes` (global lane g serves estimates g, g + lanes, ... relative to
+// ONE device counter, the parent's), their launches on the stream of the branch's first context.  Its product kernels are ONE launch per
+// step (blockIdx.y = lane), and so are its first draws, STL terms, VJP kernels and the chains' closing value kernels.  The chain that holds
+// the batch's LAST estimate writes the caller's buffers, the others their scratch.
+static mivi_status_t record_lane_branch(mivi_ctx *c, mivi_ctx *const *ctxs, int b, int E, int lanes, const void *params, int count, void *value,
+                                        void *grad) {
+  mivi_ctx *const *lane = ctxs + b * E;
+  const int q_last = (count - 1) % lanes;
+  LaneRecorder rec(E, stl_entropy(c));
+  LaneScope scope(lane, E, &rec, lane[0]->stream);
+  Chain chn[4];
+  for (int l = 0; l < E; ++l) { chn[l].on = true; chn[l].estimates_only = true; }
+  auto n_of = [&](int gl) { return (count - gl + lanes - 1) / lanes; };   // estimates of global lane gl: gl, gl + lanes, ...
+  mivi_status_t st = MIVI_OK;
+  const int steps = (count + lanes - 1) / lanes;
+  for (int i = 0; i < steps && st == MIVI_OK; ++i) {
+    int L = 0;
+    while (L < E && i < n_of(b * E + L)) ++L;
+    st = lanes_step(c, lane, rec, L, i == 0, [&](int l) {
+      const int gl = b * E + l;
+      mivi_ctx *k = lane[l];
+      RngArgs r = rng_of(k, (uint64_t)gl + (uint64_t)i * lanes);
+      r.idx_ptr = (const uint64_t *)c->d_idx.p;
+      k->cur = i & 1;
+      chn[l].has_next = (i + 1 < n_of(gl));
+      chn[l].next_rng = rng_of(k, (uint64_t)gl + ((uint64_t)i + 1) * lanes);
+      chn[l].next_rng.idx_ptr = r.idx_ptr;
+      char *ko = gl ? (char *)c->kid_out[gl - 1].p : (char *)c->tmp_out.p;
+      return run_estimate(k, params, r, k->cfg.n_mc, 1, final_out(k, gl == q_last ? value : (void *)ko, gl == q_last ? grad : (void *)(ko + 16)), &chn[l]);
+    });
+  }
+  rec.closing = true;   // the lanes' closing value kernels (the last estimate of every chain): one launch, before the scope gives the streams back
+  for (int l = 0; l < E && st == MIVI_OK; ++l) flush_chain(lane[l], params, &chn[l]);
+  if (st == MIVI_OK) launch_lanes_value(lane[0], params, rec);
+  return st;
+}
+
+mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64_t idx0, int32_t count, void *value, void *grad) {
+  if (!c || !params || !value || !grad || count <= 0) return MIVI_ERR_BAD_ARG;
+  (void)hipSetDevice(c->cfg.device);
+  if (count >= 2 && fb_route(c, params, grad, nullptr)) return fb_batch(c, params, idx0, count, value, grad, nullptr, nullptr);
+  const LanePlan plan = lane_plan(c, params, grad, count);
+  const int lanes = plan.lanes;
   if (lanes <= 1) {
     if (!c->is_child && c->idx_stride != 1) { invalidate_graph(c); c->idx_stride = 1; }
     return estimate_gradient_chain(c, params, idx0, count, value, grad);
@@ -463,7 +514,6 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
   // ONE hipGraph for the whole batch: the children's streams join the capture behind one fork event, so the batch is one graph
   // launch with `lanes` parallel branches and one join (two graph launches + events per call cost a 20-estimate batch what the
   // overlap gained: 14.7 us per estimate against 14.4 with one chain, 9.7 in steady state).
-  const int q_last = (count - 1) % lanes;
   if ((s = ensure_work(c, c->cfg.n_mc))) return s;
   prepare_tables(c, c->cfg.n_mc);
   for (int j = 0; j < lanes - 1; ++j) {
@@ -473,10 +523,8 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
     if (!lds_prepare(k, k->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");
   }
   if (!lds_prepare(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");
-  // LANE-BATCHED contexts: the launchers of the two kernels record their arguments into a sink instead of launching
-  // (kernels_fullrank_lds.hip: launch_lanes_*), the driver issues one launch per kernel and branch.
-  if (lane_e > 0) {
-    const int E = lane_e, B = lanes / E;
+  if (plan.per_branch > 0) {   // LANE-BATCHED contexts (record_lane_branch)
+    const int E = plan.per_branch, B = lanes / E;
     GraphKey key{GRAPH_LANE_BRANCHES, count, params, value, grad};
     key.lanes = lanes;
     key.per_branch = E;
@@ -486,75 +534,7 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
       mivi_ctx *ctxs[1 + mivi_ctx::kMaxKids];
       ctxs[0] = c;
       for (int l = 1; l < lanes; ++l) ctxs[l] = c->kids[l - 1];
-      const bool dense = c->target == TGT_DENSE_GAUSS;
-      // branch b: contexts b E .. b E + E - 1 (global lane g serves estimates g, g + lanes, ...), their launches on the stream of the branch's
-      // first context; its product kernels are ONE launch (blockIdx.y = lane) and so are its VJP kernels
-      auto branch = [&](int b) -> mivi_status_t {
-        mivi_status_t st = MIVI_OK;
-        LaneSink *sink = lane_sinks_alloc(E);
-        StlSink *ssink = stl_ent ? stl_sinks_alloc(E) : nullptr;
-        EpsSink *esink = eps_sink_alloc();
-        Chain chn[4];
-        hipStream_t bs = ctxs[b * E]->stream, kept[4];
-        mivi_ctx *lead = ctxs[b * E];
-        for (int l = 0; l < E; ++l) {
-          mivi_ctx *k = ctxs[b * E + l];
-          kept[l] = k->stream;
-          k->stream = bs;   // (the other lanes' few stand-alone launches -- the first eps, the last value -- go to the branch's stream too)
-          chn[l].on = true; chn[l].estimates_only = true;
-          k->lane_sink = sink; k->lane_id = l;
-          k->stl_sink = ssink;
-          k->eps_sink = esink;
-        }
-        const int steps = (count + lanes - 1) / lanes;
-        for (int i = 0; i < steps && st == MIVI_OK; ++i) {
-          int L = 0;
-          eps_sink_reset(esink);
-          for (int l = 0; l < E && st == MIVI_OK; ++l) {
-            const int gl = b * E + l;
-            const int cnt = (count - gl + lanes - 1) / lanes;   // estimates of global lane gl: gl, gl + lanes, ...
-            if (i >= cnt) break;
-            mivi_ctx *k = ctxs[gl];
-            lane_sink_reset(sink, l);
-            if (ssink) stl_sink_reset(ssink, l);
-            RngArgs r = rng_of(k, (uint64_t)gl + (uint64_t)i * lanes);
-            r.idx_ptr = (const uint64_t *)c->d_idx.p;   // ONE device counter (the parent's) for all lanes
-            k->cur = i & 1;
-            chn[l].has_next = (i + 1 < cnt);
-            chn[l].next_rng = rng_of(k, (uint64_t)gl + ((uint64_t)i + 1) * lanes);
-            chn[l].next_rng.idx_ptr = r.idx_ptr;
-            char *ko = gl ? (char *)c->kid_out[gl - 1].p : (char *)c->tmp_out.p;
-            st = run_estimate(k, params, r, k->cfg.n_mc, 1, final_out(k, gl == q_last ? value : (void *)ko, gl == q_last ? grad : (void *)(ko + 16)), &chn[l]);
-            if (st) { c->err = k->err; break; }
-            if (lane_sink_counts(sink, l) != (dense ? 2 : 1) * 16 + 1 || (ssink && stl_sink_count(ssink, l) != 1))
-              st = fail(c, MIVI_ERR_HIP, "lane-batched estimates: an estimate did not take the expected kernel route");
-            ++L;
-          }
-          if (st == MIVI_OK && L > 0) launch_lanes_eps(lead, esink, L);   // (the lanes' first draws, if this is their first estimate: one launch)
-          if (st == MIVI_OK && L > 0 && !(launch_lanes_prod(lead, sink, L, 0) && (!dense || launch_lanes_prod(lead, sink, L, 1)) &&
-                                          (!ssink || launch_lanes_stl(lead, ssink, L, i == 0)) && launch_lanes_vjp(lead, sink, L)))
-            st = fail(c, MIVI_ERR_HIP, "lane-batched estimates: the lanes' launches do not match");
-        }
-        ValueSink *vsink = value_sink_alloc();   // the lanes' closing value kernels (the last estimate of every chain): one launch
-        for (int l = 0; l < E; ++l) {
-          mivi_ctx *k = ctxs[b * E + l];
-          k->lane_sink = nullptr;
-          k->stl_sink = nullptr;
-          k->eps_sink = nullptr;
-          k->value_sink = vsink;
-          if (st == MIVI_OK) flush_chain(k, params, &chn[l]);
-          k->value_sink = nullptr;
-          k->cur = 0;
-          k->pre.clear();
-        }
-        if (st == MIVI_OK) launch_lanes_value(lead, params, vsink);
-        value_sink_free(vsink);
-        for (int l = 0; l < E; ++l) ctxs[b * E + l]->stream = kept[l];
-        lane_sinks_free(sink);
-        if (ssink) stl_sinks_free(ssink);
-        eps_sink_free(esink);
-        return st;
-      };
+      auto branch = [&](int b) { return record_lane_branch(c, ctxs, b, E, lanes, params, count, value, grad); };
       if ((s = graph_record(c, key, [&]() { return record_branches(c, B, E, count, branch); }))) return s;
     }
     return graph_replay(c, idx0, (uint64_t)count);
@@ -564,6 +544,7 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
   if (!c->graph.matches(key)) {
     invalidate_graph(c);
     if ((s = kids_before_capture(c, lanes))) return s;
+    const int q_last = (count - 1) % lanes;
     auto chain = [&](int q) -> mivi_status_t {   // chain q: this context (q = 0) or child q - 1, estimates q, q + lanes, ... relative to ONE device counter (the parent's)
       mivi_ctx *k = q ? c->kids[q - 1] : c;
       char *ko = q ? (char *)c->kid_out[q - 1].p : (char *)c->tmp_out.p;

@@ -448,11 +448,9 @@ mivi_status_t mivi_p2p_selfcheck(mivi_ctx_t *c, const void *params, uint64_t idx
 
 // buffers of the sharded estimate: padded partial vectors (two: the pipelined batch double-buffers them), slice sum, packed final
 static mivi_status_t ensure_dist(mivi_ctx *c) {
-  const int R = c->comm_world > c->p2p_world ? c->comm_world : c->p2p_world;
   const long long n = slice_len_of(c, c->comm_world), Lp = n * c->comm_world;
   long long need = Lp;
   if (c->p2p_on && c->p2p_n * c->p2p_world > need) need = c->p2p_n * c->p2p_world;
-  (void)R;
   const size_t es = c->esize;
   const size_t need34 = c->p2p_on ? (size_t)need * es : 0;
   bool ring_short = false;
@@ -479,6 +477,7 @@ static mivi_status_t dist_collective(mivi_ctx *c, const void *params, void *P, v
   const int R = c->comm_world, rank = c->comm_rank;
   const size_t es = c->esize;
   const int route = mivi_comm_route(c);
+  const ncclDataType_t dt = c->cfg.dtype == MIVI_F32 ? ncclFloat : ncclDouble;
   if (route == 3) {
     const void *Ps[1] = {P};
     launch_p2p_exchange(c, params, Ps, 1, value, grad, 7, 0, 1, 1, nullptr, nullptr, c->dist_direct);
@@ -498,7 +497,6 @@ static mivi_status_t dist_collective(mivi_ctx *c, const void *params, void *P, v
   }
   if (c->comm && !rsag) {
     RcclApi *r = rccl();
-    const ncclDataType_t dt = c->cfg.dtype == MIVI_F32 ? ncclFloat : ncclDouble;
     if (r->AllReduce(P, P, (size_t)mivi_partials_len(c), dt, ncclSum, (ncclComm_t)c->comm, c->stream) != ncclSuccess)
       return fail(c, MIVI_ERR_HIP, "ncclAllReduce failed");
     launch_finalize(c, params, P, value, grad);
@@ -508,7 +506,6 @@ static mivi_status_t dist_collective(mivi_ctx *c, const void *params, void *P, v
   const void *sum = (const char *)P + (size_t)rank * n * es;   // one rank: its "slice" is the whole vector
   if (c->comm) {
     RcclApi *r = rccl();
-    const ncclDataType_t dt = c->cfg.dtype == MIVI_F32 ? ncclFloat : ncclDouble;
     if (r->ReduceScatter(P, c->dist_S.p, (size_t)n, dt, ncclSum, (ncclComm_t)c->comm, c->stream) != ncclSuccess)
       return fail(c, MIVI_ERR_HIP, "ncclReduceScatter failed");
     sum = c->dist_S.p;
@@ -517,7 +514,6 @@ static mivi_status_t dist_collective(mivi_ctx *c, const void *params, void *P, v
   launch_finalize_slice(c, params, sum, (long long)rank * n, n, fin_slice);
   if (c->comm) {
     RcclApi *r = rccl();
-    const ncclDataType_t dt = c->cfg.dtype == MIVI_F32 ? ncclFloat : ncclDouble;
     if (r->AllGather(fin_slice, c->dist_F.p, (size_t)n, dt, (ncclComm_t)c->comm, c->stream) != ncclSuccess)
       return fail(c, MIVI_ERR_HIP, "ncclAllGather failed");
   }
@@ -525,6 +521,19 @@ static mivi_status_t dist_collective(mivi_ctx *c, const void *params, void *P, v
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
 }
+
+// "Partials into P": the OutArgs of an estimate that leaves its un-normalised partial vector in P; gi >= 0: direct staging, as vector v of
+// exchange group gi (straight into the owners' staging areas)
+static OutArgs partials_out(mivi_ctx *c, void *P, int gi = -1, int v = 0) {
+  OutArgs o = final_out(c, nullptr, nullptr);
+  o.partials = P;
+  o.partials_mode = 1;
+  o.scalars_off = mivi_partials_len(c) - 2;
+  if (gi >= 0) { o.p2p_direct = c->p2p_direct.p; o.p2p_gi = gi; o.p2p_v = v; }
+  return o;
+}
+// slot k of the ring of partial vectors the peer-to-peer pipeline works through
+static void *ring_slot(const mivi_ctx *c, int k) { return k == 0 ? c->dist_P.p : (k == 1 ? c->dist_P2.p : c->dist_ring[k - 2].p); }
 
 // Direct staging (kernels_p2p.hip; DESIGN.md 7, cut (a)): on the peer-to-peer route the second-generation full-rank f32 kernels store every
 // entry of the partial vector straight into its owner's staging area -- no ring slot, no push pass.  OFF by default (MIVI_P2P_DIRECT=1
@@ -558,13 +567,7 @@ mivi_status_t mivi_estimate_gradient_dist(mivi_ctx_t *c, const void *params, uin
   c->dist_direct = mivi_comm_route(c) == 3 && p2p_direct_ok(c, params);
   if (c->dist_direct) {   // the partial kernels store into the owners' staging areas (group 0, vector 0 of the exchange launched below)
     if ((s = ensure_work(c, c->cfg.n_mc))) return s;
-    OutArgs o = final_out(c, nullptr, nullptr);
-    o.partials = c->dist_P.p;
-    o.partials_mode = 1;
-    o.scalars_off = mivi_partials_len(c) - 2;
-    o.p2p_direct = c->p2p_direct.p;
-    o.p2p_gi = 0; o.p2p_v = 0;
-    if ((s = run_estimate(c, params, rng_of(c, idx), c->cfg.n_mc, 1, o))) return s;
+    if ((s = run_estimate(c, params, rng_of(c, idx), c->cfg.n_mc, 1, partials_out(c, c->dist_P.p, 0, 0)))) return s;
   } else if ((s = mivi_estimate_partials(c, params, idx, c->dist_P.p))) {
     return s;
   }
@@ -585,36 +588,23 @@ mivi_status_t mivi_estimate_gradient_dist(mivi_ctx_t *c, const void *params, uin
 static mivi_status_t dist_sequence_lanes(mivi_ctx *c, const void *params, bool counter_idx, uint64_t idx0, int count) {
   constexpr int E = kGroup;
   mivi_status_t s = MIVI_OK;
-  void *ringP[kRing] = {c->dist_P.p, c->dist_P2.p, c->dist_ring[0].p, c->dist_ring[1].p, c->dist_ring[2].p, c->dist_ring[3].p, c->dist_ring[4].p, c->dist_ring[5].p};
   mivi_ctx *ctxs[E];
-  hipStream_t kept[E];
   ctxs[0] = c;
   for (int l = 1; l < E; ++l) ctxs[l] = c->kids[l - 1];
-  LaneSink *sink = lane_sinks_alloc(E);
-  EpsSink *esink = eps_sink_alloc();
-  const bool dense = c->target == TGT_DENSE_GAUSS;
-  for (int l = 0; l < E; ++l) { kept[l] = ctxs[l]->stream; ctxs[l]->stream = c->stream; ctxs[l]->lane_sink = sink; ctxs[l]->lane_id = l; ctxs[l]->eps_sink = esink; }
+  LaneRecorder rec(E, false);
+  LaneScope scope(ctxs, E, &rec, c->stream);
   unsigned *w = (unsigned *)c->p2p_ctr.p;
-  for (int s0 = 0; s0 < count && s == MIVI_OK; s0 += E) {
+  for (int s0 = 0; s0 < count; s0 += E) {
     const int L = count - s0 < E ? count - s0 : E;
-    eps_sink_reset(esink);
-    for (int l = 0; l < L && s == MIVI_OK; ++l) {
+    s = lanes_step(c, ctxs, rec, L, false, [&](int l) {
       const int i = s0 + l;
       mivi_ctx *k = ctxs[l];
-      lane_sink_reset(sink, l);
       RngArgs r = rng_of(k, counter_idx ? (uint64_t)i : idx0 + (uint64_t)i);
       if (counter_idx) r.idx_ptr = (const uint64_t *)c->d_idx.p;
-      OutArgs o = final_out(k, nullptr, nullptr);
-      o.partials = ringP[i % kRing];
-      o.partials_mode = 1;
-      o.scalars_off = mivi_partials_len(c) - 2;
-      if (c->dist_direct) { o.p2p_direct = c->p2p_direct.p; o.p2p_gi = i / kGroup; o.p2p_v = i % kGroup; }
-      if ((s = run_estimate(k, params, r, k->cfg.n_mc, 1, o))) { c->err = k->err; break; }
-      if (lane_sink_counts(sink, l) != (dense ? 2 : 1) * 16 + 1) s = fail(c, MIVI_ERR_HIP, "lane-batched sharded estimates: an estimate did not take the two-kernel route");
-    }
-    if (s == MIVI_OK) launch_lanes_eps(c, esink, L);
-    if (s == MIVI_OK && !(launch_lanes_prod(c, sink, L, 0) && (!dense || launch_lanes_prod(c, sink, L, 1)) && launch_lanes_vjp(c, sink, L)))
-      s = fail(c, MIVI_ERR_HIP, "lane-batched sharded estimates: the lanes' launches do not match");
+      OutArgs o = partials_out(k, ring_slot(c, i % kRing));
+      if (c->dist_direct) { o.p2p_direct = c->p2p_direct.p; o.p2p_gi = i / kGroup; o.p2p_v = i % kGroup; }   // (the parent's table: the children have none)
+      return run_estimate(k, params, r, k->cfg.n_mc, 1, o);
+    });
     if (s) break;
     // announce the group's partial vectors; hold the chain until the exchange has read the ring slots the NEXT group overwrites
     const unsigned *fr[E];
@@ -628,15 +618,6 @@ static mivi_status_t dist_sequence_lanes(mivi_ctx *c, const void *params, bool c
     }
     launch_p2p_handover4(c, w + 64, (unsigned)(s0 + L), fr, fmin, nf);
   }
-  for (int l = 0; l < E; ++l) {
-    ctxs[l]->lane_sink = nullptr;
-    ctxs[l]->eps_sink = nullptr;
-    ctxs[l]->stream = kept[l];
-    ctxs[l]->cur = 0;
-    ctxs[l]->pre.clear();
-  }
-  lane_sinks_free(sink);
-  eps_sink_free(esink);
   return s;
 }
 
@@ -645,33 +626,17 @@ static mivi_status_t dist_sequence(mivi_ctx *c, const void *params, bool counter
   mivi_status_t s = MIVI_OK;
   hipStream_t main = c->stream;
   if (mode == 3 && c->dist_direct) {   // exchange-only (a measurement leg): both parities of the staging areas hold a complete partial vector
-    for (int g2 = 0; g2 < 2 && s == MIVI_OK; ++g2) {
-      OutArgs o = final_out(c, nullptr, nullptr);
-      o.partials = c->dist_P.p;
-      o.partials_mode = 1;
-      o.scalars_off = mivi_partials_len(c) - 2;
-      o.p2p_direct = c->p2p_direct.p;
-      o.p2p_gi = g2; o.p2p_v = 0;
-      s = run_estimate(c, params, rng_of(c, idx0), c->cfg.n_mc, 1, o);
-    }
+    for (int g2 = 0; g2 < 2 && s == MIVI_OK; ++g2) s = run_estimate(c, params, rng_of(c, idx0), c->cfg.n_mc, 1, partials_out(c, c->dist_P.p, g2, 0));
   }
   for (int i = 0; i < count && s == MIVI_OK; ++i) {
     const int par = i & 1;
-    void *ringP[kRing] = {c->dist_P.p, c->dist_P2.p, c->dist_ring[0].p, c->dist_ring[1].p, c->dist_ring[2].p, c->dist_ring[3].p, c->dist_ring[4].p, c->dist_ring[5].p};
-    void *P = mode == 4 ? ringP[i % kRing] : (par ? c->dist_P2.p : c->dist_P.p);
+    void *P = mode == 4 ? ring_slot(c, i % kRing) : (par ? c->dist_P2.p : c->dist_P.p);
     if (mode == 0 && i >= 2) HIPCHK(c, hipStreamWaitEvent(main, c->ev_comm[par], 0));   // the exchange of i - 2 has released this partial buffer
     if (mode != 3) {
       RngArgs r = rng_of(c, counter_idx ? (uint64_t)i : idx0 + (uint64_t)i);
       if (counter_idx) r.idx_ptr = (const uint64_t *)c->d_idx.p;
-      OutArgs o = final_out(c, nullptr, nullptr);
-      o.partials = P;
-      o.partials_mode = 1;
-      o.scalars_off = mivi_partials_len(c) - 2;
-      if (c->dist_direct) {   // mode 4: the persistent exchange serves groups of kGroup estimates; modes 1 / 2: one exchange launch per estimate
-        o.p2p_direct = c->p2p_direct.p;
-        o.p2p_gi = mode == 4 ? i / kGroup : 0;
-        o.p2p_v = mode == 4 ? i % kGroup : 0;
-      }
+      // direct staging, mode 4: the persistent exchange serves groups of kGroup estimates; modes 1 / 2: one exchange launch per estimate
+      const OutArgs o = !c->dist_direct ? partials_out(c, P) : (mode == 4 ? partials_out(c, P, i / kGroup, i % kGroup) : partials_out(c, P, 0, 0));
       if ((s = run_estimate(c, params, r, c->cfg.n_mc, 1, o))) break;
     }
     if (mode == 2) continue;
@@ -773,11 +738,8 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
   if (p2p_pipe) mode = 4;
   {   // lane-batched compute chain for the pipelined batches (see dist_sequence_lanes)
     static const bool no_lanes = getenv("MIVI_LANE_BATCH") && atoi(getenv("MIVI_LANE_BATCH")) == 0;
-    const bool stl_ent = c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD;
-    OutArgs on = final_out(c, nullptr, nullptr);
-    on.partials = c->dist_P.p;
-    on.partials_mode = 1;
-    const bool lane4 = mode == 4 && !no_lanes && !stl_ent && !c->dbg && c->cfg.family == MIVI_FULLRANK && lds_route(c, params, c->cfg.n_mc, 1, on) &&
+    const OutArgs on = partials_out(c, c->dist_P.p);
+    const bool lane4 = mode == 4 && !no_lanes && !stl_entropy(c) && !c->dbg && c->cfg.family == MIVI_FULLRANK && lds_route(c, params, c->cfg.n_mc, 1, on) &&
                        lds_use_prod32(c, c->cfg.n_mc) && lds_bf16x3() && count >= kGroup;
     const int stride = lane4 ? kGroup : 1;
     if (c->dist_lane4 != lane4 || c->idx_stride != stride) { invalidate_graph(c); c->dist_lane4 = lane4; c->idx_stride = stride; }
@@ -819,7 +781,8 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
     HIPCHK(c, hipMemsetAsync(w + 64, 0, 128, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_part[0], c->stream));
     hipStream_t main = c->stream;
-    const void *ringP[kRing] = {c->dist_P.p, c->dist_P2.p, c->dist_ring[0].p, c->dist_ring[1].p, c->dist_ring[2].p, c->dist_ring[3].p, c->dist_ring[4].p, c->dist_ring[5].p};
+    const void *ringP[kRing];
+    for (int k = 0; k < kRing; ++k) ringP[k] = ring_slot(c, k);
     // ONE persistent exchange kernel (measured on one GPU: 21 us per estimate against 31 with two of them serving alternate estimates -- a
     // second resident kernel costs the compute chain more than its overlap wins)
     const int lanes = 1;
@@ -883,10 +846,7 @@ mivi_status_t mivi_p2p_partials_direct(mivi_ctx_t *c, const void *params, uint64
   if (c->target == TGT_NONE) return fail(c, MIVI_ERR_NO_TARGET, "no target set");
   mivi_status_t s;
   if ((s = ensure_work(c, c->cfg.n_mc)) || (s = ensure_dist(c))) return s;
-  OutArgs o = final_out(c, nullptr, nullptr);
-  o.partials = c->dist_P.p;
-  o.partials_mode = 1;
-  o.scalars_off = mivi_partials_len(c) - 2;
+  OutArgs o = partials_out(c, c->dist_P.p);
   if (!c->p2p_direct.p || c->cfg.family != MIVI_FULLRANK || c->cfg.dtype != MIVI_F32 || !lds_route(c, params, c->cfg.n_mc, 1, o))
     return fail(c, MIVI_ERR_UNSUPPORTED, "direct staging serves the second-generation full-rank f32 kernels");
   o.p2p_direct = c->p2p_direct.p;

@@ -1,4 +1,6 @@
 // libmivi C ABI, part 7: per-kernel timing entries (bench.py's roofline block, tools/).
+#include <memory>
+
 #include "api_common.h"
 
 mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *params, int32_t reps, double *ms_out) {
@@ -22,33 +24,26 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
   // which = 10 / 11: the product / VJP launch of FOUR lane-batched estimates, as mivi_estimate_gradient_n issues them.  A batch of eight
   // estimates first (it creates and fills the four contexts), then the four contexts' launches are recorded once and the ONE launch
   // that serves them is replayed.
-  LaneSink *psink = nullptr;
-  struct SinkGuard {   // (the stage code below returns early on errors)
-    LaneSink *&p;
-    ~SinkGuard() { if (p) lane_sinks_free(p); }
-  } sink_guard{psink};
+  std::unique_ptr<LaneRecorder> prec;
   if (which == 10 || which == 11) {
     if (!(lds && lds_use_prod32(c, M)) || c->is_child || c->target != TGT_DIAG_GAUSS) return fail(c, MIVI_ERR_UNSUPPORTED, "which = 10 / 11: full-rank second-generation kernels, diagonal-Gaussian target");
     if ((s = mivi_estimate_gradient_n(c, params, 1, 8, o, o + 16))) return s;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!(c->graph.exec && c->graph.key.kind == GRAPH_LANE_BRANCHES)) return fail(c, MIVI_ERR_UNSUPPORTED, "which = 10 / 11: this configuration does not take the lane-batched route");
-    psink = lane_sinks_alloc(4);
-    for (int l = 0; l < 4 && s == MIVI_OK; ++l) {
-      mivi_ctx *k = l ? c->kids[l - 1] : c;
+    prec.reset(new LaneRecorder(4, false));
+    mivi_ctx *ctxs[4] = {c, c->kids[0], c->kids[1], c->kids[2]};
+    LaneScope scope(ctxs, 4, prec.get(), c->stream);
+    for (int l = 0; l < 4; ++l) {
+      mivi_ctx *k = ctxs[l];
       char *ko = l ? (char *)c->kid_out[l - 1].p : o;
-      hipStream_t kept = k->stream;
-      k->stream = c->stream;
-      k->lane_sink = psink; k->lane_id = l;
-      lane_sink_reset(psink, l);
+      prec->reset_lane(l);
       k->cur = 0;
       EpsJob nx{rng_of(k, (uint64_t)(100 + l)), 1};
       launch_lds_prod32(k, params, M, false, R_DIAG, nullptr, &nx, true, false);
       launch_lds_vjp(k, params, M, final_out(k, ko, ko + 16), nullptr, nullptr);
-      k->lane_sink = nullptr;
-      k->stream = kept;
     }
   }
-  if (which == 8 && !(fr && (c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD)))
+  if (which == 8 && !(fr && stl_entropy(c)))
     return fail(c, MIVI_ERR_UNSUPPORTED, "which = 8: full-rank family with a sticking-the-landing estimator");
   if (which == 5) {   // the launch-free loop of 100 estimates (mean-field + diagonal target): one launch per rep
     const bool fn5 = !fr && c->target == TGT_FUNNEL && !c->funnel_constrained;
@@ -81,8 +76,8 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
         if (lds) launch_lds_vjp(c, params, M, out, nullptr, nullptr);
         else launch_fr_vjp(c, params, M, out);
         break;
-      case 10: if (!launch_lanes_prod(c, psink, 4, 0)) st = fail(c, MIVI_ERR_HIP, "lane-batched product: the lanes' launches do not match"); break;
-      case 11: if (!launch_lanes_vjp(c, psink, 4)) st = fail(c, MIVI_ERR_HIP, "lane-batched VJP: the lanes' launches do not match"); break;
+      case 10: if (!launch_lanes_prod(c, *prec, 4, 0)) st = fail(c, MIVI_ERR_HIP, "lane-batched product: the lanes' launches do not match"); break;
+      case 11: if (!launch_lanes_vjp(c, *prec, 4)) st = fail(c, MIVI_ERR_HIP, "lane-batched VJP: the lanes' launches do not match"); break;
       case 9: {   // two EMPTY dependent launches with the grids / blocks / LDS of the product and VJP kernels: what the launch structure costs
         static bool attr_set = false;
         if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_empty), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }

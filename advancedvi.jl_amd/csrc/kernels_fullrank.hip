@@ -1242,28 +1242,24 @@ static SampleArgs<T> eps_args(mivi_ctx *c, const RngArgs &rng, int M, int parity
   return a;
 }
 
-struct EpsSink { SampleArgs<float> a[4]; int grid[4], n[4]; };
-EpsSink *eps_sink_alloc() { return new EpsSink(); }
-void eps_sink_free(EpsSink *s) { delete s; }
-void eps_sink_reset(EpsSink *s) { for (int l = 0; l < 4; ++l) s->n[l] = 0; }
 // the recorded first draws of the lanes that made one: ONE launch
-void launch_lanes_eps(mivi_ctx *c, EpsSink *s, int lanes) {
+void launch_lanes_eps(mivi_ctx *c, const LaneRecorder &rec, int lanes) {
   EpsMulti m;
   int L = 0, grid = 0;
   for (int l = 0; l < lanes && l < 4; ++l)
-    if (s->n[l] > 0) { m.lane[L++] = s->a[l]; grid = s->grid[l]; }
+    if (rec.lane[l].n_eps > 0) { m.lane[L++] = rec.eps[l]; grid = rec.eps_grid[l]; }
   if (L > 0) hipLaunchKernelGGL(k_eps_m, dim3(grid, L), dim3(512), 0, c->stream, m);
 }
 
 // returns the number of he_part entries the draw leaves
 int launch_eps(mivi_ctx *c, const RngArgs &rng, int M) {
   const int nblk = eps_blocks(c, M);
-  if (c->eps_sink && c->cfg.dtype == MIVI_F32) {   // lane-batched contexts: record (every lane has the same shape, so the same grid)
-    EpsSink *sk = (EpsSink *)c->eps_sink;        // (k_eps_m works in the riders' blocks: d % 64 == 0, M % 32 == 0 on this route)
+  if (c->rec && !c->rec->closing && c->cfg.dtype == MIVI_F32) {   // lane-batched contexts: record (every lane has the same shape, so the same grid)
+    LaneRecorder *sk = c->rec;                     // (k_eps_m works in the riders' blocks: d % 64 == 0, M % 32 == 0 on this route)
     const int nrid = (c->cfg.d / 64) * (M / 32);
-    sk->a[c->lane_id] = eps_args<float>(c, rng, M, c->cur);
-    sk->grid[c->lane_id] = nrid;
-    ++sk->n[c->lane_id];
+    sk->eps[c->lane_id] = eps_args<float>(c, rng, M, c->cur);
+    sk->eps_grid[c->lane_id] = nrid;
+    ++sk->lane[c->lane_id].n_eps;
     return nrid;
   }
   if (c->cfg.dtype == MIVI_F32)

@@ -1422,11 +1422,11 @@ static int knock_flags() {   // developer knock-outs (operand loads / MFMAs / ep
 }
 
 // eps(t+1) rider blocks of the 64 x 64 product kernel: 512 threads = 64 rows x 32 columns each
-struct LaneSink {   // one lane's recorded launches of an estimate (see launch_lanes_prod / launch_lanes_vjp)
+struct LaneKernelArgs {   // one lane's recorded launches of an estimate (LaneRecorder::kern; see launch_lanes_prod / launch_lanes_vjp)
   Prod32Args prod[2];
-  int prod_grid[2], prod_dense[2], n_prod;
+  int prod_grid[2], prod_dense[2];
   GemmArgs vjp;
-  int vjp_grid, n_vjp;
+  int vjp_grid;
 };
 int lds_eps_blocks(const mivi_ctx *c, int M) { return (c->cfg.d / 64) * (M / 32); }
 
@@ -1467,10 +1467,11 @@ void launch_lds_prod32(mivi_ctx *c, const void *params, int M, bool dense, int m
   }
   // riders hitch onto the tile workgroups; only the ones beyond the tile count get workgroups of their own
   grid = a.n_tiles > a.n_dinv + a.n_pack + a.n_eps ? a.n_tiles : a.n_dinv + a.n_pack + a.n_eps;
-  if (c->lane_sink) {   // lane-batched estimates (api_batch.hip): record the launch, the driver issues it for all lanes at once
-    LaneSink &sk = ((LaneSink *)c->lane_sink)[c->lane_id];
-    if (sk.n_prod < 2) { sk.prod[sk.n_prod] = a; sk.prod_grid[sk.n_prod] = grid; sk.prod_dense[sk.n_prod] = dense ? 1 : 0; }
-    ++sk.n_prod;
+  if (c->rec && !c->rec->closing) {   // lane-batched estimates (api_batch.hip): record the launch, the driver issues it for all lanes at once
+    LaneKernelArgs &sk = c->rec->kern[c->lane_id];
+    int &n_prod = c->rec->lane[c->lane_id].n_prod;
+    if (n_prod < 2) { sk.prod[n_prod] = a; sk.prod_grid[n_prod] = grid; sk.prod_dense[n_prod] = dense ? 1 : 0; }
+    ++n_prod;
     return;
   }
   if (dense && f32_mfma()) hipLaunchKernelGGL((k_fr_prod32<G_DENSE, false>), dim3(grid), dim3(512), 0, c->stream, a);
@@ -1480,20 +1481,21 @@ void launch_lds_prod32(mivi_ctx *c, const void *params, int M, bool dense, int m
 }
 
 // ---- lane-batched launches: up to kMaxLanes contexts' product / VJP kernels as ONE launch each (blockIdx.y = lane) ---------------------
-LaneSink *lane_sinks_alloc(int n) { return new LaneSink[n](); }
-void lane_sinks_free(LaneSink *s) { delete[] s; }
-void lane_sink_reset(LaneSink *s, int lane) { s[lane].n_prod = 0; s[lane].n_vjp = 0; }
-int lane_sink_counts(const LaneSink *s, int lane) { return s[lane].n_prod * 16 + s[lane].n_vjp; }
+void lane_args_resize(LaneKernelArgs *&p, int lanes) {
+  delete[] p;
+  p = lanes > 0 ? new LaneKernelArgs[lanes]() : nullptr;
+}
 static bool prod_quad_on() {   // MIVI_PROD_QUAD=0: four lanes' sampling products as 4 x k_fr_prod32's tiles again (A/B)
   static const bool v = !(getenv("MIVI_PROD_QUAD") && atoi(getenv("MIVI_PROD_QUAD")) == 0);
   return v;
 }
 // which: 0 = the sampling product (with the fused diagonal target, or R = Z - m of the dense one), 1 = the dense target's product
-bool launch_lanes_prod(mivi_ctx *c, LaneSink *s, int lanes, int which) {
+bool launch_lanes_prod(mivi_ctx *c, const LaneRecorder &rec, int lanes, int which) {
   if (lanes < 1 || lanes > kMaxLanes || f32_mfma()) return false;
+  const LaneKernelArgs *s = rec.kern;
   Prod32Multi m;
   for (int l = 0; l < lanes; ++l) {
-    if (s[l].n_prod <= which || s[l].n_prod > 2 || s[l].prod_dense[which] != which || s[l].prod[which].n_tiles != s[0].prod[which].n_tiles) return false;
+    if (rec.lane[l].n_prod <= which || rec.lane[l].n_prod > 2 || s[l].prod_dense[which] != which || s[l].prod[which].n_tiles != s[0].prod[which].n_tiles) return false;
     m.lane[l] = s[l].prod[which];
   }
   int gx = 0;   // (the lane that carries the STL riders may need trailing workgroups the others do not: d = 2048)
@@ -1519,11 +1521,12 @@ bool launch_lanes_prod(mivi_ctx *c, LaneSink *s, int lanes, int which) {
   else hipLaunchKernelGGL((k_fr_prod32m<G_SAMPLE, true>), grid, dim3(512), 0, c->stream, m);
   return true;
 }
-bool launch_lanes_vjp(mivi_ctx *c, LaneSink *s, int lanes) {
+bool launch_lanes_vjp(mivi_ctx *c, const LaneRecorder &rec, int lanes) {
   if (lanes < 1 || lanes > kMaxLanes || f32_mfma()) return false;
+  const LaneKernelArgs *s = rec.kern;
   GemmMulti m;
   for (int l = 0; l < lanes; ++l) {
-    if (s[l].n_vjp != 1 || s[l].vjp_grid != s[0].vjp_grid) return false;
+    if (rec.lane[l].n_vjp != 1 || rec.lane[l].vjp_refused || s[l].vjp_grid != s[0].vjp_grid) return false;
     m.lane[l] = s[l].vjp;
   }
   if (vjp_strip_len() > 0 && lanes >= 2 && m.lane[0].M == 256 && c->lds_tabS.p) {   // strips of tiles per workgroup where they apply
@@ -1614,7 +1617,8 @@ void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, 
   // two or three 32 x 32 workgroups per CU covering for each other).  MIVI_VJP_TILE=32 / 64 pins it.
   static const int pin = getenv("MIVI_VJP_TILE") ? atoi(getenv("MIVI_VJP_TILE")) : 0;
   const bool t64 = pin ? pin == 64 : ((M >= 1024 && c->cfg.d >= 2048) || (M >= 512 && c->cfg.d >= 4096));   // (4096 x 512: 90.6 -> 83.7 us)
-  if (t64 && c->lane_sink) { ((LaneSink *)c->lane_sink)[c->lane_id].n_vjp += 16; return; }   // (not a lane-batched route: the driver reports it)
+  LaneRecorder *rec = c->rec && !c->rec->closing ? c->rec : nullptr;
+  if (t64 && rec) { rec->lane[c->lane_id].vjp_refused = true; return; }   // (not a lane-batched route: the driver reports it)
   if (t64) {
     a.work = (const int4 *)c->lds_tabV64.p;
     grid = c->lds_nV64;
@@ -1625,10 +1629,11 @@ void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, 
     else hipLaunchKernelGGL((k_fr_vjp64<false, true>), dim3(grid), dim3(512), 0, c->stream, a);
     return;
   }
-  if (c->lane_sink) {   // lane-batched estimates: record (the driver only enters this mode where this route is taken)
-    LaneSink &sk = ((LaneSink *)c->lane_sink)[c->lane_id];
-    if (sk.n_vjp < 1 && !upd) { sk.vjp = a; sk.vjp_grid = grid; }
-    sk.n_vjp += upd ? 16 : 1;
+  if (rec) {   // lane-batched estimates: record (the driver only enters this mode where this route is taken)
+    LaneRecorder::Lane &ln = rec->lane[c->lane_id];
+    if (upd) { ln.vjp_refused = true; return; }   // (nor is a fused optimiser update)
+    if (ln.n_vjp < 1) { rec->kern[c->lane_id].vjp = a; rec->kern[c->lane_id].vjp_grid = grid; }
+    ++ln.n_vjp;
     return;
   }
   if (upd && f32_mfma()) hipLaunchKernelGGL((k_fr_vjp32<true, false>), dim3(grid), dim3(256), 0, c->stream, a);

@@ -435,16 +435,16 @@ struct StlUpdMulti { StlUpdArgs lane[4]; };   // lane-batched contexts: blockIdx
 __global__ __launch_bounds__(512) void k_stl_update32(StlUpdArgs a) { stl_update32_body(a); }
 __global__ __launch_bounds__(512) void k_stl_update32m(StlUpdMulti m) { stl_update32_body(m.lane[blockIdx.y]); }
 
-// one context's recorded STL term (lane-batched estimates: launch_stl2 records, launch_lanes_stl issues the lanes together)
-struct StlSink {
+// one context's recorded STL term (LaneRecorder::stl; lane-batched estimates: launch_stl2 records, launch_lanes_stl issues the lanes together)
+struct LaneStlArgs {
   StlSolveArgs solve;
   StlUpdArgs upd;
-  int upd_grid, n;
+  int upd_grid;
 };
-StlSink *stl_sinks_alloc(int n) { return new StlSink[n](); }
-void stl_sinks_free(StlSink *s) { delete[] s; }
-void stl_sink_reset(StlSink *s, int lane) { s[lane].n = 0; }
-int stl_sink_count(const StlSink *s, int lane) { return s[lane].n; }
+void lane_args_resize(LaneStlArgs *&p, int lanes) {
+  delete[] p;
+  p = lanes > 0 ? new LaneStlArgs[lanes]() : nullptr;
+}
 
 // -----------------------------------------------------------------------------------------------------------------
 bool stl2_shape_ok(const mivi_ctx *c, int M) {
@@ -492,10 +492,11 @@ void launch_stl2(mivi_ctx *c, const void *params, int M, bool dinv_done, const v
   StlUpdArgs u{};   // rows 0 .. n of W:  X1 = Y1 - F^T X2
   u.n_i = n; u.n_k = n; u.A = F; u.lda = n; u.X = Xb; u.ld_x = n; u.E = Y1; u.ld_e = n;
   u.R = Wout; u.ld_r = d; u.accumulate = overwrite ? 0 : 1; u.ncb = M / 32;
-  if (c->stl_sink) {   // lane-batched estimates (api_batch.hip): record; the driver issues the lanes' solves and products as one launch each
-    StlSink &sk = ((StlSink *)c->stl_sink)[c->lane_id];
-    if (sk.n == 0) { sk.solve = s; sk.upd = u; sk.upd_grid = (n / 32) * (M / 32); }
-    ++sk.n;
+  if (c->rec && !c->rec->closing && c->rec->stl) {   // lane-batched estimates (api_batch.hip): record; the driver issues the lanes' solves and products as one launch each
+    LaneStlArgs &sk = c->rec->stl[c->lane_id];
+    int &n_stl = c->rec->lane[c->lane_id].n_stl;
+    if (n_stl == 0) { sk.solve = s; sk.upd = u; sk.upd_grid = (n / 32) * (M / 32); }
+    ++n_stl;
     return;
   }
 #ifdef MIVI_DEV
@@ -527,13 +528,14 @@ void launch_stl2(mivi_ctx *c, const void *params, int M, bool dinv_done, const v
 // the recorded STL terms of `lanes` contexts: ONE solve launch with all their jobs, ONE combining product (blockIdx.y = lane).
 // The lanes are estimates at the SAME parameters, so the parameter-only coupling solve (job 2: F) runs for lane 0 only and every lane's
 // product reads lane 0's F; with_F = false (a later step of the same batch): nobody solves for it again.
-bool launch_lanes_stl(mivi_ctx *c, StlSink *sk, int lanes, bool with_F) {
-  if (lanes < 1 || lanes > 4) return false;
+bool launch_lanes_stl(mivi_ctx *c, const LaneRecorder &rec, int lanes, bool with_F) {
+  const LaneStlArgs *sk = rec.stl;
+  if (lanes < 1 || lanes > 4 || !sk) return false;
   StlSolveArgs s = sk[0].solve;
   StlUpdMulti m;
   s.njobs = 0;
   for (int l = 0; l < lanes; ++l) {
-    if (sk[l].n != 1 || sk[l].solve.njobs != 3 || sk[l].solve.d != s.d || sk[l].solve.n != s.n || sk[l].upd_grid != sk[0].upd_grid) return false;
+    if (rec.lane[l].n_stl != 1 || sk[l].solve.njobs != 3 || sk[l].solve.d != s.d || sk[l].solve.n != s.n || sk[l].upd_grid != sk[0].upd_grid) return false;
     for (int j = 0; j < 3; ++j)
       if (j < 2 || (l == 0 && with_F)) s.job[s.njobs++] = sk[l].solve.job[j];
     m.lane[l] = sk[l].upd;

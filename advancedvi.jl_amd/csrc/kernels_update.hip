@@ -239,20 +239,21 @@ __global__ __launch_bounds__(256) void k_value_only_m(int d, int family, const f
   finalize_value_block<float, 256, false, false>(d, m.vin[blockIdx.x], m.out[blockIdx.x], plen,
       [params, d, fam](int i) { return fam == MIVI_MEANFIELD ? params[d + i] : params[d + (size_t)i * d + i]; }, red);
 }
-struct ValueSink { ValueMulti m; int n; };
-ValueSink *value_sink_alloc() { return new ValueSink(); }
-void value_sink_free(ValueSink *s) { delete s; }
-void launch_lanes_value(mivi_ctx *c, const void *params, ValueSink *s) {
-  if (s->n > 0) hipLaunchKernelGGL(k_value_only_m, dim3(s->n), dim3(256), 0, c->stream, c->cfg.d, c->cfg.family, (const float *)params, s->m);
-  s->n = 0;
+void launch_lanes_value(mivi_ctx *c, const void *params, LaneRecorder &rec) {
+  if (rec.n_value > 0) {
+    ValueMulti m{};
+    for (int l = 0; l < rec.n_value; ++l) { m.vin[l] = rec.value_in[l]; m.out[l] = rec.value_out[l]; }
+    hipLaunchKernelGGL(k_value_only_m, dim3(rec.n_value), dim3(256), 0, c->stream, c->cfg.d, c->cfg.family, (const float *)params, m);
+  }
+  rec.n_value = 0;
 }
 
 void launch_value_only(mivi_ctx *c, const void *params, const ValueIn &vin, const OutArgs &out) {
-  if (c->value_sink && c->cfg.dtype == MIVI_F32 && !(vin.fn.ab && c->cfg.family == MIVI_MEANFIELD) && ((ValueSink *)c->value_sink)->n < 4) {
-    ValueSink *sk = (ValueSink *)c->value_sink;   // record: the driver issues the lanes' value kernels as one launch
-    sk->m.vin[sk->n] = vin;
-    sk->m.out[sk->n] = out;
-    ++sk->n;
+  if (c->rec && c->rec->closing && c->cfg.dtype == MIVI_F32 && !(vin.fn.ab && c->cfg.family == MIVI_MEANFIELD) && c->rec->n_value < 4) {
+    LaneRecorder *sk = c->rec;   // record: the driver issues the lanes' value kernels as one launch
+    sk->value_in[sk->n_value] = vin;
+    sk->value_out[sk->n_value] = out;
+    ++sk->n_value;
     return;
   }
   if (vin.fn.ab && c->cfg.family == MIVI_MEANFIELD) {

@@ -277,6 +277,49 @@ struct GraphCache {
   void drop();   // destroys the cached hipGraphExec, if any, and empties the slot
 };
 
+// Lane-batched estimates (second-generation full-rank kernels): up to four contexts -- the LANES of one graph branch -- run their estimates
+// with c->rec set.  The launchers then record their argument blocks here instead of launching, and the driver issues ONE launch per kernel
+// for all lanes (launch_lanes_*; blockIdx.y = lane).  While `closing` is false the estimates' kernels record: launch_eps (a chain's first
+// draw), launch_lds_prod32, launch_stl2 (if the recorder has the STL part), launch_lds_vjp.  While it is true only launch_value_only (a
+// chain's closing value kernel) does.  The argument blocks of the product / VJP and of the STL term stay private to their units.
+struct LaneKernelArgs;   // kernels_fullrank_lds.hip: a lane's product(s) and VJP
+struct LaneStlArgs;      // kernels_stl.hip: a lane's solve jobs and combining product
+void lane_args_resize(LaneKernelArgs *&p, int lanes);   // frees p; lanes > 0: p = new zeroed blocks for `lanes` lanes
+void lane_args_resize(LaneStlArgs *&p, int lanes);
+struct LaneRecorder {
+  struct Lane {
+    int n_prod, n_vjp, n_stl, n_eps;   // launches recorded since reset_lane (n_eps: since reset_step)
+    bool vjp_refused;                  // a VJP the lanes' launch cannot serve came by: 64 x 64 tiles, or a fused optimiser update
+  };
+  Lane lane[4] = {};
+  LaneKernelArgs *kern = nullptr;
+  LaneStlArgs *stl = nullptr;          // nullptr: no STL part (launch_stl2 launches as usual)
+  SampleArgs<float> eps[4];            // per branch: the first draws of the lanes that made one ...
+  int eps_grid[4];
+  ValueIn value_in[4];                 // ... and the closing values, in the order they came
+  OutArgs value_out[4];
+  int n_value = 0;
+  bool closing = false;
+
+  LaneRecorder(int lanes, bool with_stl) {
+    lane_args_resize(kern, lanes);
+    if (with_stl) lane_args_resize(stl, lanes);
+  }
+  ~LaneRecorder() {
+    lane_args_resize(kern, 0);
+    lane_args_resize(stl, 0);
+  }
+  LaneRecorder(const LaneRecorder &) = delete;
+  LaneRecorder &operator=(const LaneRecorder &) = delete;
+  void reset_step() { for (Lane &l : lane) l.n_eps = 0; }
+  void reset_lane(int l) { lane[l].n_prod = lane[l].n_vjp = lane[l].n_stl = 0; lane[l].vjp_refused = false; }
+  // did lane l's estimate take the route the lanes' launches serve?  Exactly one sampling product (and the dense target's, if any: their
+  // kinds are checked by launch_lanes_prod), one VJP on 32 x 32 tiles without a fused update, one STL term if any.
+  bool lane_took_route(int l, bool dense, bool with_stl) const {
+    return lane[l].n_prod == (dense ? 2 : 1) && lane[l].n_vjp == 1 && !lane[l].vjp_refused && (!with_stl || lane[l].n_stl == 1);
+  }
+};
+
 }  // namespace mivi
 
 struct mivi_ctx {
@@ -410,11 +453,8 @@ struct mivi_ctx {
   bool dist_capture_refused = false;   // the sharded batch could not be captured into a hipGraph (RCCL route): issued eagerly from then on
   bool dist_direct = false;      // sharded estimates on the peer-to-peer route: the partial kernels store straight into the owners' staging areas
   bool dist_lane4 = false;       // pipelined sharded batches: the compute chain is lane-batched (four contexts per launch)
-  void *value_sink = nullptr;    // ... and launch_value_only (a chain's closing value kernel) into the value sink
-  void *eps_sink = nullptr;      // ... and launch_eps (a chain's first draw) into the eps sink
-  void *stl_sink = nullptr;      // ... and launch_stl2 into stl_sink[lane_id]
-  void *lane_sink = nullptr;     // lane-batched estimates: the launchers of the two second-generation kernels record into sink[lane_id] instead of launching
-  int lane_id = 0;
+  mivi::LaneRecorder *rec = nullptr;   // lane-batched estimates: non-null while this context is lane `lane_id` of a branch whose launchers record
+  int lane_id = 0;                     // into `rec` instead of launching (set and cleared by LaneScope, api_common.h)
   mivi::DevBuf kid_out[kMaxKids];       // value (16 bytes) + gradient of the child chains that do not hold the batch's last estimate
 };
 
@@ -488,28 +528,12 @@ int lds_prod64_tiles(const mivi_ctx *c, int M);
 bool lds_use_prod64(const mivi_ctx *c, int M);   // large shapes: unsplit 64 x 64 tiles
 int lds_prod32_eps_blocks(const mivi_ctx *c, int M);
 bool lds_use_prod32(const mivi_ctx *c, int M);
-struct LaneSink;
-LaneSink *lane_sinks_alloc(int n);
-void lane_sinks_free(LaneSink *s);
-void lane_sink_reset(LaneSink *s, int lane);
-int lane_sink_counts(const LaneSink *s, int lane);                       // products recorded * 16 + VJPs recorded
-bool launch_lanes_prod(mivi_ctx *c, LaneSink *s, int lanes, int which);   // one launch for all lanes (blockIdx.y = lane)
-bool launch_lanes_vjp(mivi_ctx *c, LaneSink *s, int lanes);
-struct ValueSink;
-ValueSink *value_sink_alloc();
-void value_sink_free(ValueSink *s);
-void launch_lanes_value(mivi_ctx *c, const void *params, ValueSink *s);   // the recorded closing value kernels as one launch
-struct EpsSink;
-EpsSink *eps_sink_alloc();
-void eps_sink_free(EpsSink *s);
-void eps_sink_reset(EpsSink *s);
-void launch_lanes_eps(mivi_ctx *c, EpsSink *s, int lanes);               // the lanes' recorded first draws as one launch
-struct StlSink;
-StlSink *stl_sinks_alloc(int n);
-void stl_sinks_free(StlSink *s);
-void stl_sink_reset(StlSink *s, int lane);
-int stl_sink_count(const StlSink *s, int lane);
-bool launch_lanes_stl(mivi_ctx *c, StlSink *s, int lanes, bool with_F);  // one solve launch with all lanes' jobs + one combining product
+// what a LaneRecorder holds, issued on c->stream for lanes 0 .. lanes - 1 (false: the lanes' recorded launches do not match; nothing was launched)
+bool launch_lanes_prod(mivi_ctx *c, const LaneRecorder &rec, int lanes, int which);   // one launch for all lanes (blockIdx.y = lane); which: 0 sampling, 1 dense target
+bool launch_lanes_vjp(mivi_ctx *c, const LaneRecorder &rec, int lanes);
+void launch_lanes_eps(mivi_ctx *c, const LaneRecorder &rec, int lanes);              // kernels_fullrank.hip: the first draws of the lanes that made one, as one launch
+bool launch_lanes_stl(mivi_ctx *c, const LaneRecorder &rec, int lanes, bool with_F);   // kernels_stl.hip: one solve launch with all lanes' jobs + one combining product
+void launch_lanes_value(mivi_ctx *c, const void *params, LaneRecorder &rec);         // kernels_update.hip: the recorded closing value kernels as one launch
 bool lds_bf16x3();   // products on the bf16 matrix cores (three-way exact operand split); MIVI_FR_F32MFMA=1 turns it off
 void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, const ValueJob *self, const FusedUpdate *upd);
 bool lds_stein_ok(const mivi_ctx *c, int M);
