@@ -16,8 +16,9 @@ from . import optimize as _optimize
 from .optimize import (KLMinRepGradDescent, KLMinRepGradProxDescent, ADVI, KLMinScoreGradDescent, BBVI, ClipScale, IdentityOperator,
                        ProximalLocationScaleEntropy, Descent, Adam, DoG, DoWG, COCOB, NoAveraging,
                        PolynomialAveraging, optimize, step, output)
-from .measure_space import KLMinSqrtNaturalGradDescent
-from .context import MiviContext
+from .measure_space import KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent
+from . import measure_space as _measure_space
+from .context import MiviContext, NATGRAD_SMALL_D
 from .problems import subsample, LogRegSubset, FunnelConstrainedProblem, StackedBijector, TransformedProblem, ADgradient
 from . import forwarddiff
 from .subsampling import (ReshufflingBatchSubsampling, ReshufflingBatchSubsamplingState, SubsampledObjective,
@@ -29,7 +30,7 @@ from . import distributed
 def estimate_objective(*args, **kwargs):
     """Dispatches like the reference: (rng, alg|obj, q, prob) or (alg|obj, q, prob)."""
     head = args[1] if isinstance(args[0], PhiloxRNG) else args[0]
-    if isinstance(head, _optimize.PARAM_SPACE_SGD + (KLMinSqrtNaturalGradDescent,)):
+    if isinstance(head, _optimize.PARAM_SPACE_SGD + _measure_space.ALGORITHMS):
         return _optimize.estimate_objective(*args, **kwargs)
     if isinstance(head, SubsampledObjective):
         return _subsampling.estimate_objective(*args, **kwargs)
@@ -45,7 +46,7 @@ def estimate_gradient_(rng, obj, *args, **kwargs):
 
 def init(*args, **kwargs):
     """init(rng, alg, q_init, prob)  or  init(rng, obj, adtype, q, prob, params, restructure)."""
-    if isinstance(args[1], _optimize.PARAM_SPACE_SGD + (KLMinSqrtNaturalGradDescent,)):
+    if isinstance(args[1], _optimize.PARAM_SPACE_SGD + _measure_space.ALGORITHMS):
         return _optimize.init(*args, **kwargs)
     if isinstance(args[1], SubsampledObjective):
         return _subsampling.init(*args, **kwargs)

@@ -10,6 +10,8 @@ from . import _lib
 from .families import FULLRANK, MEANFIELD
 from . import problems as P
 
+NATGRAD_SMALL_D = 44   # MIVI_NATGRAD_SMALL_D (include/mivi.h): up to this d mivi_natgrad_update is the one-workgroup kernel, above it the tile path
+
 _NP2MIVI = {np.dtype(np.float32): _lib.F32, np.dtype(np.float64): _lib.F64}
 
 
@@ -349,6 +351,45 @@ class MiviContext:
         elbo = self.empty(int(count)) if elbo is None else elbo
         self._raise_cb(self.lib.mivi_sqrt_ngd_steps(self.h, self._p(params), idx0, int(count), int(n_samples), 1 if second_order else 0,
                                                     float(stepsize), self._p(elbo)))
+        return elbo
+
+    def natgrad_init(self, params, state=None):
+        """mivi_natgrad_init: the device tensor [S; Sigma] (2 d^2: precision C^-T C^-1 and covariance C C', column-major) of the device
+        parameters `params` ([m; vec C])."""
+        state = self.empty(2 * self.d * self.d) if state is None else state
+        self._chk(self.lib.mivi_natgrad_init(self.h, self._p(params), self._p(state)))
+        return state
+
+    def natgrad_update(self, params, state, grad, hess, stepsize, ensure_posdef=True, entropy=None):
+        """mivi_natgrad_update: the natural-gradient update of the device tensors `params` ([m; vec C]) and `state` ([S; Sigma]) in place
+        from grad (d) and hess (d*d column-major, as gauss_expected_grad_hess fills it); returns entropy(q') as a 1-element device tensor.
+        The new scale C' is the LOWER Cholesky factor of Sigma' (the reference's is an upper-triangular factor of the same Sigma')."""
+        entropy = self.empty(1) if entropy is None else entropy
+        hess = hess.t() if hess.dim() == 2 else hess   # the (d, d) matrix view gauss_expected_grad_hess returns -> its column-major storage
+        if not hess.is_contiguous():
+            hess = hess.contiguous()
+        self._chk(self.lib.mivi_natgrad_update(self.h, self._p(params), self._p(state), self._p(grad), self._p(hess), float(stepsize),
+                                               1 if ensure_posdef else 0, self._p(entropy)))
+        return entropy
+
+    def natgrad_update_host(self, params, state, grad, hess, stepsize, ensure_posdef=True):
+        """mivi_natgrad_update_host on numpy arrays: params ([m; vec C]), state ([S; Sigma], 2 d^2), grad (d), hess ((d, d) matrix); returns
+        (params', state', entropy(q'))."""
+        p = np.array(params, dtype=self.np_dtype, copy=True)
+        st = np.array(state, dtype=self.np_dtype, copy=True)
+        g = np.ascontiguousarray(grad, dtype=self.np_dtype)
+        H = np.asfortranarray(hess, dtype=self.np_dtype)
+        ent = np.zeros(1, dtype=self.np_dtype)
+        self._chk(self.lib.mivi_natgrad_update_host(self.h, p.ctypes.data, st.ctypes.data, g.ctypes.data, H.ctypes.data, float(stepsize),
+                                                    1 if ensure_posdef else 0, ent.ctypes.data))
+        return p, st, ent[0]
+
+    def natgrad_steps(self, params, state, idx0, count, stepsize, ensure_posdef=True, n_samples=0, second_order=False, elbo=None):
+        """mivi_natgrad_steps: `count` iterations {estimator (index idx0 + t), update} on the device tensors `params` and `state`; returns
+        elbo (count)."""
+        elbo = self.empty(int(count)) if elbo is None else elbo
+        self._raise_cb(self.lib.mivi_natgrad_steps(self.h, self._p(params), self._p(state), idx0, int(count), int(n_samples),
+                                                   1 if second_order else 0, float(stepsize), 1 if ensure_posdef else 0, self._p(elbo)))
         return elbo
 
     def estimate_partials(self, params, idx, partials=None):

@@ -14,9 +14,7 @@ static mivi_status_t ngd_update(mivi_ctx *c, void *params, const void *grad, con
   return MIVI_OK;
 }
 
-// c->ngd_est, sized: [scalar (16 bytes: entropy or logpi_avg); grad (d); hess (d x d), 16-byte aligned behind grad]
-struct NgdEst { char *scalar, *grad, *hess; };
-static mivi_status_t ngd_est(mivi_ctx *c, NgdEst *e) {
+mivi_status_t ngd_est(mivi_ctx *c, NgdEst *e) {
   const size_t es = c->esize, d = (size_t)c->cfg.d, goff = (d * es + 15) / 16 * 16;
   const mivi_status_t s = ensure(c, c->ngd_est, 16 + goff + d * d * es, false);
   if (s) return s;

@@ -1,5 +1,5 @@
-"""Measure-space algorithms: KLMinSqrtNaturalGradDescent, the host-side mirror of
-src/algorithms/klminsqrtnaturalgraddescent.jl (AdvancedVI.jl v0.7.0) over libmivi.
+"""Measure-space algorithms: KLMinSqrtNaturalGradDescent and KLMinNaturalGradDescent, the host-side mirrors of
+src/algorithms/klminsqrtnaturalgraddescent.jl and src/algorithms/klminnaturalgraddescent.jl (AdvancedVI.jl v0.7.0) over libmivi.
 
     KLMinSqrtNaturalGradDescent(stepsize, n_samples=1, subsampling=None)     :39-44
     init(rng, alg, q_init, prob)                                             :55-75
@@ -10,7 +10,14 @@ src/algorithms/klminsqrtnaturalgraddescent.jl (AdvancedVI.jl v0.7.0) over libmiv
 The variational parameters [m; vec(C)] stay resident in HBM between steps.  A step is the tuned inner estimator
 (mivi_gauss_expected_grad_hess / _hess2, chosen by the target's capability like gauss_expected_grad_hess.jl:31-32) followed by
 mivi_sqrt_ngd_update; `optimize` without a callback and without subsampling runs whole chunks of steps inside mivi_sqrt_ngd_steps, with
-bitwise the same iterates as the host-driven `step` loop."""
+bitwise the same iterates as the host-driven `step` loop.
+
+KLMinNaturalGradDescent(stepsize, n_samples=1, ensure_posdef=True, subsampling=None) (klminnaturalgraddescent.jl:56-62; init :64-91, step
+:95-153, output :93, estimate_objective :172-192) is the same loop around mivi_natgrad_update / mivi_natgrad_steps; besides the parameters
+its state carries the device buffer [S; Sigma] (precision and covariance, :83-87, mivi_natgrad_init).  The two algorithms differ in their
+update call and that one buffer; everything else below is shared.  Scale convention: the reference's new scale is upper triangular (the
+adjoint of the inverse of a lower Cholesky factor of S'); this library's iterate carries the LOWER Cholesky factor C' of Sigma' = S'^-1 --
+the same distribution, the same recursion in (m, S, Sigma); only the pairing of draws with samples differs."""
 from __future__ import annotations
 
 from . import objectives as O
@@ -37,26 +44,78 @@ class KLMinSqrtNaturalGradDescent:
         return f"KLMinSqrtNaturalGradDescent(stepsize={self.stepsize}, n_samples={self.n_samples}, subsampling={self.subsampling})"
 
 
+class KLMinNaturalGradDescent:
+    """KL minimisation by natural-gradient descent on the Gaussian's precision, also known as variational online Newton
+    (klminnaturalgraddescent.jl:2-62).  Needs a full-rank Gaussian family and a target with at least first-order capability; a target with
+    second-order capability has its Hessians used, otherwise the Stein identity on gradients.  `ensure_posdef` selects the update of the
+    precision that stays positive definite for any Hessian estimate (:129-130) over the plain convex combination (:132); like the reference,
+    the first-order branch does not require it.  The scale of the iterates is the lower Cholesky factor of the covariance (the reference's is
+    an upper-triangular factor of the same covariance: see the module docstring)."""
+
+    def __init__(self, stepsize, n_samples: int = 1, ensure_posdef: bool = True, subsampling=None, device: int = 0):
+        if not isinstance(n_samples, int) or n_samples < 1:
+            raise ValueError("n_samples must be a positive Int")
+        self.stepsize = float(stepsize)
+        self.n_samples = int(n_samples)
+        self.ensure_posdef = bool(ensure_posdef)
+        self.subsampling = subsampling
+        self.device = int(device)
+
+    def __repr__(self):
+        return (f"KLMinNaturalGradDescent(stepsize={self.stepsize}, n_samples={self.n_samples}, ensure_posdef={self.ensure_posdef}, "
+                f"subsampling={self.subsampling})")
+
+
+ALGORITHMS = (KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent)
+
+
 def _second_order(prob) -> bool:
     """LogDensityOrder{1}() < capabilities(prob): the branch test of gauss_expected_grad_hess.jl:31-32."""
     return P.LogDensityOrder(1) < P.capabilities(prob)
 
 
-def init(rng, alg: KLMinSqrtNaturalGradDescent, q_init, prob):
-    """klminsqrtnaturalgraddescent.jl:55-75."""
+def _update(alg, ctx, state, grad, hess):
+    """The algorithm's update of state["params"] (and of its own state buffer) in place; returns entropy(q') as a 1-element device tensor."""
+    if isinstance(alg, KLMinNaturalGradDescent):
+        return ctx.natgrad_update(state["params"], state["natgrad"], grad, hess, alg.stepsize, alg.ensure_posdef)
+    return ctx.sqrt_ngd_update(state["params"], grad, hess, alg.stepsize)
+
+
+def _device_steps(alg, ctx, state, idx0, n, second):
+    """`n` whole steps inside the library; returns their elbo (a device tensor)."""
+    if isinstance(alg, KLMinNaturalGradDescent):
+        return ctx.natgrad_steps(state["params"], state["natgrad"], idx0, n, alg.stepsize, alg.ensure_posdef, n_samples=alg.n_samples,
+                                 second_order=second)
+    return ctx.sqrt_ngd_steps(state["params"], idx0, n, alg.stepsize, n_samples=alg.n_samples, second_order=second)
+
+
+def _own_buffers(state):
+    """The state with copies of the device buffers a step advances in place."""
+    state = dict(state, params=state["params"].clone())
+    if "natgrad" in state:
+        state["natgrad"] = state["natgrad"].clone()
+    return state
+
+
+def init(rng, alg, q_init, prob):
+    """klminsqrtnaturalgraddescent.jl:55-75 / klminnaturalgraddescent.jl:64-91."""
+    name = type(alg).__name__
     if not isinstance(q_init, MvLocationScale) or q_init.family != FULLRANK:
-        raise TypeError("`KLMinSqrtNaturalGradDescent` expects a Gaussian with a lower-triangular scale (FullRankGaussian) as q_init")
+        raise TypeError(f"`{name}` expects a Gaussian with a lower-triangular scale (FullRankGaussian) as q_init")
     capability = P.capabilities(prob)
-    if capability < P.LogDensityOrder(1):   # :64-70 (ArgumentError)
-        raise ValueError("`KLMinSqrtNaturalGradDescent` requires at least first-order differentiation capability. The capability of the "
+    if capability < P.LogDensityOrder(1):   # :64-70 of either file (ArgumentError)
+        raise ValueError(f"`{name}` requires at least first-order differentiation capability. The capability of the "
                          f"supplied `LogDensityProblem` is {capability}.")
     sub_st = None if alg.subsampling is None else S.init_subsampling(rng, alg.subsampling)
     params_h, re = destructure(q_init)
     ctx = MiviContext(q_init.eltype, FULLRANK, len(q_init), min(alg.n_samples, 16384), O.ClosedFormEntropy.code, rng.seed, device=alg.device)
     ctx.set_problem(prob)
     d = len(q_init)
-    return dict(q=q_init, prob=prob, iteration=0, sub_st=sub_st, ctx=ctx, params=ctx.to_device(params_h).clone(), restructure=re,
-                grad_buf=ctx.empty(d), hess_buf=ctx.empty(d * d))
+    state = dict(q=q_init, prob=prob, iteration=0, sub_st=sub_st, ctx=ctx, params=ctx.to_device(params_h).clone(), restructure=re,
+                 grad_buf=ctx.empty(d), hess_buf=ctx.empty(d * d))
+    if isinstance(alg, KLMinNaturalGradDescent):   # :83-87: prec and qcov, carried from step to step
+        state["natgrad"] = ctx.natgrad_init(state["params"])
+    return state
 
 
 def _q_of(state):
@@ -66,13 +125,13 @@ def _q_of(state):
 
 
 def output(alg, state):
-    """output(::KLMinSqrtNaturalGradDescent, state) = state.q: the last iterate, no averaging (:77)."""
+    """output(alg, state) = state.q: the last iterate, no averaging (klminsqrtnaturalgraddescent.jl:77, klminnaturalgraddescent.jl:93)."""
     return _q_of(state)
 
 
-def step(rng, alg: KLMinSqrtNaturalGradDescent, state, callback, *objargs):
-    """klminsqrtnaturalgraddescent.jl:79-127.  The parameters live in ONE device buffer that the update advances in place: the state passed in is
-    consumed by the call (use the returned one; `optimize(state=...)` works on a copy of the buffer and leaves its argument as it was)."""
+def step(rng, alg, state, callback, *objargs):
+    """klminsqrtnaturalgraddescent.jl:79-127 / klminnaturalgraddescent.jl:95-153.  The parameters (and [S; Sigma]) live in ONE device buffer
+    each that the update advances in place: the state passed in is consumed by the call (use the returned one; `optimize(state=...)` works on a copy of the buffer and leaves its argument as it was)."""
     state = dict(state)
     ctx, params = state["ctx"], state["params"]
     state["iteration"] += 1
@@ -83,9 +142,9 @@ def step(rng, alg: KLMinSqrtNaturalGradDescent, state, callback, *objargs):
         ctx.set_problem(prob_sub)
     logpi, grad, _ = ctx.gauss_expected_grad_hess(params, rng.next_index(), alg.n_samples, state["grad_buf"], state["hess_buf"],
                                                   second_order=_second_order(prob_sub))
-    entropy = ctx.sqrt_ngd_update(params, grad, state["hess_buf"], alg.stepsize)
-    elbo = float((logpi + entropy).item())   # (one addition in the context's dtype: what mivi_sqrt_ngd_steps records)
-    ctx.synchronize()                        # a scale diagonal that left the positive numbers raises here (MIVI_ERR_NONPOSITIVE_SCALE)
+    entropy = _update(alg, ctx, state, grad, state["hess_buf"])
+    elbo = float((logpi + entropy).item())   # (one addition in the context's dtype: what the device step loops record)
+    ctx.synchronize()                        # a scale diagonal / pivot that left the positive numbers raises here (MIVI_ERR_NONPOSITIVE_SCALE)
     state["q"] = None                        # materialised lazily by `output` / callbacks (the parameters are device resident)
     info = {"elbo": elbo, **sub_inf}
     if callback is not None:
@@ -96,9 +155,9 @@ def step(rng, alg: KLMinSqrtNaturalGradDescent, state, callback, *objargs):
 
 
 def estimate_objective(rng, alg, q=None, prob=None, n_samples=None):
-    """estimate_objective([rng,] alg, q, prob; n_samples): klminsqrtnaturalgraddescent.jl:146-165 -- the negative ELBO with the Monte-Carlo
-    entropy; with subsampling, the average over one pass through the batches."""
-    if isinstance(rng, KLMinSqrtNaturalGradDescent):
+    """estimate_objective([rng,] alg, q, prob; n_samples): klminsqrtnaturalgraddescent.jl:146-165 / klminnaturalgraddescent.jl:172-192 -- the
+    negative ELBO with the Monte-Carlo entropy; with subsampling, the average over one pass through the batches."""
+    if isinstance(rng, ALGORITHMS):
         rng, alg, q, prob = O.default_rng(), rng, alg, q
     n = int(n_samples) if n_samples is not None else alg.n_samples
     obj = O.RepGradELBO(n, entropy=O.MonteCarloEntropy())
@@ -110,12 +169,12 @@ def estimate_objective(rng, alg, q=None, prob=None, n_samples=None):
 
 def _steps_on_device(rng, alg, max_iter, state, show_progress):
     from .optimize import DEVICE_LOOP_CHUNK
-    ctx, params = state["ctx"], state["params"]
+    ctx = state["ctx"]
     second = _second_order(state["prob"])
     info_total, done = [], 0
     while done < max_iter:
         n = min(DEVICE_LOOP_CHUNK, max_iter - done)
-        elbo = ctx.sqrt_ngd_steps(params, rng.counter, n, alg.stepsize, n_samples=alg.n_samples, second_order=second)
+        elbo = _device_steps(alg, ctx, state, rng.counter, n, second)
         ctx.synchronize()
         for _ in range(n):
             rng.next_index()
@@ -133,12 +192,12 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
              device_loop=True):
     """optimize([rng,] algorithm, max_iter, prob, q_init; show_progress, state, callback): src/optimize.jl:42-94 for this algorithm.
     Returns (output, info, state)."""
-    if isinstance(rng, KLMinSqrtNaturalGradDescent):   # default-rng overload, optimize.jl:83-94
+    if isinstance(rng, ALGORITHMS):   # default-rng overload, optimize.jl:83-94
         rng, algorithm, max_iter, prob, q_init = O.default_rng(), rng, algorithm, max_iter, prob
     if state is None:
         state = init(rng, algorithm, q_init, prob)
-    else:   # a warm start: the caller's state (its parameter buffer and cached q) stays what it was
-        state = dict(state, params=state["params"].clone())
+    else:   # a warm start: the caller's state (its device buffers and cached q) stays what it was
+        state = _own_buffers(state)
     if device_loop and callback is None and algorithm.subsampling is None and not objargs and max_iter > 0:
         state = dict(state)
         info_total = _steps_on_device(rng, algorithm, max_iter, state, show_progress)

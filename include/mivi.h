@@ -275,6 +275,43 @@ mivi_status_t mivi_sqrt_ngd_update_host(mivi_ctx_t *ctx, void *params_host, cons
 mivi_status_t mivi_sqrt_ngd_steps(mivi_ctx_t *ctx, void *params_dev, uint64_t estimate_idx0, int32_t count, int32_t n_samples,
                                   int32_t second_order, double stepsize, void *elbo_dev);
 
+/* KLMinNaturalGradDescent (variational online Newton, src/algorithms/klminnaturalgraddescent.jl).  Besides the parameters [m; vec(C)] the
+ * algorithm carries state_dev T[2*d*d] = [S; Sigma]: the precision (`prec`) and the covariance (`qcov`) of q, d x d column-major, both stored
+ * as full symmetric matrices with the two triangles bitwise mirrored, carried from step to step and not recomputed from the scale.
+ * mivi_natgrad_init (:83-87): S <- C^-T C^-1 (a triangular inverse and one product), Sigma <- C C'; params_dev is only read.
+ * mivi_natgrad_update (:129-145), params and state IN PLACE, grad (T[d]) and hess (T[d*d], column-major) read-only and hess used as it comes:
+ *   ensure_posdef != 0:  Gh = S + hess    S' = Hermitian(S - eta Gh + eta^2/2 Gh Sigma Gh)   (:129-130)
+ *   ensure_posdef == 0:                   S' = Hermitian((1 - eta) S - eta hess)             (:132)
+ *   S' = Lr' Lr (Lr lower triangular)     C' = Lr^-1     Sigma' = C' C''     m' = m - eta C' (C'' (-grad))   (:134-139)
+ *   entropy_dev T[1] <- entropy(q') = d/2 (1 + log 2 pi) + sum_i log C'_ii (the term of :145); may be NULL
+ * Hermitian(.) is the reference's: the UPPER triangle of the operand, mirrored (not the symmetric part; hess is not symmetric on the Stein
+ * branch).  SCALE CONVENTION, the one deviation from the reference: its new scale is the upper-triangular adjoint of the inverse of a lower
+ * Cholesky factor of S' (:136-138); this library's full-rank family stores a lower-triangular C with exact zeros above the diagonal, so the
+ * iterate is q' = (m', C') with C' the LOWER Cholesky factor of Sigma' = S'^-1 -- the same distribution and the same recursion in
+ * (m, S, Sigma) as a function of (grad, hess); only the pairing of draws with samples differs (z = C' u + m).
+ * d <= MIVI_NATGRAD_SMALL_D: one workgroup, one launch; above: 64 x 64 tiles on the matrix cores over context-owned padded scratch, a blocked
+ * factorisation by 64-row panels and a blocked triangular inverse (csrc/kernels_natgrad.hip; 3 nT + 5 launches, + 2 with ensure_posdef,
+ * nT = ceil(d / 64)).  m' is formed as m - eta x with x = C' C'' (-grad) refined once against S' (r = -grad - S' x, x += C' C'' r; float64
+ * sums), which an ill-conditioned S' needs in float32.  Bitwise repeatable (no floating-point atomics, one summation order).  A pivot that is not a positive finite number
+ * (the reference throws PosDefException there) or a non-finite entropy sets the sticky device flag (mivi_synchronize:
+ * MIVI_ERR_NONPOSITIVE_SCALE / MIVI_ERR_NONFINITE); the pivot is replaced by 1, the call returns, and the contents of params and state are
+ * then unspecified.  The _host form (host buffers, synchronous) returns the status itself.  Any d >= 1.  MIVI_ERR_UNSUPPORTED: a mean-field context. */
+#define MIVI_NATGRAD_SMALL_D 44
+mivi_status_t mivi_natgrad_init(mivi_ctx_t *ctx, const void *params_dev, void *state_dev);
+mivi_status_t mivi_natgrad_update(mivi_ctx_t *ctx, void *params_dev, void *state_dev, const void *grad_dev, const void *hess_dev,
+                                  double stepsize, int32_t ensure_posdef, void *entropy_dev);
+mivi_status_t mivi_natgrad_update_host(mivi_ctx_t *ctx, void *params_host, void *state_host, const void *grad_host, const void *hess_host,
+                                       double stepsize, int32_t ensure_posdef, void *entropy_host);
+/* `count` whole iterations of step(rng, alg::KLMinNaturalGradDescent, ...) (src/algorithms/klminnaturalgraddescent.jl:95-153, without
+ * subsampling and callback), parameters and state resident in HBM and no host round trip: iteration t estimates with index estimate_idx0 + t
+ * (:120; second_order as for mivi_sqrt_ngd_steps), then updates; elbo_dev T[count] (or NULL) <- logpi_avg_t + entropy(q'_t) (:145), written
+ * with the flags by the update's last launch.  The same launches and arithmetic as `count` calls of the estimator entry followed by
+ * mivi_natgrad_update: bitwise equal to them.  Asynchronous for built-in targets.  Refusals as for mivi_sqrt_ngd_steps (a mean-field
+ * context, a sharded context, no target, what the chosen estimator entry refuses); a refused call launches nothing.  Like the reference it
+ * does not require ensure_posdef for the first-order branch. */
+mivi_status_t mivi_natgrad_steps(mivi_ctx_t *ctx, void *params_dev, void *state_dev, uint64_t estimate_idx0, int32_t count, int32_t n_samples,
+                                 int32_t second_order, double stepsize, int32_t ensure_posdef, void *elbo_dev);
+
 /* ---- multi-GPU: shard the MC batch, all-reduce the partials, finalize -------------------------- *
  * No counterpart in the reference (single task).  partials_dev: T[partials_len] un-normalised sums over
  * this context's samples; the caller all-reduces (RCCL sum) and calls mivi_finalize on every rank. */
