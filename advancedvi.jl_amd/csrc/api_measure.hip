@@ -1,0 +1,161 @@
+// libmivi C ABI, parts 10 and 11: the measure-space algorithms on the device-resident [m; vec C] --
+//   KLMinSqrtNaturalGradDescent (src/algorithms/klminsqrtnaturalgraddescent.jl): the square-root natural-gradient update (kernels_ngd.hip);
+//   KLMinNaturalGradDescent (src/algorithms/klminnaturalgraddescent.jl): the state [S; Sigma] of `init` (:83-87) and the natural-gradient
+//     update of `step` (:129-145) (kernels_natgrad.hip; its scale convention, a LOWER-triangular C' where the reference's new scale is upper
+//     triangular, is stated there and in include/mivi.h)
+// -- and whole steps {estimator, update} without a host round trip.  A step is the existing estimator entry (mivi_gauss_expected_grad_hess /
+// _hess2) into context-owned buffers followed by the update, whose last launch also forms elbo = logpi_avg + entropy(q') and the sticky
+// flags: launches are fused, arithmetic is not, so the _steps entries are bitwise the single calls.  The algorithms differ in the update
+// alone (Update); the guards, the step loop and the _host staging are written once.
+#include "api_common.h"
+
+#include <string>
+
+namespace {
+
+// the estimator outputs of the step loops and the inputs of the _host updates -- c->ngd_est, sized: [scalar (16 bytes: entropy or
+// logpi_avg); grad (d); hess (d x d), 16-byte aligned behind grad]
+struct NgdEst { char *scalar, *grad, *hess; };
+
+mivi_status_t ngd_est(mivi_ctx *c, NgdEst *e) {
+  const size_t es = c->esize, d = (size_t)c->cfg.d, goff = (d * es + 15) / 16 * 16;
+  const mivi_status_t s = ensure(c, c->ngd_est, 16 + goff + d * d * es, false);
+  if (s) return s;
+  char *b = (char *)c->ngd_est.p;
+  *e = NgdEst{b, b + 16, b + 16 + goff};
+  return MIVI_OK;
+}
+
+// Which update: the natural-gradient one on (params, state) or, state == nullptr, the square-root one on params alone.  Both work in the
+// context's one scratch pair, which holds nothing between calls: each ensures it to its own need.
+struct Update {
+  void *state;
+  int ensure_posdef;
+
+  mivi_status_t scratch(mivi_ctx *c) const {
+    const size_t work = state ? natgrad_work_bytes(c) : ngd_work_bytes(c);
+    if (!work) return MIVI_OK;   // (the one-workgroup kernels need none)
+    const mivi_status_t s = ensure(c, c->ms_work, work, false);
+    return s ? s : ensure(c, c->ms_part, state ? natgrad_part_bytes(c) : ngd_part_bytes(c), false);
+  }
+  mivi_status_t operator()(mivi_ctx *c, void *params, const void *grad, const void *hess, double stepsize, const void *logpi, void *entropy,
+                           void *elbo) const {
+    const mivi_status_t s = scratch(c);
+    if (s) return s;
+    if (state) launch_natgrad_update(c, params, state, grad, hess, stepsize, ensure_posdef, logpi, entropy, elbo);
+    else launch_ngd_update(c, params, grad, hess, stepsize, logpi, entropy, elbo);
+    HIPCHK(c, hipGetLastError());
+    return MIVI_OK;
+  }
+};
+
+}  // namespace
+
+// who: the entry's name, for the _steps entries "<entry>: <algorithm>"
+static mivi_status_t need_fullrank(mivi_ctx *c, const char *who) {
+  if (c->cfg.family == MIVI_FULLRANK) return MIVI_OK;
+  return fail(c, MIVI_ERR_UNSUPPORTED, (std::string(who) + " takes a triangular scale (full-rank family)").c_str());
+}
+
+// a step needs the whole estimate on this context, and a target to estimate on
+static mivi_status_t need_whole_estimate(mivi_ctx *c, const char *entry) {
+  if (c->cfg.m_offset != 0 || (c->cfg.m_total != 0 && c->cfg.m_total != c->cfg.n_mc))
+    return fail(c, MIVI_ERR_UNSUPPORTED, (std::string(entry) + ": a sharded context is not supported (the update needs the whole estimate)").c_str());
+  if (c->target == TGT_NONE) return fail(c, MIVI_ERR_NO_TARGET, "no target set");
+  return MIVI_OK;
+}
+
+// count iterations {estimator (index idx0 + t) -> update}
+static mivi_status_t run_steps(mivi_ctx *c, const char *entry, const char *algorithm, const Update &update, void *params, uint64_t idx0, int32_t count,
+                               int32_t n_samples, int32_t second_order, double stepsize, void *elbo) {
+  mivi_status_t s;
+  if ((s = need_fullrank(c, (std::string(entry) + ": " + algorithm).c_str())) || (s = need_whole_estimate(c, entry))) return s;
+  (void)hipSetDevice(c->cfg.device);
+  NgdEst e;   // (its scalar: logpi_avg)
+  // Everything that can fail for want of memory, before any launch.  (mivi_sqrt_ngd_steps used to ensure its scratch inside the first
+  // iteration, after the estimator had launched: the one change in observable order, and only where an allocation fails.)
+  if ((s = ngd_est(c, &e)) || (s = update.scratch(c))) return s;
+  for (int32_t t = 0; t < count; ++t) {
+    // (the estimator entries refuse what they cannot do -- no Hessian / a Stacked bijector for the second-order branch, d beyond the solve --
+    // before they launch anything, so a refused call leaves parameters and state untouched)
+    s = second_order ? mivi_gauss_expected_grad_hess2(c, params, idx0 + (uint64_t)t, n_samples, e.scalar, e.grad, e.hess)
+                     : mivi_gauss_expected_grad_hess(c, params, idx0 + (uint64_t)t, n_samples, e.scalar, e.grad, e.hess);
+    if (s) return s;
+    if ((s = update(c, params, e.grad, e.hess, stepsize, e.scalar, nullptr, elbo ? (char *)elbo + (size_t)t * c->esize : nullptr))) return s;
+  }
+  return MIVI_OK;
+}
+
+// the _host form of an update: parameters, g and H (and, state_h != nullptr, the state: the natural-gradient update) staged into
+// context-owned buffers, the update, the results back
+static mivi_status_t update_host(mivi_ctx *c, const char *entry, void *params_h, void *state_h, const void *grad_h, const void *hess_h, double stepsize,
+                                 int ensure_posdef, void *entropy_h) {
+  mivi_status_t s;
+  if ((s = need_fullrank(c, entry))) return s;
+  (void)hipSetDevice(c->cfg.device);
+  const size_t es = c->esize, d = (size_t)c->cfg.d, sb = 2 * d * d * es;
+  NgdEst e;   // (its scalar: the entropy)
+  if ((s = ngd_est(c, &e)) || (state_h && (s = ensure(c, c->natgrad_host, sb, false))) || (s = stage_params(c, params_h))) return s;
+  if (state_h) HIPCHK(c, hipMemcpyAsync(c->natgrad_host.p, state_h, sb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(e.grad, grad_h, d * es, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(e.hess, hess_h, d * d * es, hipMemcpyHostToDevice, c->stream));
+  const Update update{state_h ? c->natgrad_host.p : nullptr, ensure_posdef};
+  if ((s = update(c, c->tmp_params.p, e.grad, e.hess, stepsize, nullptr, e.scalar, nullptr))) return s;
+  return fetch_results(c, {{params_h, c->tmp_params.p, (size_t)mivi_params_len(c) * es}, {state_h, c->natgrad_host.p, sb}, {entropy_h, e.scalar, es}}, true);
+}
+
+extern "C" {
+
+mivi_status_t mivi_sqrt_ngd_update(mivi_ctx_t *c, void *params, const void *grad, const void *hess, double stepsize, void *entropy) {
+  if (!c || !params || !grad || !hess) return MIVI_ERR_BAD_ARG;
+  const mivi_status_t s = need_fullrank(c, "sqrt_ngd_update");
+  if (s) return s;
+  (void)hipSetDevice(c->cfg.device);
+  return Update{nullptr, 0}(c, params, grad, hess, stepsize, nullptr, entropy, nullptr);
+}
+
+mivi_status_t mivi_sqrt_ngd_update_host(mivi_ctx_t *c, void *params_h, const void *grad_h, const void *hess_h, double stepsize, void *entropy_h) {
+  if (!c || !params_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
+  return update_host(c, "sqrt_ngd_update", params_h, nullptr, grad_h, hess_h, stepsize, 0, entropy_h);
+}
+
+mivi_status_t mivi_sqrt_ngd_steps(mivi_ctx_t *c, void *params, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
+                                  double stepsize, void *elbo) {
+  if (!c || !params || count < 0) return MIVI_ERR_BAD_ARG;
+  return run_steps(c, "sqrt_ngd_steps", "KLMinSqrtNaturalGradDescent", Update{nullptr, 0}, params, idx0, count, n_samples, second_order, stepsize, elbo);
+}
+
+mivi_status_t mivi_natgrad_init(mivi_ctx_t *c, const void *params, void *state) {
+  if (!c || !params || !state) return MIVI_ERR_BAD_ARG;
+  mivi_status_t s;
+  if ((s = need_fullrank(c, "natgrad_init"))) return s;
+  (void)hipSetDevice(c->cfg.device);
+  if ((s = Update{state, 0}.scratch(c))) return s;
+  launch_natgrad_init(c, const_cast<void *>(params), state);
+  HIPCHK(c, hipGetLastError());
+  return MIVI_OK;
+}
+
+mivi_status_t mivi_natgrad_update(mivi_ctx_t *c, void *params, void *state, const void *grad, const void *hess, double stepsize,
+                                  int32_t ensure_posdef, void *entropy) {
+  if (!c || !params || !state || !grad || !hess) return MIVI_ERR_BAD_ARG;
+  const mivi_status_t s = need_fullrank(c, "natgrad_update");
+  if (s) return s;
+  (void)hipSetDevice(c->cfg.device);
+  return Update{state, ensure_posdef}(c, params, grad, hess, stepsize, nullptr, entropy, nullptr);
+}
+
+mivi_status_t mivi_natgrad_update_host(mivi_ctx_t *c, void *params_h, void *state_h, const void *grad_h, const void *hess_h, double stepsize,
+                                       int32_t ensure_posdef, void *entropy_h) {
+  if (!c || !params_h || !state_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
+  return update_host(c, "natgrad_update", params_h, state_h, grad_h, hess_h, stepsize, ensure_posdef, entropy_h);
+}
+
+mivi_status_t mivi_natgrad_steps(mivi_ctx_t *c, void *params, void *state, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
+                                 double stepsize, int32_t ensure_posdef, void *elbo) {
+  if (!c || !params || !state || count < 0) return MIVI_ERR_BAD_ARG;
+  return run_steps(c, "natgrad_steps", "KLMinNaturalGradDescent", Update{state, ensure_posdef}, params, idx0, count, n_samples, second_order, stepsize,
+                   elbo);
+}
+
+}  // extern "C"

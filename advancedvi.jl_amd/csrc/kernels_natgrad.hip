@@ -33,6 +33,8 @@
 //               in x, which the one-workgroup kernel of an f32 context cannot afford); the last launch's first workgroup adds the panels' log sums in
 //               order and writes entropy / elbo / flags.  The one-workgroup kernel forms m' the same way.
 // 3 nT + 5 (+ 2) launches: 55 at d = 1024 with ensure_posdef.  The only ordering between workgroups is the order of the launches.
+// The chunked tile product, the mean's column-dot and row-matvec bodies, the tile geometry and the finish (entropy / elbo / flags) are
+// ngd_tile.h's, shared with kernels_ngd.hip, as is the context's scratch pair (ms_work, ms_part).
 #include "mivi_internal.h"
 #include "ngd_tile.h"
 
@@ -53,28 +55,8 @@ struct NatgradArgs {
   double *part;                // [2][nT]: sum log C'_ii of a panel, its count of bad pivots
   double *vec;                 // [4][ldp]: v = C'' (-g), x = C' v, r = -g - S' x, w = C'' r
   double eta;
-  const TI *logpi;             // nullable: elbo = *logpi + entropy(q')
-  TI *entropy_out;             // nullable
-  TI *elbo_out;                // nullable
-  int *status;                 // bit 0: entropy / elbo not finite, bit 1: a pivot that is not a positive finite number
+  NgdOut<TI> out;              // entropy / elbo / flags (ngd_tile.h)
 };
-
-__device__ __forceinline__ bool natgrad_bad(double p) { return !(p > 0.0) || !isfinite(p); }
-
-template <typename T, typename TI>
-__device__ __forceinline__ void natgrad_finish(const NatgradArgs<T, TI> &a, double logsum, int bad) {
-  const double ent = 0.5 * (double)a.d * (1.0 + kLog2Pi) + logsum;
-  const TI ent_t = (TI)ent;
-  if (a.entropy_out) *a.entropy_out = ent_t;
-  bool finite = isfinite((double)ent_t);
-  if (a.elbo_out) {
-    const TI e = (a.logpi ? *a.logpi : TI(0)) + ent_t;
-    *a.elbo_out = e;
-    finite = finite && isfinite((double)e);
-  }
-  const int bits = (bad ? 2 : 0) | (finite ? 0 : 1);
-  if (bits) atomicOr(a.status, bits);
-}
 
 // ---- a triangle of at most 64 rows in LDS (row-major, leading dimension ld): 256 threads, all of them call these ---------------------------
 // The lower triangle of s holds a symmetric A.  On return it holds Lr with A = Lr' Lr: column c = n-1 .. 0 takes its pivot, scales ROW c of
@@ -85,7 +67,7 @@ __device__ __forceinline__ void natgrad_factor(T *s, int ld, int n, int *sbad) {
   for (int c = n - 1; c >= 0; --c) {
     __syncthreads();
     T p = s[c * ld + c];
-    const bool bad = natgrad_bad((double)p);
+    const bool bad = ngd_bad((double)p);
     if (bad) p = T(1);
     const T l = (T)sqrt(p);
     __syncthreads();
@@ -125,6 +107,20 @@ __device__ __forceinline__ T natgrad_x(const T *s, int ld, const T *sd, int i, i
 }
 
 // ---- d <= kNatgradSmallD: one workgroup, everything in LDS ----------------------------------------------------------------------------------
+// the lower triangle of X X' (TRANS: X' X) for a lower-triangular X in LDS (row-major), mirrored into both triangles of dst (d x d)
+template <bool TRANS, typename T, typename TI>
+__device__ __forceinline__ void natgrad_syrk_small(const T *X, int ld, int d, TI *dst) {
+  for (int t = threadIdx.x; t < d * d; t += 256) {
+    const int i = t % d, j = t / d;
+    if (i < j) continue;
+    T s = T(0);
+    if (TRANS) for (int k = i; k < d; ++k) s += X[k * ld + i] * X[k * ld + j];
+    else for (int k = 0; k <= j; ++k) s += X[i * ld + k] * X[j * ld + k];
+    dst[(size_t)j * d + i] = s;
+    dst[(size_t)i * d + j] = s;
+  }
+}
+
 template <typename T, typename TI>
 __global__ __launch_bounds__(256) void k_natgrad_small(NatgradArgs<T, TI> a) {
   constexpr int LD = kNatgradSmallD + 1, N = kNatgradSmallD * LD;
@@ -183,14 +179,7 @@ __global__ __launch_bounds__(256) void k_natgrad_small(NatgradArgs<T, TI> a) {
     a.params[d + t] = x;
   }
   __syncthreads();
-  for (int t = tid; t < d * d; t += 256) {   // Sigma' = C' C'', lower triangle, mirrored
-    const int i = t % d, j = t / d;
-    if (i < j) continue;
-    T s = T(0);
-    for (int k = 0; k <= j; ++k) s += sW[i * LD + k] * sW[j * LD + k];
-    Pg[(size_t)j * d + i] = s;
-    Pg[(size_t)i * d + j] = s;
-  }
+  natgrad_syrk_small<false>(sW, LD, d, Pg);   // Sigma' = C' C''
   // m' = m - eta x, S' x = -g: x = C' (C'' (-g)), r = -g - S' x, x += C' (C'' r), sums in float64
   double x = 0.0;
   for (int pass = 0; pass < 2; ++pass) {
@@ -225,9 +214,9 @@ __global__ __launch_bounds__(256) void k_natgrad_small(NatgradArgs<T, TI> a) {
     int bad = sbad;
     for (int i = 0; i < d; ++i) {
       ls += log((double)sd[i]);
-      bad |= natgrad_bad((double)sd[i]) ? 1 : 0;
+      bad |= ngd_bad((double)sd[i]) ? 1 : 0;
     }
-    natgrad_finish(a, ls, bad);
+    ngd_finish(d, ls, bad, a.out);
   }
 }
 
@@ -247,67 +236,18 @@ __global__ __launch_bounds__(256) void k_natgrad_init_small(NatgradArgs<T, TI> a
   __syncthreads();
   if (tid == 0) {
     int bad = 0;
-    for (int i = 0; i < d; ++i) bad |= natgrad_bad((double)sC[i * LD + i]) ? 1 : 0;
-    if (bad) atomicOr(a.status, 2);
+    for (int i = 0; i < d; ++i) bad |= ngd_bad((double)sC[i * LD + i]) ? 1 : 0;
+    if (bad) atomicOr(a.out.status, 2);
   }
-  for (int t = tid; t < d * d; t += 256) {   // Sigma = C C'
-    const int i = t % d, j = t / d;
-    if (i < j) continue;
-    T s = T(0);
-    for (int k = 0; k <= j; ++k) s += sC[i * LD + k] * sC[j * LD + k];
-    Pg[(size_t)j * d + i] = s;
-    Pg[(size_t)i * d + j] = s;
-  }
+  natgrad_syrk_small<false>(sC, LD, d, Pg);   // Sigma = C C'
   __syncthreads();
   natgrad_invert(sC, LD, d, sd);
   for (int t = tid; t < d * d; t += 256) sX[(t % d) * LD + t / d] = natgrad_x(sC, LD, sd, t % d, t / d);
   __syncthreads();
-  for (int t = tid; t < d * d; t += 256) {   // S = X' X
-    const int i = t % d, j = t / d;
-    if (i < j) continue;
-    T s = T(0);
-    for (int k = i; k < d; ++k) s += sX[k * LD + i] * sX[k * LD + j];
-    Sg[(size_t)j * d + i] = s;
-    Sg[(size_t)i * d + j] = s;
-  }
+  natgrad_syrk_small<true>(sX, LD, d, Sg);   // S = X' X
 }
 
-// ---- the tile path ----------------------------------------------------------------------------------------------------------------------------
-// acc += sum_{k in [k_beg, k_end)} A(x, k) B(k, y) over one 64 x 64 tile.  AK: A(x, k) = A[x lda + k] (K contiguous in memory), otherwise
-// A[k lda + x]; BK the same for B(k, y).  The range is a multiple of 32 and the same for the whole workgroup; sA / sB: kNgdKC x kNgdLd each.
-template <typename T, bool AK, bool BK>
-__device__ __forceinline__ void natgrad_product(NgdFrag<T> &acc, const T *A, size_t lda, const T *B, size_t ldb, int k_beg, int k_end, T *sA,
-                                                T *sB) {
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), wr = w >> 1, wc = w & 1;
-  if (k_beg >= k_end) return;
-  T ra[8], rb[8];
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      ra[r] = AK ? A[(size_t)((tid >> 5) + 8 * r) * lda + k0 + (tid & 31)] : A[(size_t)(k0 + (tid >> 6) + 4 * r) * lda + (tid & 63)];
-      rb[r] = BK ? B[(size_t)((tid >> 5) + 8 * r) * ldb + k0 + (tid & 31)] : B[(size_t)(k0 + (tid >> 6) + 4 * r) * ldb + (tid & 63)];
-    }
-  };
-  auto stash = [&]() {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      if (AK) sA[(tid & 31) * kNgdLd + (tid >> 5) + 8 * r] = ra[r];
-      else sA[((tid >> 6) + 4 * r) * kNgdLd + (tid & 63)] = ra[r];
-      if (BK) sB[(tid & 31) * kNgdLd + (tid >> 5) + 8 * r] = rb[r];
-      else sB[((tid >> 6) + 4 * r) * kNgdLd + (tid & 63)] = rb[r];
-    }
-  };
-  load(k_beg);
-  for (int k0 = k_beg; k0 < k_end; k0 += kNgdKC) {
-    stash();
-    __syncthreads();
-    if (k0 + kNgdKC < k_end) load(k0 + kNgdKC);
-    acc.chunk(sA, sB, wr, wc, lane);
-    __syncthreads();
-  }
-}
-
-#define NATGRAD_WAVE const int lane = threadIdx.x & 63, w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wr = w_ >> 1, wc = w_ & 1
+// ---- the tile path (NgdFrag, ngd_product, NGD_WAVE, ngd_tile_of: ngd_tile.h) -------------------------------------------------------------------------
 
 // prep, one workgroup per tile of the padded square.  MODE 0: the update's operands; MODE 1: init's A = tril(C), identity on the padding
 template <typename T, typename TI, int MODE>
@@ -339,10 +279,10 @@ __global__ __launch_bounds__(256) void k_natgrad_gw(NatgradArgs<T, TI> a) {
   __shared__ T sAB[2 * kNgdKC * kNgdLd];
   const int nT = a.nT, ldp = a.ldp;
   const int i0 = ((int)blockIdx.x % nT) * kNgdTile, j0 = ((int)blockIdx.x / nT) * kNgdTile;
-  NATGRAD_WAVE;
+  NGD_WAVE;
   NgdFrag<T> acc;
   acc.zero();
-  natgrad_product<T, false, true>(acc, a.P + i0, ldp, a.G + (size_t)j0 * ldp, ldp, 0, ldp, sAB, sAB + kNgdKC * kNgdLd);
+  ngd_product<T, false, true>(acc, a.P + i0, ldp, a.G + (size_t)j0 * ldp, ldp, 0, ldp, sAB, sAB + kNgdKC * kNgdLd);
   acc.each(wr, wc, lane, [&](int ii, int jj, T x) { a.W[(size_t)(j0 + jj) * ldp + i0 + ii] = x; });
 }
 
@@ -354,10 +294,10 @@ __global__ __launch_bounds__(256) void k_natgrad_sp(NatgradArgs<T, TI> a) {
   int tc, tr;
   ngd_tile_of((int)blockIdx.x, tc, tr);   // tr <= tc: an upper tile
   const int i0 = tr * kNgdTile, j0 = tc * kNgdTile;
-  NATGRAD_WAVE;
+  NGD_WAVE;
   NgdFrag<T> acc;
   acc.zero();
-  natgrad_product<T, false, true>(acc, a.G + i0, ldp, a.W + (size_t)j0 * ldp, ldp, 0, ldp, sAB, sAB + kNgdKC * kNgdLd);
+  ngd_product<T, false, true>(acc, a.G + i0, ldp, a.W + (size_t)j0 * ldp, ldp, 0, ldp, sAB, sAB + kNgdKC * kNgdLd);
   const T eta = (T)a.eta, h = eta * eta / T(2);
   acc.each(wr, wc, lane, [&](int ii, int jj, T x) {
     const int i = i0 + ii, j = j0 + jj;
@@ -383,11 +323,11 @@ __device__ __forceinline__ void natgrad_diag_tile(const NatgradArgs<T, TI> &a, i
     int bad = *sbad;
     for (int r = 0; r < n; ++r) {
       ls += log((double)sd[r]);
-      bad |= natgrad_bad((double)sd[r]) ? 1 : 0;
+      bad |= ngd_bad((double)sd[r]) ? 1 : 0;
     }
     a.part[k] = ls;
     a.part[a.nT + k] = (double)bad;
-    if (bad) atomicOr(a.status, 2);
+    if (bad) atomicOr(a.out.status, 2);
   }
 }
 
@@ -399,11 +339,11 @@ __global__ __launch_bounds__(256) void k_natgrad_upd(NatgradArgs<T, TI> a) {
   __shared__ int sbad;
   const int ldp = a.ldp, k = a.k, j = (int)blockIdx.x;
   const int k0 = k * kNgdTile, j0 = j * kNgdTile;
-  NATGRAD_WAVE;
+  NGD_WAVE;
   if (threadIdx.x == 0) sbad = 0;
   NgdFrag<T> acc;
   acc.zero();
-  natgrad_product<T, true, true>(acc, a.A + (size_t)k0 * ldp, ldp, a.A + (size_t)j0 * ldp, ldp, k0 + kNgdTile, ldp, sAB, sAB + kNgdKC * kNgdLd);
+  ngd_product<T, true, true>(acc, a.A + (size_t)k0 * ldp, ldp, a.A + (size_t)j0 * ldp, ldp, k0 + kNgdTile, ldp, sAB, sAB + kNgdKC * kNgdLd);
   if (j < k) {
     acc.each(wr, wc, lane, [&](int ii, int jj, T x) { a.A[(size_t)(j0 + jj) * ldp + k0 + ii] -= x; });
     return;
@@ -431,11 +371,11 @@ template <typename T, typename TI>
 __global__ __launch_bounds__(256) void k_natgrad_scale(NatgradArgs<T, TI> a) {
   __shared__ T sAB[2 * kNgdKC * kNgdLd];
   const int ldp = a.ldp, k0 = a.k * kNgdTile, j0 = (int)blockIdx.x * kNgdTile;
-  NATGRAD_WAVE;
+  NGD_WAVE;
   NgdFrag<T> acc;
   acc.zero();
   T *tile = a.A + (size_t)j0 * ldp + k0;
-  natgrad_product<T, true, true>(acc, a.Dinv + (size_t)a.k * kNgdTile * kNgdTile, kNgdTile, tile, ldp, 0, kNgdTile, sAB, sAB + kNgdKC * kNgdLd);
+  ngd_product<T, true, true>(acc, a.Dinv + (size_t)a.k * kNgdTile * kNgdTile, kNgdTile, tile, ldp, 0, kNgdTile, sAB, sAB + kNgdKC * kNgdLd);
   acc.each(wr, wc, lane, [&](int ii, int jj, T x) { tile[(size_t)jj * ldp + ii] = x; });
 }
 
@@ -452,10 +392,10 @@ __global__ __launch_bounds__(256) void k_natgrad_mk(NatgradArgs<T, TI> a) {
     for (int t = threadIdx.x; t < kNgdTile * kNgdTile; t += 256) a.X[(size_t)(i0 + (t >> 6)) * ldp + i0 + (t & 63)] = Di[t];
     return;
   }
-  NATGRAD_WAVE;
+  NGD_WAVE;
   NgdFrag<T> acc;
   acc.zero();
-  natgrad_product<T, false, true>(acc, Di, kNgdTile, a.A + (size_t)j0 * ldp + i0, ldp, 0, kNgdTile, sAB, sAB + kNgdKC * kNgdLd);
+  ngd_product<T, false, true>(acc, Di, kNgdTile, a.A + (size_t)j0 * ldp + i0, ldp, 0, kNgdTile, sAB, sAB + kNgdKC * kNgdLd);
   acc.each(wr, wc, lane, [&](int ii, int jj, T x) { a.W[(size_t)(j0 + jj) * ldp + i0 + ii] = x; });
 }
 
@@ -464,10 +404,10 @@ template <typename T, typename TI>
 __global__ __launch_bounds__(256) void k_natgrad_inv(NatgradArgs<T, TI> a) {
   __shared__ T sAB[2 * kNgdKC * kNgdLd];
   const int ldp = a.ldp, i0 = a.k * kNgdTile, j0 = (int)blockIdx.x * kNgdTile;
-  NATGRAD_WAVE;
+  NGD_WAVE;
   NgdFrag<T> acc;
   acc.zero();
-  natgrad_product<T, false, true>(acc, a.W + i0, ldp, a.X + (size_t)j0 * ldp, ldp, j0, i0, sAB, sAB + kNgdKC * kNgdLd);
+  ngd_product<T, false, true>(acc, a.W + i0, ldp, a.X + (size_t)j0 * ldp, ldp, j0, i0, sAB, sAB + kNgdKC * kNgdLd);
   acc.each(wr, wc, lane, [&](int ii, int jj, T x) { a.X[(size_t)(j0 + jj) * ldp + i0 + ii] = -x; });
 }
 
@@ -478,29 +418,19 @@ template <typename T, typename TI, bool TRANS, bool FIN>
 __global__ __launch_bounds__(256) void k_natgrad_syrk(NatgradArgs<T, TI> a, const T *src, TI *dst) {
   __shared__ T sAB[2 * kNgdKC * kNgdLd];
   const int d = a.d, nT = a.nT, ldp = a.ldp, tid = threadIdx.x;
-  const int n_tiles = nT * (nT + 1) / 2;
-  if (FIN && (int)blockIdx.x >= n_tiles) {
-    // v_j = -sum_{k >= j} X_kj g_k for the 64 columns of tile b: one wave per column, lanes along k, a fixed shuffle tree
-    const int b = blockIdx.x - n_tiles, lane = tid & 63, w = tid >> 6;
-    for (int jj = w; jj < kNgdTile; jj += 4) {
-      const int j = b * kNgdTile + jj;
-      double s = 0.0;
-      if (j < d)
-        for (int k = j + lane; k < d; k += 64) s += (double)src[(size_t)j * ldp + k] * (double)a.grad[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      if (lane == 0) a.vec[j] = j < d ? -s : 0.0;
-    }
+  const int n_tiles = ngd_n_tiles(nT);
+  if (FIN && (int)blockIdx.x >= n_tiles) {   // v_j = -sum_{k >= j} X_kj g_k for the 64 columns of tile b
+    ngd_col_dots(src, ldp, a.grad, blockIdx.x - n_tiles, d, [&](int j, double s) { a.vec[j] = j < d ? -s : 0.0; });
     return;
   }
   int ti, tj;
   ngd_tile_of((int)blockIdx.x, ti, tj);
   const int i0 = ti * kNgdTile, j0 = tj * kNgdTile;
-  NATGRAD_WAVE;
+  NGD_WAVE;
   NgdFrag<T> acc;
   acc.zero();
-  if (TRANS) natgrad_product<T, true, true>(acc, src + (size_t)i0 * ldp, ldp, src + (size_t)j0 * ldp, ldp, i0, ldp, sAB, sAB + kNgdKC * kNgdLd);
-  else natgrad_product<T, false, false>(acc, src + i0, ldp, src + j0, ldp, 0, j0 + kNgdTile, sAB, sAB + kNgdKC * kNgdLd);
+  if (TRANS) ngd_product<T, true, true>(acc, src + (size_t)i0 * ldp, ldp, src + (size_t)j0 * ldp, ldp, i0, ldp, sAB, sAB + kNgdKC * kNgdLd);
+  else ngd_product<T, false, false>(acc, src + i0, ldp, src + j0, ldp, 0, j0 + kNgdTile, sAB, sAB + kNgdKC * kNgdLd);
   acc.each(wr, wc, lane, [&](int ii, int jj, T x) {
     const int i = i0 + ii, j = j0 + jj;
     if (i >= d || j >= d || i < j) return;
@@ -527,68 +457,52 @@ __global__ __launch_bounds__(256) void k_natgrad_mean(NatgradArgs<T, TI> a) {
   __shared__ double sred[4 * kNgdTile];
   const int d = a.d, ldp = a.ldp, tid = threadIdx.x, b = blockIdx.x;
   double *v = a.vec, *x = a.vec + ldp, *rr = a.vec + 2 * ldp, *w = a.vec + 3 * ldp;
-  if (STAGE == 3) {   // w_j = sum_{k >= j} X_kj r_k: one wave per column, lanes along k, a fixed shuffle tree
-    const int lane = tid & 63, wv = tid >> 6;
-    for (int jj = wv; jj < kNgdTile; jj += 4) {
-      const int j = b * kNgdTile + jj;
-      double s = 0.0;
-      if (j < d)
-        for (int k = j + lane; k < d; k += 64) s += (double)a.X[(size_t)j * ldp + k] * rr[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      if (lane == 0) w[j] = j < d ? s : 0.0;
-    }
+  if (STAGE == 3) {   // w_j = sum_{k >= j} X_kj r_k
+    ngd_col_dots(a.X, ldp, rr, b, d, [&](int j, double s) { w[j] = j < d ? s : 0.0; });
     return;
   }
-  // a row per lane, four partial sums per row (j mod 4), added in order
-  const int r = tid & 63, q = tid >> 6, i = b * kNgdTile + r;
-  double s = 0.0;
-  if (i < d) {
-    if (STAGE == 2) {
-      for (int j = q; j < d; j += 4) s += (double)a.A[j >= i ? (size_t)j * ldp + i : (size_t)i * ldp + j] * x[j];   // S'_ij from A's upper triangle
-    } else {
-      const double *u = STAGE == 1 ? v : w;
-      for (int j = q; j <= i; j += 4) s += (double)a.X[(size_t)j * ldp + i] * u[j];
-    }
-  }
-  sred[q * kNgdTile + r] = s;
-  __syncthreads();
-  if (q == 0 && i < d) {
-    const double tot = ((sred[r] + sred[kNgdTile + r]) + sred[2 * kNgdTile + r]) + sred[3 * kNgdTile + r];
-    if (STAGE == 1) x[i] = tot;
-    else if (STAGE == 2) rr[i] = -(double)a.grad[i] - tot;
-    else a.params[i] = (TI)((T)a.params[i] - (T)a.eta * (T)(x[i] + tot));
-  }
+  const double *u = STAGE == 1 ? v : w;
+  ngd_row_matvec(
+      b, d, STAGE == 2, sred,
+      [&](int i, int j) {
+        if (STAGE == 2) return (double)a.A[j >= i ? (size_t)j * ldp + i : (size_t)i * ldp + j] * x[j];   // S'_ij from A's upper triangle
+        return (double)a.X[(size_t)j * ldp + i] * u[j];
+      },
+      [&](int i, double tot) {
+        if (STAGE == 1) x[i] = tot;
+        else if (STAGE == 2) rr[i] = -(double)a.grad[i] - tot;
+        else a.params[i] = (TI)((T)a.params[i] - (T)a.eta * (T)(x[i] + tot));
+      });
   if (STAGE == 4 && b == 0 && tid == 0) {
     double tot = 0.0, bad = 0.0;
     for (int p = 0; p < a.nT; ++p) {
       tot += a.part[p];
       bad += a.part[a.nT + p];
     }
-    natgrad_finish(a, tot, bad > 0.0 ? 1 : 0);
+    ngd_finish(d, tot, bad > 0.0 ? 1 : 0, a.out);
   }
 }
 
 template <typename T, typename TI>
 static NatgradArgs<T, TI> natgrad_args(mivi_ctx *c, void *params, void *state) {
   NatgradArgs<T, TI> a{};
+  const NgdGeom g(c->cfg.d);
   a.d = c->cfg.d;
-  a.nT = (a.d + kNgdTile - 1) / kNgdTile;
-  a.ldp = a.nT * kNgdTile;
+  a.nT = g.nT;
+  a.ldp = g.ldp;
   a.params = (TI *)params;
   a.state = (TI *)state;
-  a.status = (int *)c->status.p;
+  a.out.status = (int *)c->status.p;
   if (a.d > kNatgradSmallD) {
-    const size_t mat = (size_t)a.ldp * a.ldp;
-    T *w = (T *)c->natgrad_work.p;
+    T *w = (T *)c->ms_work.p;
     a.G = w;
-    a.P = w + mat;
-    a.W = w + 2 * mat;
-    a.A = w + 3 * mat;
-    a.X = w + 4 * mat;
-    a.Dinv = w + 5 * mat;
-    a.part = (double *)c->natgrad_part.p;
-    a.vec = a.part + 2 * a.nT;
+    a.P = w + g.mat();
+    a.W = w + 2 * g.mat();
+    a.A = w + 3 * g.mat();
+    a.X = w + 4 * g.mat();
+    a.Dinv = w + 5 * g.mat();
+    a.part = (double *)c->ms_part.p;
+    a.vec = a.part + 2 * g.nT;
   }
   return a;
 }
@@ -596,7 +510,7 @@ static NatgradArgs<T, TI> natgrad_args(mivi_ctx *c, void *params, void *state) {
 // X = Lr^-1 from the Dinv tiles and the strictly lower tiles of A
 template <typename T, typename TI>
 static void launch_natgrad_inverse(mivi_ctx *c, NatgradArgs<T, TI> a) {
-  hipLaunchKernelGGL((k_natgrad_mk<T, TI>), dim3(a.nT * (a.nT + 1) / 2), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL((k_natgrad_mk<T, TI>), dim3(ngd_n_tiles(a.nT)), dim3(256), 0, c->stream, a);
   for (int i = 1; i < a.nT; ++i) {
     a.k = i;
     hipLaunchKernelGGL((k_natgrad_inv<T, TI>), dim3(i), dim3(256), 0, c->stream, a);
@@ -611,9 +525,7 @@ static NatgradArgs<T, TI> natgrad_update_args(mivi_ctx *c, void *params, void *s
   a.hess = (const TI *)hess;
   a.eta = eta;
   a.ensure = ensure ? 1 : 0;
-  a.logpi = (const TI *)logpi;
-  a.entropy_out = (TI *)entropy;
-  a.elbo_out = (TI *)elbo;
+  a.out = NgdOut<TI>{(const TI *)logpi, (TI *)entropy, (TI *)elbo, a.out.status};
   return a;
 }
 
@@ -621,7 +533,7 @@ static NatgradArgs<T, TI> natgrad_update_args(mivi_ctx *c, void *params, void *s
 template <typename TI>
 static void launch_natgrad_tiles(mivi_ctx *c, NatgradArgs<double, TI> a) {
   typedef double T;
-  const int nT = a.nT, n_tiles = nT * (nT + 1) / 2;
+  const int nT = a.nT, n_tiles = ngd_n_tiles(nT);
   hipLaunchKernelGGL((k_natgrad_prep<T, TI, 0>), dim3(nT * nT), dim3(256), 0, c->stream, a);
   if (a.ensure) {
     hipLaunchKernelGGL((k_natgrad_gw<T, TI>), dim3(nT * nT), dim3(256), 0, c->stream, a);
@@ -643,7 +555,7 @@ static void launch_natgrad_tiles(mivi_ctx *c, NatgradArgs<double, TI> a) {
 template <typename TI>
 static void launch_natgrad_init_tiles(mivi_ctx *c, NatgradArgs<double, TI> a) {
   typedef double T;
-  const int nT = a.nT, n_tiles = nT * (nT + 1) / 2;
+  const int nT = a.nT, n_tiles = ngd_n_tiles(nT);
   hipLaunchKernelGGL((k_natgrad_prep<T, TI, 1>), dim3(nT * nT), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL((k_natgrad_dinv<T, TI>), dim3(nT), dim3(256), 0, c->stream, a);
   launch_natgrad_inverse(c, a);
@@ -652,15 +564,13 @@ static void launch_natgrad_init_tiles(mivi_ctx *c, NatgradArgs<double, TI> a) {
 }
 
 size_t natgrad_work_bytes(const mivi_ctx *c) {
-  if (c->cfg.d <= kNatgradSmallD) return 0;
-  const size_t nT = (size_t)((c->cfg.d + kNgdTile - 1) / kNgdTile), ldp = nT * kNgdTile;
-  return (5 * ldp * ldp + nT * kNgdTile * kNgdTile) * sizeof(double);   // (float64 scratch whatever the context's type)
+  const NgdGeom g(c->cfg.d);   // (float64 scratch whatever the context's type)
+  return c->cfg.d <= kNatgradSmallD ? 0 : (5 * g.mat() + (size_t)g.nT * kNgdTile * kNgdTile) * sizeof(double);
 }
 
 size_t natgrad_part_bytes(const mivi_ctx *c) {
-  if (c->cfg.d <= kNatgradSmallD) return 0;
-  const size_t nT = (size_t)((c->cfg.d + kNgdTile - 1) / kNgdTile);
-  return (2 * nT + 4 * nT * kNgdTile) * sizeof(double);
+  const NgdGeom g(c->cfg.d);
+  return c->cfg.d <= kNatgradSmallD ? 0 : (2 * (size_t)g.nT + 4 * (size_t)g.ldp) * sizeof(double);
 }
 
 void launch_natgrad_update(mivi_ctx *c, void *params, void *state, const void *grad, const void *hess, double eta, int ensure_posdef, const void *logpi,

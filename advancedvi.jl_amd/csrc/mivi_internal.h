@@ -423,8 +423,8 @@ struct mivi_ctx {
   mivi::DevBuf stein_A, stein_g;   // Stein estimator: eps G^T accumulator (dP x dP, T) and the f64 column sums of G
   mivi::DevBuf sg_S, sg_d;         // score-gradient estimator (kernels_score.hip): -E diag(f - mean f) laid out like eps (full-rank); f64 [|eps_m|^2; dense ell_m; f_m - mean f] (3 x cap_M)
   int sg_cap = 0;                  // samples sg_d is sized for
-  mivi::DevBuf ngd_work, ngd_part, ngd_est;   // square-root natural-gradient update (kernels_ngd.hip): [Cc; G; T; v] padded to whole tiles; the diagonal tiles' f64 partials + the ticket; [logpi_avg (16 bytes); grad (d); hess (d x d)] of mivi_sqrt_ngd_steps
-  mivi::DevBuf natgrad_work, natgrad_part, natgrad_host;   // natural-gradient update (kernels_natgrad.hip): [Gh; Sigma; W; A; X] padded to whole tiles + the inverted diagonal tiles + v; the panels' f64 log sums and bad-pivot counts; [S; Sigma] of the _host form
+  mivi::DevBuf ms_work, ms_part;   // the measure-space updates' one scratch pair, ensured by each update to its own need and holding nothing between calls.  Square-root NGD (kernels_ngd.hip): [Cc; G; T; v] padded to whole tiles | the diagonal tiles' f64 partials + the ticket.  Natural gradient (kernels_natgrad.hip): f64 [Gh; Sigma; W; A; X] padded to whole tiles + the inverted diagonal tiles | the panels' f64 log sums and bad-pivot counts + the mean's four vectors
+  mivi::DevBuf ngd_est, natgrad_host;   // api_measure.hip: [logpi_avg or entropy (16 bytes); grad (d); hess (d x d)] of the _steps loops and the _host updates; [S; Sigma] of mivi_natgrad_update_host
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
   const uint64_t *idx_src = nullptr;   // mivi_set_index_source
@@ -581,12 +581,14 @@ void launch_sg_scale(mivi_ctx *c, int M);                              // full-r
 void launch_sg_mf_grad(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *grad);   // mean-field: [d/dmu; d/dsigma]
 
 // kernels_ngd.hip: KLMinSqrtNaturalGradDescent's update (klminsqrtnaturalgraddescent.jl:108-119) on [m; vec C] in place
-size_t ngd_work_bytes(const mivi_ctx *c);    // c->ngd_work (0: the one-workgroup kernel needs none)
-size_t ngd_part_bytes(const mivi_ctx *c);    // c->ngd_part: the diagonal tiles' partials + their ticket (0: the one-workgroup kernel needs none)
+// (both updates work in the context's one scratch pair ms_work / ms_part, which the caller ensures to the update's *_bytes before the launch;
+// ngd_tile.h holds what their kernels share)
+size_t ngd_work_bytes(const mivi_ctx *c);    // of c->ms_work (0: the one-workgroup kernel needs none)
+size_t ngd_part_bytes(const mivi_ctx *c);    // of c->ms_part: the diagonal tiles' partials + their ticket (0: the one-workgroup kernel needs none)
 void launch_ngd_update(mivi_ctx *c, void *params, const void *grad, const void *hess, double eta, const void *logpi, void *entropy, void *elbo);
 // kernels_natgrad.hip: KLMinNaturalGradDescent's state (klminnaturalgraddescent.jl:83-87) and update (:129-145) on [m; vec C] and [S; Sigma] in place
-size_t natgrad_work_bytes(const mivi_ctx *c);   // c->natgrad_work (0: the one-workgroup kernels need none)
-size_t natgrad_part_bytes(const mivi_ctx *c);   // c->natgrad_part
+size_t natgrad_work_bytes(const mivi_ctx *c);   // of c->ms_work (0: the one-workgroup kernels need none)
+size_t natgrad_part_bytes(const mivi_ctx *c);   // of c->ms_part
 void launch_natgrad_init(mivi_ctx *c, void *params, void *state);
 void launch_natgrad_update(mivi_ctx *c, void *params, void *state, const void *grad, const void *hess, double eta, int ensure_posdef, const void *logpi,
                            void *entropy, void *elbo);

@@ -36,35 +36,22 @@ import torch
 
 import advancedvi_jl_amd as avi
 from advancedvi_jl_amd import subsampling as SUB
-from advancedvi_jl_amd._lib import MiviError
 from oracle import oracle as O
 from tests import natgrad_ref as R
-from tests import solve_ref as S
 from tests.helpers import SEED, make_family, make_problem, rel_err
+from tests.measure_space_cases import DTYPES, TOL64, VALUE_RTOL
+from tests.measure_space_cases import dense_ctx as _dense_ctx, flat as _flat, logreg as _logreg, reference_model as _reference_model
+from tests.measure_space_cases import hold, refused as _refused, trajectory_case as _trajectory_case
 
 pytestmark = pytest.mark.gpu
+_hold = functools.partial(hold, "natgrad")
 
-F32_FACTOR = 8.0                 # tests/test_gpu_solve_yardstick.py
-VALUE_RTOL = 1e-5                # tests/test_gpu_parity.py (f32 values)
-TOL64 = (1e-12, 1e-11)           # tests/test_gpu_parity.py TOL[np.float64]
 SIZES = (1, 2, 5, 10, 31, 32, 33, 48, 49, 63, 64, 65, 127, 128, 129, 130, 192, 256, avi.NATGRAD_SMALL_D, avi.NATGRAD_SMALL_D + 1)
-DTYPES = pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 RULES = pytest.mark.parametrize("ensure", [True, False], ids=["ensure", "plain"])
-
-
-def _flat(H):
-    return np.ascontiguousarray(np.asarray(H).reshape(-1, order="F"))
 
 
 def _mat(v, d):
     return np.asarray(v).reshape(d, d, order="F")
-
-
-def _hold(what, d, got, yard, ref):
-    whole, block = S.block_ratios(got, yard, ref, d)
-    print(f"[natgrad yardstick] {what} {d}: {whole:.2f}, {block:.2f}")
-    assert np.all(np.isfinite(got))
-    assert whole <= F32_FACTOR and block <= F32_FACTOR, (what, d, whole, block)
 
 
 def _check_state(what, dtype, d, got, ref, yard, tol64=TOL64[1]):
@@ -178,22 +165,6 @@ def test_update_f64_on_spd4(d, eta, ensure):
 
 
 # ---- fusion and repeatability ----------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=8)
-def _dense_setup(d, dtype):
-    rng = np.random.default_rng(900 + d)
-    q, q_o = make_family(rng, d, avi.FULLRANK, dtype)
-    prob, tgt = make_problem(rng, "dense", d, dtype)
-    params, _ = avi.destructure(q)
-    return params, q_o, prob, tgt
-
-
-def _dense_ctx(d, n, dtype, second):
-    params, q_o, prob, tgt = _dense_setup(d, dtype)
-    ctx = avi.MiviContext(dtype, avi.FULLRANK, d, n, 0, SEED)
-    ctx.set_problem(avi.DenseNormalProblem(prob.mean, prob.L, order=2 if second else 1))
-    return ctx, params, q_o, tgt
-
-
 @DTYPES
 @pytest.mark.parametrize("second", [False, True], ids=["stein", "order2"])
 @pytest.mark.parametrize("d,n", [(5, 10), (70, 64)])
@@ -219,26 +190,6 @@ def test_steps_are_the_single_calls_bitwise(d, n, second, dtype):
 
 
 # ---- trajectories ------------------------------------------------------------------------------------------------------------------------------
-def _reference_model(dtype, order):
-    """test/models/normal.jl `normal_meanfield`: d = 5, mu = 5, sigma = 0.3; q0 = N(0, I)"""
-    d = 5
-    prob = avi.DiagNormalProblem(np.full(d, 5.0, dtype), np.full(d, 0.3, dtype), order=order)
-    return d, prob, O.DiagNormalTarget(np.full(d, 5.0), np.full(d, 0.3)), avi.FullRankGaussian(np.zeros(d, dtype), np.eye(d, dtype=dtype))
-
-
-def _trajectory_case(model, dtype, second):
-    if model == "reference":
-        d, prob, tgt, q0 = _reference_model(dtype, 2 if second else 1)
-        params, _ = avi.destructure(q0)
-        q_o, n, eta = O.MvLocationScale(np.zeros(d), np.eye(d)), 10, 1e-3
-        ctx = avi.MiviContext(dtype, avi.FULLRANK, d, n, 0, SEED)
-        ctx.set_problem(prob)
-    else:
-        d, n, eta = 33, 17, 0.02
-        ctx, params, q_o, tgt = _dense_ctx(d, n, dtype, second)
-    return ctx, d, n, eta, params, q_o, tgt
-
-
 @RULES
 @pytest.mark.parametrize("second", [False, True], ids=["stein", "order2"])
 @pytest.mark.parametrize("model", ["reference", "dense33"])
@@ -377,13 +328,6 @@ def test_convergence(order):
     assert len(info) == 1000 and dl <= 0.1 * d0
 
 
-def _logreg(order=1):
-    rng = np.random.default_rng(77)
-    X = rng.normal(size=(8, 3)) / 2.0
-    y = (rng.uniform(size=8) < 0.5).astype(np.uint8)
-    return avi.LogRegProblem(X, y, "logsigma_normal", 1.0, order=order)
-
-
 def test_subsampling_determinism_and_one_step():
     prob = _logreg(1)
     d = prob.dimension()
@@ -431,12 +375,6 @@ def test_subsampling_convergence():
 
 
 # ---- refusals and the failure path ---------------------------------------------------------------------------------------------------------------
-def _refused(fn):
-    with pytest.raises(MiviError) as e:
-        fn()
-    return e.value.status
-
-
 def test_refusals():
     d, n = 6, 4
     rng = np.random.default_rng(5)
