@@ -11,6 +11,7 @@ from .families import FULLRANK, MEANFIELD
 from . import problems as P
 
 NATGRAD_SMALL_D = 44   # MIVI_NATGRAD_SMALL_D (include/mivi.h): up to this d mivi_natgrad_update is the one-workgroup kernel, above it the tile path
+BAM_MAX_SAMPLES = 64   # MIVI_BAM_MAX_SAMPLES (include/mivi.h): the most samples mivi_bam_update / mivi_bam_steps take
 
 _NP2MIVI = {np.dtype(np.float32): _lib.F32, np.dtype(np.float64): _lib.F64}
 
@@ -391,6 +392,77 @@ class MiviContext:
         self._raise_cb(self.lib.mivi_natgrad_steps(self.h, self._p(params), self._p(state), idx0, int(count), int(n_samples),
                                                    1 if second_order else 0, float(stepsize), 1 if ensure_posdef else 0, self._p(elbo)))
         return elbo
+
+    # -- FisherMinBatchMatch (mivi_bam_*: fisherminbatchmatch.jl) -----------------------------------------------------------------
+    def bam_init(self, params, state=None):
+        """mivi_bam_init: the device tensor Sigma = C C' (d^2, column-major, triangles bitwise mirrored) of the device parameters `params`."""
+        state = self.empty(self.d * self.d) if state is None else state
+        self._chk(self.lib.mivi_bam_init(self.h, self._p(params), self._p(state)))
+        return state
+
+    def bam_moments(self, params, idx, n_samples, u=None, G=None):
+        """mivi_bam_moments: (u, G, fisher, logpi_avg, elbo) of estimate `idx` at the device tensor `params`; u and G are flat device
+        tensors (d * n_samples, column-major: `.view(n_samples, d).t()` is the d x n matrix), the three values 1-element device tensors."""
+        n = int(n_samples)
+        u = self.empty(self.d * max(n, 0)) if u is None else u
+        G = self.empty(self.d * max(n, 0)) if G is None else G
+        vals = self.empty(3)
+        self._raise_cb(self.lib.mivi_bam_moments(self.h, self._p(params), idx, n, self._p(u), self._p(G), self._p(vals[0:1]), self._p(vals[1:2]),
+                                                 self._p(vals[2:3])))
+        return u, G, vals[0:1], vals[1:2], vals[2:3]
+
+    def bam_moments_host(self, params, idx, n_samples):
+        """mivi_bam_moments_host on a numpy parameter vector: (u (d, n), G (d, n), fisher, logpi_avg, elbo)."""
+        n = int(n_samples)
+        p = np.ascontiguousarray(params, dtype=self.np_dtype)
+        u = np.zeros((self.d, max(n, 0)), dtype=self.np_dtype, order="F")
+        G = np.zeros((self.d, max(n, 0)), dtype=self.np_dtype, order="F")
+        vals = np.zeros(3, dtype=self.np_dtype)
+        it = vals.itemsize
+        self._raise_cb(self.lib.mivi_bam_moments_host(self.h, p.ctypes.data, idx, n, u.ctypes.data, G.ctypes.data, vals.ctypes.data,
+                                                      vals.ctypes.data + it, vals.ctypes.data + 2 * it))
+        return u, G, vals[0], vals[1], vals[2]
+
+    def estimate_fisher(self, params, idx, n_samples, value=None):
+        """mivi_estimate_fisher: the covariance-weighted Fisher divergence estimate, any n_samples >= 2; a 1-element device tensor."""
+        p = self.to_device(params)
+        value = self.empty(1) if value is None else value
+        self._raise_cb(self.lib.mivi_estimate_fisher(self.h, self._p(p), idx, int(n_samples), self._p(value)))
+        return value
+
+    def estimate_fisher_host(self, params, idx, n_samples):
+        p = np.ascontiguousarray(params, dtype=self.np_dtype)
+        value = np.zeros(1, dtype=self.np_dtype)
+        self._raise_cb(self.lib.mivi_estimate_fisher_host(self.h, p.ctypes.data, idx, int(n_samples), value.ctypes.data))
+        return value[0]
+
+    def bam_update(self, params, state, u, G, n_samples, lam, entropy=None):
+        """mivi_bam_update: (m, C, Sigma) -> (m', C', Sigma') in place on the device tensors `params` and `state` from the flat device
+        tensors u and G (d * n_samples, column-major, read-only); returns entropy(q') as a 1-element device tensor."""
+        entropy = self.empty(1) if entropy is None else entropy
+        self._chk(self.lib.mivi_bam_update(self.h, self._p(params), self._p(state), self._p(u), self._p(G), int(n_samples), float(lam),
+                                           self._p(entropy)))
+        return entropy
+
+    def bam_update_host(self, params, state, u, G, lam):
+        """mivi_bam_update_host on numpy arrays: params ([m; vec C]), state (Sigma, d^2 or (d, d)), u and G ((d, n) matrices); returns
+        (params', state' (flat, column-major), entropy(q'))."""
+        p = np.array(params, dtype=self.np_dtype, copy=True)
+        st = np.array(np.asarray(state).reshape(-1, order="F"), dtype=self.np_dtype, copy=True)
+        uu, GG = np.asfortranarray(u, dtype=self.np_dtype), np.asfortranarray(G, dtype=self.np_dtype)
+        ent = np.zeros(1, dtype=self.np_dtype)
+        self._chk(self.lib.mivi_bam_update_host(self.h, p.ctypes.data, st.ctypes.data, uu.ctypes.data, GG.ctypes.data, int(uu.shape[1]), float(lam),
+                                                ent.ctypes.data))
+        return p, st, ent[0]
+
+    def bam_steps(self, params, state, idx0, iteration0, count, n_samples, fisher=None, elbo=None):
+        """mivi_bam_steps: `count` whole steps {objective (index idx0 + t), update (lambda = d n / (iteration0 + t))} on the device tensors
+        `params` and `state`; returns (fisher (count), elbo (count)), both at the iterate each step started from."""
+        fisher = self.empty(int(count)) if fisher is None else fisher
+        elbo = self.empty(int(count)) if elbo is None else elbo
+        self._raise_cb(self.lib.mivi_bam_steps(self.h, self._p(params), self._p(state), idx0, int(iteration0), int(count), int(n_samples),
+                                               self._p(fisher), self._p(elbo)))
+        return fisher, elbo
 
     def estimate_partials(self, params, idx, partials=None):
         p = self.to_device(params)

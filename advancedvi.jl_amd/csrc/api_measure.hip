@@ -2,7 +2,9 @@
 //   KLMinSqrtNaturalGradDescent (src/algorithms/klminsqrtnaturalgraddescent.jl): the square-root natural-gradient update (kernels_ngd.hip);
 //   KLMinNaturalGradDescent (src/algorithms/klminnaturalgraddescent.jl): the state [S; Sigma] of `init` (:83-87) and the natural-gradient
 //     update of `step` (:129-145) (kernels_natgrad.hip; its scale convention, a LOWER-triangular C' where the reference's new scale is upper
-//     triangular, is stated there and in include/mivi.h)
+//     triangular, is stated there and in include/mivi.h);
+//   FisherMinBatchMatch (src/algorithms/fisherminbatchmatch.jl): the state Sigma of `init` (:76), the per-sample objective (:81-111) and the
+//     batch-and-match update of `step` (:143-155) (kernels_bam.hip; below, after the shared helpers)
 // -- and whole steps {estimator, update} without a host round trip.  A step is the existing estimator entry (mivi_gauss_expected_grad_hess /
 // _hess2) into context-owned buffers followed by the update, whose last launch also forms elbo = logpi_avg + entropy(q') and the sticky
 // flags: launches are fused, arithmetic is not, so the _steps entries are bitwise the single calls.  The algorithms differ in the update
@@ -104,7 +106,183 @@ static mivi_status_t update_host(mivi_ctx *c, const char *entry, void *params_h,
   return fetch_results(c, {{params_h, c->tmp_params.p, (size_t)mivi_params_len(c) * es}, {state_h, c->natgrad_host.p, sb}, {entropy_h, e.scalar, es}}, true);
 }
 
+// ---- FisherMinBatchMatch (src/algorithms/fisherminbatchmatch.jl; kernels_bam.hip) ------------------------------------------------------------------
+// What every batch-and-match entry refuses before anything launches.  n_samples < 0: the entry takes none; bounded: the update's rank bound.
+static mivi_status_t need_bam(mivi_ctx *c, const char *entry, int32_t n_samples, bool bounded) {
+  mivi_status_t s;
+  if ((s = need_fullrank(c, (std::string(entry) + ": FisherMinBatchMatch").c_str())) || (s = need_whole_estimate(c, entry))) return s;
+  if (c->bij_on)
+    return fail(c, MIVI_ERR_UNSUPPORTED, (std::string(entry) + ": a Stacked bijector is set (FisherMinBatchMatch requires unconstrained support)").c_str());
+  if (n_samples < 0) return MIVI_OK;
+  if (n_samples < 2) return fail(c, MIVI_ERR_BAD_ARG, (std::string(entry) + ": n_samples < 2 (the corrected sample covariance is undefined)").c_str());
+  if (bounded && n_samples > MIVI_BAM_MAX_SAMPLES)
+    return fail(c, MIVI_ERR_UNSUPPORTED, (std::string(entry) + ": n_samples > MIVI_BAM_MAX_SAMPLES (the update's eigenproblem is one workgroup's)").c_str());
+  return MIVI_OK;
+}
+
+static const int kBamChunk = 16384;
+
+// the update's scratch and room for `tiles` objective partials in the same pair
+static mivi_status_t bam_scratch(mivi_ctx *c, bool update, int tiles) {
+  mivi_status_t s;
+  if (update && (s = ensure(c, c->ms_work, bam_work_bytes(c), false))) return s;
+  const size_t pb = update ? bam_part_bytes(c) : 0, tb = (size_t)tiles * sizeof(double);
+  return ensure(c, c->ms_part, pb > tb ? pb : tb, false);
+}
+
+// One chunk of the objective's sampling stage: the draws of estimate idx, columns [off, off + Mc), in the context's eps plane (leading
+// dimension dP), the gradients in c->W, [sum logpi, ..] in c->tmp_out -- the Stein estimator's call -- and the chunk's tile partials.
+static mivi_status_t bam_chunk(mivi_ctx *c, const void *params, uint64_t idx, int off, int Mc, double *part) {
+  RngArgs r = rng_of(c, idx);
+  r.m_offset += off;
+  const mivi_status_t s = run_estimate(c, params, r, Mc, 1, chunk_partials_out(c, c->tmp_out.p, Mc), nullptr, nullptr, true);
+  if (s) return s;
+  launch_bam_fisher(c, params, Mc, c->eps[c->cur].p, (size_t)c->dP, c->W.p, part);
+  return MIVI_OK;
+}
+
+// rand_batch_match_samples_with_objective! for n <= one chunk; the scratch is the caller's to ensure.  u / G (nullable): compact copies.
+static mivi_status_t bam_moments(mivi_ctx *c, const void *params, uint64_t idx, int32_t n, void *u, void *G, void *fisher, void *logpi, void *elbo) {
+  mivi_status_t s;
+  if ((s = bam_chunk(c, params, idx, 0, n, (double *)c->ms_part.p))) return s;
+  launch_bam_objective(c, params, (const double *)c->ms_part.p, bam_fisher_tiles(c, n), (double)n, c->tmp_out.p, fisher, logpi, elbo);
+  const size_t es = c->esize, d = (size_t)c->cfg.d;
+  if (u) HIPCHK(c, hipMemcpy2DAsync(u, d * es, c->eps[c->cur].p, (size_t)c->dP * es, d * es, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+  if (G) HIPCHK(c, hipMemcpyAsync(G, c->W.p, d * (size_t)n * es, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipGetLastError());
+  return MIVI_OK;
+}
+
+static mivi_status_t bam_update(mivi_ctx *c, void *params, void *state, const void *u, size_t ldu, const void *G, int32_t n, double lambda, void *entropy) {
+  launch_bam_update(c, params, state, u, ldu, G, n, lambda, entropy);
+  HIPCHK(c, hipGetLastError());
+  return MIVI_OK;
+}
+
+// the _host entries' device staging: [Sigma (d x d); u (d x n); G (d x n); three scalars of 16 bytes]
+struct BamHost { char *state, *u, *G, *scalar; };
+static mivi_status_t bam_host(mivi_ctx *c, int32_t n, BamHost *h) {
+  const size_t es = c->esize, d = (size_t)c->cfg.d, nn = n > 0 ? (size_t)n : 0;
+  const size_t sb = (d * d * es + 15) / 16 * 16, ub = (d * nn * es + 15) / 16 * 16;
+  const mivi_status_t s = ensure(c, c->bam_host, sb + 2 * ub + 48, false);
+  if (s) return s;
+  char *b = (char *)c->bam_host.p;
+  *h = BamHost{b, b + sb, b + sb + ub, b + sb + 2 * ub};
+  return MIVI_OK;
+}
+
 extern "C" {
+
+mivi_status_t mivi_bam_init(mivi_ctx_t *c, const void *params, void *state) {
+  if (!c || !params || !state) return MIVI_ERR_BAD_ARG;
+  const mivi_status_t s = need_bam(c, "bam_init", -1, false);
+  if (s) return s;
+  (void)hipSetDevice(c->cfg.device);
+  launch_bam_init(c, params, state);
+  HIPCHK(c, hipGetLastError());
+  return MIVI_OK;
+}
+
+mivi_status_t mivi_bam_moments(mivi_ctx_t *c, const void *params, uint64_t idx, int32_t n_samples, void *u, void *G, void *fisher, void *logpi_avg,
+                               void *elbo) {
+  if (!c || !params || !u || !G || !fisher || !logpi_avg || !elbo) return MIVI_ERR_BAD_ARG;
+  mivi_status_t s;
+  if ((s = need_bam(c, "bam_moments", n_samples, false))) return s;
+  if (n_samples > kBamChunk) return fail(c, MIVI_ERR_UNSUPPORTED, "bam_moments: more than 16384 samples (mivi_estimate_fisher takes any number)");
+  (void)hipSetDevice(c->cfg.device);
+  if ((s = bam_scratch(c, false, bam_fisher_tiles(c, n_samples)))) return s;
+  return bam_moments(c, params, idx, n_samples, u, G, fisher, logpi_avg, elbo);
+}
+
+mivi_status_t mivi_bam_moments_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, int32_t n_samples, void *u_h, void *G_h, void *fisher_h,
+                                    void *logpi_avg_h, void *elbo_h) {
+  if (!c || !params_h || !u_h || !G_h || !fisher_h || !logpi_avg_h || !elbo_h) return MIVI_ERR_BAD_ARG;
+  mivi_status_t s;
+  if ((s = need_bam(c, "bam_moments", n_samples, false))) return s;
+  if (n_samples > kBamChunk) return fail(c, MIVI_ERR_UNSUPPORTED, "bam_moments: more than 16384 samples (mivi_estimate_fisher takes any number)");
+  (void)hipSetDevice(c->cfg.device);
+  BamHost h;
+  if ((s = bam_host(c, n_samples, &h)) || (s = bam_scratch(c, false, bam_fisher_tiles(c, n_samples))) || (s = stage_params(c, params_h))) return s;
+  if ((s = bam_moments(c, c->tmp_params.p, idx, n_samples, h.u, h.G, h.scalar, h.scalar + 16, h.scalar + 32))) return s;
+  const size_t es = c->esize, ub = (size_t)c->cfg.d * (size_t)n_samples * es;
+  return fetch_results(c, {{u_h, h.u, ub}, {G_h, h.G, ub}, {fisher_h, h.scalar, es}, {logpi_avg_h, h.scalar + 16, es}, {elbo_h, h.scalar + 32, es}}, true);
+}
+
+mivi_status_t mivi_estimate_fisher(mivi_ctx_t *c, const void *params, uint64_t idx, int32_t n_samples, void *value) {
+  if (!c || !params || !value) return MIVI_ERR_BAD_ARG;
+  mivi_status_t s;
+  if ((s = need_bam(c, "estimate_fisher", n_samples, false))) return s;
+  (void)hipSetDevice(c->cfg.device);
+  int tiles = 0;
+  for (int off = 0; off < n_samples; off += kBamChunk) tiles += bam_fisher_tiles(c, n_samples - off < kBamChunk ? n_samples - off : kBamChunk);
+  if ((s = bam_scratch(c, false, tiles))) return s;
+  double *part = (double *)c->ms_part.p;
+  for (int off = 0; off < n_samples; off += kBamChunk) {
+    const int Mc = n_samples - off < kBamChunk ? n_samples - off : kBamChunk;
+    if ((s = bam_chunk(c, params, idx, off, Mc, part))) return s;
+    part += bam_fisher_tiles(c, Mc);
+  }
+  launch_bam_objective(c, params, (const double *)c->ms_part.p, tiles, (double)n_samples, nullptr, value, nullptr, nullptr);
+  HIPCHK(c, hipGetLastError());
+  return MIVI_OK;
+}
+
+mivi_status_t mivi_estimate_fisher_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, int32_t n_samples, void *value_h) {
+  if (!c || !params_h || !value_h) return MIVI_ERR_BAD_ARG;
+  mivi_status_t s;
+  if ((s = need_bam(c, "estimate_fisher", n_samples, false))) return s;
+  (void)hipSetDevice(c->cfg.device);
+  BamHost h;
+  if ((s = bam_host(c, 0, &h)) || (s = stage_params(c, params_h))) return s;
+  if ((s = mivi_estimate_fisher(c, c->tmp_params.p, idx, n_samples, h.scalar))) return s;
+  return fetch_results(c, {{value_h, h.scalar, c->esize}}, false);   // (a non-finite value is returned as it is, like mivi_estimate_objective_host)
+}
+
+mivi_status_t mivi_bam_update(mivi_ctx_t *c, void *params, void *state, const void *u, const void *G, int32_t n_samples, double lambda, void *entropy) {
+  if (!c || !params || !state || !u || !G || !(lambda > 0.0)) return MIVI_ERR_BAD_ARG;
+  mivi_status_t s;
+  if ((s = need_bam(c, "bam_update", n_samples, true))) return s;
+  (void)hipSetDevice(c->cfg.device);
+  if ((s = bam_scratch(c, true, 0))) return s;
+  return bam_update(c, params, state, u, (size_t)c->cfg.d, G, n_samples, lambda, entropy);
+}
+
+mivi_status_t mivi_bam_update_host(mivi_ctx_t *c, void *params_h, void *state_h, const void *u_h, const void *G_h, int32_t n_samples, double lambda,
+                                   void *entropy_h) {
+  if (!c || !params_h || !state_h || !u_h || !G_h || !(lambda > 0.0)) return MIVI_ERR_BAD_ARG;
+  mivi_status_t s;
+  if ((s = need_bam(c, "bam_update", n_samples, true))) return s;
+  (void)hipSetDevice(c->cfg.device);
+  const size_t es = c->esize, d = (size_t)c->cfg.d, sb = d * d * es, ub = d * (size_t)n_samples * es;
+  BamHost h;
+  if ((s = bam_host(c, n_samples, &h)) || (s = bam_scratch(c, true, 0)) || (s = stage_params(c, params_h))) return s;
+  HIPCHK(c, hipMemcpyAsync(h.state, state_h, sb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h.u, u_h, ub, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h.G, G_h, ub, hipMemcpyHostToDevice, c->stream));
+  if ((s = bam_update(c, c->tmp_params.p, h.state, h.u, d, h.G, n_samples, lambda, h.scalar))) return s;
+  return fetch_results(c, {{params_h, c->tmp_params.p, (size_t)mivi_params_len(c) * es}, {state_h, h.state, sb}, {entropy_h, h.scalar, es}}, true);
+}
+
+mivi_status_t mivi_bam_steps(mivi_ctx_t *c, void *params, void *state, uint64_t idx0, uint64_t iteration0, int32_t count, int32_t n_samples, void *fisher,
+                             void *elbo) {
+  if (!c || !params || !state || count < 0 || iteration0 < 1) return MIVI_ERR_BAD_ARG;
+  mivi_status_t s;
+  if ((s = need_bam(c, "bam_steps", n_samples, true))) return s;
+  (void)hipSetDevice(c->cfg.device);
+  NgdEst e;   // (its scalar: logpi_avg)
+  if ((s = ngd_est(c, &e)) || (s = bam_scratch(c, true, bam_fisher_tiles(c, n_samples)))) return s;
+  const size_t es = c->esize;
+  for (int32_t t = 0; t < count; ++t) {
+    // step t: the objective at q_t (its draws and gradients stay where the sampling stage left them), then the update reads them there
+    if ((s = bam_moments(c, params, idx0 + (uint64_t)t, n_samples, nullptr, nullptr, fisher ? (char *)fisher + (size_t)t * es : nullptr, e.scalar,
+                         elbo ? (char *)elbo + (size_t)t * es : nullptr)))
+      return s;
+    double lambda = (double)c->cfg.d * (double)n_samples / (double)(iteration0 + (uint64_t)t);
+    if (c->cfg.dtype == MIVI_F32) lambda = (double)(float)lambda;   // convert(eltype(mu), d * n_samples / iteration) (:148)
+    if ((s = bam_update(c, params, state, c->eps[c->cur].p, (size_t)c->dP, c->W.p, n_samples, lambda, nullptr))) return s;
+  }
+  return MIVI_OK;
+}
 
 mivi_status_t mivi_sqrt_ngd_update(mivi_ctx_t *c, void *params, const void *grad, const void *hess, double stepsize, void *entropy) {
   if (!c || !params || !grad || !hess) return MIVI_ERR_BAD_ARG;

@@ -19,7 +19,7 @@ static void store_acc_value(mivi_ctx *c, void *dst) {
 }
 
 // a chunk of Mc samples leaves only its two scalar partials [sum ell, sum 0.5 eps^2] in `part`
-static OutArgs chunk_partials_out(mivi_ctx *c, void *part, int Mc) {
+OutArgs chunk_partials_out(mivi_ctx *c, void *part, int Mc) {
   OutArgs o = final_out(c, nullptr, nullptr);
   o.partials = part;
   o.partials_mode = 1;

@@ -46,6 +46,7 @@ constexpr int kNatgradSmallD = MIVI_NATGRAD_SMALL_D;   // 4 matrices of 44 x 45 
 template <typename T, typename TI>
 struct NatgradArgs {
   int d, nT, ldp, ensure, k;   // k: the panel (upd, scale) / block row (inv) of this launch
+  int keep;                    // upd: the factored diagonal tile Lr_kk goes back into the lower triangle of A_kk (launch_natgrad_factor)
   TI *params;                  // [m (d); vec C (d x d, column-major)] in / out
   TI *state;                   // [S (d x d); Sigma (d x d)] in / out
   const TI *grad;              // g (d)
@@ -351,6 +352,9 @@ __global__ __launch_bounds__(256) void k_natgrad_upd(NatgradArgs<T, TI> a) {
   __syncthreads();
   acc.each(wr, wc, lane, [&](int ii, int jj, T x) { sAB[ii * kNgdLd + jj] = a.A[(size_t)(k0 + jj) * ldp + k0 + ii] - x; });
   natgrad_diag_tile<T, TI, true>(a, k, sAB, sd, &sbad);
+  if (a.keep)   // (natgrad_invert leaves Lr_kk in the lower triangle of the tile)
+    for (int t = threadIdx.x; t < kNgdTile * kNgdTile; t += 256)
+      if ((t >> 6) <= (t & 63)) a.A[(size_t)(k0 + (t >> 6)) * ldp + k0 + (t & 63)] = sAB[(t & 63) * kNgdLd + (t >> 6)];
 }
 
 // init: Dinv_k = C_kk^-1 from the diagonal tiles of A = tril(C)
@@ -561,6 +565,27 @@ static void launch_natgrad_init_tiles(mivi_ctx *c, NatgradArgs<double, TI> a) {
   launch_natgrad_inverse(c, a);
   hipLaunchKernelGGL((k_natgrad_syrk<T, TI, true, false>), dim3(n_tiles), dim3(256), 0, c->stream, a, (const T *)a.X, a.state);
   hipLaunchKernelGGL((k_natgrad_syrk<T, TI, false, false>), dim3(n_tiles), dim3(256), 0, c->stream, a, (const T *)a.A, a.state + (size_t)a.d * a.d);
+}
+
+// The factorisation alone, for kernels_bam.hip: the padded float64 A (identity on the diagonal of its padding; only its lower tiles and the
+// lower triangles of its diagonal tiles are read) -> Lr with A = Lr' Lr in the same places, the diagonal tiles' factors included; Dinv
+// (nT tiles) and part ([2][nT]: sum log 1 / Lr_ii of a panel, its count of bad pivots) as the update leaves them.  2 nT - 1 launches.
+void launch_natgrad_factor(mivi_ctx *c, int d, double *A, double *Dinv, double *part) {
+  NatgradArgs<double, double> a{};
+  const NgdGeom g(d);
+  a.d = d;
+  a.nT = g.nT;
+  a.ldp = g.ldp;
+  a.A = A;
+  a.Dinv = Dinv;
+  a.part = part;
+  a.keep = 1;
+  a.out.status = (int *)c->status.p;
+  for (int k = g.nT - 1; k >= 0; --k) {
+    a.k = k;
+    hipLaunchKernelGGL((k_natgrad_upd<double, double>), dim3(k + 1), dim3(256), 0, c->stream, a);
+    if (k > 0) hipLaunchKernelGGL((k_natgrad_scale<double, double>), dim3(k), dim3(256), 0, c->stream, a);
+  }
 }
 
 size_t natgrad_work_bytes(const mivi_ctx *c) {

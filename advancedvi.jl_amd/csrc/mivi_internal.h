@@ -423,7 +423,8 @@ struct mivi_ctx {
   mivi::DevBuf stein_A, stein_g;   // Stein estimator: eps G^T accumulator (dP x dP, T) and the f64 column sums of G
   mivi::DevBuf sg_S, sg_d;         // score-gradient estimator (kernels_score.hip): -E diag(f - mean f) laid out like eps (full-rank); f64 [|eps_m|^2; dense ell_m; f_m - mean f] (3 x cap_M)
   int sg_cap = 0;                  // samples sg_d is sized for
-  mivi::DevBuf ms_work, ms_part;   // the measure-space updates' one scratch pair, ensured by each update to its own need and holding nothing between calls.  Square-root NGD (kernels_ngd.hip): [Cc; G; T; v] padded to whole tiles | the diagonal tiles' f64 partials + the ticket.  Natural gradient (kernels_natgrad.hip): f64 [Gh; Sigma; W; A; X] padded to whole tiles + the inverted diagonal tiles | the panels' f64 log sums and bad-pivot counts + the mean's four vectors
+  mivi::DevBuf ms_work, ms_part;   // the measure-space updates' one scratch pair, ensured by each update to its own need and holding nothing between calls.  Square-root NGD (kernels_ngd.hip): [Cc; G; T; v] padded to whole tiles | the diagonal tiles' f64 partials + the ticket.  Natural gradient (kernels_natgrad.hip): f64 [Gh; Sigma; W; A; X] padded to whole tiles + the inverted diagonal tiles | the panels' f64 log sums and bad-pivot counts + the mean's four vectors.  Batch and match (kernels_bam.hip): f64 [A; Dinv; Q, Ut, Zt, SQ, Y; M, E1, ME; gbar, ubar, zbar] | the objective's tile partials, then the panels' pairs
+  mivi::DevBuf bam_host;   // api_measure.hip: [Sigma (d x d); u (d x n); G (d x n); fisher, logpi_avg, elbo / entropy (16 bytes each)] of the batch-and-match _host entries
   mivi::DevBuf ngd_est, natgrad_host;   // api_measure.hip: [logpi_avg or entropy (16 bytes); grad (d); hess (d x d)] of the _steps loops and the _host updates; [S; Sigma] of mivi_natgrad_update_host
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
@@ -590,6 +591,17 @@ void launch_ngd_update(mivi_ctx *c, void *params, const void *grad, const void *
 size_t natgrad_work_bytes(const mivi_ctx *c);   // of c->ms_work (0: the one-workgroup kernels need none)
 size_t natgrad_part_bytes(const mivi_ctx *c);   // of c->ms_part
 void launch_natgrad_init(mivi_ctx *c, void *params, void *state);
+// its blocked factorisation alone, on a caller's padded float64 work matrix: A = Lr' Lr, Lr (diagonal tiles included) in A's lower triangle
+void launch_natgrad_factor(mivi_ctx *c, int d, double *A, double *Dinv, double *part);
+// kernels_bam.hip: FisherMinBatchMatch (fisherminbatchmatch.jl) -- Sigma of `init` (:76), the objective (:81-111) and the update (:143-155)
+size_t bam_work_bytes(const mivi_ctx *c);   // of c->ms_work (the update)
+size_t bam_part_bytes(const mivi_ctx *c);   // of c->ms_part (the update)
+int bam_fisher_tiles(const mivi_ctx *c, int M);   // the partials launch_bam_fisher leaves for M samples
+void launch_bam_init(mivi_ctx *c, const void *params, void *state);
+void launch_bam_fisher(mivi_ctx *c, const void *params, int M, const void *u, size_t ldu, const void *G, double *part);
+void launch_bam_objective(mivi_ctx *c, const void *params, const double *part, int n_part, double n, const void *ell_sum, void *fisher, void *logpi_avg,
+                          void *elbo);   // fisher = sum(part) / n; logpi_avg = *ell_sum / n and elbo = logpi_avg + entropy(q) where asked for
+void launch_bam_update(mivi_ctx *c, void *params, void *state, const void *u, size_t ldu, const void *G, int B, double lambda, void *entropy);
 void launch_natgrad_update(mivi_ctx *c, void *params, void *state, const void *grad, const void *hess, double eta, int ensure_posdef, const void *logpi,
                            void *entropy, void *elbo);
 

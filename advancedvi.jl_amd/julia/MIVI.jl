@@ -561,6 +561,63 @@ function sqrt_ngd_steps!(state::MIVIState, params_dev::Ptr{Cvoid}, count::Intege
     return state
 end
 
+# FisherMinBatchMatch (src/algorithms/fisherminbatchmatch.jl): rand_batch_match_samples_with_objective! (:81-111) into u_buf / grad_buf,
+# the BaM update of `step` (:143-155) on `params = first(Optimisers.destructure(q))` and `sigma` (:49) in place from those buffers, the
+# objective alone (:186-195) and, on device pointers, whole steps without a host round trip (mivi_bam_steps: fisher_dev, elbo_dev T[count]
+# or C_NULL; `iteration` is the state's iteration count BEFORE the first of the steps).
+function bam_moments!(state::MIVIState, params::Vector{T}, u_buf::Matrix{T}, grad_buf::Matrix{T}) where {T<:Real}
+    fisher, logpi, elbo = Ref{T}(zero(T)), Ref{T}(zero(T)), Ref{T}(zero(T))
+    check(state.ctx, ccall((:mivi_bam_moments_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, UInt64, Int32, Ptr{T}, Ptr{T}, Ref{T}, Ref{T}, Ref{T}),
+                           state.ctx, params, state.estimate_idx, Int32(size(u_buf, 2)), u_buf, grad_buf, fisher, logpi, elbo))
+    state.estimate_idx += 1
+    return u_buf, grad_buf, fisher[], logpi[], elbo[]
+end
+function estimate_fisher(state::MIVIState, params::Vector{T}, n_samples::Integer) where {T<:Real}
+    value = Ref{T}(zero(T))
+    check(state.ctx, ccall((:mivi_estimate_fisher_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, UInt64, Int32, Ref{T}),
+                           state.ctx, params, state.estimate_idx, Int32(n_samples), value))
+    state.estimate_idx += 1
+    return value[]
+end
+function bam_update!(state::MIVIState, params::Vector{T}, sigma::Matrix{T}, u_buf::Matrix{T}, grad_buf::Matrix{T}, lambda::Real) where {T<:Real}
+    entropy = Ref{T}(zero(T))
+    check(state.ctx, ccall((:mivi_bam_update_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Int32, Float64, Ref{T}),
+                           state.ctx, params, sigma, u_buf, grad_buf, Int32(size(u_buf, 2)), Float64(T(lambda)), entropy))
+    return params, sigma, entropy[]
+end
+function bam_init_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, sigma_dev::Ptr{Cvoid})
+    check(state.ctx, ccall((:mivi_bam_init, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), state.ctx, params_dev, sigma_dev))
+    return state
+end
+function bam_moments_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, n_samples::Integer, u_dev::Ptr{Cvoid}, grad_dev::Ptr{Cvoid},
+                          fisher_dev::Ptr{Cvoid}, logpi_dev::Ptr{Cvoid}, elbo_dev::Ptr{Cvoid})
+    check(state.ctx, ccall((:mivi_bam_moments, libmivi), Int32,
+                           (Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                           state.ctx, params_dev, state.estimate_idx, Int32(n_samples), u_dev, grad_dev, fisher_dev, logpi_dev, elbo_dev))
+    state.estimate_idx += 1
+    return state
+end
+function estimate_fisher_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, n_samples::Integer, value_dev::Ptr{Cvoid})
+    check(state.ctx, ccall((:mivi_estimate_fisher, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Int32, Ptr{Cvoid}),
+                           state.ctx, params_dev, state.estimate_idx, Int32(n_samples), value_dev))
+    state.estimate_idx += 1
+    return state
+end
+function bam_update_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, sigma_dev::Ptr{Cvoid}, u_dev::Ptr{Cvoid}, grad_dev::Ptr{Cvoid},
+                         n_samples::Integer, lambda::Real, entropy_dev::Ptr{Cvoid}=C_NULL)
+    check(state.ctx, ccall((:mivi_bam_update, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Ptr{Cvoid}),
+                           state.ctx, params_dev, sigma_dev, u_dev, grad_dev, Int32(n_samples), Float64(lambda), entropy_dev))
+    return state
+end
+function bam_steps!(state::MIVIState, params_dev::Ptr{Cvoid}, sigma_dev::Ptr{Cvoid}, iteration::Integer, count::Integer, n_samples::Integer,
+                    fisher_dev::Ptr{Cvoid}=C_NULL, elbo_dev::Ptr{Cvoid}=C_NULL)
+    check(state.ctx, ccall((:mivi_bam_steps, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt64, UInt64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                           state.ctx, params_dev, sigma_dev, state.estimate_idx, UInt64(iteration + 1), Int32(count), Int32(n_samples), fisher_dev, elbo_dev))
+    state.estimate_idx += count
+    check(state.ctx, ccall((:mivi_synchronize, libmivi), Int32, (Ptr{Cvoid},), state.ctx))
+    return state
+end
+
 # Constrained supports (README.md:76-82, 91-119; docs/src/tutorials/constrained.md:154-196): a Bijectors.Stacked of identity / exp
 # blocks is applied by the library around whatever target is set.  `ranges` are the Stacked's UnitRanges (1-based, as Bijectors
 # stores them), `kinds[i]` is :identity or :exp.  An empty list removes the constraint.
@@ -625,5 +682,5 @@ end
 # ProximalLocationScaleEntropy on the host arrays works unchanged (src/optimization/proximal_location_scale_entropy.jl);
 # the device-resident variant for a parameter vector that lives in HBM is mivi_prox_scale_entropy.
 
-export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!
+export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!, bam_moments!, estimate_fisher, bam_update!, bam_init_dev!, bam_moments_dev!, estimate_fisher_dev!, bam_update_dev!, bam_steps!
 end # module

@@ -1,5 +1,6 @@
-"""Measure-space algorithms: KLMinSqrtNaturalGradDescent and KLMinNaturalGradDescent, the host-side mirrors of
-src/algorithms/klminsqrtnaturalgraddescent.jl and src/algorithms/klminnaturalgraddescent.jl (AdvancedVI.jl v0.7.0) over libmivi.
+"""Measure-space algorithms: KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent and FisherMinBatchMatch, the host-side mirrors of
+src/algorithms/klminsqrtnaturalgraddescent.jl, src/algorithms/klminnaturalgraddescent.jl and src/algorithms/fisherminbatchmatch.jl
+(AdvancedVI.jl v0.7.0) over libmivi.
 
     KLMinSqrtNaturalGradDescent(stepsize, n_samples=1, subsampling=None)     :39-44
     init(rng, alg, q_init, prob)                                             :55-75
@@ -17,13 +18,21 @@ KLMinNaturalGradDescent(stepsize, n_samples=1, ensure_posdef=True, subsampling=N
 its state carries the device buffer [S; Sigma] (precision and covariance, :83-87, mivi_natgrad_init).  The two algorithms differ in their
 update call and that one buffer; everything else below is shared.  Scale convention: the reference's new scale is upper triangular (the
 adjoint of the inverse of a lower Cholesky factor of S'); this library's iterate carries the LOWER Cholesky factor C' of Sigma' = S'^-1 --
-the same distribution, the same recursion in (m, S, Sigma); only the pairing of draws with samples differs."""
+the same distribution, the same recursion in (m, S, Sigma); only the pairing of draws with samples differs.
+
+FisherMinBatchMatch(n_samples=32, subsampling=None) (fisherminbatchmatch.jl:40-44; init :56-77, step :113-167, output :79, estimate_objective
+:186-195) minimises the covariance-weighted Fisher divergence ("batch and match"): gradients only, no step size.  Its step is
+mivi_bam_moments followed by mivi_bam_update (whole chunks inside mivi_bam_steps); its state carries the device buffer Sigma (:76).  Its
+new scale is the lower Cholesky factor of Sigma', as in the reference.  `info` carries `covweighted_fisher` and `elbo`, both at the iterate
+the step STARTED from (:157-158).  The callback is called as the reference's CODE calls it (:163) -- callback(rng=, iteration=, q=, state=)
+with q the iterate the step started from and the new state -- which disagrees with the reference's docstring for `optimize` (q the new
+iterate, `info` instead of `state`); the code is what users' callbacks run against."""
 from __future__ import annotations
 
 from . import objectives as O
 from . import problems as P
 from . import subsampling as S
-from .context import MiviContext
+from .context import BAM_MAX_SAMPLES, MiviContext
 from .families import FULLRANK, MvLocationScale, destructure
 
 
@@ -66,7 +75,25 @@ class KLMinNaturalGradDescent:
                 f"subsampling={self.subsampling})")
 
 
-ALGORITHMS = (KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent)
+class FisherMinBatchMatch:
+    """Covariance-weighted Fisher divergence minimisation by the batch-and-match updates (fisherminbatchmatch.jl:2-44).  Needs a full-rank
+    Gaussian family, unconstrained support and a target with at least first-order capability; 2 <= n_samples <= BAM_MAX_SAMPLES."""
+
+    def __init__(self, n_samples: int = 32, subsampling=None, device: int = 0):
+        if not isinstance(n_samples, int) or n_samples < 2:
+            raise ValueError("n_samples must be an Int of at least 2 (the corrected sample covariance needs two samples)")
+        if n_samples > BAM_MAX_SAMPLES:
+            raise ValueError(f"n_samples must be at most {BAM_MAX_SAMPLES} (MIVI_BAM_MAX_SAMPLES)")
+        self.n_samples = int(n_samples)
+        self.subsampling = subsampling
+        self.device = int(device)
+
+    def __repr__(self):
+        return f"FisherMinBatchMatch(n_samples={self.n_samples}, subsampling={self.subsampling})"
+
+
+ALGORITHMS = (KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent, FisherMinBatchMatch)
+STATE_BUFFERS = ("natgrad", "bam")   # the device buffers, besides the parameters, that a step advances in place
 
 
 def _second_order(prob) -> bool:
@@ -82,7 +109,10 @@ def _update(alg, ctx, state, grad, hess):
 
 
 def _device_steps(alg, ctx, state, idx0, n, second):
-    """`n` whole steps inside the library; returns their elbo (a device tensor)."""
+    """`n` whole steps inside the library; returns their elbo (a device tensor) -- batch and match: (elbo, fisher)."""
+    if isinstance(alg, FisherMinBatchMatch):
+        fisher, elbo = ctx.bam_steps(state["params"], state["bam"], idx0, state["iteration"] + 1, n, alg.n_samples)
+        return elbo, fisher
     if isinstance(alg, KLMinNaturalGradDescent):
         return ctx.natgrad_steps(state["params"], state["natgrad"], idx0, n, alg.stepsize, alg.ensure_posdef, n_samples=alg.n_samples,
                                  second_order=second)
@@ -92,13 +122,14 @@ def _device_steps(alg, ctx, state, idx0, n, second):
 def _own_buffers(state):
     """The state with copies of the device buffers a step advances in place."""
     state = dict(state, params=state["params"].clone())
-    if "natgrad" in state:
-        state["natgrad"] = state["natgrad"].clone()
+    for k in STATE_BUFFERS:
+        if k in state:
+            state[k] = state[k].clone()
     return state
 
 
 def init(rng, alg, q_init, prob):
-    """klminsqrtnaturalgraddescent.jl:55-75 / klminnaturalgraddescent.jl:64-91."""
+    """klminsqrtnaturalgraddescent.jl:55-75 / klminnaturalgraddescent.jl:64-91 / fisherminbatchmatch.jl:56-77."""
     name = type(alg).__name__
     if not isinstance(q_init, MvLocationScale) or q_init.family != FULLRANK:
         raise TypeError(f"`{name}` expects a Gaussian with a lower-triangular scale (FullRankGaussian) as q_init")
@@ -111,8 +142,11 @@ def init(rng, alg, q_init, prob):
     ctx = MiviContext(q_init.eltype, FULLRANK, len(q_init), min(alg.n_samples, 16384), O.ClosedFormEntropy.code, rng.seed, device=alg.device)
     ctx.set_problem(prob)
     d = len(q_init)
-    state = dict(q=q_init, prob=prob, iteration=0, sub_st=sub_st, ctx=ctx, params=ctx.to_device(params_h).clone(), restructure=re,
-                 grad_buf=ctx.empty(d), hess_buf=ctx.empty(d * d))
+    state = dict(q=q_init, prob=prob, iteration=0, sub_st=sub_st, ctx=ctx, params=ctx.to_device(params_h).clone(), restructure=re)
+    if isinstance(alg, FisherMinBatchMatch):       # :74-76: u_buf, grad_buf and cov(q), carried from step to step
+        state.update(u_buf=ctx.empty(d * alg.n_samples), grad_buf=ctx.empty(d * alg.n_samples), bam=ctx.bam_init(state["params"]))
+        return state
+    state.update(grad_buf=ctx.empty(d), hess_buf=ctx.empty(d * d))
     if isinstance(alg, KLMinNaturalGradDescent):   # :83-87: prec and qcov, carried from step to step
         state["natgrad"] = ctx.natgrad_init(state["params"])
     return state
@@ -134,12 +168,26 @@ def step(rng, alg, state, callback, *objargs):
     each that the update advances in place: the state passed in is consumed by the call (use the returned one; `optimize(state=...)` works on a copy of the buffer and leaves its argument as it was)."""
     state = dict(state)
     ctx, params = state["ctx"], state["params"]
+    q_start = _q_of(state) if isinstance(alg, FisherMinBatchMatch) and callback is not None else None   # (:163 hands the callback the OLD iterate)
     state["iteration"] += 1
     prob_sub, sub_inf = state["prob"], {}
     if alg.subsampling is not None:   # :96-102
         batch, state["sub_st"], sub_inf = S.step_subsampling(rng, alg.subsampling, state["sub_st"])
         prob_sub = P.subsample(state["prob"], batch)
         ctx.set_problem(prob_sub)
+    if isinstance(alg, FisherMinBatchMatch):   # fisherminbatchmatch.jl:139-166
+        d, n = ctx.d, alg.n_samples
+        u, G, fisher, _, elbo = ctx.bam_moments(params, rng.next_index(), n, state["u_buf"], state["grad_buf"])
+        lam = ctx.np_dtype.type(d * n / state["iteration"])   # convert(eltype(mu), d * n_samples / iteration) (:148)
+        ctx.bam_update(params, state["bam"], u, G, n, float(lam))
+        info = {"iteration": state["iteration"], "covweighted_fisher": float(fisher.item()), "elbo": float(elbo.item()), **sub_inf}
+        ctx.synchronize()
+        state["q"] = None
+        if callback is not None:
+            extra = callback(rng=rng, iteration=state["iteration"], q=q_start, state=state)
+            if extra is not None:
+                info = {**extra, **info}
+        return state, False, info
     logpi, grad, _ = ctx.gauss_expected_grad_hess(params, rng.next_index(), alg.n_samples, state["grad_buf"], state["hess_buf"],
                                                   second_order=_second_order(prob_sub))
     entropy = _update(alg, ctx, state, grad, state["hess_buf"])
@@ -160,6 +208,15 @@ def estimate_objective(rng, alg, q=None, prob=None, n_samples=None):
     if isinstance(rng, ALGORITHMS):
         rng, alg, q, prob = O.default_rng(), rng, alg, q
     n = int(n_samples) if n_samples is not None else alg.n_samples
+    if isinstance(alg, FisherMinBatchMatch):   # fisherminbatchmatch.jl:186-195: the covariance-weighted Fisher divergence (no subsampling there)
+        if not isinstance(q, MvLocationScale) or q.family != FULLRANK:
+            raise TypeError("`FisherMinBatchMatch` expects a Gaussian with a lower-triangular scale (FullRankGaussian)")
+        ctx = MiviContext(q.eltype, FULLRANK, len(q), min(n, 16384), O.ClosedFormEntropy.code, rng.seed, device=alg.device)
+        ctx.set_problem(prob)
+        value = float(ctx.estimate_fisher(destructure(q)[0], rng.next_index(), n).item())
+        ctx.synchronize()
+        ctx.close()
+        return value
     obj = O.RepGradELBO(n, entropy=O.MonteCarloEntropy())
     adtype = O.AutoMIVI(device=alg.device)
     if alg.subsampling is None:
@@ -174,12 +231,16 @@ def _steps_on_device(rng, alg, max_iter, state, show_progress):
     info_total, done = [], 0
     while done < max_iter:
         n = min(DEVICE_LOOP_CHUNK, max_iter - done)
-        elbo = _device_steps(alg, ctx, state, rng.counter, n, second)
+        out = _device_steps(alg, ctx, state, rng.counter, n, second)
         ctx.synchronize()
         for _ in range(n):
             rng.next_index()
-        vals = elbo.cpu().numpy()
-        info_total += [{"elbo": float(vals[i]), "iteration": done + i + 1} for i in range(n)]
+        if isinstance(out, tuple):   # batch and match: the step's own `iteration` (:158) is the state's, as the host-driven loop reports it
+            vals, fish = out[0].cpu().numpy(), out[1].cpu().numpy()
+            info_total += [{"iteration": done + i + 1, "covweighted_fisher": float(fish[i]), "elbo": float(vals[i])} for i in range(n)]
+        else:
+            vals = out.cpu().numpy()
+            info_total += [{"elbo": float(vals[i]), "iteration": done + i + 1} for i in range(n)]
         state["iteration"] += n
         state["q"] = None
         done += n

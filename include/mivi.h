@@ -312,6 +312,53 @@ mivi_status_t mivi_natgrad_update_host(mivi_ctx_t *ctx, void *params_host, void 
 mivi_status_t mivi_natgrad_steps(mivi_ctx_t *ctx, void *params_dev, void *state_dev, uint64_t estimate_idx0, int32_t count, int32_t n_samples,
                                  int32_t second_order, double stepsize, int32_t ensure_posdef, void *elbo_dev);
 
+/* FisherMinBatchMatch ("batch and match", src/algorithms/fisherminbatchmatch.jl): the covariance-weighted Fisher divergence minimiser.  It
+ * needs gradients only and takes no step size.  Besides [m; vec(C)] it carries state_dev T[d*d] = Sigma, the covariance (`sigma`, :49), d x d
+ * column-major, a full symmetric matrix with bitwise-mirrored triangles, carried from step to step.  With u (d x B) standard normal,
+ * z = C u + m, g_b = grad logpi(z_b) and lambda = d B / iteration:
+ *   mivi_bam_init (:76): state_dev <- C C'; params_dev is only read.
+ *   mivi_bam_moments (rand_batch_match_samples_with_objective!, :81-111, and the elbo of :157): u_dev, G_dev T[d*n_samples] column-major <- the
+ *     draws (bitwise the eps mivi_sample returns for estimate_idx on a context with n_mc = n_samples) and the per-sample gradients;
+ *     fisher_dev <- sum |u + C' G|^2 / n_samples (:108); logpi_avg_dev <- mean_b logpi(z_b) (:99); elbo_dev <- logpi_avg + entropy(q) (:157).
+ *     2 <= n_samples <= 16384.  Asynchronous for built-in targets, synchronous for callback targets.  The same eps stream and sample / target
+ *     kernels as mivi_gauss_expected_grad_hess.
+ *   mivi_estimate_fisher (estimate_objective, :186-195): value_dev <- the same fisher for ANY n_samples >= 2, in chunks of 16384 columns.
+ *   mivi_bam_update (:143-155): (m, C, Sigma) -> (m', C', Sigma') IN PLACE from u_dev and G_dev (read-only), n_samples = B columns:
+ *       zbar, Cz = mean_and_cov(z)   gbar, Gamma = mean_and_cov(G)   (corrected, 1/(B-1))
+ *       U = lambda Gamma + lambda/(1+lambda) gbar gbar'      V = Sigma + lambda Cz + lambda/(1+lambda) (m - zbar)(m - zbar)'
+ *       Sigma' = 2 V (I + sqrt(I + 4 U V))^-1     m' = m/(1+lambda) + lambda/(1+lambda) (Sigma' gbar + zbar)     C' = cholesky(Sigma').L
+ *     entropy_dev T[1] <- entropy(q') (may be NULL).  C' is lower triangular with exact zeros above the diagonal: the reference's own scale,
+ *     no deviation.  The matrix square root of the non-symmetric U V is taken through the rank-B form of the batch-and-match paper
+ *     (csrc/kernels_bam.hip): one B x B symmetric eigenproblem (cyclic Jacobi in one workgroup, a compile-time bound on
+ *     its sweeps), thin products on the matrix cores and ONE blocked factorisation (that of mivi_natgrad_update); float64 arithmetic for
+ *     either context type; 2 nT + 6 launches, nT = ceil(d / 64).  Bitwise repeatable.  A pivot that is not a positive finite number sets the
+ *     sticky flag of MIVI_ERR_NONPOSITIVE_SCALE and is replaced by 1; an eigenproblem that does not converge within the bound (a NaN in G)
+ *     or a non-finite entropy sets that of MIVI_ERR_NONFINITE; the call returns and the contents of params and state are then unspecified.
+ *     lambda > 0 is the caller's d B / iteration, converted to the parameters' element type as the reference does (:148).
+ *   mivi_bam_steps (step, :113-167, without subsampling and callback): `count` whole steps with no host round trip; step t estimates with
+ *     index estimate_idx0 + t and uses lambda = d n_samples / (iteration0 + t) (iteration0 >= 1); fisher_dev, elbo_dev T[count] (or NULL) <-
+ *     the objective and elbo at the iterate each step STARTS from (:157-158).  The same launches and arithmetic as mivi_bam_moments
+ *     followed by mivi_bam_update: bitwise equal to them.
+ * The _host forms take host buffers, are synchronous and return the sticky status themselves.
+ * Every entry refuses, before anything launches and leaving params and state untouched: a mean-field context, a sharded context, a Stacked
+ * bijector (MIVI_ERR_UNSUPPORTED: the algorithm requires unconstrained support); no target (MIVI_ERR_NO_TARGET); n_samples < 2
+ * (MIVI_ERR_BAD_ARG: the corrected covariance is undefined); n_samples > MIVI_BAM_MAX_SAMPLES for the update and the steps entry
+ * (MIVI_ERR_UNSUPPORTED: more needs a multi-workgroup eigen-solver). */
+#define MIVI_BAM_MAX_SAMPLES 64
+mivi_status_t mivi_bam_init(mivi_ctx_t *ctx, const void *params_dev, void *state_dev);
+mivi_status_t mivi_bam_moments(mivi_ctx_t *ctx, const void *params_dev, uint64_t estimate_idx, int32_t n_samples, void *u_dev, void *G_dev,
+                               void *fisher_dev, void *logpi_avg_dev, void *elbo_dev);
+mivi_status_t mivi_bam_moments_host(mivi_ctx_t *ctx, const void *params_host, uint64_t estimate_idx, int32_t n_samples, void *u_host, void *G_host,
+                                    void *fisher_host, void *logpi_avg_host, void *elbo_host);
+mivi_status_t mivi_estimate_fisher(mivi_ctx_t *ctx, const void *params_dev, uint64_t estimate_idx, int32_t n_samples, void *value_dev);
+mivi_status_t mivi_estimate_fisher_host(mivi_ctx_t *ctx, const void *params_host, uint64_t estimate_idx, int32_t n_samples, void *value_host);
+mivi_status_t mivi_bam_update(mivi_ctx_t *ctx, void *params_dev, void *state_dev, const void *u_dev, const void *G_dev, int32_t n_samples,
+                              double lambda, void *entropy_dev);
+mivi_status_t mivi_bam_update_host(mivi_ctx_t *ctx, void *params_host, void *state_host, const void *u_host, const void *G_host,
+                                   int32_t n_samples, double lambda, void *entropy_host);
+mivi_status_t mivi_bam_steps(mivi_ctx_t *ctx, void *params_dev, void *state_dev, uint64_t estimate_idx0, uint64_t iteration0, int32_t count,
+                             int32_t n_samples, void *fisher_dev, void *elbo_dev);
+
 /* ---- multi-GPU: shard the MC batch, all-reduce the partials, finalize -------------------------- *
  * No counterpart in the reference (single task).  partials_dev: T[partials_len] un-normalised sums over
  * this context's samples; the caller all-reduces (RCCL sum) and calls mivi_finalize on every rank. */
