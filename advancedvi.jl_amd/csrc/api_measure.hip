@@ -120,7 +120,9 @@ static mivi_status_t need_bam(mivi_ctx *c, const char *entry, int32_t n_samples,
   return MIVI_OK;
 }
 
-static const int kBamChunk = 16384;
+static mivi_status_t bam_moments_too_many(mivi_ctx *c) {   // bam_moments is one chunk's work
+  return fail(c, MIVI_ERR_UNSUPPORTED, ("bam_moments: more than " + std::to_string(kSampleChunk) + " samples (mivi_estimate_fisher takes any number)").c_str());
+}
 
 // the update's scratch and room for `tiles` objective partials in the same pair
 static mivi_status_t bam_scratch(mivi_ctx *c, bool update, int tiles) {
@@ -130,11 +132,9 @@ static mivi_status_t bam_scratch(mivi_ctx *c, bool update, int tiles) {
   return ensure(c, c->ms_part, pb > tb ? pb : tb, false);
 }
 
-// One chunk of the objective's sampling stage: the draws of estimate idx, columns [off, off + Mc), in the context's eps plane (leading
+// One chunk of the objective's sampling stage: the Mc draws of `r` (an estimate's columns from r.m_offset on) in the context's eps plane (leading
 // dimension dP), the gradients in c->W, [sum logpi, ..] in c->tmp_out -- the Stein estimator's call -- and the chunk's tile partials.
-static mivi_status_t bam_chunk(mivi_ctx *c, const void *params, uint64_t idx, int off, int Mc, double *part) {
-  RngArgs r = rng_of(c, idx);
-  r.m_offset += off;
+static mivi_status_t bam_chunk(mivi_ctx *c, const void *params, const RngArgs &r, int Mc, double *part) {
   const mivi_status_t s = run_estimate(c, params, r, Mc, 1, chunk_partials_out(c, c->tmp_out.p, Mc), nullptr, nullptr, true);
   if (s) return s;
   launch_bam_fisher(c, params, Mc, c->eps[c->cur].p, (size_t)c->dP, c->W.p, part);
@@ -144,7 +144,7 @@ static mivi_status_t bam_chunk(mivi_ctx *c, const void *params, uint64_t idx, in
 // rand_batch_match_samples_with_objective! for n <= one chunk; the scratch is the caller's to ensure.  u / G (nullable): compact copies.
 static mivi_status_t bam_moments(mivi_ctx *c, const void *params, uint64_t idx, int32_t n, void *u, void *G, void *fisher, void *logpi, void *elbo) {
   mivi_status_t s;
-  if ((s = bam_chunk(c, params, idx, 0, n, (double *)c->ms_part.p))) return s;
+  if ((s = bam_chunk(c, params, rng_of(c, idx), n, (double *)c->ms_part.p))) return s;
   launch_bam_objective(c, params, (const double *)c->ms_part.p, bam_fisher_tiles(c, n), (double)n, c->tmp_out.p, fisher, logpi, elbo);
   const size_t es = c->esize, d = (size_t)c->cfg.d;
   if (u) HIPCHK(c, hipMemcpy2DAsync(u, d * es, c->eps[c->cur].p, (size_t)c->dP * es, d * es, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
@@ -188,7 +188,7 @@ mivi_status_t mivi_bam_moments(mivi_ctx_t *c, const void *params, uint64_t idx, 
   if (!c || !params || !u || !G || !fisher || !logpi_avg || !elbo) return MIVI_ERR_BAD_ARG;
   mivi_status_t s;
   if ((s = need_bam(c, "bam_moments", n_samples, false))) return s;
-  if (n_samples > kBamChunk) return fail(c, MIVI_ERR_UNSUPPORTED, "bam_moments: more than 16384 samples (mivi_estimate_fisher takes any number)");
+  if (n_samples > kSampleChunk) return bam_moments_too_many(c);
   (void)hipSetDevice(c->cfg.device);
   if ((s = bam_scratch(c, false, bam_fisher_tiles(c, n_samples)))) return s;
   return bam_moments(c, params, idx, n_samples, u, G, fisher, logpi_avg, elbo);
@@ -199,7 +199,7 @@ mivi_status_t mivi_bam_moments_host(mivi_ctx_t *c, const void *params_h, uint64_
   if (!c || !params_h || !u_h || !G_h || !fisher_h || !logpi_avg_h || !elbo_h) return MIVI_ERR_BAD_ARG;
   mivi_status_t s;
   if ((s = need_bam(c, "bam_moments", n_samples, false))) return s;
-  if (n_samples > kBamChunk) return fail(c, MIVI_ERR_UNSUPPORTED, "bam_moments: more than 16384 samples (mivi_estimate_fisher takes any number)");
+  if (n_samples > kSampleChunk) return bam_moments_too_many(c);
   (void)hipSetDevice(c->cfg.device);
   BamHost h;
   if ((s = bam_host(c, n_samples, &h)) || (s = bam_scratch(c, false, bam_fisher_tiles(c, n_samples))) || (s = stage_params(c, params_h))) return s;
@@ -214,14 +214,15 @@ mivi_status_t mivi_estimate_fisher(mivi_ctx_t *c, const void *params, uint64_t i
   if ((s = need_bam(c, "estimate_fisher", n_samples, false))) return s;
   (void)hipSetDevice(c->cfg.device);
   int tiles = 0;
-  for (int off = 0; off < n_samples; off += kBamChunk) tiles += bam_fisher_tiles(c, n_samples - off < kBamChunk ? n_samples - off : kBamChunk);
+  (void)for_each_chunk(c, idx, n_samples, 0, 1, [&](const SampleChunk &k) -> mivi_status_t { tiles += bam_fisher_tiles(c, k.Mc); return MIVI_OK; });
   if ((s = bam_scratch(c, false, tiles))) return s;
   double *part = (double *)c->ms_part.p;
-  for (int off = 0; off < n_samples; off += kBamChunk) {
-    const int Mc = n_samples - off < kBamChunk ? n_samples - off : kBamChunk;
-    if ((s = bam_chunk(c, params, idx, off, Mc, part))) return s;
-    part += bam_fisher_tiles(c, Mc);
-  }
+  s = for_each_chunk(c, idx, n_samples, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
+    const mivi_status_t se = bam_chunk(c, params, k.rng, k.Mc, part);
+    part += bam_fisher_tiles(c, k.Mc);
+    return se;
+  });
+  if (s) return s;
   launch_bam_objective(c, params, (const double *)c->ms_part.p, tiles, (double)n_samples, nullptr, value, nullptr, nullptr);
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
@@ -278,7 +279,7 @@ mivi_status_t mivi_bam_steps(mivi_ctx_t *c, void *params, void *state, uint64_t 
                          elbo ? (char *)elbo + (size_t)t * es : nullptr)))
       return s;
     double lambda = (double)c->cfg.d * (double)n_samples / (double)(iteration0 + (uint64_t)t);
-    if (c->cfg.dtype == MIVI_F32) lambda = (double)(float)lambda;   // convert(eltype(mu), d * n_samples / iteration) (:148)
+    lambda = by_dtype(c, [&](auto t) { return (double)(decltype(t))lambda; });   // convert(eltype(mu), d * n_samples / iteration) (:148)
     if ((s = bam_update(c, params, state, c->eps[c->cur].p, (size_t)c->dP, c->W.p, n_samples, lambda, nullptr))) return s;
   }
   return MIVI_OK;

@@ -36,10 +36,9 @@ mivi_status_t mivi_estimate_objective(mivi_ctx_t *c, const void *params, uint64_
   if (entropy < 0) entropy = c->cfg.entropy;
   if (entropy > MIVI_ENT_STL_ZERO_GRAD) return MIVI_ERR_BAD_ARG;
   (void)hipSetDevice(c->cfg.device);
-  const int CH = 16384;
   // all estimators share their *value* within {closed-form} / {MC, STL, STL-zero-grad}
   const bool engine_sized = c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && n_samples / c->cfg.n_mc >= 8 && c->cfg.n_mc >= 128;   // (tried below; falls back to the chunks)
-  if (n_samples <= CH && !engine_sized) {
+  if (n_samples <= kSampleChunk && !engine_sized) {
     OutArgs o = final_out(c, value, nullptr);
     o.ent_kind = entropy;
     o.M_total = n_samples;
@@ -68,17 +67,16 @@ mivi_status_t mivi_estimate_objective(mivi_ctx_t *c, const void *params, uint64_
       }
     }
   }
-  for (int off = off0, first = first0; off < n_samples; off += CH, first = 0) {
-    const int Mc = n_samples - off < CH ? n_samples - off : CH;
+  const mivi_status_t s = for_each_chunk(c, idx, n_samples, off0, first0, [&](const SampleChunk &k) -> mivi_status_t {
     OutArgs o = final_out(c, tmpv, nullptr);
     o.ent_kind = entropy;
-    o.M_total = Mc;
-    RngArgs r = rng_of(c, idx);
-    r.m_offset += off;
-    mivi_status_t s = run_estimate(c, params, r, Mc, 0, o);
-    if (s) return s;
-    acc_chunk_value(c, tmpv, (double)Mc / (double)n_samples, first);
-  }
+    o.M_total = k.Mc;
+    const mivi_status_t se = run_estimate(c, params, k.rng, k.Mc, 0, o);
+    if (se) return se;
+    acc_chunk_value(c, tmpv, (double)k.Mc / (double)n_samples, k.first);
+    return MIVI_OK;
+  });
+  if (s) return s;
   store_acc_value(c, value);
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
@@ -122,15 +120,12 @@ mivi_status_t mivi_gauss_expected_grad_hess(mivi_ctx_t *c, const void *params, u
     return s;
   const bool stl2 = stl2_shape_ok(c, d);   // second-generation solve with the d columns of the product as right-hand sides
   if (stl2 && ((s = ensure(c, c->stl_X, ((size_t)d * d + (size_t)(d / 2) * (d / 2)) * es + 4096, false)) || (s = ensure(c, c->stl_F, mivi::stl_pack_units(d) * 4, false)))) return s;
-  const int CH = 16384;
-  const bool single_chunk = n_samples <= CH;
+  const bool single_chunk = n_samples <= kSampleChunk;
   bool pack_done = false, tail_done = false;
   char *part = (char *)c->tmp_out.p;   // [sum ell, sum 0.5 eps^2] of a chunk
-  for (int off = 0, first = 1; off < n_samples; off += CH, first = 0) {
-    const int Mc = n_samples - off < CH ? n_samples - off : CH;
+  s = for_each_chunk(c, idx, n_samples, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
+    const int Mc = k.Mc, first = k.first;
     const OutArgs o = chunk_partials_out(c, part, Mc);
-    RngArgs r = rng_of(c, idx);
-    r.m_offset += off;
     c->want_stl_pack = stl2 && first;   // the solve's parameter-only preparation rides in the first chunk's sampling kernel
     c->stl_pack_done = false;
     // second-generation accumulation kernel (f32, d and chunk multiples of 64 / 128): with ONE chunk it also assembles the chunk's
@@ -139,17 +134,16 @@ mivi_status_t mivi_gauss_expected_grad_hess(mivi_ctx_t *c, const void *params, u
     ValueJob vj{};
     c->value_deferred = false;
     c->defer_value = (st2 && single_chunk) ? &vj : nullptr;
-    s = run_estimate(c, params, r, Mc, 1, o, nullptr, nullptr, true);
+    const mivi_status_t se = run_estimate(c, params, k.rng, Mc, 1, o, nullptr, nullptr, true);
     c->defer_value = nullptr;
     c->want_stl_pack = false;
-    if (s) return s;
+    if (se) return se;
     const bool fused_tail = c->value_deferred;
     c->value_deferred = false;
     if (first) pack_done = c->stl_pack_done;
     // (a single chunk's partial is read by the finishing kernel directly: no accumulation launch)
     if (!single_chunk) acc_chunk_value(c, part, 1.0, first);
-    const bool last = off + CH >= n_samples;
-    const double scale = last ? 1.0 / (double)n_samples : 1.0;
+    const double scale = k.last ? 1.0 / (double)n_samples : 1.0;
     if (st2) {
       launch_lds_stein_outer(c, Mc, c->stein_A.p, (double *)c->stein_g.p, first, scale, (double)n_samples, fused_tail ? grad : nullptr,
                              fused_tail ? logpi_avg : nullptr, fused_tail ? &vj : nullptr);
@@ -157,7 +151,9 @@ mivi_status_t mivi_gauss_expected_grad_hess(mivi_ctx_t *c, const void *params, u
     } else {
       launch_stein_outer(c, Mc, c->stein_A.p, (double *)c->stein_g.p, first, scale);
     }
-  }
+    return MIVI_OK;
+  });
+  if (s) return s;
   if (!tail_done)
     launch_stein_finish(c, (double)n_samples, (const double *)c->stein_g.p, (const double *)c->acc.p, single_chunk ? part : nullptr, grad, logpi_avg);
   if (stl2) {
@@ -196,19 +192,17 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, 
   (void)hipSetDevice(c->cfg.device);
   const int d = c->cfg.d;
   const size_t es = c->esize;
-  const int CH = 16384;
   mivi_status_t s;
   if (plugin) {
     std::vector<double> gs((size_t)d, 0.0), Hs((size_t)d * d, 0.0);
     double ls = 0.0;
     std::vector<char> hH((size_t)d * d * es);
-    for (int off = 0; off < n_samples; off += CH) {
-      const int Mc = n_samples - off < CH ? n_samples - off : CH;
-      if ((s = ensure_work(c, Mc))) return s;
-      RngArgs r = rng_of(c, idx);
-      r.m_offset += off;
+    s = for_each_chunk(c, idx, n_samples, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
+      const int Mc = k.Mc;
+      const mivi_status_t se = ensure_work(c, Mc);
+      if (se) return se;
       eps_spec_drop(c);
-      launch_eps(c, r, Mc);
+      launch_eps(c, k.rng, Mc);
       launch_fr_sample(c, params, Mc, TGT_NONE, c->Z.p);
       c->h_Z.resize((size_t)d * Mc * es);
       c->h_G.resize((size_t)d * Mc * es);
@@ -222,12 +216,13 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, 
         for (int i = 0; i < d; ++i) gs[i] += host_get(c->h_G.data(), c->cfg.dtype, (size_t)m * d + i);
       }
       for (size_t e = 0; e < (size_t)d * d; ++e) Hs[e] += host_get(hH.data(), c->cfg.dtype, e);
-    }
+      return MIVI_OK;
+    });
+    if (s) return s;
     const double inv = 1.0 / (double)n_samples;
     std::vector<char> out((1 + (size_t)d + (size_t)d * d) * es);
     auto put = [&](size_t k, double v) {
-      if (c->cfg.dtype == MIVI_F32) ((float *)out.data())[k] = (float)v;
-      else ((double *)out.data())[k] = v;
+      by_dtype(c, [&](auto t) { ((decltype(t) *)out.data())[k] = (decltype(t))v; });
     };
     put(0, ls * inv);
     for (int i = 0; i < d; ++i) put(1 + (size_t)i, gs[i] * inv);
@@ -243,18 +238,18 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, 
     if ((s = ensure(c, c->h2_acc, target_hess2_bytes(c), false))) return s;
     if (!target_hess2_begin(c)) return fail(c, MIVI_ERR_HIP, "second-order branch: clearing the accumulators failed");
   }
-  const bool single_chunk = n_samples <= CH;
+  const bool single_chunk = n_samples <= kSampleChunk;
   char *part = (char *)c->tmp_out.p;   // [sum ell, sum 0.5 eps^2] of a chunk
-  for (int off = 0, first = 1; off < n_samples; off += CH, first = 0) {
-    const int Mc = n_samples - off < CH ? n_samples - off : CH;
-    const OutArgs o = chunk_partials_out(c, part, Mc);
-    RngArgs r = rng_of(c, idx);
-    r.m_offset += off;
-    if ((s = run_estimate(c, params, r, Mc, 1, o, nullptr, nullptr, true))) return s;   // sampling + target: W = grad logpi(z), the chunk's value partials
-    if (!single_chunk) acc_chunk_value(c, part, 1.0, first);
-    launch_stein_gsum(c, Mc, (double *)c->stein_g.p, first);
-    if (sampled) target_hess2_accumulate(c, Mc);   // (the chunk's samples are still in c->Z)
-  }
+  s = for_each_chunk(c, idx, n_samples, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
+    const OutArgs o = chunk_partials_out(c, part, k.Mc);
+    const mivi_status_t se = run_estimate(c, params, k.rng, k.Mc, 1, o, nullptr, nullptr, true);   // sampling + target: W = grad logpi(z), the chunk's value partials
+    if (se) return se;
+    if (!single_chunk) acc_chunk_value(c, part, 1.0, k.first);
+    launch_stein_gsum(c, k.Mc, (double *)c->stein_g.p, k.first);
+    if (sampled) target_hess2_accumulate(c, k.Mc);   // (the chunk's samples are still in c->Z)
+    return MIVI_OK;
+  });
+  if (s) return s;
   launch_stein_finish(c, (double)n_samples, (const double *)c->stein_g.p, (const double *)c->acc.p, single_chunk ? part : nullptr, grad, logpi_avg);
   if (sampled) target_hess2_finish(c, n_samples, hess);
   else launch_const_hess(c, hess);

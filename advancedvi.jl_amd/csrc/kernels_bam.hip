@@ -486,36 +486,36 @@ static void bam_update_t(mivi_ctx *c, void *params, void *state, const void *u, 
 }
 
 void launch_bam_update(mivi_ctx *c, void *params, void *state, const void *u, size_t ldu, const void *G, int B, double lambda, void *entropy) {
-  if (c->cfg.dtype == MIVI_F32) bam_update_t<float>(c, params, state, u, ldu, G, B, lambda, entropy);
-  else bam_update_t<double>(c, params, state, u, ldu, G, B, lambda, entropy);
+  by_dtype(c, [&](auto t) { bam_update_t<decltype(t)>(c, params, state, u, ldu, G, B, lambda, entropy); });
 }
 
 void launch_bam_init(mivi_ctx *c, const void *params, void *state) {
   const int d = c->cfg.d;
   const NgdGeom g(d);
-  if (c->cfg.dtype == MIVI_F32) hipLaunchKernelGGL((k_bam_init<float>), dim3(g.n_tiles), dim3(256), 0, c->stream, d, (const float *)params + d, (float *)state);
-  else hipLaunchKernelGGL((k_bam_init<double>), dim3(g.n_tiles), dim3(256), 0, c->stream, d, (const double *)params + d, (double *)state);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_bam_init<T>), dim3(g.n_tiles), dim3(256), 0, c->stream, d, (const T *)params + d, (T *)state);
+  });
 }
 
 void launch_bam_fisher(mivi_ctx *c, const void *params, int M, const void *u, size_t ldu, const void *G, double *part) {
   const int d = c->cfg.d;
   const NgdGeom g(d);
   const dim3 grid(bam_fisher_tiles(c, M));
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL((k_bam_fisher<float>), grid, dim3(256), 0, c->stream, d, g.nT, M, (const float *)params + d, (const float *)u, ldu, (const float *)G, part);
-  else
-    hipLaunchKernelGGL((k_bam_fisher<double>), grid, dim3(256), 0, c->stream, d, g.nT, M, (const double *)params + d, (const double *)u, ldu, (const double *)G, part);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_bam_fisher<T>), grid, dim3(256), 0, c->stream, d, g.nT, M, (const T *)params + d, (const T *)u, ldu, (const T *)G, part);
+  });
 }
 
 void launch_bam_objective(mivi_ctx *c, const void *params, const double *part, int n_part, double n, const void *ell_sum, void *fisher, void *logpi_avg,
                           void *elbo) {
   int *st = (int *)c->status.p;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL((k_bam_objective<float>), dim3(1), dim3(256), 0, c->stream, c->cfg.d, (const float *)params, part, n_part, n, (const float *)ell_sum,
-                       (float *)fisher, (float *)logpi_avg, (float *)elbo, st);
-  else
-    hipLaunchKernelGGL((k_bam_objective<double>), dim3(1), dim3(256), 0, c->stream, c->cfg.d, (const double *)params, part, n_part, n, (const double *)ell_sum,
-                       (double *)fisher, (double *)logpi_avg, (double *)elbo, st);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_bam_objective<T>), dim3(1), dim3(256), 0, c->stream, c->cfg.d, (const T *)params, part, n_part, n, (const T *)ell_sum, (T *)fisher,
+                       (T *)logpi_avg, (T *)elbo, st);
+  });
 }
 
 }  // namespace mivi

@@ -1262,10 +1262,10 @@ int launch_eps(mivi_ctx *c, const RngArgs &rng, int M) {
     ++sk->lane[c->lane_id].n_eps;
     return nrid;
   }
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_eps<float>, dim3(nblk), dim3(256), 0, c->stream, eps_args<float>(c, rng, M, c->cur));
-  else
-    hipLaunchKernelGGL(k_eps<double>, dim3(nblk), dim3(256), 0, c->stream, eps_args<double>(c, rng, M, c->cur));
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_eps<T>, dim3(nblk), dim3(256), 0, c->stream, eps_args<T>(c, rng, M, c->cur));
+  });
   return nblk;
 }
 
@@ -1431,12 +1431,10 @@ void launch_fr_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, c
 void launch_rt_from_z(mivi_ctx *c, int M) {
   dim3 grid((c->cfg.d + 63) / 64, (M + 63) / 64);
   const void *tm = c->target == TGT_DENSE_GAUSS ? c->t_mean.p : nullptr;   // LogReg: plain transpose
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_rt_from_z<float>, grid, dim3(256), 0, c->stream, c->cfg.d, M, c->MP, (const float *)c->Z.p,
-                       (const float *)tm, (float *)c->RT.p);
-  else
-    hipLaunchKernelGGL(k_rt_from_z<double>, grid, dim3(256), 0, c->stream, c->cfg.d, M, c->MP, (const double *)c->Z.p,
-                       (const double *)tm, (double *)c->RT.p);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_rt_from_z<T>, grid, dim3(256), 0, c->stream, c->cfg.d, M, c->MP, (const T *)c->Z.p, (const T *)tm, (T *)c->RT.p);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1547,8 +1545,10 @@ __global__ __launch_bounds__(256) void k_stein_gsum(int d, int M, const T *G, do
 }
 void launch_stein_gsum(mivi_ctx *c, int M, double *gsum, int first) {
   const dim3 grid((c->cfg.d + 31) / 32);
-  if (c->cfg.dtype == MIVI_F32) hipLaunchKernelGGL(k_stein_gsum<float>, grid, dim3(256), 0, c->stream, c->cfg.d, M, (const float *)c->W.p, gsum, first);
-  else hipLaunchKernelGGL(k_stein_gsum<double>, grid, dim3(256), 0, c->stream, c->cfg.d, M, (const double *)c->W.p, gsum, first);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_stein_gsum<T>, grid, dim3(256), 0, c->stream, c->cfg.d, M, (const T *)c->W.p, gsum, first);
+  });
 }
 // the built-in Gaussian targets' Hessian, a constant: diagonal N(m, diag(sigma^2)): -diag(1 / sigma^2); dense N(m, L L'): -P, P = (L L')^-1
 template <typename T>
@@ -1562,28 +1562,27 @@ void launch_const_hess(mivi_ctx *c, void *hess) {
   const size_t n = (size_t)c->cfg.d * c->cfg.d;
   const dim3 grid((unsigned)((n + 255) / 256));
   const bool dense = c->target == TGT_DENSE_GAUSS;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_const_hess<float>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, (const float *)c->t_istd.p, dense ? (const float *)c->t_prec.p : nullptr, (float *)hess);
-  else
-    hipLaunchKernelGGL(k_const_hess<double>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, (const double *)c->t_istd.p, dense ? (const double *)c->t_prec.p : nullptr, (double *)hess);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_const_hess<T>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, (const T *)c->t_istd.p, dense ? (const T *)c->t_prec.p : nullptr, (T *)hess);
+  });
 }
 
 void launch_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first, double scale) {
   dim3 grid(c->dP / 32, (c->cfg.d + 31) / 32);
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_stein_outer<float>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, M, (const float *)c->eps[c->cur].p,
-                       (const float *)c->W.p, (float *)A, gsum, first, (float)scale);
-  else
-    hipLaunchKernelGGL(k_stein_outer<double>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, M, (const double *)c->eps[c->cur].p,
-                       (const double *)c->W.p, (double *)A, gsum, first, scale);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_stein_outer<T>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, M, (const T *)c->eps[c->cur].p, (const T *)c->W.p, (T *)A, gsum,
+                       first, (T)scale);
+  });
 }
 
 void launch_stein_finish(mivi_ctx *c, double n, const double *gsum, const double *ell_sum, const void *ell_single, void *grad, void *logpi_avg) {
   const int nb = (c->cfg.d + 255) / 256;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_stein_finish<float>, dim3(nb), dim3(256), 0, c->stream, c->cfg.d, n, gsum, ell_sum, (const float *)ell_single, (float *)grad, (float *)logpi_avg);
-  else
-    hipLaunchKernelGGL(k_stein_finish<double>, dim3(nb), dim3(256), 0, c->stream, c->cfg.d, n, gsum, ell_sum, (const double *)ell_single, (double *)grad, (double *)logpi_avg);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_stein_finish<T>, dim3(nb), dim3(256), 0, c->stream, c->cfg.d, n, gsum, ell_sum, (const T *)ell_single, (T *)grad, (T *)logpi_avg);
+  });
 }
 
 // W += C^-T eps for the M sample columns -- or, with `rhs` / `out` given, out += C^-T rhs for any M-column right-hand
@@ -1627,29 +1626,19 @@ void launch_fr_stl(mivi_ctx *c, const void *params, int M, const void *rhs, void
                        (const float *)c->stl_Dinv.p);
     return;
   }
-  if (c->cfg.dtype == MIVI_F32) {
-    FrArgs<float> a = fr_args<float>(c, params, M);
-    if (rhs) a.eps = (const float *)rhs;
-    if (out) a.W = (float *)out;
-    const size_t sh = (8 * (size_t)c->dP + 32 * 33) * sizeof(float);
-    static size_t attr_f = 0;
-    if (attr_f < sh) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fr_stl<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-      attr_f = sh;
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    FrArgs<T> a = fr_args<T>(c, params, M);
+    if (rhs) a.eps = (const T *)rhs;
+    if (out) a.W = (T *)out;
+    const size_t sh = (8 * (size_t)c->dP + 32 * 33) * sizeof(T);
+    static size_t attr = 0;   // (one per element type)
+    if (attr < sh) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fr_stl<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+      attr = sh;
     }
-    hipLaunchKernelGGL(k_fr_stl<float>, dim3(nblk), dim3(256), sh, c->stream, a);
-  } else {
-    FrArgs<double> a = fr_args<double>(c, params, M);
-    if (rhs) a.eps = (const double *)rhs;
-    if (out) a.W = (double *)out;
-    const size_t sh = (8 * (size_t)c->dP + 32 * 33) * sizeof(double);
-    static size_t attr_d = 0;
-    if (attr_d < sh) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fr_stl<double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-      attr_d = sh;
-    }
-    hipLaunchKernelGGL(k_fr_stl<double>, dim3(nblk), dim3(256), sh, c->stream, a);
-  }
+    hipLaunchKernelGGL(k_fr_stl<T>, dim3(nblk), dim3(256), sh, c->stream, a);
+  });
 }
 
 }  // namespace mivi

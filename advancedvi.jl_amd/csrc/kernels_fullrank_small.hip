@@ -282,8 +282,7 @@ static void fr_small_loop_impl(mivi_ctx *c, void *params, void *opt_state, uint6
 // rule 0 Descent / 1 Adam (default betas); elbo: n_steps doubles; value: one element of T
 void launch_fr_small_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta,
                           double clip_eps, double *elbo, void *value, const mivi_loop_t *gen) {
-  if (c->cfg.dtype == MIVI_F32) fr_small_loop_impl<float>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, elbo, value, gen);
-  else fr_small_loop_impl<double>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, elbo, value, gen);
+  by_dtype(c, [&](auto t) { fr_small_loop_impl<decltype(t)>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, elbo, value, gen); });
 }
 
 }  // namespace mivi

@@ -207,22 +207,24 @@ bool target_hess2_begin(mivi_ctx *c) { return hipMemsetAsync(c->h2_acc.p, 0, tar
 void target_hess2_accumulate(mivi_ctx *c, int Mc) {
   const int d = c->cfg.d;
   double *stats = (double *)c->h2_acc.p, *rows = stats + 8, *wsum = rows + d;
-  const bool f32 = c->cfg.dtype == MIVI_F32;
   const int kind = c->target == TGT_LOGREG ? 0 : (c->funnel_constrained ? 2 : 1);
-  if (f32) hipLaunchKernelGGL(k_h2_stats<float>, dim3((Mc + 3) / 4), dim3(256), 0, c->stream, kind, d, Mc, (const float *)c->Z.p, c->lr_variant, c->funnel_sigma_v, stats, rows);
-  else hipLaunchKernelGGL(k_h2_stats<double>, dim3((Mc + 3) / 4), dim3(256), 0, c->stream, kind, d, Mc, (const double *)c->Z.p, c->lr_variant, c->funnel_sigma_v, stats, rows);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_h2_stats<T>, dim3((Mc + 3) / 4), dim3(256), 0, c->stream, kind, d, Mc, (const T *)c->Z.p, c->lr_variant, c->funnel_sigma_v, stats, rows);
+  });
   if (kind == 0) {
     const int64_t n = c->lr_n;
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)((Mc + 63) / 64));
-    if (f32) hipLaunchKernelGGL(k_h2_lr_wsum<float>, grid, dim3(256), 0, c->stream, d, d - 1, Mc, n, (const float *)c->lr_X, (const float *)c->Z.p, wsum);
-    else hipLaunchKernelGGL(k_h2_lr_wsum<double>, grid, dim3(256), 0, c->stream, d, d - 1, Mc, n, (const double *)c->lr_X, (const double *)c->Z.p, wsum);
+    by_dtype(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_h2_lr_wsum<T>, grid, dim3(256), 0, c->stream, d, d - 1, Mc, n, (const T *)c->lr_X, (const T *)c->Z.p, wsum);
+    });
   }
 }
 
 void target_hess2_finish(mivi_ctx *c, int n_samples, void *hess) {
   const int d = c->cfg.d;
   double *stats = (double *)c->h2_acc.p, *rows = stats + 8, *wsum = rows + d;
-  const bool f32 = c->cfg.dtype == MIVI_F32;
   const int kind = c->target == TGT_LOGREG ? 0 : (c->funnel_constrained ? 2 : 1);
   double *Hacc = nullptr;
   if (kind == 0) {
@@ -237,13 +239,17 @@ void target_hess2_finish(mivi_ctx *c, int n_samples, void *hess) {
     const int64_t rps = ((n + S - 1) / S + 63) / 64 * 64;
     S = (int)((n + rps - 1) / rps);
     const dim3 grid(nt, nt, S);
-    if (f32) hipLaunchKernelGGL(k_h2_lr_gram<float>, grid, dim3(256), 0, c->stream, p, n, rps, (const float *)c->lr_X, wsum, Hacc);
-    else hipLaunchKernelGGL(k_h2_lr_gram<double>, grid, dim3(256), 0, c->stream, p, n, rps, (const double *)c->lr_X, wsum, Hacc);
+    by_dtype(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_h2_lr_gram<T>, grid, dim3(256), 0, c->stream, p, n, rps, (const T *)c->lr_X, wsum, Hacc);
+    });
   }
   const size_t nn = (size_t)d * d;
   const dim3 g2((unsigned)((nn + 255) / 256));
-  if (f32) hipLaunchKernelGGL(k_h2_finish<float>, g2, dim3(256), 0, c->stream, kind, d, 1.0 / (double)n_samples, c->lr_likeadj, Hacc, stats, rows, (float *)hess);
-  else hipLaunchKernelGGL(k_h2_finish<double>, g2, dim3(256), 0, c->stream, kind, d, 1.0 / (double)n_samples, c->lr_likeadj, Hacc, stats, rows, (double *)hess);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_h2_finish<T>, g2, dim3(256), 0, c->stream, kind, d, 1.0 / (double)n_samples, c->lr_likeadj, Hacc, stats, rows, (T *)hess);
+  });
 }
 
 }  // namespace mivi

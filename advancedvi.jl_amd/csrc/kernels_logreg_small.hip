@@ -548,8 +548,7 @@ static bool lr_small_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, 
 }
 // elbo: n_steps doubles; value: one element of T (the last step's objective value)
 bool launch_lr_small_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, double *elbo, void *value, double *part) {
-  if (c->cfg.dtype == MIVI_F32) return lr_small_loop_impl<float>(c, params, l, elbo, value, part);
-  return lr_small_loop_impl<double>(c, params, l, elbo, value, part);
+  return by_dtype(c, [&](auto t) { return lr_small_loop_impl<decltype(t)>(c, params, l, elbo, value, part); });
 }
 
 }  // namespace mivi

@@ -788,8 +788,7 @@ static bool mf_gen_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, do
 // hist: n_steps * 4 * ceil(d / 4) doubles; elbo: n_steps doubles; scratch: mf_gen_loop_scratch_bytes.  false: not launched (the device cannot hold the
 // exchanging grid at once): the caller takes the graph of launches
 bool launch_mf_gen_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, double *hist, double *elbo, char *scratch) {
-  if (c->cfg.dtype == MIVI_F32) return mf_gen_loop_impl<float>(c, params, l, hist, elbo, scratch);
-  return mf_gen_loop_impl<double>(c, params, l, hist, elbo, scratch);
+  return by_dtype(c, [&](auto t) { return mf_gen_loop_impl<decltype(t)>(c, params, l, hist, elbo, scratch); });
 }
 
 // rule 0 Descent / 1 Adam: n_steps SGD iterations;  rule -1: n_steps estimates at fixed parameters, the last one's gradient
@@ -797,8 +796,9 @@ bool launch_mf_gen_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, double 
 // lane_scratch (rule < 0): mf_loop_lanes(c, n_steps) * 2 d elements of T, or nullptr = one lane.
 void launch_mf_sgd_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule,
                         double eta, double clip_eps, double *hist, double *elbo, void *grad_out, void *lane_scratch, void *value_last) {
-  if (c->cfg.dtype == MIVI_F32) mf_sgd_loop_impl<float>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, hist, elbo, grad_out, lane_scratch, value_last);
-  else mf_sgd_loop_impl<double>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, hist, elbo, grad_out, lane_scratch, value_last);
+  by_dtype(c, [&](auto t) {
+    mf_sgd_loop_impl<decltype(t)>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, hist, elbo, grad_out, lane_scratch, value_last);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1011,8 +1011,7 @@ static void mf_funnel_loop_impl(mivi_ctx *c, const void *params, uint64_t idx0, 
 // e0_tab: n_steps * n_mc elements of T (eps[0, m] of every estimate, filled here by k_funnel_e0), or nullptr.
 void launch_mf_funnel_loop(mivi_ctx *c, const void *params, uint64_t idx0, int n_steps, double *hist, double *elbo, void *scratch,
                            void *value, void *grad, void *lane_scratch, void *e0_tab) {
-  if (c->cfg.dtype == MIVI_F32) mf_funnel_loop_impl<float>(c, params, idx0, n_steps, hist, elbo, scratch, value, grad, lane_scratch, e0_tab);
-  else mf_funnel_loop_impl<double>(c, params, idx0, n_steps, hist, elbo, scratch, value, grad, lane_scratch, e0_tab);
+  by_dtype(c, [&](auto t) { mf_funnel_loop_impl<decltype(t)>(c, params, idx0, n_steps, hist, elbo, scratch, value, grad, lane_scratch, e0_tab); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1347,8 +1346,9 @@ static bool mf_funnel_sgd_loop_impl(mivi_ctx *c, void *params, void *opt_state, 
 // pub: 4 elements of T; gtmp: d + 1 elements of T; elbo: n_steps doubles; value: one element of T (the last step's objective value).
 bool launch_mf_funnel_sgd_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta,
                                double clip_eps, double *hist, unsigned *sync, void *pub, void *gtmp, double *elbo, void *value) {
-  if (c->cfg.dtype == MIVI_F32) return mf_funnel_sgd_loop_impl<float>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, hist, sync, pub, gtmp, elbo, value);
-  return mf_funnel_sgd_loop_impl<double>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, hist, sync, pub, gtmp, elbo, value);
+  return by_dtype(c, [&](auto t) {
+    return mf_funnel_sgd_loop_impl<decltype(t)>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, hist, sync, pub, gtmp, elbo, value);
+  });
 }
 
 // rand(rng, q::MvLocationScale{<:Diagonal}, M): Z = mu + sigma .* eps  (location_scale.jl:80-87)
@@ -1431,10 +1431,7 @@ static void mf_main_impl(mivi_ctx *c, const void *params, const RngArgs &rng, in
 
 void launch_mf_main(mivi_ctx *c, const void *params, const RngArgs &rng, int M, int want_grad, const void *G,
                     const ValueIn &vin, const OutArgs &out, const ValueJob *prev) {
-  if (c->cfg.dtype == MIVI_F32)
-    mf_main_impl<float>(c, params, rng, M, want_grad, G, vin, out, prev);
-  else
-    mf_main_impl<double>(c, params, rng, M, want_grad, G, vin, out, prev);
+  by_dtype(c, [&](auto t) { mf_main_impl<decltype(t)>(c, params, rng, M, want_grad, G, vin, out, prev); });
 }
 
 template <typename T>
@@ -1458,10 +1455,7 @@ static void sample_mf_impl(mivi_ctx *c, const void *params, const RngArgs &rng, 
 
 void launch_sample_mf(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *Z, void *eps, int ld_eps,
                       double *he_part) {
-  if (c->cfg.dtype == MIVI_F32)
-    sample_mf_impl<float>(c, params, rng, M, Z, eps, ld_eps, he_part);
-  else
-    sample_mf_impl<double>(c, params, rng, M, Z, eps, ld_eps, he_part);
+  by_dtype(c, [&](auto t) { sample_mf_impl<decltype(t)>(c, params, rng, M, Z, eps, ld_eps, he_part); });
 }
 
 }  // namespace mivi

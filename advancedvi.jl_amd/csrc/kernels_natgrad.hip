@@ -600,28 +600,27 @@ size_t natgrad_part_bytes(const mivi_ctx *c) {
 
 void launch_natgrad_update(mivi_ctx *c, void *params, void *state, const void *grad, const void *hess, double eta, int ensure_posdef, const void *logpi,
                            void *entropy, void *elbo) {
-  const bool f32 = c->cfg.dtype == MIVI_F32;
   if (c->cfg.d <= kNatgradSmallD) {   // one workgroup, in the context's type
-    if (f32) hipLaunchKernelGGL((k_natgrad_small<float, float>), dim3(1), dim3(256), 0, c->stream,
-                                natgrad_update_args<float, float>(c, params, state, grad, hess, eta, ensure_posdef, logpi, entropy, elbo));
-    else hipLaunchKernelGGL((k_natgrad_small<double, double>), dim3(1), dim3(256), 0, c->stream,
-                            natgrad_update_args<double, double>(c, params, state, grad, hess, eta, ensure_posdef, logpi, entropy, elbo));
-  } else if (f32) {   // tiles: float64 scratch and arithmetic for either type, only the loads and stores of the caller's buffers differ
-    launch_natgrad_tiles(c, natgrad_update_args<double, float>(c, params, state, grad, hess, eta, ensure_posdef, logpi, entropy, elbo));
-  } else {
-    launch_natgrad_tiles(c, natgrad_update_args<double, double>(c, params, state, grad, hess, eta, ensure_posdef, logpi, entropy, elbo));
+    by_dtype(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_natgrad_small<T, T>), dim3(1), dim3(256), 0, c->stream,
+                         natgrad_update_args<T, T>(c, params, state, grad, hess, eta, ensure_posdef, logpi, entropy, elbo));
+    });
+  } else {   // tiles: float64 scratch and arithmetic for either type, only the loads and stores of the caller's buffers differ
+    by_dtype(c, [&](auto t) {
+      launch_natgrad_tiles(c, natgrad_update_args<double, decltype(t)>(c, params, state, grad, hess, eta, ensure_posdef, logpi, entropy, elbo));
+    });
   }
 }
 
 void launch_natgrad_init(mivi_ctx *c, void *params, void *state) {
-  const bool f32 = c->cfg.dtype == MIVI_F32;
   if (c->cfg.d <= kNatgradSmallD) {
-    if (f32) hipLaunchKernelGGL((k_natgrad_init_small<float, float>), dim3(1), dim3(256), 0, c->stream, natgrad_args<float, float>(c, params, state));
-    else hipLaunchKernelGGL((k_natgrad_init_small<double, double>), dim3(1), dim3(256), 0, c->stream, natgrad_args<double, double>(c, params, state));
-  } else if (f32) {
-    launch_natgrad_init_tiles(c, natgrad_args<double, float>(c, params, state));
+    by_dtype(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_natgrad_init_small<T, T>), dim3(1), dim3(256), 0, c->stream, natgrad_args<T, T>(c, params, state));
+    });
   } else {
-    launch_natgrad_init_tiles(c, natgrad_args<double, double>(c, params, state));
+    by_dtype(c, [&](auto t) { launch_natgrad_init_tiles(c, natgrad_args<double, decltype(t)>(c, params, state)); });
   }
 }
 

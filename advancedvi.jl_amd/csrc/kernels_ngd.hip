@@ -246,8 +246,7 @@ size_t ngd_work_bytes(const mivi_ctx *c) {
 size_t ngd_part_bytes(const mivi_ctx *c) { return c->cfg.d <= kNgdSmallD ? 0 : (2 * (size_t)NgdGeom(c->cfg.d).nT + 2) * sizeof(double); }
 
 void launch_ngd_update(mivi_ctx *c, void *params, const void *grad, const void *hess, double eta, const void *logpi, void *entropy, void *elbo) {
-  if (c->cfg.dtype == MIVI_F32) launch_ngd_t<float>(c, params, grad, hess, eta, logpi, entropy, elbo);
-  else launch_ngd_t<double>(c, params, grad, hess, eta, logpi, entropy, elbo);
+  by_dtype(c, [&](auto t) { launch_ngd_t<decltype(t)>(c, params, grad, hess, eta, logpi, entropy, elbo); });
 }
 
 }  // namespace mivi

@@ -512,7 +512,10 @@ void launch_p2p_handover4(mivi_ctx *c, unsigned *ready, unsigned ready_val, cons
 // one lane of the exchange on c->stream: estimates t = lane, lane + lanes, ... < count with partial vectors P[t % ring]
 void launch_p2p_exchange(mivi_ctx *c, const void *params, const void *const *P, int ring, void *value, void *grad, int phases, int lane, int lanes,
                          int count, const unsigned *ready, unsigned *freed, bool direct) {
-  auto fill = [&](auto &a) {
+  const size_t plen4 = (size_t)mivi_params_len(c) + 4;   // one scratch output {value (4 slots), gradient}; kP2PGroup of them per lane
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    P2PArgs<T> a{};
     a.direct = direct ? 1 : 0;
     a.d = c->cfg.d; a.family = c->cfg.family; a.ent_kind = c->cfg.entropy; a.M_total = c->M_total;
     a.L = mivi_partials_len(c); a.n = c->p2p_n; a.cn = c->p2p_cn;
@@ -527,23 +530,11 @@ void launch_p2p_exchange(mivi_ctx *c, const void *params, const void *const *P, 
     a.ring = ring;
     a.ready = ready;
     a.freed = freed;
-  };
-  const size_t plen4 = (size_t)mivi_params_len(c) + 4;   // one scratch output {value (4 slots), gradient}; kP2PGroup of them per lane
-  if (c->cfg.dtype == MIVI_F32) {
-    P2PArgs<float> a{};
-    fill(a);
-    for (int k = 0; k < ring; ++k) a.P[k] = (const float *)P[k];
-    a.params = (const float *)params; a.value = (float *)value; a.grad = (float *)grad;
-    a.scratch = (float *)c->p2p_scratch.p + plen4 * kP2PGroup * lane; a.scratch_stride = (long long)plen4;
-    hipLaunchKernelGGL(k_p2p_exchange<float>, dim3(c->p2p_G + 1), dim3(256), 0, c->stream, a);
-  } else {
-    P2PArgs<double> a{};
-    fill(a);
-    for (int k = 0; k < ring; ++k) a.P[k] = (const double *)P[k];
-    a.params = (const double *)params; a.value = (double *)value; a.grad = (double *)grad;
-    a.scratch = (double *)c->p2p_scratch.p + plen4 * kP2PGroup * lane; a.scratch_stride = (long long)plen4;
-    hipLaunchKernelGGL(k_p2p_exchange<double>, dim3(c->p2p_G + 1), dim3(256), 0, c->stream, a);
-  }
+    for (int k = 0; k < ring; ++k) a.P[k] = (const T *)P[k];
+    a.params = (const T *)params; a.value = (T *)value; a.grad = (T *)grad;
+    a.scratch = (T *)c->p2p_scratch.p + plen4 * kP2PGroup * lane; a.scratch_stride = (long long)plen4;
+    hipLaunchKernelGGL(k_p2p_exchange<T>, dim3(c->p2p_G + 1), dim3(256), 0, c->stream, a);
+  });
 }
 
 }  // namespace mivi

@@ -178,17 +178,15 @@ static void sg_norms_impl(mivi_ctx *c, const RngArgs &rng, int M) {
     hipLaunchKernelGGL((k_sg_norms<T, false>), dim3(M), dim3(256), 0, c->stream, c->cfg.d, 0, (const T *)nullptr, rng, he);
 }
 void launch_sg_norms(mivi_ctx *c, const RngArgs &rng, int M) {
-  if (c->cfg.dtype == MIVI_F32) sg_norms_impl<float>(c, rng, M); else sg_norms_impl<double>(c, rng, M);
+  by_dtype(c, [&](auto t) { sg_norms_impl<decltype(t)>(c, rng, M); });
 }
 
 void launch_sg_dense_ell(mivi_ctx *c, int M) {
   double *ell = (double *)c->sg_d.p + c->sg_cap;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_sg_dense_ell<float>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const float *)c->Z.p, (const float *)c->W.p,
-                       (const float *)c->t_mean.p, ell);
-  else
-    hipLaunchKernelGGL(k_sg_dense_ell<double>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const double *)c->Z.p, (const double *)c->W.p,
-                       (const double *)c->t_mean.p, ell);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_sg_dense_ell<T>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const T *)c->Z.p, (const T *)c->W.p, (const T *)c->t_mean.p, ell);
+  });
 }
 
 template <typename T>
@@ -210,30 +208,27 @@ static void sg_stats_impl(mivi_ctx *c, const void *params, int M, bool ell_f64, 
   hipLaunchKernelGGL(k_sg_stats<T>, dim3(1), dim3(256), 0, c->stream, a);
 }
 void launch_sg_stats(mivi_ctx *c, const void *params, int M, bool ell_f64, void *value, void *elbo) {
-  if (c->cfg.dtype == MIVI_F32) sg_stats_impl<float>(c, params, M, ell_f64, value, elbo);
-  else sg_stats_impl<double>(c, params, M, ell_f64, value, elbo);
+  by_dtype(c, [&](auto t) { sg_stats_impl<decltype(t)>(c, params, M, ell_f64, value, elbo); });
 }
 
 void launch_sg_scale(mivi_ctx *c, int M) {
   const int Mr = (M + 63) / 64 * 64;   // (<= MP: the solves read whole blocks of up to 64 columns)
   const dim3 grid((c->dP + 255) / 256, Mr);
   const double *w = (const double *)c->sg_d.p + 2 * (size_t)c->sg_cap;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_sg_scale<float>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, M, (const float *)c->eps[0].p, w, (float *)c->sg_S.p,
-                       (float *)c->W.p);
-  else
-    hipLaunchKernelGGL(k_sg_scale<double>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, M, (const double *)c->eps[0].p, w,
-                       (double *)c->sg_S.p, (double *)c->W.p);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_sg_scale<T>, grid, dim3(256), 0, c->stream, c->cfg.d, c->dP, M, (const T *)c->eps[0].p, w, (T *)c->sg_S.p, (T *)c->W.p);
+  });
 }
 
 void launch_sg_mf_grad(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *grad) {
   const int d = c->cfg.d, d4 = (d + 3) / 4;
   const dim3 grid((d4 + 15) / 16);
   const double *w = (const double *)c->sg_d.p + 2 * (size_t)c->sg_cap;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_sg_mf_grad<float>, grid, dim3(256), 0, c->stream, d, M, (const float *)params, rng, w, (float *)grad);
-  else
-    hipLaunchKernelGGL(k_sg_mf_grad<double>, grid, dim3(256), 0, c->stream, d, M, (const double *)params, rng, w, (double *)grad);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_sg_mf_grad<T>, grid, dim3(256), 0, c->stream, d, M, (const T *)params, rng, w, (T *)grad);
+  });
 }
 
 }  // namespace mivi

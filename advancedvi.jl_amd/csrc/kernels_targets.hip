@@ -74,7 +74,7 @@ static void col_target_impl(mivi_ctx *c, int M, int want_grad) {
 }
 
 void launch_col_target(mivi_ctx *c, int M, int want_grad) {
-  if (c->cfg.dtype == MIVI_F32) col_target_impl<float>(c, M, want_grad); else col_target_impl<double>(c, M, want_grad);
+  by_dtype(c, [&](auto t) { col_target_impl<decltype(t)>(c, M, want_grad); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -109,18 +109,17 @@ __global__ __launch_bounds__(256) void k_bij_bwd(int d, const uint8_t *mask, con
   if (ell && tid == 0) ell[m] += ld[m];
 }
 void launch_bij_forward(mivi_ctx *c, int M) {
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_bij_fwd<float>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const uint8_t *)c->bij_mask.p, (float *)c->Z.p, (float *)c->bij_ld.p);
-  else
-    hipLaunchKernelGGL(k_bij_fwd<double>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const uint8_t *)c->bij_mask.p, (double *)c->Z.p, (double *)c->bij_ld.p);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bij_fwd<T>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const uint8_t *)c->bij_mask.p, (T *)c->Z.p, (T *)c->bij_ld.p);
+  });
 }
 void launch_bij_backward(mivi_ctx *c, int M, int want_grad, bool add_to_ell) {
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_bij_bwd<float>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const uint8_t *)c->bij_mask.p, (const float *)c->Z.p,
-                       (float *)c->W.p, add_to_ell ? (float *)c->ell.p : nullptr, (const float *)c->bij_ld.p, want_grad);
-  else
-    hipLaunchKernelGGL(k_bij_bwd<double>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const uint8_t *)c->bij_mask.p, (const double *)c->Z.p,
-                       (double *)c->W.p, add_to_ell ? (double *)c->ell.p : nullptr, (const double *)c->bij_ld.p, want_grad);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_bij_bwd<T>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const uint8_t *)c->bij_mask.p, (const T *)c->Z.p, (T *)c->W.p,
+                       add_to_ell ? (T *)c->ell.p : nullptr, (const T *)c->bij_ld.p, want_grad);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1214,15 +1213,15 @@ void launch_logreg_gather(mivi_ctx *c, int64_t b) {
   const int p = c->cfg.d - 1;
   const dim3 g((unsigned)((b + 255) / 256), p);
   const long long *idx = (const long long *)c->lr_idx.p;
-  if (c->cfg.dtype == MIVI_F32) {
-    hipLaunchKernelGGL(k_lr_gather_cm<float>, g, dim3(256), 0, c->stream, (long long)c->lr_n_full, (long long)b, p, idx,
-                       (const float *)c->lr_X_full, c->lr_y_full, (float *)c->lr_Xsub.p, (uint8_t *)c->lr_ysub.p);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_lr_gather_cm<T>, g, dim3(256), 0, c->stream, (long long)c->lr_n_full, (long long)b, p, idx, (const T *)c->lr_X_full, c->lr_y_full,
+                       (T *)c->lr_Xsub.p, (uint8_t *)c->lr_ysub.p);
+  });
+  if (c->cfg.dtype == MIVI_F32) {   // the row-major copy exists for f32 only (the matrix-core route)
     const int ldx = (p + 31) / 32 * 32;
     hipLaunchKernelGGL(k_lr_gather_rm, dim3((unsigned)((b + 15) / 16 * 16)), dim3(128), 0, c->stream, (long long)b, ldx, idx,
                        (const float *)c->lr_Xrm.p, (float *)c->lr_Xrm_sub.p);
-  } else {
-    hipLaunchKernelGGL(k_lr_gather_cm<double>, g, dim3(256), 0, c->stream, (long long)c->lr_n_full, (long long)b, p, idx,
-                       (const double *)c->lr_X_full, c->lr_y_full, (double *)c->lr_Xsub.p, (uint8_t *)c->lr_ysub.p);
   }
 }
 
@@ -1423,8 +1422,7 @@ static bool logreg_impl(mivi_ctx *c, int M, int want_grad) {
 // false: device allocation of the residual / partial buffers failed
 bool launch_logreg_target(mivi_ctx *c, int M, int want_grad) {
   if (lr_geom(c, M).mfma) return logreg_mfma(c, M, want_grad);
-  if (c->cfg.dtype == MIVI_F32) return logreg_impl<float>(c, M, want_grad);
-  return logreg_impl<double>(c, M, want_grad);
+  return by_dtype(c, [&](auto t) { return logreg_impl<decltype(t)>(c, M, want_grad); });
 }
 
 }  // namespace mivi

@@ -8,6 +8,12 @@
 
 namespace mivi {
 
+// workgroups of 256 threads for a grid-stride walk over n elements, at most `cap` of them
+static int grid256(int64_t n, int cap = 2048) {
+  const int64_t nb = (n + 255) / 256;
+  return nb > cap ? cap : (int)nb;
+}
+
 template <typename T>
 struct FinArgs {
   int d, family;
@@ -79,14 +85,10 @@ static void finalize_impl(mivi_ctx *c, const void *params, const void *partials,
   a.ent_kind = c->cfg.entropy;
   a.M_total = c->M_total;
   a.status = (int *)c->status.p;
-  const int64_t plen = mivi_params_len(c);
-  int nb = (int)((plen + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL(k_finalize<T>, dim3(nb), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_finalize<T>, dim3(grid256(mivi_params_len(c))), dim3(256), 0, c->stream, a);
 }
 void launch_finalize(mivi_ctx *c, const void *params, const void *partials, void *value, void *grad) {
-  if (c->cfg.dtype == MIVI_F32) finalize_impl<float>(c, params, partials, value, grad);
-  else finalize_impl<double>(c, params, partials, value, grad);
+  by_dtype(c, [&](auto t) { finalize_impl<decltype(t)>(c, params, partials, value, grad); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -190,28 +192,22 @@ __global__ __launch_bounds__(256) void k_unpack_final(int d, int family, long lo
 
 void launch_finalize_slice(mivi_ctx *c, const void *params, const void *sum, long long g0, long long n, void *fin) {
   const long long L = mivi_partials_len(c);
-  int nb = (int)((n + 255) / 256);
-  if (nb > 1024) nb = 1024;
+  int nb = grid256(n, 1024);
   if (nb < 1) nb = 1;
-  if (c->cfg.dtype == MIVI_F32) {
-    SliceArgs<float> a{c->cfg.d, c->cfg.family, c->cfg.entropy, c->M_total, L, g0, n, (const float *)params, (const float *)sum, (float *)fin, 0.0, 0};
-    hipLaunchKernelGGL(k_finalize_slice<float>, dim3(nb + 1), dim3(256), 0, c->stream, a);
-  } else {
-    SliceArgs<double> a{c->cfg.d, c->cfg.family, c->cfg.entropy, c->M_total, L, g0, n, (const double *)params, (const double *)sum, (double *)fin, 0.0, 0};
-    hipLaunchKernelGGL(k_finalize_slice<double>, dim3(nb + 1), dim3(256), 0, c->stream, a);
-  }
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    SliceArgs<T> a{c->cfg.d, c->cfg.family, c->cfg.entropy, c->M_total, L, g0, n, (const T *)params, (const T *)sum, (T *)fin, 0.0, 0};
+    hipLaunchKernelGGL(k_finalize_slice<T>, dim3(nb + 1), dim3(256), 0, c->stream, a);
+  });
 }
 void launch_unpack_final(mivi_ctx *c, const void *fin, void *value, void *grad) {
   const long long L = mivi_partials_len(c);
-  const int64_t plen = mivi_params_len(c);
-  int nb = (int)((plen + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_unpack_final<float>, dim3(nb), dim3(256), 0, c->stream, c->cfg.d, c->cfg.family, L, (const float *)fin, (float *)value,
-                       (float *)grad, (int *)c->status.p);
-  else
-    hipLaunchKernelGGL(k_unpack_final<double>, dim3(nb), dim3(256), 0, c->stream, c->cfg.d, c->cfg.family, L, (const double *)fin, (double *)value,
-                       (double *)grad, (int *)c->status.p);
+  const int nb = grid256(mivi_params_len(c));
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_unpack_final<T>, dim3(nb), dim3(256), 0, c->stream, c->cfg.d, c->cfg.family, L, (const T *)fin, (T *)value, (T *)grad,
+                       (int *)c->status.p);
+  });
 }
 
 template <typename T>
@@ -257,18 +253,16 @@ void launch_value_only(mivi_ctx *c, const void *params, const ValueIn &vin, cons
     return;
   }
   if (vin.fn.ab && c->cfg.family == MIVI_MEANFIELD) {
-    if (c->cfg.dtype == MIVI_F32)
-      hipLaunchKernelGGL(k_value_funnel<float>, dim3(1), dim3(256), 0, c->stream, c->cfg.d, (const float *)params, vin, out);
-    else
-      hipLaunchKernelGGL(k_value_funnel<double>, dim3(1), dim3(256), 0, c->stream, c->cfg.d, (const double *)params, vin, out);
+    by_dtype(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_value_funnel<T>, dim3(1), dim3(256), 0, c->stream, c->cfg.d, (const T *)params, vin, out);
+    });
     return;
   }
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_value_only<float>, dim3(1), dim3(256), 0, c->stream, c->cfg.d, c->cfg.family,
-                       (const float *)params, vin, out);
-  else
-    hipLaunchKernelGGL(k_value_only<double>, dim3(1), dim3(256), 0, c->stream, c->cfg.d, c->cfg.family,
-                       (const double *)params, vin, out);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_value_only<T>, dim3(1), dim3(256), 0, c->stream, c->cfg.d, c->cfg.family, (const T *)params, vin, out);
+  });
 }
 
 template <typename T>
@@ -281,12 +275,10 @@ __global__ void k_clip(int d, int family, T *params, T epsilon) {
 }
 void launch_clip(mivi_ctx *c, void *params, double epsilon) {
   const int d = c->cfg.d;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_clip<float>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, c->cfg.family, (float *)params,
-                       (float)epsilon);
-  else
-    hipLaunchKernelGGL(k_clip<double>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, c->cfg.family,
-                       (double *)params, epsilon);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_clip<T>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, c->cfg.family, (T *)params, (T)epsilon);
+  });
 }
 
 // ProximalLocationScaleEntropy (src/optimization/proximal_location_scale_entropy.jl:44-61).  The step size comes from the
@@ -307,12 +299,10 @@ __global__ void k_prox(int d, int family, T *params, double stepsize, const doub
 void launch_prox(mivi_ctx *c, void *params, double stepsize, const void *dog_state, int dog_kind) {
   const int d = c->cfg.d;
   const double *sc = dog_state ? (const double *)((const char *)dog_state + mivi_dog_state_bytes(c) - 16) : nullptr;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_prox<float>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, c->cfg.family, (float *)params,
-                       stepsize, sc, dog_kind);
-  else
-    hipLaunchKernelGGL(k_prox<double>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, c->cfg.family, (double *)params,
-                       stepsize, sc, dog_kind);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_prox<T>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, c->cfg.family, (T *)params, stepsize, sc, dog_kind);
+  });
 }
 
 // is flat index i a scale-diagonal entry? (ClipScale fused into the update; clip_eps = NaN means "no ClipScale": any real epsilon, also <= 0, is a legal one)
@@ -333,14 +323,11 @@ __global__ void k_descent(int64_t n, T *params, const T *grad, T eta, int d, int
 }
 void launch_descent(mivi_ctx *c, void *params, const void *grad, double eta, double clip_eps) {
   const int64_t n = mivi_params_len(c);
-  int nb = (int)((n + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_descent<float>, dim3(nb), dim3(256), 0, c->stream, n, (float *)params, (const float *)grad,
-                       (float)eta, c->cfg.d, c->cfg.family, (float)clip_eps);
-  else
-    hipLaunchKernelGGL(k_descent<double>, dim3(nb), dim3(256), 0, c->stream, n, (double *)params, (const double *)grad,
-                       eta, c->cfg.d, c->cfg.family, clip_eps);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_descent<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, (T)eta, c->cfg.d, c->cfg.family,
+                       (T)clip_eps);
+  });
 }
 
 // Optimisers.Adam (optim_rules.h); bias corrections once per workgroup
@@ -363,14 +350,11 @@ __global__ void k_adam(int64_t n, T *params, const T *grad, T *state, const int6
 void launch_adam(mivi_ctx *c, void *params, const void *grad, void *state, const int64_t *t_ptr, int64_t t_base,
                  double eta, double b1, double b2, double eps, double clip_eps) {
   const int64_t n = mivi_params_len(c);
-  int nb = (int)((n + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_adam<float>, dim3(nb), dim3(256), 0, c->stream, n, (float *)params, (const float *)grad,
-                       (float *)state, t_ptr, t_base, eta, b1, b2, eps, c->cfg.d, c->cfg.family, (float)clip_eps);
-  else
-    hipLaunchKernelGGL(k_adam<double>, dim3(nb), dim3(256), 0, c->stream, n, (double *)params, (const double *)grad,
-                       (double *)state, t_ptr, t_base, eta, b1, b2, eps, c->cfg.d, c->cfg.family, clip_eps);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_adam<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, (T *)state, t_ptr, t_base, eta, b1, b2,
+                       eps, c->cfg.d, c->cfg.family, (T)clip_eps);
+  });
 }
 
 // COCOB (optim_rules.h): state = [L; G; R; theta; x1], n elements each
@@ -389,14 +373,11 @@ __global__ void k_cocob(int64_t n, T *params, const T *grad, T *state, T alpha, 
 }
 void launch_cocob(mivi_ctx *c, void *params, const void *grad, void *state, double alpha, double clip_eps) {
   const int64_t n = mivi_params_len(c);
-  int nb = (int)((n + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_cocob<float>, dim3(nb), dim3(256), 0, c->stream, n, (float *)params, (const float *)grad, (float *)state,
-                       (float)alpha, c->cfg.d, c->cfg.family, (float)clip_eps);
-  else
-    hipLaunchKernelGGL(k_cocob<double>, dim3(nb), dim3(256), 0, c->stream, n, (double *)params, (const double *)grad, (double *)state,
-                       alpha, c->cfg.d, c->cfg.family, clip_eps);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_cocob<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, (T *)state, (T)alpha, c->cfg.d,
+                       c->cfg.family, (T)clip_eps);
+  });
 }
 
 __global__ void k_bump(uint64_t *ctr, uint64_t by) { *ctr += by; }
@@ -425,12 +406,10 @@ __global__ void k_poly_average(int64_t n, T *y, const T *x, double avg_eta, cons
 }
 void launch_poly_average(mivi_ctx *c, void *avg, const void *params, double avg_eta, const long long *t_ptr, long long t_base) {
   const int64_t n = mivi_params_len(c);
-  int nb = (int)((n + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_poly_average<float>, dim3(nb), dim3(256), 0, c->stream, n, (float *)avg, (const float *)params, avg_eta, t_ptr, t_base);
-  else
-    hipLaunchKernelGGL(k_poly_average<double>, dim3(nb), dim3(256), 0, c->stream, n, (double *)avg, (const double *)params, avg_eta, t_ptr, t_base);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_poly_average<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)avg, (const T *)params, avg_eta, t_ptr, t_base);
+  });
 }
 
 template <typename T>
@@ -505,20 +484,18 @@ __global__ __launch_bounds__(1024) void k_dog_update(int64_t n, T *params, const
 }
 
 void launch_axpby(mivi_ctx *c, void *y, double a, const void *x, double b, int64_t n) {
-  int nb = (int)((n + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_axpby<float>, dim3(nb), dim3(256), 0, c->stream, n, (float *)y, a, (const float *)x, b);
-  else
-    hipLaunchKernelGGL(k_axpby<double>, dim3(nb), dim3(256), 0, c->stream, n, (double *)y, a, (const double *)x, b);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_axpby<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)y, a, (const T *)x, b);
+  });
 }
 void launch_dog_init(mivi_ctx *c, const void *params, void *state, double alpha) {
   const int64_t n = mivi_params_len(c);
   double *sc = (double *)((char *)state + mivi_dog_state_bytes(c) - 16);
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_dog_init<float>, dim3(1), dim3(1024), 0, c->stream, n, (const float *)params, (float *)state, sc, alpha);
-  else
-    hipLaunchKernelGGL(k_dog_init<double>, dim3(1), dim3(1024), 0, c->stream, n, (const double *)params, (double *)state, sc, alpha);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_dog_init<T>, dim3(1), dim3(1024), 0, c->stream, n, (const T *)params, (T *)state, sc, alpha);
+  });
 }
 // Large parameter vectors (full-rank: d + d^2): the single-workgroup kernel above walks 10^6 elements in 600 us.
 // Three launches instead: per-workgroup partials of the two norms -> one thread folds them (fixed order), advances
@@ -598,30 +575,23 @@ bool launch_dog_update_fused(mivi_ctx *c, void *params, const void *grad, void *
   const int64_t n = mivi_params_len(c);
   double *sc = (double *)((char *)state + mivi_dog_state_bytes(c) - 16);
   if (!(n > 16384 && c->dog_part.p)) {   // small vectors: the single-workgroup kernel, with the same fused tail
-    if (c->cfg.dtype == MIVI_F32)
-      hipLaunchKernelGGL((k_dog_update<float, true>), dim3(1), dim3(1024), 0, c->stream, n, (float *)params, (const float *)grad,
-                         (const float *)state, sc, kind, c->cfg.d, c->cfg.family, (float)clip_eps, (float *)avg, avg_eta, t_ptr, t_base);
-    else
-      hipLaunchKernelGGL((k_dog_update<double, true>), dim3(1), dim3(1024), 0, c->stream, n, (double *)params, (const double *)grad,
-                         (const double *)state, sc, kind, c->cfg.d, c->cfg.family, clip_eps, (double *)avg, avg_eta, t_ptr, t_base);
-    return true;
+    return by_dtype(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_dog_update<T, true>), dim3(1), dim3(1024), 0, c->stream, n, (T *)params, (const T *)grad, (const T *)state, sc, kind,
+                         c->cfg.d, c->cfg.family, (T)clip_eps, (T *)avg, avg_eta, t_ptr, t_base);
+      return true;
+    });
   }
   const int nb = 512;
   double *part = (double *)c->dog_part.p, *eta = part + 2 * nb;
-  if (c->cfg.dtype == MIVI_F32) {
-    hipLaunchKernelGGL(k_dog_norms<float>, dim3(nb), dim3(256), 0, c->stream, n, (const float *)params, (const float *)grad,
-                       (const float *)state, part);
+  return by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_dog_norms<T>, dim3(nb), dim3(256), 0, c->stream, n, (const T *)params, (const T *)grad, (const T *)state, part);
     hipLaunchKernelGGL(k_dog_eta, dim3(1), dim3(256), 0, c->stream, nb, part, sc, eta, kind);
-    hipLaunchKernelGGL(k_dog_apply_fused<float>, dim3(2048), dim3(256), 0, c->stream, n, (float *)params, (const float *)grad,
-                       eta, c->cfg.d, c->cfg.family, (float)clip_eps, (float *)avg, avg_eta, t_ptr, t_base);
-  } else {
-    hipLaunchKernelGGL(k_dog_norms<double>, dim3(nb), dim3(256), 0, c->stream, n, (const double *)params, (const double *)grad,
-                       (const double *)state, part);
-    hipLaunchKernelGGL(k_dog_eta, dim3(1), dim3(256), 0, c->stream, nb, part, sc, eta, kind);
-    hipLaunchKernelGGL(k_dog_apply_fused<double>, dim3(2048), dim3(256), 0, c->stream, n, (double *)params,
-                       (const double *)grad, eta, c->cfg.d, c->cfg.family, clip_eps, (double *)avg, avg_eta, t_ptr, t_base);
-  }
-  return true;
+    hipLaunchKernelGGL(k_dog_apply_fused<T>, dim3(2048), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, eta, c->cfg.d, c->cfg.family,
+                       (T)clip_eps, (T *)avg, avg_eta, t_ptr, t_base);
+    return true;
+  });
 }
 
 void launch_dog_update(mivi_ctx *c, void *params, const void *grad, void *state, int kind) {
@@ -630,25 +600,18 @@ void launch_dog_update(mivi_ctx *c, void *params, const void *grad, void *state,
   if (n > 16384 && c->dog_part.p) {
     const int nb = 512;
     double *part = (double *)c->dog_part.p, *eta = part + 2 * nb;
-    if (c->cfg.dtype == MIVI_F32) {
-      hipLaunchKernelGGL(k_dog_norms<float>, dim3(nb), dim3(256), 0, c->stream, n, (const float *)params, (const float *)grad,
-                         (const float *)state, part);
+    by_dtype(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_dog_norms<T>, dim3(nb), dim3(256), 0, c->stream, n, (const T *)params, (const T *)grad, (const T *)state, part);
       hipLaunchKernelGGL(k_dog_eta, dim3(1), dim3(256), 0, c->stream, nb, part, sc, eta, kind);
-      hipLaunchKernelGGL(k_dog_apply<float>, dim3(2048), dim3(256), 0, c->stream, n, (float *)params, (const float *)grad, eta);
-    } else {
-      hipLaunchKernelGGL(k_dog_norms<double>, dim3(nb), dim3(256), 0, c->stream, n, (const double *)params,
-                         (const double *)grad, (const double *)state, part);
-      hipLaunchKernelGGL(k_dog_eta, dim3(1), dim3(256), 0, c->stream, nb, part, sc, eta, kind);
-      hipLaunchKernelGGL(k_dog_apply<double>, dim3(2048), dim3(256), 0, c->stream, n, (double *)params, (const double *)grad, eta);
-    }
+      hipLaunchKernelGGL(k_dog_apply<T>, dim3(2048), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, eta);
+    });
     return;
   }
-  if (c->cfg.dtype == MIVI_F32)
-    hipLaunchKernelGGL(k_dog_update<float>, dim3(1), dim3(1024), 0, c->stream, n, (float *)params, (const float *)grad,
-                       (const float *)state, sc, kind);
-  else
-    hipLaunchKernelGGL(k_dog_update<double>, dim3(1), dim3(1024), 0, c->stream, n, (double *)params, (const double *)grad,
-                       (const double *)state, sc, kind);
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_dog_update<T>, dim3(1), dim3(1024), 0, c->stream, n, (T *)params, (const T *)grad, (const T *)state, sc, kind);
+  });
 }
 
 }  // namespace mivi

@@ -460,6 +460,11 @@ struct mivi_ctx {
   mivi::DevBuf kid_out[kMaxKids];       // value (16 bytes) + gradient of the child chains that do not hold the batch's last estimate
 };
 
+// The one precision dispatch of the host launch layer: f(T{}) with T the context's element type, its result returned.  A launch whose two
+// precisions differ in nothing but T goes through it; one whose precisions take different routes keeps its explicit test on cfg.dtype.
+template <typename F>
+inline auto by_dtype(const mivi_ctx *c, F &&f) { return c->cfg.dtype == MIVI_F32 ? f(float{}) : f(double{}); }
+
 namespace mivi {
 
 // kernels_meanfield.hip

@@ -187,6 +187,20 @@ def test_graph_capture_has_one_owner():
     assert not re.search(r"\b(p0|p1|aux0|aux1)\b", cache), cache
 
 
+def test_precision_dispatch_is_written_once():
+    """A kernel that exists for float and double is launched through by_dtype (csrc/mivi_internal.h), where its name carries the element
+    type as a template parameter.  Only a launcher whose two precisions take different routes may name `k_x<float` and `k_x<double`."""
+    csrc = os.path.join(ROOT, "advancedvi.jl_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip"))
+    both = set(re.findall(r"\b(k_\w+)<float", src)) & set(re.findall(r"\b(k_\w+)<double", src))
+    assert both == {
+        # launch_fr_stl (kernels_fullrank.hip): the 16-column solve is taken by f64 only off the MIVI_F64_VALU cross-check and within its
+        # own LDS bound (d <= 1024; f32: d <= 2304), so each precision tests for its route and prepares its transposed scale there
+        "k_stl_prep",
+        "k_stl_solve_la16",
+    }, sorted(both)
+
+
 def test_host_philox_matches_oracle_bit_exact(lib):
     rng = np.random.default_rng(0)
     for _ in range(50):
