@@ -77,6 +77,10 @@ SIGNATURES = {
     "mivi_bam_update": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
     "mivi_bam_update_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
     "mivi_bam_steps": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mivi_wass_init": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mivi_wass_update": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "mivi_wass_update_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "mivi_wass_steps": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p]),
     "mivi_set_target_hess_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_GRADIENT_AND_HESSIAN_FN, C.c_void_p]),
     "mivi_set_logreg_route": (C.c_int32, [C.c_void_p, C.c_int32]),
     "mivi_estimate_partials": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -464,6 +464,44 @@ class MiviContext:
                                                self._p(fisher), self._p(elbo)))
         return fisher, elbo
 
+    # -- KLMinWassFwdBwd (mivi_wass_*: klminwassfwdbwd.jl) ----------------------------------------------------------------------
+    def wass_init(self, params, state=None):
+        """mivi_wass_init: the device tensor Sigma = C C' (d^2, column-major, triangles bitwise mirrored) of the device parameters `params`."""
+        state = self.empty(self.d * self.d) if state is None else state
+        self._chk(self.lib.mivi_wass_init(self.h, self._p(params), self._p(state)))
+        return state
+
+    def wass_update(self, params, state, grad, hess, stepsize, entropy=None):
+        """mivi_wass_update: the proximal (forward-backward) update of the device tensors `params` ([m; vec C]) and `state` (Sigma) in place
+        from grad (d) and hess (d*d column-major, as gauss_expected_grad_hess fills it); returns entropy(q') as a 1-element device tensor."""
+        entropy = self.empty(1) if entropy is None else entropy
+        hess = hess.t() if hess.dim() == 2 else hess   # the (d, d) matrix view gauss_expected_grad_hess returns -> its column-major storage
+        if not hess.is_contiguous():
+            hess = hess.contiguous()
+        self._chk(self.lib.mivi_wass_update(self.h, self._p(params), self._p(state), self._p(grad), self._p(hess), float(stepsize),
+                                            self._p(entropy)))
+        return entropy
+
+    def wass_update_host(self, params, state, grad, hess, stepsize):
+        """mivi_wass_update_host on numpy arrays: params ([m; vec C]), state (Sigma, d^2 or (d, d)), grad (d), hess ((d, d) matrix); returns
+        (params', state' (flat, column-major), entropy(q'))."""
+        p = np.array(params, dtype=self.np_dtype, copy=True)
+        st = np.array(np.asarray(state).reshape(-1, order="F"), dtype=self.np_dtype, copy=True)
+        g = np.ascontiguousarray(grad, dtype=self.np_dtype)
+        H = np.asfortranarray(hess, dtype=self.np_dtype)
+        ent = np.zeros(1, dtype=self.np_dtype)
+        self._chk(self.lib.mivi_wass_update_host(self.h, p.ctypes.data, st.ctypes.data, g.ctypes.data, H.ctypes.data, float(stepsize),
+                                                 ent.ctypes.data))
+        return p, st, ent[0]
+
+    def wass_steps(self, params, state, idx0, count, stepsize, n_samples=0, second_order=False, elbo=None):
+        """mivi_wass_steps: `count` iterations {estimator (index idx0 + t), update} on the device tensors `params` and `state`; returns
+        elbo (count)."""
+        elbo = self.empty(int(count)) if elbo is None else elbo
+        self._raise_cb(self.lib.mivi_wass_steps(self.h, self._p(params), self._p(state), idx0, int(count), int(n_samples),
+                                                1 if second_order else 0, float(stepsize), self._p(elbo)))
+        return elbo
+
     def estimate_partials(self, params, idx, partials=None):
         p = self.to_device(params)
         partials = self.empty(self.partials_len) if partials is None else partials

@@ -1,10 +1,12 @@
-// libmivi C ABI, parts 10 and 11: the measure-space algorithms on the device-resident [m; vec C] --
+// libmivi C ABI, parts 10 to 12: the measure-space algorithms on the device-resident [m; vec C] --
 //   KLMinSqrtNaturalGradDescent (src/algorithms/klminsqrtnaturalgraddescent.jl): the square-root natural-gradient update (kernels_ngd.hip);
 //   KLMinNaturalGradDescent (src/algorithms/klminnaturalgraddescent.jl): the state [S; Sigma] of `init` (:83-87) and the natural-gradient
 //     update of `step` (:129-145) (kernels_natgrad.hip; its scale convention, a LOWER-triangular C' where the reference's new scale is upper
 //     triangular, is stated there and in include/mivi.h);
 //   FisherMinBatchMatch (src/algorithms/fisherminbatchmatch.jl): the state Sigma of `init` (:76), the per-sample objective (:81-111) and the
-//     batch-and-match update of `step` (:143-155) (kernels_bam.hip; below, after the shared helpers)
+//     batch-and-match update of `step` (:143-155) (kernels_bam.hip; below, after the shared helpers);
+//   KLMinWassFwdBwd (src/algorithms/klminwassfwdbwd.jl): the state Sigma of `init` (:75, batch and match's launch) and the proximal update of
+//     `step` (:105-114) (kernels_wass.hip)
 // -- and whole steps {estimator, update} without a host round trip.  A step is the existing estimator entry (mivi_gauss_expected_grad_hess /
 // _hess2) into context-owned buffers followed by the update, whose last launch also forms elbo = logpi_avg + entropy(q') and the sticky
 // flags: launches are fused, arithmetic is not, so the _steps entries are bitwise the single calls.  The algorithms differ in the update
@@ -28,24 +30,43 @@ mivi_status_t ngd_est(mivi_ctx *c, NgdEst *e) {
   return MIVI_OK;
 }
 
-// Which update: the natural-gradient one on (params, state) or, state == nullptr, the square-root one on params alone.  Both work in the
-// context's one scratch pair, which holds nothing between calls: each ensures it to its own need.
-struct Update {
-  void *state;
-  int ensure_posdef;
+// Which update.  The three work in the context's one scratch pair, which holds nothing between calls: each ensures it to its own need.
+enum class Algorithm { SqrtNgd, NatGrad, Wass };
 
+struct Update {
+  Algorithm alg;
+  void *state;         // SqrtNgd: none; NatGrad: [S; Sigma]; Wass: Sigma
+  int ensure_posdef;   // NatGrad
+
+  // the elements of `state`
+  static size_t state_len(const mivi_ctx *c, Algorithm alg) {
+    const size_t d = (size_t)c->cfg.d;
+    switch (alg) {
+      case Algorithm::NatGrad: return 2 * d * d;
+      case Algorithm::Wass: return d * d;
+      default: return 0;
+    }
+  }
   mivi_status_t scratch(mivi_ctx *c) const {
-    const size_t work = state ? natgrad_work_bytes(c) : ngd_work_bytes(c);
+    size_t work = 0, part = 0;
+    switch (alg) {
+      case Algorithm::SqrtNgd: work = ngd_work_bytes(c), part = ngd_part_bytes(c); break;
+      case Algorithm::NatGrad: work = natgrad_work_bytes(c), part = natgrad_part_bytes(c); break;
+      case Algorithm::Wass: work = wass_work_bytes(c), part = wass_part_bytes(c); break;
+    }
     if (!work) return MIVI_OK;   // (the one-workgroup kernels need none)
     const mivi_status_t s = ensure(c, c->ms_work, work, false);
-    return s ? s : ensure(c, c->ms_part, state ? natgrad_part_bytes(c) : ngd_part_bytes(c), false);
+    return s ? s : ensure(c, c->ms_part, part, false);
   }
   mivi_status_t operator()(mivi_ctx *c, void *params, const void *grad, const void *hess, double stepsize, const void *logpi, void *entropy,
                            void *elbo) const {
     const mivi_status_t s = scratch(c);
     if (s) return s;
-    if (state) launch_natgrad_update(c, params, state, grad, hess, stepsize, ensure_posdef, logpi, entropy, elbo);
-    else launch_ngd_update(c, params, grad, hess, stepsize, logpi, entropy, elbo);
+    switch (alg) {
+      case Algorithm::SqrtNgd: launch_ngd_update(c, params, grad, hess, stepsize, logpi, entropy, elbo); break;
+      case Algorithm::NatGrad: launch_natgrad_update(c, params, state, grad, hess, stepsize, ensure_posdef, logpi, entropy, elbo); break;
+      case Algorithm::Wass: launch_wass_update(c, params, state, grad, hess, stepsize, logpi, entropy, elbo); break;
+    }
     HIPCHK(c, hipGetLastError());
     return MIVI_OK;
   }
@@ -88,20 +109,20 @@ static mivi_status_t run_steps(mivi_ctx *c, const char *entry, const char *algor
   return MIVI_OK;
 }
 
-// the _host form of an update: parameters, g and H (and, state_h != nullptr, the state: the natural-gradient update) staged into
-// context-owned buffers, the update, the results back
-static mivi_status_t update_host(mivi_ctx *c, const char *entry, void *params_h, void *state_h, const void *grad_h, const void *hess_h, double stepsize,
-                                 int ensure_posdef, void *entropy_h) {
+// the _host form of an update: parameters, g and H (and the state of an update that carries one) staged into context-owned buffers, the
+// update, the results back
+static mivi_status_t update_host(mivi_ctx *c, const char *entry, Algorithm alg, void *params_h, void *state_h, const void *grad_h, const void *hess_h,
+                                 double stepsize, int ensure_posdef, void *entropy_h) {
   mivi_status_t s;
   if ((s = need_fullrank(c, entry))) return s;
   (void)hipSetDevice(c->cfg.device);
-  const size_t es = c->esize, d = (size_t)c->cfg.d, sb = 2 * d * d * es;
+  const size_t es = c->esize, d = (size_t)c->cfg.d, sb = Update::state_len(c, alg) * es;
   NgdEst e;   // (its scalar: the entropy)
   if ((s = ngd_est(c, &e)) || (state_h && (s = ensure(c, c->natgrad_host, sb, false))) || (s = stage_params(c, params_h))) return s;
   if (state_h) HIPCHK(c, hipMemcpyAsync(c->natgrad_host.p, state_h, sb, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(e.grad, grad_h, d * es, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(e.hess, hess_h, d * d * es, hipMemcpyHostToDevice, c->stream));
-  const Update update{state_h ? c->natgrad_host.p : nullptr, ensure_posdef};
+  const Update update{alg, state_h ? c->natgrad_host.p : nullptr, ensure_posdef};
   if ((s = update(c, c->tmp_params.p, e.grad, e.hess, stepsize, nullptr, e.scalar, nullptr))) return s;
   return fetch_results(c, {{params_h, c->tmp_params.p, (size_t)mivi_params_len(c) * es}, {state_h, c->natgrad_host.p, sb}, {entropy_h, e.scalar, es}}, true);
 }
@@ -290,18 +311,18 @@ mivi_status_t mivi_sqrt_ngd_update(mivi_ctx_t *c, void *params, const void *grad
   const mivi_status_t s = need_fullrank(c, "sqrt_ngd_update");
   if (s) return s;
   (void)hipSetDevice(c->cfg.device);
-  return Update{nullptr, 0}(c, params, grad, hess, stepsize, nullptr, entropy, nullptr);
+  return Update{Algorithm::SqrtNgd, nullptr, 0}(c, params, grad, hess, stepsize, nullptr, entropy, nullptr);
 }
 
 mivi_status_t mivi_sqrt_ngd_update_host(mivi_ctx_t *c, void *params_h, const void *grad_h, const void *hess_h, double stepsize, void *entropy_h) {
   if (!c || !params_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
-  return update_host(c, "sqrt_ngd_update", params_h, nullptr, grad_h, hess_h, stepsize, 0, entropy_h);
+  return update_host(c, "sqrt_ngd_update", Algorithm::SqrtNgd, params_h, nullptr, grad_h, hess_h, stepsize, 0, entropy_h);
 }
 
 mivi_status_t mivi_sqrt_ngd_steps(mivi_ctx_t *c, void *params, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
                                   double stepsize, void *elbo) {
   if (!c || !params || count < 0) return MIVI_ERR_BAD_ARG;
-  return run_steps(c, "sqrt_ngd_steps", "KLMinSqrtNaturalGradDescent", Update{nullptr, 0}, params, idx0, count, n_samples, second_order, stepsize, elbo);
+  return run_steps(c, "sqrt_ngd_steps", "KLMinSqrtNaturalGradDescent", Update{Algorithm::SqrtNgd, nullptr, 0}, params, idx0, count, n_samples, second_order, stepsize, elbo);
 }
 
 mivi_status_t mivi_natgrad_init(mivi_ctx_t *c, const void *params, void *state) {
@@ -309,7 +330,7 @@ mivi_status_t mivi_natgrad_init(mivi_ctx_t *c, const void *params, void *state) 
   mivi_status_t s;
   if ((s = need_fullrank(c, "natgrad_init"))) return s;
   (void)hipSetDevice(c->cfg.device);
-  if ((s = Update{state, 0}.scratch(c))) return s;
+  if ((s = Update{Algorithm::NatGrad, state, 0}.scratch(c))) return s;
   launch_natgrad_init(c, const_cast<void *>(params), state);
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
@@ -321,20 +342,50 @@ mivi_status_t mivi_natgrad_update(mivi_ctx_t *c, void *params, void *state, cons
   const mivi_status_t s = need_fullrank(c, "natgrad_update");
   if (s) return s;
   (void)hipSetDevice(c->cfg.device);
-  return Update{state, ensure_posdef}(c, params, grad, hess, stepsize, nullptr, entropy, nullptr);
+  return Update{Algorithm::NatGrad, state, ensure_posdef}(c, params, grad, hess, stepsize, nullptr, entropy, nullptr);
 }
 
 mivi_status_t mivi_natgrad_update_host(mivi_ctx_t *c, void *params_h, void *state_h, const void *grad_h, const void *hess_h, double stepsize,
                                        int32_t ensure_posdef, void *entropy_h) {
   if (!c || !params_h || !state_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
-  return update_host(c, "natgrad_update", params_h, state_h, grad_h, hess_h, stepsize, ensure_posdef, entropy_h);
+  return update_host(c, "natgrad_update", Algorithm::NatGrad, params_h, state_h, grad_h, hess_h, stepsize, ensure_posdef, entropy_h);
 }
 
 mivi_status_t mivi_natgrad_steps(mivi_ctx_t *c, void *params, void *state, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
                                  double stepsize, int32_t ensure_posdef, void *elbo) {
   if (!c || !params || !state || count < 0) return MIVI_ERR_BAD_ARG;
-  return run_steps(c, "natgrad_steps", "KLMinNaturalGradDescent", Update{state, ensure_posdef}, params, idx0, count, n_samples, second_order, stepsize,
+  return run_steps(c, "natgrad_steps", "KLMinNaturalGradDescent", Update{Algorithm::NatGrad, state, ensure_posdef}, params, idx0, count, n_samples, second_order, stepsize,
                    elbo);
+}
+
+mivi_status_t mivi_wass_init(mivi_ctx_t *c, const void *params, void *state) {
+  if (!c || !params || !state) return MIVI_ERR_BAD_ARG;
+  const mivi_status_t s = need_fullrank(c, "wass_init");
+  if (s) return s;
+  (void)hipSetDevice(c->cfg.device);
+  launch_bam_init(c, params, state);   // Sigma = C C': the state of FisherMinBatchMatch's `init`
+  HIPCHK(c, hipGetLastError());
+  return MIVI_OK;
+}
+
+mivi_status_t mivi_wass_update(mivi_ctx_t *c, void *params, void *state, const void *grad, const void *hess, double stepsize, void *entropy) {
+  if (!c || !params || !state || !grad || !hess) return MIVI_ERR_BAD_ARG;
+  const mivi_status_t s = need_fullrank(c, "wass_update");
+  if (s) return s;
+  (void)hipSetDevice(c->cfg.device);
+  return Update{Algorithm::Wass, state, 0}(c, params, grad, hess, stepsize, nullptr, entropy, nullptr);
+}
+
+mivi_status_t mivi_wass_update_host(mivi_ctx_t *c, void *params_h, void *state_h, const void *grad_h, const void *hess_h, double stepsize,
+                                    void *entropy_h) {
+  if (!c || !params_h || !state_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
+  return update_host(c, "wass_update", Algorithm::Wass, params_h, state_h, grad_h, hess_h, stepsize, 0, entropy_h);
+}
+
+mivi_status_t mivi_wass_steps(mivi_ctx_t *c, void *params, void *state, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
+                              double stepsize, void *elbo) {
+  if (!c || !params || !state || count < 0) return MIVI_ERR_BAD_ARG;
+  return run_steps(c, "wass_steps", "KLMinWassFwdBwd", Update{Algorithm::Wass, state, 0}, params, idx0, count, n_samples, second_order, stepsize, elbo);
 }
 
 }  // extern "C"

@@ -22,7 +22,8 @@
 //     factor  kernels_natgrad.hip's blocked factorisation A = Lr' Lr (2 nT - 1 launches).  It runs from the bottom-right corner, so on the
 //             reversed matrix it IS the lower Cholesky factorisation: C'_pq = Lr_(d-1-q)(d-1-p).  A pivot that is not a positive finite number
 //             sets MIVI_ERR_NONPOSITIVE_SCALE's flag and is replaced by 1 there.
-//     fin     C' into the parameter vector (exact zeros above the diagonal); entropy(q') and the flags (ngd_finish)
+//     fin     kernels_natgrad.hip's finish of a reversed factor: C' into the parameter vector (exact zeros above the diagonal); entropy(q')
+//             and the flags (ngd_finish)
 // 2 nT + 6 launches: 8 for d <= 64, 38 at d = 1024.  No floating-point atomics, one summation order: bitwise repeatable.  u and G are read-only.
 // The moments: one launch of 64 x 64 tiles of C' G (float64, ngd_tile.h) whose epilogue adds u, squares and leaves one partial per tile, and
 // a one-workgroup finish (fisher, logpi_avg, elbo = logpi_avg + entropy(q), the flags); init: the lower tiles of C C', mirrored.
@@ -314,26 +315,6 @@ __global__ __launch_bounds__(256) void k_bam_mean(BamArgs<TI> a) {
       [&](int i, double tot) { a.params[i] = (TI)((double)a.params[i] / (1.0 + a.lambda) + w * (tot + a.zbar[i])); });
 }
 
-// ---- fin: C' from the factor of the reversed matrix; entropy(q') and the flags ------------------------------------------------------------------------------
-template <typename TI>
-__global__ __launch_bounds__(256) void k_bam_fin(BamArgs<TI> a) {
-  const int d = a.d, nT = a.nT, ldp = a.ldp;
-  const int i0 = ((int)blockIdx.x % nT) * kNgdTile, j0 = ((int)blockIdx.x / nT) * kNgdTile;
-  for (int t = threadIdx.x; t < kNgdTile * kNgdTile; t += 256) {
-    const int p = i0 + (t & 63), q = j0 + (t >> 6);
-    if (p >= d || q >= d) continue;
-    a.params[d + (size_t)q * d + p] = p >= q ? (TI)a.A[(size_t)(d - 1 - p) * ldp + (d - 1 - q)] : TI(0);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    double tot = 0.0, bad = 0.0;
-    for (int p = 0; p < nT; ++p) {
-      tot += a.part[p];   // sum log 1 / Lr_ii
-      bad += a.part[nT + p];
-    }
-    ngd_finish(d, -tot, bad > 0.0 ? 1 : 0, a.out);
-  }
-}
-
 // ---- init: Sigma = C C', the lower tiles, mirrored -------------------------------------------------------------------------------------------------------------
 template <typename TI>
 __global__ __launch_bounds__(256) void k_bam_init(int d, const TI *C, TI *Sigma) {
@@ -482,7 +463,7 @@ static void bam_update_t(mivi_ctx *c, void *params, void *state, const void *u, 
   hipLaunchKernelGGL((k_bam_sigma<TI>), dim3(g.n_tiles), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL((k_bam_mean<TI>), dim3(g.nT), dim3(256), 0, c->stream, a);
   launch_natgrad_factor(c, a.d, a.A, a.Dinv, a.part);
-  hipLaunchKernelGGL((k_bam_fin<TI>), dim3(g.nT * g.nT), dim3(256), 0, c->stream, a);
+  launch_natgrad_factor_fin(c, a.A, a.part, params, nullptr, entropy, nullptr);
 }
 
 void launch_bam_update(mivi_ctx *c, void *params, void *state, const void *u, size_t ldu, const void *G, int B, double lambda, void *entropy) {

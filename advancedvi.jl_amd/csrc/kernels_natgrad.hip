@@ -588,6 +588,37 @@ void launch_natgrad_factor(mivi_ctx *c, int d, double *A, double *Dinv, double *
   }
 }
 
+// The finish of an update that factored the index-REVERSED Sigma' (kernels_bam.hip, kernels_wass.hip): run from the bottom-right corner on the
+// reversed matrix the factorisation IS the lower Cholesky factorisation, C'_pq = Lr_(d-1-q)(d-1-p).  C' into the parameter vector (exact zeros
+// above the diagonal); the first workgroup adds the panels' partials in order: entropy(q'), elbo and the flags (ngd_finish).
+template <typename TI>
+__global__ __launch_bounds__(256) void k_natgrad_factor_fin(int d, int nT, int ldp, const double *A, const double *part, TI *params, NgdOut<TI> out) {
+  const int i0 = ((int)blockIdx.x % nT) * kNgdTile, j0 = ((int)blockIdx.x / nT) * kNgdTile;
+  for (int t = threadIdx.x; t < kNgdTile * kNgdTile; t += 256) {
+    const int p = i0 + (t & 63), q = j0 + (t >> 6);
+    if (p >= d || q >= d) continue;
+    params[d + (size_t)q * d + p] = p >= q ? (TI)A[(size_t)(d - 1 - p) * ldp + (d - 1 - q)] : TI(0);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    double tot = 0.0, bad = 0.0;
+    for (int p = 0; p < nT; ++p) {
+      tot += part[p];   // sum log 1 / Lr_ii
+      bad += part[nT + p];
+    }
+    ngd_finish(d, -tot, bad > 0.0 ? 1 : 0, out);
+  }
+}
+
+void launch_natgrad_factor_fin(mivi_ctx *c, const double *A, const double *part, void *params, const void *logpi, void *entropy, void *elbo) {
+  const int d = c->cfg.d;
+  const NgdGeom g(d);
+  by_dtype(c, [&](auto t) {
+    using TI = decltype(t);
+    hipLaunchKernelGGL((k_natgrad_factor_fin<TI>), dim3(g.nT * g.nT), dim3(256), 0, c->stream, d, g.nT, g.ldp, A, part, (TI *)params,
+                       NgdOut<TI>{(const TI *)logpi, (TI *)entropy, (TI *)elbo, (int *)c->status.p});
+  });
+}
+
 size_t natgrad_work_bytes(const mivi_ctx *c) {
   const NgdGeom g(c->cfg.d);   // (float64 scratch whatever the context's type)
   return c->cfg.d <= kNatgradSmallD ? 0 : (5 * g.mat() + (size_t)g.nT * kNgdTile * kNgdTile) * sizeof(double);

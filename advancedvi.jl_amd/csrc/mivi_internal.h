@@ -425,7 +425,7 @@ struct mivi_ctx {
   int sg_cap = 0;                  // samples sg_d is sized for
   mivi::DevBuf ms_work, ms_part;   // the measure-space updates' one scratch pair, ensured by each update to its own need and holding nothing between calls.  Square-root NGD (kernels_ngd.hip): [Cc; G; T; v] padded to whole tiles | the diagonal tiles' f64 partials + the ticket.  Natural gradient (kernels_natgrad.hip): f64 [Gh; Sigma; W; A; X] padded to whole tiles + the inverted diagonal tiles | the panels' f64 log sums and bad-pivot counts + the mean's four vectors.  Batch and match (kernels_bam.hip): f64 [A; Dinv; Q, Ut, Zt, SQ, Y; M, E1, ME; gbar, ubar, zbar] | the objective's tile partials, then the panels' pairs
   mivi::DevBuf bam_host;   // api_measure.hip: [Sigma (d x d); u (d x n); G (d x n); fisher, logpi_avg, elbo / entropy (16 bytes each)] of the batch-and-match _host entries
-  mivi::DevBuf ngd_est, natgrad_host;   // api_measure.hip: [logpi_avg or entropy (16 bytes); grad (d); hess (d x d)] of the _steps loops and the _host updates; [S; Sigma] of mivi_natgrad_update_host
+  mivi::DevBuf ngd_est, natgrad_host;   // api_measure.hip: [logpi_avg or entropy (16 bytes); grad (d); hess (d x d)] of the _steps loops and the _host updates; [S; Sigma] of mivi_natgrad_update_host / Sigma of mivi_wass_update_host
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
   const uint64_t *idx_src = nullptr;   // mivi_set_index_source
@@ -598,6 +598,8 @@ size_t natgrad_part_bytes(const mivi_ctx *c);   // of c->ms_part
 void launch_natgrad_init(mivi_ctx *c, void *params, void *state);
 // its blocked factorisation alone, on a caller's padded float64 work matrix: A = Lr' Lr, Lr (diagonal tiles included) in A's lower triangle
 void launch_natgrad_factor(mivi_ctx *c, int d, double *A, double *Dinv, double *part);
+// ... and the finish of an update that factored the index-reversed Sigma': C' into params, entropy(q') / elbo / flags from `part`
+void launch_natgrad_factor_fin(mivi_ctx *c, const double *A, const double *part, void *params, const void *logpi, void *entropy, void *elbo);
 // kernels_bam.hip: FisherMinBatchMatch (fisherminbatchmatch.jl) -- Sigma of `init` (:76), the objective (:81-111) and the update (:143-155)
 size_t bam_work_bytes(const mivi_ctx *c);   // of c->ms_work (the update)
 size_t bam_part_bytes(const mivi_ctx *c);   // of c->ms_part (the update)
@@ -609,6 +611,11 @@ void launch_bam_objective(mivi_ctx *c, const void *params, const double *part, i
 void launch_bam_update(mivi_ctx *c, void *params, void *state, const void *u, size_t ldu, const void *G, int B, double lambda, void *entropy);
 void launch_natgrad_update(mivi_ctx *c, void *params, void *state, const void *grad, const void *hess, double eta, int ensure_posdef, const void *logpi,
                            void *entropy, void *elbo);
+// kernels_wass.hip: KLMinWassFwdBwd's update (klminwassfwdbwd.jl:105-114) on [m; vec C] and Sigma in place (its `init` state is launch_bam_init's)
+size_t wass_work_bytes(const mivi_ctx *c);   // of c->ms_work
+size_t wass_part_bytes(const mivi_ctx *c);   // of c->ms_part
+void launch_wass_update(mivi_ctx *c, void *params, void *state, const void *grad, const void *hess, double eta, const void *logpi, void *entropy,
+                        void *elbo);
 
 // kernels_p2p.hip: phases bit 0 push, 1 reduce + finalise, 2 unpack (7 = the whole exchange in one launch)
 void launch_p2p_handover4(mivi_ctx *c, unsigned *ready, unsigned ready_val, const unsigned *const *freed, const unsigned *freed_min, int n);

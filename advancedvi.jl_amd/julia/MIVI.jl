@@ -618,6 +618,36 @@ function bam_steps!(state::MIVIState, params_dev::Ptr{Cvoid}, sigma_dev::Ptr{Cvo
     return state
 end
 
+# KLMinWassFwdBwd (src/algorithms/klminwassfwdbwd.jl): the proximal update of `step` (:105-114) on `params = first(Optimisers.destructure(q))`
+# and `sigma` (:49) in place from the buffers gaussian_expectation_gradient_and_hessian! filled, entropy(q') (the term of :114) returned;
+# on device pointers: sigma_dev <- cov(q_init) (:75), the update, and whole iterations {estimator, update} without a host round trip
+# (mivi_wass_steps: elbo_dev T[count] or C_NULL; second_order as the reference's capability test).
+function wass_update!(state::MIVIState, params::Vector{T}, sigma::Matrix{T}, grad_buf::Vector{T}, hess_buf::Matrix{T}, stepsize::Real) where {T<:Real}
+    entropy = Ref{T}(zero(T))
+    check(state.ctx, ccall((:mivi_wass_update_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Float64, Ref{T}),
+                           state.ctx, params, sigma, grad_buf, hess_buf, Float64(stepsize), entropy))
+    return params, sigma, entropy[]
+end
+function wass_init_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, sigma_dev::Ptr{Cvoid})
+    check(state.ctx, ccall((:mivi_wass_init, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), state.ctx, params_dev, sigma_dev))
+    return state
+end
+function wass_update_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, sigma_dev::Ptr{Cvoid}, grad_dev::Ptr{Cvoid}, hess_dev::Ptr{Cvoid},
+                          stepsize::Real, entropy_dev::Ptr{Cvoid}=C_NULL)
+    check(state.ctx, ccall((:mivi_wass_update, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}),
+                           state.ctx, params_dev, sigma_dev, grad_dev, hess_dev, Float64(stepsize), entropy_dev))
+    return state
+end
+function wass_steps!(state::MIVIState, params_dev::Ptr{Cvoid}, sigma_dev::Ptr{Cvoid}, count::Integer, n_samples::Integer, second_order::Bool,
+                     stepsize::Real, elbo_dev::Ptr{Cvoid}=C_NULL)
+    check(state.ctx, ccall((:mivi_wass_steps, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Int32, Int32, Int32, Float64, Ptr{Cvoid}),
+                           state.ctx, params_dev, sigma_dev, state.estimate_idx, Int32(count), Int32(n_samples), Int32(second_order), Float64(stepsize),
+                           elbo_dev))
+    state.estimate_idx += count
+    check(state.ctx, ccall((:mivi_synchronize, libmivi), Int32, (Ptr{Cvoid},), state.ctx))
+    return state
+end
+
 # Constrained supports (README.md:76-82, 91-119; docs/src/tutorials/constrained.md:154-196): a Bijectors.Stacked of identity / exp
 # blocks is applied by the library around whatever target is set.  `ranges` are the Stacked's UnitRanges (1-based, as Bijectors
 # stores them), `kinds[i]` is :identity or :exp.  An empty list removes the constraint.
@@ -682,5 +712,5 @@ end
 # ProximalLocationScaleEntropy on the host arrays works unchanged (src/optimization/proximal_location_scale_entropy.jl);
 # the device-resident variant for a parameter vector that lives in HBM is mivi_prox_scale_entropy.
 
-export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!, bam_moments!, estimate_fisher, bam_update!, bam_init_dev!, bam_moments_dev!, estimate_fisher_dev!, bam_update_dev!, bam_steps!
+export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!, bam_moments!, estimate_fisher, bam_update!, bam_init_dev!, bam_moments_dev!, estimate_fisher_dev!, bam_update_dev!, bam_steps!, wass_update!, wass_init_dev!, wass_update_dev!, wass_steps!
 end # module

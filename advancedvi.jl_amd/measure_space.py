@@ -1,5 +1,5 @@
-"""Measure-space algorithms: KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent and FisherMinBatchMatch, the host-side mirrors of
-src/algorithms/klminsqrtnaturalgraddescent.jl, src/algorithms/klminnaturalgraddescent.jl and src/algorithms/fisherminbatchmatch.jl
+"""Measure-space algorithms: KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent, FisherMinBatchMatch and KLMinWassFwdBwd, the host-side
+mirrors of src/algorithms/klminsqrtnaturalgraddescent.jl, klminnaturalgraddescent.jl, fisherminbatchmatch.jl and klminwassfwdbwd.jl
 (AdvancedVI.jl v0.7.0) over libmivi.
 
     KLMinSqrtNaturalGradDescent(stepsize, n_samples=1, subsampling=None)     :39-44
@@ -26,7 +26,12 @@ mivi_bam_moments followed by mivi_bam_update (whole chunks inside mivi_bam_steps
 new scale is the lower Cholesky factor of Sigma', as in the reference.  `info` carries `covweighted_fisher` and `elbo`, both at the iterate
 the step STARTED from (:157-158).  The callback is called as the reference's CODE calls it (:163) -- callback(rng=, iteration=, q=, state=)
 with q the iterate the step started from and the new state -- which disagrees with the reference's docstring for `optimize` (q the new
-iterate, `info` instead of `state`); the code is what users' callbacks run against."""
+iterate, `info` instead of `state`); the code is what users' callbacks run against.
+
+KLMinWassFwdBwd(stepsize, n_samples=1, subsampling=None) (klminwassfwdbwd.jl:39-44; init :56-76, step :80-122, output :78,
+estimate_objective :141-160) is stochastic proximal gradient descent in Wasserstein space: the loop of the two natural-gradient algorithms
+around mivi_wass_update / mivi_wass_steps; its state carries the device buffer Sigma (:75, mivi_wass_init).  Its new scale is the lower
+Cholesky factor of Sigma', as in the reference, and its callback receives the new iterate and `info` (:118)."""
 from __future__ import annotations
 
 from . import objectives as O
@@ -92,8 +97,25 @@ class FisherMinBatchMatch:
         return f"FisherMinBatchMatch(n_samples={self.n_samples}, subsampling={self.subsampling})"
 
 
-ALGORITHMS = (KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent, FisherMinBatchMatch)
-STATE_BUFFERS = ("natgrad", "bam")   # the device buffers, besides the parameters, that a step advances in place
+class KLMinWassFwdBwd:
+    """KL minimisation by stochastic proximal gradient descent (forward-backward splitting) in Wasserstein space (klminwassfwdbwd.jl:2-44).
+    Needs a full-rank Gaussian family and a target with at least first-order capability; a target with second-order capability has its
+    Hessians used, otherwise the Stein identity on gradients."""
+
+    def __init__(self, stepsize, n_samples: int = 1, subsampling=None, device: int = 0):
+        if not isinstance(n_samples, int) or n_samples < 1:
+            raise ValueError("n_samples must be a positive Int")
+        self.stepsize = float(stepsize)
+        self.n_samples = int(n_samples)
+        self.subsampling = subsampling
+        self.device = int(device)
+
+    def __repr__(self):
+        return f"KLMinWassFwdBwd(stepsize={self.stepsize}, n_samples={self.n_samples}, subsampling={self.subsampling})"
+
+
+ALGORITHMS = (KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent, FisherMinBatchMatch, KLMinWassFwdBwd)
+STATE_BUFFERS = ("natgrad", "bam", "wass")   # the device buffers, besides the parameters, that a step advances in place
 
 
 def _second_order(prob) -> bool:
@@ -105,6 +127,8 @@ def _update(alg, ctx, state, grad, hess):
     """The algorithm's update of state["params"] (and of its own state buffer) in place; returns entropy(q') as a 1-element device tensor."""
     if isinstance(alg, KLMinNaturalGradDescent):
         return ctx.natgrad_update(state["params"], state["natgrad"], grad, hess, alg.stepsize, alg.ensure_posdef)
+    if isinstance(alg, KLMinWassFwdBwd):
+        return ctx.wass_update(state["params"], state["wass"], grad, hess, alg.stepsize)
     return ctx.sqrt_ngd_update(state["params"], grad, hess, alg.stepsize)
 
 
@@ -116,6 +140,8 @@ def _device_steps(alg, ctx, state, idx0, n, second):
     if isinstance(alg, KLMinNaturalGradDescent):
         return ctx.natgrad_steps(state["params"], state["natgrad"], idx0, n, alg.stepsize, alg.ensure_posdef, n_samples=alg.n_samples,
                                  second_order=second)
+    if isinstance(alg, KLMinWassFwdBwd):
+        return ctx.wass_steps(state["params"], state["wass"], idx0, n, alg.stepsize, n_samples=alg.n_samples, second_order=second)
     return ctx.sqrt_ngd_steps(state["params"], idx0, n, alg.stepsize, n_samples=alg.n_samples, second_order=second)
 
 
@@ -129,7 +155,7 @@ def _own_buffers(state):
 
 
 def init(rng, alg, q_init, prob):
-    """klminsqrtnaturalgraddescent.jl:55-75 / klminnaturalgraddescent.jl:64-91 / fisherminbatchmatch.jl:56-77."""
+    """klminsqrtnaturalgraddescent.jl:55-75 / klminnaturalgraddescent.jl:64-91 / fisherminbatchmatch.jl:56-77 / klminwassfwdbwd.jl:56-76."""
     name = type(alg).__name__
     if not isinstance(q_init, MvLocationScale) or q_init.family != FULLRANK:
         raise TypeError(f"`{name}` expects a Gaussian with a lower-triangular scale (FullRankGaussian) as q_init")
@@ -149,6 +175,8 @@ def init(rng, alg, q_init, prob):
     state.update(grad_buf=ctx.empty(d), hess_buf=ctx.empty(d * d))
     if isinstance(alg, KLMinNaturalGradDescent):   # :83-87: prec and qcov, carried from step to step
         state["natgrad"] = ctx.natgrad_init(state["params"])
+    if isinstance(alg, KLMinWassFwdBwd):           # klminwassfwdbwd.jl:75: cov(q_init), carried from step to step
+        state["wass"] = ctx.wass_init(state["params"])
     return state
 
 

@@ -207,8 +207,8 @@ PARAM_SPACE_SGD = (KLMinRepGradDescent, KLMinScoreGradDescent)   # the ParamSpac
 
 
 def _measure_space(*heads):
-    """The measure_space module when one of `heads` is a measure-space algorithm (KLMinSqrtNaturalGradDescent,
-    KLMinNaturalGradDescent: they have a loop of their own, no objective / optimiser / averager), else None."""
+    """The measure_space module when one of `heads` is a measure-space algorithm (measure_space.ALGORITHMS: they have a loop of their
+    own, no objective / optimiser / averager), else None."""
     from . import measure_space as M
     return M if any(isinstance(h, M.ALGORITHMS) for h in heads) else None
 

@@ -359,6 +359,41 @@ mivi_status_t mivi_bam_update_host(mivi_ctx_t *ctx, void *params_host, void *sta
 mivi_status_t mivi_bam_steps(mivi_ctx_t *ctx, void *params_dev, void *state_dev, uint64_t estimate_idx0, uint64_t iteration0, int32_t count,
                              int32_t n_samples, void *fisher_dev, void *elbo_dev);
 
+/* KLMinWassFwdBwd (stochastic proximal gradient descent in Wasserstein space, src/algorithms/klminwassfwdbwd.jl).  Besides [m; vec(C)] it
+ * carries state_dev T[d*d] = Sigma, the covariance (`sigma`, :49), d x d column-major, a full symmetric matrix with bitwise-mirrored
+ * triangles, carried from step to step.
+ *   mivi_wass_init (:75): state_dev <- C C' (the launch of mivi_bam_init); params_dev is only read.
+ *   mivi_wass_update (:105-114), params and state IN PLACE, grad (T[d]) and hess (T[d*d], column-major) read-only and hess used as it comes
+ *   (not symmetric on the Stein branch; note the transpose), eta = stepsize converted to T (:88):
+ *       m' = m + eta grad        M = I + eta hess'        Sh = Hermitian(M Sigma M')                                     (:105-107)
+ *       Sigma' = (Sh + 2 eta I + sqrt(Hermitian(Sh (Sh + 4 eta I)))) / 2        C' = cholesky(Sigma').L                   (:110-111)
+ *       entropy_dev T[1] <- entropy(q') = d/2 (1 + log 2 pi) + sum_i log C'_ii (the term of :114); may be NULL
+ *     Hermitian(.) is the reference's: the UPPER triangle of the operand, mirrored.  C' is lower triangular with exact zeros above the
+ *     diagonal: the reference's own scale, no deviation.  The symmetric square root is not an eigendecomposition but the coupled
+ *     Newton-Schulz iteration on the matrix cores (csrc/kernels_wass.hip): A = Hermitian(Sh (Sh + 4 eta I)),
+ *     c = |A|_F, Y_0 = A / c, Z_0 = I, E_k = I - Z_k Y_k, Y_k+1 = Y_k + Y_k E_k / 2, Z_k+1 = Z_k + E_k Z_k / 2, sqrt(A) = sqrt(c) (Y + Y')/2,
+ *     stopped on the device at the first round with |E_k|_F <= 64 d eps or, from the fifth round on, with |E_k|_F no longer halving below
+ *     1e-6 or growing; at most MIVI_WASS_MAX_ROUNDS rounds.  Float64 arithmetic for either context type.
+ *     2 nT + 2 MIVI_WASS_MAX_ROUNDS + 5 launches, nT = ceil(d / 64) (the rounds after the stop return at once), the last 2 nT of them the
+ *     blocked factorisation of mivi_natgrad_update and its finish.  Bitwise repeatable (no floating-point atomics, one summation order).
+ *     A pivot that is not a positive finite number sets the sticky flag of MIVI_ERR_NONPOSITIVE_SCALE and is replaced by 1; an iteration
+ *     that does not stop within the bound, a non-finite |E_k|_F (a NaN in grad or hess) or a non-finite entropy sets that of
+ *     MIVI_ERR_NONFINITE; the call returns and the contents of params and state are then unspecified.  The _host form (host buffers,
+ *     synchronous) returns the status itself.  Any d >= 1.  MIVI_ERR_UNSUPPORTED: a mean-field context.
+ *   mivi_wass_steps (step, :80-122, without subsampling and callback): `count` whole iterations with no host round trip: iteration t
+ *     estimates with index estimate_idx0 + t (:101; second_order as for mivi_sqrt_ngd_steps), then updates; elbo_dev T[count] (or NULL) <-
+ *     logpi_avg_t + entropy(q'_t) (:114).  The same launches and arithmetic as `count` calls of the estimator entry followed by
+ *     mivi_wass_update: bitwise equal to them.  Refusals as for mivi_natgrad_steps (a mean-field context, a sharded context, no target, what
+ *     the chosen estimator entry refuses); a refused call launches nothing. */
+#define MIVI_WASS_MAX_ROUNDS 64
+mivi_status_t mivi_wass_init(mivi_ctx_t *ctx, const void *params_dev, void *state_dev);
+mivi_status_t mivi_wass_update(mivi_ctx_t *ctx, void *params_dev, void *state_dev, const void *grad_dev, const void *hess_dev, double stepsize,
+                               void *entropy_dev);
+mivi_status_t mivi_wass_update_host(mivi_ctx_t *ctx, void *params_host, void *state_host, const void *grad_host, const void *hess_host,
+                                    double stepsize, void *entropy_host);
+mivi_status_t mivi_wass_steps(mivi_ctx_t *ctx, void *params_dev, void *state_dev, uint64_t estimate_idx0, int32_t count, int32_t n_samples,
+                              int32_t second_order, double stepsize, void *elbo_dev);
+
 /* ---- multi-GPU: shard the MC batch, all-reduce the partials, finalize -------------------------- *
  * No counterpart in the reference (single task).  partials_dev: T[partials_len] un-normalised sums over
  * this context's samples; the caller all-reduces (RCCL sum) and calls mivi_finalize on every rank. */
