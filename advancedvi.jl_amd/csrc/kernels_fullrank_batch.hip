@@ -106,56 +106,53 @@ struct FbArgs {
 #endif
 
 // -----------------------------------------------------------------------------------------------------------------
-// A parameter-only A operand as operand planes: ONE workgroup (512 threads) per 32-row block rb -- the rows' largest magnitudes over the
-// k range the products read (fragments kg_lo .. kg_hi) -> one power-of-two scale per row (scale[row], scale[d + row] = its inverse) ->
-// the block's fragments, one wave per fragment.  ld(k, row) returns the (masked) f32 element.  red: 16 * 32 + 32 floats of LDS.
+// A parameter-only A operand as operand planes: workgroups of NT threads per 32-row block rb (nsub of them, sub = which) -- the rows' largest
+// magnitudes over the k range the products read (fragments kg_lo .. kg_hi) -> one power-of-two scale per row (scale[row], scale[d + row] =
+// its inverse) -> the block's fragments, one wave per fragment.  ld(k, row) returns the (masked) f32 element.  red: NT / 2 floats of LDS.
+// The planes and scales do not depend on NT or nsub: a maximum is exact in any order, a fragment element is scaled and split on its own.
 // -----------------------------------------------------------------------------------------------------------------
-template <class Ld4, class Ld>
+template <int NT, class Ld4, class Ld>
 __device__ __forceinline__ void fb_rowblock_planes(int d, int rb, int kg_lo, int kg_hi, int sub, int nsub, Ld4 ld4, Ld ld, unsigned *planes, float *scale, float *red) {
-  // row maxima: a thread takes 4 rows x one k per 16-byte load (rows are the contiguous axis), 64 k parts, eight loads in flight
+  // row maxima: a thread takes 4 rows x one k per 16-byte load (rows are the contiguous axis), NT / 8 k parts, eight loads in flight
+  constexpr int NP = NT / 8, NW = NT / 64;
   const int tid = threadIdx.x, r4 = tid & 7, part = tid >> 3, ng = d >> 4;
   f32x4 m = {0.f, 0.f, 0.f, 0.f};
   {
     int k = 16 * kg_lo + part;
-    for (; k + 448 <= 16 * kg_hi + 15; k += 512) {
+    for (; k + 7 * NP <= 16 * kg_hi + 15; k += 8 * NP) {
       f32x4 v[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = ld4(k + 64 * u, 32 * rb + 4 * r4);
+      for (int u = 0; u < 8; ++u) v[u] = ld4(k + NP * u, 32 * rb + 4 * r4);
 #pragma unroll
       for (int u = 0; u < 8; ++u)
 #pragma unroll
         for (int c = 0; c < 4; ++c) m[c] = fmaxf(m[c], fabsf(v[u][c]));
     }
-    for (; k <= 16 * kg_hi + 15; k += 64) {
+    for (; k <= 16 * kg_hi + 15; k += NP) {
       const f32x4 v = ld4(k, 32 * rb + 4 * r4);
 #pragma unroll
       for (int c = 0; c < 4; ++c) m[c] = fmaxf(m[c], fabsf(v[c]));
     }
   }
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {   // lanes 8 apart hold the same rows: the wave's eight parts, then the eight waves through LDS
+  for (int c = 0; c < 4; ++c) {   // lanes 8 apart hold the same rows: the wave's eight parts, then the waves through LDS
     m[c] = fmaxf(m[c], __shfl_xor(m[c], 8, 64));
     m[c] = fmaxf(m[c], __shfl_xor(m[c], 16, 64));
     m[c] = fmaxf(m[c], __shfl_xor(m[c], 32, 64));
   }
   if ((tid & 63) < 8) *(f32x4 *)(red + (tid >> 6) * 32 + 4 * r4) = m;
   lds_barrier();
-  if (tid < 32) {
-    float mm = red[tid];
-#pragma unroll
-    for (int p = 1; p < 8; ++p) mm = fmaxf(mm, red[p * 32 + tid]);
-    float s, inv;
-    fb_scale_of(mm, s, inv);
-    red[512 + tid] = s;
-    if (sub == 0) {
-      scale[32 * rb + tid] = s;
-      scale[d + 32 * rb + tid] = inv;
-    }
-  }
-  lds_barrier();
   const int w = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-  const float s = red[512 + l31];
-  for (int kg = kg_lo + w + 8 * sub; kg <= kg_hi; kg += 8 * nsub) {
+  float mm = red[l31];   // (every thread forms the scale of its fragment row itself: no second barrier, no scale area in LDS)
+#pragma unroll
+  for (int p = 1; p < NW; ++p) mm = fmaxf(mm, red[p * 32 + l31]);
+  float s, inv;
+  fb_scale_of(mm, s, inv);
+  if (sub == 0 && tid < 32) {
+    scale[32 * rb + tid] = s;
+    scale[d + 32 * rb + tid] = inv;
+  }
+  for (int kg = kg_lo + w + NW * sub; kg <= kg_hi; kg += NW * nsub) {
     float x[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) x[e] = ld(16 * kg + 8 * (e >> 2) + 4 * h + (e & 3), 32 * rb + l31) * s;
@@ -164,12 +161,13 @@ __device__ __forceinline__ void fb_rowblock_planes(int d, int rb, int kg_lo, int
 }
 // tril(C): the fragments up to the diagonal block + the two zero groups behind it (a wave of k_fb_prod walks the K range of its SECOND row
 // block with both of its blocks: the first one's chain adds exact zeros there)
+template <int NT>
 __device__ __forceinline__ void fb_cplanes_block(const FbArgs &a, int rb, int sub, int nsub, float *red) {
   const int d = a.d, ng = d >> 4, dT = a.dT;
   const float *C = a.params + dT;   // (leading dimension dT; rows / columns beyond dT are padding: zeros)
   const int hi = 2 * rb + 3 < ng - 1 ? 2 * rb + 3 : ng - 1;
   if (dT == d) {   // whole tiles (the common case, and every benchmark shape): no padding masks in the row-maximum loops
-    fb_rowblock_planes(d, rb, 0, hi, sub, nsub,
+    fb_rowblock_planes<NT>(d, rb, 0, hi, sub, nsub,
                        [C, d](int k, int row) { f32x4 v = *(const f32x4 *)(C + (size_t)k * d + row);
 #pragma unroll
                                                 for (int c = 0; c < 4; ++c) v[c] = k > row + c ? 0.f : v[c];
@@ -177,7 +175,7 @@ __device__ __forceinline__ void fb_cplanes_block(const FbArgs &a, int rb, int su
                        [C, d](int k, int row) { const float v = C[(size_t)k * d + row]; return k > row ? 0.f : v; }, a.CA, a.cscale, red);
     return;
   }
-  fb_rowblock_planes(d, rb, 0, hi, sub, nsub,
+  fb_rowblock_planes<NT>(d, rb, 0, hi, sub, nsub,
                      [C, dT](int k, int row) { const bool in = row < dT && k < dT;   // (dT % 4 == 0: a vector is inside or outside; outside: any valid address, masked)
                                                f32x4 v = *(const f32x4 *)(C + (size_t)(in ? k : 0) * dT + (in ? row : 0));
 #pragma unroll
@@ -187,20 +185,20 @@ __device__ __forceinline__ void fb_cplanes_block(const FbArgs &a, int rb, int su
 }
 // k_fb_pplanes: the dense-Gaussian target's precision matrix P (every k group: P is full).  Once per target.
 __global__ __launch_bounds__(512) void k_fb_pplanes(FbArgs a) {
-  __shared__ float red[16 * 32 + 32];
+  __shared__ float red[8 * 32];
   const float *P = a.t_prec;
   const int dP = a.dP;
-  fb_rowblock_planes(a.d, (int)blockIdx.x, 0, (a.d >> 4) - 1, (int)blockIdx.y, (int)gridDim.y,
+  fb_rowblock_planes<512>(a.d, (int)blockIdx.x, 0, (a.d >> 4) - 1, (int)blockIdx.y, (int)gridDim.y,
                      [P, dP](int k, int row) { return *(const f32x4 *)(P + (size_t)k * dP + row); },
                      [P, dP](int k, int row) { return P[(size_t)k * dP + row]; }, a.PA, a.pscale, red);
 }
 // k_fb_tplanes: C^-T (upper triangular) -- entries below the diagonal are exact zeros whatever the solve left there; a 128-row tile of
 // k_fb_prod<FB_STL_U> starts its K range at its FIRST row block's diagonal, so a row block's fragments start there.  Once per call.
 __global__ __launch_bounds__(512) void k_fb_tplanes(FbArgs a) {
-  __shared__ float red[16 * 32 + 32];
+  __shared__ float red[8 * 32];
   const float *T = a.Tinv;
   const int d = a.d, rb = (int)blockIdx.x;
-  fb_rowblock_planes(d, rb, 2 * (rb & ~3), (d >> 4) - 1, (int)blockIdx.y, (int)gridDim.y,
+  fb_rowblock_planes<512>(d, rb, 2 * (rb & ~3), (d >> 4) - 1, (int)blockIdx.y, (int)gridDim.y,
                      [T, d](int k, int row) { f32x4 v = *(const f32x4 *)(T + (size_t)k * d + row);
 #pragma unroll
                                               for (int c = 0; c < 4; ++c) v[c] = k >= row + c ? v[c] : 0.f;
@@ -209,46 +207,56 @@ __global__ __launch_bounds__(512) void k_fb_tplanes(FbArgs a) {
 }
 
 // -----------------------------------------------------------------------------------------------------------------
-// k_fb_eps: eps of L estimates as operand planes (of 2^11 eps).  Draws: blocks of 64 rows x 32 columns, one Philox block
-// per thread (rows 4 q .. 4 q + 3 of one column: the stream and the he_part partials of the single calls' k_eps); the block's values go
-// through an LDS tile, threads 0..255 then assemble the four product fragments (column = row of the B operand, k = rows 16 ig ..).
-// The kernel is bound by the generator's vector arithmetic (Philox's 32-bit multiplies + Box-Muller), not by its plane writes: halving the
-// writes (round 6) took 7 % off it.  blockIdx.y - n_riders = lane; the first n_riders grid rows
-// (a call's first draw only) lay out tril(C): one workgroup per 32-row block, the heaviest first.
+// k_fb_eps: eps of L estimates as operand planes (of 2^11 eps).  Four waves draw one block of 64 rows x 32 columns: 512 Philox blocks,
+// four consecutive rows of one column each (the stream of the single calls' k_eps).  Wave f lays down the block's fragment
+// (mb32 = c32, kg = 4 R64 + f); its lane (column l31, half h) holds rows 16 f + 4 h + {0..3} and 16 f + 8 + 4 h + {0..3} of the column, i.e.
+// exactly the column's Philox blocks 4 f + h and 4 f + 2 + h: the thread draws those two and owns its eight slots -- no LDS tile, no
+// barrier in front of the plane stores, every wave stores (tests/test_eps_direct_layout.py restates the map; before, the threads drew one
+// block each the other way round and transposed the 64 x 32 block through an 8 KiB tile, half the waves gone before the stores: 22 us per 50
+// lanes, now 16-18).  A workgroup is two such blocks (waves 0-3, waves 4-7), so that the riders keep their 512 threads.  k_fb_vjp takes its B
+// operand from these same planes and transposes it on the way out of LDS.  The kernel is bound by the generator's vector arithmetic
+// (Philox's 32-bit multiplies + Box-Muller), not by its plane writes.  blockIdx.y - n_riders = lane; the first n_riders grid rows (a
+// call's first draw only) lay out tril(C): four workgroups per 32-row block (each finds the rows' scales, takes every fourth share of the
+// fragments), the heaviest block first.
 // -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512) void k_fb_eps(FbArgs a) {
-  __shared__ double red[8];
-  __shared__ float E[32 * 65];   // E[m][i], leading dimension 65 (the riders' reduction area: 544 floats)
-  const int tid = threadIdx.x, eb = blockIdx.x, d = a.d;
-  if ((int)blockIdx.y < a.n_riders) {   // four workgroups per 32-row block of tril(C) (each finds the rows' scales, takes every fourth share of the fragments)
-    const int r = (int)blockIdx.y * (int)gridDim.x + eb;
-    if (r < 4 * (d >> 5)) fb_cplanes_block(a, (d >> 5) - 1 - (r >> 2), r & 3, 4, E);
+  __shared__ double red[128];   // draws: eight wave totals; riders: 8 x 32 row maxima (floats)
+  const int tid = threadIdx.x, d = a.d;
+  if ((int)blockIdx.y < a.n_riders) {
+    const int r = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
+    if (r < 4 * (d >> 5)) fb_cplanes_block<512>(a, (d >> 5) - 1 - (r >> 2), r & 3, 4, (float *)red);
     return;
   }
-  const int l = (int)blockIdx.y - a.n_riders;
+  const int l = (int)blockIdx.y - a.n_riders, eb = 2 * (int)blockIdx.x + (tid >> 8);   // eb: the 64 x 32 block of this half of the workgroup
   const uint64_t idx = rng_index(a.rng) + (a.obj ? 0ull : (uint64_t)l);
   const int moff = a.rng.m_offset + (a.obj ? l * a.MT : 0);
   unsigned *epsP = a.epsP + (size_t)l * a.plane_stride;
   const int nrb6 = d >> 6;
   const int R64 = eb % nrb6, c32 = eb / nrb6;
-  const int q = tid & 15, c = tid >> 4;
-  const int ri = R64 * 64 + 4 * q, rm = c32 * 32 + c;
-  float e[4];   // (the stream's index arithmetic is the family's: dT / 4 Philox blocks per sample; a padding row / sample holds zeros -- drawn and
-  eps_block<float>(a.rng.seed, idx, (uint64_t)(moff + rm) * (uint64_t)(a.dT >> 2) + (uint64_t)(ri >> 2), e);   // discarded: a branch around the draw cost 18 registers)
-  if (!(ri < a.dT && rm < a.MT)) { e[0] = 0.f; e[1] = 0.f; e[2] = 0.f; e[3] = 0.f; }
+  const int lane = tid & 63, l31 = lane & 31, h = lane >> 5, f = (tid >> 6) & 3;
+  const int rm = c32 * 32 + l31;
+  const uint64_t q0 = (uint64_t)(moff + rm) * (uint64_t)(a.dT >> 2);   // (the stream's index arithmetic is the family's: dT / 4 Philox blocks per sample)
+  float x[8], he = 0.f;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) E[c * 65 + 4 * q + r] = e[r] * kEpsScale;
-  const float he = 0.5f * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2] + e[3] * e[3]);
-  const double sh = block_sum_nodrain_f32<512>(he, red);   // (its barriers also publish the tile)
-  if (tid == 0) a.he_part[(size_t)l * a.he_stride + eb] = sh;
-  // ONE orientation (round 6): the product's fragments (mb32 = c32, kg = 4 R64 + f): lane = column l31, slots = rows 16 f + ..; k_fb_vjp takes its B
-  // operand from these same planes and transposes it on the way out of LDS.  (Rounds 4-5 wrote a second, VJP-oriented set: 2 MB per lane.)
-  if (tid >= 256) return;
-  const int lane = tid & 63, l31 = lane & 31, h = lane >> 5, f = tid >> 6;
-  float x[8];
+  for (int b = 0; b < 2; ++b) {
+    const int ri = R64 * 64 + 4 * (4 * f + 2 * b + h);
+    float e[4];   // (a padding row / sample holds zeros -- drawn and discarded: a branch around the draw costs registers)
+    eps_block<float>(a.rng.seed, idx, q0 + (uint64_t)(ri >> 2), e);
+    if (!(ri < a.dT && rm < a.MT)) { e[0] = 0.f; e[1] = 0.f; e[2] = 0.f; e[3] = 0.f; }
 #pragma unroll
-  for (int s = 0; s < 8; ++s) x[s] = E[l31 * 65 + 16 * f + 8 * (s >> 2) + 4 * h + (s & 3)];
+    for (int r = 0; r < 4; ++r) x[4 * b + r] = e[r] * kEpsScale;
+    he += 0.5f * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2] + e[3] * e[3]);
+  }
   fb_store_frag(epsP + ((size_t)c32 * (d >> 4) + 4 * R64 + f) * kFrag + 4 * lane, x);
+  // he_part: one double per 64 x 32 block -- f32 wave totals (DPP), the block's four summed in f64 in wave order; behind the stores, and the
+  // barrier orders LDS only
+  const float hw = wave_sum_f32(he);
+  if (lane == 0) red[tid >> 6] = (double)hw;
+  lds_barrier();
+  if ((tid & 255) == 0) {
+    const double *r4 = red + 4 * (tid >> 8);
+    a.he_part[(size_t)l * a.he_stride + eb] = ((r4[0] + r4[1]) + r4[2]) + r4[3];
+  }
 }
 
 // -----------------------------------------------------------------------------------------------------------------
@@ -1245,7 +1253,7 @@ void fb_launch_eps(mivi_ctx *c, const FbStep &s, bool with_cplanes, hipStream_t 
   a.L = L;
   a.rng = s.rng;
   a.obj = s.obj;
-  const int gx = (d / 64) * (M / 32);
+  const int gx = (d / 64) * (M / 32) / 2;   // two 64 x 32 blocks per workgroup (M / 32 is a multiple of four)
   a.n_riders = with_cplanes ? (4 * (d / 32) + gx - 1) / gx : 0;   // tril(C)'s planes: four workgroups per 32-row block, in FRONT of the lanes' draws
   hipLaunchKernelGGL(k_fb_eps, dim3(gx, L + a.n_riders), dim3(512), 0, stream, a);
 }
