@@ -4,7 +4,8 @@ reference's own interface.  Import as `import advancedvi_jl_amd as avi` (shim at
 Everything numerical is a hand-written HIP kernel in libmivi.so (csrc/, C ABI in include/mivi.h);
 this package is the host-side mirror of the reference's operator interface for that path."""
 from ._lib import LIB_PATH, MiviError, load as load_library
-from .families import MvLocationScale, MeanFieldGaussian, FullRankGaussian, destructure, MEANFIELD, FULLRANK
+from .families import (MvLocationScale, MeanFieldGaussian, FullRankGaussian, MvLocationScaleLowRank, LowRankGaussian, Restructure, destructure,
+                       MEANFIELD, FULLRANK, LOWRANK)
 from .problems import (LogDensityOrder, DiagNormalProblem, DenseNormalProblem, LogRegProblem, FunnelProblem,
                        dimension, capabilities)
 from .objectives import (RepGradELBO, RepGradELBOState, ScoreGradELBO, ScoreGradELBOState, ClosedFormEntropy, ClosedFormEntropyZeroGradient,

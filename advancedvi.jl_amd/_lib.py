@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "libmivi.so")
 
 MIVI_OK, ERR_BAD_ARG, ERR_NONFINITE, ERR_NONPOSITIVE_SCALE, ERR_HIP, ERR_NO_TARGET, ERR_UNSUPPORTED = range(7)
 F32, F64 = 0, 1
-MEANFIELD, FULLRANK = 0, 1
+MEANFIELD, FULLRANK, LOWRANK = 0, 1, 2
 
 
 class MiviConfig(C.Structure):
@@ -18,7 +18,7 @@ class MiviConfig(C.Structure):
         ("dtype", C.c_int32), ("family", C.c_int32), ("d", C.c_int32), ("n_mc", C.c_int32),
         ("entropy", C.c_int32), ("device", C.c_int32), ("seed", C.c_uint64),
         ("m_offset", C.c_int32), ("m_total", C.c_int32), ("stream", C.c_void_p),
-        ("own_stream", C.c_int32), ("reserved", C.c_int32),
+        ("own_stream", C.c_int32), ("rank", C.c_int32),   # rank: MIVI_LOWRANK only
     ]
 
 

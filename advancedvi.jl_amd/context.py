@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .families import FULLRANK, MEANFIELD
+from .families import FULLRANK, LOWRANK, MEANFIELD
 from . import problems as P
 
 NATGRAD_SMALL_D = 44   # MIVI_NATGRAD_SMALL_D (include/mivi.h): up to this d mivi_natgrad_update is the one-workgroup kernel, above it the tile path
@@ -32,18 +32,19 @@ def torch_dtype(np_dtype):
 class MiviContext:
     """One RepGradELBO estimator instance on one GPU (mivi_create ... mivi_destroy)."""
 
-    def __init__(self, dtype, family, d, n_mc, entropy, seed, device=0, m_offset=0, m_total=0, stream=None):
+    def __init__(self, dtype, family, d, n_mc, entropy, seed, device=0, m_offset=0, m_total=0, stream=None, rank=0):
         torch = _torch()
         self.lib = _lib.load()
         self.np_dtype = np.dtype(dtype)
         self.family, self.d, self.n_mc, self.entropy = int(family), int(d), int(n_mc), int(entropy)
         self.device = int(device)
+        self.rank = int(rank)   # columns of scale_factors (the low-rank family; not read for the others)
         self.tdtype = torch_dtype(self.np_dtype)
         self.tdevice = torch.device("cuda", self.device)
         if stream is None:
             stream = torch.cuda.current_stream(self.tdevice).cuda_stream
         cfg = _lib.MiviConfig(_NP2MIVI[self.np_dtype], self.family, self.d, self.n_mc, self.entropy, self.device,
-                              C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(m_offset), int(m_total), C.c_void_p(stream), 0, 0)
+                              C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(m_offset), int(m_total), C.c_void_p(stream), 0, self.rank)
         h = C.c_void_p()
         st = self.lib.mivi_create(C.byref(cfg), C.byref(h))
         _lib.check(self.lib, None, st)
@@ -240,11 +241,12 @@ class MiviContext:
     def sample(self, params, idx, want_eps=True):
         p = self.to_device(params)
         Z = self.empty(self.d * self.n_mc)
-        eps = self.empty(self.d * self.n_mc) if want_eps else None
+        de = self.d + (self.rank if self.family == LOWRANK else 0)   # low-rank: the draws are (u1 (d); u2 (rank)) per column
+        eps = self.empty(de * self.n_mc) if want_eps else None
         self._chk(self.lib.mivi_sample(self.h, self._p(p), idx, self._p(Z), self._p(eps) if want_eps else None))
         # d x M column-major -> torch (M, d) row-major view transposed
         Zv = Z.view(self.n_mc, self.d).t()
-        return (Zv, eps.view(self.n_mc, self.d).t()) if want_eps else Zv
+        return (Zv, eps.view(self.n_mc, de).t()) if want_eps else Zv
 
     def estimate_gradient(self, params, idx, value=None, grad=None):
         p = self.to_device(params)

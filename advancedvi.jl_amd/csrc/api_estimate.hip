@@ -227,6 +227,7 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
   if (s) return s;
   out.M_local = M;
   if (!out.status) out.status = (int *)c->status.p;
+  if (c->cfg.family == MIVI_LOWRANK) return run_estimate_lowrank(c, params, rng, M, want_grad, out);   // (its own kernels; nothing below knows the family)
   if (c->cfg.family == MIVI_FULLRANK && lds_route(c, params, M, want_grad, out))
     return run_estimate_lds(c, params, rng, M, want_grad, out, ch, upd, stop_after_target);
   ValueIn vin{};
@@ -357,6 +358,7 @@ mivi_status_t mivi_sample(mivi_ctx_t *c, const void *params, uint64_t idx, void 
   const int M = c->cfg.n_mc, d = c->cfg.d;
   mivi_status_t s = ensure_work(c, M);
   if (s) return s;
+  if (c->cfg.family == MIVI_LOWRANK) return sample_lowrank(c, params, idx, Z, eps);
   if (c->cfg.family == MIVI_MEANFIELD) {
     launch_sample_mf(c, params, rng_of(c, idx), M, Z, eps, d, nullptr);
   } else {
@@ -420,6 +422,7 @@ mivi_status_t mivi_estimate_gradient_host(mivi_ctx_t *c, const void *params_h, u
 
 mivi_status_t mivi_estimate_partials(mivi_ctx_t *c, const void *params, uint64_t idx, void *partials) {
   if (!c || !params || !partials) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_lowrank(c, "mivi_estimate_partials")) return rs;
   (void)hipSetDevice(c->cfg.device);
   OutArgs o = final_out(c, nullptr, nullptr);
   o.partials = partials;
@@ -430,6 +433,7 @@ mivi_status_t mivi_estimate_partials(mivi_ctx_t *c, const void *params, uint64_t
 
 mivi_status_t mivi_finalize(mivi_ctx_t *c, const void *params, const void *partials, void *value, void *grad) {
   if (!c || !params || !partials || !value || !grad) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_lowrank(c, "mivi_finalize")) return rs;
   (void)hipSetDevice(c->cfg.device);
   launch_finalize(c, params, partials, value, grad);
   HIPCHK(c, hipGetLastError());

@@ -106,6 +106,7 @@ mivi_status_t mivi_estimate_objective_host(mivi_ctx_t *c, const void *params_h, 
 mivi_status_t mivi_gauss_expected_grad_hess(mivi_ctx_t *c, const void *params, uint64_t idx, int32_t n_samples,
                                             void *logpi_avg, void *grad, void *hess) {
   if (!c || !params || !logpi_avg || !grad || !hess) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_lowrank(c, "mivi_gauss_expected_grad_hess")) return rs;
   if (c->cfg.family != MIVI_FULLRANK)
     return fail(c, MIVI_ERR_UNSUPPORTED, "gauss_expected_grad_hess takes a triangular scale (full-rank family)");
   if (n_samples <= 0) n_samples = c->cfg.n_mc;
@@ -180,6 +181,7 @@ mivi_status_t mivi_set_target_hess_callback(mivi_ctx_t *c, mivi_logdensity_gradi
 mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, uint64_t idx, int32_t n_samples,
                                              void *logpi_avg, void *grad, void *hess) {
   if (!c || !params || !logpi_avg || !grad || !hess) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_lowrank(c, "mivi_gauss_expected_grad_hess2")) return rs;
   if (c->cfg.family != MIVI_FULLRANK)
     return fail(c, MIVI_ERR_UNSUPPORTED, "gauss_expected_grad_hess takes a triangular scale (full-rank family)");
   const bool sampled = target_has_hess2(c);   // logistic regression / funnel: the Hessian depends on z -- linear in per-sample statistics (kernels_hess2.hip)
@@ -262,6 +264,7 @@ using GradHessEntry = mivi_status_t (*)(mivi_ctx_t *, const void *, uint64_t, in
 static mivi_status_t grad_hess_host(mivi_ctx *c, GradHessEntry entry, const void *params_h, uint64_t idx, int32_t n_samples, void *logpi_avg_h,
                                     void *grad_h, void *hess_h) {
   if (!c || !params_h || !logpi_avg_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_lowrank(c, "mivi_gauss_expected_grad_hess_host / mivi_gauss_expected_grad_hess2_host")) return rs;
   if (c->cfg.family != MIVI_FULLRANK)
     return fail(c, MIVI_ERR_UNSUPPORTED, "gauss_expected_grad_hess takes a triangular scale (full-rank family)");
   (void)hipSetDevice(c->cfg.device);

@@ -10,6 +10,7 @@ mivi_status_t mivi_clip_scale(mivi_ctx_t *c, void *params, double epsilon) {
 }
 mivi_status_t mivi_prox_scale_entropy(mivi_ctx_t *c, void *params, double stepsize, const void *dog_state, int32_t dog_kind) {
   if (!c || !params || (dog_state && dog_kind != 0 && dog_kind != 1)) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_lowrank(c, "mivi_prox_scale_entropy (the reference has no ProximalLocationScaleEntropy method for it)")) return rs;
   if (!dog_state && !(stepsize >= 0.0)) return fail(c, MIVI_ERR_BAD_ARG, "proximal step size must be non-negative");
   (void)hipSetDevice(c->cfg.device);
   launch_prox(c, params, stepsize, dog_state, dog_kind);
@@ -85,6 +86,8 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   if (rule != 0 && !l.opt_state_dev) return fail(c, MIVI_ERR_BAD_ARG, "this optimisation rule needs opt_state_dev");
   if (l.averager == 1 && !l.avg_params_dev) return fail(c, MIVI_ERR_BAD_ARG, "PolynomialAveraging needs avg_params_dev");
   if (l.op == 2 && (rule == 1 || rule == 4)) return fail(c, MIVI_ERR_BAD_ARG, "ProximalLocationScaleEntropy does not support Adam / COCOB (Descent, DoG, DoWG: proximal_location_scale_entropy.jl:26-42)");
+  if (l.op == 2)
+    if (mivi_status_t rs = refuse_lowrank(c, "mivi_optimize_loop with op = 2 (the reference has no ProximalLocationScaleEntropy method for it)")) return rs;
   const bool dog = rule == 2 || rule == 3;        // the rules with two global norms per step
   const bool loops_know = rule <= 3;              // the launch-free loops implement rules 0..3; COCOB (4) runs on the graph of launches
   if (!graph_capturable(c)) return fail(c, MIVI_ERR_UNSUPPORTED, "device-resident loop needs a built-in target");
@@ -107,7 +110,8 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   char *vbuf = (char *)c->X.p;
   char *gbuf = vbuf + 8 * es;
   double *rec = (double *)(((uintptr_t)(gbuf + plen * es) + 7) & ~(uintptr_t)7);
-  static const bool no_fused_loop = getenv("MIVI_NO_FUSED_LOOP") != nullptr;
+  static const bool no_fused_loop_env = getenv("MIVI_NO_FUSED_LOOP") != nullptr;
+  const bool no_fused_loop = no_fused_loop_env || c->cfg.family == MIVI_LOWRANK;   // (the low-rank family: the graph of launches only)
   const bool simple = rule <= 1 && l.op <= 1 && l.averager == 0;   // what the fused paths implement
   const bool default_adam = l.beta1 == 0.9 && l.beta2 == 0.999 && l.adam_eps == 1e-8;
   if (simple && (rule == 0 || default_adam) && c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on &&

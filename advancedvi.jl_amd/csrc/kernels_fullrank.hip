@@ -1212,7 +1212,7 @@ static void ensure_tabs(mivi_ctx *c, int M) {
 void prepare_tables(mivi_ctx *c, int M) {
   if (lds_path_shape_ok(c, M) && (c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS)) (void)lds_prepare(c, M);
   if (c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32) ensure_tabs(c, M);
-  if (c->cfg.family == MIVI_MEANFIELD && c->cfg.dtype == MIVI_F32 && c->target == TGT_DENSE_GAUSS) ensure_tabs(c, M);
+  if (c->cfg.family != MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && c->target == TGT_DENSE_GAUSS) ensure_tabs(c, M);   // (mean-field, low-rank: the dense target's tiles)
 }
 
 int eps_blocks(const mivi_ctx *c, int M) { return ((c->cfg.d + 15) / 16) * ((M + 63) / 64); }

@@ -269,7 +269,7 @@ template <typename T>
 __global__ void k_clip(int d, int family, T *params, T epsilon) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < d) {
-    const size_t o = family == MIVI_MEANFIELD ? (size_t)d + i : (size_t)d + (size_t)i * d + i;
+    const size_t o = family != MIVI_FULLRANK ? (size_t)d + i : (size_t)d + (size_t)i * d + i;   // (low-rank: scale_diag = params[d .. 2d))
     params[o] = clip_step(params[o], epsilon);
   }
 }
@@ -309,6 +309,7 @@ void launch_prox(mivi_ctx *c, void *params, double stepsize, const void *dog_sta
 __device__ __forceinline__ bool is_scale_diag(int64_t i, int d, int family) {
   if (i < d) return false;
   if (family == MIVI_MEANFIELD) return true;
+  if (family == MIVI_LOWRANK) return i < 2 * (int64_t)d;   // [m; D; vec U]
   const int64_t e = i - d;
   return (e / d) == (e % d);
 }

@@ -427,6 +427,7 @@ struct mivi_ctx {
   mivi::DevBuf bam_host;   // api_measure.hip: [Sigma (d x d); u (d x n); G (d x n); fisher, logpi_avg, elbo / entropy (16 bytes each)] of the batch-and-match _host entries
   mivi::DevBuf ngd_est, natgrad_host;   // api_measure.hip: [logpi_avg or entropy (16 bytes); grad (d); hess (d x d)] of the _steps loops and the _host updates; [S; Sigma] of mivi_natgrad_update_host / Sigma of mivi_wass_update_host
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
+  mivi::DevBuf lowr_E, lowr_V, lowr_prep, lowr_sx, lowr_part;   // low-rank family (kernels_lowrank.hip): the draws (d + r) x cap_M; V = Sigma^-1 (z - m), d x cap_M (t before that); the f64 prep block; f64 [s (r x cap_M); x (r x cap_M); |t|^2 (cap_M); log q (cap_M)]; the VJP's f64 partials, 8 slices x params_len
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
   const uint64_t *idx_src = nullptr;   // mivi_set_index_source
   mivi::EpsSpec pre;   // the eps speculation across single calls
@@ -616,6 +617,14 @@ size_t wass_work_bytes(const mivi_ctx *c);   // of c->ms_work
 size_t wass_part_bytes(const mivi_ctx *c);   // of c->ms_part
 void launch_wass_update(mivi_ctx *c, void *params, void *state, const void *grad, const void *hess, double eta, const void *logpi, void *entropy,
                         void *elbo);
+
+// kernels_lowrank.hip: the low-rank family's estimate (api_lowrank.hip drives it)
+size_t lowr_prep_doubles(int d, int r);                                        // f64 entries of c->lowr_prep
+int lowr_vjp_slices(int M);                                                    // slices of the sample axis the VJP leaves partials for (<= 8)
+void launch_lowr_draw_prep(mivi_ctx *c, const RngArgs &rng, int M, const void *params);   // (u1; u2) of M columns -> lowr_E; params != nullptr: A^-1, sum log D, 1/2 logdet A -> lowr_prep
+void launch_lowr_sample(mivi_ctx *c, const void *params, int M, void *Z, bool with_t);   // Z = D o u1 + U u2 + m (with_t: t = u1 + D^-1 U u2 -> lowr_V)
+void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v);   // t -> s, x, log q (want_v: V over t)
+void launch_lowr_vjp_finish(mivi_ctx *c, const void *params, int M, int want_grad, const ValueIn &vin, const OutArgs &out);   // W = G (and V, x, the draws) -> out.grad; out.value, the non-finite flag, the elbo record
 
 // kernels_p2p.hip: phases bit 0 push, 1 reduce + finalise, 2 unpack (7 = the whole exchange in one launch)
 void launch_p2p_handover4(mivi_ctx *c, unsigned *ready, unsigned ready_val, const unsigned *const *freed, const unsigned *freed_min, int n);

@@ -6,6 +6,9 @@
 //   counter     = (lo32 q, hi32 q, lo32 estimate_idx, hi32 estimate_idx),  key = (lo32 seed, hi32 seed)
 //   words w0..w3 -> (eps[4b], eps[4b+1]) = BoxMuller(w0, w1), (eps[4b+2], eps[4b+3]) = BoxMuller(w2, w3)
 // so any shard of the columns regenerates exactly its slice of the one-GPU stream.
+// Low-rank family (location_scale_low_rank.jl:66-100 draws u1 (d) and u2 (r) per sample): ONE stream of d + r rows per column, i.e. the
+// formulas above with d + r in place of d; rows 0 .. d-1 are u1, rows d .. d+r-1 are u2.  A column stays a pure function of (seed,
+// estimate_idx, global column): oracle.philox_normal(seed, idx, d + r, m_lo, m_hi).
 // Restated in numpy by oracle/oracle.py (philox_bits / box_muller_from_bits).
 #pragma once
 #include <stdint.h>

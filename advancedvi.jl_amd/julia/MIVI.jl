@@ -57,7 +57,7 @@ end
 # mivi_config_t (include/mivi.h)
 struct MiviConfig
     dtype::Int32; family::Int32; d::Int32; n_mc::Int32; entropy::Int32; device::Int32
-    seed::UInt64; m_offset::Int32; m_total::Int32; stream::Ptr{Cvoid}; own_stream::Int32; reserved::Int32
+    seed::UInt64; m_offset::Int32; m_total::Int32; stream::Ptr{Cvoid}; own_stream::Int32; rank::Int32   # rank: MIVI_LOWRANK only (columns of scale_factors)
 end
 
 entropy_code(::ClosedFormEntropy) = Int32(0)
@@ -69,6 +69,10 @@ dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 family_code(::MvLocationScale{<:Diagonal}) = Int32(0)
 family_code(::MvLocationScale) = Int32(1)
+family_code(::AdvancedVI.MvLocationScaleLowRank) = Int32(2)   # MIVI_LOWRANK: params = [location; scale_diag; vec(scale_factors)]
+family_rank(::MvLocationScale) = Int32(0)
+family_rank(q::AdvancedVI.MvLocationScaleLowRank) = Int32(size(q.scale_factors, 2))
+const RepGradFamily = Union{MvLocationScale,AdvancedVI.MvLocationScaleLowRank}   # what the RepGradELBO entries take
 
 mutable struct MIVIState
     problem::Any                 # the (possibly minibatch-conditioned) LogDensityProblem
@@ -109,13 +113,13 @@ function target_callback(user::Ptr{Cvoid}, Zp::Ptr{Cvoid}, d::Int32, M::Int32, e
     end
 end
 
-function AdvancedVI.init(rng::Random.AbstractRNG, obj::RepGradELBO, ad::AutoMIVI, q::MvLocationScale, prob, params, restructure)
+function AdvancedVI.init(rng::Random.AbstractRNG, obj::RepGradELBO, ad::AutoMIVI, q::RepGradFamily, prob, params, restructure)
     T = eltype(params)
     # order 0 (README.md:64-66, bench/benchmarks.jl:39-41): differentiate through `logdensity` on the host, with the reference's @info
     # (checked before any native resource exists: nothing to release on the error path)
     prob = ad_problem(ad, prob)
     cfg = Ref(MiviConfig(dtype_code(T), family_code(q), length(q), obj.n_samples, entropy_code(obj.entropy),
-                         ad.device, rand(rng, UInt64), 0, 0, C_NULL, 1, 0))
+                         ad.device, rand(rng, UInt64), 0, 0, C_NULL, 1, family_rank(q)))
     ctx = Ref{Ptr{Cvoid}}(C_NULL)
     status = ccall((:mivi_create, libmivi), Int32, (Ref{MiviConfig}, Ref{Ptr{Cvoid}}), cfg, ctx)
     status == 0 || error("mivi_create failed with status $status (no HIP device?)")
@@ -146,7 +150,7 @@ function AdvancedVI.estimate_gradient!(rng::Random.AbstractRNG, obj::RepGradELBO
     return out, state, (elbo = -value[],)
 end
 
-function AdvancedVI.estimate_objective(rng::Random.AbstractRNG, obj::RepGradELBO, q::MvLocationScale, prob, ad::AutoMIVI;
+function AdvancedVI.estimate_objective(rng::Random.AbstractRNG, obj::RepGradELBO, q::RepGradFamily, prob, ad::AutoMIVI;
                                        n_samples::Int = obj.n_samples)
     params, re = Optimisers.destructure(q)
     st = AdvancedVI.init(rng, RepGradELBO(min(n_samples, 16384); entropy = obj.entropy), ad, q, prob, params, re)

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import problems as P
 from .context import MiviContext
-from .families import MvLocationScale, destructure
+from .families import MvLocationScale, MvLocationScaleLowRank, destructure
 
 
 _log = logging.getLogger("advancedvi_jl_amd")
@@ -178,16 +178,19 @@ def _ad_problem(adtype, prob, announce=True):
 
 
 def _make_ctx(rng, obj, adtype, q, prob, n_mc=None, entropy=None):
-    if not isinstance(q, MvLocationScale):
-        raise TypeError("libmivi implements the RepGradELBO path for MvLocationScale families only")
+    if not isinstance(q, (MvLocationScale, MvLocationScaleLowRank)):
+        raise TypeError("libmivi implements the RepGradELBO path for MvLocationScale and MvLocationScaleLowRank families only")
     device = getattr(adtype, "device", 0)
     ctx = MiviContext(q.eltype, q.family, len(q), n_mc or obj.n_samples,
-                      (entropy or obj.entropy).code, rng.seed, device=device)
+                      (entropy or obj.entropy).code, rng.seed, device=device, rank=getattr(q, "rank", 0))
     ctx.set_problem(prob)
     return ctx
 
 
 def _make_score_ctx(rng, obj, adtype, q, prob):
+    if isinstance(q, MvLocationScaleLowRank):
+        raise TypeError("ScoreGradELBO is not implemented for the low-rank family (MvLocationScaleLowRank): use RepGradELBO "
+                        "(KLMinRepGradDescent), or a MeanFieldGaussian / FullRankGaussian")
     if not isinstance(q, MvLocationScale):
         raise TypeError("libmivi implements the ScoreGradELBO path for MvLocationScale families only")
     ctx = MiviContext(q.eltype, q.family, len(q), obj.n_samples, MonteCarloEntropy.code, rng.seed, device=getattr(adtype, "device", 0))
@@ -266,10 +269,10 @@ def estimate_objective(rng, obj, q, prob=None, n_samples: int = None, adtype=Non
         ctx.close()
 
 
-def rand(rng, q: MvLocationScale, num_samples: int, device: int = 0):
-    """rand(rng, q, num_samples): d x num_samples samples (location_scale.jl:71-87), returned as a
+def rand(rng, q, num_samples: int, device: int = 0):
+    """rand(rng, q, num_samples): d x num_samples samples (location_scale.jl:71-87, location_scale_low_rank.jl:66-100), returned as a
     device tensor (column m = sample m)."""
-    ctx = MiviContext(q.eltype, q.family, len(q), num_samples, 0, rng.seed, device=device)
+    ctx = MiviContext(q.eltype, q.family, len(q), num_samples, 0, rng.seed, device=device, rank=getattr(q, "rank", 0))
     try:
         params, _ = destructure(q)
         return ctx.sample(params, rng.next_index(), want_eps=False).clone()

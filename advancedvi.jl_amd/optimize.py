@@ -10,7 +10,7 @@ import numpy as np
 
 from . import objectives as O
 from . import subsampling as S
-from .families import MvLocationScale, destructure
+from .families import LOWRANK, MvLocationScale, MvLocationScaleLowRank, destructure
 
 
 # --- operators (src/optimization/clip_scale.jl, src/AdvancedVI.jl:173-204) ------------------------
@@ -30,12 +30,18 @@ class ClipScale:
         return params
 
 
+_NO_PROX_LOWRANK = ("`ProximalLocationScaleEntropy` has no method for the low-rank family (MvLocationScaleLowRank), as in the reference "
+                    "(proximal_location_scale_entropy.jl:44): use `ClipScale`")
+
+
 class ProximalLocationScaleEntropy:
     """Proximal operator of the entropy of a location-scale family, applied after the optimiser step with that step's
     size: src/optimization/proximal_location_scale_entropy.jl:17-61.  Supports Descent, DoG, DoWG (:26-42); the DoG/DoWG
     step size is read from the optimiser state on the device."""
 
     def apply(self, ctx, params, optimizer=None, opt_st=None):
+        if ctx.family == LOWRANK:
+            raise TypeError(_NO_PROX_LOWRANK)
         if isinstance(optimizer, DoG):            # DoWG is a subclass
             ctx.prox_scale_entropy(params, 0.0, opt_st, optimizer.kind)
         elif isinstance(optimizer, Descent):
@@ -247,7 +253,9 @@ def init(rng, alg, q_init, prob):
     M = _measure_space(alg)
     if M is not None:
         return M.init(rng, alg, q_init, prob)
-    if isinstance(q_init, MvLocationScale) and isinstance(alg.operator, IdentityOperator):
+    if isinstance(q_init, MvLocationScaleLowRank) and isinstance(alg.operator, ProximalLocationScaleEntropy):
+        raise TypeError(_NO_PROX_LOWRANK)
+    if isinstance(q_init, (MvLocationScale, MvLocationScaleLowRank)) and isinstance(alg.operator, IdentityOperator):
         warnings.warn(
             "IdentityOperator is used with a variational family <:MvLocationScale. Optimization can easily fail under "
             "this combination due to singular scale matrices. Consider using the operator `ClipScale` in the algorithm "

@@ -17,10 +17,14 @@
  *       full-rank : [location (d); vec(scale) column-major (d*d)]   src/families/location_scale.jl:21
  *                   entries above the diagonal are ignored on input (LowerTriangular) and the
  *                   gradient written there is exactly 0.
+ *       low-rank  : [location (d); scale_diag (d); vec(scale_factors) column-major (d*rank)]
+ *                   src/families/location_scale_low_rank.jl:22-41 (the functor's field order)
  *   - The objective value is the NEGATIVE ELBO (src/algorithms/repgradelbo.jl:117,148).
  *   - Randomness is explicit: eps is a pure function of (seed, estimate_idx, global sample m, i)
  *     through Philox4x32-10 + Box-Muller (csrc/philox.h), replacing the mutable `rng` threaded
  *     through src/algorithms/repgradelbo.jl:104-110.  One estimate consumes one estimate_idx.
+ *     Low-rank family: the draws of an estimate are ONE stream of d + rank rows per column (i runs over d + rank, the Philox block
+ *     index is m * ceil((d + rank)/4) + i/4); rows 0 .. d-1 are u1 (the diagonal part), rows d .. d+rank-1 are u2 (the factors' part).
  *   - A context is single-owner (like the reference's rng); distinct contexts are independent.
  */
 #ifndef MIVI_H
@@ -49,8 +53,16 @@ enum {
 
 typedef enum { MIVI_F32 = 0, MIVI_F64 = 1 } mivi_dtype_t;
 
-/* MeanFieldGaussian / FullRankGaussian: src/families/location_scale.jl:139-141 / :124-128 */
-typedef enum { MIVI_MEANFIELD = 0, MIVI_FULLRANK = 1 } mivi_family_t;
+/* MeanFieldGaussian / FullRankGaussian: src/families/location_scale.jl:139-141 / :124-128;
+ * LowRankGaussian: src/families/location_scale_low_rank.jl:140-145 -- z = scale_diag .* u1 + scale_factors * u2 + location, rank =
+ * cfg.rank columns of factors.  What family 2 supports: create / destroy / synchronize / set_stream / params_len, every mivi_set_target_*
+ * and mivi_set_bijector_stacked, mivi_sample (eps_dev: T[(d + rank) * n_mc]), mivi_estimate_gradient[_host / _n / _each] (the batched
+ * forms as sequential single calls), mivi_estimate_objective[_host], mivi_clip_scale / _descent_update / _adam_update / _cocob_update /
+ * the DoG entries, and mivi_optimize_steps / _loop as a graph of launches (op 0 or 1).  Every other entry that reads parameters returns
+ * MIVI_ERR_UNSUPPORTED on it (the score-gradient and measure-space entries, partials / finalize / dist / p2p, the profile entries,
+ * mivi_prox_scale_entropy and op = 2: the reference has no ProximalLocationScaleEntropy method for the family). */
+typedef enum { MIVI_MEANFIELD = 0, MIVI_FULLRANK = 1, MIVI_LOWRANK = 2 } mivi_family_t;
+#define MIVI_LOWRANK_MAX_RANK 64
 
 /* src/algorithms/entropy.jl: ClosedFormEntropy :25-29, ClosedFormEntropyZeroGradient :11-15,
  * MonteCarloEntropy :40-46, StickingTheLandingEntropy :57-65, StickingTheLandingEntropyZeroGradient :78-90 */
@@ -75,14 +87,16 @@ typedef struct {
   int32_t m_total;    /* GLOBAL n_samples the estimate is normalised by; 0 => n_mc */
   void *stream;       /* hipStream_t to launch on; NULL = the HIP null (legacy default) stream */
   int32_t own_stream; /* != 0: ignore `stream` and create a non-blocking stream owned by the context */
-  int32_t reserved;
+  int32_t rank;       /* MIVI_LOWRANK only: columns of scale_factors, 1 .. MIVI_LOWRANK_MAX_RANK (not read for the other families) */
 } mivi_config_t;
 
 typedef struct mivi_ctx mivi_ctx_t;
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
 /* replaces AdvancedVI.init(rng, obj::RepGradELBO, adtype, q, prob, params, restructure)
- * (src/algorithms/repgradelbo.jl:41-70): one-time preparation, no AD to prepare. */
+ * (src/algorithms/repgradelbo.jl:41-70): one-time preparation, no AD to prepare.
+ * MIVI_LOWRANK: MIVI_ERR_BAD_ARG unless 1 <= rank <= MIVI_LOWRANK_MAX_RANK; MIVI_ERR_UNSUPPORTED for a sharded context (m_offset != 0 or
+ * m_total not in {0, n_mc}). */
 mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out);
 mivi_status_t mivi_destroy(mivi_ctx_t *ctx);
 const char *mivi_last_error(const mivi_ctx_t *ctx);
@@ -93,11 +107,12 @@ mivi_status_t mivi_set_stream(mivi_ctx_t *ctx, void *hip_stream);
  * clears, returning MIVI_ERR_NONFINITE / MIVI_ERR_NONPOSITIVE_SCALE -- the once-per-step isfinite check of
  * src/algorithms/common.jl:83-89. */
 mivi_status_t mivi_synchronize(mivi_ctx_t *ctx);
-/* length of `params` / gradient: 2d or d + d*d  (test/families/location_scale.jl:146-155) */
+/* length of `params` / gradient: 2d or d + d*d  (test/families/location_scale.jl:146-155); low-rank: 2d + d*rank */
 int64_t mivi_params_len(const mivi_ctx_t *ctx);
 /* length of the shard-additive partials buffer ([sum_m W (d); sum_m W (x) eps; sum ell; sum 0.5|eps|^2]):
  * mean-field 2d + 2; full-rank d + d(d+1)/2 + 2 -- only the lower triangle travels, packed column by column
- * (entry (i, j), j <= i, at d + j*d - j(j-1)/2 + (i - j)) so the all-reduce moves half the bytes of the gradient. */
+ * (entry (i, j), j <= i, at d + j*d - j(j-1)/2 + (i - j)) so the all-reduce moves half the bytes of the gradient.
+ * Low-rank family: 0 (no sharded estimates). */
 int64_t mivi_partials_len(const mivi_ctx_t *ctx);
 
 /* ---- targets: the LogDensityProblems plugin seam --------------------------------------------- *
@@ -159,7 +174,8 @@ mivi_status_t mivi_set_target_value_callback(mivi_ctx_t *ctx, mivi_logdensity_fn
 
 /* ---- the hot path ----------------------------------------------------------------------------- */
 /* rand(rng, q, n_mc): src/families/location_scale.jl:71-87 (exposes the sample kernel for parity).
- * Z_dev: T[d*n_mc]; eps_dev: T[d*n_mc] or NULL. */
+ * Z_dev: T[d*n_mc]; eps_dev: T[d*n_mc] or NULL.  Low-rank family (location_scale_low_rank.jl:66-100): eps_dev is T[(d + rank)*n_mc],
+ * column m = (u1 (d); u2 (rank)) of sample m. */
 mivi_status_t mivi_sample(mivi_ctx_t *ctx, const void *params_dev, uint64_t estimate_idx,
                           void *Z_dev, void *eps_dev);
 
@@ -403,7 +419,8 @@ mivi_status_t mivi_finalize(mivi_ctx_t *ctx, const void *params_dev, const void 
                             void *value_dev, void *grad_dev);
 
 /* ---- next to the hot path: projection + optimiser step, device-resident ---------- */
-/* ClipScale: scale[diagind] = max(scale[diagind], eps)   src/optimization/clip_scale.jl:18-29 */
+/* ClipScale: scale[diagind] = max(scale[diagind], eps)   src/optimization/clip_scale.jl:18-29; low-rank family: scale_diag, params[d .. 2d)
+ * (clip_scale.jl:31-41) */
 mivi_status_t mivi_clip_scale(mivi_ctx_t *ctx, void *params_dev, double epsilon);
 /* Optimisers.Descent(eta): params .-= eta .* grad  (the rule of test/algorithms/klminrepgraddescent.jl:110) */
 mivi_status_t mivi_descent_update(mivi_ctx_t *ctx, void *params_dev, const void *grad_dev, double eta);
