@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmivi.so")
 MIVI_OK, ERR_BAD_ARG, ERR_NONFINITE, ERR_NONPOSITIVE_SCALE, ERR_HIP, ERR_NO_TARGET, ERR_UNSUPPORTED = range(7)
 F32, F64 = 0, 1
 MEANFIELD, FULLRANK, LOWRANK = 0, 1, 2
+BASE_NORMAL, BASE_LAPLACE, BASE_TDIST = 0, 1, 2
 
 
 class MiviConfig(C.Structure):
@@ -36,6 +37,7 @@ SIGNATURES = {
     "mivi_synchronize": (C.c_int32, [C.c_void_p]),
     "mivi_params_len": (C.c_int64, [C.c_void_p]),
     "mivi_partials_len": (C.c_int64, [C.c_void_p]),
+    "mivi_set_base_dist": (C.c_int32, [C.c_void_p, C.c_int32, C.c_double]),
     "mivi_optimize_loop": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mivi_logreg_select_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
     "mivi_prox_scale_entropy": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32]),

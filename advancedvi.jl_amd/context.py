@@ -147,6 +147,12 @@ class MiviContext:
             self._set_callback(prob, values_only=values_only)
         self.problem = prob
 
+    def set_base_dist(self, dist):
+        """mivi_set_base_dist: the base distribution of the location-scale family -- families.Normal() (None: the same), Laplace() or
+        TDist(nu).  Normal() on a context that never left it changes nothing."""
+        code, nu = (0, 0.0) if dist is None else (int(dist.code), float(dist.nu))
+        self._chk(self.lib.mivi_set_base_dist(self.h, code, nu))
+
     def set_bijector(self, bij):
         """mivi_set_bijector_stacked: a P.StackedBijector around whatever target is set (None removes it)."""
         if bij is None:

@@ -193,7 +193,7 @@ static bool fb_stl_on() {   // MIVI_FB_STL=0: the sticking-the-landing estimator
 }
 static bool fb_route(const mivi_ctx *c, const void *params, const void *grad_last, const void *grads_all) {
   const bool stl = stl_entropy(c);
-  return !c->is_child && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && !c->bij_on && !c->idx_src && !c->dbg &&
+  return !c->is_child && c->base == MIVI_BASE_NORMAL && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && !c->bij_on && !c->idx_src && !c->dbg &&
          (c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS) && (!stl || (fb_stl_on() && stl2_shape_ok(c, c->cfg.d))) &&
          fb_shape_ok(c, c->cfg.n_mc) && ((!stl && c->target == TGT_DIAG_GAUSS) || fb_whole_tiles(c, c->cfg.n_mc)) &&   // (padded geometry: the diagonal target, no STL term)
          ((uintptr_t)params & 15) == 0 && ((uintptr_t)grad_last & 15) == 0 && ((uintptr_t)grads_all & 15) == 0;
@@ -360,7 +360,7 @@ int32_t mivi_batch_info(const mivi_ctx_t *c, const void *params, int32_t what) {
 // target's product (0 with the diagonal target), the sticking-the-landing product (0 with the other estimators).
 mivi_status_t mivi_profile_batch(mivi_ctx_t *c, const void *params, int32_t lanes, int32_t reps, double *us_out) {
   if (!c || !params || lanes <= 0 || reps <= 0 || !us_out) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_profile_batch")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_profile_batch")) return rs;
   (void)hipSetDevice(c->cfg.device);
   if (!fb_route(c, params, nullptr, nullptr)) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_profile_batch: this configuration does not take the batch engine");
   if (lanes > fb_lanes_max()) lanes = fb_lanes_max();
@@ -499,7 +499,7 @@ static mivi_status_t record_lane_branch(mivi_ctx *c, mivi_ctx *const *ctxs, int 
 mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64_t idx0, int32_t count, void *value, void *grad) {
   if (!c || !params || !value || !grad || count <= 0) return MIVI_ERR_BAD_ARG;
   (void)hipSetDevice(c->cfg.device);
-  if (c->cfg.family == MIVI_LOWRANK) {   // the single calls, one after the other: no lanes, no child contexts, no engine, no graph
+  if (c->cfg.family == MIVI_LOWRANK || c->base != MIVI_BASE_NORMAL) {   // the single calls, one after the other: no lanes, no child contexts, no engine, no graph
     mivi_status_t sl = MIVI_OK;
     for (int i = 0; i < count && sl == MIVI_OK; ++i) sl = run_estimate(c, params, rng_of(c, idx0 + (uint64_t)i), c->cfg.n_mc, 1, final_out(c, value, grad));
     return sl;

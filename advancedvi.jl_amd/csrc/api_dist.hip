@@ -49,7 +49,7 @@ int64_t mivi_slice_len(const mivi_ctx_t *c, int32_t world) { return (c && world 
 
 mivi_status_t mivi_finalize_slice(mivi_ctx_t *c, const void *params, const void *slice_sum, int32_t rank, int32_t world, void *final_slice) {
   if (!c || !params || !slice_sum || !final_slice || world <= 0 || rank < 0 || rank >= world) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_finalize_slice")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_finalize_slice")) return rs;
   (void)hipSetDevice(c->cfg.device);
   const long long n = slice_len_of(c, world);
   if (world > 1 && n < world + 2) return fail(c, MIVI_ERR_UNSUPPORTED, "parameter vector too short to shard over this many ranks");
@@ -60,7 +60,7 @@ mivi_status_t mivi_finalize_slice(mivi_ctx_t *c, const void *params, const void 
 
 mivi_status_t mivi_unpack_final(mivi_ctx_t *c, const void *packed_final, void *value, void *grad) {
   if (!c || !packed_final || !value || !grad) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_unpack_final")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_unpack_final")) return rs;
   (void)hipSetDevice(c->cfg.device);
   launch_unpack_final(c, packed_final, value, grad);
   HIPCHK(c, hipGetLastError());
@@ -141,7 +141,7 @@ mivi_status_t mivi_p2p_detach(mivi_ctx_t *c) {
 
 mivi_status_t mivi_p2p_export(mivi_ctx_t *c, int32_t rank, int32_t world, void *handle_out) {
   if (!c || !handle_out || world < 1 || world > 8 || rank < 0 || rank >= world) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_p2p_export")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_p2p_export")) return rs;
   (void)hipSetDevice(c->cfg.device);
   (void)mivi_p2p_detach(c);
   const long long L = mivi_partials_len(c);
@@ -187,7 +187,7 @@ mivi_status_t mivi_p2p_export(mivi_ctx_t *c, int32_t rank, int32_t world, void *
 
 mivi_status_t mivi_p2p_attach(mivi_ctx_t *c, const void *handles) {
   if (!c || !handles) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_p2p_attach")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_p2p_attach")) return rs;
   if (!c->p2p_buf) return fail(c, MIVI_ERR_BAD_ARG, "mivi_p2p_export has not been called");
   (void)hipSetDevice(c->cfg.device);
   const int R = c->p2p_world;
@@ -332,7 +332,7 @@ mivi_status_t mivi_comm_destroy(mivi_ctx_t *c) {
 
 mivi_status_t mivi_comm_init(mivi_ctx_t *c, const void *id_host, int32_t rank, int32_t world) {
   if (!c || world <= 0 || rank < 0 || rank >= world || (world > 1 && !id_host)) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_comm_init")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_comm_init")) return rs;
   (void)hipSetDevice(c->cfg.device);
   (void)mivi_comm_destroy(c);
   invalidate_graph(c);
@@ -358,7 +358,7 @@ mivi_status_t mivi_comm_init(mivi_ctx_t *c, const void *id_host, int32_t rank, i
 // A failure leaves the context on the RCCL routes (the reason is in mivi_last_error).
 mivi_status_t mivi_comm_enable_p2p(mivi_ctx_t *c) {
   if (!c) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_comm_enable_p2p")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_comm_enable_p2p")) return rs;
   (void)hipSetDevice(c->cfg.device);
   const int R = c->comm_world;
   if (R > 8) return fail(c, MIVI_ERR_UNSUPPORTED, "peer-to-peer exchange: at most 8 ranks (one xGMI node)");
@@ -397,7 +397,7 @@ mivi_status_t mivi_comm_enable_p2p(mivi_ctx_t *c) {
 // A peer-to-peer exchange that does not complete (bounded waits) detaches the areas: the context stays on the RCCL routes.
 mivi_status_t mivi_p2p_selfcheck(mivi_ctx_t *c, const void *params, uint64_t idx, double *rel_out) {
   if (!c || !params) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_p2p_selfcheck")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_p2p_selfcheck")) return rs;
   (void)hipSetDevice(c->cfg.device);
   if (!c->p2p_on) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_p2p_selfcheck: no exchange areas attached");
   if (c->p2p_world > 1 && !c->comm) return fail(c, MIVI_ERR_BAD_ARG, "mivi_p2p_selfcheck: needs the RCCL communicator of mivi_comm_init to compare against");
@@ -567,7 +567,7 @@ static mivi_status_t dist_check(mivi_ctx *c) {
 // [m_offset, m_offset + n_mc) of m_total): partials -> exchange -> finalisation, all on the context's stream.
 mivi_status_t mivi_estimate_gradient_dist(mivi_ctx_t *c, const void *params, uint64_t idx, void *value, void *grad) {
   if (!c || !params || !value || !grad) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_estimate_gradient_dist")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_estimate_gradient_dist")) return rs;
   (void)hipSetDevice(c->cfg.device);
   if (c->p2p_on && !c->comm) { c->comm_world = c->p2p_world; c->comm_rank = c->p2p_rank; }   // (peer-to-peer without RCCL)
   mivi_status_t s;
@@ -830,7 +830,7 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
 
 mivi_status_t mivi_estimate_gradient_dist_n(mivi_ctx_t *c, const void *params, uint64_t idx0, int32_t count, void *value, void *grad) {
   if (!c || !params || !value || !grad || count <= 0) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_estimate_gradient_dist_n")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_estimate_gradient_dist_n")) return rs;
   (void)hipSetDevice(c->cfg.device);
   return dist_batch(c, params, idx0, count, value, grad, 0);
 }
@@ -838,7 +838,7 @@ mivi_status_t mivi_estimate_gradient_dist_n(mivi_ctx_t *c, const void *params, u
 // tests: the phases of the peer-to-peer exchange one launch at a time (several ranks of ONE process driven from one host thread)
 mivi_status_t mivi_p2p_exchange(mivi_ctx_t *c, const void *params, const void *partials, void *value, void *grad, int32_t phases) {
   if (!c || !params || !value || !grad || phases < 1 || phases > 7) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_p2p_exchange")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_p2p_exchange")) return rs;
   if (!c->p2p_on) return fail(c, MIVI_ERR_BAD_ARG, "no peer-to-peer exchange buffers attached");
   (void)hipSetDevice(c->cfg.device);
   const void *Ps[1] = {partials};   // NULL: direct mode -- mivi_p2p_partials_direct stored the vector into the owners' staging areas
@@ -851,7 +851,7 @@ mivi_status_t mivi_p2p_exchange(mivi_ctx_t *c, const void *params, const void *p
 // staging area, as vector 0 of the exchange launched next (mivi_p2p_exchange with partials = NULL).  Second-generation full-rank f32 route.
 mivi_status_t mivi_p2p_partials_direct(mivi_ctx_t *c, const void *params, uint64_t idx) {
   if (!c || !params) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_p2p_partials_direct")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_p2p_partials_direct")) return rs;
   if (!c->p2p_on) return fail(c, MIVI_ERR_BAD_ARG, "no peer-to-peer exchange buffers attached");
   (void)hipSetDevice(c->cfg.device);
   if (c->target == TGT_NONE) return fail(c, MIVI_ERR_NO_TARGET, "no target set");
@@ -870,7 +870,7 @@ mivi_status_t mivi_p2p_partials_direct(mivi_ctx_t *c, const void *params, uint64
 // stream around ONE graph replay of `reps` estimates each (after a warm replay).
 mivi_status_t mivi_profile_dist(mivi_ctx_t *c, const void *params, int32_t reps, double *us_out) {
   if (!c || !params || reps <= 0 || !us_out) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_profile_dist")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_profile_dist")) return rs;
   (void)hipSetDevice(c->cfg.device);
   char *o = (char *)c->tmp_out.p;
   hipEvent_t e0, e1;

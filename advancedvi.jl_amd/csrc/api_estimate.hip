@@ -48,7 +48,7 @@ bool no_fused_update() {   // MIVI_NO_FUSED_UPDATE=1: separate update kernel in 
 }
 
 bool hetero_ok(const mivi_ctx *c, int want_grad, const Chain *ch) {
-  if (!want_grad || c->bij_on) return false;   // (a Stacked bijector runs on the explicit-sample route)
+  if (!want_grad || c->bij_on || c->base != MIVI_BASE_NORMAL) return false;   // (a Stacked bijector, a non-normal base: the explicit-sample routes)
   // (the fused funnel target's value workgroup also finishes two gradient entries, which an optimiser step right after the
   //  estimate must already see: chained only when nothing reads the gradient between the estimates)
   if (c->cfg.family == MIVI_MEANFIELD)
@@ -228,6 +228,7 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
   out.M_local = M;
   if (!out.status) out.status = (int *)c->status.p;
   if (c->cfg.family == MIVI_LOWRANK) return run_estimate_lowrank(c, params, rng, M, want_grad, out);   // (its own kernels; nothing below knows the family)
+  if (c->base != MIVI_BASE_NORMAL) return run_estimate_base(c, params, rng, M, want_grad, out);   // (everything below draws its own normals)
   if (c->cfg.family == MIVI_FULLRANK && lds_route(c, params, M, want_grad, out))
     return run_estimate_lds(c, params, rng, M, want_grad, out, ch, upd, stop_after_target);
   ValueIn vin{};
@@ -359,6 +360,7 @@ mivi_status_t mivi_sample(mivi_ctx_t *c, const void *params, uint64_t idx, void 
   mivi_status_t s = ensure_work(c, M);
   if (s) return s;
   if (c->cfg.family == MIVI_LOWRANK) return sample_lowrank(c, params, idx, Z, eps);
+  if (c->base != MIVI_BASE_NORMAL) return sample_base(c, params, idx, Z, eps);
   if (c->cfg.family == MIVI_MEANFIELD) {
     launch_sample_mf(c, params, rng_of(c, idx), M, Z, eps, d, nullptr);
   } else {
@@ -422,7 +424,7 @@ mivi_status_t mivi_estimate_gradient_host(mivi_ctx_t *c, const void *params_h, u
 
 mivi_status_t mivi_estimate_partials(mivi_ctx_t *c, const void *params, uint64_t idx, void *partials) {
   if (!c || !params || !partials) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_estimate_partials")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_estimate_partials")) return rs;
   (void)hipSetDevice(c->cfg.device);
   OutArgs o = final_out(c, nullptr, nullptr);
   o.partials = partials;
@@ -433,7 +435,7 @@ mivi_status_t mivi_estimate_partials(mivi_ctx_t *c, const void *params, uint64_t
 
 mivi_status_t mivi_finalize(mivi_ctx_t *c, const void *params, const void *partials, void *value, void *grad) {
   if (!c || !params || !partials || !value || !grad) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_finalize")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_finalize")) return rs;
   (void)hipSetDevice(c->cfg.device);
   launch_finalize(c, params, partials, value, grad);
   HIPCHK(c, hipGetLastError());

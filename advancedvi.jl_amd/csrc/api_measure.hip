@@ -196,7 +196,7 @@ extern "C" {
 
 mivi_status_t mivi_bam_init(mivi_ctx_t *c, const void *params, void *state) {
   if (!c || !params || !state) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_bam_init")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_bam_init")) return rs;
   const mivi_status_t s = need_bam(c, "bam_init", -1, false);
   if (s) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -208,7 +208,7 @@ mivi_status_t mivi_bam_init(mivi_ctx_t *c, const void *params, void *state) {
 mivi_status_t mivi_bam_moments(mivi_ctx_t *c, const void *params, uint64_t idx, int32_t n_samples, void *u, void *G, void *fisher, void *logpi_avg,
                                void *elbo) {
   if (!c || !params || !u || !G || !fisher || !logpi_avg || !elbo) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_bam_moments")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_bam_moments")) return rs;
   mivi_status_t s;
   if ((s = need_bam(c, "bam_moments", n_samples, false))) return s;
   if (n_samples > kSampleChunk) return bam_moments_too_many(c);
@@ -220,7 +220,7 @@ mivi_status_t mivi_bam_moments(mivi_ctx_t *c, const void *params, uint64_t idx, 
 mivi_status_t mivi_bam_moments_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, int32_t n_samples, void *u_h, void *G_h, void *fisher_h,
                                     void *logpi_avg_h, void *elbo_h) {
   if (!c || !params_h || !u_h || !G_h || !fisher_h || !logpi_avg_h || !elbo_h) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_bam_moments_host")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_bam_moments_host")) return rs;
   mivi_status_t s;
   if ((s = need_bam(c, "bam_moments", n_samples, false))) return s;
   if (n_samples > kSampleChunk) return bam_moments_too_many(c);
@@ -234,7 +234,7 @@ mivi_status_t mivi_bam_moments_host(mivi_ctx_t *c, const void *params_h, uint64_
 
 mivi_status_t mivi_estimate_fisher(mivi_ctx_t *c, const void *params, uint64_t idx, int32_t n_samples, void *value) {
   if (!c || !params || !value) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_estimate_fisher")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_estimate_fisher")) return rs;
   mivi_status_t s;
   if ((s = need_bam(c, "estimate_fisher", n_samples, false))) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -255,7 +255,7 @@ mivi_status_t mivi_estimate_fisher(mivi_ctx_t *c, const void *params, uint64_t i
 
 mivi_status_t mivi_estimate_fisher_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, int32_t n_samples, void *value_h) {
   if (!c || !params_h || !value_h) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_estimate_fisher_host")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_estimate_fisher_host")) return rs;
   mivi_status_t s;
   if ((s = need_bam(c, "estimate_fisher", n_samples, false))) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -267,7 +267,7 @@ mivi_status_t mivi_estimate_fisher_host(mivi_ctx_t *c, const void *params_h, uin
 
 mivi_status_t mivi_bam_update(mivi_ctx_t *c, void *params, void *state, const void *u, const void *G, int32_t n_samples, double lambda, void *entropy) {
   if (!c || !params || !state || !u || !G || !(lambda > 0.0)) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_bam_update")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_bam_update")) return rs;
   mivi_status_t s;
   if ((s = need_bam(c, "bam_update", n_samples, true))) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -278,7 +278,7 @@ mivi_status_t mivi_bam_update(mivi_ctx_t *c, void *params, void *state, const vo
 mivi_status_t mivi_bam_update_host(mivi_ctx_t *c, void *params_h, void *state_h, const void *u_h, const void *G_h, int32_t n_samples, double lambda,
                                    void *entropy_h) {
   if (!c || !params_h || !state_h || !u_h || !G_h || !(lambda > 0.0)) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_bam_update_host")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_bam_update_host")) return rs;
   mivi_status_t s;
   if ((s = need_bam(c, "bam_update", n_samples, true))) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -295,7 +295,7 @@ mivi_status_t mivi_bam_update_host(mivi_ctx_t *c, void *params_h, void *state_h,
 mivi_status_t mivi_bam_steps(mivi_ctx_t *c, void *params, void *state, uint64_t idx0, uint64_t iteration0, int32_t count, int32_t n_samples, void *fisher,
                              void *elbo) {
   if (!c || !params || !state || count < 0 || iteration0 < 1) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_bam_steps")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_bam_steps")) return rs;
   mivi_status_t s;
   if ((s = need_bam(c, "bam_steps", n_samples, true))) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -316,7 +316,7 @@ mivi_status_t mivi_bam_steps(mivi_ctx_t *c, void *params, void *state, uint64_t 
 
 mivi_status_t mivi_sqrt_ngd_update(mivi_ctx_t *c, void *params, const void *grad, const void *hess, double stepsize, void *entropy) {
   if (!c || !params || !grad || !hess) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_sqrt_ngd_update")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_sqrt_ngd_update")) return rs;
   const mivi_status_t s = need_fullrank(c, "sqrt_ngd_update");
   if (s) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -325,20 +325,20 @@ mivi_status_t mivi_sqrt_ngd_update(mivi_ctx_t *c, void *params, const void *grad
 
 mivi_status_t mivi_sqrt_ngd_update_host(mivi_ctx_t *c, void *params_h, const void *grad_h, const void *hess_h, double stepsize, void *entropy_h) {
   if (!c || !params_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_sqrt_ngd_update_host")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_sqrt_ngd_update_host")) return rs;
   return update_host(c, "sqrt_ngd_update", Algorithm::SqrtNgd, params_h, nullptr, grad_h, hess_h, stepsize, 0, entropy_h);
 }
 
 mivi_status_t mivi_sqrt_ngd_steps(mivi_ctx_t *c, void *params, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
                                   double stepsize, void *elbo) {
   if (!c || !params || count < 0) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_sqrt_ngd_steps")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_sqrt_ngd_steps")) return rs;
   return run_steps(c, "sqrt_ngd_steps", "KLMinSqrtNaturalGradDescent", Update{Algorithm::SqrtNgd, nullptr, 0}, params, idx0, count, n_samples, second_order, stepsize, elbo);
 }
 
 mivi_status_t mivi_natgrad_init(mivi_ctx_t *c, const void *params, void *state) {
   if (!c || !params || !state) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_natgrad_init")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_natgrad_init")) return rs;
   mivi_status_t s;
   if ((s = need_fullrank(c, "natgrad_init"))) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -351,7 +351,7 @@ mivi_status_t mivi_natgrad_init(mivi_ctx_t *c, const void *params, void *state) 
 mivi_status_t mivi_natgrad_update(mivi_ctx_t *c, void *params, void *state, const void *grad, const void *hess, double stepsize,
                                   int32_t ensure_posdef, void *entropy) {
   if (!c || !params || !state || !grad || !hess) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_natgrad_update")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_natgrad_update")) return rs;
   const mivi_status_t s = need_fullrank(c, "natgrad_update");
   if (s) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -361,21 +361,21 @@ mivi_status_t mivi_natgrad_update(mivi_ctx_t *c, void *params, void *state, cons
 mivi_status_t mivi_natgrad_update_host(mivi_ctx_t *c, void *params_h, void *state_h, const void *grad_h, const void *hess_h, double stepsize,
                                        int32_t ensure_posdef, void *entropy_h) {
   if (!c || !params_h || !state_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_natgrad_update_host")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_natgrad_update_host")) return rs;
   return update_host(c, "natgrad_update", Algorithm::NatGrad, params_h, state_h, grad_h, hess_h, stepsize, ensure_posdef, entropy_h);
 }
 
 mivi_status_t mivi_natgrad_steps(mivi_ctx_t *c, void *params, void *state, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
                                  double stepsize, int32_t ensure_posdef, void *elbo) {
   if (!c || !params || !state || count < 0) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_natgrad_steps")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_natgrad_steps")) return rs;
   return run_steps(c, "natgrad_steps", "KLMinNaturalGradDescent", Update{Algorithm::NatGrad, state, ensure_posdef}, params, idx0, count, n_samples, second_order, stepsize,
                    elbo);
 }
 
 mivi_status_t mivi_wass_init(mivi_ctx_t *c, const void *params, void *state) {
   if (!c || !params || !state) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_wass_init")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_wass_init")) return rs;
   const mivi_status_t s = need_fullrank(c, "wass_init");
   if (s) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -386,7 +386,7 @@ mivi_status_t mivi_wass_init(mivi_ctx_t *c, const void *params, void *state) {
 
 mivi_status_t mivi_wass_update(mivi_ctx_t *c, void *params, void *state, const void *grad, const void *hess, double stepsize, void *entropy) {
   if (!c || !params || !state || !grad || !hess) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_wass_update")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_wass_update")) return rs;
   const mivi_status_t s = need_fullrank(c, "wass_update");
   if (s) return s;
   (void)hipSetDevice(c->cfg.device);
@@ -396,14 +396,14 @@ mivi_status_t mivi_wass_update(mivi_ctx_t *c, void *params, void *state, const v
 mivi_status_t mivi_wass_update_host(mivi_ctx_t *c, void *params_h, void *state_h, const void *grad_h, const void *hess_h, double stepsize,
                                     void *entropy_h) {
   if (!c || !params_h || !state_h || !grad_h || !hess_h) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_wass_update_host")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_wass_update_host")) return rs;
   return update_host(c, "wass_update", Algorithm::Wass, params_h, state_h, grad_h, hess_h, stepsize, 0, entropy_h);
 }
 
 mivi_status_t mivi_wass_steps(mivi_ctx_t *c, void *params, void *state, uint64_t idx0, int32_t count, int32_t n_samples, int32_t second_order,
                               double stepsize, void *elbo) {
   if (!c || !params || !state || count < 0) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_wass_steps")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_wass_steps")) return rs;
   return run_steps(c, "wass_steps", "KLMinWassFwdBwd", Update{Algorithm::Wass, state, 0}, params, idx0, count, n_samples, second_order, stepsize, elbo);
 }
 

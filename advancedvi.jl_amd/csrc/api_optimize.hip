@@ -111,7 +111,7 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   char *gbuf = vbuf + 8 * es;
   double *rec = (double *)(((uintptr_t)(gbuf + plen * es) + 7) & ~(uintptr_t)7);
   static const bool no_fused_loop_env = getenv("MIVI_NO_FUSED_LOOP") != nullptr;
-  const bool no_fused_loop = no_fused_loop_env || c->cfg.family == MIVI_LOWRANK;   // (the low-rank family: the graph of launches only)
+  const bool no_fused_loop = no_fused_loop_env || c->cfg.family == MIVI_LOWRANK || c->base != MIVI_BASE_NORMAL;   // (the low-rank family, a non-normal base: the graph of launches only)
   const bool simple = rule <= 1 && l.op <= 1 && l.averager == 0;   // what the fused paths implement
   const bool default_adam = l.beta1 == 0.9 && l.beta2 == 0.999 && l.adam_eps == 1e-8;
   if (simple && (rule == 0 || default_adam) && c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on &&

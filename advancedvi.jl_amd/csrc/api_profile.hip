@@ -5,7 +5,7 @@
 
 mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *params, int32_t reps, double *ms_out) {
   if (!c || !params || reps <= 0 || !ms_out || which < 0 || which > 11) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_profile_kernel")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_profile_kernel")) return rs;
   (void)hipSetDevice(c->cfg.device);
   const int M = c->cfg.n_mc;
   char *o = (char *)c->tmp_out.p;

@@ -76,14 +76,14 @@ static mivi_status_t run_score_estimate(mivi_ctx *c, const void *params, uint64_
 
 mivi_status_t mivi_estimate_score_gradient(mivi_ctx_t *c, const void *params, uint64_t idx, void *value, void *elbo, void *grad) {
   if (!c || !params || !value || !grad) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_estimate_score_gradient")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_estimate_score_gradient")) return rs;
   (void)hipSetDevice(c->cfg.device);
   return run_score_estimate(c, params, idx, value, elbo, grad);
 }
 
 mivi_status_t mivi_estimate_score_gradient_host(mivi_ctx_t *c, const void *params_h, uint64_t idx, void *value_h, void *elbo_h, void *grad_h) {
   if (!c || !params_h || !value_h || !grad_h) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_lowrank(c, "mivi_estimate_score_gradient_host")) return rs;
+  if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_estimate_score_gradient_host")) return rs;
   (void)hipSetDevice(c->cfg.device);
   const size_t es = c->esize;
   mivi_status_t s = stage_params(c, params_h);

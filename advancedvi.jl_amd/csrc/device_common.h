@@ -283,6 +283,7 @@ __device__ __forceinline__ void partial_store(const PartialDst &pd, long long id
 //   value = -( sum_ell / M_total + entropy_estimate )
 //   closed-form estimators: d/2 (1 + log 2pi) + sum_i log C_ii            location_scale.jl:52-57
 //   MC / STL estimators   : mean_m 0.5|eps_m|^2 + d/2 log 2pi + sum_i log C_ii   (C^-1 (z_m - mu) == eps_m)
+//   a non-normal base phi (vin.base): d H(phi) + sum_i log C_ii, resp. mean_m -sum_i log phi(u_im) + sum_i log C_ii   (families.md:31-39)
 // `scale_diag(i)` returns C_ii. `red` holds 6 * NT/64 doubles.
 // FUNNEL: also finish the fused funnel target (funnel_finish).  Only k_value_funnel and the funnel instantiation of k_mf_main
 // carry it: the other kernels never take that path.
@@ -349,7 +350,9 @@ __device__ void finalize_value_block(int d, const ValueIn &vin, const OutArgs &o
       }
     } else {
       const double Mt = (double)out.M_total;
-      const double ent = (ent_is_closed(out.ent_kind) ? 0.5 * d * (1.0 + kLog2Pi) : s_he / Mt + 0.5 * d * kLog2Pi) + s_ld;
+      // (a non-normal base: d H(phi) + log|C|, or the Monte-Carlo mean of -sum log phi(u) + log|C|; the normal base's arithmetic is untouched)
+      const double ent = vin.base ? (ent_is_closed(out.ent_kind) ? d * vin.base_H : s_he / Mt + d * vin.base_c0) + s_ld
+                                  : (ent_is_closed(out.ent_kind) ? 0.5 * d * (1.0 + kLog2Pi) : s_he / Mt + 0.5 * d * kLog2Pi) + s_ld;
       const double value = -(sum_ell / Mt + ent);
       *(T *)out.value = (T)value;
       int st = 0;

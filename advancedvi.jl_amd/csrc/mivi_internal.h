@@ -69,6 +69,10 @@ struct ValueIn {
   const double *ld_part;   // [2][n_ld_part]: partial sums of log C_ii, then counts of non-positive C_ii (or nullptr)
   int n_ld_part;
   double ell_const;        // constant added per sample (target normaliser)
+  // a non-normal base distribution (mivi_set_base_dist; 0 = Normal: the two constants are not read): he_part then holds the partial sums of
+  // the variable part of -sum log phi(u), base_c0 = -(log phi's constant) per element, base_H = H(phi)
+  int base;
+  double base_c0, base_H;
 };
 
 // how results are emitted
@@ -428,6 +432,10 @@ struct mivi_ctx {
   mivi::DevBuf ngd_est, natgrad_host;   // api_measure.hip: [logpi_avg or entropy (16 bytes); grad (d); hess (d x d)] of the _steps loops and the _host updates; [S; Sigma] of mivi_natgrad_update_host / Sigma of mivi_wass_update_host
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
   mivi::DevBuf lowr_E, lowr_V, lowr_prep, lowr_sx, lowr_part;   // low-rank family (kernels_lowrank.hip): the draws (d + r) x cap_M; V = Sigma^-1 (z - m), d x cap_M (t before that); the f64 prep block; f64 [s (r x cap_M); x (r x cap_M); |t|^2 (cap_M); log q (cap_M)]; the VJP's f64 partials, 8 slices x params_len
+  // base distribution of the location-scale families (mivi_set_base_dist; base_dist.h, kernels_basedist.hip, api_basedist.hip)
+  int base = MIVI_BASE_NORMAL;
+  double base_nu = 0.0, base_c0 = 0.0, base_H = 0.0;   // TDist's degrees of freedom; -(constant of log phi); H(phi) -- f64, computed once on the host
+  mivi::DevBuf bd_U, bd_R;   // mean-field: the draws laid out like eps (ld dP, zero padded); both families, sticking-the-landing kinds: the plane -psi(U), same layout
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
   const uint64_t *idx_src = nullptr;   // mivi_set_index_source
   mivi::EpsSpec pre;   // the eps speculation across single calls
@@ -625,6 +633,11 @@ void launch_lowr_draw_prep(mivi_ctx *c, const RngArgs &rng, int M, const void *p
 void launch_lowr_sample(mivi_ctx *c, const void *params, int M, void *Z, bool with_t);   // Z = D o u1 + U u2 + m (with_t: t = u1 + D^-1 U u2 -> lowr_V)
 void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v);   // t -> s, x, log q (want_v: V over t)
 void launch_lowr_vjp_finish(mivi_ctx *c, const void *params, int M, int want_grad, const ValueIn &vin, const OutArgs &out);   // W = G (and V, x, the draws) -> out.grad; out.value, the non-finite flag, the elbo record
+
+// kernels_basedist.hip: the draw stage and the mean-field kernels of a non-normal base (api_basedist.hip drives them)
+void launch_bd_draw(mivi_ctx *c, const RngArgs &rng, int M, void *U, void *UT, void *R);   // U (ld dP), UT (ld MP; or nullptr), R = -psi(U) (ld dP; or nullptr); he_part[cur]: eps_blocks partials of the variable part of -sum log phi(u)
+void launch_bd_mf_sample(mivi_ctx *c, const void *params, int M, const void *U, void *Z);   // Z = sigma o U + m
+void launch_bd_mf_grad(mivi_ctx *c, const void *params, int M, const void *U, const void *R, const OutArgs &out);   // W (and R / sigma) -> [dm; dsigma]
 
 // kernels_p2p.hip: phases bit 0 push, 1 reduce + finalise, 2 unpack (7 = the whole exchange in one launch)
 void launch_p2p_handover4(mivi_ctx *c, unsigned *ready, unsigned ready_val, const unsigned *const *freed, const unsigned *freed_min, int n);

@@ -9,7 +9,14 @@
 // Low-rank family (location_scale_low_rank.jl:66-100 draws u1 (d) and u2 (r) per sample): ONE stream of d + r rows per column, i.e. the
 // formulas above with d + r in place of d; rows 0 .. d-1 are u1, rows d .. d+r-1 are u2.  A column stays a pure function of (seed,
 // estimate_idx, global column): oracle.philox_normal(seed, idx, d + r, m_lo, m_hi).
-// Restated in numpy by oracle/oracle.py (philox_bits / box_muller_from_bits).
+// Non-normal base distributions (mivi_set_base_dist; base_dist.h holds the transforms): the same key and counter, and
+//   Laplace : the block and word assignment above; sign + if the word's top bit is set, magnitude -ln v with
+//             v = (((w >> 8) & 0x7fffff) + 0.5) 2^-23 (f32 stream),  v = ((w & 0x7fffffff) + 0.5) 2^-31 (f64 stream)
+//   TDist nu: Bailey's polar form T = sqrt(nu expm1(-(2/nu) ln U)) cos(2 pi V).  Its sine partner is not independent of T (the pair is
+//             bivariate t), so a variate costs two words: element (i, m) takes words 2 (i % 2) (-> U) and 2 (i % 2) + 1 (-> V) of block
+//             q = m * ceil(d/2) + i/2 -- rows 2i, 2i + 1 of oracle.philox_bits(seed, idx, 2 d, ...); word -> uniform as Box-Muller's
+//             (u(w) below).  expm1 avoids the cancellation of U^(-2/nu) - 1 near U = 1.
+// Restated in numpy by oracle/oracle.py (philox_bits / box_muller_from_bits) and, for the two streams above, tests/basedist_ref.py.
 #pragma once
 #include <stdint.h>
 

@@ -108,6 +108,8 @@ class DistributedRepGradELBO:
         from .context import MiviContext
         from .families import destructure
 
+        if getattr(getattr(q, "dist", None), "code", 0) != 0:   # (the library refuses a non-normal base on the sharded entries: say so before any context exists)
+            raise TypeError(f"sharded estimates are not implemented for the base distribution {q.dist!r}: use a family with dist = Normal()")
         self.group = group
         self.force_collective = force_collective
         if dist.is_available() and dist.is_initialized():

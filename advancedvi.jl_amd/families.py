@@ -1,11 +1,12 @@
 """Variational family containers mirroring src/families/location_scale.jl and location_scale_low_rank.jl (AdvancedVI.jl v0.7.0).
 
-Only what the RepGradELBO hot path needs: the `MvLocationScale` container, the two Gaussian
-constructors, and `destructure` / restructure.  All arithmetic on samples (rand, entropy, logpdf
+Only what the RepGradELBO hot path needs: the `MvLocationScale` container with its base distribution
+(`Normal()`, `Laplace()`, `TDist(nu)`), the two Gaussian constructors, and `destructure` / restructure.  All arithmetic on samples (rand, entropy, logpdf
 inside the estimators) runs in libmivi's HIP kernels."""
 from __future__ import annotations
 
-from dataclasses import dataclass
+import math
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -13,16 +14,93 @@ MEANFIELD, FULLRANK, LOWRANK = 0, 1, 2
 LOWRANK_MAX_RANK = 64   # MIVI_LOWRANK_MAX_RANK (include/mivi.h)
 
 
+# --- univariate base distributions of MvLocationScale (docs/src/families.md:59-101): mivi_base_t codes, host statistics ---------------
+def _digamma(x: float) -> float:
+    """digamma(x), x > 0: the recurrence up to x >= 10, then the asymptotic series."""
+    r = 0.0
+    while x < 10.0:
+        r -= 1.0 / x
+        x += 1.0
+    i2 = 1.0 / (x * x)
+    ser = i2 * (1 / 12 - i2 * (1 / 120 - i2 * (1 / 252 - i2 * (1 / 240 - i2 * (1 / 132 - i2 * (691 / 32760 - i2 / 12))))))
+    return r + math.log(x) - 0.5 / x - ser
+
+
+class Normal:
+    """Normal(): the standard normal base (MIVI_BASE_NORMAL), the default of every family."""
+    code, nu = 0, 0.0
+
+    def entropy(self):
+        return 0.5 * (1.0 + math.log(2.0 * math.pi))
+
+    def mean(self):
+        return 0.0
+
+    def var(self):
+        return 1.0
+
+    def __eq__(self, other):
+        return type(other) is type(self) and other.nu == self.nu
+
+    def __hash__(self):
+        return hash((type(self).__name__, self.nu))
+
+    def __repr__(self):
+        return f"{type(self).__name__}()"
+
+
+class Laplace(Normal):
+    """Laplace(): location 0, scale 1 (MIVI_BASE_LAPLACE; families.md:88-101)."""
+    code = 1
+
+    def entropy(self):
+        return 1.0 + math.log(2.0)
+
+    def var(self):
+        return 2.0
+
+
+class TDist(Normal):
+    """TDist(nu): Student-t with nu > 0 degrees of freedom (MIVI_BASE_TDIST; families.md:72-86)."""
+    code = 2
+
+    def __init__(self, nu):
+        nu = float(nu)
+        if not (nu > 0.0 and math.isfinite(nu)):
+            raise ValueError("TDist: the degrees of freedom nu must be positive and finite")
+        self.nu = nu
+
+    def entropy(self):
+        nu = self.nu
+        a, b = 0.5 * (nu + 1.0), 0.5 * nu
+        lbeta = math.lgamma(b) + math.lgamma(0.5) - math.lgamma(a)
+        return a * (_digamma(a) - _digamma(b)) + 0.5 * math.log(nu) + lbeta
+
+    def mean(self):   # as Distributions.jl: NaN for nu <= 1
+        return 0.0 if self.nu > 1.0 else math.nan
+
+    def var(self):    # as Distributions.jl: nu / (nu - 2), Inf for 1 < nu <= 2, NaN below
+        if self.nu > 2.0:
+            return self.nu / (self.nu - 2.0)
+        return math.inf if self.nu > 1.0 else math.nan
+
+    def __repr__(self):
+        return f"TDist({self.nu})"
+
+
 @dataclass
 class MvLocationScale:
-    """MvLocationScale(location, scale, dist) with dist = Normal(0, 1)
-    (src/families/location_scale.jl:15-19).  `scale` is a length-d vector (Diagonal) or a d x d
+    """MvLocationScale(location, scale, dist), dist = Normal() unless given (src/families/location_scale.jl:15-19): z = scale u + location
+    with the entries of u i.i.d. from `dist` -- Normal(), Laplace() or TDist(nu).  `scale` is a length-d vector (Diagonal) or a d x d
     lower-triangular matrix (LowerTriangular).  Arrays are numpy (host) float32/float64."""
 
     location: np.ndarray
     scale: np.ndarray
+    dist: Normal = field(default_factory=Normal)
 
     def __post_init__(self):
+        if not isinstance(self.dist, Normal):
+            raise TypeError("MvLocationScale: dist must be Normal(), Laplace() or TDist(nu)")
         self.location = np.ascontiguousarray(self.location)
         self.scale = np.asarray(self.scale, dtype=self.location.dtype)
         if self.location.dtype not in (np.float32, np.float64):
@@ -41,6 +119,25 @@ class MvLocationScale:
     @property
     def eltype(self):  # Base.eltype, location_scale.jl:49
         return self.location.dtype
+
+    # host statistics (numpy): location_scale.jl:52-57, 98-113
+    def _dense_scale(self):
+        return np.diag(self.scale) if self.scale.ndim == 1 else self.scale
+
+    def entropy(self):
+        diag = self.scale if self.scale.ndim == 1 else np.diagonal(self.scale)
+        return self.eltype.type(len(self) * self.eltype.type(self.dist.entropy()) + np.log(diag).sum())   # d H(dist) + logdet(scale)
+
+    def mean(self):
+        return self.location + self._dense_scale() @ np.full(len(self), self.dist.mean(), dtype=self.eltype)
+
+    def var(self):
+        C = self._dense_scale()
+        return self.dist.var() * np.diagonal(C @ C.T)
+
+    def cov(self):
+        C = self._dense_scale()
+        return self.dist.var() * (C @ C.T)
 
 
 def MeanFieldGaussian(mu, diag) -> MvLocationScale:
@@ -112,8 +209,9 @@ class Restructure:
     """The `re` closure returned by Optimisers.destructure; RestructureMeanField for the
     Diagonal case (src/families/location_scale.jl:28-37)."""
 
-    def __init__(self, d: int, family: int, dtype, rank: int = 0):
+    def __init__(self, d: int, family: int, dtype, rank: int = 0, dist=None):
         self.d, self.family, self.dtype, self.rank = d, family, dtype, rank
+        self.dist = dist if dist is not None else Normal()   # carried through, as re.model.dist (location_scale.jl:32-37)
 
     def __call__(self, flat):
         flat = np.asarray(flat, dtype=self.dtype)
@@ -125,10 +223,10 @@ class Restructure:
         if self.family == MEANFIELD:
             if flat.shape[0] != 2 * d:
                 raise ValueError("flat parameter vector has the wrong length")
-            return MvLocationScale(flat[:d].copy(), flat[d:].copy())
+            return MvLocationScale(flat[:d].copy(), flat[d:].copy(), self.dist)
         if flat.shape[0] != d + d * d:
             raise ValueError("flat parameter vector has the wrong length")
-        return MvLocationScale(flat[:d].copy(), np.tril(flat[d:].reshape(d, d, order="F")))
+        return MvLocationScale(flat[:d].copy(), np.tril(flat[d:].reshape(d, d, order="F")), self.dist)
 
 
 def destructure(q):
@@ -145,4 +243,4 @@ def destructure(q):
         flat = np.concatenate([q.location, q.scale])
     else:
         flat = np.concatenate([q.location, np.tril(q.scale).reshape(-1, order="F")])
-    return flat.astype(q.eltype, copy=False), Restructure(d, q.family, q.eltype)
+    return flat.astype(q.eltype, copy=False), Restructure(d, q.family, q.eltype, dist=q.dist)

@@ -11,7 +11,7 @@
 module MIVI
 
 using AdvancedVI, ADTypes, AbstractPPL, DiffResults, LogDensityProblems, Optimisers, Random, LinearAlgebra
-using Distributions: Normal
+using Distributions: Normal, Laplace, TDist
 using AdvancedVI: MvLocationScale, RepGradELBO, ScoreGradELBO, KLMinRepGradDescent, ClosedFormEntropy, ClosedFormEntropyZeroGradient,
                   MonteCarloEntropy, StickingTheLandingEntropy, StickingTheLandingEntropyZeroGradient
 
@@ -73,6 +73,13 @@ family_code(::AdvancedVI.MvLocationScaleLowRank) = Int32(2)   # MIVI_LOWRANK: pa
 family_rank(::MvLocationScale) = Int32(0)
 family_rank(q::AdvancedVI.MvLocationScaleLowRank) = Int32(size(q.scale_factors, 2))
 const RepGradFamily = Union{MvLocationScale,AdvancedVI.MvLocationScaleLowRank}   # what the RepGradELBO entries take
+# MvLocationScale(location, scale, dist) (location_scale.jl:15-19): (mivi_base_t, nu) of the STANDARD base distributions libmivi draws
+base_code(d::Normal) = (iszero(d.μ) && isone(d.σ)) ? (Int32(0), 0.0) : throw(ArgumentError("libmivi draws the standard Normal() only"))
+base_code(d::Laplace) = (iszero(d.μ) && isone(d.θ)) ? (Int32(1), 0.0) : throw(ArgumentError("libmivi draws the standard Laplace() only"))
+base_code(d::TDist) = (Int32(2), Float64(d.ν))
+base_code(d) = throw(ArgumentError("libmivi has no draw stream for the base distribution $(typeof(d)): Normal(), Laplace() or TDist(nu)"))
+base_code(q::MvLocationScale) = base_code(q.dist)
+base_code(::AdvancedVI.MvLocationScaleLowRank) = (Int32(0), 0.0)   # (the low-rank family: Normal() only)
 
 mutable struct MIVIState
     problem::Any                 # the (possibly minibatch-conditioned) LogDensityProblem
@@ -125,6 +132,8 @@ function AdvancedVI.init(rng::Random.AbstractRNG, obj::RepGradELBO, ad::AutoMIVI
     status == 0 || error("mivi_create failed with status $status (no HIP device?)")
     st = MIVIState(prob, T, ctx[], UInt64(0), nothing, false, nothing, false, ad.target_ad)
     finalizer(s -> ccall((:mivi_destroy, libmivi), Int32, (Ptr{Cvoid},), s.ctx), st)
+    base, nu = base_code(q)           # q.dist: Normal() changes nothing; Laplace() / TDist(nu) select their draw streams
+    check(st.ctx, ccall((:mivi_set_base_dist, libmivi), Int32, (Ptr{Cvoid}, Int32, Float64), st.ctx, base, nu))
     if prob isa NativeTarget          # a target whose arithmetic stays on the GPU: no host callback at all
         set_native_target!(st, prob)
         return st
@@ -181,6 +190,7 @@ end
 
 function AdvancedVI.init(rng::Random.AbstractRNG, obj::ScoreGradELBO, ad::AutoMIVI, q::MvLocationScale, prob, params, restructure)
     T = eltype(params)
+    first(base_code(q)) == 0 || throw(ArgumentError("libmivi's ScoreGradELBO path takes dist = Normal() only (use RepGradELBO for $(typeof(q.dist)))"))
     cfg = Ref(MiviConfig(dtype_code(T), family_code(q), length(q), obj.n_samples, entropy_code(MonteCarloEntropy()),
                          ad.device, rand(rng, UInt64), 0, 0, C_NULL, 1, 0))
     ctx = Ref{Ptr{Cvoid}}(C_NULL)

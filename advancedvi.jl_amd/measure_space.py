@@ -159,6 +159,8 @@ def init(rng, alg, q_init, prob):
     name = type(alg).__name__
     if not isinstance(q_init, MvLocationScale) or q_init.family != FULLRANK:
         raise TypeError(f"`{name}` expects a Gaussian with a lower-triangular scale (FullRankGaussian) as q_init")
+    if q_init.dist.code != 0:   # (the reference types these algorithms on FullRankGaussian)
+        raise TypeError(f"`{name}` expects a Gaussian q_init (FullRankGaussian): the base distribution {q_init.dist!r} is not Normal()")
     capability = P.capabilities(prob)
     if capability < P.LogDensityOrder(1):   # :64-70 of either file (ArgumentError)
         raise ValueError(f"`{name}` requires at least first-order differentiation capability. The capability of the "

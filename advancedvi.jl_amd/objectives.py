@@ -183,7 +183,12 @@ def _make_ctx(rng, obj, adtype, q, prob, n_mc=None, entropy=None):
     device = getattr(adtype, "device", 0)
     ctx = MiviContext(q.eltype, q.family, len(q), n_mc or obj.n_samples,
                       (entropy or obj.entropy).code, rng.seed, device=device, rank=getattr(q, "rank", 0))
-    ctx.set_problem(prob)
+    try:
+        ctx.set_base_dist(getattr(q, "dist", None))   # MvLocationScale(location, scale, dist); the low-rank family: Normal() only
+        ctx.set_problem(prob)
+    except Exception:
+        ctx.close()
+        raise
     return ctx
 
 
@@ -193,6 +198,9 @@ def _make_score_ctx(rng, obj, adtype, q, prob):
                         "(KLMinRepGradDescent), or a MeanFieldGaussian / FullRankGaussian")
     if not isinstance(q, MvLocationScale):
         raise TypeError("libmivi implements the ScoreGradELBO path for MvLocationScale families only")
+    if q.dist.code != 0:
+        raise TypeError(f"ScoreGradELBO is not implemented for the base distribution {q.dist!r}: use RepGradELBO (KLMinRepGradDescent), "
+                        "or a family with dist = Normal()")
     ctx = MiviContext(q.eltype, q.family, len(q), obj.n_samples, MonteCarloEntropy.code, rng.seed, device=getattr(adtype, "device", 0))
     ctx.set_problem(prob, values_only=True)
     return ctx
@@ -274,6 +282,7 @@ def rand(rng, q, num_samples: int, device: int = 0):
     device tensor (column m = sample m)."""
     ctx = MiviContext(q.eltype, q.family, len(q), num_samples, 0, rng.seed, device=device, rank=getattr(q, "rank", 0))
     try:
+        ctx.set_base_dist(getattr(q, "dist", None))
         params, _ = destructure(q)
         return ctx.sample(params, rng.next_index(), want_eps=False).clone()
     finally:

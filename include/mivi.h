@@ -115,6 +115,29 @@ int64_t mivi_params_len(const mivi_ctx_t *ctx);
  * Low-rank family: 0 (no sharded estimates). */
 int64_t mivi_partials_len(const mivi_ctx_t *ctx);
 
+/* ---- the base distribution of the location-scale families ----------------------------------- *
+ * MvLocationScale(location, scale, dist): src/families/location_scale.jl:15-19, docs/src/families.md:72-101 -- z = C u + m with the
+ * entries of u i.i.d. from a univariate base phi: Normal() (the default), Laplace() or TDist(nu).
+ * nu: degrees of freedom, read for MIVI_BASE_TDIST only (nu > 0, any real).
+ * The draws stay a pure function of (seed, estimate_idx, global column m, row i), key and counter as for the normal stream (philox.h):
+ *   Laplace: element (i, m) takes word i % 4 of block q = m * ceil(d/4) + i/4; sign + if the word's top bit is set; magnitude -ln v,
+ *            v = (((w >> 8) & 0x7fffff) + 0.5) 2^-23 (f32 contexts), v = ((w & 0x7fffffff) + 0.5) 2^-31 (f64 contexts).
+ *   TDist  : Bailey's polar form T = sqrt(nu expm1(-(2/nu) ln U)) cos(2 pi V); element (i, m) takes words 2 (i % 2) (-> U) and
+ *            2 (i % 2) + 1 (-> V) of block q = m * ceil(d/2) + i/2; word -> uniform as Box-Muller: ((w >> 9) + 0.5) 2^-23 (f32),
+ *            (w + 0.5) 2^-32 (f64).
+ * MIVI_BASE_NORMAL is a no-op in effect: such a context gives bitwise the results of one that never called this, on every route.
+ * MIVI_ERR_BAD_ARG: an unknown base, nu <= 0 or not finite.  MIVI_ERR_UNSUPPORTED for a non-normal base on a MIVI_LOWRANK context or a
+ * sharded one (m_offset != 0 or m_total not in {0, n_mc}).  Invalidates captured graphs, like mivi_set_target_*.
+ * What a non-normal base supports (both families, both precisions): mivi_sample, mivi_estimate_gradient[_host / _n / _each] (the batched
+ * forms as sequential single calls, bitwise equal to them), mivi_estimate_objective[_host] (any n_samples, all five entropy kinds), every
+ * mivi_set_target_* incl. the gradient callback, mivi_set_bijector_stacked, the update entries (clip, descent, adam, cocob, DoG / DoWG,
+ * mivi_prox_scale_entropy, mivi_axpby) and mivi_optimize_steps / _loop as the graph of launches with every rule, operator and averager.
+ * Every other entry that reads parameters returns MIVI_ERR_UNSUPPORTED with a message naming the base, before it reads a buffer: the
+ * score-gradient entries, mivi_gauss_expected_grad_hess*, the natgrad / sqrt-ngd / bam / wass entries (Gaussian by definition),
+ * partials / finalize / dist / comm / p2p, the profile entries. */
+typedef enum { MIVI_BASE_NORMAL = 0, MIVI_BASE_LAPLACE = 1, MIVI_BASE_TDIST = 2 } mivi_base_t;
+mivi_status_t mivi_set_base_dist(mivi_ctx_t *ctx, int32_t base, double nu);
+
 /* ---- targets: the LogDensityProblems plugin seam --------------------------------------------- *
  * replaces LogDensityProblems.logdensity / logdensity_and_gradient / dimension as called from
  * src/algorithms/repgradelbo.jl:84-86 and src/mixedad_logdensity.jl:23-34.  Built-in targets run
