@@ -254,6 +254,43 @@ class MiviContext:
         Zv = Z.view(self.n_mc, self.d).t()
         return (Zv, eps.view(self.n_mc, de).t()) if want_eps else Zv
 
+    def _points(self, Z):
+        """the d x n points of logpdf as column-major device storage: (flat tensor of d * n elements, n).  A (d, n) matrix (numpy or
+        tensor; the transposed view `sample` returns is taken as it is), a vector of d (n = 1), or the flat column-major storage."""
+        torch = _torch()
+        if not isinstance(Z, torch.Tensor):
+            Z = np.asarray(Z)
+        if Z.ndim == 2:
+            if Z.shape[0] != self.d:
+                raise ValueError(f"logpdf: points must be (d, n) with d = {self.d}, got {tuple(Z.shape)}")
+            Z = Z.t() if isinstance(Z, torch.Tensor) else Z.T   # (n, d): row-major storage of this IS the column-major d x n
+        elif Z.ndim != 1 or Z.shape[0] % self.d:
+            raise ValueError(f"logpdf: points must be (d, n), (d,) or flat d * n with d = {self.d}, got {tuple(Z.shape)}")
+        Zd = self.to_device(Z).reshape(-1)
+        return Zd, Zd.numel() // self.d
+
+    def logpdf(self, params, Z, out=None, std=None):
+        """mivi_logpdf: log q(z_k) for the n columns of Z (see _points) as a device tensor of n values; needs no target and ignores a
+        bijector (q lives on the unconstrained scale).  std: None -- not wanted; True or a flat device tensor of d * n elements -- the
+        standardised points u = C^-1 (z - mu) are written too and (logq, u as a (d, n) view) is returned (not on the low-rank family)."""
+        p = self.to_device(params)
+        Zd, n = self._points(Z)
+        out = self.empty(n) if out is None else out
+        if std is True:
+            std = self.empty(self.d * n)
+        self._chk(self.lib.mivi_logpdf(self.h, self._p(p), self._p(Zd), n, self._p(out), self._p(std) if std is not None else None))
+        return out if std is None else (out, std.view(n, self.d).t())
+
+    def logpdf_host(self, params, Z, want_std=False):
+        """mivi_logpdf_host: numpy in, numpy out, synchronous; Z (d, n).  Returns logq (n) or (logq, u (d, n))."""
+        p = np.ascontiguousarray(params, dtype=self.np_dtype)
+        Zh = np.asfortranarray(np.asarray(Z, dtype=self.np_dtype).reshape(self.d, -1))
+        n = Zh.shape[1]
+        out = np.zeros(n, dtype=self.np_dtype)
+        stdh = np.zeros((self.d, n), dtype=self.np_dtype, order="F") if want_std else None
+        self._chk(self.lib.mivi_logpdf_host(self.h, p.ctypes.data, Zh.ctypes.data, n, out.ctypes.data, stdh.ctypes.data if want_std else None))
+        return (out, stdh) if want_std else out
+
     def estimate_gradient(self, params, idx, value=None, grad=None):
         p = self.to_device(params)
         value = self.empty(1) if value is None else value
@@ -545,6 +582,10 @@ class MiviContext:
     def batch_takes_engine(self, params):
         """True when batches of estimates at this configuration run on the batch engine (mivi_batch_info what = 0)."""
         return int(self.lib.mivi_batch_info(self.h, self._p(params), 0)) == 1
+
+    def graph_recordings(self):
+        """hipGraphs recorded into the context's graph cache so far (mivi_batch_info what = 4): unchanged across two calls = the second replayed."""
+        return int(self.lib.mivi_batch_info(self.h, None, 4))
 
     def exchange_lost(self):
         """True once a launch-free loop's grid-wide exchange was lost on this context: the loops with a per-step exchange are then not taken

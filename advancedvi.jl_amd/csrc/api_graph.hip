@@ -56,7 +56,10 @@ void GraphCache::drop() {
 mivi_status_t graph_record_fn(mivi_ctx *c, const GraphKey &key, mivi_status_t (*body)(void *), void *arg) {
   c->graph.drop();   // (the routes call invalidate_graph before whatever they prepare for a capture: nothing is cached here)
   const mivi_status_t s = capture_graph_fn(c, &c->graph.exec, body, arg);
-  if (s == MIVI_OK) c->graph.key = key;
+  if (s == MIVI_OK) {
+    c->graph.key = key;
+    ++c->graph_records;
+  }
   return s;
 }
 

@@ -364,4 +364,21 @@ __device__ void finalize_value_block(int d, const ValueIn &vin, const OutArgs &o
   }
 }
 
+// v_mfma_{f32,f64}_16x16x4: A operand lane l: A[row = l&15][k = l>>4],  B: B[k = l>>4][col = l&15],  accumulator register r of lane l:
+// row = row(l>>4, r), col = l&15 (the 16-column triangular solves: k_stl_solve_la16 in kernels_fullrank.hip, k_lp_fwd16 in kernels_logpdf.hip)
+template <typename T>
+struct Mfma16;
+template <>
+struct Mfma16<float> {
+  typedef float acc_t __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ int row(int kq, int r) { return 4 * kq + r; }
+};
+template <>
+struct Mfma16<double> {
+  typedef double acc_t __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ int row(int kq, int r) { return kq + 4 * r; }
+};
+
 }  // namespace mivi

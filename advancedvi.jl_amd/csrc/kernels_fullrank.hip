@@ -960,21 +960,6 @@ __global__ __launch_bounds__(256) void k_stl_prep(int d, int dP, const T *C, T *
 //   A operand lane l: A[row = l&15][k = l>>4],  B: B[k = l>>4][col = l&15],  D reg r: row = 4*(l>>4) + r, col = l&15
 // The same kernel serves MIVI_F64 through v_mfma_f64_16x16x4_f64: identical A / B operand shapes, only the accumulator
 // rows differ (f32: row = 4*(l>>4) + r;  f64: row = (l>>4) + 4*r).
-template <typename T>
-struct Mfma16;
-template <>
-struct Mfma16<float> {
-  typedef float acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int row(int kq, int r) { return 4 * kq + r; }
-};
-template <>
-struct Mfma16<double> {
-  typedef double acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int row(int kq, int r) { return kq + 4 * r; }
-};
-
 template <typename T, int NW>
 __global__ __launch_bounds__(NW * 64) void k_stl_solve_la16(FrArgs<T> a, const T *CT, const T *DinvT) {
   typedef typename Mfma16<T>::acc_t f32x4a;
@@ -1582,6 +1567,16 @@ void launch_stein_finish(mivi_ctx *c, double n, const double *gsum, const double
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(k_stein_finish<T>, dim3(nb), dim3(256), 0, c->stream, c->cfg.d, n, gsum, ell_sum, (const T *)ell_single, (T *)grad, (T *)logpi_avg);
+  });
+}
+
+// the inverses of the 32 x 32 diagonal blocks alone (k_stl_prep's first nb workgroups; the transposed copy is not made): DinvT[b][k + 32 i] =
+// (C_bb^-1)[i, k], what the forward solve of mivi_logpdf (kernels_logpdf.hip) multiplies with
+void launch_stl_dinv32(mivi_ctx *c, const void *params, void *DinvT) {
+  const int d = c->cfg.d, nb = (d + 31) / 32;
+  by_dtype(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_stl_prep<T>, dim3(nb), dim3(256), 0, c->stream, d, nb * 32, (const T *)params + d, (T *)nullptr, (T *)DinvT);
   });
 }
 

@@ -426,15 +426,16 @@ __global__ __launch_bounds__(256) void k_lowr_finish(int d, int r, int n_slices,
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------
 // the draws of M columns -> lowr_E; params != nullptr: also the parameter-only preparation -> lowr_prep
-void launch_lowr_draw_prep(mivi_ctx *c, const RngArgs &rng, int M, const void *params) {
+void launch_lowr_draw_prep(mivi_ctx *c, const RngArgs &rng, int M, const void *params, double *prep) {
+  if (!prep) prep = (double *)c->lowr_prep.p;
   const int d = c->cfg.d, r = c->cfg.rank;
   const long long nt = (long long)((d + r + 3) / 4) * M;
   const int with_prep = params ? 1 : 0, gram = (params && r > 4) ? 1 : 0;
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
-    if (gram) hipLaunchKernelGGL(k_lowr_gram<T>, dim3((r + 3) / 4, (r + 3) / 4), dim3(256), 0, c->stream, d, r, (const T *)params, (double *)c->lowr_prep.p);
+    if (gram) hipLaunchKernelGGL(k_lowr_gram<T>, dim3((r + 3) / 4, (r + 3) / 4), dim3(256), 0, c->stream, d, r, (const T *)params, prep);
     hipLaunchKernelGGL(k_lowr_draw_prep<T>, dim3((unsigned)((nt + 255) / 256) + with_prep), dim3(256), 0, c->stream, d, r, M, rng, (T *)c->lowr_E.p, with_prep,
-                       gram, (const T *)params, (double *)c->lowr_prep.p, (int *)c->status.p);
+                       gram, (const T *)params, prep, (int *)c->status.p);
   });
 }
 
@@ -447,21 +448,24 @@ void launch_lowr_sample(mivi_ctx *c, const void *params, int M, void *Z, bool wi
   });
 }
 
-static double *lowr_sx_part(const mivi_ctx *c, int which) {   // f64 [s (r x cap_M) | x (r x cap_M) | |t|^2 (cap_M) | log q (cap_M)]
-  const size_t r = c->cfg.rank, cap = c->cap_M;
+static double *lowr_sx_part(double *sx, size_t r, size_t cap, int which) {   // f64 [s (r x cap) | x (r x cap) | |t|^2 (cap) | log q (cap)]
   const size_t off[4] = {0, r * cap, 2 * r * cap, (2 * r + 1) * cap};
-  return (double *)c->lowr_sx.p + off[which];
+  return sx + off[which];
 }
+static double *lowr_sx_part(const mivi_ctx *c, int which) { return lowr_sx_part((double *)c->lowr_sx.p, c->cfg.rank, c->cap_M, which); }
+double *lowr_logq_of(const mivi_ctx *c, const LowrPoints &pts) { return lowr_sx_part(pts.sx, c->cfg.rank, pts.cap, 3); }
 
-// t (in lowr_V) -> s, x, log q and V = Sigma^-1 (z - m) (in lowr_V)
-void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v) {
+// t (in lowr_V, or pts->t) -> s, x, log q and V = Sigma^-1 (z - m) (over t)
+void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v, const LowrPoints *pts) {
   const int d = c->cfg.d, r = c->cfg.rank;
-  double *s = lowr_sx_part(c, 0), *x = lowr_sx_part(c, 1), *tt = lowr_sx_part(c, 2), *lq = lowr_sx_part(c, 3);
+  const LowrPoints own{c->lowr_V.p, (double *)c->lowr_prep.p, (double *)c->lowr_sx.p, (size_t)c->cap_M};
+  const LowrPoints &P = pts ? *pts : own;
+  double *s = lowr_sx_part(P.sx, r, P.cap, 0), *x = lowr_sx_part(P.sx, r, P.cap, 1), *tt = lowr_sx_part(P.sx, r, P.cap, 2), *lq = lowr_sx_part(P.sx, r, P.cap, 3);
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_lowr_s<T>, dim3((r + 3) / 4, (M + 3) / 4), dim3(256), 0, c->stream, d, r, M, (const T *)params, (const T *)c->lowr_V.p, s, tt);
+    hipLaunchKernelGGL(k_lowr_s<T>, dim3((r + 3) / 4, (M + 3) / 4), dim3(256), 0, c->stream, d, r, M, (const T *)params, (const T *)P.t, s, tt);
     hipLaunchKernelGGL((k_lowr_xv<T, 8>), dim3(want_v ? (d + 255) / 256 : 1, (M + 7) / 8), dim3(256), 0, c->stream, d, r, M, (const T *)params,
-                       (const double *)c->lowr_prep.p, (const double *)s, (const double *)tt, x, lq, want_v ? (T *)c->lowr_V.p : (T *)nullptr);
+                       (const double *)P.prep, (const double *)s, (const double *)tt, x, lq, want_v ? (T *)P.t : (T *)nullptr);
   });
 }
 

@@ -436,6 +436,10 @@ struct mivi_ctx {
   int base = MIVI_BASE_NORMAL;
   double base_nu = 0.0, base_c0 = 0.0, base_H = 0.0;   // TDist's degrees of freedom; -(constant of log phi); H(phi) -- f64, computed once on the host
   mivi::DevBuf bd_U, bd_R;   // mean-field: the draws laid out like eps (ld dP, zero padded); both families, sticking-the-landing kinds: the plane -psi(U), same layout
+  // mivi_logpdf (api_logpdf.hip, kernels_logpdf.hip): scratch of its own, so that a call between two estimates touches nothing of theirs.
+  // lp_dinv: the inverted 32 x 32 diagonal blocks (full-rank); lp_scal: f64 [sum log C_ii] (low-rank: the prep block of kernels_lowrank.hip);
+  // lp_work: the f64 X of a chunk when it does not fit LDS (full-rank), t and f64 [s; x; |t|^2; log q] of a chunk (low-rank); lp_host: [Z; log q; u] of the _host form
+  mivi::DevBuf lp_dinv, lp_scal, lp_work, lp_host;
   mivi::DevBuf dog_part;   // DoG / DoWG on large parameter vectors: 512 x 2 partial norms + the step size
   const uint64_t *idx_src = nullptr;   // mivi_set_index_source
   mivi::EpsSpec pre;   // the eps speculation across single calls
@@ -443,6 +447,7 @@ struct mivi_ctx {
   int dP = 0, MP = 0;
 
   mivi::GraphCache graph;
+  int graph_records = 0;   // graphs recorded into the cache slot so far (mivi_batch_info what = 4: a test can tell a replay from a re-capture)
   mivi::FbTables fb;   // batch engine buffers (mivi_estimate_gradient_n / _each on the third-generation route)
 
   // Interleaved chains (mivi_estimate_gradient_n, full-rank + Gaussian targets): estimates at fixed parameters are independent, so a
@@ -629,10 +634,27 @@ void launch_wass_update(mivi_ctx *c, void *params, void *state, const void *grad
 // kernels_lowrank.hip: the low-rank family's estimate (api_lowrank.hip drives it)
 size_t lowr_prep_doubles(int d, int r);                                        // f64 entries of c->lowr_prep
 int lowr_vjp_slices(int M);                                                    // slices of the sample axis the VJP leaves partials for (<= 8)
-void launch_lowr_draw_prep(mivi_ctx *c, const RngArgs &rng, int M, const void *params);   // (u1; u2) of M columns -> lowr_E; params != nullptr: A^-1, sum log D, 1/2 logdet A -> lowr_prep
+// the Woodbury stage on points that are not the context's own draws (mivi_logpdf): t (d x cap, the element type), the prep block and the
+// f64 [s; x; |t|^2; log q] block (2 r + 2) x cap, all the caller's; nullptr everywhere below: the context's lowr_V / lowr_prep / lowr_sx (cap_M)
+struct LowrPoints {
+  void *t;
+  double *prep, *sx;
+  size_t cap;
+};
+void launch_lowr_draw_prep(mivi_ctx *c, const RngArgs &rng, int M, const void *params, double *prep = nullptr);   // (u1; u2) of M columns -> lowr_E; params != nullptr: A^-1, sum log D, 1/2 logdet A -> prep (default lowr_prep); M = 0: the parameter half alone
 void launch_lowr_sample(mivi_ctx *c, const void *params, int M, void *Z, bool with_t);   // Z = D o u1 + U u2 + m (with_t: t = u1 + D^-1 U u2 -> lowr_V)
-void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v);   // t -> s, x, log q (want_v: V over t)
+void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v, const LowrPoints *pts = nullptr);   // t -> s, x, log q (want_v: V over t)
+double *lowr_logq_of(const mivi_ctx *c, const LowrPoints &pts);   // where launch_lowr_woodbury leaves the f64 log q of pts' columns
 void launch_lowr_vjp_finish(mivi_ctx *c, const void *params, int M, int want_grad, const ValueIn &vin, const OutArgs &out);   // W = G (and V, x, the draws) -> out.grad; out.value, the non-finite flag, the elbo record
+
+// kernels_logpdf.hip: logpdf(q, z) at the caller's points (api_logpdf.hip drives them); n <= kSampleChunk columns per launch
+void launch_stl_dinv32(mivi_ctx *c, const void *params, void *DinvT);   // kernels_fullrank.hip: k_stl_prep's diagonal workgroups alone
+void launch_lp_logdet(mivi_ctx *c, const void *params, double *scal);   // scal[0] = sum log C_ii (f64); the non-positive-scale flag
+void launch_lp_mf(mivi_ctx *c, const void *params, const void *Z, int n, void *logq, void *std, const double *scal);
+bool lp_fwd_x_in_lds(const mivi_ctx *c);   // 16 f64 columns of X fit LDS beside the solve's partials (otherwise X lives in xg, f64 d x n)
+void launch_lp_fwd(mivi_ctx *c, const void *params, const void *Z, int n, const void *Dinv, void *logq, void *std, double *xg, const double *scal);
+void launch_lp_lowr_t(mivi_ctx *c, const void *params, const void *Z, int n, void *tbuf);   // t = D^-1 (z - m)
+void launch_lp_store(mivi_ctx *c, int n, const double *lq, void *logq);
 
 // kernels_basedist.hip: the draw stage and the mean-field kernels of a non-normal base (api_basedist.hip drives them)
 void launch_bd_draw(mivi_ctx *c, const RngArgs &rng, int M, void *U, void *UT, void *R);   // U (ld dP), UT (ld MP; or nullptr), R = -psi(U) (ld dP; or nullptr); he_part[cur]: eps_blocks partials of the variable part of -sum log phi(u)

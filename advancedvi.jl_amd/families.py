@@ -190,6 +190,12 @@ class MvLocationScaleLowRank:
         return self.location.dtype
 
     # host statistics with the base distribution Normal(0, 1): location_scale_low_rank.jl:102-121
+    def entropy(self):   # location_scale_low_rank.jl:35-43: d H(Normal) + (2 sum log D + logdet(I + U' D^-2 U)) / 2
+        D, U = self.scale_diag, self.scale_factors
+        UtDinvU = U.T @ (U / (D * D)[:, None])
+        logdet_sigma = 2.0 * np.log(D).sum() + np.linalg.slogdet(np.eye(self.rank, dtype=self.eltype) + UtDinvU)[1]
+        return self.eltype.type(len(self) * self.eltype.type(Normal().entropy()) + logdet_sigma / 2.0)
+
     def mean(self):
         return self.location.copy()   # mean(dist) = 0: the scale terms of :105-107 vanish
 

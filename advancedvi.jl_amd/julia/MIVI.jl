@@ -11,7 +11,7 @@
 module MIVI
 
 using AdvancedVI, ADTypes, AbstractPPL, DiffResults, LogDensityProblems, Optimisers, Random, LinearAlgebra
-using Distributions: Normal, Laplace, TDist
+using Distributions: Distributions, Normal, Laplace, TDist
 using AdvancedVI: MvLocationScale, RepGradELBO, ScoreGradELBO, KLMinRepGradDescent, ClosedFormEntropy, ClosedFormEntropyZeroGradient,
                   MonteCarloEntropy, StickingTheLandingEntropy, StickingTheLandingEntropyZeroGradient
 
@@ -168,6 +168,38 @@ function AdvancedVI.estimate_objective(rng::Random.AbstractRNG, obj::RepGradELBO
     check(st.ctx, ccall((:mivi_estimate_objective_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, UInt64, Int32, Int32, Ref{T}),
                         st.ctx, params, UInt64(0), n_samples, entropy_code(obj.entropy), value))
     return value[]
+end
+
+# ---- Distributions.logpdf(q, z) on the device (location_scale.jl:59-63, location_scale_low_rank.jl:45-68) --------------------------------
+# logpdf(ad, q, z): z a vector (d) -> one value, z a matrix (d x n) -> n values in eltype(q).  The points are the caller's; no target, no
+# RNG.  `q` lives on the unconstrained scale (a bijector wraps the target, not q).  A non-positive scale diagonal throws the DomainError
+# `logdet` would.  The device form mivi_logpdf (device pointers, asynchronous, optional standardised points) is logpdf_dev!.
+function Distributions.logpdf(ad::AutoMIVI, q::RepGradFamily, z::AbstractVecOrMat{<:Real})
+    params, _ = Optimisers.destructure(q)
+    T = eltype(params)
+    d = length(q)
+    size(z, 1) == d || throw(DimensionMismatch("logpdf: z has $(size(z, 1)) rows, q has dimension $d"))
+    cfg = Ref(MiviConfig(dtype_code(T), family_code(q), d, 1, Int32(0), ad.device, UInt64(0), 0, 0, C_NULL, 1, family_rank(q)))
+    ctx = Ref{Ptr{Cvoid}}(C_NULL)
+    status = ccall((:mivi_create, libmivi), Int32, (Ref{MiviConfig}, Ref{Ptr{Cvoid}}), cfg, ctx)
+    status == 0 || error("mivi_create failed with status $status (no HIP device?)")
+    try
+        base, nu = base_code(q)
+        check(ctx[], ccall((:mivi_set_base_dist, libmivi), Int32, (Ptr{Cvoid}, Int32, Float64), ctx[], base, nu))
+        Z = Matrix{T}(reshape(z, d, :))
+        logq = Vector{T}(undef, size(Z, 2))
+        check(ctx[], ccall((:mivi_logpdf_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, Ptr{T}, Int64, Ptr{T}, Ptr{Cvoid}),
+                           ctx[], params, Z, size(Z, 2), logq, C_NULL))
+        return z isa AbstractVector ? logq[1] : logq
+    finally
+        ccall((:mivi_destroy, libmivi), Int32, (Ptr{Cvoid},), ctx[])
+    end
+end
+
+function logpdf_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, z_dev::Ptr{Cvoid}, n::Integer, logq_dev::Ptr{Cvoid}, std_dev::Ptr{Cvoid}=C_NULL)
+    check(state.ctx, ccall((:mivi_logpdf, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                           state.ctx, params_dev, z_dev, n, logq_dev, std_dev))
+    return nothing
 end
 
 # ---- ScoreGradELBO (src/algorithms/scoregradelbo.jl; KLMinScoreGradDescent = BBVI, src/algorithms/constructors.jl:199-233) ----------
@@ -726,5 +758,5 @@ end
 # ProximalLocationScaleEntropy on the host arrays works unchanged (src/optimization/proximal_location_scale_entropy.jl);
 # the device-resident variant for a parameter vector that lives in HBM is mivi_prox_scale_entropy.
 
-export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!, bam_moments!, estimate_fisher, bam_update!, bam_init_dev!, bam_moments_dev!, estimate_fisher_dev!, bam_update_dev!, bam_steps!, wass_update!, wass_init_dev!, wass_update_dev!, wass_steps!
+export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, logpdf_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!, bam_moments!, estimate_fisher, bam_update!, bam_init_dev!, bam_moments_dev!, estimate_fisher_dev!, bam_update_dev!, bam_steps!, wass_update!, wass_init_dev!, wass_update_dev!, wass_steps!
 end # module

@@ -289,6 +289,24 @@ def rand(rng, q, num_samples: int, device: int = 0):
         ctx.close()
 
 
+def logpdf(q, z, device: int = 0):
+    """logpdf(q, z): Distributions.logpdf of the variational family at the caller's points (location_scale.jl:59-63,
+    location_scale_low_rank.jl:45-68) -- MvLocationScale with a diagonal or triangular scale and any `dist`, MvLocationScaleLowRank.
+    z of shape (d,): a Python float.  z of shape (d, n), numpy or device tensor: a device tensor of n values in q.eltype."""
+    ctx = MiviContext(q.eltype, q.family, len(q), 1, 0, 0, device=device, rank=getattr(q, "rank", 0))
+    try:
+        ctx.set_base_dist(getattr(q, "dist", None))
+        params, _ = destructure(q)
+        single = getattr(z, "ndim", None) == 1 or (not hasattr(z, "ndim") and np.ndim(z) == 1)
+        if single and len(z) != len(q):
+            raise ValueError(f"logpdf: z has {len(z)} entries, q has dimension {len(q)}")
+        out = ctx.logpdf(params, z)
+        ctx.synchronize()   # (a non-positive scale diagonal raises here, like the reference's DomainError)
+        return float(out.item()) if single else out
+    finally:
+        ctx.close()
+
+
 def gaussian_expectation_gradient_and_hessian_(rng, q: MvLocationScale, n_samples: int, grad_buf, hess_buf, prob,
                                                adtype=None, _ctx=None):
     """`gaussian_expectation_gradient_and_hessian!(rng, q, n_samples, grad_buf, hess_buf, prob)`:

@@ -56,7 +56,7 @@ typedef enum { MIVI_F32 = 0, MIVI_F64 = 1 } mivi_dtype_t;
 /* MeanFieldGaussian / FullRankGaussian: src/families/location_scale.jl:139-141 / :124-128;
  * LowRankGaussian: src/families/location_scale_low_rank.jl:140-145 -- z = scale_diag .* u1 + scale_factors * u2 + location, rank =
  * cfg.rank columns of factors.  What family 2 supports: create / destroy / synchronize / set_stream / params_len, every mivi_set_target_*
- * and mivi_set_bijector_stacked, mivi_sample (eps_dev: T[(d + rank) * n_mc]), mivi_estimate_gradient[_host / _n / _each] (the batched
+ * and mivi_set_bijector_stacked, mivi_sample (eps_dev: T[(d + rank) * n_mc]), mivi_logpdf[_host] (std NULL), mivi_estimate_gradient[_host / _n / _each] (the batched
  * forms as sequential single calls), mivi_estimate_objective[_host], mivi_clip_scale / _descent_update / _adam_update / _cocob_update /
  * the DoG entries, and mivi_optimize_steps / _loop as a graph of launches (op 0 or 1).  Every other entry that reads parameters returns
  * MIVI_ERR_UNSUPPORTED on it (the score-gradient and measure-space entries, partials / finalize / dist / p2p, the profile entries,
@@ -128,7 +128,7 @@ int64_t mivi_partials_len(const mivi_ctx_t *ctx);
  * MIVI_BASE_NORMAL is a no-op in effect: such a context gives bitwise the results of one that never called this, on every route.
  * MIVI_ERR_BAD_ARG: an unknown base, nu <= 0 or not finite.  MIVI_ERR_UNSUPPORTED for a non-normal base on a MIVI_LOWRANK context or a
  * sharded one (m_offset != 0 or m_total not in {0, n_mc}).  Invalidates captured graphs, like mivi_set_target_*.
- * What a non-normal base supports (both families, both precisions): mivi_sample, mivi_estimate_gradient[_host / _n / _each] (the batched
+ * What a non-normal base supports (both families, both precisions): mivi_sample, mivi_logpdf[_host], mivi_estimate_gradient[_host / _n / _each] (the batched
  * forms as sequential single calls, bitwise equal to them), mivi_estimate_objective[_host] (any n_samples, all five entropy kinds), every
  * mivi_set_target_* incl. the gradient callback, mivi_set_bijector_stacked, the update entries (clip, descent, adam, cocob, DoG / DoWG,
  * mivi_prox_scale_entropy, mivi_axpby) and mivi_optimize_steps / _loop as the graph of launches with every rule, operator and averager.
@@ -201,6 +201,29 @@ mivi_status_t mivi_set_target_value_callback(mivi_ctx_t *ctx, mivi_logdensity_fn
  * column m = (u1 (d); u2 (rank)) of sample m. */
 mivi_status_t mivi_sample(mivi_ctx_t *ctx, const void *params_dev, uint64_t estimate_idx,
                           void *Z_dev, void *eps_dev);
+
+/* Distributions.logpdf(q, z) for the n columns of Z, points the CALLER supplies: src/families/location_scale.jl:59-63,
+ * src/families/location_scale_low_rank.jl:45-68 (checked by test/families/location_scale.jl:38-42, location_scale_low_rank.jl:37-46).
+ *   Z_dev    T[d*n], d x n column-major with leading dimension d -- the layout mivi_sample writes.  n >= 1 is independent of cfg.n_mc
+ *            (columns are walked 16384 at a time); n > 2^31 - 16385: MIVI_ERR_BAD_ARG.
+ *   logq_dev T[n] <- logq[k] = sum_i log phi(u_ik) - log det C with u_k = C^-1 (z_k - mu) and phi the context's base (mivi_set_base_dist:
+ *            Normal, Laplace, TDist(nu)); the sums over i are accumulated in f64.  Low-rank family (Gaussian only): the Woodbury form
+ *            -d/2 log 2 pi - sum log D - 1/2 logdet(I + U' D^-2 U) - 1/2 (|t|^2 - s' (I + U' D^-2 U)^-1 s), t = D^-1 (z - m), s = U' D^-1 t.
+ *   std_dev  T[d*n] or NULL <- u, the standardised points (the residuals of z under q), same layout as Z.  The low-rank family has no
+ *            square scale to standardise by: a non-NULL std_dev returns MIVI_ERR_UNSUPPORTED there, before any buffer is read.
+ * Mean-field: one streaming kernel.  Full-rank: a forward block substitution C X = Z - mu on the matrix cores
+ * (kernels_logpdf.hip: f32 operands, exact products, every sum and X itself in f64), for EVERY d mivi_create admits -- X stays in LDS
+ * while 16 columns of it fit and in an f64 scratch of min(n, 16384) columns past that; there is no size at which the entry refuses.
+ * q lives on the unconstrained scale: a Stacked bijector (mivi_set_bijector_stacked) wraps the TARGET and is ignored here, and no
+ * target is needed.  Allowed on sharded contexts (nothing of the estimate's sample axis is involved).  Asynchronous on the context's
+ * stream.  The call works in scratch of its own and leaves the context as it found it: cached graphs stay valid, the eps speculation
+ * and every estimate buffer are untouched, so the estimates before and after it are bitwise those of a context that never called it.
+ * MIVI_ERR_BAD_ARG: params_dev, Z_dev or logq_dev NULL; n < 1.  A scale diagonal that is not positive sets the sticky device flag
+ * (MIVI_ERR_NONPOSITIVE_SCALE from mivi_synchronize), like the estimates.  A non-finite point gives a non-finite logq[k] for that column
+ * only and sets no flag: it is the caller's data, not the iterate's state. */
+mivi_status_t mivi_logpdf(mivi_ctx_t *ctx, const void *params_dev, const void *Z_dev, int64_t n, void *logq_dev, void *std_dev);
+/* Same, host buffers, synchronous; returns MIVI_ERR_NONPOSITIVE_SCALE itself. */
+mivi_status_t mivi_logpdf_host(mivi_ctx_t *ctx, const void *params_host, const void *Z_host, int64_t n, void *logq_host, void *std_host);
 
 /* estimate_gradient!(rng, obj::RepGradELBO, adtype, out, state, params, restructure):
  * src/algorithms/repgradelbo.jl:151-177 (+ the AD shim src/AdvancedVI.jl:57-67 it replaces).
@@ -628,7 +651,8 @@ int32_t mivi_batch_lanes(const mivi_ctx_t *ctx, int32_t count);
  * `estimate_gradient!` there is one AD call, src/algorithms/repgradelbo.jl:151-177).  what = 0: 1 when mivi_estimate_gradient_n / _each with
  * these (16-byte aligned) device parameters take the batch engine, 0 otherwise; 1: matrix-pipe products per 32 x 32 x 16 block of the engine's
  * split-operand contractions (3: f16 hi / lo planes); 2: bytes per operand-plane element (4); 3: 1 once a launch-free optimisation loop's grid-wide
- * exchange was lost on this context (mivi_optimize_loop then restored the caller's state, re-ran the steps on the graph of launches and stays there). */
+ * exchange was lost on this context (mivi_optimize_loop then restored the caller's state, re-ran the steps on the graph of launches and stays there);
+ * 4: the number of hipGraphs recorded into the context's graph cache so far -- unchanged across two calls means the second one replayed. */
 int32_t mivi_batch_info(const mivi_ctx_t *ctx, const void *params_dev, int32_t what);
 
 /* ---- measurement hook (bench.py roofline leg) --------------------------------------------------------- *
