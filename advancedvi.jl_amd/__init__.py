@@ -10,7 +10,7 @@ from .problems import (LogDensityOrder, DiagNormalProblem, DenseNormalProblem, L
                        dimension, capabilities)
 from .objectives import (RepGradELBO, RepGradELBOState, ScoreGradELBO, ScoreGradELBOState, ClosedFormEntropy, ClosedFormEntropyZeroGradient,
                          MonteCarloEntropy, StickingTheLandingEntropy, StickingTheLandingEntropyZeroGradient,
-                         AutoMIVI, PhiloxRNG, DiffResult, set_objective_state_problem, rand, logpdf,
+                         AutoMIVI, PhiloxRNG, DiffResult, set_objective_state_problem, rand, logpdf, TransformedDistribution,
                          gaussian_expectation_gradient_and_hessian_)
 from . import objectives as _objectives
 from . import optimize as _optimize

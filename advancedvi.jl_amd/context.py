@@ -154,13 +154,18 @@ class MiviContext:
         self._chk(self.lib.mivi_set_base_dist(self.h, code, nu))
 
     def set_bijector(self, bij):
-        """mivi_set_bijector_stacked: a P.StackedBijector around whatever target is set (None removes it)."""
+        """mivi_set_bijector_stacked: a P.StackedBijector around whatever target is set (None removes it); one with a truncated or an
+        ordered block goes through mivi_set_bijector_stacked_ex."""
         if bij is None:
             self._chk(self.lib.mivi_set_bijector_stacked(self.h, 0, None, None))
             return
         rng = np.ascontiguousarray([[lo, hi] for lo, hi, _ in bij.blocks], dtype=np.int32)
         kinds = np.ascontiguousarray([P.StackedBijector.KINDS[k] for _, _, k in bij.blocks], dtype=np.int32)
-        self._chk(self.lib.mivi_set_bijector_stacked(self.h, len(bij.blocks), rng.ctypes.data, kinds.ctypes.data))
+        if bij.is_legacy:
+            self._chk(self.lib.mivi_set_bijector_stacked(self.h, len(bij.blocks), rng.ctypes.data, kinds.ctypes.data))
+            return
+        bounds = np.ascontiguousarray(bij.bounds, dtype=np.float64).reshape(-1)   # truncated / ordered blocks: the _ex entry
+        self._chk(self.lib.mivi_set_bijector_stacked_ex(self.h, len(bij.blocks), rng.ctypes.data, kinds.ctypes.data, bounds.ctypes.data))
 
     def _set_callback(self, prob, values_only=False):
         has_grad = hasattr(prob, "logdensity_and_gradient") or hasattr(prob, "logdensity_and_gradient_batch")
@@ -290,6 +295,34 @@ class MiviContext:
         stdh = np.zeros((self.d, n), dtype=self.np_dtype, order="F") if want_std else None
         self._chk(self.lib.mivi_logpdf_host(self.h, p.ctypes.data, Zh.ctypes.data, n, out.ctypes.data, stdh.ctypes.data if want_std else None))
         return (out, stdh) if want_std else out
+
+    def sample_constrained(self, params, idx, want_eta=False):
+        """mivi_sample_constrained: X = binv(z) for the draws z `sample` returns at `idx`, pushed through the bijector that is set, as a
+        (d, n_mc) view; want_eta: (X, z)."""
+        p = self.to_device(params)
+        X = self.empty(self.d * self.n_mc)
+        eta = self.empty(self.d * self.n_mc) if want_eta else None
+        self._chk(self.lib.mivi_sample_constrained(self.h, self._p(p), idx, self._p(X), self._p(eta) if want_eta else None))
+        Xv = X.view(self.n_mc, self.d).t()
+        return (Xv, eta.view(self.n_mc, self.d).t()) if want_eta else Xv
+
+    def logpdf_constrained(self, params, X, out=None):
+        """mivi_logpdf_constrained: logpdf of the transformed distribution at the n constrained points X (see _points): log q(b(x)) -
+        logabsdetjac(binv, b(x)) as a device tensor of n values; -inf outside the support, NaN for a NaN point."""
+        p = self.to_device(params)
+        Xd, n = self._points(X)
+        out = self.empty(n) if out is None else out
+        self._chk(self.lib.mivi_logpdf_constrained(self.h, self._p(p), self._p(Xd), n, self._p(out)))
+        return out
+
+    def logpdf_constrained_host(self, params, X):
+        """mivi_logpdf_constrained_host: numpy in, numpy out, synchronous; X (d, n)."""
+        p = np.ascontiguousarray(params, dtype=self.np_dtype)
+        Xh = np.asfortranarray(np.asarray(X, dtype=self.np_dtype).reshape(self.d, -1))
+        n = Xh.shape[1]
+        out = np.zeros(n, dtype=self.np_dtype)
+        self._chk(self.lib.mivi_logpdf_constrained_host(self.h, p.ctypes.data, Xh.ctypes.data, n, out.ctypes.data))
+        return out
 
     def estimate_gradient(self, params, idx, value=None, grad=None):
         p = self.to_device(params)

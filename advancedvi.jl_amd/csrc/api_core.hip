@@ -117,6 +117,7 @@ mivi_status_t ensure_work(mivi_ctx *c, int M) {
     if ((s = ensure(c, c->W, (size_t)d * capM * es, false))) return s;
     if ((s = ensure(c, c->ell, (size_t)capM * es, false))) return s;
     if (c->bij_on && (s = ensure(c, c->bij_ld, (size_t)capM * es, false))) return s;
+    if (c->bij_on && c->bij_ext && (s = ensure(c, c->bij_eta, (size_t)d * capM * es, false))) return s;   // eta for the backward pass
     if ((s = ensure(c, c->row_part, ncc * d4 * 8 * sizeof(double), false))) return s;
     c->cap_M = capM;
   }
@@ -201,7 +202,7 @@ mivi_status_t mivi_destroy(mivi_ctx_t *c) {
   DevBuf *bufs[] = {&c->t_mean, &c->t_istd, &c->t_prec, &c->lr_X_own, &c->lr_y_own, &c->lr_scratch, &c->lr_part, &c->lr_Xrm,
                     &c->eps[0], &c->eps[1], &c->epsT[0], &c->epsT[1], &c->Z, &c->W, &c->RT, &c->ell, &c->X,
                     &c->ell_part[0], &c->ell_part[1], &c->he_part[0], &c->he_part[1], &c->row_part,
-                    &c->sc_part[0], &c->sc_part[1], &c->ld_part[0], &c->ld_part[1], &c->tabA, &c->tabB, &c->tabD, &c->stl_CT, &c->stl_Dinv, &c->stl_X, &c->stl_F, &c->lr_xmax, &c->lr_XA, &c->lr_XB, &c->lr_ZP, &c->lr_Xsub, &c->lr_ysub, &c->lr_Xrm_sub, &c->lr_idx, &c->dog_part, &c->stein_A, &c->stein_g, &c->h2_acc, &c->sg_S, &c->sg_d, &c->bij_mask, &c->bij_ld, &c->dist_P, &c->dist_P2, &c->dist_ring[0], &c->dist_ring[1], &c->dist_ring[2], &c->dist_ring[3], &c->dist_ring[4], &c->dist_ring[5], &c->p2p_scratch, &c->dist_S, &c->dist_F, &c->p2p_tab, &c->p2p_ctr, &c->lds_tabV, &c->lds_tabV64, &c->lds_tabS, &c->lds_tabSt, &c->status, &c->d_idx, &c->acc, &c->tmp_params, &c->tmp_out, &c->obj_vals, &c->lowr_E, &c->lowr_V, &c->lowr_prep, &c->lowr_sx, &c->lowr_part, &c->bd_U, &c->bd_R, &c->lp_dinv, &c->lp_scal, &c->lp_work, &c->lp_host};
+                    &c->sc_part[0], &c->sc_part[1], &c->ld_part[0], &c->ld_part[1], &c->tabA, &c->tabB, &c->tabD, &c->stl_CT, &c->stl_Dinv, &c->stl_X, &c->stl_F, &c->lr_xmax, &c->lr_XA, &c->lr_XB, &c->lr_ZP, &c->lr_Xsub, &c->lr_ysub, &c->lr_Xrm_sub, &c->lr_idx, &c->dog_part, &c->stein_A, &c->stein_g, &c->h2_acc, &c->sg_S, &c->sg_d, &c->bij_mask, &c->bij_ld, &c->bij_code, &c->bij_bnd, &c->bij_eta, &c->bij_scr, &c->dist_P, &c->dist_P2, &c->dist_ring[0], &c->dist_ring[1], &c->dist_ring[2], &c->dist_ring[3], &c->dist_ring[4], &c->dist_ring[5], &c->p2p_scratch, &c->dist_S, &c->dist_F, &c->p2p_tab, &c->p2p_ctr, &c->lds_tabV, &c->lds_tabV64, &c->lds_tabS, &c->lds_tabSt, &c->status, &c->d_idx, &c->acc, &c->tmp_params, &c->tmp_out, &c->obj_vals, &c->lowr_E, &c->lowr_V, &c->lowr_prep, &c->lowr_sx, &c->lowr_part, &c->bd_U, &c->bd_R, &c->lp_dinv, &c->lp_scal, &c->lp_work, &c->lp_host};
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   {
@@ -423,6 +424,9 @@ mivi_status_t mivi_set_bijector_stacked(mivi_ctx_t *c, int32_t n_blocks, const i
   }
   invalidate_graph(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));   // an estimate in flight may still read the old mask
+  c->bij_ext = c->bij_ord = c->bij_tab = false;   // (the description the constrained rand / logpdf entries upload on first use: exp = lb 0)
+  c->bij_code_h = mask;
+  c->bij_bnd_h.assign(2 * (size_t)d, 0.0);
   if (!any) {   // all-identity (or no) bijector: nothing to apply
     c->bij_on = false;
     return MIVI_OK;

@@ -8,8 +8,20 @@
 // eps speculation, the buffer parity nor a cached graph: estimates around it are bitwise what they are without it.
 #include "api_common.h"
 
+// the points of chunk k: the caller's, or -- mivi_logpdf_constrained -- eta = b(x) of the caller's constrained points, left in the hook's scratch
+static const char *chunk_points(mivi_ctx *c, const SampleChunk &k, const char *Z, const LogpdfBij *bij) {
+  const size_t off = (size_t)k.off * c->cfg.d * c->esize;
+  if (!bij) return Z + off;
+  launch_bijx_inverse(c, k.Mc, bij->X + off, bij->eta, bij->ladj, bij->flag);
+  return bij->eta;
+}
+// ... and what follows its density: logq <- logq - ladj, or -inf / NaN by the column's flag
+static void chunk_finish(mivi_ctx *c, const SampleChunk &k, char *logq, const LogpdfBij *bij) {
+  if (bij) launch_bijx_finish(c, k.Mc, logq + (size_t)k.off * c->esize, bij->ladj, bij->flag);
+}
+
 // the launches of one call: the parameter-only stage once, then the columns kSampleChunk at a time
-static mivi_status_t logpdf_launches(mivi_ctx *c, const void *params, const char *Z, int n, char *logq, char *std) {
+mivi_status_t logpdf_launches(mivi_ctx *c, const void *params, const char *Z, int n, char *logq, char *std, const LogpdfBij *bij) {
   const size_t d = c->cfg.d, es = c->esize;
   const int cap = n < kSampleChunk ? n : kSampleChunk;
   mivi_status_t s;
@@ -21,9 +33,10 @@ static mivi_status_t logpdf_launches(mivi_ctx *c, const void *params, const char
     const LowrPoints pts{c->lp_work.p, (double *)c->lp_scal.p, (double *)((char *)c->lp_work.p + t_bytes), (size_t)cap};
     launch_lowr_draw_prep(c, rng_of(c, 0), 0, params, pts.prep);   // the parameter half alone: A^-1, sum log D, 1/2 logdet A, the scale flag
     return for_each_chunk(c, 0, n, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
-      launch_lp_lowr_t(c, params, Z + (size_t)k.off * d * es, k.Mc, pts.t);
+      launch_lp_lowr_t(c, params, chunk_points(c, k, Z, bij), k.Mc, pts.t);
       launch_lowr_woodbury(c, params, k.Mc, false, &pts);
       launch_lp_store(c, k.Mc, lowr_logq_of(c, pts), logq + (size_t)k.off * es);
+      chunk_finish(c, k, logq, bij);
       return MIVI_OK;
     });
   }
@@ -32,7 +45,8 @@ static mivi_status_t logpdf_launches(mivi_ctx *c, const void *params, const char
   if (c->cfg.family == MIVI_MEANFIELD) {
     launch_lp_logdet(c, params, scal);
     return for_each_chunk(c, 0, n, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
-      launch_lp_mf(c, params, Z + (size_t)k.off * d * es, k.Mc, logq + (size_t)k.off * es, std ? std + (size_t)k.off * d * es : nullptr, scal);
+      launch_lp_mf(c, params, chunk_points(c, k, Z, bij), k.Mc, logq + (size_t)k.off * es, std ? std + (size_t)k.off * d * es : nullptr, scal);
+      chunk_finish(c, k, logq, bij);
       return MIVI_OK;
     });
   }
@@ -42,8 +56,9 @@ static mivi_status_t logpdf_launches(mivi_ctx *c, const void *params, const char
   launch_stl_dinv32(c, params, c->lp_dinv.p);
   launch_lp_logdet(c, params, scal);
   return for_each_chunk(c, 0, n, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
-    launch_lp_fwd(c, params, Z + (size_t)k.off * d * es, k.Mc, c->lp_dinv.p, logq + (size_t)k.off * es, std ? std + (size_t)k.off * d * es : nullptr,
+    launch_lp_fwd(c, params, chunk_points(c, k, Z, bij), k.Mc, c->lp_dinv.p, logq + (size_t)k.off * es, std ? std + (size_t)k.off * d * es : nullptr,
                   need_xg ? (double *)c->lp_work.p : nullptr, scal);
+    chunk_finish(c, k, logq, bij);
     return MIVI_OK;
   });
 }
@@ -55,7 +70,7 @@ mivi_status_t mivi_logpdf(mivi_ctx_t *c, const void *params, const void *Z, int6
   if (std)
     if (mivi_status_t rs = refuse_lowrank(c, "mivi_logpdf with std_dev (the family has no square scale to standardise by)")) return rs;
   (void)hipSetDevice(c->cfg.device);
-  if (mivi_status_t s = logpdf_launches(c, params, (const char *)Z, (int)n, (char *)logq, (char *)std)) return s;
+  if (mivi_status_t s = logpdf_launches(c, params, (const char *)Z, (int)n, (char *)logq, (char *)std, nullptr)) return s;
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
 }

@@ -109,12 +109,14 @@ __global__ __launch_bounds__(256) void k_bij_bwd(int d, const uint8_t *mask, con
   if (ell && tid == 0) ell[m] += ld[m];
 }
 void launch_bij_forward(mivi_ctx *c, int M) {
+  if (c->bij_ext) return launch_bijx_forward(c, M, c->Z.p, c->bij_eta.p, c->bij_ld.p);   // truncated / ordered blocks: kernels_bijector.hip
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(k_bij_fwd<T>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const uint8_t *)c->bij_mask.p, (T *)c->Z.p, (T *)c->bij_ld.p);
   });
 }
 void launch_bij_backward(mivi_ctx *c, int M, int want_grad, bool add_to_ell) {
+  if (c->bij_ext) return launch_bijx_backward(c, M, want_grad, add_to_ell);
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(k_bij_bwd<T>, dim3(M), dim3(256), 0, c->stream, c->cfg.d, (const uint8_t *)c->bij_mask.p, (const T *)c->Z.p, (T *)c->W.p,

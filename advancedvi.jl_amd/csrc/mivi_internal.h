@@ -33,6 +33,17 @@ enum TargetKind : int {
   TGT_CALLBACK = 5
 };
 
+// What the Stacked bijector does to one coordinate (kernels_bijector.hip).  The legacy mask of mivi_set_bijector_stacked holds 0 / 1:
+// its exp kind IS BIJ_LOWER with lb = 0.
+enum BijCode : int {
+  BIJ_ID = 0,
+  BIJ_LOWER = 1,      // x = lb + e^eta
+  BIJ_UPPER = 2,      // x = ub - e^eta
+  BIJ_BOTH = 3,       // x = lb + (ub - lb) sigma(eta)
+  BIJ_ORD_HEAD = 4,   // first coordinate of an ordered block: x = eta
+  BIJ_ORD = 5         // x_k = x_{k-1} + e^eta_k
+};
+
 // Fused funnel target (mean-field): the only cross-row coupling of Neal's funnel is S_m = sum_i x_im^2 per sample, needed by
 // row 0's gradient and by ell -- and every use of it is LINEAR in S_m with a per-column weight any workgroup can re-derive
 // from the eps stream (exp(-2 e1_m), exp(-2 e1_m) eps_0m).  So the main kernel's workgroups (rows >= 1) leave two scalar
@@ -343,6 +354,15 @@ struct mivi_ctx {
   int funnel_constrained = 0;
   // Stacked bijector (mivi_set_bijector_stacked): per-coordinate kind (0 identity, 1 exp) and per-column sum of eta over exp rows
   mivi::DevBuf bij_mask, bij_ld;
+  // ... and its extended form (mivi_set_bijector_stacked_ex, kernels_bijector.hip): the host description per coordinate (BijCode; lb, ub),
+  // its device copy (uploaded by the _ex setter, or on the first constrained rand / logpdf behind the legacy setter), the eta the backward
+  // pass reads (d x cap_M, only with bij_ext) and the scratch of mivi_logpdf_constrained
+  std::vector<uint8_t> bij_code_h;
+  std::vector<double> bij_bnd_h;
+  mivi::DevBuf bij_code, bij_bnd, bij_eta, bij_scr;
+  bool bij_ext = false;   // a truncated / ordered block is present: launch_bij_forward / _backward take the kernels of kernels_bijector.hip
+  bool bij_ord = false;   // ... an ordered one: the segmented scan runs
+  bool bij_tab = false;   // bij_code / bij_bnd on the device match the host description
   // collective behind the C ABI (mivi_comm_init): RCCL communicator + padded partial / packed-final buffers
   void *comm = nullptr;
   int comm_rank = 0, comm_world = 1;
@@ -587,6 +607,12 @@ void launch_stl2(mivi_ctx *c, const void *params, int M, bool dinv_done = false,
 void launch_col_target(mivi_ctx *c, int M, int want_grad);
 void launch_bij_forward(mivi_ctx *c, int M);                        // Z <- binv(Z) in place, bij_ld[m] = sum_exp eta
 void launch_bij_backward(mivi_ctx *c, int M, int want_grad, bool add_to_ell);   // G <- J' G + 1_exp; ell[m] += bij_ld[m]
+// kernels_bijector.hip: the same two steps with truncated / ordered blocks (what the two launchers above take when c->bij_ext), and the
+// inverse direction of mivi_logpdf_constrained
+void launch_bijx_forward(mivi_ctx *c, int M, void *Z, void *save, void *ld);   // Z <- binv(Z) in place; save (or NULL) <- eta; ld (or NULL) <- ladj
+void launch_bijx_backward(mivi_ctx *c, int M, int want_grad, bool add_to_ell);
+void launch_bijx_inverse(mivi_ctx *c, int n, const void *X, void *eta, double *ladj, int *flag);   // eta <- b(X); flag: 1 outside the support, 2 NaN
+void launch_bijx_finish(mivi_ctx *c, int n, void *logq, const double *ladj, const int *flag);     // logq <- logq - ladj, or -inf / NaN by flag
 bool launch_logreg_target(mivi_ctx *c, int M, int want_grad);   // false: scratch allocation failed
 int logreg_kernel_bits(const mivi_ctx *c, int M);         // mivi_logreg_kernels
 bool logreg_uses_mfma(const mivi_ctx *c, int M);          // the matrix-core route (needs Z^T staged in RT)

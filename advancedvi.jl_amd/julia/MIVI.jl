@@ -708,6 +708,44 @@ function set_bijector!(state::MIVIState, ranges::Vector{UnitRange{Int}}, kinds::
     return state
 end
 
+# Bounded and ordered supports (mivi_set_bijector_stacked_ex): kinds[i] may also be :truncated -- bounds[i] = (lb, ub), either of which may
+# be infinite: what Bijectors.bijector(Uniform(..)), (Beta(..)), (truncated(d, lb, ub)) attach -- or :ordered (Bijectors.OrderedBijector:
+# x_1 = eta_1, x_k = x_{k-1} + exp(eta_k)).  bounds[i] is ignored for the other kinds.  Dimension-changing maps (simplex, Cholesky
+# factors) are not supported: target and family share one dimension.
+const BIJECTOR_KINDS = Dict(:identity => Int32(0), :exp => Int32(1), :truncated => Int32(2), :ordered => Int32(3))
+function set_bijector!(state::MIVIState, ranges::Vector{UnitRange{Int}}, kinds::Vector{Symbol}, bounds::Vector{<:Tuple{Real,Real}})
+    length(bounds) == length(kinds) == length(ranges) || throw(ArgumentError("set_bijector!: ranges, kinds and bounds must have one entry per block"))
+    r = Int32[]
+    for rg in ranges
+        push!(r, Int32(first(rg) - 1)); push!(r, Int32(last(rg)))          # [begin, end) 0-based
+    end
+    k = Int32[get(() -> throw(ArgumentError("set_bijector!: unknown kind $kd")), BIJECTOR_KINDS, kd) for kd in kinds]
+    b = Float64[]
+    for (lb, ub) in bounds
+        push!(b, Float64(lb)); push!(b, Float64(ub))
+    end
+    check(state.ctx, ccall((:mivi_set_bijector_stacked_ex, libmivi), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                           state.ctx, Int32(length(kinds)), r, k, b))
+    return state
+end
+
+# Bijectors.TransformedDistribution(q, binv) on the device, with the bijector set_bijector! installed: constrained draws of estimate `idx`
+# (x_dev: d x n_mc; eta_dev, if given, receives the unconstrained draws) and the log-density of the transformed distribution at the
+# caller's constrained points (-Inf outside the support).
+function rand_constrained_dev!(state::MIVIState, params_dev::Ptr{Cvoid}, idx::Integer, x_dev::Ptr{Cvoid}, eta_dev::Ptr{Cvoid}=C_NULL)
+    check(state.ctx, ccall((:mivi_sample_constrained, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Ptr{Cvoid}),
+                           state.ctx, params_dev, UInt64(idx), x_dev, eta_dev))
+    return nothing
+end
+
+function logpdf_constrained(state::MIVIState, params::Vector{T}, x::AbstractVecOrMat{<:Real}) where {T<:Union{Float32,Float64}}
+    X = Matrix{T}(reshape(x, :, x isa AbstractVector ? 1 : size(x, 2)))
+    logq = Vector{T}(undef, size(X, 2))
+    check(state.ctx, ccall((:mivi_logpdf_constrained_host, libmivi), Int32, (Ptr{Cvoid}, Ptr{T}, Ptr{T}, Int64, Ptr{T}),
+                           state.ctx, params, X, size(X, 2), logq))
+    return x isa AbstractVector ? logq[1] : logq
+end
+
 # Multi-GPU (one process per GPU): the collective lives behind the C ABI (RCCL opened by libmivi).  Rank 0 creates the id,
 # the host broadcasts its 128 bytes by its own means (MPI.Bcast!, a file, ...), every rank attaches it.  The context must have
 # been created with this rank's slice of the sample axis (MiviConfig.m_offset / m_total: build the MiviConfig with n_mc = the local share,
@@ -758,5 +796,5 @@ end
 # ProximalLocationScaleEntropy on the host arrays works unchanged (src/optimization/proximal_location_scale_entropy.jl);
 # the device-resident variant for a parameter vector that lives in HBM is mivi_prox_scale_entropy.
 
-export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, logpdf_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!, bam_moments!, estimate_fisher, bam_update!, bam_init_dev!, bam_moments_dev!, estimate_fisher_dev!, bam_update_dev!, bam_steps!, wass_update!, wass_init_dev!, wass_update_dev!, wass_steps!
+export AutoMIVI, SecondOrder, NativeDiagNormal, NativeDenseNormal, NativeFunnel, NativeLogReg, native_logreg!, MIVITarget, set_bijector!, rand_constrained_dev!, logpdf_constrained, comm_unique_id, comm_init!, comm_enable_p2p!, comm_destroy!, estimate_gradient_dist!, estimate_gradient_dist_n!, estimate_gradient_each!, estimate_score_gradient_dev!, logpdf_dev!, sqrt_ngd_update!, sqrt_ngd_update_dev!, sqrt_ngd_steps!, bam_moments!, estimate_fisher, bam_update!, bam_init_dev!, bam_moments_dev!, estimate_fisher_dev!, bam_update_dev!, bam_steps!, wass_update!, wass_init_dev!, wass_update_dev!, wass_steps!
 end # module

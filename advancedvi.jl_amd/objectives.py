@@ -277,13 +277,36 @@ def estimate_objective(rng, obj, q, prob=None, n_samples: int = None, adtype=Non
         ctx.close()
 
 
+class TransformedDistribution:
+    """Bijectors.TransformedDistribution(q, binv) (docs/src/tutorials/basic.md:210-247, constrained.md:228-231): the variational
+    approximation on the constrained scale -- `q` a fitted family on the unconstrained scale, `bijector` the P.StackedBijector whose
+    inverse maps its draws to the support.  rand(rng, qt, n) samples it, logpdf(qt, x) scores constrained points."""
+
+    def __init__(self, q, bijector: P.StackedBijector):
+        if not isinstance(bijector, P.StackedBijector):
+            raise TypeError("TransformedDistribution(q, bijector): bijector must be a StackedBijector")
+        for lo, hi, _ in bijector.blocks:
+            if lo < 0 or hi > len(q) or lo > hi:
+                raise ValueError(f"bijector block [{lo}, {hi}) lies outside the {len(q)} coordinates of q")
+        # (not `dist`: on a family that attribute is the BASE distribution, and a helper handed this object must not take one for the other)
+        self.q = q
+        self.bijector = bijector
+
+    def __len__(self):
+        return len(self.q)
+
+
 def rand(rng, q, num_samples: int, device: int = 0):
     """rand(rng, q, num_samples): d x num_samples samples (location_scale.jl:71-87, location_scale_low_rank.jl:66-100), returned as a
-    device tensor (column m = sample m)."""
+    device tensor (column m = sample m).  q::TransformedDistribution: the draws of q.q pushed through the bijector (constrained)."""
+    qt, q = (q, q.q) if isinstance(q, TransformedDistribution) else (None, q)
     ctx = MiviContext(q.eltype, q.family, len(q), num_samples, 0, rng.seed, device=device, rank=getattr(q, "rank", 0))
     try:
         ctx.set_base_dist(getattr(q, "dist", None))
         params, _ = destructure(q)
+        if qt is not None:
+            ctx.set_bijector(qt.bijector)
+            return ctx.sample_constrained(params, rng.next_index()).clone()
         return ctx.sample(params, rng.next_index(), want_eps=False).clone()
     finally:
         ctx.close()
@@ -292,7 +315,9 @@ def rand(rng, q, num_samples: int, device: int = 0):
 def logpdf(q, z, device: int = 0):
     """logpdf(q, z): Distributions.logpdf of the variational family at the caller's points (location_scale.jl:59-63,
     location_scale_low_rank.jl:45-68) -- MvLocationScale with a diagonal or triangular scale and any `dist`, MvLocationScaleLowRank.
-    z of shape (d,): a Python float.  z of shape (d, n), numpy or device tensor: a device tensor of n values in q.eltype."""
+    z of shape (d,): a Python float.  z of shape (d, n), numpy or device tensor: a device tensor of n values in q.eltype.
+    q::TransformedDistribution: z are constrained points, the value is log q.q(b(z)) - logabsdetjac(binv, b(z)); -inf outside the support."""
+    qt, q = (q, q.q) if isinstance(q, TransformedDistribution) else (None, q)
     ctx = MiviContext(q.eltype, q.family, len(q), 1, 0, 0, device=device, rank=getattr(q, "rank", 0))
     try:
         ctx.set_base_dist(getattr(q, "dist", None))
@@ -300,7 +325,9 @@ def logpdf(q, z, device: int = 0):
         single = getattr(z, "ndim", None) == 1 or (not hasattr(z, "ndim") and np.ndim(z) == 1)
         if single and len(z) != len(q):
             raise ValueError(f"logpdf: z has {len(z)} entries, q has dimension {len(q)}")
-        out = ctx.logpdf(params, z)
+        if qt is not None:
+            ctx.set_bijector(qt.bijector)
+        out = ctx.logpdf_constrained(params, z) if qt is not None else ctx.logpdf(params, z)
         ctx.synchronize()   # (a non-positive scale diagonal raises here, like the reference's DomainError)
         return float(out.item()) if single else out
     finally:

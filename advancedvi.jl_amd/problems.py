@@ -191,15 +191,43 @@ class FunnelConstrainedProblem:
 
 class StackedBijector:
     """inverse(Bijectors.Stacked(bijectors, ranges)) restricted to identity / exp blocks (README.md:76-82):
-    blocks = [(begin, end, kind)], 0-based half-open ranges, kind in {"identity", "exp"}."""
+    blocks = [(begin, end, kind)], 0-based half-open ranges, kind in {"identity", "exp"}.
+    Bounded and ordered supports (mivi_set_bijector_stacked_ex): (begin, end, "truncated", (lb, ub)) -- one pair of bounds per block, either
+    of which may be infinite (both finite: the scaled logistic map; one: a shifted exp; none: identity) -- and (begin, end, "ordered"), a
+    strictly increasing block x_b = eta_b, x_k = x_{k-1} + exp(eta_k).  `.blocks` stays a list of 3-tuples; `.bounds` is the parallel list
+    of (lb, ub) pairs ((-inf, +inf) for a block that is not truncated)."""
 
-    KINDS = {"identity": 0, "exp": 1}
+    KINDS = {"identity": 0, "exp": 1, "truncated": 2, "ordered": 3}
+    LEGACY_KINDS = ("identity", "exp")   # what mivi_set_bijector_stacked itself takes
 
     def __init__(self, blocks):
-        self.blocks = [(int(lo), int(hi), str(kind)) for lo, hi, kind in blocks]
-        for _, _, kind in self.blocks:
+        self.blocks, self.bounds = [], []
+        for blk in blocks:
+            blk = tuple(blk)
+            if len(blk) not in (3, 4):
+                raise ValueError(f"a bijector block is (begin, end, kind) or (begin, end, 'truncated', (lb, ub)), got {blk!r}")
+            lo, hi, kind = int(blk[0]), int(blk[1]), str(blk[2])
             if kind not in self.KINDS:
                 raise ValueError(f"unknown bijector kind {kind}")
+            if (len(blk) == 4) != (kind == "truncated"):
+                raise ValueError(f"bounds go with a 'truncated' block and only with one, got {blk!r}")
+            lb, ub = -np.inf, np.inf
+            if kind == "truncated":
+                try:
+                    lb, ub = (float(v) for v in blk[3])
+                except (TypeError, ValueError):
+                    raise ValueError(f"the bounds of a truncated block are a pair (lb, ub), got {blk[3]!r}") from None
+                if np.isnan(lb) or np.isnan(ub):
+                    raise ValueError("a bound of a truncated block is NaN")
+                if not lb < ub:
+                    raise ValueError(f"a truncated block needs lb < ub, got ({lb}, {ub})")
+            self.blocks.append((lo, hi, kind))
+            self.bounds.append((lb, ub))
+
+    @property
+    def is_legacy(self):
+        """identity / exp blocks only: what mivi_set_bijector_stacked takes"""
+        return all(kind in self.LEGACY_KINDS for _, _, kind in self.blocks)
 
 
 class TransformedProblem:

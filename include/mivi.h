@@ -179,6 +179,31 @@ mivi_status_t mivi_set_target_funnel_constrained(mivi_ctx_t *ctx, double sigma_v
  * With a bijector the estimate runs on the explicit-sample route (Z materialised, transformed in place). */
 mivi_status_t mivi_set_bijector_stacked(mivi_ctx_t *ctx, int32_t n_blocks, const int32_t *ranges_host, const int32_t *kinds_host);
 
+/* The same with bounded and ordered blocks: the maps Bijectors.jl attaches to Uniform / Beta / truncated supports, to half-bounded
+ * parameters with a non-zero bound and to ordered vectors (cut-points, mixture locations).  kinds_host[b] is a mivi_bijector_kind_t:
+ *   MIVI_BIJ_TRUNCATED  one pair (lb, ub) = bounds_host[2 b], bounds_host[2 b + 1] per block; +-INFINITY means "no bound"
+ *       both finite : s = sigma(eta), x = lb + (ub - lb) s, ladj = log(ub - lb) - |eta| - 2 log1p(e^-|eta|),
+ *                     d/d eta = (ub - lb) s (1 - s) g + (1 - 2 s)
+ *       lb only     : x = lb + e^eta, ladj = eta, d/d eta =  e^eta g + 1        (lb = 0: bitwise MIVI_BIJ_EXP)
+ *       ub only     : x = ub - e^eta, ladj = eta, d/d eta = -e^eta g + 1
+ *       neither     : identity
+ *   MIVI_BIJ_ORDERED    the block [b, e) maps to a strictly increasing vector: x_b = eta_b, x_k = x_{k-1} + e^eta_k, ladj = sum_{k>b} eta_k;
+ *                       with S_k = sum_{j=k}^{e-1} g_j: d/d eta_b = S_b, d/d eta_k = e^eta_k S_k + 1.  A block of length 1 is identity.
+ * (g = grad_x log pi(x), ladj = the block's part of logabsdetjac(binv, eta) per sample.)  bounds_host: double[2 n_blocks], read for
+ * MIVI_BIJ_TRUNCATED blocks only; may be NULL when there is none.  One workgroup per sample column, the ordered kind as a segmented scan
+ * in f64; the backward pass takes e^eta and sigma(eta) from a saved copy of eta (d x n_mc, allocated only when such a block is present),
+ * never from differences of the stored x, which cancel in f32 next to a large bound.  In f32 a two-sided block saturates to x = lb or
+ * x = ub for |eta| beyond ~17 (a target that is finite there keeps value and gradient finite); ladj never evaluates log sigma of a
+ * saturated sigma.  Every route mivi_set_bijector_stacked serves takes the new kinds; the refusals behind a bijector (the second-order
+ * branch, FisherMinBatchMatch, the fused / launch-free routes) are the same.  A list of identity / exp blocks alone (truncated(-inf, +inf)
+ * and one-coordinate ordered blocks are identity) is exactly mivi_set_bijector_stacked.  Dimension-changing maps (simplex, correlation /
+ * covariance Cholesky) are out of scope: target and family share one d.
+ * MIVI_ERR_BAD_ARG with a message: a NaN bound, lb >= ub, a kind outside 0 .. 3, a range outside [0, d), overlapping blocks; the bijector
+ * that was set stays.  MIVI_ERR_HIP (the tables could not be placed on the device): the context is left with NO bijector. */
+typedef enum { MIVI_BIJ_IDENTITY = 0, MIVI_BIJ_EXP = 1, MIVI_BIJ_TRUNCATED = 2, MIVI_BIJ_ORDERED = 3 } mivi_bijector_kind_t;
+mivi_status_t mivi_set_bijector_stacked_ex(mivi_ctx_t *ctx, int32_t n_blocks, const int32_t *ranges_host, const int32_t *kinds_host,
+                                           const double *bounds_host);
+
 /* Generic plugin: batched `logdensity_and_gradient` (src/mixedad_logdensity.jl:28) over the columns of Z.
  * Called on the host thread inside mivi_estimate_* with HOST buffers: Z (d x M col-major) in,
  * ell (M) and G (d x M) out.  Return non-zero to abort (-> MIVI_ERR_BAD_ARG). */
@@ -224,6 +249,23 @@ mivi_status_t mivi_sample(mivi_ctx_t *ctx, const void *params_dev, uint64_t esti
 mivi_status_t mivi_logpdf(mivi_ctx_t *ctx, const void *params_dev, const void *Z_dev, int64_t n, void *logq_dev, void *std_dev);
 /* Same, host buffers, synchronous; returns MIVI_ERR_NONPOSITIVE_SCALE itself. */
 mivi_status_t mivi_logpdf_host(mivi_ctx_t *ctx, const void *params_host, const void *Z_host, int64_t n, void *logq_host, void *std_host);
+
+/* Bijectors.TransformedDistribution(q, binv) with the Stacked bijector that is set (docs/src/tutorials/basic.md:210-247,
+ * constrained.md:228-231): the constrained approximation people sample from and score.  Every family and base mivi_sample / mivi_logpdf serve.
+ *
+ * mivi_sample_constrained: X_dev T[d*n_mc] <- binv(z), z the draws mivi_sample returns for estimate_idx; eta_dev T[d*n_mc] or NULL <- z itself.
+ * No bijector: X = z.
+ *
+ * mivi_logpdf_constrained: logq[k] = log q(b(x_k)) - logabsdetjac(binv, b(x_k)) at the caller's CONSTRAINED points X (d x n, the layout of
+ * mivi_logpdf).  An inverse-direction kernel (truncated: u = (x - lb) / (ub - lb), eta = log u - log1p(-u), or log(x - lb) / log(ub - x);
+ * ordered: eta_k = log(x_k - x_{k-1}); everything in f64, rounded once) runs in front of mivi_logpdf, in scratch of its own: the same
+ * "leaves the context as it found it" contract.  A finite point outside the support -- on or beyond a bound, a non-increasing ordered
+ * block -- gives exactly -inf for that column, a NaN point gives NaN for that column only; neither sets a status flag.  No bijector:
+ * mivi_logpdf. */
+mivi_status_t mivi_sample_constrained(mivi_ctx_t *ctx, const void *params_dev, uint64_t estimate_idx, void *X_dev, void *eta_dev);
+mivi_status_t mivi_logpdf_constrained(mivi_ctx_t *ctx, const void *params_dev, const void *X_dev, int64_t n, void *logq_dev);
+/* Same, host buffers, synchronous. */
+mivi_status_t mivi_logpdf_constrained_host(mivi_ctx_t *ctx, const void *params_host, const void *X_host, int64_t n, void *logq_host);
 
 /* estimate_gradient!(rng, obj::RepGradELBO, adtype, out, state, params, restructure):
  * src/algorithms/repgradelbo.jl:151-177 (+ the AD shim src/AdvancedVI.jl:57-67 it replaces).
