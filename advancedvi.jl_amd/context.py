@@ -620,6 +620,11 @@ class MiviContext:
         """hipGraphs recorded into the context's graph cache so far (mivi_batch_info what = 4): unchanged across two calls = the second replayed."""
         return int(self.lib.mivi_batch_info(self.h, None, 4))
 
+    def live_allocations(self):
+        """Device allocations the library holds right now in this process, over all contexts (mivi_batch_info what = 5): equal before a
+        context's creation and after its close() = the context returned everything."""
+        return int(self.lib.mivi_batch_info(self.h, None, 5))
+
     def exchange_lost(self):
         """True once a launch-free loop's grid-wide exchange was lost on this context: the loops with a per-step exchange are then not taken
         again, their graph-of-launches equivalents run instead (mivi_batch_info what = 3)."""

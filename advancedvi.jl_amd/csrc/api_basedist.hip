@@ -54,14 +54,14 @@ mivi_status_t mivi_set_base_dist(mivi_ctx_t *c, int32_t base, double nu) {
   return MIVI_OK;
 }
 
-// the base's planes for cap samples per launch (ensure_work): zeroed, the kernels keep their padding zero
+// the base's planes for cap samples per launch (ensure_work): zeroed, the kernels keep their padding zero; one the configuration does not read is released
 mivi_status_t ensure_work_base(mivi_ctx *c, int cap) {
   const size_t plane = (size_t)c->dP * (size_t)cap * c->esize;
   mivi_status_t s;
-  c->bd_U.bytes = 0;
-  c->bd_R.bytes = 0;
-  if (c->cfg.family == MIVI_MEANFIELD && (s = ensure(c, c->bd_U, plane, true))) return s;
-  if (stl_entropy(c) && (s = ensure(c, c->bd_R, plane, true))) return s;
+  if (c->cfg.family != MIVI_MEANFIELD) c->bd_U.release();
+  else if ((s = ensure_zeroed(c, c->bd_U, plane))) return s;
+  if (!stl_entropy(c)) c->bd_R.release();
+  else if ((s = ensure_zeroed(c, c->bd_R, plane))) return s;
   return MIVI_OK;
 }
 

@@ -46,7 +46,7 @@ static mivi_status_t estimate_gradient_chain(mivi_ctx *c, const void *params, ui
   (void)hipSetDevice(c->cfg.device);
   mivi_status_t s = ensure_work(c, c->cfg.n_mc);
   if (s) return s;
-  prepare_tables(c, c->cfg.n_mc);   // host->device uploads are not allowed inside the capture
+  if (!prepare_tables(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");   // host->device uploads are not allowed inside the capture
   if ((s = reserve_target(c, c->cfg.n_mc))) return s;
   static const bool no_fused_loop_n = getenv("MIVI_NO_FUSED_LOOP") != nullptr;
   if (c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on && c->cfg.n_mc <= 4096 && !c->idx_src && !no_fused_loop_n) {
@@ -112,7 +112,7 @@ mivi_status_t sync_kid(mivi_ctx *c, mivi_ctx *k, int lanes) {
   invalidate_graph(k);
   k->target = c->target;
   k->t_const = c->t_const;
-  k->t_mean = c->t_mean; k->t_istd = c->t_istd; k->t_prec = c->t_prec;   // borrowed (is_child: never freed there)
+  k->t_mean.borrow(c->t_mean.p, c->t_mean.bytes); k->t_istd.borrow(c->t_istd.p, c->t_istd.bytes); k->t_prec.borrow(c->t_prec.p, c->t_prec.bytes);   // views of the parent's target, re-taken whenever its generation moves
   k->M_total = c->M_total;
   if (k->target == TGT_DENSE_GAUSS && !k->RT.p) k->cap_M = 0;              // (allocates its own transposed-sample buffer)
   k->idx_stride = lanes;
@@ -131,8 +131,7 @@ mivi_status_t ensure_kids(mivi_ctx *c, int lanes) {
     if ((s = mivi_create(&cfg, &k))) return fail(c, s, "interleaved chains: child context creation failed");
     k->is_child = true;
     const int j = c->n_kids;
-    (void)hipFree(k->status.p);                                    // the child's sticky flags: word j + 1 of the parent's status buffer
-    k->status.p = (char *)c->status.p + sizeof(int) * (j + 1);    // (borrowed: is_child contexts never free it)
+    k->status.borrow((char *)c->status.p + sizeof(int) * (j + 1), sizeof(int));   // the child's sticky flags: word j + 1 of the parent's status buffer
     if ((s = ensure(c, c->kid_out[j], 16 + (size_t)mivi_params_len(c) * c->esize, false))) { (void)mivi_destroy(k); return s; }
     if (hipEventCreateWithFlags(&c->ev_join[j], hipEventDisableTiming) != hipSuccess ||
         (!c->ev_fork && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess)) {
@@ -230,8 +229,7 @@ static mivi_status_t fb_batch(mivi_ctx *c, const void *params, uint64_t idx0, in
         (s = ensure(c, t.ld, 2 * (size_t)(dG / 32) * sizeof(double) + 64, false)) || (s = ensure(c, t.values, (size_t)L * 4 + 64, false)) ||
         (s = ensure(c, t.cscale, 2 * (size_t)dG * 4, false)) || (s = ensure(c, t.winv, (size_t)L * (MG / 128) * dG * 4, false)))
       return s;
-    t.grads.bytes = 0;   // (re-zeroed: the lanes' scratch gradients rely on exact zeros above the diagonal that no kernel writes)
-    if ((s = ensure(c, t.grads, (size_t)L * plen * 4, true))) return s;
+    if ((s = ensure_zeroed(c, t.grads, (size_t)L * plen * 4))) return s;   // (the lanes' scratch gradients rely on exact zeros above the diagonal that no kernel writes)
     t.cap_L = L;
     t.cap_M = M;
     t.cap_LR = 0;
@@ -353,6 +351,7 @@ int32_t mivi_batch_info(const mivi_ctx_t *c, const void *params, int32_t what) {
   if (what == 2) return 4;   // two f16 planes
   if (what == 3) return c->exchange_lost ? 1 : 0;
   if (what == 4) return c->graph_records;
+  if (what == 5) return live_allocations();
   return (what == 0 && params && fb_route(c, params, nullptr, nullptr)) ? 1 : 0;
 }
 
@@ -522,11 +521,11 @@ mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64
   // launch with `lanes` parallel branches and one join (two graph launches + events per call cost a 20-estimate batch what the
   // overlap gained: 14.7 us per estimate against 14.4 with one chain, 9.7 in steady state).
   if ((s = ensure_work(c, c->cfg.n_mc))) return s;
-  prepare_tables(c, c->cfg.n_mc);
+  if (!prepare_tables(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
   for (int j = 0; j < lanes - 1; ++j) {
     mivi_ctx *k = c->kids[j];
     if ((s = ensure_work(k, k->cfg.n_mc))) { c->err = k->err; return s; }
-    prepare_tables(k, k->cfg.n_mc);
+    if (!prepare_tables(k, k->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
     if (!lds_prepare(k, k->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");
   }
   if (!lds_prepare(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");

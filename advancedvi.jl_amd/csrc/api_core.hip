@@ -4,6 +4,8 @@
 // parameters), api_objective.hip (estimate_objective, the Gaussian-expectation gradient / Hessian), api_dist.hip (sharded
 // estimates), api_optimize.hip (update rules, the device-resident loop), api_profile.hip (per-kernel timing entries),
 // api_graph.hip (hipGraph capture, the context's graph cache and its replay).
+#include <atomic>
+
 #include "api_common.h"
 
 // ---- one-thread kernels shared by the api_*.hip units (declared in api_common.h) ----
@@ -49,18 +51,38 @@ bool grid_resident(const mivi_ctx *c, const void *kernel, int block, size_t dyn_
 }
 }  // namespace mivi
 
-mivi_status_t ensure(mivi_ctx *c, DevBuf &b, size_t bytes, bool zero) {
+// ---- the library's device memory: ensure allocates, DevBuf::release frees, and nothing else in libmivi does either ----
+static std::atomic<int32_t> g_live_allocations{0};   // allocations held in this process (mivi_batch_info what = 5)
+int32_t live_allocations() { return g_live_allocations.load(); }
+
+void mivi::DevBuf::release() {
+  if (owned && p) { (void)hipFree(p); --g_live_allocations; }
+  p = nullptr; bytes = 0; owned = false;
+}
+
+mivi_status_t ensure(mivi_ctx *c, DevBuf &b, size_t bytes, bool zero, bool fine_grained) {
   if (b.bytes >= bytes && b.p) return MIVI_OK;
-  if (b.p) HIPCHK(c, hipFree(b.p));
-  b.p = nullptr;
-  b.bytes = 0;
+  b.release();
   if (bytes == 0) bytes = 16;
-  HIPCHK(c, hipMalloc(&b.p, bytes));
-  b.bytes = bytes;
+  void *p = nullptr;
+  HIPCHK(c, fine_grained ? hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained) : hipMalloc(&p, bytes));
+  ++g_live_allocations;
+  b.p = p; b.bytes = bytes; b.owned = true;
   if (zero) HIPCHK(c, hipMemsetAsync(b.p, 0, bytes, c->stream));
   return MIVI_OK;
 }
 
+mivi_status_t ensure_zeroed(mivi_ctx *c, DevBuf &b, size_t bytes) {
+  if (mivi_status_t s = ensure(c, b, bytes, false)) return s;
+  HIPCHK(c, hipMemsetAsync(b.p, 0, bytes ? bytes : b.bytes, c->stream));
+  return MIVI_OK;
+}
+
+mivi_status_t upload(mivi_ctx *c, DevBuf &b, const void *src, size_t bytes) {
+  if (mivi_status_t s = ensure(c, b, bytes, false)) return s;
+  HIPCHK(c, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+  return MIVI_OK;
+}
 
 // A captured graph bakes buffer pointers, leading dimensions and work-list contents; the eps speculation remembers a buffer
 // parity.  Anything that reallocates or rewrites those calls this.
@@ -92,9 +114,8 @@ mivi_status_t ensure_work(mivi_ctx *c, int M) {
     const size_t ncc = (size_t)(capM / 256 + 2);
     for (int b = 0; b < 2; ++b) {
       if (c->cfg.family == MIVI_FULLRANK) {
-        c->eps[b].bytes = 0; c->epsT[b].bytes = 0;
-        if ((s = ensure(c, c->eps[b], (size_t)c->dP * c->MP * es, true))) return s;
-        if ((s = ensure(c, c->epsT[b], (size_t)c->dP * c->MP * es, true))) return s;
+        if ((s = ensure_zeroed(c, c->eps[b], (size_t)c->dP * c->MP * es))) return s;
+        if ((s = ensure_zeroed(c, c->epsT[b], (size_t)c->dP * c->MP * es))) return s;
       }
       if ((s = ensure(c, c->ell_part[b], n_part * sizeof(double), false))) return s;
       if ((s = ensure(c, c->he_part[b], (n_he + 64) * sizeof(double), false))) return s;
@@ -102,8 +123,7 @@ mivi_status_t ensure_work(mivi_ctx *c, int M) {
       if ((s = ensure(c, c->ld_part[b], 2 * (size_t)((d + 31) / 32) * sizeof(double) + 64, false))) return s;
     }
     if (c->target == TGT_DENSE_GAUSS || (c->target == TGT_LOGREG && c->cfg.dtype == MIVI_F32)) {
-      c->RT.bytes = 0;
-      if ((s = ensure(c, c->RT, (size_t)c->dP * c->MP * es, true))) return s;
+      if ((s = ensure_zeroed(c, c->RT, (size_t)c->dP * c->MP * es))) return s;
     }
     if (c->cfg.family == MIVI_FULLRANK && (c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD)) {
       if ((s = ensure(c, c->stl_CT, (size_t)c->dP * c->dP * es, true))) return s;
@@ -186,49 +206,24 @@ mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out) {
   return MIVI_OK;
 }
 
+mivi_ctx_streams::~mivi_ctx_streams() {
+  if (own_stream) (void)hipStreamDestroy(stream);
+  if (cap_stream) (void)hipStreamDestroy(cap_stream);
+  for (hipStream_t s : {comm_stream, comm_stream2, fb_comm_stream})
+    if (s) (void)hipStreamDestroy(s);
+  for (hipEvent_t e : ev_join)
+    if (e) (void)hipEventDestroy(e);
+  if (ev_fork) (void)hipEventDestroy(ev_fork);
+  for (hipEvent_t *pair : {fb_ev_part, fb_ev_comm, ev_part, ev_comm})
+    for (int k = 0; k < 2; ++k)
+      if (pair[k]) (void)hipEventDestroy(pair[k]);
+}
+
 mivi_status_t mivi_destroy(mivi_ctx_t *c) {
   if (!c) return MIVI_ERR_BAD_ARG;
   (void)hipSetDevice(c->cfg.device);
   (void)hipStreamSynchronize(c->stream);
-  for (int j = 0; j < c->n_kids; ++j) {
-    (void)mivi_destroy(c->kids[j]);
-    if (c->ev_join[j]) (void)hipEventDestroy(c->ev_join[j]);
-    if (c->kid_out[j].p) (void)hipFree(c->kid_out[j].p);
-  }
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->is_child) c->t_mean = c->t_istd = c->t_prec = c->status = mivi::DevBuf{};   // borrowed from the parent
-  (void)mivi_comm_destroy(c);
-  c->graph.drop();
-  DevBuf *bufs[] = {&c->t_mean, &c->t_istd, &c->t_prec, &c->lr_X_own, &c->lr_y_own, &c->lr_scratch, &c->lr_part, &c->lr_Xrm,
-                    &c->eps[0], &c->eps[1], &c->epsT[0], &c->epsT[1], &c->Z, &c->W, &c->RT, &c->ell, &c->X,
-                    &c->ell_part[0], &c->ell_part[1], &c->he_part[0], &c->he_part[1], &c->row_part,
-                    &c->sc_part[0], &c->sc_part[1], &c->ld_part[0], &c->ld_part[1], &c->tabA, &c->tabB, &c->tabD, &c->stl_CT, &c->stl_Dinv, &c->stl_X, &c->stl_F, &c->lr_xmax, &c->lr_XA, &c->lr_XB, &c->lr_ZP, &c->lr_Xsub, &c->lr_ysub, &c->lr_Xrm_sub, &c->lr_idx, &c->dog_part, &c->stein_A, &c->stein_g, &c->h2_acc, &c->sg_S, &c->sg_d, &c->bij_mask, &c->bij_ld, &c->bij_code, &c->bij_bnd, &c->bij_eta, &c->bij_scr, &c->dist_P, &c->dist_P2, &c->dist_ring[0], &c->dist_ring[1], &c->dist_ring[2], &c->dist_ring[3], &c->dist_ring[4], &c->dist_ring[5], &c->p2p_scratch, &c->dist_S, &c->dist_F, &c->p2p_tab, &c->p2p_ctr, &c->lds_tabV, &c->lds_tabV64, &c->lds_tabS, &c->lds_tabSt, &c->status, &c->d_idx, &c->acc, &c->tmp_params, &c->tmp_out, &c->obj_vals, &c->lowr_E, &c->lowr_V, &c->lowr_prep, &c->lowr_sx, &c->lowr_part, &c->bd_U, &c->bd_R, &c->lp_dinv, &c->lp_scal, &c->lp_work, &c->lp_host};
-  for (DevBuf *b : bufs)
-    if (b->p) (void)hipFree(b->p);
-  {
-    DevBuf *fbb[] = {&c->fb.CA, &c->fb.epsP, &c->fb.WV, &c->fb.ell, &c->fb.he, &c->fb.ld, &c->fb.grads, &c->fb.values, &c->fb.PA, &c->fb.RP, &c->fb.Tinv, &c->fb.TA, &c->fb.Eye, &c->snap, &c->fb.cscale, &c->fb.pscale, &c->fb.tscale, &c->fb.winv, &c->fb.rinv, &c->p2p_direct, &c->rows_eps, &c->gen_scratch, &c->ms_work, &c->ms_part, &c->ngd_est, &c->natgrad_host, &c->bam_host};
-    for (DevBuf *b : fbb)
-      if (b->p) (void)hipFree(b->p);
-    for (auto &tb : c->fb.tab) {
-      if (tb.prod.p) (void)hipFree(tb.prod.p);
-      if (tb.vjp.p) (void)hipFree(tb.vjp.p);
-      if (tb.prod2.p) (void)hipFree(tb.prod2.p);
-      if (tb.prod3.p) (void)hipFree(tb.prod3.p);
-    }
-  }
-  if (c->own_stream) (void)hipStreamDestroy(c->stream);
-  if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
-  if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-  if (c->comm_stream2) (void)hipStreamDestroy(c->comm_stream2);
-  if (c->fb_comm_stream) (void)hipStreamDestroy(c->fb_comm_stream);
-  for (int k = 0; k < 2; ++k) {
-    if (c->fb_ev_part[k]) (void)hipEventDestroy(c->fb_ev_part[k]);
-    if (c->fb_ev_comm[k]) (void)hipEventDestroy(c->fb_ev_comm[k]);
-  }
-  for (int k = 0; k < 2; ++k) {
-    if (c->ev_part[k]) (void)hipEventDestroy(c->ev_part[k]);
-    if (c->ev_comm[k]) (void)hipEventDestroy(c->ev_comm[k]);
-  }
+  for (int j = 0; j < c->n_kids; ++j) (void)mivi_destroy(c->kids[j]);   // (before their views of this context's buffers dangle)
   delete c;
   return MIVI_OK;
 }
@@ -256,15 +251,9 @@ double host_get(const void *p, int dtype, size_t i) {
   return dtype == MIVI_F32 ? (double)((const float *)p)[i] : ((const double *)p)[i];
 }
 static mivi_status_t upload_vec(mivi_ctx *c, DevBuf &b, const std::vector<double> &v) {
-  mivi_status_t s = ensure(c, b, v.size() * c->esize, false);
-  if (s) return s;
-  if (c->cfg.dtype == MIVI_F32) {
-    std::vector<float> f(v.begin(), v.end());
-    HIPCHK(c, hipMemcpy(b.p, f.data(), f.size() * 4, hipMemcpyHostToDevice));
-  } else {
-    HIPCHK(c, hipMemcpy(b.p, v.data(), v.size() * 8, hipMemcpyHostToDevice));
-  }
-  return MIVI_OK;
+  if (c->cfg.dtype != MIVI_F32) return upload(c, b, v.data(), v.size() * 8);
+  const std::vector<float> f(v.begin(), v.end());
+  return upload(c, b, f.data(), f.size() * 4);
 }
 
 mivi_status_t mivi_set_target_diag_gauss(mivi_ctx_t *c, const void *mean, const void *stdv) {

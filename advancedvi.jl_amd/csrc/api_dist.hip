@@ -132,9 +132,7 @@ mivi_status_t mivi_p2p_detach(mivi_ctx_t *c) {
     c->p2p_opened[r] = false;
     c->p2p_peer[r] = nullptr;
   }
-  if (c->p2p_buf) (void)hipFree(c->p2p_buf);
-  c->p2p_buf = nullptr;
-  c->p2p_bytes = 0;
+  c->p2p_buf.release();   // (behind the peers' handles, closed above)
   c->p2p_on = false;
   return MIVI_OK;
 }
@@ -160,16 +158,14 @@ mivi_status_t mivi_p2p_export(mivi_ctx_t *c, int32_t rank, int32_t world, void *
   // uncached allocation corrupted UNRELATED buffers of later contexts once the area had been freed and its pages re-used (found on one
   // GPU: the estimates of contexts created after a p2p context were off by 1e-2 until their buffers had been rewritten a few times;
   // fine-grained and plain allocations never showed it).
-  void *buf = nullptr;
-  hipError_t e = hipExtMallocWithFlags(&buf, bytes, hipDeviceMallocFinegrained);
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, MIVI_ERR_HIP, "peer-to-peer exchange buffer: fine-grained allocation failed"); }
+  if (ensure(c, c->p2p_buf, bytes, false, true)) { (void)hipGetLastError(); return fail(c, MIVI_ERR_HIP, "peer-to-peer exchange buffer: fine-grained allocation failed"); }
+  void *const buf = c->p2p_buf.p;
+  hipError_t e;
   if ((e = hipMemset(buf, 0, bytes)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
-    (void)hipFree(buf);   // (not yet owned by the context: nothing else would free it)
+    c->p2p_buf.release();   // (an area that was never zeroed is not one an attach may find)
     c->err = std::string("peer-to-peer exchange buffer: ") + hipGetErrorString(e);
     return MIVI_ERR_HIP;
   }
-  c->p2p_buf = buf;
-  c->p2p_bytes = bytes;
   c->p2p_rank = rank; c->p2p_world = world; c->p2p_n = n; c->p2p_cn = cn; c->p2p_G = G; c->p2p_vs = vs;
   c->p2p_lane_bytes = lane_bytes; c->p2p_off_fin = b_stage; c->p2p_off_arr = b_stage + b_fin; c->p2p_off_farr = b_stage + b_fin + b_arr;
   P2PHandle h{};
@@ -188,7 +184,7 @@ mivi_status_t mivi_p2p_export(mivi_ctx_t *c, int32_t rank, int32_t world, void *
 mivi_status_t mivi_p2p_attach(mivi_ctx_t *c, const void *handles) {
   if (!c || !handles) return MIVI_ERR_BAD_ARG;
   if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_p2p_attach")) return rs;
-  if (!c->p2p_buf) return fail(c, MIVI_ERR_BAD_ARG, "mivi_p2p_export has not been called");
+  if (!c->p2p_buf.p) return fail(c, MIVI_ERR_BAD_ARG, "mivi_p2p_export has not been called");
   (void)hipSetDevice(c->cfg.device);
   const int R = c->p2p_world;
   const uint64_t me = (uint64_t)getpid();
@@ -199,11 +195,11 @@ mivi_status_t mivi_p2p_attach(mivi_ctx_t *c, const void *handles) {
     P2PHandle h;
     memcpy(&h, (const char *)handles + (size_t)r * MIVI_P2P_HANDLE_BYTES, sizeof(h));
     if (h.magic != kP2PMagic || h.version != 3 || h.rank != r || h.world != R || h.L != mivi_partials_len(c) || h.n != c->p2p_n ||
-        h.cn != c->p2p_cn || h.G != c->p2p_G || h.esize != (int32_t)c->esize || h.bytes != c->p2p_bytes)
+        h.cn != c->p2p_cn || h.G != c->p2p_G || h.esize != (int32_t)c->esize || h.bytes != c->p2p_buf.bytes)
       return fail(c, MIVI_ERR_BAD_ARG, "peer-to-peer handle does not match this context (rank order, family, d, dtype or world differ)");
     void *base = nullptr;
     if (r == c->p2p_rank) {
-      base = c->p2p_buf;
+      base = c->p2p_buf.p;
     } else if (h.pid == me) {   // another context of this process: its pointer is valid here (peer access for another device)
       base = (void *)(uintptr_t)h.local_ptr;
       if (h.device != c->cfg.device) {
@@ -370,9 +366,8 @@ mivi_status_t mivi_comm_enable_p2p(mivi_ctx_t *c) {
     RcclApi *r = rccl();
     DevBuf tmp;
     if ((s = ensure(c, tmp, all.size(), false))) { (void)mivi_p2p_detach(c); return s; }
-    auto give_up = [&](const char *why) {   // (the temporary and the exported areas go with every failure)
+    auto give_up = [&](const char *why) {   // (the exported areas go with every failure; the temporary goes with its scope)
       (void)hipGetLastError();
-      (void)hipFree(tmp.p);
       (void)mivi_p2p_detach(c);
       return fail(c, MIVI_ERR_HIP, why);
     };
@@ -384,7 +379,6 @@ mivi_status_t mivi_comm_enable_p2p(mivi_ctx_t *c) {
     if (e != ncclSuccess) return give_up("ncclAllGather of the peer-to-peer handles failed");
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(all.data(), tmp.p, all.size(), hipMemcpyDeviceToHost) != hipSuccess)
       return give_up("peer-to-peer handles: the gathered blobs could not be read back");
-    (void)hipFree(tmp.p);
   }
   s = mivi_p2p_attach(c, all.data());
   if (s) { const std::string why = c->err; (void)mivi_p2p_detach(c); c->err = why; }
@@ -402,11 +396,11 @@ mivi_status_t mivi_p2p_selfcheck(mivi_ctx_t *c, const void *params, uint64_t idx
   if (!c->p2p_on) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_p2p_selfcheck: no exchange areas attached");
   if (c->p2p_world > 1 && !c->comm) return fail(c, MIVI_ERR_BAD_ARG, "mivi_p2p_selfcheck: needs the RCCL communicator of mivi_comm_init to compare against");
   const size_t plen = (size_t)mivi_params_len(c), es = c->esize;
-  DevBuf a, b;
+  DevBuf a, b;   // (the two routes' results: they go with this scope)
   mivi_status_t s;
-  if ((s = ensure(c, a, (plen + 16) * es, false)) || (s = ensure(c, b, (plen + 16) * es + 64, false))) { if (a.p) (void)hipFree(a.p); return s; }
+  if ((s = ensure(c, a, (plen + 16) * es, false)) || (s = ensure(c, b, (plen + 16) * es + 64, false))) return s;
   const int keep = c->dist_route;
-  auto done = [&](mivi_status_t st) { (void)hipFree(a.p); (void)hipFree(b.p); c->dist_route = keep; invalidate_graph(c); return st; };
+  auto done = [&](mivi_status_t st) { c->dist_route = keep; invalidate_graph(c); return st; };
   c->dist_route = c->comm ? 1 : 3;
   invalidate_graph(c);
   // Every rank takes part in BOTH estimates and in the verdict's all-reduce WHATEVER happened to its own calls (bounded waits end the peer-to-peer
@@ -466,12 +460,9 @@ static mivi_status_t ensure_dist(mivi_ctx *c) {
       c->dist_S.bytes < (size_t)n * es || c->dist_F.bytes < (size_t)Lp * es) {
     invalidate_graph(c);
     mivi_status_t s;
-    c->dist_P.bytes = 0; c->dist_P2.bytes = 0;   // (re-zero: the padding behind the partial vector must be 0)
-    for (int k = 0; k < 6; ++k) {
-      c->dist_ring[k].bytes = 0;
-      if (need34 && (s = ensure(c, c->dist_ring[k], need34, true))) return s;
-    }
-    if ((s = ensure(c, c->dist_P, (size_t)need * es, true)) || (s = ensure(c, c->dist_P2, (size_t)need * es, true)) ||
+    for (int k = 0; k < 6; ++k)
+      if (need34 && (s = ensure_zeroed(c, c->dist_ring[k], need34))) return s;
+    if ((s = ensure_zeroed(c, c->dist_P, (size_t)need * es)) || (s = ensure_zeroed(c, c->dist_P2, (size_t)need * es)) ||   // (the padding behind the partial vector must be 0)
         (s = ensure(c, c->dist_S, (size_t)n * es, true)) || (s = ensure(c, c->dist_F, (size_t)Lp * es, true)))
       return s;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -708,7 +699,7 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
     return fb_batch_dist(c, params, idx0, count, value, grad);
   }
   if ((s = dist_check(c)) || (s = ensure_work(c, c->cfg.n_mc))) return s;
-  prepare_tables(c, c->cfg.n_mc);
+  if (!prepare_tables(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
   if ((s = reserve_target(c, c->cfg.n_mc)) || (s = ensure_dist(c))) return s;
   if (c->cfg.family == MIVI_FULLRANK && lds_path_shape_ok(c, c->cfg.n_mc) && !lds_prepare(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");
   if (!c->comm_stream) {
@@ -756,7 +747,7 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
       for (int j = 0; j < kGroup - 1; ++j) {
         mivi_ctx *k = c->kids[j];
         if ((s = sync_kid(c, k, kGroup)) || (s = ensure_work(k, k->cfg.n_mc))) { c->err = k->err; return s; }
-        prepare_tables(k, k->cfg.n_mc);
+        if (!prepare_tables(k, k->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
         if (!lds_prepare(k, k->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");
       }
     }

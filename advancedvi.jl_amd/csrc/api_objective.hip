@@ -146,8 +146,9 @@ mivi_status_t mivi_gauss_expected_grad_hess(mivi_ctx_t *c, const void *params, u
     if (!single_chunk) acc_chunk_value(c, part, 1.0, first);
     const double scale = k.last ? 1.0 / (double)n_samples : 1.0;
     if (st2) {
-      launch_lds_stein_outer(c, Mc, c->stein_A.p, (double *)c->stein_g.p, first, scale, (double)n_samples, fused_tail ? grad : nullptr,
-                             fused_tail ? logpi_avg : nullptr, fused_tail ? &vj : nullptr);
+      if (!launch_lds_stein_outer(c, Mc, c->stein_A.p, (double *)c->stein_g.p, first, scale, (double)n_samples, fused_tail ? grad : nullptr,
+                                  fused_tail ? logpi_avg : nullptr, fused_tail ? &vj : nullptr))
+        return fail(c, MIVI_ERR_HIP, "Stein accumulation: tile table allocation or upload failed");
       tail_done = fused_tail;
     } else {
       launch_stein_outer(c, Mc, c->stein_A.p, (double *)c->stein_g.p, first, scale);
@@ -203,6 +204,7 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, 
       const int Mc = k.Mc;
       const mivi_status_t se = ensure_work(c, Mc);
       if (se) return se;
+      if (!fr_prepare(c, Mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
       eps_spec_drop(c);
       launch_eps(c, k.rng, Mc);
       launch_fr_sample(c, params, Mc, TGT_NONE, c->Z.p);

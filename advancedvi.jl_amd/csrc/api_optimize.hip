@@ -95,7 +95,7 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   (void)hipSetDevice(c->cfg.device);
   mivi_status_t s = ensure_work(c, c->cfg.n_mc);
   if (s) return s;
-  prepare_tables(c, c->cfg.n_mc);
+  if (!prepare_tables(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
   if ((s = reserve_target(c, c->cfg.n_mc))) return s;
   const size_t plen = (size_t)mivi_params_len(c), es = c->esize;
   const double eta = l.eta, clip_eps = (l.op == 1) ? l.clip_epsilon : (double)NAN;   // NaN = no ClipScale

@@ -21,6 +21,7 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
   const bool fr = c->cfg.family == MIVI_FULLRANK;
   c->cur = 0;
   const bool lds = fr && lds_route(c, params, M, 1, out);   // second-generation kernels: stages 2 / 4 include their reduce
+  if (fr && !lds && !fr_prepare(c, M)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");   // (the warm estimate has: the stage launches below read its tables)
   if (which == 6 || which == 7) return fail(c, MIVI_ERR_UNSUPPORTED, "which = 6 / 7: the split-K product / reduce stages were removed (round 3)");
   // which = 10 / 11: the product / VJP launch of FOUR lane-batched estimates, as mivi_estimate_gradient_n issues them.  A batch of eight
   // estimates first (it creates and fills the four contexts), then the four contexts' launches are recorded once and the ONE launch

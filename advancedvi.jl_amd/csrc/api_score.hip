@@ -27,6 +27,7 @@ static mivi_status_t run_score_estimate(mivi_ctx *c, const void *params, uint64_
   const bool full = c->cfg.family == MIVI_FULLRANK;
   mivi_status_t s = ensure_work(c, M);
   if (s) return s;
+  if (!fr_prepare(c, M)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
   const bool stl2 = full && stl2_shape_ok(c, M);
   if (full) {
     const int dP = c->dP;

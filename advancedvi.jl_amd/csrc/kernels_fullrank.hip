@@ -1108,15 +1108,7 @@ __global__ __launch_bounds__(256) void k_rt_from_z(int d, int M, int MP, const T
 // ---------------------------------------------------------------------------------------------
 // Host side: work tables (XCD-aware block -> tile maps) and launchers
 // ---------------------------------------------------------------------------------------------
-static void upload_tab(mivi_ctx *c, DevBuf &b, const std::vector<int2> &t) {
-  const size_t bytes = t.size() * sizeof(int2);
-  if (b.bytes < bytes) {
-    if (b.p) (void)hipFree(b.p);
-    (void)hipMalloc(&b.p, bytes);
-    b.bytes = bytes;
-  }
-  (void)hipMemcpy(b.p, t.data(), bytes, hipMemcpyHostToDevice);
-}
+static bool upload_tab(mivi_ctx *c, DevBuf &b, const std::vector<int2> &t) { return upload(c, b, t.data(), t.size() * sizeof(int2)) == MIVI_OK; }
 
 // move work from the fullest to the emptiest XCD list until they differ by at most one item
 static void rebalance(std::vector<std::vector<int2>> &lists) {
@@ -1141,9 +1133,13 @@ static std::vector<int2> interleave_xcd(const std::vector<std::vector<int2>> &li
   return tab;
 }
 
-// (re)build the tables for M samples per launch
-static void ensure_tabs(mivi_ctx *c, int M) {
-  if (c->tab_M == M && c->tabA.p) return;
+// the tables are the ones for M samples per launch (what a launcher below asks before it reads them)
+static bool tabs_ready(const mivi_ctx *c, int M) { return c->tab_M == M && c->tabA.p; }
+
+// (re)build the tables for M samples per launch (false: an allocation or upload failed, c->err says which; the tables then count as not built)
+static bool ensure_tabs(mivi_ctx *c, int M) {
+  if (tabs_ready(c, M)) return true;
+  c->tab_M = -1;
   const int d = c->cfg.d, nb = (d + 31) / 32, ncb = (M + 31) / 32;
   {  // sample: pairs (p, nb-1-p), XCD x owns pairs p = x (mod 8), all column blocks
     const int npairs = (nb + 1) / 2;
@@ -1152,7 +1148,7 @@ static void ensure_tabs(mivi_ctx *c, int M) {
       for (int cb = 0; cb < ncb; ++cb) lists[pq % 8].push_back(make_int2(pq, cb));
     auto tab = interleave_xcd(lists);
     c->nA = (int)tab.size();
-    upload_tab(c, c->tabA, tab);
+    if (!upload_tab(c, c->tabA, tab)) return false;
   }
   {  // dense target: XCD x owns row-blocks ib = x (mod 8)
     std::vector<std::vector<int2>> lists(8);
@@ -1160,7 +1156,7 @@ static void ensure_tabs(mivi_ctx *c, int M) {
       for (int cb = 0; cb < ncb; ++cb) lists[ib % 8].push_back(make_int2(ib, cb));
     auto tab = interleave_xcd(lists);
     c->nD = (int)tab.size();
-    upload_tab(c, c->tabD, tab);
+    if (!upload_tab(c, c->tabD, tab)) return false;
   }
   {  // vjp: 8x8 super-blocks of the lower triangle, longest-processing-time assignment to the 8 XCDs
     std::vector<std::vector<int2>> lists(8);
@@ -1189,24 +1185,29 @@ static void ensure_tabs(mivi_ctx *c, int M) {
     }
     auto tab = interleave_xcd(lists);
     c->nB = (int)tab.size();
-    upload_tab(c, c->tabB, tab);
+    if (!upload_tab(c, c->tabB, tab)) return false;
   }
   c->tab_M = M;
+  return true;
 }
 
-void prepare_tables(mivi_ctx *c, int M) {
-  if (lds_path_shape_ok(c, M) && (c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS)) (void)lds_prepare(c, M);
-  if (c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32) ensure_tabs(c, M);
-  if (c->cfg.family != MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && c->target == TGT_DENSE_GAUSS) ensure_tabs(c, M);   // (mean-field, low-rank: the dense target's tiles)
+bool fr_prepare(mivi_ctx *c, int M) {
+  if (c->cfg.dtype != MIVI_F32) return true;   // (the f64 kernels derive their tile from blockIdx)
+  if (c->cfg.family != MIVI_FULLRANK && c->target != TGT_DENSE_GAUSS) return true;   // (mean-field, low-rank: the dense target's tiles only)
+  return ensure_tabs(c, M);
+}
+bool prepare_tables(mivi_ctx *c, int M) {
+  if (lds_path_shape_ok(c, M) && (c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS) && !lds_prepare(c, M)) return false;
+  return fr_prepare(c, M);
 }
 
 int eps_blocks(const mivi_ctx *c, int M) { return ((c->cfg.d + 15) / 16) * ((M + 63) / 64); }
 int fr_sample_blocks(const mivi_ctx *c, int M) {
-  if (c->cfg.dtype == MIVI_F32) { ensure_tabs(const_cast<mivi_ctx *>(c), M); return c->nA; }
+  if (c->cfg.dtype == MIVI_F32) return tabs_ready(c, M) ? c->nA : 0;
   return ((c->cfg.d + 31) / 32) * ((M + 31) / 32);
 }
 int fr_dense_blocks(const mivi_ctx *c, int M) {
-  if (c->cfg.dtype == MIVI_F32) { ensure_tabs(const_cast<mivi_ctx *>(c), M); return c->nD; }
+  if (c->cfg.dtype == MIVI_F32) return tabs_ready(c, M) ? c->nD : 0;
   return ((c->cfg.d + 31) / 32) * ((M + 31) / 32);
 }
 int fr_ld_blocks(const mivi_ctx *c) { return (c->cfg.d + 31) / 32; }
@@ -1293,10 +1294,14 @@ bool f64_valu() {
   return v;
 }
 
+// The f32 launchers below read the tables their driver prepared (fr_prepare).  Tables built for another sample count would send a kernel
+// past its buffers, so a launcher that does not find the ones for its M launches nothing and leaves the reason in c->err.
+static void tabs_missing(mivi_ctx *c) { c->err = "full-rank work tables: a launch came before fr_prepare for its sample count"; }
+
 // Z = mu + C eps (+ fused target).  prev != nullptr: one extra workgroup assembles the PREVIOUS estimate's value.
 void launch_fr_sample(mivi_ctx *c, const void *params, int M, int fused_target, void *Z, const ValueJob *prev) {
   if (c->cfg.dtype == MIVI_F32) {
-    ensure_tabs(c, M);
+    if (!tabs_ready(c, M)) return tabs_missing(c);
     FrArgs<float> a = fr_args<float>(c, params, M);
     a.fused_target = fused_target;
     a.Z = (float *)Z;
@@ -1338,7 +1343,7 @@ void launch_fr_sample(mivi_ctx *c, const void *params, int M, int fused_target, 
 void launch_fr_dense_target(mivi_ctx *c, int M, int want_grad) {
   (void)want_grad;
   if (c->cfg.dtype == MIVI_F32) {
-    ensure_tabs(c, M);
+    if (!tabs_ready(c, M)) return tabs_missing(c);
     FrArgs<float> a = fr_args<float>(c, nullptr, M);
     a.work_tab = (const int2 *)c->tabD.p;
     a.n_work = 0x7fffffff;
@@ -1361,7 +1366,7 @@ void launch_fr_dense_target(mivi_ctx *c, int M, int want_grad) {
 void launch_fr_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, const EpsJob *next, const ValueJob *self,
                    const FusedUpdate *upd) {
   if (c->cfg.dtype == MIVI_F32) {
-    ensure_tabs(c, M);
+    if (!tabs_ready(c, M)) return tabs_missing(c);
     FrArgs<float> a = fr_args<float>(c, params, M);
     a.out = out;
     if (upd) a.upd = *upd;

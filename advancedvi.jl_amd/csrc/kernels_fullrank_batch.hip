@@ -1084,15 +1084,6 @@ constexpr int kBM = 128, kBN = 128;
 constexpr int kWJ = FB_WJ;      // 32-column blocks per wave (k_fb_prod / k_fb_vjp): 2 = four waves of 64 x 64 per tile, 1 = eight waves of 64 x 32
 constexpr int kOwnCuTilesPerCU10 = 17;   // (x 0.1) tiles per CU up to which the triangular products keep one workgroup per CU at d = 1024 (fb_launch_compute: scaled by the heaviest tile's chain)
 // (the product: register prefetch + one workgroup per CU at few lanes; the VJP: plain loops, three workgroups per CU)
-
-void fb_upload(DevBuf &b, const void *src, size_t bytes) {
-  if (b.bytes < bytes || !b.p) {
-    if (b.p) (void)hipFree(b.p);
-    (void)hipMalloc(&b.p, bytes);
-    b.bytes = bytes;
-  }
-  (void)hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
-}
 }  // namespace
 
 // Round 6: d and n_mc are multiples of 32 (round 5: of 128); the geometry is padded to whole 128 x 128 tiles (fb_pad), whole 32-blocks of
@@ -1201,11 +1192,9 @@ const FbTab *fb_prepare(mivi_ctx *c, int M, int L) {
   for (size_t i = 0; i < mx; ++i)
     for (int x = 0; x < 8; ++x)
       if (i < lists[x].size()) prod3.push_back(lists[x][i]);
-  fb_upload(t.prod, prod.data(), prod.size() * sizeof(int4));
-  fb_upload(t.vjp, vjp.data(), vjp.size() * sizeof(int4));
-  fb_upload(t.prod2, prod2.data(), prod2.size() * sizeof(int4));
-  fb_upload(t.prod3, prod3.data(), prod3.size() * sizeof(int4));
-  if (!t.prod.p || !t.vjp.p || !t.prod2.p || !t.prod3.p) return nullptr;
+  if (upload(c, t.prod, prod.data(), prod.size() * sizeof(int4)) || upload(c, t.vjp, vjp.data(), vjp.size() * sizeof(int4)) ||
+      upload(c, t.prod2, prod2.data(), prod2.size() * sizeof(int4)) || upload(c, t.prod3, prod3.data(), prod3.size() * sizeof(int4)))
+    return nullptr;
   t.n_prod2 = (int)prod2.size();
   t.n_prod = (int)prod.size();
   t.n_vjp = (int)vjp.size();
@@ -1279,6 +1268,8 @@ void fb_launch_compute(mivi_ctx *c, const FbStep &s, hipStream_t stream, int whi
   a.parts = (float *)s.parts; a.part_stride = s.part_stride;
   if (s.obj) { a.ent_kind = s.ent_kind; a.M_total = s.M; }
 #ifdef MIVI_DEV
+  // The one allocation outside ensure / DevBuf::release (api_core.hip), on purpose: a developer timeline buffer that lives as long as the
+  // process.  It must not become a static DevBuf: its destructor would call into a HIP runtime that is already torn down at exit.
   static long long *dbg_buf = nullptr;
   static const bool dbg_on = getenv("MIVI_FB_DBG") != nullptr;
   if (dbg_on && !dbg_buf) (void)hipMalloc(&dbg_buf, 2 * 8192 * 8 * sizeof(long long));

@@ -1228,22 +1228,13 @@ std::vector<Item> interleave8(std::vector<std::vector<Item>> &lists) {
   return out;
 }
 
-void upload(mivi_ctx *c, DevBuf &b, const void *src, size_t bytes) {
-  if (b.bytes < bytes || !b.p) {
-    if (b.p) (void)hipFree(b.p);
-    (void)hipMalloc(&b.p, bytes);
-    b.bytes = bytes;
-  }
-  (void)hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
-}
-
 std::vector<int4> pack(const std::vector<Item> &v) {
   std::vector<int4> t(v.size());
   for (size_t i = 0; i < v.size(); ++i) t[i] = make_int4(v[i].rb | (v[i].cb << 16), v[i].s0 | (v[i].s1 << 16), v[i].slab, v[i].flags);
   return t;
 }
 
-void build_vjp(mivi_ctx *c, int d, int M, int tile, DevBuf &tab, int &n_items) {
+bool build_vjp(mivi_ctx *c, int d, int M, int tile, DevBuf &tab, int &n_items) {   // (false, as build_strips: the list could not be uploaded)
   const int kVBM = tile, kVBN = tile;   // (shadows the 32 x 32 constants: the same table for either tile size)
   const int nrb = d / kVBM;
   const int SR = 256 / kVBM, SC = 256 / kVBN;   // super-blocks of 256 x 256 elements: one XCD's L2 holds their operands
@@ -1272,14 +1263,14 @@ void build_vjp(mivi_ctx *c, int d, int M, int tile, DevBuf &tab, int &n_items) {
   auto items = interleave8(lists);
   n_items = (int)items.size();
   auto packed = pack(items);
-  upload(c, tab, packed.data(), packed.size() * sizeof(int4));
+  return upload(c, tab, packed.data(), packed.size() * sizeof(int4)) == MIVI_OK;
 }
 
 // strips of k_fr_vjp32s: up to NS consecutive tiles of one block row per workgroup.  XCD x (= workgroup index % 8) takes whole 8 x 8-tile
 // super-blocks of the lower triangle (its L2 then holds 8 W panels + 8 eps panels per super-block: 5 MB over the fabric per estimate at the
 // north star, against 9 MB when an XCD owns whole block rows and so pulls every eps panel), super-blocks dealt heaviest first onto the
 // lightest XCD; with fewer than eight super-blocks (d < 1024) the block rows {x, 15 - x, 16 + x, 31 - x} instead.
-void build_strips(mivi_ctx *c, int d, int NS, DevBuf &tab, int &n_items) {
+bool build_strips(mivi_ctx *c, int d, int NS, DevBuf &tab, int &n_items) {
   const int nrb = d / 32, nsr = (nrb + 7) / 8;
   std::vector<std::vector<int4>> lists(8);
   if (nsr * (nsr + 1) / 2 >= 8) {
@@ -1328,7 +1319,7 @@ void build_strips(mivi_ctx *c, int d, int NS, DevBuf &tab, int &n_items) {
   for (size_t i = 0; i < L; ++i)
     for (int x = 0; x < 8; ++x) out.push_back(i < lists[x].size() ? lists[x][i] : make_int4(0, 0, 0, 0));
   n_items = (int)out.size();
-  upload(c, tab, out.data(), out.size() * sizeof(int4));
+  return upload(c, tab, out.data(), out.size() * sizeof(int4)) == MIVI_OK;
 }
 
 }  // namespace
@@ -1351,10 +1342,10 @@ bool lds_prepare(mivi_ctx *c, int M) {
   if (c->lds_M == M && c->lds_tabV.p) return true;
   invalidate_graph(c);   // a captured graph bakes the list contents and sizes
   const int d = c->cfg.d;
-  build_vjp(c, d, M, 32, c->lds_tabV, c->lds_nV);
-  build_vjp(c, d, M, 64, c->lds_tabV64, c->lds_nV64);
-  build_strips(c, d, vjp_strip_len() ? vjp_strip_len() : 1, c->lds_tabS, c->lds_nS);
-  if (!c->lds_tabV.p || !c->lds_tabV64.p || !c->lds_tabS.p) return false;
+  c->lds_M = -1;   // (a failure below leaves no list looking valid)
+  if (!build_vjp(c, d, M, 32, c->lds_tabV, c->lds_nV) || !build_vjp(c, d, M, 64, c->lds_tabV64, c->lds_nV64) ||
+      !build_strips(c, d, vjp_strip_len() ? vjp_strip_len() : 1, c->lds_tabS, c->lds_nS))
+    return false;
   c->lds_M = M;
   return true;
 }
@@ -1365,7 +1356,7 @@ bool lds_stein_ok(const mivi_ctx *c, int M) {
   static const bool off = getenv("MIVI_STEIN_GEN1") != nullptr;   // A/B: the first-generation kernel
   return !off && lds_path_shape_ok(c, M) && !f32_mfma();   // (d is a multiple of 64: the padded leading dimension dP equals d)
 }
-void launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first, double scale, double n, void *grad, void *logpi,
+bool launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first, double scale, double n, void *grad, void *logpi,
                             const ValueJob *self) {
   const int d = c->cfg.d, nb = d / 64;
   if (c->lds_st_d != d) {   // full square of 64 x 64 tiles; 4 x 4 super-blocks (256 x 256 elements: one XCD's L2 holds their operands)
@@ -1377,7 +1368,7 @@ void launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first
           for (int cb = sc * 4; cb < sc * 4 + 4 && cb < nb; ++cb) lists[sbi % 8].push_back(Item{rb, cb, 0, 0, 0, 0, 1});
     auto items = interleave8(lists);
     auto packed = pack(items);
-    upload(c, c->lds_tabSt, packed.data(), packed.size() * sizeof(int4));
+    if (upload(c, c->lds_tabSt, packed.data(), packed.size() * sizeof(int4))) return false;
     c->lds_nSt = (int)items.size();
     c->lds_st_d = d;
   }
@@ -1404,6 +1395,7 @@ void launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first
     grid += 1;
   }
   hipLaunchKernelGGL((k_fr_vjp64<false, true, true>), dim3(grid), dim3(512), 0, c->stream, a);
+  return true;
 }
 
 int lds_ld_blocks(const mivi_ctx *c) { return c->cfg.d / 64; }

@@ -1148,28 +1148,17 @@ __global__ __launch_bounds__(256) void k_lr_greduce(int S, size_t len, float *g_
   g_part[e] = s;
 }
 
-// grow-only device buffer; false on allocation failure (the buffer is then empty)
-static bool grow(DevBuf &b, size_t bytes) {
-  if (b.bytes >= bytes) return true;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  if (hipMalloc(&b.p, bytes) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
-  b.bytes = bytes;
-  return true;
-}
-
 bool logreg_prepare_f32(mivi_ctx *c) {
   // builds Xrm in c->lr_Xrm (called by mivi_set_target_logreg for MIVI_F32)
   const int p = c->cfg.d - 1;
   const int ldx = (p + 31) / 32 * 32;
   const size_t n16 = ((size_t)c->lr_n + 15) / 16 * 16;   // zero rows up to a whole 16-row stage (k_lr_xtr_f16x2)
   const size_t bytes = n16 * ldx * sizeof(float);
-  if (!grow(c->lr_Xrm, bytes)) return false;
+  if (ensure(c, c->lr_Xrm, bytes, false)) return false;
   if (n16 > (size_t)c->lr_n &&
       hipMemsetAsync((float *)c->lr_Xrm.p + (size_t)c->lr_n * ldx, 0, (n16 - (size_t)c->lr_n) * ldx * sizeof(float), c->stream) != hipSuccess)
     return false;
-  if (!grow(c->lr_xmax, 64) || hipMemsetAsync(c->lr_xmax.p, 0, 64, c->stream) != hipSuccess) return false;
+  if (ensure(c, c->lr_xmax, 64, false) || hipMemsetAsync(c->lr_xmax.p, 0, 64, c->stream) != hipSuccess) return false;
   dim3 grid((unsigned)((c->lr_n + 63) / 64), (ldx + 63) / 64);
   hipLaunchKernelGGL(k_lr_make_xrm, grid, dim3(256), 0, c->stream, (long long)c->lr_n, p, ldx, (const float *)c->lr_X,
                      (float *)c->lr_Xrm.p, (unsigned *)c->lr_xmax.p);
@@ -1177,19 +1166,17 @@ bool logreg_prepare_f32(mivi_ctx *c) {
   if ((double)c->lr_n * p >= 1.0e5) {
     const long long nrb32 = (c->lr_n + 127) / 128 * 4;
     const size_t nfr = (size_t)nrb32 * (ldx / 16);
-    if (!grow(c->lr_XA, nfr * kFrag * 4)) return false;
+    if (ensure(c, c->lr_XA, nfr * kFrag * 4, false)) return false;
     hipLaunchKernelGGL(k_lr_xplanes, dim3((unsigned)((nfr + 3) / 4)), dim3(256), 0, c->stream, (long long)c->lr_n, nrb32, ldx, (const float *)c->lr_Xrm.p,
                        (const unsigned *)c->lr_xmax.p, (unsigned *)c->lr_XA.p);
     const long long nrg = nrb32 / 4 * 8;
     const size_t nfb = (size_t)((ldx + 127) / 128 * 4) * nrg;   // (whole 128-feature groups: k_lr_xtr_planes stages four 32-feature blocks per group)
-    if (!grow(c->lr_XB, nfb * kFrag * 4)) return false;
+    if (ensure(c, c->lr_XB, nfb * kFrag * 4, false)) return false;
     hipLaunchKernelGGL(k_lr_xbplanes, dim3((unsigned)((nfb + 3) / 4)), dim3(256), 0, c->stream, (long long)c->lr_n, nrg, ldx, (const float *)c->lr_Xrm.p,
                        (const unsigned *)c->lr_xmax.p, (unsigned *)c->lr_XB.p);
   } else {
-    if (c->lr_XA.p) (void)hipFree(c->lr_XA.p);
-    if (c->lr_XB.p) (void)hipFree(c->lr_XB.p);
-    c->lr_XA = DevBuf{};
-    c->lr_XB = DevBuf{};
+    c->lr_XA.release();
+    c->lr_XB.release();
   }
   return true;
 }
@@ -1306,8 +1293,8 @@ int logreg_kernel_bits(const mivi_ctx *c, int M) {
 }
 bool logreg_reserve(mivi_ctx *c, int M) {
   const LrGeom g = lr_geom(c, M);
-  if (g.planes && !grow(c->lr_ZP, (size_t)(M / 32) * (((c->cfg.d - 1 + 31) / 32 * 32) / 16) * kFrag * 4)) return false;
-  return grow(c->lr_scratch, g.need_R + g.need_g) && grow(c->lr_part, g.need_ll);
+  if (g.planes && ensure(c, c->lr_ZP, (size_t)(M / 32) * (((c->cfg.d - 1 + 31) / 32 * 32) / 16) * kFrag * 4, false)) return false;
+  return !ensure(c, c->lr_scratch, g.need_R + g.need_g, false) && !ensure(c, c->lr_part, g.need_ll, false);
 }
 
 static bool logreg_mfma(mivi_ctx *c, int M, int want_grad) {
@@ -1339,7 +1326,7 @@ static bool logreg_mfma(mivi_ctx *c, int M, int want_grad) {
   const bool part = M % 128 != 0 && M % 128 <= 96;   // whole 32-sample tiles of the last 128-sample group are empty
   if (geo.planes) {
     const int ng = a.ldx / 16, nfz = (M / 32) * ng;
-    if (!grow(c->lr_ZP, (size_t)nfz * kFrag * 4)) return false;
+    if (ensure(c, c->lr_ZP, (size_t)nfz * kFrag * 4, false)) return false;
     a.XA = (const unsigned *)c->lr_XA.p;
     a.ZP = (unsigned *)c->lr_ZP.p;
     a.XB = (const unsigned *)c->lr_XB.p;

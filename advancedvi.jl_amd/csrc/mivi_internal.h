@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mivi.h"
@@ -227,17 +228,30 @@ struct ColTargetArgs {  // standalone per-column targets: Z -> (ell, G)
 // --------------------------------------------------------------------------------------------
 // Context
 // --------------------------------------------------------------------------------------------
-struct DevBuf {
+// Device memory of the library.  A DevBuf OWNS what `ensure` gave it (api_core.hip: the one function that allocates, next to release(), the
+// one that frees) and frees it when it is released or destroyed; or it is a VIEW of memory another buffer owns (borrow: a child context's
+// target vectors and status word), which it never frees.  Move-only: a copy would be a second owner.  p and bytes are there to be read;
+// ensure, borrow and release are what writes them.
+struct __attribute__((visibility("hidden"))) DevBuf {
   void *p = nullptr;
   size_t bytes = 0;
+  bool owned = false;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept { *this = static_cast<DevBuf &&>(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); std::swap(owned, o.owned); return *this; }   // (o takes what this held, and frees it)
+  ~DevBuf() { release(); }
+  void borrow(void *ptr, size_t n) { release(); p = ptr; bytes = n; }   // a view of [ptr, ptr + n): whoever owns it outlives this buffer
+  void release();                                                       // frees what it owns, forgets what it borrowed: the buffer is empty
 };
 
 // third-generation batch engine (kernels_fullrank_batch.hip): work tables per lane count, per-lane work buffers (base + lane * stride)
-struct FbTab {
+struct __attribute__((visibility("hidden"))) FbTab {
   DevBuf prod, vjp, prod2, prod3;         // work tables: the draw's product, the VJP, the dense target's product, the sticking-the-landing product
   int n_prod = 0, n_vjp = 0, n_prod2 = 0, L = 0, M = 0;
 };
-struct FbTables {
+struct __attribute__((visibility("hidden"))) FbTables {
   FbTab tab[4];                           // per lane count (the full step's, the last shorter step's, other batch lengths'), round robin
   int next_tab = 0;
   DevBuf CA, epsP, WV, ell, he, ld, grads, values;   // operand planes (tril(C) once per call; eps -- ONE orientation since round 6 -- and W per lane)
@@ -337,11 +351,30 @@ struct LaneRecorder {
 
 }  // namespace mivi
 
-struct mivi_ctx {
-  mivi_config_t cfg;
+// The streams and events a context created.  A base of mivi_ctx, so that they are destroyed AFTER the context's buffers are freed (members
+// go before bases): no buffer outlives the stream its last launch ran on.
+struct mivi_ctx_streams {
+  static constexpr int kMaxKids = 15;   // up to sixteen contexts (eight are used); at most FOUR graph branches (a forked graph with five branches crashed inside hipGraphLaunch,
+                                       // hip::Graph::UpdateStreams, after a re-capture on ROCm 7.0's runtime; four is also the number of hardware queues)
   hipStream_t stream = nullptr;
   hipStream_t cap_stream = nullptr;   // internal stream used only for graph capture
   bool own_stream = false;
+  // Pipelined exchange (mivi_estimate_gradient_dist_n): the collective of estimate t runs on comm_stream under the kernels of t + 1;
+  // partial vectors double-buffered (dist_P, dist_P2), event pairs per parity
+  hipStream_t comm_stream = nullptr;
+  hipEvent_t ev_part[2] = {nullptr, nullptr}, ev_comm[2] = {nullptr, nullptr};
+  hipStream_t comm_stream2 = nullptr;
+  // the batch engine's sharded batches (api_batch.hip fb_batch, dist): the all-reduce + finalisation of step s on fb_comm_stream under the
+  // kernels of step s + 1 (streams of their own: comm_stream carries the CU mask the peer-to-peer pipeline needs)
+  hipStream_t fb_comm_stream = nullptr;
+  hipEvent_t fb_ev_part[2] = {nullptr, nullptr}, fb_ev_comm[2] = {nullptr, nullptr};
+  hipEvent_t ev_fork = nullptr, ev_join[kMaxKids] = {};   // interleaved chains: the fork of a recording's branches, the join of child j's
+  __attribute__((visibility("hidden"))) ~mivi_ctx_streams();   // api_core.hip
+};
+
+// Every device buffer below is a member and nothing else: ensure() fills it where it is needed, the context's destruction returns it.
+struct mivi_ctx : mivi_ctx_streams {
+  mivi_config_t cfg;
   std::string err;
   int target = mivi::TGT_NONE;
   int M_total = 0;
@@ -368,21 +401,11 @@ struct mivi_ctx {
   int comm_rank = 0, comm_world = 1;
   mivi::DevBuf dist_P, dist_S, dist_F;
   bool bij_on = false;
-  // Pipelined exchange (mivi_estimate_gradient_dist_n): the collective of estimate t runs on comm_stream under the kernels of t + 1;
-  // partial vectors double-buffered (dist_P, dist_P2), event pairs per parity
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t ev_part[2] = {nullptr, nullptr}, ev_comm[2] = {nullptr, nullptr};
-  mivi::DevBuf dist_P2, dist_ring[6];       // ring of partial vectors (two for the RCCL pipeline, eight = two groups of four for the peer-to-peer pipeline)
-  hipStream_t comm_stream2 = nullptr;
-  // the batch engine's sharded batches (api_batch.hip fb_batch, dist): the all-reduce + finalisation of step s on fb_comm_stream under the
-  // kernels of step s + 1 (streams of their own: comm_stream carries the CU mask the peer-to-peer pipeline needs)
-  hipStream_t fb_comm_stream = nullptr;
-  hipEvent_t fb_ev_part[2] = {nullptr, nullptr}, fb_ev_comm[2] = {nullptr, nullptr};
+  mivi::DevBuf dist_P2, dist_ring[6];       // the pipelined exchange's second partial vector; ring of partial vectors (two for the RCCL pipeline, eight = two groups of four for the peer-to-peer pipeline)
   int p2p_pipe_state = 1;   // persistent peer-to-peer pipeline in batched calls: 1 on, -1 off (mivi_p2p_set_pipeline: serial steps)
   int dist_route = 0;   // mivi_comm_set_route: 0 by size, 1 ncclAllReduce, 2 ncclReduceScatter / ncclAllGather, 3 peer-to-peer kernel
   // peer-to-peer exchange over xGMI (kernels_p2p.hip): one uncached allocation per rank [stage | final | flags], mapped into the peers by IPC
-  void *p2p_buf = nullptr;
-  size_t p2p_bytes = 0;
+  mivi::DevBuf p2p_buf;   // (fine-grained device memory)
   void *p2p_peer[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // mapped bases (own entry = p2p_buf)
   bool p2p_opened[8] = {false, false, false, false, false, false, false, false};                   // hipIpcOpenMemHandle'd (to be closed)
   mivi::DevBuf rows_eps;   // kernels_fullrank_rows.hip: eps of all steps of a device-resident loop call
@@ -474,25 +497,35 @@ struct mivi_ctx {
   // batch is dealt round-robin onto `1 + n_kids` chains -- this context and child contexts with their own work buffers and streams --
   // whose kernels overlap on the device (the product of one chain's estimate runs beside the VJP of another's).
   int idx_stride = 1;            // estimate-index step between consecutive estimates of THIS context's chain
-  bool is_child = false;         // target buffers are borrowed from the parent
+  bool is_child = false;         // t_mean / t_istd / t_prec and status are views of the parent's (sync_kid, ensure_kids)
   int n_cu = 0;                  // compute units of the device, LDS bytes a workgroup may take: what the launch-free loops with a grid-wide
   size_t lds_max = 64 * 1024;    // exchange per step check their grids against (hipOccupancyMaxActiveBlocksPerMultiprocessor x n_cu >= grid)
   bool exchange_lost = false;    // a grid-wide exchange expired once on this context (status bit 8): those loops are not taken again
   int last_status_bits = 0;      // the sticky device flags read_status saw last
   mivi::DevBuf snap;             // parameters / optimiser state / average before a loop with a grid-wide exchange (restored if it is lost)
-  static constexpr int kMaxKids = 15;   // up to sixteen contexts (eight are used); at most FOUR graph branches (a forked graph with five branches crashed inside hipGraphLaunch,
-                                       // hip::Graph::UpdateStreams, after a re-capture on ROCm 7.0's runtime; four is also the number of hardware queues)
   mivi_ctx *kids[kMaxKids] = {};
   int n_kids = 0;
   unsigned long long target_gen = 0, kid_gen = ~0ull;   // parent: bumped whenever a captured graph is invalidated; child: the generation it mirrors
-  hipEvent_t ev_fork = nullptr, ev_join[kMaxKids] = {};
   bool dist_capture_refused = false;   // the sharded batch could not be captured into a hipGraph (RCCL route): issued eagerly from then on
   bool dist_direct = false;      // sharded estimates on the peer-to-peer route: the partial kernels store straight into the owners' staging areas
   bool dist_lane4 = false;       // pipelined sharded batches: the compute chain is lane-batched (four contexts per launch)
   mivi::LaneRecorder *rec = nullptr;   // lane-batched estimates: non-null while this context is lane `lane_id` of a branch whose launchers record
   int lane_id = 0;                     // into `rec` instead of launching (set and cleared by LaneScope, api_common.h)
   mivi::DevBuf kid_out[kMaxKids];       // value (16 bytes) + gradient of the child chains that do not hold the batch's last estimate
+
+  // The communicator and the peer-to-peer areas (mivi_p2p_detach closes the peers' IPC handles before the area is released), the graph cache;
+  // then the buffers go (members), then the streams and events (the base).  The wait for the stream and the children are mivi_destroy's.
+  ~mivi_ctx() { (void)mivi_comm_destroy(this); graph.drop(); }
 };
+
+#pragma GCC visibility push(hidden)   // api_core.hip: the library's device memory (DevBuf); internal to libmivi like everything in api_common.h
+// b holds at least `bytes` bytes (0: 16) afterwards.  Grow-only: a buffer that is large enough is kept, with its contents; otherwise it is
+// released and allocated anew (fine_grained: as fine-grained device memory, the peer-to-peer area), and zeroed by a memset on c->stream if `zero`.
+mivi_status_t ensure(mivi_ctx *c, mivi::DevBuf &b, size_t bytes, bool zero, bool fine_grained = false);
+mivi_status_t ensure_zeroed(mivi_ctx *c, mivi::DevBuf &b, size_t bytes);         // ensure, and the first `bytes` bytes are zero (a memset on c->stream) whether the buffer was kept or not
+mivi_status_t upload(mivi_ctx *c, mivi::DevBuf &b, const void *src, size_t bytes);   // ensure, then a synchronous copy of `bytes` host bytes into it
+int32_t live_allocations();   // what this process holds of them right now, over all contexts (mivi_batch_info what = 5)
+#pragma GCC visibility pop
 
 // The one precision dispatch of the host launch layer: f(T{}) with T the context's element type, its result returned.  A launch whose two
 // precisions differ in nothing but T goes through it; one whose precisions take different routes keeps its explicit test on cfg.dtype.
@@ -537,7 +570,11 @@ void launch_fr_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, c
                    const ValueJob *self = nullptr, const FusedUpdate *upd = nullptr);
 int fr_ld_blocks(const mivi_ctx *c);
 bool f64_valu();   // MIVI_F64_VALU=1: keep the f64 full-rank tiles on the vector ALU
-void prepare_tables(mivi_ctx *c, int M);   // build + upload the MFMA work tables (no-op for f64 / mean-field)
+// Build + upload the first-generation MFMA kernels' work tables for M samples per launch, once per M (nothing to do for f64, nor for the
+// other families without the dense target).  A driver calls it before its first launch_fr_* / fr_*_blocks for that M; false: an allocation
+// or upload failed.  prepare_tables: the same and the second-generation work lists where the shape takes them (lds_prepare), ahead of a capture.
+__attribute__((visibility("hidden"))) bool fr_prepare(mivi_ctx *c, int M);
+bool prepare_tables(mivi_ctx *c, int M);
 void launch_fr_dense_target(mivi_ctx *c, int M, int want_grad);
 void launch_rt_from_z(mivi_ctx *c, int M);
 void launch_fr_stl(mivi_ctx *c, const void *params, int M, const void *rhs = nullptr, void *out = nullptr);
@@ -551,8 +588,8 @@ size_t target_hess2_bytes(const mivi_ctx *c);
 bool target_hess2_begin(mivi_ctx *c);
 void target_hess2_accumulate(mivi_ctx *c, int Mc);
 void target_hess2_finish(mivi_ctx *c, int n_samples, void *hess);
-int fr_sample_blocks(const mivi_ctx *c, int M);
-int fr_dense_blocks(const mivi_ctx *c, int M);
+int fr_sample_blocks(const mivi_ctx *c, int M);   // workgroups (= ell partials) of launch_fr_sample / launch_fr_dense_target: read off the tables
+int fr_dense_blocks(const mivi_ctx *c, int M);    // fr_prepare built (f32; 0 if it has not)
 int eps_blocks(const mivi_ctx *c, int M);
 
 // kernels_fullrank_lds.hip (f32, d and M multiples of 64)
@@ -578,8 +615,8 @@ void launch_lanes_value(mivi_ctx *c, const void *params, LaneRecorder &rec);    
 bool lds_bf16x3();   // products on the bf16 matrix cores (three-way exact operand split); MIVI_FR_F32MFMA=1 turns it off
 void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, const ValueJob *self, const FusedUpdate *upd);
 bool lds_stein_ok(const mivi_ctx *c, int M);
-void launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first, double scale, double n, void *grad, void *logpi,
-                            const ValueJob *self);
+bool launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first, double scale, double n, void *grad, void *logpi,
+                            const ValueJob *self);   // false: its tile table could not be uploaded (nothing was launched)
 void invalidate_graph(mivi_ctx *c);            // api_core.hip: drop the cached hipGraphExec and the eps speculation
 
 // kernels_fullrank_batch.hip (f32, diagonal-Gaussian target, d % 128 == 0, M % 128 == 0): L estimates at the same parameters per launch

@@ -694,7 +694,9 @@ int32_t mivi_batch_lanes(const mivi_ctx_t *ctx, int32_t count);
  * these (16-byte aligned) device parameters take the batch engine, 0 otherwise; 1: matrix-pipe products per 32 x 32 x 16 block of the engine's
  * split-operand contractions (3: f16 hi / lo planes); 2: bytes per operand-plane element (4); 3: 1 once a launch-free optimisation loop's grid-wide
  * exchange was lost on this context (mivi_optimize_loop then restored the caller's state, re-ran the steps on the graph of launches and stays there);
- * 4: the number of hipGraphs recorded into the context's graph cache so far -- unchanged across two calls means the second one replayed. */
+ * 4: the number of hipGraphs recorded into the context's graph cache so far -- unchanged across two calls means the second one replayed;
+ * 5: the number of device allocations the library holds right now in this process, over all contexts (the library's one allocate / free pair
+ * counts them): equal before a context's creation and after its mivi_destroy means the context returned every allocation it made. */
 int32_t mivi_batch_info(const mivi_ctx_t *ctx, const void *params_dev, int32_t what);
 
 /* ---- measurement hook (bench.py roofline leg) --------------------------------------------------------- *
