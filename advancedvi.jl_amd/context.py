@@ -625,6 +625,11 @@ class MiviContext:
         context's creation and after its close() = the context returned everything."""
         return int(self.lib.mivi_batch_info(self.h, None, 5))
 
+    def live_handles(self):
+        """Streams, events and graph execs the library holds right now in this process, over all contexts (mivi_batch_info what = 6):
+        equal before a context's creation and after its close() = the context destroyed every handle it created."""
+        return int(self.lib.mivi_batch_info(self.h, None, 6))
+
     def exchange_lost(self):
         """True once a launch-free loop's grid-wide exchange was lost on this context: the loops with a per-step exchange are then not taken
         again, their graph-of-launches equivalents run instead (mivi_batch_info what = 3)."""

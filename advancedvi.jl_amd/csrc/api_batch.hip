@@ -132,12 +132,10 @@ mivi_status_t ensure_kids(mivi_ctx *c, int lanes) {
     k->is_child = true;
     const int j = c->n_kids;
     k->status.borrow((char *)c->status.p + sizeof(int) * (j + 1), sizeof(int));   // the child's sticky flags: word j + 1 of the parent's status buffer
-    if ((s = ensure(c, c->kid_out[j], 16 + (size_t)mivi_params_len(c) * c->esize, false))) { (void)mivi_destroy(k); return s; }
-    if (hipEventCreateWithFlags(&c->ev_join[j], hipEventDisableTiming) != hipSuccess ||
-        (!c->ev_fork && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess)) {
-      (void)hipGetLastError();
+    if ((s = ensure(c, c->kid_out[j], 16 + (size_t)mivi_params_len(c) * c->esize, false)) || (s = make_event(c, c->ev_join[j], false)) ||
+        (!c->ev_fork && (s = make_event(c, c->ev_fork, false)))) {
       (void)mivi_destroy(k);   // (not yet registered with the parent: nobody else would)
-      return fail(c, MIVI_ERR_HIP, "interleaved chains: event creation failed");
+      return s;
     }
     c->kids[c->n_kids++] = k;
   }
@@ -159,16 +157,16 @@ mivi_status_t kids_before_capture(mivi_ctx *c, int lanes) {
 // recording closes by advancing the device-side estimate counter by `count`.
 template <class Branch> static mivi_status_t record_branches(mivi_ctx *c, int B, int E, int count, Branch &branch) {
   mivi_status_t s = MIVI_OK;
-  hipError_t he = hipEventRecord(c->ev_fork, c->stream);
+  hipError_t he = hipEventRecord(c->ev_fork.get(), c->stream);
   for (int b = 1; b < B && s == MIVI_OK && he == hipSuccess; ++b) {
     hipStream_t bs = c->kids[b * E - 1]->stream;
-    he = hipStreamWaitEvent(bs, c->ev_fork, 0);   // the branch's stream joins the capture
+    he = hipStreamWaitEvent(bs, c->ev_fork.get(), 0);   // the branch's stream joins the capture
     if (he != hipSuccess) break;
     s = branch(b);
-    if (s == MIVI_OK) he = hipEventRecord(c->ev_join[b * E - 1], bs);
+    if (s == MIVI_OK) he = hipEventRecord(c->ev_join[b * E - 1].get(), bs);
   }
   if (s == MIVI_OK && he == hipSuccess) s = branch(0);
-  for (int b = 1; b < B && s == MIVI_OK && he == hipSuccess; ++b) he = hipStreamWaitEvent(c->stream, c->ev_join[b * E - 1], 0);
+  for (int b = 1; b < B && s == MIVI_OK && he == hipSuccess; ++b) he = hipStreamWaitEvent(c->stream, c->ev_join[b * E - 1].get(), 0);
   if (s == MIVI_OK && he == hipSuccess) hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, (uint64_t)count);
   if (s) return s;
   HIPCHK(c, he);
@@ -210,12 +208,12 @@ static mivi_status_t fb_batch(mivi_ctx *c, const void *params, uint64_t idx0, in
   const int M = c->cfg.n_mc, d = c->cfg.d;
   if ((s = ensure_work(c, M))) return s;
   // sharded batches with a communicator: steps of at most 24 lanes, so that a 100-estimate call is five steps whose all-reduces (on
-  // comm_stream, the partial vectors double-buffered) run UNDER the next steps' kernels -- across ranks the exchange, not the kernels, paces
+  // fb_pipe.stream, the partial vectors double-buffered) run UNDER the next steps' kernels -- across ranks the exchange, not the kernels, paces
   // the batch
   const bool overlap = dist && c->comm != nullptr;
   const int Lmax = (overlap && c->comm_world > 1) ? (fb_lanes_max() < 24 ? fb_lanes_max() : 24) : fb_lanes_max();   // (one rank: nothing to hide, the widest steps)
   const int steps = (count + Lmax - 1) / Lmax, L = (count + steps - 1) / steps, Llast = count - (steps - 1) * L;
-  if (overlap && (s = dist_comm_stream(c))) return s;
+  if (overlap && (s = ensure_pipe(c, c->fb_pipe, false))) return s;
   const size_t plen = (size_t)mivi_params_len(c);
   const int dG = (d + 127) / 128 * 128, MG = (M + 127) / 128 * 128;   // the engine's geometry: whole 128 x 128 tiles (kernels_fullrank_batch.hip fb_pad)
   FbTables &t = c->fb;
@@ -307,28 +305,30 @@ static mivi_status_t fb_batch(mivi_ctx *c, const void *params, uint64_t idx0, in
   // fb_lanes_max() estimates; the host is far ahead of the device.  (Measured and dropped: the batch as ONE hipGraph -- 4.45 against 4.26 us
   // per estimate in 100-estimate batches -- and the draws of step s + 1 on a second graph branch beside the products of step s: the draws
   // are bound by their 3 MB of plane writes per estimate and by the vector ALU, beside them the products ran 25 % longer: 4.58 us.)
-  for (int st = 0; st < steps; ++st) {
+  ExchangePipe &pipe = c->fb_pipe;
+  int handed = 0;   // steps handed over to the pipe's stream so far
+  auto step = [&](int st) -> mivi_status_t {
     const FbStep fs = make_step(st);
-    const int b = st & 1;
-    if (overlap && st >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->fb_ev_comm[b], 0));   // the finalisation of step st - 2 has read this set of partial vectors
+    if (overlap && (s = pipe.reuse(c, c->stream, st))) return s;   // the finalisation of step st - 2 has read this set of partial vectors
     fb_launch_eps(c, fs, st == 0, c->stream);
     fb_launch_compute(c, fs, c->stream);
-    if (dist) {
-      hipStream_t xs = c->stream;
-      if (overlap) {
-        HIPCHK(c, hipEventRecord(c->fb_ev_part[b], c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->fb_comm_stream, c->fb_ev_part[b], 0));
-        xs = c->fb_comm_stream;
-      }
-      if ((s = dist_allreduce_f32(c, fs.parts, (size_t)fs.L * part_len, xs))) return s;
-      fb_launch_finalize_parts(c, fs, xs);
-      if (overlap) HIPCHK(c, hipEventRecord(c->fb_ev_comm[b], c->fb_comm_stream));
+    if (!dist) return MIVI_OK;
+    hipStream_t xs = c->stream;
+    if (overlap) {
+      if ((s = pipe.hand_over(c, c->stream, st, &xs))) return s;
+      handed = st + 1;
     }
+    if ((s = dist_allreduce_f32(c, fs.parts, (size_t)fs.L * part_len, xs))) return s;
+    fb_launch_finalize_parts(c, fs, xs);
+    return overlap ? pipe.finish(c, st) : MIVI_OK;
+  };
+  s = MIVI_OK;
+  for (int st = 0; st < steps && s == MIVI_OK; ++st) s = step(st);
+  if (s) {
+    pipe.join_after_error(c->stream, handed);
+    return s;
   }
-  if (overlap) {   // join: the batch is complete when its last two exchanges + finalisations are
-    if (steps >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->fb_ev_comm[(steps - 2) & 1], 0));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->fb_ev_comm[(steps - 1) & 1], 0));
-  }
+  if (overlap && (s = pipe.join(c, c->stream, steps))) return s;   // the batch is complete when its last two exchanges + finalisations are
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
 }
@@ -352,6 +352,7 @@ int32_t mivi_batch_info(const mivi_ctx_t *c, const void *params, int32_t what) {
   if (what == 3) return c->exchange_lost ? 1 : 0;
   if (what == 4) return c->graph_records;
   if (what == 5) return live_allocations();
+  if (what == 6) return live_handles();
   return (what == 0 && params && fb_route(c, params, nullptr, nullptr)) ? 1 : 0;
 }
 
@@ -376,24 +377,18 @@ mivi_status_t mivi_profile_batch(mivi_ctx_t *c, const void *params, int32_t lane
   fs.dense = c->target == TGT_DENSE_GAUSS ? 1 : 0;
   fs.stl = stl_entropy(c) ? 1 : 0;
   us_out[3] = us_out[4] = 0.0;
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0));
-  HIPCHK(c, hipEventCreate(&e1));
+  EventTimer timer;
   for (int which = 0; which < 5; ++which) {
     if ((which == 3 && !fs.dense) || (which == 4 && !fs.stl)) continue;
     for (int r = -2; r < reps; ++r) {
-      if (r == 0) HIPCHK(c, hipEventRecord(e0, c->stream));
+      if (r == 0 && (s = timer.start(c, c->stream))) return s;
       if (which == 0) fb_launch_eps(c, fs, true, c->stream);
       else fb_launch_compute(c, fs, c->stream, which == 1 ? 1 : (which == 2 ? 2 : (which == 3 ? 4 : 8)));
     }
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-    us_out[which] = (double)ms * 1e3 / reps;
+    double us = 0.0;
+    if ((s = timer.stop_us(c, c->stream, &us))) return s;
+    us_out[which] = us / reps;
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
 }

@@ -84,6 +84,43 @@ mivi_status_t upload(mivi_ctx *c, DevBuf &b, const void *src, size_t bytes) {
   return MIVI_OK;
 }
 
+// ---- the library's streams and events: make_stream / make_event create, handle_destroy destroys, and nothing else in libmivi does either ----
+static std::atomic<int32_t> g_live_handles{0};   // streams, events and graph execs held in this process (mivi_batch_info what = 6)
+int32_t live_handles() { return g_live_handles.load(); }
+void mivi::count_handles(int delta) { g_live_handles += delta; }
+void mivi::handle_destroy(hipStream_t h) { (void)hipStreamDestroy(h); }
+void mivi::handle_destroy(hipEvent_t h) { (void)hipEventDestroy(h); }
+
+mivi_status_t make_stream(mivi_ctx *c, Stream &s, bool own_queue) {
+  hipStream_t h = nullptr;
+  uint32_t mask[16];   // all CUs enabled = no restriction: the mask is there for the queue it brings
+  for (int k = 0; k < 16; ++k) mask[k] = 0xFFFFFFFFu;
+  if (own_queue && c->stream != nullptr && hipExtStreamCreateWithCUMask(&h, 16, mask) != hipSuccess) {
+    (void)hipGetLastError();
+    h = nullptr;
+  }
+  if (!h) HIPCHK(c, hipStreamCreateWithFlags(&h, hipStreamNonBlocking));
+  s.adopt(h);
+  return MIVI_OK;
+}
+
+mivi_status_t make_event(mivi_ctx *c, Event &e, bool timing) {
+  hipEvent_t h = nullptr;
+  HIPCHK(c, timing ? hipEventCreate(&h) : hipEventCreateWithFlags(&h, hipEventDisableTiming));
+  e.adopt(h);
+  return MIVI_OK;
+}
+
+mivi_status_t ensure_pipe(mivi_ctx *c, ExchangePipe &p, bool own_queue) {
+  if (p) return MIVI_OK;
+  ExchangePipe made;   // (a failed attempt destroys what it made and leaves p empty: the next call tries again)
+  mivi_status_t s = make_stream(c, made.stream, own_queue);
+  for (int k = 0; k < 2 && s == MIVI_OK; ++k)
+    if (!(s = make_event(c, made.part[k], false))) s = make_event(c, made.done[k], false);
+  if (s == MIVI_OK) p = std::move(made);
+  return s;
+}
+
 // A captured graph bakes buffer pointers, leading dimensions and work-list contents; the eps speculation remembers a buffer
 // parity.  Anything that reallocates or rewrites those calls this.
 namespace mivi {
@@ -187,13 +224,13 @@ mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out) {
   }
   c->M_total = cfg->m_total > 0 ? cfg->m_total : cfg->n_mc;
   if (hipSetDevice(cfg->device) != hipSuccess) { delete c; return MIVI_ERR_HIP; }
+  mivi_status_t s;
   if (!cfg->own_stream) {
     c->stream = (hipStream_t)cfg->stream;   // NULL = the null stream
   } else {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return MIVI_ERR_HIP; }
-    c->own_stream = true;
+    if ((s = make_stream(c, c->own, false))) { delete c; return s; }
+    c->stream = c->own.get();
   }
-  mivi_status_t s;
   if ((s = ensure(c, c->status, 64, true)) ||
       (s = ensure(c, c->d_idx, 64, true)) || (s = ensure(c, c->acc, 64, true)) ||
       (s = ensure(c, c->dog_part, (2 * 512 + 8) * sizeof(double), true)) ||
@@ -204,19 +241,6 @@ mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out) {
   }
   *out = c;
   return MIVI_OK;
-}
-
-mivi_ctx_streams::~mivi_ctx_streams() {
-  if (own_stream) (void)hipStreamDestroy(stream);
-  if (cap_stream) (void)hipStreamDestroy(cap_stream);
-  for (hipStream_t s : {comm_stream, comm_stream2, fb_comm_stream})
-    if (s) (void)hipStreamDestroy(s);
-  for (hipEvent_t e : ev_join)
-    if (e) (void)hipEventDestroy(e);
-  if (ev_fork) (void)hipEventDestroy(ev_fork);
-  for (hipEvent_t *pair : {fb_ev_part, fb_ev_comm, ev_part, ev_comm})
-    for (int k = 0; k < 2; ++k)
-      if (pair[k]) (void)hipEventDestroy(pair[k]);
 }
 
 mivi_status_t mivi_destroy(mivi_ctx_t *c) {
@@ -230,7 +254,7 @@ mivi_status_t mivi_destroy(mivi_ctx_t *c) {
 
 mivi_status_t mivi_set_stream(mivi_ctx_t *c, void *s) {
   if (!c) return MIVI_ERR_BAD_ARG;
-  if (c->own_stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); c->own_stream = false; }
+  if (c->own) { (void)hipStreamSynchronize(c->own.get()); c->own.reset(); }
   c->stream = (hipStream_t)s;   // NULL = the null stream
   c->pre.clear();
   c->graph.drop();   // (not invalidate_graph: the children's generation stays)

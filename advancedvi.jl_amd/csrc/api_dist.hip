@@ -124,8 +124,7 @@ mivi_status_t mivi_p2p_detach(mivi_ctx_t *c) {
   if (!c) return MIVI_ERR_BAD_ARG;
   (void)hipSetDevice(c->cfg.device);
   (void)hipStreamSynchronize(c->stream);
-  if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
-  if (c->comm_stream2) (void)hipStreamSynchronize(c->comm_stream2);
+  if (c->pipe) (void)hipStreamSynchronize(c->pipe.stream.get());
   invalidate_graph(c);
   for (int r = 0; r < 8; ++r) {
     if (c->p2p_opened[r] && c->p2p_peer[r]) (void)hipIpcCloseMemHandle(c->p2p_peer[r]);
@@ -577,7 +576,7 @@ mivi_status_t mivi_estimate_gradient_dist(mivi_ctx_t *c, const void *params, uin
 // Sharded estimates in batches: the exchange of estimate t overlapped with the kernels of estimate t + 1
 // ---------------------------------------------------------------------------------------------
 // Estimates at fixed parameters are independent (what mivi_estimate_gradient_n serves on one GPU), so the exchange + finalisation of
-// estimate t (comm_stream) runs UNDER the partial kernels of estimate t + 1 (the context's stream): partial vectors are double
+// estimate t (c->pipe's stream) runs UNDER the partial kernels of estimate t + 1 (the context's stream): partial vectors are double
 // buffered, estimate t + 2 waits for the exchange of t to release its buffer.  One hipGraph with two branches per estimate; if the
 // capture is refused (a collective that cannot be captured) the same sequence is issued eagerly with events.
 //   mode 0 pipelined | 1 serial {partials -> exchange} on one stream | 2 partials only | 3 exchange only (on the last partial vector)
@@ -623,22 +622,23 @@ static mivi_status_t dist_sequence_lanes(mivi_ctx *c, const void *params, bool c
 static mivi_status_t dist_sequence(mivi_ctx *c, const void *params, bool counter_idx, uint64_t idx0, int count, void *value, void *grad, int mode) {
   if (mode == 4 && c->dist_lane4) return dist_sequence_lanes(c, params, counter_idx, idx0, count);
   mivi_status_t s = MIVI_OK;
-  hipStream_t main = c->stream;
+  const hipStream_t main = c->stream;
+  ExchangePipe &pipe = c->pipe;
+  int handed = 0;   // mode 0: estimates handed over to the pipe's stream so far
   if (mode == 3 && c->dist_direct) {   // exchange-only (a measurement leg): both parities of the staging areas hold a complete partial vector
     for (int g2 = 0; g2 < 2 && s == MIVI_OK; ++g2) s = run_estimate(c, params, rng_of(c, idx0), c->cfg.n_mc, 1, partials_out(c, c->dist_P.p, g2, 0));
   }
-  for (int i = 0; i < count && s == MIVI_OK; ++i) {
-    const int par = i & 1;
-    void *P = mode == 4 ? ring_slot(c, i % kRing) : (par ? c->dist_P2.p : c->dist_P.p);
-    if (mode == 0 && i >= 2) HIPCHK(c, hipStreamWaitEvent(main, c->ev_comm[par], 0));   // the exchange of i - 2 has released this partial buffer
+  auto step = [&](int i) -> mivi_status_t {
+    void *P = mode == 4 ? ring_slot(c, i % kRing) : ((i & 1) ? c->dist_P2.p : c->dist_P.p);
+    if (mode == 0 && (s = pipe.reuse(c, main, i))) return s;   // the exchange of i - 2 has released this partial buffer
     if (mode != 3) {
       RngArgs r = rng_of(c, counter_idx ? (uint64_t)i : idx0 + (uint64_t)i);
       if (counter_idx) r.idx_ptr = (const uint64_t *)c->d_idx.p;
       // direct staging, mode 4: the persistent exchange serves groups of kGroup estimates; modes 1 / 2: one exchange launch per estimate
       const OutArgs o = !c->dist_direct ? partials_out(c, P) : (mode == 4 ? partials_out(c, P, i / kGroup, i % kGroup) : partials_out(c, P, 0, 0));
-      if ((s = run_estimate(c, params, r, c->cfg.n_mc, 1, o))) break;
+      if ((s = run_estimate(c, params, r, c->cfg.n_mc, 1, o))) return s;
     }
-    if (mode == 2) continue;
+    if (mode == 2) return MIVI_OK;
     if (mode == 4) {   // peer-to-peer pipeline, compute chain: announce partial vector i, then wait until the exchange has read the ring slot estimate i + 1 overwrites
       unsigned *w = (unsigned *)c->p2p_ctr.p;
       const int slot = (i + 1) % kRing, prev_users = (i + 1) / kRing;
@@ -646,25 +646,24 @@ static mivi_status_t dist_sequence(mivi_ctx *c, const void *params, bool counter
       //  dispatch to completion beside the persistent exchange kernels moved into that kernel -- 9 + 8 -> 21.5 us --, the step stayed at 31 us)
       launch_p2p_handover(c, w + 64, (unsigned)i + 1u, prev_users >= 1 ? w + 80 + slot : nullptr,
                           (unsigned)prev_users * (unsigned)(c->p2p_G + (c->dist_direct ? 1 : 0)));
-      continue;
+      return MIVI_OK;
     }
-    if (mode == 0) {
-      HIPCHK(c, hipEventRecord(c->ev_part[par], main));
-      HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_part[par], 0));
-      c->stream = c->comm_stream;
-      s = dist_collective(c, params, P, value, grad);
-      c->stream = main;
-      if (s) break;
-      HIPCHK(c, hipEventRecord(c->ev_comm[par], c->comm_stream));
-    } else {
-      s = dist_collective(c, params, mode == 3 ? c->dist_P.p : P, value, grad);
+    if (mode != 0) return dist_collective(c, params, mode == 3 ? c->dist_P.p : P, value, grad);
+    hipStream_t xs;
+    if ((s = pipe.hand_over(c, main, i, &xs))) return s;
+    handed = i + 1;
+    {
+      StreamScope on_pipe(c, xs);
+      if ((s = dist_collective(c, params, P, value, grad))) return s;
     }
+    return pipe.finish(c, i);
+  };
+  for (int i = 0; i < count && s == MIVI_OK; ++i) s = step(i);
+  if (s) {
+    pipe.join_after_error(main, handed);
+    return s;
   }
-  if (s == MIVI_OK && mode == 0) {   // join: the batch is complete when its last two exchanges are
-    if (count >= 2) HIPCHK(c, hipStreamWaitEvent(main, c->ev_comm[(count - 2) & 1], 0));
-    HIPCHK(c, hipStreamWaitEvent(main, c->ev_comm[(count - 1) & 1], 0));
-  }
-  return s;
+  return mode == 0 ? pipe.join(c, main, count) : MIVI_OK;   // the batch is complete when its last two exchanges are
 }
 
 // the one collective of the engine's sharded batches: the lanes' partial vectors summed over the ranks, in place, on the context's stream
@@ -673,15 +672,6 @@ mivi_status_t dist_allreduce_f32(mivi_ctx *c, void *buf, size_t count, hipStream
   RcclApi *r = rccl();
   if (!r || !r->AllReduce) return fail(c, MIVI_ERR_UNSUPPORTED, "this librccl exports no ncclAllReduce");
   if (r->AllReduce(buf, buf, count, ncclFloat, ncclSum, (ncclComm_t)c->comm, stream) != ncclSuccess) return fail(c, MIVI_ERR_HIP, "ncclAllReduce failed");
-  return MIVI_OK;
-}
-mivi_status_t dist_comm_stream(mivi_ctx *c) {
-  if (c->fb_comm_stream) return MIVI_OK;
-  HIPCHK(c, hipStreamCreateWithFlags(&c->fb_comm_stream, hipStreamNonBlocking));
-  for (int k = 0; k < 2; ++k) {
-    HIPCHK(c, hipEventCreateWithFlags(&c->fb_ev_part[k], hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->fb_ev_comm[k], hipEventDisableTiming));
-  }
   return MIVI_OK;
 }
 
@@ -702,31 +692,17 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
   if (!prepare_tables(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
   if ((s = reserve_target(c, c->cfg.n_mc)) || (s = ensure_dist(c))) return s;
   if (c->cfg.family == MIVI_FULLRANK && lds_path_shape_ok(c, c->cfg.n_mc) && !lds_prepare(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work lists: allocation failed");
-  if (!c->comm_stream) {
-    // (plain non-blocking streams: a HIGH-priority stream starved the compute chain it was supposed to run beside -- its spinning
-    //  kernel was scheduled first and the normal-priority graph never progressed; found on the GPU)
-    // The persistent exchange kernels run BESIDE the compute chain on these streams.  Non-blocking: a blocking stream (what
-    // hipExtStreamCreateWithCUMask creates) synchronises with the null stream, so a context living on the null stream deadlocked
-    // against its own exchange kernel; a HIGH-priority stream starved the compute chain (both found on the GPU).
-    // They need hardware queues of their own (HIP maps streams onto a small pool, GPU_MAX_HW_QUEUES, and two streams on one queue
-    // serialise: the bounded hand-over waits then expire): a stream created with a CU mask carries the mask in its queue and gets one
-    // -- all CUs enabled = no restriction.  Only for contexts on a real stream (see above).
-    uint32_t mask[16];
-    for (int k = 0; k < 16; ++k) mask[k] = 0xFFFFFFFFu;
-    hipStream_t *cs[2] = {&c->comm_stream, &c->comm_stream2};
-    for (int k = 0; k < 2; ++k) {
-      if (c->stream == nullptr || hipExtStreamCreateWithCUMask(cs[k], 16, mask) != hipSuccess) {
-        (void)hipGetLastError();
-        HIPCHK(c, hipStreamCreateWithFlags(cs[k], hipStreamNonBlocking));
-      }
-    }
-    for (int k = 0; k < 2; ++k) {
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_part[k], hipEventDisableTiming));
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_comm[k], hipEventDisableTiming));
-    }
-  }
+  // (a plain non-blocking stream: a HIGH-priority stream starved the compute chain it was supposed to run beside -- its spinning
+  //  kernel was scheduled first and the normal-priority graph never progressed; found on the GPU)
+  // The persistent exchange kernel runs BESIDE the compute chain on the pipe's stream.  Non-blocking: a blocking stream (what the
+  // creation call that takes a CU mask gives) synchronises with the null stream, so a context living on the null stream deadlocked
+  // against its own exchange kernel; a HIGH-priority stream starved the compute chain (both found on the GPU).
+  // It needs a hardware queue of its own (HIP maps streams onto a small pool, GPU_MAX_HW_QUEUES, and two streams on one queue
+  // serialise: the bounded hand-over waits then expire): a stream created with a CU mask carries the mask in its queue and gets one
+  // -- all CUs enabled = no restriction.  Only for contexts on a real stream (see above).  That is make_stream's own_queue.
+  if ((s = ensure_pipe(c, c->pipe, true))) return s;
   const int route = mivi_comm_route(c);
-  // Peer-to-peer route, pipelined: the exchange is ONE persistent kernel on comm_stream for the whole batch (kernels_p2p.hip), the compute
+  // Peer-to-peer route, pipelined: the exchange is ONE persistent kernel on the pipe's stream for the whole batch (kernels_p2p.hip), the compute
   // chain is a single-stream graph of {partial kernels, hand-over} per estimate; the two talk through two device words.
   {
     const bool direct = route == 3 && p2p_direct_ok(c, params);
@@ -772,33 +748,25 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
     if (s) {   // refused (or the sequence failed): the same sequence is issued eagerly below, from now on
       (void)hipGetLastError();
       capture_refused = true;
-      (void)hipStreamSynchronize(c->comm_stream);
+      (void)hipStreamSynchronize(c->pipe.stream.get());
     }
   }
-  auto p2p_front = [&]() -> mivi_status_t {   // hand-over words reset, then the persistent exchange kernels (one per lane) on their own streams
+  auto p2p_front = [&]() -> mivi_status_t {   // hand-over words reset, then the persistent exchange kernel on the pipe's stream (between part[0] and done[0])
     unsigned *w = (unsigned *)c->p2p_ctr.p;
     HIPCHK(c, hipMemsetAsync(w + 64, 0, 128, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_part[0], c->stream));
-    hipStream_t main = c->stream;
     const void *ringP[kRing];
     for (int k = 0; k < kRing; ++k) ringP[k] = ring_slot(c, k);
     // ONE persistent exchange kernel (measured on one GPU: 21 us per estimate against 31 with two of them serving alternate estimates -- a
     // second resident kernel costs the compute chain more than its overlap wins)
-    const int lanes = 1;
-    for (int ln = 0; ln < lanes; ++ln) {
-      hipStream_t cs = ln ? c->comm_stream2 : c->comm_stream;
-      HIPCHK(c, hipStreamWaitEvent(cs, c->ev_part[0], 0));
-      c->stream = cs;
-      launch_p2p_exchange(c, params, ringP, kRing, value, grad, 7, ln, lanes, count, w + 64, w + 80, c->dist_direct);
-      c->stream = main;
-      HIPCHK(c, hipEventRecord(c->ev_comm[ln], cs));
+    hipStream_t xs;
+    if (mivi_status_t hs = c->pipe.hand_over(c, c->stream, 0, &xs)) return hs;
+    {
+      StreamScope on_pipe(c, xs);
+      launch_p2p_exchange(c, params, ringP, kRing, value, grad, 7, 0, 1, count, w + 64, w + 80, c->dist_direct);
     }
-    return MIVI_OK;
+    return c->pipe.finish(c, 0);
   };
-  auto p2p_back = [&]() -> mivi_status_t {
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_comm[0], 0));
-    return MIVI_OK;
-  };
+  auto p2p_back = [&]() -> mivi_status_t { return c->pipe.join(c, c->stream, 1); };
   if (c->graph.matches(key)) {
     graph_seek(c, idx0);
     if (p2p_pipe && (s = p2p_front())) return s;
@@ -864,24 +832,16 @@ mivi_status_t mivi_profile_dist(mivi_ctx_t *c, const void *params, int32_t reps,
   if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_profile_dist")) return rs;
   (void)hipSetDevice(c->cfg.device);
   char *o = (char *)c->tmp_out.p;
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0));
-  HIPCHK(c, hipEventCreate(&e1));
+  EventTimer timer;
   mivi_status_t s = MIVI_OK;
   const int order[4] = {2, 3, 1, 0};   // partials first: the exchange-only leg works on the partial vector they leave
   for (int k = 0; k < 4 && s == MIVI_OK; ++k) {
     const int mode = order[k];
     if ((s = dist_batch(c, params, 1000, reps, o, o + 16, mode))) break;   // warm (captures)
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-    if ((s = dist_batch(c, params, 1000 + reps, reps, o, o + 16, mode))) break;
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-    us_out[mode == 2 ? 0 : (mode == 3 ? 1 : (mode == 1 ? 2 : 3))] = (double)ms * 1e3 / reps;
+    double us = 0.0;
+    if ((s = timer.start(c, c->stream)) || (s = dist_batch(c, params, 1000 + reps, reps, o, o + 16, mode)) || (s = timer.stop_us(c, c->stream, &us))) break;
+    us_out[mode == 2 ? 0 : (mode == 3 ? 1 : (mode == 1 ? 2 : 3))] = us / reps;
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   invalidate_graph(c);
   return s;
 }

@@ -7,23 +7,26 @@
 // The null stream cannot be captured: record on an internal stream, replay on the context's stream.
 // Whatever `body` and HIP return: on exit c->stream is the caller's stream, no capture is open on the internal stream and the intermediate
 // hipGraph_t is destroyed.  Failures in the order the routes always reported them: the body's status, the end of the capture, the
-// instantiation; *exec stays null on all of them.
-mivi_status_t capture_graph_fn(mivi_ctx *c, hipGraphExec_t *exec, mivi_status_t (*body)(void *), void *arg) {
-  *exec = nullptr;
-  if (!c->cap_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
+// instantiation; the owner *exec stays empty on all of them.  The instantiated graph goes into it here (GraphExec, mivi_internal.h), and
+// handle_destroy below is where the library destroys one.
+mivi_status_t capture_graph_fn(mivi_ctx *c, GraphExec *exec, mivi_status_t (*body)(void *), void *arg) {
+  exec->reset();
+  mivi_status_t s;
+  if (!c->cap_stream && (s = make_stream(c, c->cap_stream, false))) return s;
   HIPCHK(c, hipStreamSynchronize(c->stream));   // pending memsets / uploads on the launch stream
-  HIPCHK(c, hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-  hipStream_t saved = c->stream;
-  c->stream = c->cap_stream;
-  const mivi_status_t s = body(arg);
-  c->stream = saved;
+  HIPCHK(c, hipStreamBeginCapture(c->cap_stream.get(), hipStreamCaptureModeThreadLocal));
+  {
+    StreamScope on_capture(c, c->cap_stream.get());
+    s = body(arg);
+  }
   hipGraph_t graph = nullptr;
-  hipError_t e = hipStreamEndCapture(c->cap_stream, &graph);
+  hipError_t e = hipStreamEndCapture(c->cap_stream.get(), &graph);
   const char *what = "hipStreamEndCapture";
   if (s == MIVI_OK && e == hipSuccess) {
-    e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+    hipGraphExec_t made = nullptr;
+    e = hipGraphInstantiate(&made, graph, nullptr, nullptr, 0);
     what = "hipGraphInstantiate";
-    if (e != hipSuccess) *exec = nullptr;
+    if (e == hipSuccess) exec->adopt(made);
   }
   if (graph) (void)hipGraphDestroy(graph);
   if (s) return s;
@@ -48,9 +51,10 @@ bool GraphCache::matches(const GraphKey &k) const {
          (k.kind != GRAPH_LOOP || same_loop(key.loop, k.loop));
 }
 void GraphCache::drop() {
-  if (exec) (void)hipGraphExecDestroy(exec);
-  *this = GraphCache{};
+  exec.reset();
+  key = GraphKey{};
 }
+void handle_destroy(hipGraphExec_t h) { (void)hipGraphExecDestroy(h); }
 }  // namespace mivi
 
 mivi_status_t graph_record_fn(mivi_ctx *c, const GraphKey &key, mivi_status_t (*body)(void *), void *arg) {
@@ -71,7 +75,7 @@ void graph_seek(mivi_ctx *c, uint64_t idx0) {
     hipLaunchKernelGGL(k_set_u64x2, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, idx0, 0ull, 1);
 }
 mivi_status_t graph_launch(mivi_ctx *c, uint64_t idx0, uint64_t advance, bool advances) {
-  HIPCHK(c, hipGraphLaunch(c->graph.exec, c->stream));
+  HIPCHK(c, hipGraphLaunch(c->graph.exec.get(), c->stream));
   c->d_idx_valid = advances;
   c->d_idx_expect = idx0 + advance;
   return MIVI_OK;

@@ -268,7 +268,7 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   c->d_idx_valid = false;
   hipLaunchKernelGGL(k_set_u64x2, dim3(1), dim3(1), 0, c->stream, (uint64_t *)c->d_idx.p, l.estimate_idx0, (uint64_t)l.t0, 2);
   HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));   // a stale flag of earlier estimates (this context's word or a child context's: read_status folds them all in) is not this run's
-  HIPCHK(c, hipGraphLaunch(c->graph.exec, c->stream));
+  HIPCHK(c, hipGraphLaunch(c->graph.exec.get(), c->stream));
   if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
   return read_status(c);
 }

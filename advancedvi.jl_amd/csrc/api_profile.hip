@@ -115,39 +115,30 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
     }
     return st;
   };
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0));
-  HIPCHK(c, hipEventCreate(&e1));
-  float ms = 0.f;
+  EventTimer timer;   // (the timer and the temporary graph are locals: every return below takes them along)
+  GraphExec exec;
+  double us = 0.0;
   const bool graphed = which != 0 && which != 5 && !c->dbg;
   if (graphed) {
     invalidate_graph(c);
-    hipGraphExec_t exec = nullptr;
     s = capture_graph(c, &exec, [&]() -> mivi_status_t {
       mivi_status_t rs = MIVI_OK;
       for (int r = 0; r < reps && rs == MIVI_OK; ++r) rs = one(r);
       return rs;
     });
     if (s) return s;
-    HIPCHK(c, hipGraphLaunch(exec, c->stream));   // warm replay
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-    HIPCHK(c, hipGraphLaunch(exec, c->stream));
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(e1));
-    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-    (void)hipGraphExecDestroy(exec);
+    HIPCHK(c, hipGraphLaunch(exec.get(), c->stream));   // warm replay
+    if ((s = timer.start(c, c->stream))) return s;
+    HIPCHK(c, hipGraphLaunch(exec.get(), c->stream));
+    if ((s = timer.stop_us(c, c->stream, &us))) return s;
   } else {
-    HIPCHK(c, hipEventRecord(e0, c->stream));
+    if ((s = timer.start(c, c->stream))) return s;
     for (int r = 0; r < reps && s == MIVI_OK; ++r) s = one(r);
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(e1));
-    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
+    if (mivi_status_t ts = timer.stop_us(c, c->stream, &us)) return ts;
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   if (which != 0) c->pre.clear();
   if (s) return s;
-  *ms_out = (double)ms / reps;
+  *ms_out = us * 1e-3 / reps;
   return MIVI_OK;
 }
 

@@ -246,6 +246,54 @@ struct __attribute__((visibility("hidden"))) DevBuf {
   void release();                                                       // frees what it owns, forgets what it borrowed: the buffer is empty
 };
 
+// The HIP handles of the library have owners of the same kind.  A Stream, an Event or a GraphExec holds ONE handle the library created and
+// destroys it when it is reset or destroyed; move-only.  They are filled by make_stream / make_event (api_core.hip) and capture_graph
+// (api_graph.hip) and by nothing else: those three, and handle_destroy below them, are the only places that name HIP's create / destroy
+// calls.  A stream the CALLER owns (mivi_config_t.stream, mivi_set_stream) is never put into one.  None of them may have static storage
+// duration: its destructor would run after the HIP runtime is gone (the note at MIVI_FB_DBG, kernels_fullrank_batch.hip).
+#pragma GCC visibility push(hidden)
+void handle_destroy(hipStream_t h);       // api_core.hip
+void handle_destroy(hipEvent_t h);        // api_core.hip
+void handle_destroy(hipGraphExec_t h);    // api_graph.hip
+void count_handles(int delta);            // api_core.hip: the handles held in this process (mivi_batch_info what = 6)
+#pragma GCC visibility pop
+template <class H>
+struct __attribute__((visibility("hidden"))) Handle {
+  Handle() = default;
+  Handle(const Handle &) = delete;
+  Handle &operator=(const Handle &) = delete;
+  Handle(Handle &&o) noexcept { std::swap(h, o.h); }
+  Handle &operator=(Handle &&o) noexcept { std::swap(h, o.h); return *this; }   // (o takes what this held, and destroys it)
+  ~Handle() { reset(); }
+  H get() const { return h; }
+  explicit operator bool() const { return h != nullptr; }
+  void reset() { if (h) { handle_destroy(h); count_handles(-1); } h = nullptr; }
+  void adopt(H created) { reset(); h = created; if (h) count_handles(1); }       // the three makers' only
+ private:
+  H h = nullptr;
+};
+using Stream = Handle<hipStream_t>;
+using Event = Handle<hipEvent_t>;
+using GraphExec = Handle<hipGraphExec_t>;
+
+// The double-buffered two-stream exchange of the sharded batches: the exchange + finalisation of step i run on `stream` under the main
+// stream's kernels of step i + 1, the buffers they read in two sets (i & 1).  ensure_pipe (api_core.hip) fills all five handles or none.
+// Per step:  reuse (the exchange of step i - 2 has released this set) -> the main stream's kernels -> hand_over (part[i & 1] recorded on
+// main, the pipe's stream waits for it and is what *xs names afterwards) -> the exchange on *xs -> finish (done[i & 1] recorded there);
+// after the last step join: main waits for the done of the last min(n, 2) steps.  join_after_error is for a loop that leaves with an error
+// after `n` hand-overs: it closes step n - 1 where the pipe's stream stands and joins the same way, unchecked -- the first error is the one
+// reported, and no work that reads the caller's buffers stays queued on a stream the caller's does not wait for.  (api_common.h)
+struct __attribute__((visibility("hidden"))) ExchangePipe {
+  Stream stream;
+  Event part[2], done[2];
+  explicit operator bool() const { return (bool)stream; }
+  mivi_status_t reuse(mivi_ctx *c, hipStream_t main, int i);
+  mivi_status_t hand_over(mivi_ctx *c, hipStream_t main, int i, hipStream_t *xs);
+  mivi_status_t finish(mivi_ctx *c, int i);
+  mivi_status_t join(mivi_ctx *c, hipStream_t main, int n);
+  void join_after_error(hipStream_t main, int n);
+};
+
 // third-generation batch engine (kernels_fullrank_batch.hip): work tables per lane count, per-lane work buffers (base + lane * stride)
 struct __attribute__((visibility("hidden"))) FbTab {
   DevBuf prod, vjp, prod2, prod3;         // work tables: the draw's product, the VJP, the dense target's product, the sticking-the-landing product
@@ -300,7 +348,7 @@ struct GraphKey {
   mivi_loop_t loop{};              // GRAPH_LOOP: the configuration the captured loop was built for
 };
 struct GraphCache {
-  hipGraphExec_t exec = nullptr;
+  GraphExec exec;
   GraphKey key;
   bool matches(const GraphKey &k) const;
   void drop();   // destroys the cached hipGraphExec, if any, and empties the slot
@@ -351,25 +399,23 @@ struct LaneRecorder {
 
 }  // namespace mivi
 
-// The streams and events a context created.  A base of mivi_ctx, so that they are destroyed AFTER the context's buffers are freed (members
-// go before bases): no buffer outlives the stream its last launch ran on.
+// The streams and events a context created, every one in its owner.  A base of mivi_ctx, so that they are destroyed AFTER the context's
+// buffers are freed (members go before bases): no buffer outlives the stream its last launch ran on.
 struct mivi_ctx_streams {
   static constexpr int kMaxKids = 15;   // up to sixteen contexts (eight are used); at most FOUR graph branches (a forked graph with five branches crashed inside hipGraphLaunch,
                                        // hip::Graph::UpdateStreams, after a re-capture on ROCm 7.0's runtime; four is also the number of hardware queues)
-  hipStream_t stream = nullptr;
-  hipStream_t cap_stream = nullptr;   // internal stream used only for graph capture
-  bool own_stream = false;
-  // Pipelined exchange (mivi_estimate_gradient_dist_n): the collective of estimate t runs on comm_stream under the kernels of t + 1;
-  // partial vectors double-buffered (dist_P, dist_P2), event pairs per parity
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t ev_part[2] = {nullptr, nullptr}, ev_comm[2] = {nullptr, nullptr};
-  hipStream_t comm_stream2 = nullptr;
-  // the batch engine's sharded batches (api_batch.hip fb_batch, dist): the all-reduce + finalisation of step s on fb_comm_stream under the
-  // kernels of step s + 1 (streams of their own: comm_stream carries the CU mask the peer-to-peer pipeline needs)
-  hipStream_t fb_comm_stream = nullptr;
-  hipEvent_t fb_ev_part[2] = {nullptr, nullptr}, fb_ev_comm[2] = {nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_join[kMaxKids] = {};   // interleaved chains: the fork of a recording's branches, the join of child j's
-  __attribute__((visibility("hidden"))) ~mivi_ctx_streams();   // api_core.hip
+  hipStream_t stream = nullptr;   // what the context launches on: the CALLER's stream (or the null stream), or a view of `own`
+  mivi::Stream own;               // mivi_config_t.own_stream: the non-blocking stream the context created for itself
+  mivi::Stream cap_stream;        // internal stream used only for graph capture (api_graph.hip)
+  // Pipelined exchange (mivi_estimate_gradient_dist_n, api_dist.hip): the collective of estimate t runs on pipe.stream under the kernels of
+  // t + 1, the partial vectors double-buffered (dist_P, dist_P2).  The peer-to-peer pipeline runs its persistent exchange kernel there
+  // between part[0] and done[0], which is why the stream has a hardware queue of its own (dist_batch).
+  mivi::ExchangePipe pipe;
+  // the batch engine's sharded batches (api_batch.hip fb_batch, dist): the all-reduce + finalisation of step s on fb_pipe.stream under the
+  // kernels of step s + 1 (a plain non-blocking stream of its own: pipe.stream carries the CU mask the peer-to-peer pipeline needs)
+  mivi::ExchangePipe fb_pipe;
+  mivi::Event ev_fork, ev_join[kMaxKids];   // interleaved chains: the fork of a recording's branches, the join of child j's
+  __attribute__((visibility("hidden"))) ~mivi_ctx_streams() = default;   // (the owners' work; said only to keep it out of the exported symbols)
 };
 
 // Every device buffer below is a member and nothing else: ensure() fills it where it is needed, the context's destruction returns it.
@@ -525,6 +571,13 @@ mivi_status_t ensure(mivi_ctx *c, mivi::DevBuf &b, size_t bytes, bool zero, bool
 mivi_status_t ensure_zeroed(mivi_ctx *c, mivi::DevBuf &b, size_t bytes);         // ensure, and the first `bytes` bytes are zero (a memset on c->stream) whether the buffer was kept or not
 mivi_status_t upload(mivi_ctx *c, mivi::DevBuf &b, const void *src, size_t bytes);   // ensure, then a synchronous copy of `bytes` host bytes into it
 int32_t live_allocations();   // what this process holds of them right now, over all contexts (mivi_batch_info what = 5)
+// api_core.hip: the library's streams and events.  Each leaves its owner filled, or reports through c->err and leaves it as it was.
+// own_queue: a stream with a hardware queue of its own (dist_batch says who needs one and why); a plain non-blocking stream otherwise, and
+// whenever the context lives on the null stream or the runtime refuses.  timing = false: hipEventDisableTiming.
+mivi_status_t make_stream(mivi_ctx *c, mivi::Stream &s, bool own_queue);
+mivi_status_t make_event(mivi_ctx *c, mivi::Event &e, bool timing);
+mivi_status_t ensure_pipe(mivi_ctx *c, mivi::ExchangePipe &p, bool own_queue);   // nothing to do on a filled pipe; all five handles or none
+int32_t live_handles();       // streams, events and graph execs the library holds right now in this process (mivi_batch_info what = 6)
 #pragma GCC visibility pop
 
 // The one precision dispatch of the host launch layer: f(T{}) with T the context's element type, its result returned.  A launch whose two

@@ -696,7 +696,10 @@ int32_t mivi_batch_lanes(const mivi_ctx_t *ctx, int32_t count);
  * exchange was lost on this context (mivi_optimize_loop then restored the caller's state, re-ran the steps on the graph of launches and stays there);
  * 4: the number of hipGraphs recorded into the context's graph cache so far -- unchanged across two calls means the second one replayed;
  * 5: the number of device allocations the library holds right now in this process, over all contexts (the library's one allocate / free pair
- * counts them): equal before a context's creation and after its mivi_destroy means the context returned every allocation it made. */
+ * counts them): equal before a context's creation and after its mivi_destroy means the context returned every allocation it made;
+ * 6: the number of HIP streams, events and graph execs the library holds right now in this process, over all contexts (the caller's stream
+ * is not one of them; every one sits in an owner that counts its creation and its destruction): the same equality means the context
+ * destroyed every handle it created, the children's, the exchange pipelines' and the cached graph included. */
 int32_t mivi_batch_info(const mivi_ctx_t *ctx, const void *params_dev, int32_t what);
 
 /* ---- measurement hook (bench.py roofline leg) --------------------------------------------------------- *

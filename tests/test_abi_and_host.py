@@ -174,9 +174,7 @@ def test_graph_capture_has_one_owner():
         lines = [ln for ln in txt.splitlines() if "cap_stream" in ln]
         if f == owner:
             assert lines, f
-        elif f == "api_core.hip":   # the context's destruction releases it (~mivi_ctx_streams)
-            assert len(lines) == 1 and "hipStreamDestroy(cap_stream)" in lines[0], lines
-        else:
+        else:   # (the context's destruction releases it without naming it: the member is a Stream)
             assert not lines, (f, lines)
     abi = [(f, txt) for f, txt in hip.items() if f.startswith("api_")]   # (the kernels have `kind`s of their own)
     for f, txt in abi + [(h, open(os.path.join(csrc, h)).read()) for h in ("api_common.h", "mivi_internal.h")]:
@@ -185,6 +183,24 @@ def test_graph_capture_has_one_owner():
     internal = open(os.path.join(csrc, "mivi_internal.h")).read()
     cache = re.search(r"struct GraphKey \{.*?\n\};.*?struct GraphCache \{.*?\n\};", internal, flags=re.S).group(0)
     assert not re.search(r"\b(p0|p1|aux0|aux1)\b", cache), cache
+
+
+def test_stream_and_event_handles_have_one_owner():
+    """Streams and events are created and destroyed in ONE translation unit (csrc/api_core.hip: make_stream, make_event, handle_destroy),
+    a hipGraphExec is destroyed in the graph unit only; every other unit holds them in a Stream / Event / GraphExec (csrc/mivi_internal.h).
+    No unit but api_core.hip assigns a context's stream (StreamScope and LaneScope of api_common.h do it for a scope), and the context
+    keeps no own_stream flag: the name survives as the mivi_config_t field."""
+    csrc = os.path.join(ROOT, "advancedvi.jl_amd", "csrc")
+    hip = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+    owner_of = {"hipStreamCreate": "api_core.hip", "hipExtStreamCreateWithCUMask": "api_core.hip", "hipStreamDestroy": "api_core.hip",
+                "hipEventCreate": "api_core.hip", "hipEventDestroy": "api_core.hip", "hipGraphExecDestroy": "api_graph.hip",
+                "->stream = ": "api_core.hip"}
+    for tok, owner in owner_of.items():
+        named_in = [f for f, txt in hip.items() if tok in txt]
+        assert named_in == [owner], (tok, named_in)
+    for f, txt in hip.items():
+        stray = [ln for ln in txt.splitlines() if re.search(r"(?<!cfg\.)(?<!cfg->)\bown_stream\b", ln)]
+        assert not stray, (f, stray)
 
 
 def test_precision_dispatch_is_written_once():

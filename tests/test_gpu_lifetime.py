@@ -4,6 +4,11 @@ allocate / free pair), so each scenario reads the count through a small probe co
 in its docstring at the smallest shapes that reach them, closes it and asks for the SAME count -- an equality with no margin.  The count
 must also have been larger while the scenario's contexts lived, so a counter that never moves cannot pass.
 
+The streams, events and graph execs the library creates have owners of the same kind (Stream, Event, GraphExec) and a count of their own
+(mivi_batch_info what = 6): every scenario asks for the same equality on it, and the scenarios that must create handles -- children with
+their streams and fork / join events, the capture stream and a cached graph, the two exchange pipelines -- also for its growth.  The
+timing entries hold only temporaries (two events, a graph), so theirs is the equality alone.
+
 A child context of the lane-batched routes borrows the parent's target vectors and its status word instead of owning copies; the second
 test changes the parent's target under living children and asks for the single calls' results."""
 import gc
@@ -73,6 +78,29 @@ def engine_batches():
     stl.estimate_gradient_each(ps, 1, 4)
     stl.synchronize()
     return [ctx, stl]
+
+
+def engine_sharded_with_communicator():
+    """the batch engine's sharded batch behind a communicator of one rank, full-rank f32 d = 128: 90 estimates are two engine steps, the
+    all-reduce + finalisation of each on the engine's exchange pipeline (fb_pipe: a stream and four events)"""
+    ctx, p, _ = _ctx(avi.FULLRANK, 128, 128, "diag")
+    ctx.comm_init(ctx.comm_unique_id(), 0, 1)
+    ctx.comm_set_route("allreduce")
+    ctx.estimate_gradient_dist_n(p, 3, 90, ctx.empty(1), ctx.empty(ctx.params_len))
+    ctx.synchronize()
+    return [ctx]
+
+
+def profile_entries():
+    """the three timing entries, full-rank f32 d = 128: a product and a VJP stage (two timing events and a temporary graph each), the
+    engine's kernels, the sharded step on one rank without a communicator"""
+    ctx, p, _ = _ctx(avi.FULLRANK, 128, 128, "diag")
+    ctx.profile_kernel(2, p, 2)
+    ctx.profile_kernel(3, p, 2)
+    ctx.profile_batch(p, 4, 2)
+    ctx.profile_dist(p, 4)
+    ctx.synchronize()
+    return [ctx]
 
 
 def _p2p(detach):
@@ -182,7 +210,10 @@ def measure_space_host_updates():
 
 SCENARIOS = [meanfield_f64_loop, fullrank_stl_children_stein, engine_batches, p2p_world_one_detached, p2p_world_one_left_attached,
              logreg_planes_and_rows, lowrank_estimate_sample_logpdf, laplace_base_then_normal, stacked_bijector_blocks, score_gradient,
-             measure_space_host_updates]
+             measure_space_host_updates, engine_sharded_with_communicator, profile_entries]
+# (scenario, it must leave handles on its contexts)
+HANDLE_SCENARIOS = [(fullrank_stl_children_stein, True), (p2p_world_one_detached, True), (p2p_world_one_left_attached, True),
+                    (engine_sharded_with_communicator, True), (profile_entries, False)]
 
 
 def _probe():
@@ -191,19 +222,37 @@ def _probe():
     return probe, probe.live_allocations()
 
 
-@pytest.mark.parametrize("scenario", SCENARIOS, ids=lambda s: s.__name__)
-def test_destroy_returns_every_allocation(scenario):
-    probe, n0 = _probe()
+def _run(scenario, count):
+    """count() before the scenario, with its contexts alive, after their close()"""
+    n0 = count()
     ctxs = scenario()
-    alive = probe.live_allocations()
+    alive = count()
     for c in ctxs:
         c.close()
     del ctxs
     gc.collect()
-    n1 = probe.live_allocations()
+    return n0, alive, count()
+
+
+@pytest.mark.parametrize("scenario", SCENARIOS, ids=lambda s: s.__name__)
+def test_destroy_returns_every_allocation(scenario):
+    probe, _ = _probe()
+    (n0, h0), (alive, h_alive), (n1, h1) = _run(scenario, lambda: (probe.live_allocations(), probe.live_handles()))
     probe.close()
-    print(f"[lifetime] {scenario.__name__}: {n0} allocations before, {alive} with the scenario's contexts alive, {n1} after close()")
+    print(f"[lifetime] {scenario.__name__}: {n0} allocations before, {alive} with the scenario's contexts alive, {n1} after close(); "
+          f"handles {h0}, {h_alive}, {h1}")
     assert alive > n0
+    assert n1 == n0
+    assert h1 == h0
+
+
+@pytest.mark.parametrize("scenario,grows", HANDLE_SCENARIOS, ids=[s.__name__ for s, _ in HANDLE_SCENARIOS])
+def test_destroy_returns_every_handle(scenario, grows):
+    probe, _ = _probe()
+    n0, alive, n1 = _run(scenario, probe.live_handles)
+    probe.close()
+    print(f"[lifetime] {scenario.__name__}: {n0} handles before, {alive} with the scenario's contexts alive, {n1} after close()")
+    assert not grows or alive > n0
     assert n1 == n0
 
 
@@ -212,6 +261,7 @@ def test_children_borrow_the_parents_target():
     the same batch must give what single calls on a second context with that target give (tests/helpers.py assert_batch_matches_single);
     close() then returns everything, the children's buffers included."""
     probe, n0 = _probe()
+    h0 = probe.live_handles()
     d, M, n, idx = 64, 64, 8, 3
     ctx, p, rng = _ctx(avi.FULLRANK, d, M, "diag")
     ref = avi.MiviContext(F32, avi.FULLRANK, d, M, 0, SEED)
@@ -228,9 +278,11 @@ def test_children_borrow_the_parents_target():
     ref.synchronize()
     assert_batch_matches_single(v.item(), v1.item(), g.cpu().numpy(), g1.cpu().numpy(), engine=ctx.batch_takes_engine(p), what="new target")
     assert probe.live_allocations() > n0
+    assert probe.live_handles() > h0   # (the children's streams, the fork / join events, the capture stream, the cached graph)
     ctx.close()
     ref.close()
     gc.collect()
-    n1 = probe.live_allocations()
+    n1, h1 = probe.live_allocations(), probe.live_handles()
     probe.close()
     assert n1 == n0
+    assert h1 == h0
