@@ -4,7 +4,13 @@ the float64 autograd restatement of the reference's own expressions (tests/lowra
 Tolerances.  Samples and draws: those of tests/test_gpu_parity.py (1e-6 f32, 1e-14 f64, relative l2).  Closed-form estimators: TOL of
 that file (value relative, gradient relative l2: f32 1e-5 / 2e-5, f64 1e-12 / 1e-11).  Monte-Carlo / sticking-the-landing estimators (log q
 and Sigma^-1 (z - m) by Woodbury): the rule of tests/test_gpu_product_yardstick.py -- the error against the float64 reference is at most
-8 x the error of the numpy Woodbury evaluation in the context's dtype on the same inputs, floored at TOL."""
+8 x the error of the numpy Woodbury evaluation in the context's dtype on the same inputs, floored at TOL.
+
+For GRADIENTS the test to read is tests/test_gpu_lowrank_yardstick.py: per entry and per 64-row block, on classes that span decades, at
+shapes past one row block, one slice and one factor-column block (this file stops at d = 256, M = 128, and its whole-gradient bound
+admits a lost block on small D: tests/test_lowrank_ref_host.py).  What only this file covers: the entries' contracts (sample / rand,
+estimate_objective at any n_samples, the plugin route, _n / _each bitwise against single calls), the refusals and status bits, the
+device loop's equality with the host-driven loop for every rule and averager, and ClipScale on the scale diagonal."""
 import ctypes as C
 
 import numpy as np

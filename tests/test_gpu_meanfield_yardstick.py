@@ -23,8 +23,8 @@ rule restated as meanfield_ref.n_cc(d, M) and, for the launch-free batches, from
     f64        the single and split shape lists on one class each, one funnel and one batch case: u = 2^-53, a float64 yardstick, an
                np.longdouble reference
 Left out, and why:
-    the non-normal bases, the score estimator, the low-rank family: other kernels (csrc/kernels_basedist.hip, kernels_score.hip,
-        kernels_lowrank.hip) with restatements of their own; the criterion carries over, the expressions do not
+    the non-normal bases, the score estimator: other kernels (csrc/kernels_basedist.hip, kernels_score.hip) with restatements of their
+        own; the criterion carries over, the expressions do not (the low-rank family has its own: tests/test_gpu_lowrank_yardstick.py)
     k_mf_gen_loop and the funnel's updating loop (k_mf_funnel_sgd_loop): tests/test_gpu_optimize.py holds both to sequences of single
         calls plus update launches -- BITWISE for Descent and Adam wherever the loop and the single call share a summation order (the
         funnel loop always: M <= 256; k_mf_gen_loop for M <= 256 or d >= 2045), and only through the update rule (the step of a
