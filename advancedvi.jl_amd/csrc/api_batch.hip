@@ -48,8 +48,7 @@ static mivi_status_t estimate_gradient_chain(mivi_ctx *c, const void *params, ui
   if (s) return s;
   if (!prepare_tables(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");   // host->device uploads are not allowed inside the capture
   if ((s = reserve_target(c, c->cfg.n_mc))) return s;
-  static const bool no_fused_loop_n = getenv("MIVI_NO_FUSED_LOOP") != nullptr;
-  if (c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on && c->cfg.n_mc <= 4096 && !c->idx_src && !no_fused_loop_n) {
+  if (c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on && c->cfg.n_mc <= 4096 && !c->idx_src && !switches().no_fused_loop) {
     // rows are independent for this family / target pair: all `count` estimates run inside ONE launch (every workgroup
     // keeps its four rows and walks the estimate indices), the value partials are reduced by a second launch
     const size_t hist_doubles = (size_t)count * 4 * (size_t)((c->cfg.d + 3) / 4);
@@ -62,7 +61,7 @@ static mivi_status_t estimate_gradient_chain(mivi_ctx *c, const void *params, ui
     return MIVI_OK;
   }
   if (c->cfg.family == MIVI_MEANFIELD && c->target == TGT_FUNNEL && !c->funnel_constrained && !c->bij_on && c->cfg.n_mc <= 256 && !c->idx_src &&
-      !no_fused_loop_n) {
+      !switches().no_fused_loop) {
     // fused funnel target (BASELINE config 5): the cross-row sums enter row 0 and ell linearly, so the batch is launch-free too --
     // per-estimate partials to a history buffer, one finishing workgroup per estimate (k_mf_funnel_loop / _value)
     const size_t d4 = (size_t)((c->cfg.d + 3) / 4);
@@ -83,8 +82,7 @@ static mivi_status_t estimate_gradient_chain(mivi_ctx *c, const void *params, ui
   // use a capture + instantiation), an eager chain ~17 us but ~0.7 us more per estimate (north star, n = 1 / 5 / 10 / 20 estimates
   // done after 31 / 93 / 168 / 314 us eagerly against 39 / 97 / 166 / 301 us replayed).  MIVI_GRAPH_MIN pins the
   // smallest batch that is captured.
-  static const int graph_min = getenv("MIVI_GRAPH_MIN") ? atoi(getenv("MIVI_GRAPH_MIN")) : 6;
-  if (count < graph_min && c->cfg.family == MIVI_FULLRANK) {
+  if (count < switches().graph_min && c->cfg.family == MIVI_FULLRANK) {
     if ((s = record_chain(c, params, idx0, st, count, nullptr, value, grad))) return s;
     HIPCHK(c, hipGetLastError());
     return MIVI_OK;
@@ -103,10 +101,6 @@ static mivi_status_t estimate_gradient_chain(mivi_ctx *c, const void *params, ui
 }
 
 // ---- interleaved chains ------------------------------------------------------------------------------------------------------------
-static int chain_lanes() {   // developer override (A/B): MIVI_CHAINS = 1 .. 4
-  static const int v = getenv("MIVI_CHAINS") ? atoi(getenv("MIVI_CHAINS")) : 0;
-  return v;
-}
 mivi_status_t sync_kid(mivi_ctx *c, mivi_ctx *k, int lanes) {
   if (k->kid_gen == c->target_gen && k->idx_stride == lanes) return MIVI_OK;
   invalidate_graph(k);
@@ -174,24 +168,17 @@ template <class Branch> static mivi_status_t record_branches(mivi_ctx *c, int B,
 }
 
 // ---- third-generation batch engine (kernels_fullrank_batch.hip) -------------------------------------------------------------------------
-// `count` estimates at the same parameters as steps of up to fb_lanes_max() LANES: a step is four launches (eps, product + target, VJP,
+// `count` estimates at the same parameters as steps of up to switches().fb_lanes LANES: a step is four launches (eps, product + target, VJP,
 // values) that cover all of its lanes.  No child contexts, no forked graph: a lane's buffers are base + lane * stride.
-static int fb_lanes_max() {
-  // MIVI_FB_LANES: estimates per step (A/B).  Per estimate (eps + product + VJP, tools/fb_lane_curve.py, north-star shape): 8 lanes 8.4 us,
-  // 20: 4.6, 32: 4.05, 48: 3.95, 80: 3.90, 100: 4.05, 128: 4.11 -- the triangular product is paced by its heaviest tile up to ~30 lanes, and
-  // beyond ~90 the step's planes (4.5 MB per lane) outgrow the 256 MB memory-side cache (the draws' writes slow down first).  So long batches
-  // are cut into equal steps of at most 80 lanes (100 estimates: two steps of 50).
-  static const int v = getenv("MIVI_FB_LANES") ? atoi(getenv("MIVI_FB_LANES")) : 80;
-  return v < 1 ? 1 : (v > 256 ? 256 : v);
-}
-static bool fb_stl_on() {   // MIVI_FB_STL=0: the sticking-the-landing estimators keep the lane-batched second-generation kernels + solves (A/B)
-  static const bool off = getenv("MIVI_FB_STL") && atoi(getenv("MIVI_FB_STL")) == 0;
-  return !off;
-}
+// MIVI_FB_LANES: estimates per step (A/B).  Per estimate (eps + product + VJP, tools/fb_lane_curve.py, north-star shape): 8 lanes 8.4 us,
+// 20: 4.6, 32: 4.05, 48: 3.95, 80: 3.90, 100: 4.05, 128: 4.11 -- the triangular product is paced by its heaviest tile up to ~30 lanes, and
+// beyond ~90 the step's planes (4.5 MB per lane) outgrow the 256 MB memory-side cache (the draws' writes slow down first).  So long batches
+// are cut into equal steps of at most 80 lanes (100 estimates: two steps of 50).
+// MIVI_FB_STL=0: the sticking-the-landing estimators keep the lane-batched second-generation kernels + solves (A/B).
 static bool fb_route(const mivi_ctx *c, const void *params, const void *grad_last, const void *grads_all) {
   const bool stl = stl_entropy(c);
   return !c->is_child && c->base == MIVI_BASE_NORMAL && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && !c->bij_on && !c->idx_src && !c->dbg &&
-         (c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS) && (!stl || (fb_stl_on() && stl2_shape_ok(c, c->cfg.d))) &&
+         (c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS) && (!stl || (switches().fb_stl && stl2_shape_ok(c, c->cfg.d))) &&
          fb_shape_ok(c, c->cfg.n_mc) && ((!stl && c->target == TGT_DIAG_GAUSS) || fb_whole_tiles(c, c->cfg.n_mc)) &&   // (padded geometry: the diagonal target, no STL term)
          ((uintptr_t)params & 15) == 0 && ((uintptr_t)grad_last & 15) == 0 && ((uintptr_t)grads_all & 15) == 0;
 }
@@ -211,7 +198,7 @@ static mivi_status_t fb_batch(mivi_ctx *c, const void *params, uint64_t idx0, in
   // fb_pipe.stream, the partial vectors double-buffered) run UNDER the next steps' kernels -- across ranks the exchange, not the kernels, paces
   // the batch
   const bool overlap = dist && c->comm != nullptr;
-  const int Lmax = (overlap && c->comm_world > 1) ? (fb_lanes_max() < 24 ? fb_lanes_max() : 24) : fb_lanes_max();   // (one rank: nothing to hide, the widest steps)
+  const int Lmax = (overlap && c->comm_world > 1) ? (switches().fb_lanes < 24 ? switches().fb_lanes : 24) : switches().fb_lanes;   // (one rank: nothing to hide, the widest steps)
   const int steps = (count + Lmax - 1) / Lmax, L = (count + steps - 1) / steps, Llast = count - (steps - 1) * L;
   if (overlap && (s = ensure_pipe(c, c->fb_pipe, false))) return s;
   const size_t plen = (size_t)mivi_params_len(c);
@@ -302,7 +289,7 @@ static mivi_status_t fb_batch(mivi_ctx *c, const void *params, uint64_t idx0, in
     return fs;
   };
   // One stream, no graph: per step {draws (+ tril(C)'s planes as riders of the first) -> product -> VJP + values} = three launches for up to
-  // fb_lanes_max() estimates; the host is far ahead of the device.  (Measured and dropped: the batch as ONE hipGraph -- 4.45 against 4.26 us
+  // switches().fb_lanes estimates; the host is far ahead of the device.  (Measured and dropped: the batch as ONE hipGraph -- 4.45 against 4.26 us
   // per estimate in 100-estimate batches -- and the draws of step s + 1 on a second graph branch beside the products of step s: the draws
   // are bound by their 3 MB of plane writes per estimate and by the vector ALU, beside them the products ran 25 % longer: 4.58 us.)
   ExchangePipe &pipe = c->fb_pipe;
@@ -341,7 +328,7 @@ mivi_status_t mivi::fb_objective(mivi_ctx *c, const void *params, uint64_t idx, 
 // Lanes per step of a `count`-estimate batch on the batch engine (equal steps of at most MIVI_FB_LANES = 80): what a roofline leg must profile.
 int32_t mivi_batch_lanes(const mivi_ctx_t *c, int32_t count) {
   if (!c || count <= 0) return 0;
-  const int Lmax = fb_lanes_max(), steps = (count + Lmax - 1) / Lmax;
+  const int Lmax = switches().fb_lanes, steps = (count + Lmax - 1) / Lmax;
   return (count + steps - 1) / steps;
 }
 
@@ -364,7 +351,7 @@ mivi_status_t mivi_profile_batch(mivi_ctx_t *c, const void *params, int32_t lane
   if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_profile_batch")) return rs;
   (void)hipSetDevice(c->cfg.device);
   if (!fb_route(c, params, nullptr, nullptr)) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_profile_batch: this configuration does not take the batch engine");
-  if (lanes > fb_lanes_max()) lanes = fb_lanes_max();
+  if (lanes > switches().fb_lanes) lanes = switches().fb_lanes;
   char *o = (char *)c->tmp_out.p;
   mivi_status_t s = fb_batch(c, params, 1, lanes, o, o + 16, nullptr, nullptr);   // buffers, tables, operand planes of every lane
   if (s) return s;
@@ -436,14 +423,14 @@ static LanePlan lane_plan(const mivi_ctx *c, const void *params, const void *gra
   // branch pays for 20-estimate calls too: 9.0 -> 8.1 us; 100-estimate calls back to back 7.0 us; 8, 12 and 16 contexts agree there).
   // MIVI_LANE_BATCH=0 keeps every context on a branch of its own (A/B reference; the STL estimators do where their solve is not the
   // second-generation one); MIVI_CHAINS = contexts.
-  static const int lane_env = getenv("MIVI_LANE_BATCH") ? atoi(getenv("MIVI_LANE_BATCH")) : -1;
+  const int lane_env = switches().lane_batch, chains = switches().chains;
   int lane_e = 0;   // contexts per branch (0: one each)
-  if (lanes > 1 && (!stl_entropy(c) || stl2_shape_ok(c, c->cfg.n_mc)) && lds_use_prod32(c, c->cfg.n_mc) && lds_bf16x3() && ((uintptr_t)params & 15) == 0 &&
+  if (lanes > 1 && (!stl_entropy(c) || stl2_shape_ok(c, c->cfg.n_mc)) && lds_use_prod32(c, c->cfg.n_mc) && ((uintptr_t)params & 15) == 0 &&
       ((uintptr_t)grad & 15) == 0 && lane_env != 0) {
     lane_e = lane_env > 0 ? (lane_env > 4 ? 4 : lane_env) : 4;
     lanes = count < 12 ? 4 : 8;   // (isolated batches at the north star, 4 vs 8 contexts, us per estimate: 8: 10.8 / 10.4, 10: 11.0 / 11.5, 12: 9.9 / 9.4, 20: 9.1 / 8.1, 48: 8.3 / 7.2)
   }
-  if (chain_lanes() > 0) lanes = c->is_child ? 1 : (chain_lanes() > mivi_ctx::kMaxKids + 1 ? mivi_ctx::kMaxKids + 1 : chain_lanes());
+  if (chains > 0) lanes = c->is_child ? 1 : (chains > mivi_ctx::kMaxKids + 1 ? mivi_ctx::kMaxKids + 1 : chains);
   if (lane_e > 0 && (lanes % lane_e != 0 || count < lanes)) lane_e = 0;
   if (lane_e <= 0 && lanes > 4) lanes = 4;          // (as graph BRANCHES: at most four -- see kMaxKids)
   if (lane_e > 0 && lanes / lane_e > 4) lanes = 4 * lane_e;

@@ -5,6 +5,9 @@
 // estimates), api_optimize.hip (update rules, the device-resident loop), api_profile.hip (per-kernel timing entries),
 // api_graph.hip (hipGraph capture, the context's graph cache and its replay).
 #include <atomic>
+#include <climits>
+#include <cstddef>
+#include <cstdlib>
 
 #include "api_common.h"
 
@@ -43,7 +46,71 @@ mivi_status_t fail(mivi_ctx *c, mivi_status_t s, const char *msg) {
   return s;
 }
 
+// ---- the environment switches (switches.h): this table is the one place where libmivi reads the environment ----
 namespace mivi {
+namespace {
+enum SwitchKind {
+  SW_PRESENCE,      // bool: set to anything (also "0") = on
+  SW_ON_UNLESS_0,   // bool: on; "=0" (atoi) turns it off
+  SW_OFF_UNLESS_1,  // bool: off; "=1" (atoi) turns it on
+  SW_INT,           // int: atoi of the value, `def` when unset, clamped to lo .. hi
+  SW_STRING         // const char *: the value itself, nullptr when unset
+};
+constexpr int kNoLo = INT_MIN, kNoHi = INT_MAX;
+struct SwitchRow { const char *name; SwitchKind kind; size_t field; int def, lo, hi; const char *meaning; };
+#define SW(f) offsetof(Switches, f)
+const SwitchRow kSwitchTable[] = {
+    {"MIVI_FR_GEN1", SW_PRESENCE, SW(fr_gen1), 0, 0, 0, "full-rank f32: first-generation tile kernels at every shape (lds_path_shape_ok)"},
+    {"MIVI_STEIN_GEN1", SW_PRESENCE, SW(stein_gen1), 0, 0, 0, "Stein accumulation stage on the first-generation kernel (lds_stein_ok)"},
+    {"MIVI_STL_GEN1", SW_PRESENCE, SW(stl_gen1), 0, 0, 0, "sticking-the-landing solve: not the second-generation packed solve (stl2_shape_ok)"},
+    {"MIVI_STL_VALU", SW_PRESENCE, SW(stl_valu), 0, 0, 0, "first-generation solve on the vector ALU, not the 16-column look-ahead solve (launch_fr_stl)"},
+    {"MIVI_LR_F32_LOGITS", SW_PRESENCE, SW(lr_f32_logits), 0, 0, 0, "logistic regression: f32-MFMA logits kernel (the one d % 4 != 0 takes), no operand planes"},
+    {"MIVI_LR_NO_PLANES", SW_PRESENCE, SW(lr_no_planes), 0, 0, 0, "logistic regression: logits with X split in the tile (k_lr_logits_f16x2)"},
+    {"MIVI_LR_NO_XPLANES", SW_PRESENCE, SW(lr_no_xplanes), 0, 0, 0, "logistic regression: X^T R with the splits made in the tile (k_lr_xtr_f16x2)"},
+    {"MIVI_NO_FUSED_LOOP", SW_PRESENCE, SW(no_fused_loop), 0, 0, 0, "no launch-free loop kernels: batches and optimisation loops as graphs of launches"},
+    {"MIVI_NO_FUSED_UPDATE", SW_PRESENCE, SW(no_fused_update), 0, 0, 0, "graph loop: the optimiser step as a kernel of its own, not in the VJP epilogue"},
+    {"MIVI_FORCE_EXCHANGE_LOST", SW_PRESENCE, SW(force_exchange_lost), 0, 0, 0, "test hook (tests/test_gpu_loop_oracle.py): the first exchanging loop call counts as lost"},
+    {"MIVI_BATCH_GEN3", SW_ON_UNLESS_0, SW(batch_gen3), 0, 0, 0, "=0: batches off the third-generation engine, on the lane-batched second-generation kernels"},
+    {"MIVI_FB_STL", SW_ON_UNLESS_0, SW(fb_stl), 0, 0, 0, "=0: sticking-the-landing batches off the engine (lane-batched kernels + solves)"},
+    {"MIVI_PROD_QUAD", SW_ON_UNLESS_0, SW(prod_quad), 0, 0, 0, "=0: four lanes' sampling products as k_fr_prod32m tiles, not k_fr_prod32q"},
+    {"MIVI_P2P_DIRECT", SW_OFF_UNLESS_1, SW(p2p_direct), 0, 0, 0, "=1: sharded partials staged straight into the peers' buffers (mivi_p2p_partials_direct)"},
+    {"MIVI_GRAPH_MIN", SW_INT, SW(graph_min), 6, kNoLo, kNoHi, "smallest full-rank batch that is captured as a graph (shorter: an eager chain)"},
+    {"MIVI_CHAINS", SW_INT, SW(chains), 0, kNoLo, kNoHi, "> 0: that many interleaved contexts per batch (0: by shape)"},
+    {"MIVI_FB_LANES", SW_INT, SW(fb_lanes), 80, 1, 256, "estimates per step of the batch engine"},
+    {"MIVI_LANE_BATCH", SW_INT, SW(lane_batch), -1, kNoLo, kNoHi, "contexts per graph branch: 0 = every context on a branch of its own, 1 .. 4, < 0 = by shape"},
+    {"MIVI_VJP_STRIP", SW_INT, SW(vjp_strip), 3, 0, 32, "tiles per workgroup of the lane-batched VJP (k_fr_vjp32s); 0 = one each (k_fr_vjp32m)"},
+    {"MIVI_VJP_TILE", SW_INT, SW(vjp_tile), 0, kNoLo, kNoHi, "32 / 64 pins the second-generation VJP's tile size (0: by shape)"},
+    {"MIVI_RCCL_LIB", SW_STRING, SW(rccl_lib), 0, 0, 0, "path of the RCCL library to load (unset: the loader's search)"},
+#ifdef MIVI_DEV
+    {"MIVI_FB_DBG", SW_PRESENCE, SW(fb_dbg), 0, 0, 0, "batch engine: per-workgroup clock stamps, summarised on stderr"},
+    {"MIVI_STL_STAMPS", SW_PRESENCE, SW(stl_stamps), 0, 0, 0, "second-generation solve: per-block clock stamps on stderr"},
+    {"MIVI_FB_KNOCK", SW_INT, SW(fb_knock), 0, kNoLo, kNoHi, "batch engine: work-skipping bits (operand loads / MFMAs / epilogue / stores)"},
+    {"MIVI_FB_RING", SW_INT, SW(fb_ring), 0, kNoLo, kNoHi, "4 / 8 pins the engine product's ring depth (tools/fb_lane_curve.py)"},
+    {"MIVI_KNOCK", SW_INT, SW(knock), 0, kNoLo, kNoHi, "second-generation kernels: work-skipping bits"},
+#endif
+};
+#undef SW
+Switches read_switches() {
+  Switches s{};
+  for (const SwitchRow &r : kSwitchTable) {
+    const char *v = getenv(r.name);
+    void *f = (char *)&s + r.field;
+    switch (r.kind) {
+      case SW_PRESENCE: *(bool *)f = v != nullptr; break;
+      case SW_ON_UNLESS_0: *(bool *)f = !(v && atoi(v) == 0); break;
+      case SW_OFF_UNLESS_1: *(bool *)f = v && atoi(v) == 1; break;
+      case SW_INT: { const int x = v ? atoi(v) : r.def; *(int *)f = x < r.lo ? r.lo : (x > r.hi ? r.hi : x); break; }
+      case SW_STRING: *(const char **)f = v; break;
+    }
+  }
+  return s;
+}
+}  // namespace
+const Switches &switches() {
+  static const Switches s = read_switches();
+  return s;
+}
+
 bool grid_resident(const mivi_ctx *c, const void *kernel, int block, size_t dyn_lds, long long grid) {
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, dyn_lds) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -478,7 +545,7 @@ int32_t mivi_fullrank_route(const mivi_ctx_t *c, int32_t n_samples) {
   if (!c || c->cfg.family != MIVI_FULLRANK) return 0;
   if (n_samples <= 0) n_samples = c->cfg.n_mc;
   if (!lds_path_shape_ok(c, n_samples) || (c->target != TGT_DIAG_GAUSS && c->target != TGT_DENSE_GAUSS)) return 0;
-  return (lds_use_prod32(c, n_samples) ? 1 : 3) | (lds_bf16x3() ? 16 : 0);
+  return (lds_use_prod32(c, n_samples) ? 1 : 3) | 16;   // (bit 4: the bf16 matrix cores -- the only products this route has)
 }
 
 int32_t mivi_logreg_kernels(const mivi_ctx_t *c, int32_t n_samples) {

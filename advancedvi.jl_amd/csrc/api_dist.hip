@@ -18,8 +18,7 @@ struct RcclApi {
   const char *(*GetErrorString)(ncclResult_t) = nullptr;
 };
 void load_rccl(RcclApi &api) {
-  const char *env = getenv("MIVI_RCCL_LIB");
-  const char *cands[] = {env, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+  const char *cands[] = {switches().rccl_lib, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
   for (int pass = 0; pass < 2 && !api.lib; ++pass)       // pass 0: a copy the process already loaded (e.g. the host framework's)
     for (const char *n : cands)
       if (n && !api.lib) api.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL | (pass == 0 ? RTLD_NOLOAD : 0));
@@ -539,8 +538,7 @@ static void *ring_slot(const mivi_ctx *c, int k) { return k == 0 ? c->dist_P.p :
 // 13.4 -> 17.2 us), and a staging slot is released only after the unpack (the compute chain runs one group ahead instead of two): serial step
 // 36.9 -> 38.5 us, pipelined batch 13.2 -> 20.0 us per estimate.  It pays once the packed layout pads every column to 16 bytes.
 static bool p2p_direct_ok(const mivi_ctx *c, const void *params) {
-  static const bool off = !(getenv("MIVI_P2P_DIRECT") && atoi(getenv("MIVI_P2P_DIRECT")) == 1);
-  if (off || !c->p2p_on || !c->p2p_direct.p || c->cfg.family != MIVI_FULLRANK || c->cfg.dtype != MIVI_F32 || c->dbg) return false;
+  if (!switches().p2p_direct || !c->p2p_on || !c->p2p_direct.p || c->cfg.family != MIVI_FULLRANK || c->cfg.dtype != MIVI_F32 || c->dbg) return false;
   OutArgs on{};
   on.partials_mode = 1;
   return lds_route(c, params, c->cfg.n_mc, 1, on);
@@ -712,10 +710,9 @@ static mivi_status_t dist_batch(mivi_ctx *c, const void *params, uint64_t idx0, 
   if (p2p_pipe && c->p2p_pipe_state < 0) { p2p_pipe = false; mode = 1; }   // (its kernels did not run beside the compute chain on this context: serial steps)
   if (p2p_pipe) mode = 4;
   {   // lane-batched compute chain for the pipelined batches (see dist_sequence_lanes)
-    static const bool no_lanes = getenv("MIVI_LANE_BATCH") && atoi(getenv("MIVI_LANE_BATCH")) == 0;
     const OutArgs on = partials_out(c, c->dist_P.p);
-    const bool lane4 = mode == 4 && !no_lanes && !stl_entropy(c) && !c->dbg && c->cfg.family == MIVI_FULLRANK && lds_route(c, params, c->cfg.n_mc, 1, on) &&
-                       lds_use_prod32(c, c->cfg.n_mc) && lds_bf16x3() && count >= kGroup;
+    const bool lane4 = mode == 4 && switches().lane_batch != 0 && !stl_entropy(c) && !c->dbg && c->cfg.family == MIVI_FULLRANK && lds_route(c, params, c->cfg.n_mc, 1, on) &&
+                       lds_use_prod32(c, c->cfg.n_mc) && count >= kGroup;
     const int stride = lane4 ? kGroup : 1;
     if (c->dist_lane4 != lane4 || c->idx_stride != stride) { invalidate_graph(c); c->dist_lane4 = lane4; c->idx_stride = stride; }
     if (lane4) {

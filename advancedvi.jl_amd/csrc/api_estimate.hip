@@ -42,18 +42,12 @@ mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
   }
 }
 
-bool no_fused_update() {   // MIVI_NO_FUSED_UPDATE=1: separate update kernel in the graph loop (A/B reference)
-  static const bool v = getenv("MIVI_NO_FUSED_UPDATE") != nullptr;
-  return v;
-}
-
 bool hetero_ok(const mivi_ctx *c, int want_grad, const Chain *ch) {
   if (!want_grad || c->bij_on || c->base != MIVI_BASE_NORMAL) return false;   // (a Stacked bijector, a non-normal base: the explicit-sample routes)
   // (the fused funnel target's value workgroup also finishes two gradient entries, which an optimiser step right after the
   //  estimate must already see: chained only when nothing reads the gradient between the estimates)
   if (c->cfg.family == MIVI_MEANFIELD)
     return c->target == TGT_DIAG_GAUSS || (c->target == TGT_FUNNEL && !c->funnel_constrained && ch && ch->estimates_only);
-  if (c->cfg.dtype != MIVI_F32 && f64_valu()) return false;
   return c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS;
 }
 

@@ -110,8 +110,7 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   char *vbuf = (char *)c->X.p;
   char *gbuf = vbuf + 8 * es;
   double *rec = (double *)(((uintptr_t)(gbuf + plen * es) + 7) & ~(uintptr_t)7);
-  static const bool no_fused_loop_env = getenv("MIVI_NO_FUSED_LOOP") != nullptr;
-  const bool no_fused_loop = no_fused_loop_env || c->cfg.family == MIVI_LOWRANK || c->base != MIVI_BASE_NORMAL;   // (the low-rank family, a non-normal base: the graph of launches only)
+  const bool no_fused_loop = switches().no_fused_loop || c->cfg.family == MIVI_LOWRANK || c->base != MIVI_BASE_NORMAL;   // (the low-rank family, a non-normal base: the graph of launches only)
   const bool simple = rule <= 1 && l.op <= 1 && l.averager == 0;   // what the fused paths implement
   const bool default_adam = l.beta1 == 0.9 && l.beta2 == 0.999 && l.adam_eps == 1e-8;
   if (simple && (rule == 0 || default_adam) && c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on &&
@@ -223,7 +222,7 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
       chn.next_rng.idx_ptr = r.idx_ptr;
       // full-rank f32 MFMA path: the optimiser step (and ClipScale) rides in the VJP epilogue -- no update kernel
       const bool fuse_upd = simple && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && hetero_ok(c, 1) &&
-                            !no_fused_update();
+                            !switches().no_fused_update;
       FusedUpdate fu;
       if (fuse_upd) {
         fu.rule = rule;
@@ -296,8 +295,7 @@ mivi_status_t mivi_optimize_loop(mivi_ctx_t *c, void *params, const mivi_loop_t 
   bool used = false;
   c->last_status_bits = 0;   // only a bit-8 ("exchange lost") flag read by THIS call may trigger the retry below: a stale one would mask a real HIP error
   mivi_status_t s = optimize_loop_run(c, params, lp, may_exchange, &used);
-  static const bool force_lost = getenv("MIVI_FORCE_EXCHANGE_LOST") != nullptr;   // test hook (tests/test_gpu_loop_oracle.py): treat the first exchanging call as lost
-  if (force_lost && used && s == MIVI_OK) { s = MIVI_ERR_HIP; c->last_status_bits |= 8; }
+  if (switches().force_exchange_lost && used && s == MIVI_OK) { s = MIVI_ERR_HIP; c->last_status_bits |= 8; }
   if (s == MIVI_ERR_HIP && used && (c->last_status_bits & 8)) {
     const char *sp = (const char *)c->snap.p;
     HIPCHK(c, hipMemcpyAsync(params, sp, plen * es, hipMemcpyDeviceToDevice, c->stream));

@@ -120,13 +120,9 @@ __device__ __forceinline__ void tile_coords(const int d, const int M, int &ib, i
     Ktile = (MODE == MODE_SAMPLE) ? min(d, 32 * (ib + 1)) : d;
   }
 }
-template <int MODE>
-__device__ __forceinline__ void tile_coords(const int d, const int M, int &ib, int &nb_col, int &Ktile) {
-  tile_coords<MODE>(d, M, ib, nb_col, Ktile, (int)blockIdx.x);
-}
 
 // ---------------------------------------------------------------------------------------------
-// Epilogue shared by the MFMA and the generic tile kernels.  `get(row, col)` returns the reduced
+// Epilogue shared by the f32 and f64 MFMA tile kernels.  `get(row, col)` returns the reduced
 // accumulator of tile element (row, col); rs_lds[NT] holds per-thread partial row sums of A
 // (only meaningful for diagonal VJP tiles).  NT threads, all participate.
 // ---------------------------------------------------------------------------------------------
@@ -636,67 +632,6 @@ __global__ __launch_bounds__(NW * 64) void k_fr_tile_mfma(FrArgs<float> a) {
     if (tid == 0) a.ell_part[widx] = s;
   }
   MIVI_STAMP_K(a.dbg, MODE, 3);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Generic tile kernel (any T, VALU): same tiles and epilogue, 256 threads, LDS-staged 32x32x32.
-// Used for MIVI_F64 and as the in-library cross-check of the MFMA kernel.
-// ---------------------------------------------------------------------------------------------
-template <typename T, int MODE>
-__global__ __launch_bounds__(256) void k_fr_tile_generic(FrArgs<T> a) {
-  constexpr int NT = 256;
-  __shared__ T As[32][33];   // As[k][i]
-  __shared__ T Bs[32][33];   // Bs[k][n]
-  __shared__ T outt[32][33]; // outt[col][row]
-  __shared__ T rs_lds[NT];
-  __shared__ double red[4];
-  const int tid = threadIdx.x;
-  const int d = a.d, M = a.M;
-  int ib, cb, Ktile;
-  tile_coords<MODE>(d, M, ib, cb, Ktile);
-  const int i0 = ib * 32, n0 = cb * 32;
-  const int row = tid & 31, cg = tid >> 5;
-  T acc[4] = {0, 0, 0, 0};
-  T rs = 0;
-  for (int k0 = 0; k0 < Ktile; k0 += 32) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int kl = cg + 8 * u, kk = k0 + kl;
-      const int gi = i0 + row, gn = n0 + row;
-      T av = 0, bv = 0;
-      if (MODE == MODE_SAMPLE) {
-        if (gi < d && kk <= gi && kk < d) av = a.params[d + (size_t)kk * d + gi];
-        if (kk < d) bv = a.epsT[(size_t)kk * a.MP + gn];
-      } else if (MODE == MODE_VJP) {
-        if (gi < d && kk < M) av = a.W[(size_t)kk * d + gi];
-        if (kk < M) bv = a.eps[(size_t)kk * a.dP + gn];
-      } else {
-        if (kk < d) av = a.t_prec[(size_t)kk * a.dP + gi];
-        if (kk < d) bv = a.RT[(size_t)kk * a.MP + gn];
-      }
-      As[kl][row] = av;
-      Bs[kl][row] = bv;
-      if (MODE == MODE_VJP) rs += av;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int kl = 0; kl < 32; ++kl) {
-      const T av = As[kl][row];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] += av * Bs[kl][cg + 8 * j];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) outt[cg + 8 * j][row] = acc[j];
-  rs_lds[tid] = rs;
-  __syncthreads();
-  auto get = [&](int r, int c) -> T { return outt[c][r]; };
-  const double ell = tile_epilogue<T, MODE, NT>(a, ib, cb, get, rs_lds, red);
-  if (MODE != MODE_VJP && (MODE == MODE_DENSE || a.fused_target == TGT_DIAG_GAUSS)) {
-    const double s2 = block_sum<double, NT>(ell, red);
-    if (tid == 0) a.ell_part[blockIdx.x] = s2;
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1288,12 +1223,6 @@ static FrArgs<T> fr_args(mivi_ctx *c, const void *params, int M) {
   return a;
 }
 
-// MIVI_F64_VALU=1 keeps the f64 tiles on the vector ALU (the in-library cross-check of the f64 MFMA kernel)
-bool f64_valu() {
-  static const bool v = getenv("MIVI_F64_VALU") != nullptr;
-  return v;
-}
-
 // The f32 launchers below read the tables their driver prepared (fr_prepare).  Tables built for another sample count would send a kernel
 // past its buffers, so a launcher that does not find the ones for its M launches nothing and leaves the reason in c->err.
 static void tabs_missing(mivi_ctx *c) { c->err = "full-rank work tables: a launch came before fr_prepare for its sample count"; }
@@ -1325,18 +1254,14 @@ void launch_fr_sample(mivi_ctx *c, const void *params, int M, int fused_target, 
     a.fused_target = fused_target;
     a.Z = (double *)Z;
     a.n_work = 0x7fffffff;
-    if (f64_valu()) {
-      hipLaunchKernelGGL((k_fr_tile_generic<double, MODE_SAMPLE>), dim3(nblk), dim3(256), 0, c->stream, a);
-    } else {
-      int grid = nblk;
-      if (prev) {   // one trailing workgroup assembles the previous estimate's value
-        a.n_work = nblk;
-        a.prev_vin = prev->vin;
-        a.prev_out = prev->out;
-        grid += 1;
-      }
-      hipLaunchKernelGGL((k_fr_tile_mfma64<MODE_SAMPLE, 8>), dim3(grid), dim3(512), 0, c->stream, a);
+    int grid = nblk;
+    if (prev) {   // one trailing workgroup assembles the previous estimate's value
+      a.n_work = nblk;
+      a.prev_vin = prev->vin;
+      a.prev_out = prev->out;
+      grid += 1;
     }
+    hipLaunchKernelGGL((k_fr_tile_mfma64<MODE_SAMPLE, 8>), dim3(grid), dim3(512), 0, c->stream, a);
   }
 }
 
@@ -1355,10 +1280,7 @@ void launch_fr_dense_target(mivi_ctx *c, int M, int want_grad) {
     const int nblk = ((c->cfg.d + 31) / 32) * ((M + 31) / 32);
     FrArgs<double> a = fr_args<double>(c, nullptr, M);
     a.n_work = 0x7fffffff;
-    if (f64_valu())
-      hipLaunchKernelGGL((k_fr_tile_generic<double, MODE_DENSE>), dim3(nblk), dim3(256), 0, c->stream, a);
-    else
-      hipLaunchKernelGGL((k_fr_tile_mfma64<MODE_DENSE, 8>), dim3(nblk), dim3(512), 0, c->stream, a);
+    hipLaunchKernelGGL((k_fr_tile_mfma64<MODE_DENSE, 8>), dim3(nblk), dim3(512), 0, c->stream, a);
   }
 }
 
@@ -1398,23 +1320,19 @@ void launch_fr_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, c
     a.out = out;
     const int ntile = nb * (nb + 1) / 2;
     a.n_work = 0x7fffffff;
-    if (f64_valu()) {
-      hipLaunchKernelGGL((k_fr_tile_generic<double, MODE_VJP>), dim3(ntile), dim3(256), 0, c->stream, a);
-    } else {
-      int grid = ntile;
-      if (self) {
-        a.n_work = ntile;
-        a.prev_vin = self->vin;
-        a.prev_out = self->out;
-        grid += 1;
-      }
-      if (next) {
-        a.n_pre = eps_blocks(c, M);
-        a.next_eps = eps_args<double>(c, next->rng, M, next->parity);
-        grid += a.n_pre;
-      }
-      hipLaunchKernelGGL((k_fr_tile_mfma64<MODE_VJP, 8>), dim3(grid), dim3(512), 0, c->stream, a);
+    int grid = ntile;
+    if (self) {
+      a.n_work = ntile;
+      a.prev_vin = self->vin;
+      a.prev_out = self->out;
+      grid += 1;
     }
+    if (next) {
+      a.n_pre = eps_blocks(c, M);
+      a.next_eps = eps_args<double>(c, next->rng, M, next->parity);
+      grid += a.n_pre;
+    }
+    hipLaunchKernelGGL((k_fr_tile_mfma64<MODE_VJP, 8>), dim3(grid), dim3(512), 0, c->stream, a);
   }
 }
 
@@ -1589,10 +1507,10 @@ void launch_stl_dinv32(mivi_ctx *c, const void *params, void *DinvT) {
 // side laid out like eps (leading dimension dP, zero padded) and any output laid out like W (leading dimension d)
 void launch_fr_stl(mivi_ctx *c, const void *params, int M, const void *rhs, void *out) {
   const int nblk = (M + 7) / 8;
-  static const bool old_stl = getenv("MIVI_STL_VALU") != nullptr;
+  const bool old_stl = switches().stl_valu;
   const size_t sh_mfma16 = ((size_t)c->dP * 16 + 8 * 8 * 64) * sizeof(float);   // 16-column solve: d up to 2304
   const size_t sh16_f64 = ((size_t)c->dP * 16 + 8 * 8 * 64) * sizeof(double);   // f64: d up to 1024
-  if (c->cfg.dtype == MIVI_F64 && c->stl_CT.p && sh16_f64 <= 160 * 1024 && !old_stl && !f64_valu()) {
+  if (c->cfg.dtype == MIVI_F64 && c->stl_CT.p && sh16_f64 <= 160 * 1024 && !old_stl) {
     FrArgs<double> a = fr_args<double>(c, params, M);
     if (rhs) a.eps = (const double *)rhs;
     if (out) a.W = (double *)out;

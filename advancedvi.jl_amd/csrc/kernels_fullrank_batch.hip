@@ -1091,8 +1091,7 @@ constexpr int kOwnCuTilesPerCU10 = 17;   // (x 0.1) tiles per CU up to which the
 // batches keep whole tiles (fb_whole_tiles: their parameter-only operands P / C^-T and the tile-packed partial vector are laid out by d).
 static int fb_pad(int x) { return (x + 127) / 128 * 128; }
 bool fb_shape_ok(const mivi_ctx *c, int M) {
-  static const bool off = getenv("MIVI_BATCH_GEN3") && atoi(getenv("MIVI_BATCH_GEN3")) == 0;   // A/B: the lane-batched second-generation kernels
-  return !off && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && c->cfg.d % 32 == 0 && M % 32 == 0 && c->cfg.d >= kBM &&
+  return switches().batch_gen3 && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && c->cfg.d % 32 == 0 && M % 32 == 0 && c->cfg.d >= kBM &&
          c->cfg.d <= 2048 && M >= 128 && M <= 2048;   // (the inverse-scale tables of k_fb_prod<FB_DENSE_G> / k_fb_vjp hold 2048 entries)
 }
 bool fb_whole_tiles(const mivi_ctx *c, int M) { return c->cfg.d % kBM == 0 && M % kBN == 0; }
@@ -1271,7 +1270,7 @@ void fb_launch_compute(mivi_ctx *c, const FbStep &s, hipStream_t stream, int whi
   // The one allocation outside ensure / DevBuf::release (api_core.hip), on purpose: a developer timeline buffer that lives as long as the
   // process.  It must not become a static DevBuf: its destructor would call into a HIP runtime that is already torn down at exit.
   static long long *dbg_buf = nullptr;
-  static const bool dbg_on = getenv("MIVI_FB_DBG") != nullptr;
+  const bool dbg_on = switches().fb_dbg;
   if (dbg_on && !dbg_buf) (void)hipMalloc(&dbg_buf, 2 * 8192 * 8 * sizeof(long long));
   auto dump = [&](const char *name, int n) {
     if (!dbg_on) return;
@@ -1290,7 +1289,7 @@ void fb_launch_compute(mivi_ctx *c, const FbStep &s, hipStream_t stream, int whi
     fprintf(stderr, "[fbdbg]   starts (us): p25 %.2f p50 %.2f p75 %.2f p90 %.2f max %.2f\n", st[n / 4] * 0.01, st[n / 2] * 0.01, st[3 * n / 4] * 0.01, st[9 * n / 10] * 0.01, st[n - 1] * 0.01);
   };
   a.dbg = dbg_on ? dbg_buf : nullptr;
-  a.knock = getenv("MIVI_FB_KNOCK") ? atoi(getenv("MIVI_FB_KNOCK")) : 0;
+  a.knock = switches().fb_knock;
 #endif
   a.work = (const int4 *)tb.prod.p; a.n_work = tb.n_prod;
   // One workgroup per CU (eight ring slots) where a step's heaviest tiles pace the launch and a second workgroup on their CU only slows them:
@@ -1303,9 +1302,8 @@ void fb_launch_compute(mivi_ctx *c, const FbStep &s, hipStream_t stream, int whi
   const int n_cu = c->n_cu > 0 ? c->n_cu : 256;
   auto own_cu_for = [&](int n, bool equal_tiles) {
 #ifdef MIVI_DEV
-    static const int force_ring = getenv("MIVI_FB_RING") ? atoi(getenv("MIVI_FB_RING")) : 0;   // developer builds: 4 / 8 pins the ring (tools/fb_lane_curve.py)
-    if (force_ring == 4) return false;
-    if (force_ring == 8) return true;
+    if (switches().fb_ring == 4) return false;   // developer builds: 4 / 8 pins the ring (tools/fb_lane_curve.py)
+    if (switches().fb_ring == 8) return true;
 #endif
     // tiles per CU (x 10) up to which the one-per-CU ring wins, by the heaviest tile's chain (gmax = d / 16 groups): measured at
     // (512, 128) and (512, 512) -- 32 groups: never --, (1024, 256) -- 64 groups: up to 1.7 --, (2048, 128) -- 128 groups: up to 2.2 (32 lanes:

@@ -10,8 +10,8 @@
 // contraction at d=1024, M=256 against 3.1 MB of input).  What runs now, by shape (launch_* at the end of the file):
 //   * every wave stages its OWN k range of both operands through a private LDS buffer with direct-to-LDS loads
 //     (global_load_lds_dwordx4) and waits on its own vmcnt: no workgroup barrier before the epilogue;
-//   * products are v_mfma_f32_32x32x16_bf16 x 6 on the exact three-way bf16 split of the f32 operands (mfma_bf16x3);
-//     MIVI_FR_F32MFMA=1 keeps the v_mfma_f32_32x32x2_f32 chains as a reference;
+//   * products are v_mfma_f32_32x32x16_bf16 x 6 on the exact three-way bf16 split of the f32 operands (mfma_bf16x3); the
+//     v_mfma_f32_32x32x2_f32 chains they replaced (same 1e-7 against the fp64 oracle) were a switch-only reference and are gone;
 //   * k_fr_prod32 / k_fr_vjp32: 32x32 tiles, one per workgroup, for d * n_mc <= 1024 * 512 (the north star: 256 product tiles = 256
 //     CUs, 528 VJP tiles, three resident per CU); the target, the ell / log-det partials and (riders) eps of the next estimate
 //     and the STL solve's parameter-only preparation live in the product kernel, the optimiser step in the VJP epilogue;
@@ -81,7 +81,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 // v_mfma_f32_32x32x16_bf16  lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi  accumulated in f32 (smallest terms first).  The three
 // dropped terms are <= 3 * 2^-24 of |x y|: f32-roundoff class (measured against the fp64 oracle: the same 1e-7 as the
 // f32-MFMA chain).  Six 8-pass MFMAs per 16 k replace eight 16-pass f32 MFMAs: 2.7x less matrix-pipe time; the split costs
-// ~5.5 VALU per operand element, which runs beside the other wave's MFMAs.  MIVI_FR_F32MFMA=1 selects the f32-MFMA chain.
+// ~5.5 VALU per operand element, which runs beside the other wave's MFMAs.
 // -----------------------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
@@ -125,7 +125,7 @@ __device__ __forceinline__ void mfma_bf16x3(const float *av, const float *bv, f3
 //   a SIMD (2-3 workgroups are resident per CU: 48 KiB of LDS each) drift apart and fill each other's load latency.
 //   All 528 tiles of the north star are resident at once: no second dispatch round for the tiles beyond 2 x 256.
 // -----------------------------------------------------------------------------------------------------------------
-template <bool FUSED, bool BF3>
+template <bool FUSED>
 __device__ __forceinline__ void fr_vjp32_body(const GemmArgs &a) {
   constexpr int BM = 32, BN = 32, KW = 4, NT = 256, SUB = 32, RING = 1, NV = SUB / 2;   // (SUB 16, RING 3 measured slower: 7.4 vs 6.6 us)
   constexpr int LDC = BM + 4;
@@ -214,13 +214,8 @@ __device__ __forceinline__ void fr_vjp32_body(const GemmArgs &a) {
       for (int i = 0; i < NV; ++i) rsum += av[i];
     }
     if (!MIVI_KNOCKED(a, 2)) {
-      if (BF3) {
 #pragma unroll
-        for (int g = 0; g < NV / 8; ++g) mfma_bf16x3(av + 8 * g, bv + 8 * g, acc);
-      } else {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[i], acc, 0, 0, 0);
-      }
+      for (int g = 0; g < NV / 8; ++g) mfma_bf16x3(av + 8 * g, bv + 8 * g, acc);
     }
   }
   __builtin_amdgcn_s_barrier();   // every wave is done with its buffer: LDS becomes the epilogue image
@@ -241,10 +236,10 @@ __device__ __forceinline__ void fr_vjp32_body(const GemmArgs &a) {
 }
 
 struct GemmMulti { GemmArgs lane[4]; };   // (kMaxLanes, see k_fr_prod32m)
-template <bool FUSED, bool BF3>
-__global__ __launch_bounds__(256) void k_fr_vjp32(GemmArgs a) { fr_vjp32_body<FUSED, BF3>(a); }
-template <bool FUSED, bool BF3>
-__global__ __launch_bounds__(256) void k_fr_vjp32m(GemmMulti m) { fr_vjp32_body<FUSED, BF3>(m.lane[blockIdx.y]); }
+template <bool FUSED>
+__global__ __launch_bounds__(256) void k_fr_vjp32(GemmArgs a) { fr_vjp32_body<FUSED>(a); }
+template <bool FUSED>
+__global__ __launch_bounds__(256) void k_fr_vjp32m(GemmMulti m) { fr_vjp32_body<FUSED>(m.lane[blockIdx.y]); }
 
 // -----------------------------------------------------------------------------------------------------------------
 // k_fr_vjp32s: the VJP of lane-batched estimates on STRIPS -- a workgroup takes up to NS consecutive 32 x 32 tiles of ONE block row
@@ -357,7 +352,7 @@ __global__ __launch_bounds__(256) void k_fr_vjp32s(StripMulti m) {
 //   (6.0 vs 7.4 us) although its most loaded CUs carry 192 KiB against 128 KiB here -- see launch_lds_vjp.
 // Epilogue: vjp_epilogue<64, 64, 8, 512> (the eight partial tiles summed in wave order through LDS).
 // -----------------------------------------------------------------------------------------------------------------
-template <bool FUSED, bool BF3, bool STEIN = false>
+template <bool FUSED, bool STEIN = false>
 __global__ __launch_bounds__(512) void k_fr_vjp64(GemmArgs a) {
   constexpr int BM = 64, BN = 64, KW = 8, NT = 512, SUB = 32;
   constexpr int LDC = BM + 4;
@@ -450,36 +445,27 @@ __global__ __launch_bounds__(512) void k_fr_vjp64(GemmArgs a) {
       for (int i = 0; i < 16; ++i) { rsum[0] += bv[0][i]; rsum[1] += bv[1][i]; }
     }
     if (!MIVI_KNOCKED(a, 2)) {
-      if (BF3) {
 #pragma unroll
-        for (int g = 0; g < 2; ++g) {   // two K = 16 groups per sub-stage; every operand half is split ONCE for its two tiles
-          bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
+      for (int g = 0; g < 2; ++g) {   // two K = 16 groups per sub-stage; every operand half is split ONCE for its two tiles
+        bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
 #pragma unroll
-          for (int x = 0; x < 2; ++x) {
-            split3_bf16(av[x] + 8 * g, ah[x], am[x], al[x]);
-            split3_bf16(bv[x] + 8 * g, bh[x], bm[x], bl[x]);
-          }
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              f32x16 c = acc[i][j];
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bm[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], c, 0, 0, 0);
-              acc[i][j] = c;
-            }
+        for (int x = 0; x < 2; ++x) {
+          split3_bf16(av[x] + 8 * g, ah[x], am[x], al[x]);
+          split3_bf16(bv[x] + 8 * g, bh[x], bm[x], bl[x]);
         }
-      } else {
 #pragma unroll
-        for (int e = 0; e < 16; ++e)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < 2; ++j) {
+            f32x16 c = acc[i][j];
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bm[j], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], c, 0, 0, 0);
+            acc[i][j] = c;
+          }
       }
     }
   }
@@ -523,7 +509,7 @@ __global__ __launch_bounds__(512) void k_fr_vjp64(GemmArgs a) {
 // Trailing workgroups draw eps of the next estimate; the first column block's workgroups leave the log-det partials.
 // -----------------------------------------------------------------------------------------------------------------
 
-template <int MODE, bool BF3>
+template <int MODE>
 __device__ __forceinline__ void fr_prod32_body(const Prod32Args &a) {
   constexpr int NW = 8, NT = 512, SUB = 32, LDC = 36;
   // ONE sub-stage buffer per wave (64 KiB per workgroup): with two (128 KiB, the wave's next sub-stage in flight under its MFMAs) a product
@@ -671,16 +657,11 @@ __device__ __forceinline__ void fr_prod32_body(const Prod32Args &a) {
         if (8 * (i >> 2) + 4 * h + (i & 3) > l31) av[i] = 0.f;
     }
     if (!MIVI_KNOCKED(a, 2)) {
-      if (BF3) {
-        float bv[16];
+      float bv[16];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) bv[i] = bq[i >> 2][i & 3];
-        mfma_bf16x3(av, bv, acc);
-        mfma_bf16x3(av + 8, bv + 8, acc);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bq[i >> 2][i & 3], acc, 0, 0, 0);
-      }
+      for (int i = 0; i < 16; ++i) bv[i] = bq[i >> 2][i & 3];
+      mfma_bf16x3(av, bv, acc);
+      mfma_bf16x3(av + 8, bv + 8, acc);
     }
   }
   __builtin_amdgcn_s_barrier();   // every wave is done with its buffer: LDS becomes the epilogue image
@@ -748,10 +729,10 @@ __device__ __forceinline__ void fr_prod32_body(const Prod32Args &a) {
 // operands and outputs: the contexts of mivi_estimate_gradient_n's interleaved estimates, api_batch.hip)
 constexpr int kMaxLanes = 4;
 struct Prod32Multi { Prod32Args lane[kMaxLanes]; };
-template <int MODE, bool BF3>
-__global__ __launch_bounds__(512) void k_fr_prod32(Prod32Args a) { fr_prod32_body<MODE, BF3>(a); }
-template <int MODE, bool BF3>
-__global__ __launch_bounds__(512) void k_fr_prod32m(Prod32Multi m) { fr_prod32_body<MODE, BF3>(m.lane[blockIdx.y]); }
+template <int MODE>
+__global__ __launch_bounds__(512) void k_fr_prod32(Prod32Args a) { fr_prod32_body<MODE>(a); }
+template <int MODE>
+__global__ __launch_bounds__(512) void k_fr_prod32m(Prod32Multi m) { fr_prod32_body<MODE>(m.lane[blockIdx.y]); }
 
 // -----------------------------------------------------------------------------------------------------------------
 // k_fr_prod32q: the sampling product of FOUR lanes (estimates at the same parameters: one tril(C), four eps) as 2 x 2 work per
@@ -999,7 +980,7 @@ __global__ __launch_bounds__(512) void k_fr_prod32q(Prod32Multi m) {
 // 8192 x 2048 against the 152 TF of the VJP kernel with this structure).  Tiles heaviest first (K = 64 (rb + 1) for the triangular product).
 // Trailing workgroups draw eps of the next estimate.
 // -----------------------------------------------------------------------------------------------------------------
-template <int MODE, bool BF3>
+template <int MODE>
 __global__ __launch_bounds__(512) void k_fr_prod64(Prod32Args a) {
   constexpr int BM = 64, BN = 64, KW = 8, NT = 512, SUB = 32;
   constexpr int LDC = BM + 4;
@@ -1108,36 +1089,27 @@ __global__ __launch_bounds__(512) void k_fr_prod64(Prod32Args a) {
         for (int i = 0; i < 16; ++i)
           if (32 * t + 8 * (i >> 2) + 4 * h + (i & 3) > row0 + 32 * x + l31) av[x][i] = 0.f;
     }
-    if (BF3) {
 #pragma unroll
-      for (int g = 0; g < 2; ++g) {   // two K = 16 groups per sub-stage; every operand half is split ONCE for its two tiles
-        bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
+    for (int g = 0; g < 2; ++g) {   // two K = 16 groups per sub-stage; every operand half is split ONCE for its two tiles
+      bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
 #pragma unroll
-        for (int x = 0; x < 2; ++x) {
-          split3_bf16(av[x] + 8 * g, ah[x], am[x], al[x]);
-          split3_bf16(bv[x] + 8 * g, bh[x], bm[x], bl[x]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            f32x16 c = acc[i][j];
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bm[j], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], c, 0, 0, 0);
-            acc[i][j] = c;
-          }
+      for (int x = 0; x < 2; ++x) {
+        split3_bf16(av[x] + 8 * g, ah[x], am[x], al[x]);
+        split3_bf16(bv[x] + 8 * g, bh[x], bm[x], bl[x]);
       }
-    } else {
 #pragma unroll
-      for (int e = 0; e < 16; ++e)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) {
+          f32x16 c = acc[i][j];
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bm[j], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], c, 0, 0, 0);
+          acc[i][j] = c;
+        }
     }
   }
   __builtin_amdgcn_s_barrier();   // every wave is done with its buffer: LDS becomes the epilogue image
@@ -1325,16 +1297,8 @@ bool build_strips(mivi_ctx *c, int d, int NS, DevBuf &tab, int &n_items) {
 }  // namespace
 
 bool lds_path_shape_ok(const mivi_ctx *c, int M) {
-  static const bool off = getenv("MIVI_FR_GEN1") != nullptr;   // A/B: first-generation tile kernels
-  return !off && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && c->cfg.d % 64 == 0 && M % 128 == 0 &&
+  return !switches().fr_gen1 && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && c->cfg.d % 64 == 0 && M % 128 == 0 &&
          c->cfg.d <= 65535 * 32 && M > 0;
-}
-
-static bool f32_mfma();
-static int knock_flags();
-static int vjp_strip_len() {   // MIVI_VJP_STRIP: tiles per workgroup of the lane-batched VJP (k_fr_vjp32s); 0 = one tile per workgroup (k_fr_vjp32m)
-  static const int v = getenv("MIVI_VJP_STRIP") ? atoi(getenv("MIVI_VJP_STRIP")) : 3;   // (748 workgroups at the north star: one round of three per CU)
-  return v < 0 ? 0 : (v > 32 ? 32 : v);
 }
 
 // (re)build the VJP work lists for M samples per launch (the product kernels derive their tile from blockIdx)
@@ -1344,7 +1308,7 @@ bool lds_prepare(mivi_ctx *c, int M) {
   const int d = c->cfg.d;
   c->lds_M = -1;   // (a failure below leaves no list looking valid)
   if (!build_vjp(c, d, M, 32, c->lds_tabV, c->lds_nV) || !build_vjp(c, d, M, 64, c->lds_tabV64, c->lds_nV64) ||
-      !build_strips(c, d, vjp_strip_len() ? vjp_strip_len() : 1, c->lds_tabS, c->lds_nS))
+      !build_strips(c, d, switches().vjp_strip ? switches().vjp_strip : 1, c->lds_tabS, c->lds_nS))   // (default 3: 748 workgroups at the north star, one round of three per CU)
     return false;
   c->lds_M = M;
   return true;
@@ -1353,8 +1317,7 @@ bool lds_prepare(mivi_ctx *c, int M) {
 // Stein accumulation stage on the second-generation kernels: A (+)= eps G^T (all of it), gsum (+)= G 1, one 64 x 64 tile per workgroup
 // (k_fr_vjp64<.., STEIN>); self: the chunk's value partials are assembled by one more workgroup of the same launch.
 bool lds_stein_ok(const mivi_ctx *c, int M) {
-  static const bool off = getenv("MIVI_STEIN_GEN1") != nullptr;   // A/B: the first-generation kernel
-  return !off && lds_path_shape_ok(c, M) && !f32_mfma();   // (d is a multiple of 64: the padded leading dimension dP equals d)
+  return !switches().stein_gen1 && lds_path_shape_ok(c, M);   // (d is a multiple of 64: the padded leading dimension dP equals d)
 }
 bool launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first, double scale, double n, void *grad, void *logpi,
                             const ValueJob *self) {
@@ -1379,7 +1342,7 @@ bool launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first
   a.work = (const int4 *)c->lds_tabSt.p;
   a.n_work = 0x7fffffff;
   a.dbg = c->dbg;
-  a.knock = knock_flags();
+  a.knock = switches().knock;   // developer knock-outs (operand loads / MFMAs / epilogue / stores): 0 outside -DMIVI_DEV builds
   a.st_A = (float *)A; a.st_ld = c->dP;
   a.st_gsum = gsum;
   a.st_grad = (float *)grad;
@@ -1394,24 +1357,11 @@ bool launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first
     a.self_out = self->out;
     grid += 1;
   }
-  hipLaunchKernelGGL((k_fr_vjp64<false, true, true>), dim3(grid), dim3(512), 0, c->stream, a);
+  hipLaunchKernelGGL((k_fr_vjp64<false, true>), dim3(grid), dim3(512), 0, c->stream, a);
   return true;
 }
 
 int lds_ld_blocks(const mivi_ctx *c) { return c->cfg.d / 64; }
-
-static bool f32_mfma() {   // MIVI_FR_F32MFMA=1: v_mfma_f32_32x32x2_f32 chains instead of bf16x3 (A/B reference)
-  static const bool v = getenv("MIVI_FR_F32MFMA") != nullptr;
-  return v;
-}
-static int knock_flags() {   // developer knock-outs (operand loads / MFMAs / epilogue / stores): -DMIVI_DEV builds only (make DEV=1)
-#ifdef MIVI_DEV
-  static const int v = getenv("MIVI_KNOCK") ? atoi(getenv("MIVI_KNOCK")) : 0;
-  return v;
-#else
-  return 0;
-#endif
-}
 
 // eps(t+1) rider blocks of the 64 x 64 product kernel: 512 threads = 64 rows x 32 columns each
 struct LaneKernelArgs {   // one lane's recorded launches of an estimate (LaneRecorder::kern; see launch_lanes_prod / launch_lanes_vjp)
@@ -1441,7 +1391,7 @@ void launch_lds_prod32(mivi_ctx *c, const void *params, int M, bool dense, int m
   a.ncb = M / 32;
   a.n_tiles = (c->cfg.d / 32) * a.ncb;
   a.dbg = c->dbg;
-  a.knock = knock_flags();
+  a.knock = switches().knock;
   int grid = a.n_tiles;
   if (next) {
     a.next_eps.d = c->cfg.d;
@@ -1466,10 +1416,8 @@ void launch_lds_prod32(mivi_ctx *c, const void *params, int M, bool dense, int m
     ++n_prod;
     return;
   }
-  if (dense && f32_mfma()) hipLaunchKernelGGL((k_fr_prod32<G_DENSE, false>), dim3(grid), dim3(512), 0, c->stream, a);
-  else if (dense) hipLaunchKernelGGL((k_fr_prod32<G_DENSE, true>), dim3(grid), dim3(512), 0, c->stream, a);
-  else if (f32_mfma()) hipLaunchKernelGGL((k_fr_prod32<G_SAMPLE, false>), dim3(grid), dim3(512), 0, c->stream, a);
-  else hipLaunchKernelGGL((k_fr_prod32<G_SAMPLE, true>), dim3(grid), dim3(512), 0, c->stream, a);
+  if (dense) hipLaunchKernelGGL(k_fr_prod32<G_DENSE>, dim3(grid), dim3(512), 0, c->stream, a);
+  else hipLaunchKernelGGL(k_fr_prod32<G_SAMPLE>, dim3(grid), dim3(512), 0, c->stream, a);
 }
 
 // ---- lane-batched launches: up to kMaxLanes contexts' product / VJP kernels as ONE launch each (blockIdx.y = lane) ---------------------
@@ -1477,13 +1425,9 @@ void lane_args_resize(LaneKernelArgs *&p, int lanes) {
   delete[] p;
   p = lanes > 0 ? new LaneKernelArgs[lanes]() : nullptr;
 }
-static bool prod_quad_on() {   // MIVI_PROD_QUAD=0: four lanes' sampling products as 4 x k_fr_prod32's tiles again (A/B)
-  static const bool v = !(getenv("MIVI_PROD_QUAD") && atoi(getenv("MIVI_PROD_QUAD")) == 0);
-  return v;
-}
 // which: 0 = the sampling product (with the fused diagonal target, or R = Z - m of the dense one), 1 = the dense target's product
 bool launch_lanes_prod(mivi_ctx *c, const LaneRecorder &rec, int lanes, int which) {
-  if (lanes < 1 || lanes > kMaxLanes || f32_mfma()) return false;
+  if (lanes < 1 || lanes > kMaxLanes) return false;
   const LaneKernelArgs *s = rec.kern;
   Prod32Multi m;
   for (int l = 0; l < lanes; ++l) {
@@ -1492,7 +1436,7 @@ bool launch_lanes_prod(mivi_ctx *c, const LaneRecorder &rec, int lanes, int whic
   }
   int gx = 0;   // (the lane that carries the STL riders may need trailing workgroups the others do not: d = 2048)
   for (int l = 0; l < lanes; ++l) gx = s[l].prod_grid[which] > gx ? s[l].prod_grid[which] : gx;
-  if (which == 0 && lanes == 4 && prod_quad_on()) {   // two tiles x two lanes per workgroup (k_fr_prod32q) where it applies
+  if (which == 0 && lanes == 4 && switches().prod_quad) {   // two tiles x two lanes per workgroup (k_fr_prod32q) where it applies (MIVI_PROD_QUAD=0: k_fr_prod32m's tiles)
     const Prod32Args &a = m.lane[0];
     const int nrb = a.d >> 5;
     bool ok = a.n_dinv == 0 && a.n_pack == 0 && (nrb & 3) == 0 && (a.ncb & 1) == 0 && a.n_tiles >= 256 &&
@@ -1509,19 +1453,19 @@ bool launch_lanes_prod(mivi_ctx *c, const LaneRecorder &rec, int lanes, int whic
     }
   }
   const dim3 grid(gx, lanes);
-  if (which) hipLaunchKernelGGL((k_fr_prod32m<G_DENSE, true>), grid, dim3(512), 0, c->stream, m);
-  else hipLaunchKernelGGL((k_fr_prod32m<G_SAMPLE, true>), grid, dim3(512), 0, c->stream, m);
+  if (which) hipLaunchKernelGGL(k_fr_prod32m<G_DENSE>, grid, dim3(512), 0, c->stream, m);
+  else hipLaunchKernelGGL(k_fr_prod32m<G_SAMPLE>, grid, dim3(512), 0, c->stream, m);
   return true;
 }
 bool launch_lanes_vjp(mivi_ctx *c, const LaneRecorder &rec, int lanes) {
-  if (lanes < 1 || lanes > kMaxLanes || f32_mfma()) return false;
+  if (lanes < 1 || lanes > kMaxLanes) return false;
   const LaneKernelArgs *s = rec.kern;
   GemmMulti m;
   for (int l = 0; l < lanes; ++l) {
     if (rec.lane[l].n_vjp != 1 || rec.lane[l].vjp_refused || s[l].vjp_grid != s[0].vjp_grid) return false;
     m.lane[l] = s[l].vjp;
   }
-  if (vjp_strip_len() > 0 && lanes >= 2 && m.lane[0].M == 256 && c->lds_tabS.p) {   // strips of tiles per workgroup where they apply
+  if (switches().vjp_strip > 0 && lanes >= 2 && m.lane[0].M == 256 && c->lds_tabS.p) {   // strips of tiles per workgroup where they apply
     bool ok = true;
     const bool self = m.lane[0].n_work != 0x7fffffff;   // (one more workgroup per lane assembles the estimate's value)
     for (int l = 0; l < lanes; ++l) ok = ok && (m.lane[l].n_work != 0x7fffffff) == self && m.lane[l].M == 256 && m.lane[l].d == m.lane[0].d;
@@ -1536,7 +1480,7 @@ bool launch_lanes_vjp(mivi_ctx *c, const LaneRecorder &rec, int lanes) {
       return true;
     }
   }
-  hipLaunchKernelGGL((k_fr_vjp32m<false, true>), dim3(s[0].vjp_grid, lanes), dim3(256), 0, c->stream, m);
+  hipLaunchKernelGGL(k_fr_vjp32m<false>, dim3(s[0].vjp_grid, lanes), dim3(256), 0, c->stream, m);
   return true;
 }
 // unsplit 64 x 64-tile product + fused epilogue for the large shapes (k_fr_prod64); arguments as launch_lds_prod32
@@ -1567,10 +1511,8 @@ void launch_lds_prod64(mivi_ctx *c, const void *params, int M, bool dense, int m
     a.n_eps = (c->cfg.d / 64) * (M / 32);
     grid += a.n_eps;
   }
-  if (dense && f32_mfma()) hipLaunchKernelGGL((k_fr_prod64<G_DENSE, false>), dim3(grid), dim3(512), 0, c->stream, a);
-  else if (dense) hipLaunchKernelGGL((k_fr_prod64<G_DENSE, true>), dim3(grid), dim3(512), 0, c->stream, a);
-  else if (f32_mfma()) hipLaunchKernelGGL((k_fr_prod64<G_SAMPLE, false>), dim3(grid), dim3(512), 0, c->stream, a);
-  else hipLaunchKernelGGL((k_fr_prod64<G_SAMPLE, true>), dim3(grid), dim3(512), 0, c->stream, a);
+  if (dense) hipLaunchKernelGGL(k_fr_prod64<G_DENSE>, dim3(grid), dim3(512), 0, c->stream, a);
+  else hipLaunchKernelGGL(k_fr_prod64<G_SAMPLE>, dim3(grid), dim3(512), 0, c->stream, a);
 }
 int lds_prod64_tiles(const mivi_ctx *c, int M) { return (c->cfg.d / 64) * (M / 64); }
 // beyond the 32 x 32 kernel's range (d n_mc > 1024 x 512: at least 128 tiles of 64 x 64) the 64 x 64 kernel; at and below the boundary
@@ -1580,7 +1522,6 @@ bool lds_use_prod64(const mivi_ctx *c, int M) { return !lds_use_prod32(c, M); }
 int lds_prod32_tiles(const mivi_ctx *c, int M) { return (c->cfg.d / 32) * (M / 32); }
 int lds_prod32_eps_blocks(const mivi_ctx *c, int M) { return (c->cfg.d / 64) * (M / 32); }
 // the unsplit 32 x 32 product is bounded by its heaviest tile (d/32 sub-stages on one CU); beyond this the 64 x 64 kernel takes over
-bool lds_bf16x3() { return !f32_mfma(); }
 bool lds_use_prod32(const mivi_ctx *c, int M) { return (long long)c->cfg.d * M <= 1024LL * 512; }
 
 // tril(W eps^T) (+ d/dmu); self != nullptr: one trailing workgroup assembles this estimate's objective value
@@ -1594,7 +1535,7 @@ void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, 
   a.params = (const float *)params;
   a.out = out;
   a.dbg = c->dbg;
-  a.knock = knock_flags();
+  a.knock = switches().knock;
   int grid = c->lds_nV;
   if (self) {
     a.n_work = c->lds_nV;
@@ -1607,7 +1548,7 @@ void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, 
   // staging with -- measured: 4096 x 1024 VJP 159 -> 145 us (118 TF), but 1024 x 256 6.0 -> 7.4 us and 2048 x 256 16.9 -> 20.4 us
   // (a wave's single sub-stage there is load, then compute, then a four times larger epilogue, nothing overlapped, against
   // two or three 32 x 32 workgroups per CU covering for each other).  MIVI_VJP_TILE=32 / 64 pins it.
-  static const int pin = getenv("MIVI_VJP_TILE") ? atoi(getenv("MIVI_VJP_TILE")) : 0;
+  const int pin = switches().vjp_tile;
   const bool t64 = pin ? pin == 64 : ((M >= 1024 && c->cfg.d >= 2048) || (M >= 512 && c->cfg.d >= 4096));   // (4096 x 512: 90.6 -> 83.7 us)
   LaneRecorder *rec = c->rec && !c->rec->closing ? c->rec : nullptr;
   if (t64 && rec) { rec->lane[c->lane_id].vjp_refused = true; return; }   // (not a lane-batched route: the driver reports it)
@@ -1615,10 +1556,8 @@ void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, 
     a.work = (const int4 *)c->lds_tabV64.p;
     grid = c->lds_nV64;
     if (self) { a.n_work = c->lds_nV64; grid += 1; }
-    if (upd && f32_mfma()) hipLaunchKernelGGL((k_fr_vjp64<true, false>), dim3(grid), dim3(512), 0, c->stream, a);
-    else if (upd) hipLaunchKernelGGL((k_fr_vjp64<true, true>), dim3(grid), dim3(512), 0, c->stream, a);
-    else if (f32_mfma()) hipLaunchKernelGGL((k_fr_vjp64<false, false>), dim3(grid), dim3(512), 0, c->stream, a);
-    else hipLaunchKernelGGL((k_fr_vjp64<false, true>), dim3(grid), dim3(512), 0, c->stream, a);
+    if (upd) hipLaunchKernelGGL(k_fr_vjp64<true>, dim3(grid), dim3(512), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_fr_vjp64<false>, dim3(grid), dim3(512), 0, c->stream, a);
     return;
   }
   if (rec) {   // lane-batched estimates: record (the driver only enters this mode where this route is taken)
@@ -1628,10 +1567,8 @@ void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, 
     ++ln.n_vjp;
     return;
   }
-  if (upd && f32_mfma()) hipLaunchKernelGGL((k_fr_vjp32<true, false>), dim3(grid), dim3(256), 0, c->stream, a);
-  else if (upd) hipLaunchKernelGGL((k_fr_vjp32<true, true>), dim3(grid), dim3(256), 0, c->stream, a);
-  else if (f32_mfma()) hipLaunchKernelGGL((k_fr_vjp32<false, false>), dim3(grid), dim3(256), 0, c->stream, a);
-  else hipLaunchKernelGGL((k_fr_vjp32<false, true>), dim3(grid), dim3(256), 0, c->stream, a);
+  if (upd) hipLaunchKernelGGL(k_fr_vjp32<true>, dim3(grid), dim3(256), 0, c->stream, a);
+  else hipLaunchKernelGGL(k_fr_vjp32<false>, dim3(grid), dim3(256), 0, c->stream, a);
 }
 
 }  // namespace mivi

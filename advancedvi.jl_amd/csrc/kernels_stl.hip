@@ -448,9 +448,8 @@ void lane_args_resize(LaneStlArgs *&p, int lanes) {
 
 // -----------------------------------------------------------------------------------------------------------------
 bool stl2_shape_ok(const mivi_ctx *c, int M) {
-  static const bool off = getenv("MIVI_STL_GEN1") != nullptr;
   const int d = c->cfg.d;
-  return !off && c->cfg.dtype == MIVI_F32 && c->cfg.family == MIVI_FULLRANK && (d == 256 || d == 512 || d == 1024 || d == 2048) &&
+  return !switches().stl_gen1 && c->cfg.dtype == MIVI_F32 && c->cfg.family == MIVI_FULLRANK && (d == 256 || d == 512 || d == 1024 || d == 2048) &&
          M % 32 == 0 && M > 0;
 }
 
@@ -500,7 +499,7 @@ void launch_stl2(mivi_ctx *c, const void *params, int M, bool dinv_done, const v
     return;
   }
 #ifdef MIVI_DEV
-  static const bool stamps = getenv("MIVI_STL_STAMPS") != nullptr;
+  const bool stamps = switches().stl_stamps;
   if (stamps) s.stamps = (unsigned *)((char *)c->stl_X.p + c->stl_X.bytes - 4096);
 #endif
   launch_solve(c, s);

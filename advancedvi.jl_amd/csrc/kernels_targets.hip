@@ -387,91 +387,9 @@ typedef float lr_f32x4 __attribute__((ext_vector_type(4)));
 // Staging makes the sharing explicit: every operand byte is fetched once per workgroup with 16-byte coalesced loads
 // (3 per thread per stage instead of 32 dword loads per wave), a two-slot LDS ring feeds the MFMAs through ds_read,
 // global loads run two stages ahead in registers, one barrier per stage.  X^T R 1.52 -> 1.13 ms (74 % of the f32 MFMA
-// peak), logits 1.90 -> 1.33 ms (63 %) at n = 1e6, p = 511, M = 128.
-//   stage = 16 data rows: Rs[16][128] samples, Xs[16][256] features  (24 KB per slot)
+// peak), logits 1.90 -> 1.33 ms (63 %) at n = 1e6, p = 511, M = 128.  The logits kernel is what runs for d % 4 != 0; the f32-MFMA
+// X^T R kernel was reachable only through an environment switch and went with it (k_lr_xtr_f16x2 serves every shape).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512) void k_lr_xtr_mfma_lds(LrMfmaArgs a) {
-  __shared__ __attribute__((aligned(16))) float Rs[2][16 * 128];
-  __shared__ __attribute__((aligned(16))) float Xs[2][16 * 256];
-  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = w >> 2, wk = w & 3;
-  const int mbase = blockIdx.z * 128, kbase = blockIdx.y * 256;
-  const int m0 = mbase + wm * 64, k0 = kbase + wk * 64;
-  const long long rbeg = (long long)blockIdx.x * a.rows_per_split;
-  const long long rend = min(a.n, rbeg + a.rows_per_split);
-  const int ldr = a.ldr, ldx = a.ldx;
-  const int nst = (int)((rend - rbeg + 15) / 16);
-  // cooperative loads: R one float4 per thread (row t>>5, 4 samples), X two (rows t>>6 and 8 + t>>6, 4 features)
-  const int rrow = tid >> 5, rcol = min(mbase + 4 * (tid & 31), ldr - 4);
-  const int xrow = tid >> 6, xcol = min(kbase + 4 * (tid & 63), ldx - 4);
-  struct G { lr_f32x4 r, x0, x1; };
-  auto gload = [&](int st, G &g) {
-    st = min(st, nst - 1);
-    const long long rb = rbeg + 16LL * st;
-    const long long r_r = rb + rrow, r_x0 = rb + xrow, r_x1 = rb + 8 + xrow;
-    const bool okr = r_r < rend;
-    g.r = *(const lr_f32x4 *)(a.R + (size_t)(okr ? r_r : rend - 1) * ldr + rcol);
-    g.x0 = *(const lr_f32x4 *)(a.Xrm + (size_t)min(r_x0, rend - 1) * ldx + xcol);
-    g.x1 = *(const lr_f32x4 *)(a.Xrm + (size_t)min(r_x1, rend - 1) * ldx + xcol);
-    if (!okr) g.r = lr_f32x4{0.f, 0.f, 0.f, 0.f};   // rows past the split contribute nothing (X stays finite)
-  };
-  auto lstore = [&](int slot, const G &g) {
-    *(lr_f32x4 *)&Rs[slot][rrow * 128 + 4 * (tid & 31)] = g.r;
-    *(lr_f32x4 *)&Xs[slot][xrow * 256 + 4 * (tid & 63)] = g.x0;
-    *(lr_f32x4 *)&Xs[slot][(8 + xrow) * 256 + 4 * (tid & 63)] = g.x1;
-  };
-  lr_f32x16 c00, c01, c10, c11;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { c00[r] = 0.f; c01[r] = 0.f; c10[r] = 0.f; c11[r] = 0.f; }
-  const int ao = h * 128 + wm * 64 + l31, bo = h * 256 + wk * 64 + l31;
-  auto compute = [&](int slot) {
-    const float *rs = &Rs[slot][ao], *xs = &Xs[slot][bo];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const float a0 = rs[2 * u * 128], a1 = rs[2 * u * 128 + 32];
-      const float b0 = xs[2 * u * 256], b1 = xs[2 * u * 256 + 32];
-      c00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, c00, 0, 0, 0);
-      c01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, c01, 0, 0, 0);
-      c10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, c10, 0, 0, 0);
-      c11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, c11, 0, 0, 0);
-    }
-  };
-  if (nst > 0) {
-    G ga, gb;
-    gload(0, ga);
-    lstore(0, ga);
-    gload(1, ga);
-    gload(2, gb);
-    lds_barrier();   // LDS-only: __syncthreads() would also drain the prefetch loads (vmcnt)
-    int st = 0;
-    while (true) {
-      lstore((st + 1) & 1, ga);      // stage st+1 (loaded two iterations ago)
-      gload(st + 3, ga);
-      compute(st & 1);
-      lds_barrier();   // LDS-only: __syncthreads() would also drain the prefetch loads (vmcnt)
-      if (++st >= nst) break;
-      lstore((st + 1) & 1, gb);
-      gload(st + 3, gb);
-      compute(st & 1);
-      lds_barrier();   // LDS-only: __syncthreads() would also drain the prefetch loads (vmcnt)
-      if (++st >= nst) break;
-    }
-  }
-  auto epi = [&](const lr_f32x16 &c, int mb, int kb) {
-    const int k = k0 + kb * 32 + l31;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int m = m0 + mb * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-      if (k < a.p && m < a.M) a.g_part[((size_t)blockIdx.x * a.M + m) * a.p + k] = c[q];
-    }
-  };
-  epi(c00, 0, 0);
-  epi(c01, 0, 1);
-  epi(c10, 1, 0);
-  epi(c11, 1, 1);
-}
-
 // logits through LDS: 256 rows x 128 samples per workgroup (8 waves as 4 x 2, each 64 x 64), stage = 16 k:
 //   Xs[256][20]  (row-major slab of Xrm, row stride 20 words: 16-byte aligned and conflict-free for the b128 operand reads)
 //   Zs[16][128]  (ZT rows)
@@ -1225,7 +1143,7 @@ struct LrGeom {
   size_t need_R, need_g, need_ll;
 };
 static LrGeom lr_geom(const mivi_ctx *c, int M) {
-  static const bool force_generic = getenv("MIVI_LOGREG_GENERIC") != nullptr;
+  const Switches &sw = switches();
   LrGeom g;
   g.planes = false;
   g.xplanes = false;
@@ -1235,13 +1153,10 @@ static LrGeom lr_geom(const mivi_ctx *c, int M) {
   const int p = c->cfg.d - 1;
   // small problems take the VALU route: the matrix-core kernels carry fixed 256-row x 128-sample tiles and three more
   // launches (measured crossover around n p M = 2e7: n = 1000, p = 32: 35 vs 47 us at 16 samples, 50 vs 57 us at 128)
-  static const bool force_mfma = getenv("MIVI_LOGREG_MFMA") != nullptr;
-  g.mfma = c->cfg.dtype == MIVI_F32 && c->lr_Xrm_act && !force_generic && c->lr_route != 2 &&
-           (force_mfma || c->lr_route == 1 || (double)n * (double)p * (double)M >= 1.6e7);
+  g.mfma = c->cfg.dtype == MIVI_F32 && c->lr_Xrm_act && c->lr_route != 2 && (c->lr_route == 1 || (double)n * (double)p * (double)M >= 1.6e7);
   if (g.mfma) {
     g.ldr = (M + 63) / 64 * 64;
-    static const bool no_planes = getenv("MIVI_LR_NO_PLANES") != nullptr;   // A/B: the logits kernel that splits X in the tile (k_lr_logits_f16x2)
-    g.planes = M % 128 == 0 && c->lr_XA.p && c->lr_Xrm_act == c->lr_Xrm.p && !no_planes && !getenv("MIVI_LR_F32_LOGITS");
+    g.planes = M % 128 == 0 && c->lr_XA.p && c->lr_Xrm_act == c->lr_Xrm.p && !sw.lr_no_planes && !sw.lr_f32_logits;
     g.nrb = g.planes ? (int)((n + 127) / 128) : (int)((n + 255) / 256);
     // row splits of X^T R: 128 x 2 feature groups = one workgroup per CU at C3 (n = 1e6, p = 511); small data sets still
     // get a split per 128 rows (one workgroup walking n = 20 000 rows alone is a 270 us chain of 16-row stages)
@@ -1253,9 +1168,8 @@ static LrGeom lr_geom(const mivi_ctx *c, int M) {
     g.S = (int)((n + rps - 1) / rps);
     g.rps = rps;
     g.need_R = ((size_t)((n + 15) / 16 * 16) * g.ldr * sizeof(float) + 255) / 256 * 256;   // + zero rows to a whole stage
-    static const bool no_xplanes = getenv("MIVI_LR_NO_XPLANES") != nullptr;   // A/B: X^T R with the splits made in the tile (k_lr_xtr_f16x2)
     g.nrg = (n + 127) / 128 * 8;
-    g.xplanes = g.planes && c->lr_XB.p && !no_xplanes && !getenv("MIVI_LR_F32_XTR") && g.nrg >= 16;
+    g.xplanes = g.planes && c->lr_XB.p && !sw.lr_no_xplanes && g.nrg >= 16;
     if (g.xplanes) {
       // row splits: three workgroups per CU over the feature groups (at C3: 4 feature groups x 192 splits = 768 workgroups), at least 8 row groups each
       int S2 = (int)(768 / ((p + 127) / 128) / (M / 128));
@@ -1320,7 +1234,6 @@ static bool logreg_mfma(mivi_ctx *c, int M, int want_grad) {
   a.R = (float *)c->lr_scratch.p;
   a.g_part = (float *)((char *)c->lr_scratch.p + need_R);
   a.ll_part = (double *)c->lr_part.p;
-  static const bool no_split = getenv("MIVI_LR_F32_LOGITS") != nullptr;   // A/B: f32 MFMA logits
   a.Zcm = (const float *)c->Z.p;
   a.xmax = (const unsigned *)c->lr_xmax.p;
   const bool part = M % 128 != 0 && M % 128 <= 96;   // whole 32-sample tiles of the last 128-sample group are empty
@@ -1335,7 +1248,7 @@ static bool logreg_mfma(mivi_ctx *c, int M, int want_grad) {
     a.gps = geo.gps;
     hipLaunchKernelGGL(k_lr_zplanes, dim3((nfz + 3) / 4), dim3(256), 0, c->stream, M, a.d, a.ldx, a.Zcm, a.ZP);
     hipLaunchKernelGGL(k_lr_logits_planes, dim3(nrb, M / 128), dim3(512), 0, c->stream, a);
-  } else if (a.d % 4 == 0 && a.d >= 4 && !no_split) {
+  } else if (a.d % 4 == 0 && a.d >= 4 && !switches().lr_f32_logits) {
     if (part) hipLaunchKernelGGL(k_lr_logits_f16x2_part, dim3(nrb, (M + 127) / 128), dim3(512), 0, c->stream, a);
     else hipLaunchKernelGGL(k_lr_logits_f16x2, dim3(nrb, (M + 127) / 128), dim3(512), 0, c->stream, a);
   } else {
@@ -1352,12 +1265,8 @@ static bool logreg_mfma(mivi_ctx *c, int M, int want_grad) {
     hipLaunchKernelGGL(k_lr_xtr_planes, dim3((a.p + 127) / 128, S, M / 128), dim3(512), 0, c->stream, a);
   } else if (want_grad) {
     const dim3 gx(S, (a.p + 255) / 256, (M + 127) / 128);
-    static const bool xtr_f32 = getenv("MIVI_LR_F32_XTR") != nullptr;   // A/B: f32 MFMA X^T R
-    if (!xtr_f32) {
-      if (part) hipLaunchKernelGGL((k_lr_xtr_f16x2<4, true>), gx, dim3(512), 0, c->stream, a);
-      else hipLaunchKernelGGL((k_lr_xtr_f16x2<4, false>), gx, dim3(512), 0, c->stream, a);
-    }
-    else hipLaunchKernelGGL(k_lr_xtr_mfma_lds, gx, dim3(512), 0, c->stream, a);
+    if (part) hipLaunchKernelGGL((k_lr_xtr_f16x2<4, true>), gx, dim3(512), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_lr_xtr_f16x2<4, false>), gx, dim3(512), 0, c->stream, a);
   }
   if (want_grad && S > 1) {
     const size_t len = (size_t)a.p * M;

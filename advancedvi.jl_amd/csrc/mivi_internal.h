@@ -10,6 +10,7 @@
 
 #include "../../include/mivi.h"
 #include "philox.h"
+#include "switches.h"
 
 namespace mivi {
 
@@ -622,7 +623,6 @@ void launch_fr_sample(mivi_ctx *c, const void *params, int M, int fused_target, 
 void launch_fr_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, const EpsJob *next = nullptr,
                    const ValueJob *self = nullptr, const FusedUpdate *upd = nullptr);
 int fr_ld_blocks(const mivi_ctx *c);
-bool f64_valu();   // MIVI_F64_VALU=1: keep the f64 full-rank tiles on the vector ALU
 // Build + upload the first-generation MFMA kernels' work tables for M samples per launch, once per M (nothing to do for f64, nor for the
 // other families without the dense target).  A driver calls it before its first launch_fr_* / fr_*_blocks for that M; false: an allocation
 // or upload failed.  prepare_tables: the same and the second-generation work lists where the shape takes them (lds_prepare), ahead of a capture.
@@ -665,7 +665,6 @@ bool launch_lanes_vjp(mivi_ctx *c, const LaneRecorder &rec, int lanes);
 void launch_lanes_eps(mivi_ctx *c, const LaneRecorder &rec, int lanes);              // kernels_fullrank.hip: the first draws of the lanes that made one, as one launch
 bool launch_lanes_stl(mivi_ctx *c, const LaneRecorder &rec, int lanes, bool with_F);   // kernels_stl.hip: one solve launch with all lanes' jobs + one combining product
 void launch_lanes_value(mivi_ctx *c, const void *params, LaneRecorder &rec);         // kernels_update.hip: the recorded closing value kernels as one launch
-bool lds_bf16x3();   // products on the bf16 matrix cores (three-way exact operand split); MIVI_FR_F32MFMA=1 turns it off
 void launch_lds_vjp(mivi_ctx *c, const void *params, int M, const OutArgs &out, const ValueJob *self, const FusedUpdate *upd);
 bool lds_stein_ok(const mivi_ctx *c, int M);
 bool launch_lds_stein_outer(mivi_ctx *c, int M, void *A, double *gsum, int first, double scale, double n, void *grad, void *logpi,

@@ -185,6 +185,39 @@ def test_graph_capture_has_one_owner():
     assert not re.search(r"\b(p0|p1|aux0|aux1)\b", cache), cache
 
 
+def test_environment_switches_have_one_table():
+    """The environment is read in ONE translation unit (csrc/api_core.hip: kSwitchTable behind switches(), csrc/switches.h).  The table, the
+    switch paragraph of DESIGN.md and the cases of tests/test_gpu_ab_switches.py name the same switches, and the switches retired with the
+    routes only they reached are named nowhere in the sources, tests and tools."""
+    csrc = os.path.join(ROOT, "advancedvi.jl_amd", "csrc")
+    src = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    assert [f for f, txt in src.items() if "getenv(" in txt] == ["api_core.hip"]
+    table = re.search(r"const SwitchRow kSwitchTable\[\] = \{\n(.*?)\n\};", src["api_core.hip"], flags=re.S).group(1)
+    release, dev = table.split("#ifdef MIVI_DEV")
+    row = r'\{"(MIVI_\w+)", SW_\w+, SW\(\w+\), [^"]*"[^"]+"\}'
+    release, dev = re.findall(row, release), re.findall(row, dev)
+    names = set(release) | set(dev)
+    assert len(release) + len(dev) == len(names) == table.count('{"'), table   # (every row parsed, no name twice)
+    assert set(dev) == {"MIVI_FB_DBG", "MIVI_FB_KNOCK", "MIVI_FB_RING", "MIVI_KNOCK", "MIVI_STL_STAMPS"}
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    para = re.search(r"\*\*Environment switches\.\*\*.*?(\n\n|\Z)", design, flags=re.S).group(0)
+    kept, cut = para.split("Cut in round 5")
+    assert set(re.findall(r"`(MIVI_\w+)`", kept)) - {"MIVI_DEV"} == names, sorted(set(re.findall(r"`(MIVI_\w+)`", kept)) ^ names)
+    retired = ["MIVI_" + n for n in ("FR_F32MFMA", "F64_VALU", "LR_F32_XTR", "LOGREG_GENERIC", "LOGREG_MFMA")]   # (in pieces: this file is searched too)
+    assert set(retired) <= set(re.findall(r"`(MIVI_\w+)`", cut)), cut
+    import tests.test_gpu_ab_switches as ab
+    tested = {kv.split("=")[0] for c in ab.CASES if c for kv in c[0].split(",")}
+    untested = set(release) - {"MIVI_FORCE_EXCHANGE_LOST", "MIVI_RCCL_LIB"} - tested
+    assert not untested, sorted(untested)
+    tools = os.path.join(ROOT, "tools")
+    searched = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
+    searched += [os.path.join(ROOT, "tests", f) for f in sorted(os.listdir(os.path.join(ROOT, "tests"))) if f.endswith(".py")]
+    searched += [os.path.join(tools, f) for f in sorted(os.listdir(tools)) if f.endswith((".py", ".sh"))]
+    for path in searched:
+        txt = open(path).read()
+        assert not [n for n in retired if n in txt], path
+
+
 def test_stream_and_event_handles_have_one_owner():
     """Streams and events are created and destroyed in ONE translation unit (csrc/api_core.hip: make_stream, make_event, handle_destroy),
     a hipGraphExec is destroyed in the graph unit only; every other unit holds them in a Stream / Event / GraphExec (csrc/mivi_internal.h).
@@ -210,8 +243,8 @@ def test_precision_dispatch_is_written_once():
     src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip"))
     both = set(re.findall(r"\b(k_\w+)<float", src)) & set(re.findall(r"\b(k_\w+)<double", src))
     assert both == {
-        # launch_fr_stl (kernels_fullrank.hip): the 16-column solve is taken by f64 only off the MIVI_F64_VALU cross-check and within its
-        # own LDS bound (d <= 1024; f32: d <= 2304), so each precision tests for its route and prepares its transposed scale there
+        # launch_fr_stl (kernels_fullrank.hip): the 16-column solve is taken by f64 only within its own LDS bound (d <= 1024; f32:
+        # d <= 2304), so each precision tests for its route and prepares its transposed scale there
         "k_stl_prep",
         "k_stl_solve_la16",
     }, sorted(both)

@@ -12,11 +12,12 @@ if len(sys.argv) > 1:
     params, _ = avi.destructure(q)
     ctx = avi.MiviContext(np.float32, avi.FULLRANK, d, M, 0, 1)
     ctx.set_problem(avi.LogRegProblem(X, y))
+    ctx.set_logreg_route(int(sys.argv[2]))   # 0: by size, 2: the vector-ALU kernels
     v, g = ctx.estimate_gradient(params, 3)
     np.save(sys.argv[1], np.concatenate([[float(v.item())], g.cpu().numpy().astype(np.float64)]))
 else:
-    for name, env in (("bf16x3", {}), ("f32", {"MIVI_LR_F32_LOGITS": "1"}), ("generic", {"MIVI_LOGREG_GENERIC": "1"})):
-        subprocess.run([sys.executable, __file__, f"/tmp/acc_{name}.npy"], env={**os.environ, **env}, check=True, stderr=subprocess.DEVNULL)
+    for name, env, route in (("bf16x3", {}, 0), ("f32", {"MIVI_LR_F32_LOGITS": "1"}, 0), ("generic", {}, 2)):
+        subprocess.run([sys.executable, __file__, f"/tmp/acc_{name}.npy", str(route)], env={**os.environ, **env}, check=True, stderr=subprocess.DEVNULL)
     a, b, c = (np.load(f"/tmp/acc_{n}.npy") for n in ("bf16x3", "f32", "generic"))
     for nm, x in (("bf16x3 vs f32-mfma", (a, b)), ("bf16x3 vs generic", (a, c)), ("f32-mfma vs generic", (b, c))):
         u, w = x

@@ -11,6 +11,7 @@ for n, p, M in [(1000, 32, 16), (1000, 32, 128), (20000, 128, 16), (20000, 128, 
     params, _ = avi.destructure(q)
     ctx = avi.MiviContext(np.float32, 0, d, M, 0, 1)
     ctx.set_problem(avi.LogRegProblem(X, y))
+    ctx.set_logreg_route(int(sys.argv[2]))   # 0: by size, 2: the vector-ALU kernels
     pd = ctx.to_device(params); v, g = ctx.empty(1), ctx.empty(ctx.params_len)
     for i in range(5): ctx.estimate_gradient(pd, i, v, g)
     torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -19,5 +20,5 @@ for n, p, M in [(1000, 32, 16), (1000, 32, 128), (20000, 128, 16), (20000, 128, 
     print(f"n={n} p={p} M={M}: {(time.perf_counter() - t0) / 200 * 1e6:8.1f} us/estimate", flush=True)
     ctx.close()
 PY
-echo "== default (MFMA route)"; python /tmp/lr2.py $REPO 2>&1 | grep us/est
-echo "== MIVI_LOGREG_GENERIC=1"; MIVI_LOGREG_GENERIC=1 python /tmp/lr2.py $REPO 2>&1 | grep us/est
+echo "== default (MFMA route)"; python /tmp/lr2.py $REPO 0 2>&1 | grep us/est
+echo "== set_logreg_route(2)"; python /tmp/lr2.py $REPO 2 2>&1 | grep us/est
