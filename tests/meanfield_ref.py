@@ -81,6 +81,12 @@ def family_and_target(kind, d, rng):
 def _target(tgt, Z, dtype):
     """(log pi(z_m) (M), grad log pi(z_m) (d x M)) for the columns of Z, every step in `dtype`"""
     d = Z.shape[0]
+    if hasattr(tgt, "blocks") and hasattr(tgt, "inner"):   # tests/bijector_ref.py BijectorTarget: its steps at the kernels' documented precisions
+        from tests import bijector_ref as BR
+        acc = np.float64 if dtype is np.float32 else None
+        X, ladj = BR.forward(tgt.blocks, Z, dtype, acc)
+        ell, G = _target(tgt.inner, X, dtype)
+        return (ell + ladj).astype(dtype), BR.backward(tgt.blocks, Z, G, dtype, acc)
     if isinstance(tgt, O.StackedBijectorTarget):   # x = exp(eta) on the masked rows: logdensity + sum eta, gradient x g + 1
         mask = tgt.mask[:, None]
         with np.errstate(over="ignore"):
@@ -159,6 +165,11 @@ def envelope(params, d, tgt, eps, ent, dtype=np.float32, ref=None):
 
 def _magnitude_target(tgt, za, Z, d):
     """(ell_a (M), Wa (d x M)): the magnitudes of log pi and its gradient (module docstring)"""
+    if hasattr(tgt, "blocks") and hasattr(tgt, "inner"):   # tests/bijector_ref.py BijectorTarget and its magnitudes
+        from tests import bijector_ref as BR
+        Sx, Sl = BR.magnitude_forward(tgt.blocks, Z)
+        ell_a, Ga = _magnitude_target(tgt.inner, Sx, None, d)
+        return ell_a + Sl, BR.magnitude_backward(tgt.blocks, Z, Ga)
     if isinstance(tgt, O.StackedBijectorTarget):
         mask = tgt.mask[:, None]
         with np.errstate(over="ignore"):

@@ -1,5 +1,6 @@
 """CPU checks of tests/bijector_ref.py, the restatement the GPU tests of the extended Stacked bijector (tests/test_gpu_bijector_kinds.py)
-are held against, and of the host mirror's StackedBijector.  No GPU."""
+are held against, of the host mirror's StackedBijector, and of the per-entry criterion of tests/test_gpu_bijector_yardstick.py (second
+half: the reference alone stays inside half the factor on every GPU case; injected faults under the old and the new criterion).  No GPU."""
 import math
 
 import numpy as np
@@ -159,3 +160,299 @@ def test_stacked_bijector_argument_checks_and_blocks_stay_triples():
         avi.TransformedDistribution(q, avi.StackedBijector([(0, 5, "ordered")]))
     with pytest.raises(TypeError):
         avi.TransformedDistribution(q, [(0, 4, "ordered")])
+
+
+# ==== the per-entry criterion of tests/test_gpu_bijector_yardstick.py: the reference alone stays inside it, and it has teeth =================
+F32 = np.float32
+HALF = 4.0     # half of F32_FACTOR: what the reference alone may use up (tests/test_logpdf_ref_host.py: "under 4.0 on every case")
+FACTOR = 8.0   # F32_FACTOR of tests/measure_space_cases.py
+OLD_INDICES = (0, 1, 2, 7, 1000003)   # tests/test_gpu_bijector_kinds.py INDICES
+_CASE_GROUPS = sorted({(c[0], c[2]) for c in BR.estimate_cases()})
+
+
+def _draws(d, M, idx=3):
+    return O.philox_normal(11, idx, d, 0, M).astype(F32)
+
+
+@pytest.mark.parametrize("cls,family", _CASE_GROUPS, ids=[f"{c}-{'meanfield' if f == O.MEANFIELD else 'fullrank'}" for c, f in _CASE_GROUPS])
+def test_reference_alone_stays_inside_half_the_factor_on_every_gpu_case(cls, family):
+    """Every (class, layout, family, target, entropy kind, M) of bijector_ref.estimate_cases(): the float32 yardstick under the column orders
+    9 .. 12 against max(envelope of the orders 1 .. 8, u S).  Measured: whole 1.58, block 2.43, row 2.74, entry of dm 2.93, value 1.53
+    (worst of all cases) -- dC is held per ROW and per 64-row block, not per entry (4.43 was measured per entry with a rougher S), and no
+    quantity had to be widened further."""
+    worst = dict(whole=0.0, block=0.0, row=0.0, entry=0.0, value=0.0)
+    for c_cls, name, fam, tgt, ent, M in BR.estimate_cases():
+        if (c_cls, fam) != (cls, family):
+            continue
+        c = BR.make_case(cls, name, fam, tgt, F32)
+        d, args = c["d"], (c["params"], c["d"], fam, c["inner"], c["blocks"])
+        eps = _draws(d, M)
+        ref = BR.gradient(*args, eps, ent, np.float64, order=np.arange(M))
+        assert np.all(np.isfinite(ref["grad"])) and np.isfinite(ref["value"])
+        env, mag = BR.envelope(*args, eps, ent, F32, ref), BR.magnitude(*args, eps, ent)
+        for k in range(9, 13):
+            y = BR.gradient(*args, eps, ent, F32, order=np.random.default_rng(1000 + k).permutation(M))
+            r = BR.ratios(y["grad"], env["grad"], ref["grad"], mag["grad"], d, fam, BR.U32)
+            r["value"] = BR.value_ratio(y["value"], env["value"], ref["value"], mag["value"], BR.U32)
+            assert max(r.values()) <= HALF, (cls, name, fam, tgt, ent, M, k, r)
+            worst = {key: max(worst[key], r[key]) for key in worst}
+    print(f"[bijector reference alone] {cls} fam={family}: " + ", ".join(f"{k} {v:.2f}" for k, v in worst.items()))
+
+
+def _wide_zero_rows(eta, rows):
+    """eta = 0 exactly and +- one float32 spacing on the first columns of a two-sided row (not reachable from a draw)"""
+    eta = eta.copy()
+    eta[rows[0], :3] = [0.0, np.spacing(F32(0.0)), -np.spacing(F32(0.0))]
+    if eta.shape[1] > 5:
+        eta[rows[0], 3:5] = [np.spacing(F32(1.0)), -np.spacing(F32(1.0))]
+    return eta
+
+
+@pytest.mark.parametrize("cls", BR.CLASSES)
+def test_forward_backward_and_logpdf_restatements_stay_inside_half_the_factor(cls):
+    """Nothing to permute here: the float32 restatement WITH THE KERNELS' DOCUMENTED PRECISIONS (bijector_ref.forward / backward with acc =
+    float64: e^eta in float32 on the exp-like rows, the sigmoid, the scan and the sum of ladj in float64 from the stored eta, one rounding)
+    against u S on every layout, at most 4.0.  Measured worst: x 2.89, ladj 0.84, W 2.88, logpdf 0.76.
+    The PLAIN float32 restatement does not stay inside, and that is the restatement's arithmetic, not the magnitudes': a float32 running
+    sum of 513 increments is 20 u S from the float64 scan (layout 513), a float32 sum of 512 eta's 9 u S from ladj (wide 513), and 1 - 2 p
+    formed in float32 next to eta = 0 cancels to 400 u S (S counts |1 - 2 p| as the kernels' one rounding of a float64 result).  The test
+    prints the plain restatement's worst ratios per class next to the asserted ones."""
+    worst, plain = dict(x=0.0, ladj=0.0, W=0.0, logpdf=0.0), dict(x=0.0, ladj=0.0, W=0.0)
+    for name, (d, _) in BR.LAYOUTS.items():
+        c = BR.make_case(cls, name, O.MEANFIELD, "diag", F32)
+        blocks, M = c["blocks"], 9
+        eta = BR.samples(c["params"], d, O.MEANFIELD, _draws(d, M), F32)
+        both = [i for i, k in enumerate(BR.row_codes(d, blocks)) if k == "both"]
+        if cls == "wide" and both:
+            eta = _wide_zero_rows(eta, both)
+        x, ladj = BR.forward(blocks, eta, F32, np.float64)
+        x64, ladj64 = BR.forward(blocks, eta)
+        Sx, Sl = BR.magnitude_forward(blocks, eta)
+        _, G = BR.graded_probe(d, blocks, M, np.random.default_rng(d))
+        W, W64, Sw = BR.backward(blocks, eta, G, F32, np.float64), BR.backward(blocks, eta, G), BR.magnitude_backward(blocks, eta, G)
+        assert np.all(np.isfinite(x)) and np.all(np.isfinite(W))
+        r = dict(x=BR.entry_ratio(x, x64, Sx, BR.U32), ladj=BR.entry_ratio(ladj, ladj64, Sl, BR.U32), W=BR.entry_ratio(W, W64, Sw, BR.U32))
+        xp, lp = BR.forward(blocks, eta, F32)
+        for k, v in (("x", BR.entry_ratio(xp, x64, Sx, BR.U32)), ("ladj", BR.entry_ratio(lp, ladj64, Sl, BR.U32)),
+                     ("W", BR.entry_ratio(BR.backward(blocks, eta, G, F32), W64, Sw, BR.U32))):
+            plain[k] = max(plain[k], v)
+        if cls != "wide":   # (e^-30 next to e^30: the float32 points of `wide` tie, the inverse has nothing to hold there)
+            for fam in (O.MEANFIELD, O.FULLRANK):
+                cf = BR.make_case(cls, name, fam, "diag", F32)
+                X = BR.forward(blocks, BR.samples(cf["params"], d, fam, _draws(d, M), F32), F32, np.float64)[0]
+                ref = BR.logpdf_constrained(cf["params"], d, fam, cf["blocks"], X)
+                yard = BR.logpdf_yard(cf["params"], d, fam, cf["blocks"], X, F32).astype(F32)
+                ins = np.isfinite(ref)
+                assert np.array_equal(ins, np.isfinite(yard))
+                Sp = BR.magnitude_logpdf_constrained(cf["params"], d, fam, cf["blocks"], X)
+                r["logpdf"] = max(r.get("logpdf", 0.0), BR.entry_ratio(yard[ins], ref[ins], Sp[ins], BR.U32))
+        assert max(r.values()) <= HALF, (cls, name, r)
+        worst = {k: max(worst[k], r.get(k, 0.0)) for k in worst}
+    print(f"[bijector reference alone] {cls} forward / backward / logpdf: " + ", ".join(f"{k} {v:.2f}" for k, v in worst.items()))
+    print(f"[bijector reference alone] {cls} the PLAIN float32 restatement (not asserted): " + ", ".join(f"{k} {v:.2f}" for k, v in plain.items()))
+
+
+@pytest.mark.parametrize("family", BR.FAMILIES, ids=["meanfield", "fullrank"])
+def test_score_reference_alone_stays_inside_half_the_factor(family):
+    """the ScoreGradELBO restatement behind the bijector (bijector_ref.score_gradient) under the column orders 9 .. 12 against
+    max(envelope of the orders 1 .. 8, u S), S = bijector_ref.score_magnitude, on the case the GPU file runs.  Measured: at most 1.58."""
+    c = BR.make_case("default", "257", family, "diag", F32)
+    d, M = c["d"], BR.M_EST
+    args = (c["params"], d, family, c["inner"], c["blocks"], _draws(d, M))
+    ref = BR.score_gradient(*args, np.float64)
+    env, mag = BR.score_envelope(*args, F32, ref), BR.score_magnitude(*args)
+    lit = SR_closed_form(c, family, args[-1])
+    assert np.linalg.norm(lit["grad"] - ref["grad"]) <= 1e-10 * np.linalg.norm(ref["grad"]) and abs(lit["value"] - ref["value"]) <= 1e-10 * abs(ref["value"])
+    worst = 0.0
+    for k in range(9, 13):
+        y = BR.score_gradient(*args, F32, np.random.default_rng(1000 + k).permutation(M))
+        r = BR.ratios(y["grad"], env["grad"], ref["grad"], mag["grad"], d, family, BR.U32)
+        r.update({q: BR.value_ratio(y[q], env[q], ref[q], mag[q], BR.U32) for q in ("value", "elbo")})
+        assert max(r.values()) <= HALF, (family, k, r)
+        worst = max(worst, max(r.values()))
+    print(f"[bijector reference alone] score fam={family}: worst {worst:.2f}")
+
+
+def SR_closed_form(c, family, eps):
+    from tests import scoregrad_ref as R
+    return R.closed_form(c["params"].astype(np.float64), c["d"], family, BR.BijectorTarget(c["inner"], c["blocks"]), eps.astype(np.float64))
+
+
+def test_documented_scan_order_is_not_monotone_in_float64_on_the_class_wide():
+    """What the f64 order assertion of tests/test_gpu_bijector_yardstick.py rests on, from the restatement alone.  seg_scan256 is a
+    Hillis-Steele scan: every prefix is a differently associated tree of at most log2(256) = 8 additions, each rounding by half a
+    spacing.  In float64 numpy (bijector_ref.documented_scan) that order is monotone on the classes default and far and NOT on wide, where
+    e^-30 is added to 1e13: x_{k+1} < x_k on layouts 257, 512 and 300 (measured: 19, 1261 and 17 steps, the worst -1, -3 and -1
+    spacings), never by more than the 8 spacings the depth of the tree allows.  A sequential sum is monotone; so is the float32 context's
+    result, which rounds the float64 scan to a spacing 2^29 times coarser."""
+    worst = {}
+    for cls in BR.CLASSES:
+        for name in ("257", "513", "512", "300"):
+            d, _ = BR.LAYOUTS[name]
+            c = BR.make_case(cls, name, O.MEANFIELD, "diag", np.float64)
+            eta = BR.samples(c["params"], d, O.MEANFIELD, O.philox_normal(11, 3, d, 0, 33, f64=True))
+            steps = [np.diff(x, axis=0) / np.spacing(np.abs(x[1:])) for _, _, x in BR.documented_scan(d, c["blocks"], eta)]
+            worst[cls, name] = (min(float(s.min()) for s in steps), sum(int((s < 0).sum()) for s in steps))
+            seq = BR.forward(c["blocks"], eta)[0]
+            assert all(np.all(np.diff(seq[lo:hi], axis=0) >= 0) for lo, hi, _ in BR.documented_scan(d, c["blocks"], eta))   # (the sequential sum)
+    print("[bijector scan order] worst step in spacings, decreasing steps:", worst)
+    assert all(w >= 0 for (cls, _), (w, _) in worst.items() if cls != "wide")
+    assert all(worst["wide", n][1] > 0 for n in ("257", "512", "300")) and all(w >= -8.0 for w, _ in worst.values())
+
+
+def test_layouts_reach_the_mechanisms_they_are_listed_for():
+    BR.assert_layouts_reach_their_mechanisms()
+
+
+def test_order_argument_and_longdouble_agree_with_the_float64_restatement():
+    c = BR.make_case("default", "300", O.FULLRANK, "dense")
+    d, M = c["d"], 10
+    args = (c["params"], d, O.FULLRANK, c["inner"], c["blocks"], _draws(d, M).astype(np.float64), 3)
+    a, b = BR.estimate_gradient(*args), BR.estimate_gradient(*args, order=np.random.default_rng(1).permutation(M))
+    w = BR.estimate_gradient(*args, np.longdouble)
+    gn = np.linalg.norm(a["grad"])
+    assert np.linalg.norm(a["grad"] - b["grad"]) <= 1e-12 * gn and abs(a["value"] - float(b["value"])) <= 1e-12 * abs(a["value"])
+    assert np.linalg.norm(a["grad"] - w["grad"].astype(np.float64)) <= 1e-12 * gn and abs(a["value"] - float(w["value"])) <= 1e-12 * abs(a["value"])
+
+
+# ---- teeth ---------------------------------------------------------------------------------------------------------------------------------
+def _old_admits(c, ent, M, mutate):
+    """hold() of tests/test_gpu_bijector_kinds.py restated: the l2 distance of the whole gradient (and the distance of the value) from the
+    float64 restatement, maximised over OLD_INDICES, within 8 x the same of ONE float32 evaluation"""
+    args = (c["d"], c["family"], c["inner"], c["blocks"])
+    lib, cpu = [], []
+    for idx in OLD_INDICES:
+        eps = _draws(c["d"], M, idx)
+        ref = BR.estimate_gradient(c["params"].astype(np.float64), *args, eps.astype(np.float64), ent)
+        dist = lambda r: (abs(float(r["value"]) - ref["value"]), float(np.linalg.norm(np.asarray(r["grad"], dtype=np.float64) - ref["grad"])))   # noqa: E731
+        lib.append(dist(BR.gradient(c["params"], *args, eps, ent, F32, mutate=mutate)))
+        cpu.append(dist(BR.estimate_gradient(c["params"], *args, eps, ent, F32)))
+    lib_m, cpu_m = np.max(lib, axis=0), np.max(cpu, axis=0)
+    return bool(np.all(lib_m <= FACTOR * cpu_m))
+
+
+def _new_worst(c, ent, M, mutate):
+    args = (c["params"], c["d"], c["family"], c["inner"], c["blocks"])
+    eps = _draws(c["d"], M, OLD_INDICES[0])
+    ref = BR.gradient(*args, eps, ent, np.float64, order=np.arange(M))
+    env, mag = BR.envelope(*args, eps, ent, F32, ref), BR.magnitude(*args, eps, ent)
+    y = BR.gradient(*args, eps, ent, F32, mutate=mutate)
+    r = BR.ratios(y["grad"], env["grad"], ref["grad"], mag["grad"], c["d"], c["family"], BR.U32)
+    r["value"] = BR.value_ratio(y["value"], env["value"], ref["value"], mag["value"], BR.U32)
+    assert max(BR.ratios(BR.gradient(*args, eps, ent, F32)["grad"], env["grad"], ref["grad"], mag["grad"], c["d"], c["family"],
+                         BR.U32).values()) <= HALF   # (the unmutated yardstick passes)
+    return max(r.values())
+
+
+def _row_of(c, code, pick=0):
+    return [i for i, k in enumerate(BR.row_codes(c["d"], c["blocks"])) if k == code][pick]
+
+
+def _scaled_row(r):
+    def f(W, Z, G, x):
+        W[r] = W[r] * F32(1.001)
+        return W
+    return dict(backward=f)
+
+
+def _mutants():
+    """[(name, class, family, mutate)] on layout 257, M = 33, the diagonal target, entropy kind 0"""
+    out = []
+    dflt = {f: BR.make_case("default", "257", f, "diag", F32) for f in BR.FAMILIES}
+    far, wide = BR.make_case("far", "257", O.MEANFIELD, "diag", F32), BR.make_case("wide", "257", O.MEANFIELD, "diag", F32)
+    r_both = _row_of(dflt[O.MEANFIELD], "both", 1)
+
+    def untransformed(W, Z, G, x):
+        W[r_both, 5] = G[r_both, 5]
+        return W
+    out.append(("1 one (row, column) of W left untransformed on a two-sided row", dflt[O.MEANFIELD], dict(backward=untransformed)))
+    for fam in BR.FAMILIES:
+        for code, pick in (("lower", 0), ("lower", 2), ("upper", 0), ("both", 0), ("head", 1), ("ordered", 9), ("identity", 20)):
+            r = _row_of(dflt[fam], code, pick)
+            out.append((f"2 row {r} ({code}) of W off by 1e-3, family {fam}", dflt[fam], _scaled_row(r)))
+
+    def carry_dropped(x, ladj, Z):
+        x[256] = np.exp(Z[256])   # the scan restarts at the chunk boundary: the carry x_255 is lost
+        return x, ladj
+    out.append(("3 forward carry dropped at row 256, class far", far, dict(forward=carry_dropped)))
+
+    def leak(W, Z, G, x):   # the mirrored segment of [240, 250) does not stop at row 249: it takes in g_250
+        W[240] = W[240] + G[250]
+        W[241:250] = W[241:250] + np.exp(Z[241:250]) * G[250]
+        return W
+    out.append(("4 mirrored suffix sum takes in the first row of the neighbouring block", dflt[O.MEANFIELD], dict(backward=leak)))
+    loc = wide["params"][:257]
+    r_tail = [i for i, k in enumerate(BR.row_codes(257, wide["blocks"])) if k == "both" and loc[i] > 10.0][0]
+
+    def wrong_sign(W, Z, G, x):   # eta >= 0: 2 p - 1 is right, 1 - 2 p was taken
+        p = BR._sigmoid_parts(Z[r_tail].astype(np.float64))[0]
+        W[r_tail] = (W[r_tail].astype(np.float64) + np.where(Z[r_tail] >= 0, 2.0 * (1.0 - 2.0 * p), 0.0)).astype(F32)
+        return W
+    out.append((f"5 1 - 2 p with the wrong sign for eta >= 0 on row {r_tail} (eta ~ {loc[r_tail]:.0f}), class wide", wide, dict(backward=wrong_sign)))
+
+    def ladj_short(x, ladj, Z):
+        return x, (ladj - Z[256]).astype(F32)
+    out.append(("6 ladj without row d - 1", dflt[O.MEANFIELD], dict(forward=ladj_short)))
+    lows = [(lo, hi, lb) for lo, hi, kind, (lb, ub) in BR.normalise(far["blocks"]) if BR._case(kind, lb, ub) == "lower" and kind != "exp"]
+
+    def from_difference(W, Z, G, x):
+        for lo, hi, lb in lows:
+            W[lo:hi] = (x[lo:hi] - F32(lb)) * G[lo:hi] + F32(1)
+        return W
+    out.append(("7 e^eta taken from x - lb in float32, class far", far, dict(backward=from_difference)))
+    return out
+
+
+def test_every_fault_fails_the_per_entry_criterion_and_the_old_one_admits_several():
+    """Faults injected into the float32 restatement (layout 257, M = 33, diagonal target, entropy kind 0), scored under hold() of
+    tests/test_gpu_bijector_kinds.py (restated: _old_admits, both sides maximised over its five estimate indices) and under the per-entry
+    criterion.  The new criterion rejects every one (worst ratio in brackets).  The old one, as measured here at the DEFAULT scales:
+        1 one (row, column) of W untransformed, two-sided row             rejects   [1.8e5]
+        2 a whole row of W off by 1e-3, mean-field: lower 3, exp 10,
+          upper 5, ordered 247                                            rejects   [1.2e4, 2.4e3, 9.8e3, 1.5e4] (rows that carry the norm)
+          two-sided 7, head 14, identity 35                               ADMITS    [5.6e3, 9.0e3, 1.5e4]
+          full-rank: lower 3, exp 10, upper 5, two-sided 7, head 14,
+          identity 35                                                     ADMITS    [6.2e3, 5.1e3, 3.4e3, 6.3e3, 1.4e4, 5.3e3]
+          full-rank: ordered 247                                          rejects   [8.9e3]
+        3 forward carry dropped at row 256, far                           rejects   [2.0e6] (x_256 falls from x_b to e^eta: the target's gradient moves by x_b)
+        4 mirrored suffix sum takes in the neighbour's first row          rejects   [7.2e5]
+        5 1 - 2 p with the wrong sign at eta ~ 13, wide                   rejects   [3.4e7] (listed although the old criterion sees it too)
+        6 ladj without row d - 1                                          rejects   [57] (the value moves by mean eta_256)
+        7 e^eta from x - lb in float32, far                               ADMITS    [1.5e3] (the one float32 evaluation it is measured by is itself
+                                                                                    far from float64 on the rows with x ~ 1e5)
+        8 eta rounded to bf16 before log q (the test below)               see its printed line
+    So a relative error of 1e-3 in a whole row of W passes the old criterion on nine of the fourteen rows tried, and the differencing
+    backward pass passes it on the class `far`; the faults that move a dominant row do not.  The lines are printed with -s."""
+    admitted = {}
+    for name, c, mutate in _mutants():
+        old, new = _old_admits(c, 0, 33, mutate), _new_worst(c, 0, 33, mutate)
+        print(f"[bijector teeth] {name}: old criterion {'ADMITS' if old else 'rejects'}, new criterion worst ratio {new:.3g}")
+        assert new > FACTOR, (name, new)
+        admitted.setdefault(name[0], []).append(old)
+    assert sum(admitted["2"]) >= len(admitted["2"]) // 2 and all(admitted["7"]), admitted   # (the gap the new criterion closes is real)
+
+
+@pytest.mark.parametrize("family", BR.FAMILIES, ids=["meanfield", "fullrank"])
+def test_bf16_eta_fails_the_logpdf_criterion(family):
+    """fault 8: eta rounded to bf16 between the inverse and log q.  Old criterion (tests/test_gpu_bijector_kinds.py): the largest relative
+    error over the columns within 8 x that of the float32 round trip; new: per column within 8 x max(|yard - ref|, u S)."""
+    c = BR.make_case("default", "257", family, "diag", F32)
+    d, blocks, M = c["d"], c["blocks"], 33
+    from tests import scoregrad_ref as R
+    Z = BR.samples(c["params"], d, family, _draws(d, M), F32)
+    X = BR.forward(blocks, Z, F32, np.float64)[0]
+    ref = BR.logpdf_constrained(c["params"], d, family, blocks, X)
+    yard = BR.logpdf_yard(c["params"], d, family, blocks, X, F32)
+    eta, ladj, inside = BR.inverse(blocks, X.astype(np.float64))
+    assert inside.all()
+    bf = (eta.astype(F32).view(np.uint32) & np.uint32(0xFFFF0000)).view(F32).astype(np.float64)
+    bad = (np.asarray(R.logpdf_cols(c["params"].astype(np.float64), d, family, bf)) - ladj).astype(F32)
+    Sp = BR.magnitude_logpdf_constrained(c["params"], d, family, blocks, X)
+    new = BR.entry_ratio(bad, ref, Sp, BR.U32, env=np.abs(yard - ref))
+    assert BR.entry_ratio(yard.astype(F32), ref, Sp, BR.U32, env=np.abs(yard - ref)) <= HALF
+    want = ref   # (the old test's `want` is log q(eta) - ladj at the float64 eta: the same number to float32 rounding of X)
+    eta32, ladj32, _ = BR.inverse(blocks, X, F32)
+    old_yard = np.max(np.abs(R.logpdf_cols(c["params"], d, family, eta32, F32).astype(np.float64) - ladj32 - want) / np.abs(want))
+    old = np.max(np.abs(bad - want) / np.abs(want)) <= FACTOR * old_yard
+    print(f"[bijector teeth] 8 eta rounded to bf16 before log q, family {family}: old criterion {'ADMITS' if old else 'rejects'}, new criterion worst ratio {new:.3g}")
+    assert new > FACTOR

@@ -6,7 +6,8 @@ Tolerances
     f64: TOL64 of tests/test_gpu_scoregrad.py (value rel 1e-12, gradient l2 1e-11 against max(|g|, 1)), against the float64 restatement.
     f32: no number.  The library's distance from the float64 result is at most F32_FACTOR = 8 x the distance of the same restatement
          evaluated in float32 numpy, both maximised over the estimate indices INDICES (the yardstick and factor of test_gpu_scoregrad.py).
-Shapes: d in {5, 37, 300} (300 > 256: the column loop and the scan carry across a chunk), M in {1, 10, 33}; layouts: bijector_ref.layout."""
+Shapes: d in {5, 37, 300} (300 > 256: the column loop and the scan carry across a chunk), M in {1, 10, 33}; layouts: bijector_ref.layout.
+The same kernels are held PER ENTRY, at the helpers' default scales and on wider classes, by tests/test_gpu_bijector_yardstick.py."""
 import ctypes as C
 import math
 import warnings
