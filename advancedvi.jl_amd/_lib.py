@@ -40,6 +40,9 @@ SIGNATURES = {
     "mivi_set_base_dist": (C.c_int32, [C.c_void_p, C.c_int32, C.c_double]),
     "mivi_optimize_loop": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mivi_logreg_select_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
+    "mivi_logreg_set_batch_schedule": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mivi_logreg_seek_batch": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "mivi_optimize_loop_batches": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "mivi_prox_scale_entropy": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32]),
     "mivi_set_target_diag_gauss": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mivi_set_target_dense_gauss": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -179,6 +182,12 @@ class MiviLoop(C.Structure):
                 ("clip_epsilon", C.c_double), ("avg_eta", C.c_double),
                 ("opt_state_dev", C.c_void_p), ("avg_params_dev", C.c_void_p),
                 ("estimate_idx0", C.c_uint64), ("t0", C.c_int64), ("elbo_dev", C.c_void_p)]
+
+
+class MiviBatchSchedule(C.Structure):
+    """mivi_batch_schedule_t (include/mivi.h)"""
+    _fields_ = [("rows_host", C.c_void_p), ("estimate_idx_host", C.c_void_p), ("batch", C.c_int64),
+                ("n_batches", C.c_int32), ("kernels", C.c_int32), ("likeadj", C.c_double)]
 
 
 def check(lib, ctx, status):

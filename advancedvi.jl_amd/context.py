@@ -796,6 +796,54 @@ class MiviContext:
                           self._p(elbo) if elbo is not None else None)
         self._chk(self.lib.mivi_optimize_loop(self.h, self._p(params), C.byref(l)))
 
+    # -- a schedule of minibatches resident on the device (the built-in logistic regression) ----------
+    def set_batch_schedule(self, rows, estimate_idx=None, likeadj=None, kernels=0):
+        """mivi_logreg_set_batch_schedule: rows int[n_batches, batch] (0-based rows of the resident data set), estimate_idx
+        uint64[n_batches] or None, likeadj = n_data / batch (None: the data set's row count over `batch`).  rows = None or an empty
+        schedule removes it (the full data set again).  After the call the target is batch 0."""
+        if rows is None or np.size(rows) == 0:
+            sched = _lib.MiviBatchSchedule(None, None, 0, 0, 0, 1.0)
+            self._chk(self.lib.mivi_logreg_set_batch_schedule(self.h, C.byref(sched)))
+            return
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 2:
+            raise ValueError("rows must be a matrix: one row of data-set indices per batch")
+        n_batches, batch = rows.shape
+        idx = None
+        if estimate_idx is not None:
+            idx = np.ascontiguousarray(estimate_idx, dtype=np.uint64)
+            if idx.shape != (n_batches,):
+                raise ValueError("estimate_idx must hold one index per batch")
+        if likeadj is None:
+            full = getattr(self, "_lr_full", None)
+            if full is None:
+                raise ValueError("likeadj is needed: the context holds no LogRegProblem to take n_data from")
+            likeadj = full.likeadj * full.n_rows() / batch   # (what LogRegSubset gives a batch of that size)
+        sched = _lib.MiviBatchSchedule(rows.ctypes.data, idx.ctypes.data if idx is not None else None, batch, n_batches, int(kernels),
+                                       float(likeadj))
+        self._chk(self.lib.mivi_logreg_set_batch_schedule(self.h, C.byref(sched)))
+
+    def seek_batch(self, k):
+        """mivi_logreg_seek_batch: the target becomes batch k of the schedule (host-side: no device work)."""
+        self._chk(self.lib.mivi_logreg_seek_batch(self.h, int(k)))
+
+    def batch_route(self, n_samples=0):
+        """Which kernels evaluate the selected batch of a scheduled context for n_samples per launch: 1 the fused minibatch kernel,
+        2 the device gather + the resident-data kernels; 0 without a schedule (mivi_logreg_kernels, bits 3 and 4)."""
+        r = int(self.lib.mivi_logreg_kernels(self.h, int(n_samples)))
+        return 1 if r & 8 else (2 if r & 16 else 0)
+
+    def optimize_loop_batches(self, params, n_steps, idx0, t0, first_batch=0, rule=0, op=0, averager=0, eta=0.0, beta=(0.9, 0.999),
+                              adam_eps=1e-8, clip_epsilon=0.0, avg_eta=8.0, opt_state=None, avg_params=None, elbo=None):
+        """mivi_optimize_loop_batches: optimize_loop where step t evaluates batch first_batch + t of the schedule (and draws at that
+        batch's estimate index when the schedule carries them; at idx0 + t otherwise)."""
+        l = _lib.MiviLoop(int(rule), int(op), int(averager), int(n_steps), float(eta), float(beta[0]), float(beta[1]),
+                          float(adam_eps), float(clip_epsilon), float(avg_eta),
+                          self._p(opt_state) if opt_state is not None else None,
+                          self._p(avg_params) if avg_params is not None else None, int(idx0), int(t0),
+                          self._p(elbo) if elbo is not None else None)
+        self._chk(self.lib.mivi_optimize_loop_batches(self.h, self._p(params), C.byref(l), int(first_batch)))
+
     def optimize_steps(self, params, opt_state, idx0, t0, n_steps, rule, eta, clip_epsilon, elbo=None):
         st = self.lib.mivi_optimize_steps(self.h, self._p(params), self._p(opt_state) if opt_state is not None else None,
                                           idx0, int(t0), int(n_steps), int(rule), float(eta), float(clip_epsilon),

@@ -9,6 +9,7 @@ static const char *base_name(const mivi_ctx *c) { return c->base == MIVI_BASE_LA
 
 mivi_status_t refuse_non_gaussian(mivi_ctx *c, const char *entry) {
   if (mivi_status_t rs = refuse_lowrank(c, entry)) return rs;
+  if (mivi_status_t rs = refuse_batch_schedule(c, entry)) return rs;   // (these entries are also the ones that read a logistic regression's data set themselves)
   if (c->base == MIVI_BASE_NORMAL) return MIVI_OK;
   c->err = std::string(entry) + ": not supported with the non-normal base distribution " + base_name(c) + " (mivi_set_base_dist)";
   return MIVI_ERR_UNSUPPORTED;

@@ -435,6 +435,7 @@ mivi_status_t mivi_set_target_logreg(mivi_ctx_t *c, const void *X, const uint8_t
   c->lr_y_full = c->lr_y;
   c->lr_n_full = n;
   c->lr_likeadj_full = likeadj;
+  c->lr_sched_n = c->lr_sched_k = 0;   // (a schedule of batches named rows of the previous data set)
   c->t_const = 0.0;
   c->target = TGT_LOGREG;
   c->cap_M = 0;   // (re)allocate the transposed-sample buffer
@@ -444,11 +445,33 @@ mivi_status_t mivi_set_target_logreg(mivi_ctx_t *c, const void *X, const uint8_t
   return MIVI_OK;
 }
 
+// the gathered copy of a batch of b rows (launch_logreg_gather): both orientations for f32; then the active fields on it
+static mivi_status_t ensure_batch_copy(mivi_ctx *c, int64_t b) {
+  const int p = c->cfg.d - 1;
+  mivi_status_t s;
+  if ((s = ensure(c, c->lr_Xsub, (size_t)b * p * c->esize, false)) || (s = ensure(c, c->lr_ysub, (size_t)b, false))) return s;
+  if (c->cfg.dtype == MIVI_F32 && (s = ensure(c, c->lr_Xrm_sub, (size_t)((b + 15) / 16 * 16) * ((p + 31) / 32 * 32) * sizeof(float), false))) return s;
+  return MIVI_OK;
+}
+static void point_at_batch_copy(mivi_ctx *c, int64_t b, double likeadj) {
+  c->lr_X = c->lr_Xsub.p;
+  c->lr_y = (const uint8_t *)c->lr_ysub.p;
+  c->lr_n = b;
+  c->lr_likeadj = likeadj;
+  c->lr_Xrm_act = c->cfg.dtype == MIVI_F32 ? c->lr_Xrm_sub.p : nullptr;
+}
+
 mivi_status_t mivi_logreg_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t b, double likeadj) {
   if (!c || b < 0 || (b > 0 && !idx)) return MIVI_ERR_BAD_ARG;
   if (c->target != TGT_LOGREG || !c->lr_X_full) return fail(c, MIVI_ERR_NO_TARGET, "no logistic-regression target set");
   (void)hipSetDevice(c->cfg.device);
+  if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection -- rows or a schedule -- in force)
+    if (!(likeadj > 0.0)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive");
+    for (int64_t j = 0; j < b; ++j)
+      if (idx[j] < 0 || idx[j] >= c->lr_n_full) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
+  }
   invalidate_graph(c);
+  c->lr_sched_n = c->lr_sched_k = 0;   // the row selection replaces a schedule of batches
   if (b == 0) {   // back to the full data set
     c->lr_X = c->lr_X_full;
     c->lr_y = c->lr_y_full;
@@ -457,25 +480,75 @@ mivi_status_t mivi_logreg_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t
     c->lr_Xrm_act = c->cfg.dtype == MIVI_F32 ? c->lr_Xrm.p : nullptr;
     return MIVI_OK;
   }
-  if (!(likeadj > 0.0)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive");
-  for (int64_t j = 0; j < b; ++j)
-    if (idx[j] < 0 || idx[j] >= c->lr_n_full) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
-  const int p = c->cfg.d - 1;
   mivi_status_t s;
-  if ((s = ensure(c, c->lr_idx, (size_t)b * sizeof(int64_t), false)) ||
-      (s = ensure(c, c->lr_Xsub, (size_t)b * p * c->esize, false)) || (s = ensure(c, c->lr_ysub, (size_t)b, false)))
-    return s;
-  if (c->cfg.dtype == MIVI_F32 && (s = ensure(c, c->lr_Xrm_sub, (size_t)((b + 15) / 16 * 16) * ((p + 31) / 32 * 32) * sizeof(float), false))) return s;
+  if ((s = ensure(c, c->lr_idx, (size_t)b * sizeof(int64_t), false)) || (s = ensure_batch_copy(c, b))) return s;
   // the previous estimate may still be reading the batch buffers: order the upload behind it
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(c->lr_idx.p, idx, (size_t)b * sizeof(int64_t), hipMemcpyHostToDevice));
   launch_logreg_gather(c, b);
   HIPCHK(c, hipGetLastError());
-  c->lr_X = c->lr_Xsub.p;
-  c->lr_y = (const uint8_t *)c->lr_ysub.p;
-  c->lr_n = b;
-  c->lr_likeadj = likeadj;
-  c->lr_Xrm_act = c->cfg.dtype == MIVI_F32 ? c->lr_Xrm_sub.p : nullptr;
+  point_at_batch_copy(c, b, likeadj);
+  return MIVI_OK;
+}
+
+// ---- a schedule of minibatches resident on the device (include/mivi.h) ----
+// THE guard of every entry that reads the logistic regression's data set outside launch_logreg_target (the Hessian, measure-space, score,
+// partials / sharded / peer-to-peer and profile entries: refuse_non_gaussian reaches it for them): on a scheduled context the active
+// fields name the gather buffers, which hold whatever batch was gathered last.  Call it before reading a buffer.
+mivi_status_t refuse_batch_schedule(mivi_ctx *c, const char *entry) {
+  if (c->lr_sched_n <= 0) return MIVI_OK;
+  c->err = std::string(entry) + ": not supported while a schedule of minibatches is set (mivi_logreg_set_batch_schedule): select the rows with mivi_logreg_select_rows";
+  return MIVI_ERR_UNSUPPORTED;
+}
+
+mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *c, const mivi_batch_schedule_t *sp) {
+  if (!c || !sp) return MIVI_ERR_BAD_ARG;
+  if (c->target != TGT_LOGREG || !c->lr_X_full) return fail(c, MIVI_ERR_NO_TARGET, "no logistic-regression target set");
+  const mivi_batch_schedule_t &sc = *sp;
+  if (sc.n_batches < 0 || sc.kernels < 0 || sc.kernels > 2) return fail(c, MIVI_ERR_BAD_ARG, "batch schedule: n_batches >= 0 and kernels in 0 .. 2");
+  if (sc.n_batches == 0) return mivi_logreg_select_rows(c, nullptr, 0, 1.0);
+  if (!sc.rows_host) return MIVI_ERR_BAD_ARG;
+  if (sc.batch < 1 || sc.batch > INT32_MAX) return fail(c, MIVI_ERR_BAD_ARG, "batch schedule: a batch has at least one row");
+  if (!(sc.likeadj > 0.0)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive");
+  if (c->lr_n_full > INT32_MAX) return fail(c, MIVI_ERR_UNSUPPORTED, "batch schedule: the rows are kept as int32");
+  const size_t total = (size_t)sc.n_batches * (size_t)sc.batch;
+  std::vector<int32_t> rows(total);
+  for (size_t j = 0; j < total; ++j) {
+    if (sc.rows_host[j] < 0 || sc.rows_host[j] >= c->lr_n_full) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
+    rows[j] = (int32_t)sc.rows_host[j];
+  }
+  (void)hipSetDevice(c->cfg.device);
+  const bool has_idx = sc.estimate_idx_host != nullptr;
+  const void *was[5] = {c->lr_sched_rows.p, c->lr_sched_idx.p, c->lr_Xsub.p, c->lr_ysub.p, c->lr_Xrm_sub.p};
+  mivi_status_t s;
+  if ((s = ensure(c, c->lr_sched_rows, total * sizeof(int32_t), false)) || (has_idx && (s = ensure(c, c->lr_sched_idx, (size_t)sc.n_batches * sizeof(uint64_t), false))) ||
+      (s = ensure_batch_copy(c, sc.batch))) {
+    (void)mivi_logreg_select_rows(c, nullptr, 0, 1.0);   // (a buffer of the previous selection may be gone: the full data set)
+    return s;
+  }
+  const void *now[5] = {c->lr_sched_rows.p, c->lr_sched_idx.p, c->lr_Xsub.p, c->lr_ysub.p, c->lr_Xrm_sub.p};
+  // a recorded loop walks rows + k * batch and the index table by address: it stays valid when a schedule of the same shape replaces one
+  // in place (a chunked driver), everything else re-records
+  const bool in_place = c->lr_sched_n > 0 && c->lr_sched_k == 0 && c->lr_n == sc.batch && c->lr_sched_kernels == sc.kernels && c->lr_likeadj == sc.likeadj &&
+                        c->lr_sched_has_idx == has_idx && memcmp(was, now, sizeof(was)) == 0;
+  if (!in_place) invalidate_graph(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // an estimate in flight may still read the previous schedule
+  HIPCHK(c, hipMemcpy(c->lr_sched_rows.p, rows.data(), total * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (has_idx) HIPCHK(c, hipMemcpy(c->lr_sched_idx.p, sc.estimate_idx_host, (size_t)sc.n_batches * sizeof(uint64_t), hipMemcpyHostToDevice));
+  c->lr_sched_n = sc.n_batches;
+  c->lr_sched_k = 0;
+  c->lr_sched_kernels = sc.kernels;
+  c->lr_sched_has_idx = has_idx;
+  point_at_batch_copy(c, sc.batch, sc.likeadj);   // (where the device-gather route leaves the selected batch; the fused kernel reads the resident data set)
+  return MIVI_OK;
+}
+
+mivi_status_t mivi_logreg_seek_batch(mivi_ctx_t *c, int32_t k) {
+  if (!c) return MIVI_ERR_BAD_ARG;
+  if (c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "no batch schedule set (mivi_logreg_set_batch_schedule)");
+  if (k < 0 || k >= c->lr_sched_n) return fail(c, MIVI_ERR_BAD_ARG, "batch index outside the schedule");
+  invalidate_graph(c);
+  c->lr_sched_k = k;
   return MIVI_OK;
 }
 

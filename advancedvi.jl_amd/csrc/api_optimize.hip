@@ -210,16 +210,24 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
     Chain chn;
     chn.on = true;
     const long long *t_ptr = (const long long *)c->d_idx.p + 1;   // iterations done before this call
+    // mivi_optimize_loop_batches: step i evaluates batch first + i of the schedule (launch_logreg_target passes its rows by value) and, when
+    // the schedule carries them, draws at the batch's own index: a device word of the uploaded table, nothing added
+    const int first = c->lr_loop_first, k_kept = c->lr_sched_k;
+    const uint64_t *tab = first >= 0 && c->lr_sched_has_idx ? (const uint64_t *)c->lr_sched_idx.p + first : nullptr;
+    auto rng_at = [&](uint64_t i) {
+      RngArgs r = rng_of(c, tab ? 0ull : i);
+      r.idx_ptr = tab ? tab + i : (const uint64_t *)c->d_idx.p;
+      return r;
+    };
     for (int i = 0; i < n_steps && s == MIVI_OK; ++i) {
-      RngArgs r = rng_of(c, (uint64_t)i);
-      r.idx_ptr = (const uint64_t *)c->d_idx.p;
+      const RngArgs r = rng_at((uint64_t)i);
+      if (first >= 0) c->lr_sched_k = first + i;
       OutArgs o = final_out(c, vbuf, gbuf);
       o.elbo_rec = rec;
       o.rec_slot = i;
       c->cur = i & 1;
       chn.has_next = (i + 1 < n_steps);
-      chn.next_rng = rng_of(c, (uint64_t)i + 1);
-      chn.next_rng.idx_ptr = r.idx_ptr;
+      chn.next_rng = rng_at((uint64_t)i + 1);
       // full-rank f32 MFMA path: the optimiser step (and ClipScale) rides in the VJP epilogue -- no update kernel
       const bool fuse_upd = simple && c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && hetero_ok(c, 1) &&
                             !switches().no_fused_update;
@@ -256,10 +264,12 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
     }
     if (s == MIVI_OK) flush_chain(c, params, &chn);
     c->cur = 0;
+    c->lr_sched_k = k_kept;   // (the recorder walked it; the selected batch is the caller's)
     return s;
   };
   GraphKey key{GRAPH_LOOP, n_steps, params, vbuf};
   key.loop = l;
+  key.mode = c->lr_loop_first + 1;   // (0: mivi_optimize_loop, the selected batch or the whole data set)
   if (!c->graph.matches(key)) {
     invalidate_graph(c);
     if ((s = graph_record(c, key, record_steps))) return s;
@@ -283,7 +293,7 @@ mivi_status_t mivi_optimize_loop(mivi_ctx_t *c, void *params, const mivi_loop_t 
   const size_t plen = (size_t)mivi_params_len(c), es = c->esize;
   const size_t st_bytes = !l.opt_state_dev ? 0 : (l.rule == 1 ? 2 * plen * es : (l.rule == 4 ? 5 * plen * es : (l.rule >= 2 ? (size_t)mivi_dog_state_bytes(c) : 0)));
   const size_t avg_bytes = (l.averager == 1 && l.avg_params_dev) ? plen * es : 0;
-  const bool may_exchange = !c->exchange_lost && (l.rule == 2 || l.rule == 3 || c->target == TGT_FUNNEL || c->target == TGT_LOGREG);
+  const bool may_exchange = !c->exchange_lost && (l.rule == 2 || l.rule == 3 || c->target == TGT_FUNNEL || (c->target == TGT_LOGREG && c->lr_sched_n == 0));
   if (may_exchange && l.n_steps > 0 && l.rule >= 0 && l.rule <= 4) {
     mivi_status_t s = ensure(c, c->snap, plen * es + st_bytes + avg_bytes + 64, false);
     if (s) return s;
@@ -306,5 +316,19 @@ mivi_status_t mivi_optimize_loop(mivi_ctx_t *c, void *params, const mivi_loop_t 
     used = false;
     s = optimize_loop_run(c, params, lp, false, &used);
   }
+  return s;
+}
+
+// Whole steps of a SubsampledObjective (src/algorithms/subsampledobjective.jl:64-90) on the device: the loop above over the batches
+// first_batch, first_batch + 1, ... of the resident schedule.  A scheduled context takes no launch-free loop (lr_small_loop_ok sees the
+// schedule), so this is the graph of launches with the batch of every step baked in (record_steps).
+mivi_status_t mivi_optimize_loop_batches(mivi_ctx_t *c, void *params, const mivi_loop_t *lp, int32_t first_batch) {
+  if (!c || !params || !lp) return MIVI_ERR_BAD_ARG;
+  if (c->target != TGT_LOGREG || c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_batches: no batch schedule set (mivi_logreg_set_batch_schedule)");
+  if (first_batch < 0 || lp->n_steps <= 0 || (long long)first_batch + lp->n_steps > c->lr_sched_n)
+    return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_batches: first_batch + n_steps must lie inside the schedule");
+  c->lr_loop_first = first_batch;
+  const mivi_status_t s = mivi_optimize_loop(c, params, lp);
+  c->lr_loop_first = -1;
   return s;
 }

@@ -480,7 +480,8 @@ bool lr_small_loop_ok(const mivi_ctx *c) {
   const int d = c->cfg.d, M = c->cfg.n_mc;
   const bool stl = c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD;
   if (!(c->target == TGT_LOGREG && !c->bij_on && !stl && d >= 2 && d <= kLrSmallD && M >= 1 && M <= kLrSmallM && c->cfg.m_offset == 0 && c->M_total == M &&
-        c->lr_X && c->lr_y && c->lr_n >= 1 && c->lr_route == 0))   // (mivi_set_logreg_route pins the general route's kernels: the graph of launches)
+        c->lr_X && c->lr_y && c->lr_n >= 1 && c->lr_route == 0 &&   // (mivi_set_logreg_route pins the general route's kernels: the graph of launches)
+        c->lr_sched_n == 0))   // (a schedule of minibatches: the batch's rows are read through the schedule, by launch_logreg_target alone)
     return false;
   const bool fr = c->cfg.family == MIVI_FULLRANK;
   const long long ne = d + (fr ? (long long)d * (d + 1) / 2 : d);

@@ -1099,9 +1099,10 @@ bool logreg_prepare_f32(mivi_ctx *c) {
   return true;
 }
 
-// minibatch gather: column-major subset (generic / f64 route), labels, and -- f32 -- whole rows of the row-major copy
-template <typename T>
-__global__ void k_lr_gather_cm(long long n, long long b, int p, const long long *idx, const T *X, const uint8_t *y, T *Xs,
+// minibatch gather: column-major subset (generic / f64 route), labels, and -- f32 -- whole rows of the row-major copy.  The row list is
+// mivi_logreg_select_rows' upload (int64) or a batch of the resident schedule (int32: mivi_logreg_set_batch_schedule)
+template <typename T, typename I>
+__global__ void k_lr_gather_cm(long long n, long long b, int p, const I *idx, const T *X, const uint8_t *y, T *Xs,
                                uint8_t *ys) {
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= b) return;
@@ -1110,26 +1111,31 @@ __global__ void k_lr_gather_cm(long long n, long long b, int p, const long long 
   Xs[(size_t)k * b + j] = X[(size_t)k * n + r];
   if (k == 0) ys[j] = y[r];
 }
-__global__ void k_lr_gather_rm(long long b, int ldx, const long long *idx, const float *Xrm, float *Xs) {
+template <typename I>
+__global__ void k_lr_gather_rm(long long b, int ldx, const I *idx, const float *Xrm, float *Xs) {
   const long long j = blockIdx.x;   // rows b .. gridDim.x-1: the zero padding up to a whole 16-row stage
   const float4 *src = (const float4 *)(Xrm + (size_t)(j < b ? idx[j] : 0) * ldx);
   float4 *dst = (float4 *)(Xs + (size_t)j * ldx);
   for (int t = threadIdx.x; t < ldx / 4; t += 128) dst[t] = j < b ? src[t] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
-void launch_logreg_gather(mivi_ctx *c, int64_t b) {
+template <typename I>
+static void logreg_gather_impl(mivi_ctx *c, int64_t b, const I *idx) {
   const int p = c->cfg.d - 1;
   const dim3 g((unsigned)((b + 255) / 256), p);
-  const long long *idx = (const long long *)c->lr_idx.p;
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_lr_gather_cm<T>, g, dim3(256), 0, c->stream, (long long)c->lr_n_full, (long long)b, p, idx, (const T *)c->lr_X_full, c->lr_y_full,
+    hipLaunchKernelGGL((k_lr_gather_cm<T, I>), g, dim3(256), 0, c->stream, (long long)c->lr_n_full, (long long)b, p, idx, (const T *)c->lr_X_full, c->lr_y_full,
                        (T *)c->lr_Xsub.p, (uint8_t *)c->lr_ysub.p);
   });
   if (c->cfg.dtype == MIVI_F32) {   // the row-major copy exists for f32 only (the matrix-core route)
     const int ldx = (p + 31) / 32 * 32;
-    hipLaunchKernelGGL(k_lr_gather_rm, dim3((unsigned)((b + 15) / 16 * 16)), dim3(128), 0, c->stream, (long long)b, ldx, idx,
+    hipLaunchKernelGGL(k_lr_gather_rm<I>, dim3((unsigned)((b + 15) / 16 * 16)), dim3(128), 0, c->stream, (long long)b, ldx, idx,
                        (const float *)c->lr_Xrm.p, (float *)c->lr_Xrm_sub.p);
   }
+}
+void launch_logreg_gather(mivi_ctx *c, int64_t b, const int32_t *rows) {
+  if (rows) logreg_gather_impl<int32_t>(c, b, rows);
+  else logreg_gather_impl<long long>(c, b, (const long long *)c->lr_idx.p);
 }
 
 // Scratch geometry of the two routes.  logreg_reserve() sizes the buffers ahead of time (and is what makes the target
@@ -1199,13 +1205,29 @@ static LrGeom lr_geom(const mivi_ctx *c, int M) {
   }
   return g;
 }
-bool logreg_uses_mfma(const mivi_ctx *c, int M) { return c->target == TGT_LOGREG && lr_geom(c, M).mfma; }
+// A scheduled context (mivi_logreg_set_batch_schedule): which kernels evaluate the selected batch.  1: the fused minibatch kernel
+// (kernels_logreg_batch.hip) -- by size below the matrix-core threshold of lr_geom, where a slab fits the LDS and k_lr_finish's serial walk
+// over the slabs stays short; 2: the device gather and the resident-data kernels on the gathered copy.
+int logreg_batch_route(const mivi_ctx *c, int M) {
+  if (c->target != TGT_LOGREG || c->lr_sched_n <= 0) return 0;
+  if (c->lr_sched_kernels == 2 || !lr_batch_fits(c, M)) return 2;
+  if (c->lr_sched_kernels == 1) return 1;
+  return (double)c->lr_n * (double)(c->cfg.d - 1) * (double)M < 1.6e7 && lr_batch_slabs(c, M) <= 256 ? 1 : 2;
+}
+bool logreg_uses_mfma(const mivi_ctx *c, int M) { return c->target == TGT_LOGREG && logreg_batch_route(c, M) != 1 && lr_geom(c, M).mfma; }
 int logreg_kernel_bits(const mivi_ctx *c, int M) {
   if (c->target != TGT_LOGREG) return 0;
+  const int br = logreg_batch_route(c, M);
+  if (br == 1) return 8;
   const LrGeom g = lr_geom(c, M);
-  return (g.mfma ? 1 : 0) | (g.planes ? 2 : 0) | (g.xplanes ? 4 : 0);
+  return (g.mfma ? 1 : 0) | (g.planes ? 2 : 0) | (g.xplanes ? 4 : 0) | (br == 2 ? 16 : 0);
 }
 bool logreg_reserve(mivi_ctx *c, int M) {
+  if (logreg_batch_route(c, M) == 1) {   // [slab][M] f64 and [slab][M][p] partials, nothing else
+    const size_t S = (size_t)lr_batch_slabs(c, M);
+    return lr_batch_prepare(c, M) && !ensure(c, c->lr_scratch, S * (size_t)(c->cfg.d - 1) * M * c->esize, false) &&
+           !ensure(c, c->lr_part, S * M * sizeof(double), false);
+  }
   const LrGeom g = lr_geom(c, M);
   if (g.planes && ensure(c, c->lr_ZP, (size_t)(M / 32) * (((c->cfg.d - 1 + 31) / 32 * 32) / 16) * kFrag * 4, false)) return false;
   return !ensure(c, c->lr_scratch, g.need_R + g.need_g, false) && !ensure(c, c->lr_part, g.need_ll, false);
@@ -1317,8 +1339,37 @@ static bool logreg_impl(mivi_ctx *c, int M, int want_grad) {
   return true;
 }
 
+// a batch of the schedule on the fused minibatch kernel: its partials, then the finisher of the other routes
+template <typename T>
+static bool logreg_batch_fused(mivi_ctx *c, int M, int want_grad, const int32_t *rows) {
+  if (!logreg_reserve(c, M)) return false;
+  LrArgs<T> a{};
+  a.d = c->cfg.d;
+  a.p = a.d - 1;
+  a.M = M;
+  a.n = c->lr_n;
+  a.Z = (const T *)c->Z.p;
+  a.ll_part = (double *)c->lr_part.p;
+  a.g_part = (T *)c->lr_scratch.p;
+  int S = 0;
+  launch_lr_batch(c, M, want_grad, rows, a.ll_part, a.g_part, &S);
+  a.S = a.nrb = S;
+  a.G = (T *)c->W.p;
+  a.ell = (T *)c->ell.p;
+  a.variant = c->lr_variant;
+  a.likeadj = c->lr_likeadj;
+  a.want_grad = want_grad;
+  hipLaunchKernelGGL(k_lr_finish<T>, dim3(M), dim3(256), 0, c->stream, a);
+  return true;
+}
+
 // false: device allocation of the residual / partial buffers failed
 bool launch_logreg_target(mivi_ctx *c, int M, int want_grad) {
+  if (const int br = logreg_batch_route(c, M)) {   // the selected batch of the schedule: its rows by value
+    const int32_t *rows = (const int32_t *)c->lr_sched_rows.p + (size_t)c->lr_sched_k * (size_t)c->lr_n;
+    if (br == 1) return by_dtype(c, [&](auto t) { return logreg_batch_fused<decltype(t)>(c, M, want_grad, rows); });
+    launch_logreg_gather(c, c->lr_n, rows);   // ... into lr_Xsub / lr_ysub / lr_Xrm_sub, which the kernels below read
+  }
   if (lr_geom(c, M).mfma) return logreg_mfma(c, M, want_grad);
   return by_dtype(c, [&](auto t) { return logreg_impl<decltype(t)>(c, M, want_grad); });
 }

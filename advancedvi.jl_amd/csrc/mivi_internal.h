@@ -345,7 +345,7 @@ struct GraphKey {
   void *value = nullptr;
   void *grad = nullptr;
   int lanes = 0, per_branch = 0;   // GRAPH_FORKED_CHAINS / GRAPH_LANE_BRANCHES
-  int route = 0, mode = 0;         // GRAPH_SHARDED: mivi_comm_route, the sequence (api_dist.hip dist_sequence)
+  int route = 0, mode = 0;         // GRAPH_SHARDED: mivi_comm_route, the sequence (api_dist.hip dist_sequence); GRAPH_LOOP: mode = first_batch + 1 of mivi_optimize_loop_batches (0: not over a schedule)
   mivi_loop_t loop{};              // GRAPH_LOOP: the configuration the captured loop was built for
 };
 struct GraphCache {
@@ -480,6 +480,15 @@ struct mivi_ctx : mivi_ctx_streams {
   int64_t lr_n = 0;
   int lr_variant = 0;
   double lr_likeadj = 1.0;
+  // schedule of minibatches (mivi_logreg_set_batch_schedule): n_batches x batch rows of the full data set, resident as int32, and the
+  // estimate index of every batch (if given).  While one is set lr_n = batch and lr_likeadj is the schedule's; the selected batch lr_sched_k
+  // is a host-side field -- a launch passes lr_sched_rows + k * batch by value -- and nothing is gathered ahead of an estimate.
+  mivi::DevBuf lr_sched_rows, lr_sched_idx;
+  int lr_sched_n = 0;                      // batches (0: no schedule)
+  int lr_sched_k = 0;                      // the selected batch (mivi_logreg_seek_batch; the loop's recorder walks it)
+  int lr_sched_kernels = 0;                // 0 by size | 1 the fused minibatch kernel | 2 device gather + the resident-data kernels
+  bool lr_sched_has_idx = false;
+  int lr_loop_first = -1;                  // >= 0 while mivi_optimize_loop_batches runs: step t of the loop evaluates batch lr_loop_first + t
   // callback
   mivi_logdensity_and_gradient_fn cb_grad = nullptr;
   mivi_logdensity_fn cb_value = nullptr;
@@ -791,7 +800,12 @@ void launch_poly_average(mivi_ctx *c, void *avg, const void *params, double avg_
 void launch_dog_update(mivi_ctx *c, void *params, const void *grad, void *state, int kind);
 bool launch_dog_update_fused(mivi_ctx *c, void *params, const void *grad, void *state, int kind, double clip_eps, void *avg,
                              double avg_eta, const long long *t_ptr, long long t_base);
-void launch_logreg_gather(mivi_ctx *c, int64_t b);   // batch rows lr_idx[0..b) of the full data set -> lr_Xsub / lr_ysub / lr_Xrm_sub
+void launch_logreg_gather(mivi_ctx *c, int64_t b, const int32_t *rows = nullptr);   // batch rows lr_idx[0..b) (rows: that device list instead, a batch of the schedule) of the full data set -> lr_Xsub / lr_ysub / lr_Xrm_sub
+int logreg_batch_route(const mivi_ctx *c, int M);   // a scheduled context: 1 the fused minibatch kernel (kernels_logreg_batch.hip), 2 device gather + the resident-data kernels; 0: no schedule
+bool lr_batch_fits(const mivi_ctx *c, int M);       // kernels_logreg_batch.hip: a minimal slab of the fused minibatch kernel fits the LDS
+bool lr_batch_prepare(mivi_ctx *c, int M);          // its LDS attribute, ahead of a capture
+void launch_lr_batch(mivi_ctx *c, int M, int want_grad, const int32_t *rows, double *ll_part, void *g_part, int *n_slabs);   // ll_part[slab][M], g_part[slab][M][p]
+int lr_batch_slabs(const mivi_ctx *c, int M);
 void launch_value_only(mivi_ctx *c, const void *params, const ValueIn &vin, const OutArgs &out);   // on c->stream
 void launch_clip(mivi_ctx *c, void *params, double epsilon);
 void launch_descent(mivi_ctx *c, void *params, const void *grad, double eta, double clip_eps = NAN);   // NaN: no ClipScale

@@ -523,6 +523,46 @@ function native_logreg!(state::MIVIState, m::NativeLogReg; variant::Int = 0, lik
     return state
 end
 
+# A schedule of minibatches resident on the device (include/mivi.h: mivi_batch_schedule_t): what ReshufflingBatchSubsampling delivers to
+# estimate_gradient! over a run of steps (src/reshuffling.jl:38-60), uploaded once per chunk; the estimates then read the selected batch's rows
+# of the resident data set through it, and mivi_optimize_loop_batches runs whole steps of a SubsampledObjective
+# (src/algorithms/subsampledobjective.jl:64-90) on the device.  Thin wrappers: the planning of a chunk (the shuffles and the estimate
+# indices, in the order `step` consumes the rng) is the caller's.
+struct MiviBatchSchedule
+    rows_host::Ptr{Int64}; estimate_idx_host::Ptr{UInt64}
+    batch::Int64
+    n_batches::Int32; kernels::Int32
+    likeadj::Float64
+end
+
+# rows0: batch x n_batches, 0-based rows of the data set (one COLUMN per batch: batch-major in memory); estimate_idx: one index per batch or
+# nothing; kernels: 0 by size | 1 the fused minibatch kernel | 2 device gather + the resident-data kernels.  After the call the target is batch 0.
+function set_batch_schedule!(state::MIVIState, rows0::Matrix{Int64}, estimate_idx::Union{Nothing,Vector{UInt64}}, likeadj::Real; kernels::Integer = 0)
+    estimate_idx === nothing || length(estimate_idx) == size(rows0, 2) || throw(ArgumentError("one estimate index per batch"))
+    GC.@preserve rows0 estimate_idx begin
+        sched = Ref(MiviBatchSchedule(pointer(rows0), estimate_idx === nothing ? Ptr{UInt64}(C_NULL) : pointer(estimate_idx),
+                                      Int64(size(rows0, 1)), Int32(size(rows0, 2)), Int32(kernels), Float64(likeadj)))
+        check(state.ctx, ccall((:mivi_logreg_set_batch_schedule, libmivi), Int32, (Ptr{Cvoid}, Ref{MiviBatchSchedule}), state.ctx, sched))
+    end
+    return state
+end
+# back to the full data set
+function clear_batch_schedule!(state::MIVIState)
+    sched = Ref(MiviBatchSchedule(Ptr{Int64}(C_NULL), Ptr{UInt64}(C_NULL), Int64(0), Int32(0), Int32(0), 1.0))
+    check(state.ctx, ccall((:mivi_logreg_set_batch_schedule, libmivi), Int32, (Ptr{Cvoid}, Ref{MiviBatchSchedule}), state.ctx, sched))
+    return state
+end
+# the target becomes batch k (0-based) of the schedule: host-side, no device work
+seek_batch!(state::MIVIState, k::Integer) =
+    (check(state.ctx, ccall((:mivi_logreg_seek_batch, libmivi), Int32, (Ptr{Cvoid}, Int32), state.ctx, Int32(k))); state)
+# mivi_optimize_loop where step t evaluates batch first_batch + t (and draws at that batch's estimate index when the schedule has them)
+function optimize_loop_batches!(state::MIVIState, params_dev::Ptr{Cvoid}, loop::MiviLoop, first_batch::Integer)
+    status = ccall((:mivi_optimize_loop_batches, libmivi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{MiviLoop}, Int32), state.ctx, params_dev, Ref(loop), Int32(first_batch))
+    status == 2 && throw(ErrorException("The objective value is not finite. This indicates that the optimization run diverged."))
+    check(state.ctx, status)
+    return state
+end
+
 # gaussian_expectation_gradient_and_hessian! (src/algorithms/gauss_expected_grad_hess.jl:20-60), the inner estimator of
 # KLMinWassFwdBwd / KLMinNaturalGradDescent / KLMinSqrtNaturalGradDescent.  That function has no `adtype` to dispatch on,
 # so the seam is the problem argument: wrap the target in `MIVITarget(prob, state)` (state from `AdvancedVI.init` above,

@@ -319,11 +319,24 @@ _AVGS = {NoAveraging: 0, PolynomialAveraging: 1}
 DEVICE_LOOP_CHUNK = 256   # iterations per mivi_optimize_loop call (bounds the work done past a divergence)
 
 
-def _device_loop_codes(alg, callback, objargs):
+SUBSAMPLED_KERNELS = 0    # tools / tests: the `kernels` of the chunk schedules (0 by size, 1 the fused minibatch kernel, 2 device gather)
+
+
+def _scheduled_logreg(obj, prob):
+    """A SubsampledObjective whose steps can run off a schedule of minibatches resident on the device (MiviContext.set_batch_schedule):
+    a plain RepGradELBO inside, reshuffled batches, and the built-in logistic regression (also behind a TransformedProblem) as data."""
+    from . import problems as P
+    inner = prob.prob if isinstance(prob, P.TransformedProblem) else prob
+    return (isinstance(obj, S.SubsampledObjective) and type(obj.objective) is O.RepGradELBO and
+            isinstance(obj.subsampling, S.ReshufflingBatchSubsampling) and type(inner) is P.LogRegProblem)
+
+
+def _device_loop_codes(alg, callback, objargs, prob=None):
     """(rule, op, averager) when a whole `step` can run inside mivi_optimize_loop, else None: no callback (it needs the
-    parameters on the host every iteration), a plain RepGradELBO, and rule / operator / averager of the exact reference
+    parameters on the host every iteration), a plain RepGradELBO -- or a SubsampledObjective around one over the built-in
+    logistic regression `prob` (mivi_optimize_loop_batches) -- and rule / operator / averager of the exact reference
     types (subclasses may override behaviour)."""
-    if callback is not None or objargs or not isinstance(alg.objective, O.RepGradELBO):
+    if callback is not None or objargs or not (isinstance(alg.objective, O.RepGradELBO) or _scheduled_logreg(alg.objective, prob)):
         return None
     r, o, a = _RULES.get(type(alg.optimizer)), _OPS.get(type(alg.operator)), _AVGS.get(type(alg.averager))
     if r is None or o is None or a is None or (o == 2 and r in (1, 4)):
@@ -342,6 +355,7 @@ def _optimize_on_device(rng, alg, max_iter, state, codes, show_progress):
     params = state["params"]
     opt, info_total = alg.optimizer, []
     done = 0
+    subsampled = isinstance(alg.objective, S.SubsampledObjective)   # (_device_loop_codes: the built-in logistic regression, batches off a resident schedule)
     import torch
 
     def _tensors(x):   # the device tensors inside an optimiser / averager state (tensor, tuple of tensors and scalars, None)
@@ -359,18 +373,32 @@ def _optimize_on_device(rng, alg, max_iter, state, codes, show_progress):
         # Optimisers.update! (common.jl:83-94), leaving every earlier step applied
         live = [params] + _tensors(state["opt_st"]) + _tensors(state["avg_st"])
         snap = [t.clone() for t in live]
+        loop_args = dict(rule=rule, op=op, averager=avg,
+                         eta=getattr(opt, "alpha", 0.0) if rule == 4 else getattr(opt, "eta", 0.0), beta=getattr(opt, "beta", (0.9, 0.999)),
+                         adam_eps=getattr(opt, "epsilon", 1e-8), clip_epsilon=getattr(alg.operator, "epsilon", 0.0),
+                         avg_eta=getattr(alg.averager, "eta", 8), opt_state=state["opt_st"], avg_params=avg_params, elbo=elbo)
+        counter0, sub_infos = rng.counter, None   # (the shuffles and the estimates share the counter: a replay starts from it)
         try:
-            ctx.optimize_loop(params, n, rng.counter, state["iteration"], rule=rule, op=op, averager=avg,
-                              eta=getattr(opt, "alpha", 0.0) if rule == 4 else getattr(opt, "eta", 0.0), beta=getattr(opt, "beta", (0.9, 0.999)),
-                              adam_eps=getattr(opt, "epsilon", 1e-8), clip_epsilon=getattr(alg.operator, "epsilon", 0.0),
-                              avg_eta=getattr(alg.averager, "eta", 8), opt_state=state["opt_st"], avg_params=avg_params,
-                              elbo=elbo)
+            if subsampled:
+                # the chunk's steps planned ahead -- the batches and the estimate indices `estimate_gradient_` would have taken off `rng`
+                # one step at a time -- and resident on the device: one upload per chunk, the batch of every step read through it
+                sub_st0 = state["obj_st"].sub_st
+                rows, est_idx, sub_infos, sub_st1 = S.plan_batches(rng, alg.objective.subsampling, sub_st0, n)
+                ctx.set_batch_schedule(rows, est_idx, kernels=SUBSAMPLED_KERNELS)
+                ctx.optimize_loop_batches(params, n, counter0, state["iteration"], first_batch=0, **loop_args)
+                state["obj_st"] = S.SubsampledObjectiveState(state["obj_st"].prob, sub_st1, state["obj_st"].obj_st)
+            else:
+                ctx.optimize_loop(params, n, rng.counter, state["iteration"], **loop_args)
         except MiviError as e:
             if e.status == 6 and done == 0:      # MIVI_ERR_UNSUPPORTED: not a device-resident target
+                rng.counter = counter0
                 return None
             if e.status in (2, 3):               # common.jl:83-89 (a non-positive scale makes the objective NaN)
                 # the chunk ran past the bad step: restore its entry state and replay it on the host-driven loop, which raises
                 # at the offending iteration with the steps before it applied and rng / iteration advanced consistently
+                # (a subsampled chunk: the counter and the subsampling state as well -- the replay shuffles and draws again, and
+                # its row selections replace the schedule)
+                rng.counter = counter0
                 for t_live, t_snap in zip(live, snap):
                     t_live.copy_(t_snap)
                 try:
@@ -398,12 +426,13 @@ def _optimize_on_device(rng, alg, max_iter, state, codes, show_progress):
                 done += n
                 continue
             raise
-        for _ in range(n):
-            rng.next_index()
+        if not subsampled:   # (the plan of a subsampled chunk has taken the indices already)
+            for _ in range(n):
+                rng.next_index()
         vals = elbo.cpu().numpy()
         # info = merge(info', (iteration = t,)) with t the loop index of THIS `optimize` call (src/optimize.jl:64-68) -- not the state's
-        # cumulative counter, which a warm start carries on (common.jl:75): both routes report the same `info`
-        info_total += [{"elbo": float(vals[i]), "iteration": done + i + 1} for i in range(n)]
+        # cumulative counter, which a warm start carries on (common.jl:75): both routes report the same `info`; subsampling adds (epoch, step)
+        info_total += [{**(sub_infos[i] if subsampled else {}), "elbo": float(vals[i]), "iteration": done + i + 1} for i in range(n)]
         state["iteration"] = state["iteration"] + n
         state["avg_st"] = (state["avg_st"][0], state["avg_st"][1] + n) if avg == 1 else params
         done += n
@@ -418,7 +447,9 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
     """optimize([rng,] algorithm, max_iter, prob, q_init; show_progress, state, callback): src/optimize.jl:42-94.
     Returns (output, info, state).  Without a callback and with a device-resident target every iteration runs inside
     mivi_optimize_loop (`device_loop=False` forces the host-driven `step` loop; both give the same result -- bitwise or to rounding, see
-    _optimize_on_device)."""
+    _optimize_on_device).  With `subsampling=` over the built-in logistic regression the chunks run off a schedule of minibatches resident
+    on the device (mivi_optimize_loop_batches; to rounding where the fused minibatch kernel runs, bitwise on the device gather); other
+    subsampled models keep the host loop."""
     M = _measure_space(rng, algorithm)
     if M is not None:
         return M.optimize(rng, algorithm, max_iter, prob, q_init, *objargs, show_progress=show_progress, state=state, callback=callback,
@@ -430,7 +461,7 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
     info_total = []
     if state is None:
         state = init(rng, algorithm, q_init, prob)
-    codes = _device_loop_codes(algorithm, callback, objargs) if device_loop else None
+    codes = _device_loop_codes(algorithm, callback, objargs, state.get("prob")) if device_loop else None
     if codes is not None and max_iter > 0:
         state = dict(state)
         info_dev = _optimize_on_device(rng, algorithm, max_iter, state, codes, show_progress)

@@ -244,5 +244,8 @@ class TransformedProblem:
     def capabilities(self):
         return self.prob.capabilities()
 
+    def subsample(self, batch):   # AdvancedVI.subsample forwards to the wrapped problem, as ADgradient's does
+        return TransformedProblem(subsample(self.prob, batch), self.bijector)
+
 
 BUILTIN = (DiagNormalProblem, DenseNormalProblem, LogRegProblem, LogRegSubset, FunnelProblem, FunnelConstrainedProblem)

@@ -6,6 +6,10 @@
 The objective state keeps ONE libmivi context; a step only re-points its target at the minibatch
 (`set_objective_state_problem`, repgradelbo.jl:31-39) -- for the built-in logistic regression that is a row gather on
 the device (mivi_logreg_select_rows), for plugin targets it is whatever the model's `subsample` returns.
+
+Inside `optimize` (no callback, the built-in logistic regression) the steps of a chunk are planned ahead instead (`plan_batches`: the
+batches and estimate indices the steps would take off the rng), kept resident on the device as a schedule and run as whole steps of the
+device loop (MiviContext.set_batch_schedule / optimize_loop_batches; optimize._optimize_on_device).
 """
 from dataclasses import dataclass
 
@@ -57,15 +61,40 @@ def step_subsampling(rng, sub: ReshufflingBatchSubsampling, state: ReshufflingBa
                      drop_trailing_batch_if_too_small: bool = False):
     """step(rng, sub, state, drop_trailing_batch_if_too_small): reshuffling.jl:38-60.  Returns (batch, state, info).
     When the batch just taken was the last of its epoch the next epoch is shuffled immediately, and -- gradient
-    estimation only -- a trailing batch shorter than `batchsize` is replaced by the first batch of that next epoch."""
+    estimation only -- a trailing batch shorter than `batchsize` is replaced by the first batch of that next epoch.
+    A data set smaller than `batchsize` is one batch per epoch, the whole data set: all batches then have the same size, which is what
+    the replacement is for, and it is kept (the reference peels an exhausted iterator there and throws on the second step)."""
     epoch, batches = state.epoch, list(state.batches)
     sub_step, batch = batches.pop(0)
     if not batches:
         batches = reshuffle_batches(rng, sub)
-        if drop_trailing_batch_if_too_small and len(batch) < sub.batchsize:
+        if drop_trailing_batch_if_too_small and len(batch) < min(sub.batchsize, sub.dataset.size):
             sub_step, batch = batches.pop(0)
         epoch += 1
     return batch, ReshufflingBatchSubsamplingState(epoch, batches), {"epoch": epoch, "step": sub_step}
+
+
+def plan_batches(rng, sub: ReshufflingBatchSubsampling, sub_st: ReshufflingBatchSubsamplingState, n_steps: int):
+    """The next `n_steps` steps of `estimate_gradient_` planned ahead, for a schedule resident on the device
+    (MiviContext.set_batch_schedule): returns (rows int64[n_steps, b_eff], estimate_idx uint64[n_steps], infos, new_sub_st).
+
+    `rng` is consumed exactly as `n_steps` calls of `estimate_gradient_` consume it: inside a step the shuffle's index (taken when the
+    step used up its epoch: step_subsampling) comes before that step's estimate index, and a trailing batch shorter than `batchsize`
+    is replaced by the first batch of the next epoch (drop_trailing_batch_if_too_small).  Every planned batch therefore has
+    b_eff = min(batchsize, n) rows; infos[t] = {"epoch", "step"} as the step reports them."""
+    n = sub.dataset.size
+    b_eff = min(sub.batchsize, n)
+    rows = np.empty((int(n_steps), b_eff), dtype=np.int64)
+    idx = np.empty(int(n_steps), dtype=np.uint64)
+    infos = []
+    for t in range(int(n_steps)):
+        batch, sub_st, inf = step_subsampling(rng, sub, sub_st, True)
+        if len(batch) != b_eff:   # (n < batchsize is the only way to a short batch here, and then b_eff = n is its length)
+            raise AssertionError("a planned batch has an unexpected number of rows")
+        rows[t] = batch
+        idx[t] = rng.next_index()
+        infos.append(inf)
+    return rows, idx, infos, sub_st
 
 
 class SubsampledObjective:

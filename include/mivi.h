@@ -160,6 +160,35 @@ mivi_status_t mivi_set_target_logreg(mivi_ctx_t *ctx, const void *X, const uint8
  * b = 0 restores the full data set.  Synchronises the stream (the batch buffers are reused from step to step). */
 mivi_status_t mivi_logreg_select_rows(mivi_ctx_t *ctx, const int64_t *idx_host, int64_t b, double likeadj);
 
+/* A schedule of minibatches resident on the device: what ReshufflingBatchSubsampling delivers to estimate_gradient! over a run of steps
+ * (src/reshuffling.jl:38-60 with drop_trailing_batch_if_too_small: every batch has `batch` rows), uploaded once per chunk of steps.  While one
+ * is set every estimate entry (mivi_estimate_gradient[_host/_n/_each], mivi_estimate_objective[_host], mivi_optimize_steps / _loop) evaluates
+ * the SELECTED batch -- its rows are read out of the resident data set through the schedule, nothing is gathered ahead of the estimate and
+ * no host round trip is made per step; mivi_optimize_loop_batches walks the batches, one per step.
+ *   kernels  0 by size | 1 the fused minibatch kernel (one workgroup per slab of batch rows, rows and residuals in LDS: the target is two
+ *            launches; where not even a minimal slab fits the LDS -- p beyond a few thousand -- it is 2) | 2 a device gather of the batch
+ *            and the kernels of the resident data set on the copy (bitwise what mivi_logreg_select_rows + the estimate give)
+ * Every index is checked on the host before anything is uploaded: MIVI_ERR_BAD_ARG for a row outside the data set, batch < 1, likeadj <= 0;
+ * MIVI_ERR_NO_TARGET without a logistic regression; a failed call leaves the previous selection in force.  Repeated rows are allowed.
+ * After the call the target is batch 0.  The schedule and mivi_logreg_select_rows replace each other; n_batches = 0 (like select_rows with
+ * b = 0) restores the full data set.  The buffers grow but do not move when a schedule of the same or a smaller size replaces one, and a
+ * schedule of the same batch size, kernels and likeadj keeps a recorded loop: a chunked driver records once.  May synchronise the stream.
+ * The other entries that read the data set (mivi_gauss_expected_grad_hess*, the measure-space updates and steps, the score-gradient,
+ * partials / sharded / peer-to-peer and profile entries) return MIVI_ERR_UNSUPPORTED on a scheduled context: their host-driven drivers
+ * select rows with mivi_logreg_select_rows. */
+typedef struct mivi_batch_schedule {
+  const int64_t *rows_host;          /* int64[n_batches * batch], batch-major, 0-based rows of the data set given to mivi_set_target_logreg */
+  const uint64_t *estimate_idx_host; /* uint64[n_batches] or NULL: the estimate index mivi_optimize_loop_batches uses for each batch */
+  int64_t batch;                     /* rows per batch, >= 1 */
+  int32_t n_batches;                 /* 0 removes the schedule: back to the full data set */
+  int32_t kernels;                   /* 0 | 1 | 2, above */
+  double likeadj;                    /* n_data / batch (subsampling.md:37), > 0 */
+} mivi_batch_schedule_t;
+mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *ctx, const mivi_batch_schedule_t *sched);
+/* The target becomes batch k of the schedule, 0 <= k < n_batches (MIVI_ERR_BAD_ARG otherwise, the selection unchanged).  A host-side
+ * selection: no device work, no synchronisation; captured graphs are invalidated as by mivi_logreg_select_rows. */
+mivi_status_t mivi_logreg_seek_batch(mivi_ctx_t *ctx, int32_t k);
+
 /* Neal's funnel on the constrained scale + Stacked([log, identity]) bijector (README.md:76-82,102-106):
  * theta_1 = exp(eta_1) ~ LogNormal(0, sigma_v), theta_i ~ Normal(0, theta_1), log|det J| = eta_1. */
 mivi_status_t mivi_set_target_funnel(mivi_ctx_t *ctx, double sigma_v);
@@ -579,6 +608,13 @@ typedef struct mivi_loop {
   void *elbo_dev;     /* T[n_steps] or NULL: info.elbo of every iteration */
 } mivi_loop_t;
 mivi_status_t mivi_optimize_loop(mivi_ctx_t *ctx, void *params_dev, const mivi_loop_t *loop);
+/* mivi_optimize_loop on a scheduled context (mivi_logreg_set_batch_schedule) where step t (0-based) evaluates batch first_batch + t: whole
+ * steps of a SubsampledObjective (src/algorithms/subsampledobjective.jl:64-90) on the device.  When the schedule carries estimate indices,
+ * step t draws at estimate_idx_host[first_batch + t] (loop->estimate_idx0 is not read), otherwise at estimate_idx0 + t.  Requires
+ * 0 <= first_batch and first_batch + n_steps <= n_batches (MIVI_ERR_BAD_ARG).  Runs as the hipGraph of chained estimates -- a step's batch
+ * is a kernel argument, its index a device word of the uploaded table -- recorded once per (loop configuration, first_batch); every rule,
+ * operator and averager, elbo_dev, the sticky status and the non-finite behaviour of mivi_optimize_loop.  The selected batch is unchanged. */
+mivi_status_t mivi_optimize_loop_batches(mivi_ctx_t *ctx, void *params_dev, const mivi_loop_t *loop, int32_t first_batch);
 
 /* Estimate-index source: when idx_dev != NULL every estimate uses estimate_idx + *idx_dev (read on the device at
  * kernel time), so a captured graph (e.g. a torch CUDAGraph holding kernels + the RCCL all-reduce) advances the
@@ -724,7 +760,9 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *ctx, int32_t which, const void *pa
 int32_t mivi_fullrank_route(const mivi_ctx_t *ctx, int32_t n_samples);
 /* Which kernels the native logistic-regression target's two data contractions run for `n_samples` per launch (same kind of hook):
  *   0 = vector-ALU kernels (small problems, f64); bit 0: matrix cores (two-way f16 splits); bit 1: the logits on prebuilt operand planes of X
- *   (k_lr_logits_planes); bit 2: X^T R on planes too (k_lr_xtr_planes, residual planes straight from the logits kernel). */
+ *   (k_lr_logits_planes); bit 2: X^T R on planes too (k_lr_xtr_planes, residual planes straight from the logits kernel).
+ *   On a scheduled context (mivi_logreg_set_batch_schedule): 8 alone = the fused minibatch kernel reads the selected batch through the
+ *   schedule; bit 4 (16) = the batch is gathered on the device first, the other bits say which kernels then run on the copy. */
 int32_t mivi_logreg_kernels(const mivi_ctx_t *ctx, int32_t n_samples);
 
 /* Developer tool: when buf_dev != NULL every workgroup of the main kernels records wall_clock64() stamps
