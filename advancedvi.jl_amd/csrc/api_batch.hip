@@ -48,33 +48,22 @@ static mivi_status_t estimate_gradient_chain(mivi_ctx *c, const void *params, ui
   if (s) return s;
   if (!prepare_tables(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");   // host->device uploads are not allowed inside the capture
   if ((s = reserve_target(c, c->cfg.n_mc))) return s;
-  if (c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on && c->cfg.n_mc <= 4096 && !c->idx_src && !switches().no_fused_loop) {
+  if (mf_diag_loop_ok(c) && !c->idx_src && !switches().no_fused_loop) {
     // rows are independent for this family / target pair: all `count` estimates run inside ONE launch (every workgroup
     // keeps its four rows and walks the estimate indices), the value partials are reduced by a second launch
-    const size_t hist_doubles = (size_t)count * 4 * (size_t)((c->cfg.d + 3) / 4);
-    const size_t lane_bytes = (size_t)mf_loop_lanes(c, count) * 2 * (size_t)c->cfg.d * c->esize;   // the estimate lanes' gradient scratch
-    if ((s = ensure(c, c->X, ((size_t)count + hist_doubles + 8) * sizeof(double) + lane_bytes, false))) return s;
-    double *rec = (double *)c->X.p;
-    launch_mf_sgd_loop(c, const_cast<void *>(params), nullptr, idx0, 0, count, -1, 0.0, (double)NAN, rec + count, rec, grad,
-                       (void *)(rec + count + hist_doubles + 8), value);   // (the value kernel also leaves the last estimate's objective value: no launch of its own)
+    if ((s = ensure(c, c->X, mf_est_loop_scratch_doubles(c, count) * sizeof(double), false))) return s;
+    const MfEstScratch w = mf_est_loop_carve(c, c->X.p, count);
+    launch_mf_sgd_loop(c, const_cast<void *>(params), nullptr, idx0, 0, count, -1, 0.0, (double)NAN, w.hist, w.elbo, grad, w.lanes,
+                       value);   // (the value kernel also leaves the last estimate's objective value: no launch of its own)
     HIPCHK(c, hipGetLastError());
     return MIVI_OK;
   }
-  if (c->cfg.family == MIVI_MEANFIELD && c->target == TGT_FUNNEL && !c->funnel_constrained && !c->bij_on && c->cfg.n_mc <= 256 && !c->idx_src &&
-      !switches().no_fused_loop) {
+  if (mf_funnel_loop_ok(c) && !c->idx_src && !switches().no_fused_loop) {
     // fused funnel target (BASELINE config 5): the cross-row sums enter row 0 and ell linearly, so the batch is launch-free too --
     // per-estimate partials to a history buffer, one finishing workgroup per estimate (k_mf_funnel_loop / _value)
-    const size_t d4 = (size_t)((c->cfg.d + 3) / 4);
-    const size_t nd = (size_t)count * 6 * d4 + (size_t)count + 8;
-    const size_t sc_bytes = ((size_t)count * ((size_t)c->cfg.d + 2) * c->esize + 63) & ~(size_t)63;
-    const size_t lane_bytes = (size_t)mf_loop_lanes(c, count) * 2 * (size_t)c->cfg.d * c->esize;   // the estimate lanes' gradient scratch
-    const size_t lane_al = (lane_bytes + 63) & ~(size_t)63;
-    const size_t e0_bytes = (size_t)count * (size_t)c->cfg.n_mc * c->esize;   // eps[0, m] of every estimate, shared by the row quads
-    if ((s = ensure(c, c->X, nd * sizeof(double) + sc_bytes + lane_al + e0_bytes + 64, false))) return s;
-    double *hist = (double *)c->X.p, *elbo = hist + (size_t)count * 6 * d4;
-    void *scratch = (void *)(elbo + count + 8);
-    launch_mf_funnel_loop(c, params, idx0, count, hist, elbo, scratch, value, grad, (void *)((char *)scratch + sc_bytes),
-                          (void *)((char *)scratch + sc_bytes + lane_al));
+    if ((s = ensure(c, c->X, mf_funnel_loop_scratch_doubles(c, count) * sizeof(double), false))) return s;
+    const MfEstScratch w = mf_funnel_loop_carve(c, c->X.p, count);
+    launch_mf_funnel_loop(c, params, idx0, count, w.hist, w.elbo, w.sc, value, grad, w.lanes, w.e0);
     HIPCHK(c, hipGetLastError());
     return MIVI_OK;
   }
@@ -340,6 +329,7 @@ int32_t mivi_batch_info(const mivi_ctx_t *c, const void *params, int32_t what) {
   if (what == 4) return c->graph_records;
   if (what == 5) return live_allocations();
   if (what == 6) return live_handles();
+  if (what == 7) return c->last_loop;
   return (what == 0 && params && fb_route(c, params, nullptr, nullptr)) ? 1 : 0;
 }
 

@@ -89,7 +89,6 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   if (l.op == 2)
     if (mivi_status_t rs = refuse_lowrank(c, "mivi_optimize_loop with op = 2 (the reference has no ProximalLocationScaleEntropy method for it)")) return rs;
   const bool dog = rule == 2 || rule == 3;        // the rules with two global norms per step
-  const bool loops_know = rule <= 3;              // the launch-free loops implement rules 0..3; COCOB (4) runs on the graph of launches
   if (!graph_capturable(c)) return fail(c, MIVI_ERR_UNSUPPORTED, "device-resident loop needs a built-in target");
   if (c->idx_src) return fail(c, MIVI_ERR_UNSUPPORTED, "an index source is set (mivi_set_index_source): the device-resident loop keeps its own counter");
   (void)hipSetDevice(c->cfg.device);
@@ -98,112 +97,34 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   if (!prepare_tables(c, c->cfg.n_mc)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
   if ((s = reserve_target(c, c->cfg.n_mc))) return s;
   const size_t plen = (size_t)mivi_params_len(c), es = c->esize;
-  const double eta = l.eta, clip_eps = (l.op == 1) ? l.clip_epsilon : (double)NAN;   // NaN = no ClipScale
+  const double eta = l.eta, clip_eps = loop_clip_eps(l);
   void *opt_state = l.opt_state_dev;
-  // internal value/grad/elbo-record buffers
-  size_t hist_doubles = (size_t)n_steps * 4 * (size_t)((c->cfg.d + 3) / 4);
-  {   // (the funnel loop: six partials per row quad and step, every step's set at addresses of its own, 128-byte aligned)
-    const size_t fh = (size_t)n_steps * ((6 * (size_t)((c->cfg.d + 3) / 4) + 15) / 16 * 16) + 16 + (size_t)((c->cfg.d + 3) / 4) / 2 + 8;   // (+ the arrival flags, the published row)
-    if (hist_doubles < fh) hist_doubles = fh;
-  }
-  if ((s = ensure(c, c->X, (plen + 8) * es + ((size_t)n_steps + hist_doubles + 8) * sizeof(double), false))) return s;
+  // internal value / grad / elbo-record buffers, and the hist / partials area: the largest any launch-free loop asks for, whichever runs
+  size_t area_doubles = 0;
+  for (const DeviceLoop &row : kDeviceLoops)
+    if (row.hist_doubles && area_doubles < row.hist_doubles(c, n_steps)) area_doubles = row.hist_doubles(c, n_steps);
+  if ((s = ensure(c, c->X, (plen + 8) * es + ((size_t)n_steps + area_doubles + 8) * sizeof(double), false))) return s;
   char *vbuf = (char *)c->X.p;
   char *gbuf = vbuf + 8 * es;
   double *rec = (double *)(((uintptr_t)(gbuf + plen * es) + 7) & ~(uintptr_t)7);
-  const bool no_fused_loop = switches().no_fused_loop || c->cfg.family == MIVI_LOWRANK || c->base != MIVI_BASE_NORMAL;   // (the low-rank family, a non-normal base: the graph of launches only)
+  const LoopBufs b{vbuf, gbuf, rec, rec + n_steps};
   const bool simple = rule <= 1 && l.op <= 1 && l.averager == 0;   // what the fused paths implement
-  const bool default_adam = l.beta1 == 0.9 && l.beta2 == 0.999 && l.adam_eps == 1e-8;
-  if (simple && (rule == 0 || default_adam) && c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on &&
-      c->cfg.n_mc <= 4096 && !no_fused_loop) {   // (the launch-free kernel has no Stacked-bijector handling: explicit-sample route)
-    // launch-free loop: every workgroup owns four rows of (mu, sigma); no graph, two launches for all n_steps
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));   // (every word read_status folds in: a stale flag of an
-    launch_mf_sgd_loop(c, params, opt_state, l.estimate_idx0, (long long)l.t0, n_steps, rule, eta, clip_eps, rec + n_steps, rec);   //  earlier batch's child contexts is not this run's)
-    HIPCHK(c, hipGetLastError());
-    if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
-    return read_status(c);
-  }
-  if (loops_know && lr_small_loop_ok(c) && !no_fused_loop && allow_exchange) {
-    // small hierarchical logistic regressions (the reference README's own example, BASELINE configs[0]): the whole loop in ONE workgroup, every
-    // rule x operator x averager (k_lr_small_loop); larger ones: up to 64 workgroups that exchange partial sums every step
-    if (lr_small_part_bytes(c, n_steps) && (s = ensure(c, c->gen_scratch, lr_small_part_bytes(c, n_steps) + 256, false))) return s;
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));
-    if (launch_lr_small_loop(c, params, l, rec, vbuf, (double *)c->gen_scratch.p)) {
-      *used_exchange = true;
+  const bool general = loop_general(l);
+  c->last_loop = LOOP_GRAPH;
+  if (!no_device_loops(c))
+    for (const DeviceLoop &row : kDeviceLoops) {
+      const bool exchanges = rule >= row.exchanges_from;
+      if (!row.takes(c, l, general) || (exchanges && !allow_exchange)) continue;
+      if (row.reserve && (s = row.reserve(c, l))) return s;
+      // every word read_status folds in: a stale flag of an earlier batch's child contexts is not this run's
+      HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));
+      if (!row.launch(c, params, l, b)) continue;   // (not launched: the next row)
+      c->last_loop = row.id;
+      if (exchanges) *used_exchange = true;
       HIPCHK(c, hipGetLastError());
       if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
       return read_status(c);
     }
-  }
-  const bool general = !simple || (rule == 1 && !default_adam);   // (Adam with other betas than the fused paths' defaults: the general loops take them from the call)
-  if (general && loops_know && mf_gen_loop_ok(c, rule) && !no_fused_loop && (rule < 2 || allow_exchange)) {
-    // every other rule x operator x averager of the reference's algorithms (DoG / DoWG, ProximalLocationScaleEntropy, PolynomialAveraging -- its
-    // defaults), mean-field + diagonal-Gaussian target: launch-free as well (k_mf_gen_loop; DoG / DoWG: one grid-wide exchange of two norms per step)
-    if ((s = ensure(c, c->gen_scratch, mf_gen_loop_scratch_bytes(c, n_steps), false))) return s;
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));
-    if (launch_mf_gen_loop(c, params, l, rec + n_steps, rec, (char *)c->gen_scratch.p)) {
-      if (rule >= 2) *used_exchange = true;
-      HIPCHK(c, hipGetLastError());
-      if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
-      return read_status(c);
-    }
-  }
-  if (general && loops_know && fr_small_loop_ok(c) && !no_fused_loop) {
-    // ... and small full-rank problems in one workgroup (k_fr_small_loop: the two norms of DoG / DoWG are block sums there)
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));
-    launch_fr_small_loop(c, params, opt_state, l.estimate_idx0, (long long)l.t0, n_steps, rule, eta, clip_eps, rec, vbuf, &l);
-    HIPCHK(c, hipGetLastError());
-    if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
-    return read_status(c);
-  }
-  if (general && loops_know && fr_rows_loop_ok(c) && (rule < 2 || allow_exchange) && !no_fused_loop && fr_rows_eps_bytes(c, n_steps) <= ((size_t)1 << 31)) {
-    // ... and on the full-rank family with few samples per step (the reference's default n_samples = 1): the row-owning workgroups of
-    // k_fr_rows_loop, DoG / DoWG with the same per-step exchange of two norm partials (every workgroup resident: checked by the launcher)
-    if ((s = ensure(c, c->rows_eps, fr_rows_eps_bytes(c, n_steps), false))) return s;
-    if (rule >= 2 && (s = ensure(c, c->gen_scratch, fr_rows_part_bytes(c, n_steps) + 256, false))) return s;
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));
-    if (launch_fr_rows_loop(c, params, opt_state, l.estimate_idx0, (long long)l.t0, n_steps, rule, eta, clip_eps, (float *)c->rows_eps.p, rec + n_steps, rec, vbuf, &l,
-                            (double *)c->gen_scratch.p)) {
-      if (rule >= 2) *used_exchange = true;
-      HIPCHK(c, hipGetLastError());
-      if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
-      return read_status(c);
-    }
-  }
-  if (simple && (rule == 0 || default_adam) && fr_small_loop_ok(c) && !no_fused_loop) {
-    // small full-rank problems (the reference's own benchmark grid: d = 10, one sample per step): the whole loop in ONE workgroup
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));
-    launch_fr_small_loop(c, params, opt_state, l.estimate_idx0, (long long)l.t0, n_steps, rule, eta, clip_eps, rec, vbuf);
-    HIPCHK(c, hipGetLastError());
-    if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
-    return read_status(c);
-  }
-  if (simple && (rule == 0 || default_adam) && fr_rows_loop_ok(c) && !no_fused_loop && fr_rows_eps_bytes(c, n_steps) <= ((size_t)1 << 31)) {
-    // full-rank family, few samples per step, elementwise target: the rows are independent -- every workgroup keeps its rows' parameters and
-    // optimiser state in registers for all n_steps (k_fr_rows_loop); eps of the whole call is drawn up front
-    if ((s = ensure(c, c->rows_eps, fr_rows_eps_bytes(c, n_steps), false))) return s;
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));
-    if (launch_fr_rows_loop(c, params, opt_state, l.estimate_idx0, (long long)l.t0, n_steps, rule, eta, clip_eps, (float *)c->rows_eps.p, rec + n_steps, rec, vbuf)) {
-      HIPCHK(c, hipGetLastError());
-      if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
-      return read_status(c);
-    }
-  }
-  if (simple && (rule == 0 || default_adam) && c->cfg.family == MIVI_MEANFIELD && c->target == TGT_FUNNEL && !c->funnel_constrained && !c->bij_on &&
-      c->cfg.n_mc <= 256 && c->cfg.d <= 16384 && !no_fused_loop && allow_exchange) {
-    // launch-free loop for the fused funnel target: the row quads and the row-0 workgroup of ONE kernel exchange two scalars per workgroup and
-    // row 0's parameters per step (k_mf_funnel_sgd_loop) instead of three launches per step
-    double *hist = (double *)(((uintptr_t)(rec + n_steps) + 127) & ~(uintptr_t)127);
-    const size_t nq = (size_t)((c->cfg.d + 3) / 4);
-    void *pub = (void *)(rec + n_steps + hist_doubles - (nq / 2 + 8));
-    unsigned *sync = (unsigned *)((double *)pub + 4);
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, sizeof(int) * (1 + mivi_ctx::kMaxKids), c->stream));
-    if (launch_mf_funnel_sgd_loop(c, params, opt_state, l.estimate_idx0, (long long)l.t0, n_steps, rule, eta, clip_eps, hist, sync, pub, gbuf, rec, vbuf)) {
-      *used_exchange = true;
-      HIPCHK(c, hipGetLastError());
-      if ((s = deliver_elbo(c, rec, n_steps, l.elbo_dev))) return s;
-      return read_status(c);
-    }
-  }
   // every other configuration: the steps as a graph of launches, recorded once per loop configuration
   auto record_steps = [&]() -> mivi_status_t {
     mivi_status_t s = MIVI_OK;
@@ -320,7 +241,7 @@ mivi_status_t mivi_optimize_loop(mivi_ctx_t *c, void *params, const mivi_loop_t 
 }
 
 // Whole steps of a SubsampledObjective (src/algorithms/subsampledobjective.jl:64-90) on the device: the loop above over the batches
-// first_batch, first_batch + 1, ... of the resident schedule.  A scheduled context takes no launch-free loop (lr_small_loop_ok sees the
+// first_batch, first_batch + 1, ... of the resident schedule.  A scheduled context takes no launch-free loop (lr_small_loop_takes sees the
 // schedule), so this is the graph of launches with the batch of every step baked in (record_steps).
 mivi_status_t mivi_optimize_loop_batches(mivi_ctx_t *c, void *params, const mivi_loop_t *lp, int32_t first_batch) {
   if (!c || !params || !lp) return MIVI_ERR_BAD_ARG;

@@ -50,8 +50,7 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
   if (which == 5) {   // the launch-free loop of 100 estimates (mean-field + diagonal target): one launch per rep
     const bool fn5 = !fr && c->target == TGT_FUNNEL && !c->funnel_constrained;
     if (fr || (c->target != TGT_DIAG_GAUSS && !fn5) || c->bij_on || M > 4096) return fail(c, MIVI_ERR_UNSUPPORTED, "which = 5: mean-field + diagonal-Gaussian / fused funnel target, no bijector");
-    if ((s = ensure(c, c->X, ((size_t)100 + 600 * (size_t)((c->cfg.d + 3) / 4) + 16) * sizeof(double) + 100 * ((size_t)c->cfg.d + 2) * c->esize + 64 +
-                              32 * 2 * (size_t)c->cfg.d * c->esize + 64 + 100 * (size_t)M * c->esize + 64, false))) return s;   // (+ the estimate lanes' gradient scratch, + the funnel loop's eps[0, m] table)
+    if ((s = ensure(c, c->X, (fn5 ? mf_funnel_loop_scratch_doubles(c, 100) : mf_est_loop_scratch_doubles(c, 100)) * sizeof(double), false))) return s;
   } else if (which != 0 && which != 8 && which != 9) {
     if (!fr && which != 2) return fail(c, MIVI_ERR_UNSUPPORTED, "mean-field has a single fused kernel (which = 2)");
     if (which == 4 && c->target != TGT_DENSE_GAUSS) return fail(c, MIVI_ERR_UNSUPPORTED, "no dense target set");
@@ -94,16 +93,12 @@ mivi_status_t mivi_profile_kernel(mivi_ctx_t *c, int32_t which, const void *para
         break;
       case 5:
         if (c->target == TGT_FUNNEL) {
-          const size_t d4 = (size_t)((c->cfg.d + 3) / 4);
-          double *hist = (double *)c->X.p, *elbo = hist + 600 * d4;
-          char *sc = (char *)(elbo + 108);
-          char *ls = sc + ((100 * ((size_t)c->cfg.d + 2) * c->esize + 63) & ~(size_t)63);
-          launch_mf_funnel_loop(c, params, (uint64_t)r * 100, 100, hist, elbo, (void *)sc, o, o + 16, (void *)ls,
-                                (void *)(ls + ((32 * 2 * (size_t)c->cfg.d * c->esize + 63) & ~(size_t)63)));
-          break;
+          const MfEstScratch w = mf_funnel_loop_carve(c, c->X.p, 100);
+          launch_mf_funnel_loop(c, params, (uint64_t)r * 100, 100, w.hist, w.elbo, w.sc, o, o + 16, w.lanes, w.e0);
+        } else {
+          const MfEstScratch w = mf_est_loop_carve(c, c->X.p, 100);
+          launch_mf_sgd_loop(c, const_cast<void *>(params), nullptr, (uint64_t)r * 100, 0, 100, -1, 0.0, (double)NAN, w.hist, w.elbo, o + 16, w.lanes);
         }
-        launch_mf_sgd_loop(c, const_cast<void *>(params), nullptr, (uint64_t)r * 100, 0, 100, -1, 0.0, (double)NAN, (double *)c->X.p + 100,
-                           (double *)c->X.p, o + 16, (void *)((double *)c->X.p + 100 + 400 * (size_t)((c->cfg.d + 3) / 4) + 8));
         break;
       default:
         if (lds && lds_use_prod32(c, M)) {

@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256) void k_fr_rows_value(int d, int nwg, int M_loc
   }
 }
 
-bool fr_rows_loop_ok(const mivi_ctx *c) {
+static bool fr_rows_loop_ok(const mivi_ctx *c) {
   const int d = c->cfg.d, M = c->cfg.n_mc;
   const bool stl = c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD;
   if (!(c->cfg.family == MIVI_FULLRANK && c->cfg.dtype == MIVI_F32 && c->target == TGT_DIAG_GAUSS && !c->bij_on && !stl && M >= 1 && M <= kRowsMaxM &&
@@ -445,15 +445,22 @@ bool fr_rows_loop_ok(const mivi_ctx *c) {
   // two rows' threads fit 128 (d <= 1126); the slab fits the LDS beside the exchange areas; 16-byte slab copies
   return d >= 8 && d <= 126 * kRowsEPT - 8 && ((long long)d * Mp) % 4 == 0 && (size_t)d * Mp * 4 + (8 * kRowsMaxM + 32 + 2 * 256 + 32) * 4 <= c->lds_max;
 }
-size_t fr_rows_eps_bytes(const mivi_ctx *c, int n_steps) { return (size_t)n_steps * c->cfg.d * rows_mp(rows_mm(c->cfg.n_mc)) * sizeof(float); }
-size_t fr_rows_hist_doubles(const mivi_ctx *c, int n_steps) { return (size_t)n_steps * 4 * (size_t)((c->cfg.d + 3) / 4); }
+static size_t fr_rows_eps_bytes(const mivi_ctx *c, int n_steps) { return (size_t)n_steps * c->cfg.d * rows_mp(rows_mm(c->cfg.n_mc)) * sizeof(float); }
+static size_t fr_rows_hist_doubles(const mivi_ctx *c, int n_steps) { return (size_t)n_steps * 4 * (size_t)((c->cfg.d + 3) / 4); }
+static size_t fr_rows_part_bytes(const mivi_ctx *c, int n_steps) { return (size_t)n_steps * (size_t)((c->cfg.d + 3) / 4) * 2 * sizeof(double); }
+static bool fr_rows_loop_takes(const mivi_ctx *c, const mivi_loop_t &l, bool) {
+  return l.rule <= 3 && fr_rows_loop_ok(c) && fr_rows_eps_bytes(c, l.n_steps) <= ((size_t)1 << 31);
+}
+// eps of the whole call is drawn up front (c->rows_eps); DoG / DoWG: the two norm partials of every step (c->gen_scratch)
+static mivi_status_t fr_rows_loop_reserve(mivi_ctx *c, const mivi_loop_t &l) {
+  if (mivi_status_t s = ensure(c, c->rows_eps, fr_rows_eps_bytes(c, l.n_steps), false)) return s;
+  return l.rule >= 2 ? ensure(c, c->gen_scratch, fr_rows_part_bytes(c, l.n_steps) + 256, false) : MIVI_OK;
+}
 
 // eps_all: fr_rows_eps_bytes; hist: fr_rows_hist_doubles; elbo: n_steps doubles; value: one float (the last step's objective value)
-size_t fr_rows_part_bytes(const mivi_ctx *c, int n_steps) { return (size_t)n_steps * (size_t)((c->cfg.d + 3) / 4) * 2 * sizeof(double); }
-
 // gen: the general loop's description (rules / operators / averager beyond Descent / Adam + ClipScale; part: fr_rows_part_bytes) or nullptr
-bool launch_fr_rows_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta, double clip_eps,
-                         float *eps_all, double *hist, double *elbo, void *value, const mivi_loop_t *gen, double *part) {
+static bool fr_rows_loop_impl(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta, double clip_eps,
+                              float *eps_all, double *hist, double *elbo, void *value, const mivi_loop_t *gen, double *part) {
   const int d = c->cfg.d, M = c->cfg.n_mc, d4 = (d + 3) / 4, MM = rows_mm(M), Mp = rows_mp(MM);
   {
     const long long n = (long long)n_steps * d4 * Mp;
@@ -526,5 +533,13 @@ bool launch_fr_rows_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t id
                      (float *)value, n_steps, (int *)c->status.p);
   return true;
 }
+// The kernel's description of the rule is the call's for the general class (loop_general), which also hands it the partials area, and the
+// fused paths' defaults otherwise (a fast-class call with op = 1 and a NaN clip_epsilon runs with op = 0).
+static bool launch_fr_rows_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b) {
+  const bool gen = loop_general(l);
+  return fr_rows_loop_impl(c, params, l.opt_state_dev, l.estimate_idx0, (long long)l.t0, l.n_steps, l.rule, l.eta, loop_clip_eps(l), (float *)c->rows_eps.p, b.area, b.rec,
+                           b.value, gen ? &l : nullptr, gen ? (double *)c->gen_scratch.p : nullptr);
+}
+DeviceLoop loop_fr_rows() { return {LOOP_FR_ROWS, fr_rows_loop_takes, 2, fr_rows_loop_reserve, fr_rows_hist_doubles, launch_fr_rows_loop}; }
 
 }  // namespace mivi

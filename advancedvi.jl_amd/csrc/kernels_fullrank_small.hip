@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void k_fr_small_loop(FrSmallLoopArgs<T> a) {
 // Where ONE workgroup beats the graph of launches (tools/small_loop_bench.py, us per step, this loop / the graph): d x n_mc = 10 x 1: 2.3 / 8.8
 // (STL 3.9 / 17.2), 16 x 32: 4.9 / 9.0 (STL 15.5 / 18.5), 32 x 16: 6.3 / 9.7 (STL 17.2 / 19.0), 10 x 64: 7.2 / 9.1 (STL 20.4 / 19.1),
 // 32 x 32: 10.0 / 9.6, 32 x 64: 17.8 / 9.9 -- the single workgroup's time grows with d x n_mc, a launch's hardly does.
-bool fr_small_loop_ok(const mivi_ctx *c) {
+static bool fr_small_loop_ok(const mivi_ctx *c) {
   const bool stl = c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD;
   const long long dm = (long long)c->cfg.d * c->cfg.n_mc;
   return c->cfg.family == MIVI_FULLRANK && c->target == TGT_DIAG_GAUSS && !c->bij_on && c->cfg.d <= kSmallD && c->cfg.n_mc <= kSmallM &&
@@ -279,10 +279,14 @@ static void fr_small_loop_impl(mivi_ctx *c, void *params, void *opt_state, uint6
   else if (rule == 2) hipLaunchKernelGGL((k_fr_small_loop<T, 2>), dim3(1), dim3(256), 0, c->stream, a);
   else hipLaunchKernelGGL((k_fr_small_loop<T, 3>), dim3(1), dim3(256), 0, c->stream, a);
 }
-// rule 0 Descent / 1 Adam (default betas); elbo: n_steps doubles; value: one element of T
-void launch_fr_small_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta,
-                          double clip_eps, double *elbo, void *value, const mivi_loop_t *gen) {
-  by_dtype(c, [&](auto t) { fr_small_loop_impl<decltype(t)>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, elbo, value, gen); });
+static bool fr_small_loop_takes(const mivi_ctx *c, const mivi_loop_t &l, bool) { return l.rule <= 3 && fr_small_loop_ok(c); }
+// The whole loop in ONE workgroup (the two norms of DoG / DoWG are block sums there).  The kernel's description of the rule is the call's
+// for the general class (loop_general) and the fused paths' defaults otherwise (a fast-class call with op = 1 and a NaN clip_epsilon runs with op = 0).
+static bool launch_fr_small_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b) {
+  const mivi_loop_t *gen = loop_general(l) ? &l : nullptr;
+  by_dtype(c, [&](auto t) { fr_small_loop_impl<decltype(t)>(c, params, l.opt_state_dev, l.estimate_idx0, (long long)l.t0, l.n_steps, l.rule, l.eta, loop_clip_eps(l), b.rec, b.value, gen); });
+  return true;
 }
+DeviceLoop loop_fr_small() { return {LOOP_FR_SMALL, fr_small_loop_takes, kExchangesNever, nullptr, nullptr, launch_fr_small_loop}; }
 
 }  // namespace mivi

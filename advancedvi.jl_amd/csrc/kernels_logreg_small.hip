@@ -470,13 +470,13 @@ static size_t lr_small_lds(const mivi_ctx *c, int G, bool resident, int *ldx_out
   b += ((size_t)nloc + 15) & ~(size_t)15;   // y
   return b;
 }
-size_t lr_small_part_bytes(const mivi_ctx *c, int n_steps) {
+static size_t lr_small_part_bytes(const mivi_ctx *c, int n_steps) {
   const int G = lr_small_groups(c);
   if (G <= 1) return 0;
   const size_t ps = (((size_t)(c->cfg.d - 1) * c->cfg.n_mc + c->cfg.n_mc) + 15) & ~(size_t)15;
   return (size_t)n_steps * G * ps * sizeof(double);
 }
-bool lr_small_loop_ok(const mivi_ctx *c) {
+static bool lr_small_loop_ok(const mivi_ctx *c) {
   const int d = c->cfg.d, M = c->cfg.n_mc;
   const bool stl = c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD;
   if (!(c->target == TGT_LOGREG && !c->bij_on && !stl && d >= 2 && d <= kLrSmallD && M >= 1 && M <= kLrSmallM && c->cfg.m_offset == 0 && c->M_total == M &&
@@ -547,9 +547,16 @@ static bool lr_small_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, 
   }
   return launched;
 }
-// elbo: n_steps doubles; value: one element of T (the last step's objective value)
-bool launch_lr_small_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, double *elbo, void *value, double *part) {
-  return by_dtype(c, [&](auto t) { return lr_small_loop_impl<decltype(t)>(c, params, l, elbo, value, part); });
+static bool lr_small_loop_takes(const mivi_ctx *c, const mivi_loop_t &l, bool) { return l.rule <= 3 && lr_small_loop_ok(c); }
+static mivi_status_t lr_small_loop_reserve(mivi_ctx *c, const mivi_loop_t &l) {   // (0 bytes: one workgroup, no exchange)
+  const size_t pb = lr_small_part_bytes(c, l.n_steps);
+  return pb ? ensure(c, c->gen_scratch, pb + 256, false) : MIVI_OK;
 }
+// Small hierarchical logistic regressions (the reference README's own example): the whole loop in ONE workgroup, every rule x operator x
+// averager; larger ones: up to 64 workgroups that exchange partial sums every step.  elbo: n_steps doubles; value: one element of T
+static bool launch_lr_small_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b) {
+  return by_dtype(c, [&](auto t) { return lr_small_loop_impl<decltype(t)>(c, params, l, b.rec, b.value, (double *)c->gen_scratch.p); });
+}
+DeviceLoop loop_lr_small() { return {LOOP_LR_SMALL, lr_small_loop_takes, 0, lr_small_loop_reserve, nullptr, launch_lr_small_loop}; }
 
 }  // namespace mivi

@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void k_mf_loop_value(int d, int nblk, int M_lo
 // work in flight (a row-quad's workgroup is 4 waves -- or ONE for the funnel shard with n_mc <= 64 -- on a chip of 1024 SIMDs), at most 32,
 // at most n_steps.  Measured (C2 / C5, estimates per second): 1 lane 0.86 M / 0.62 M, 4 / 8 lanes 1.22 M / 1.62 M, 8 / 16: 1.34 M / 1.69 M,
 // 16 / 32: 1.38 M / 1.71 M.
-int mf_loop_lanes(const mivi_ctx *c, int n_steps) {
+static int mf_loop_lanes(const mivi_ctx *c, int n_steps) {
   const int d4 = (c->cfg.d + 3) / 4;
   const int waves = (c->target == TGT_FUNNEL && c->cfg.n_mc <= 64) ? 1 : 4;
   int e = 16384 / (d4 * waves > 0 ? d4 * waves : 1);
@@ -743,15 +743,20 @@ __global__ __launch_bounds__(256) void k_mf_gen_loop(MfGenLoopArgs<T> a) {
   if (RULE >= 2 && rq == 0 && tid == 0) { a.dog_sc[0] = dog_v; a.dog_sc[1] = dog_r; }
 }
 
-bool mf_gen_loop_ok(const mivi_ctx *c, int rule) {
-  if (!(c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on && c->cfg.n_mc <= 4096)) return false;
+// (the launch-free kernels have no Stacked-bijector handling: explicit-sample route)
+bool mf_diag_loop_ok(const mivi_ctx *c) { return c->cfg.family == MIVI_MEANFIELD && c->target == TGT_DIAG_GAUSS && !c->bij_on && c->cfg.n_mc <= 4096; }
+static size_t mf_loop_hist_doubles(const mivi_ctx *c, int n_steps) { return (size_t)n_steps * 4 * (size_t)((c->cfg.d + 3) / 4); }
+static bool mf_sgd_loop_takes(const mivi_ctx *c, const mivi_loop_t &, bool general) { return !general && mf_diag_loop_ok(c); }
+static bool mf_gen_loop_takes(const mivi_ctx *c, const mivi_loop_t &l, bool general) {
+  if (!(general && l.rule <= 3 && mf_diag_loop_ok(c))) return false;
   // DoG / DoWG: a grid-wide exchange per step -- every workgroup resident (f32: six one-wave-per-SIMD workgroups fit a CU, f64: three)
-  return rule <= 1 || c->cfg.d <= (c->cfg.dtype == MIVI_F32 ? 4096 : 2048);
+  return l.rule <= 1 || c->cfg.d <= (c->cfg.dtype == MIVI_F32 ? 4096 : 2048);
 }
-size_t mf_gen_loop_scratch_bytes(const mivi_ctx *c, int n_steps) {   // partial norms of every step
+static size_t mf_gen_loop_scratch_bytes(const mivi_ctx *c, int n_steps) {   // partial norms of every step
   const size_t nblk = (size_t)(c->cfg.d + 3) / 4;
   return (size_t)n_steps * nblk * 2 * sizeof(double) + 256;
 }
+static mivi_status_t mf_gen_loop_reserve(mivi_ctx *c, const mivi_loop_t &l) { return ensure(c, c->gen_scratch, mf_gen_loop_scratch_bytes(c, l.n_steps), false); }
 
 template <typename T>
 static bool mf_gen_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, double *hist, double *elbo, char *scratch) {
@@ -785,11 +790,12 @@ static bool mf_gen_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, do
                      (int *)c->status.p);
   return true;
 }
-// hist: n_steps * 4 * ceil(d / 4) doubles; elbo: n_steps doubles; scratch: mf_gen_loop_scratch_bytes.  false: not launched (the device cannot hold the
+// hist: mf_loop_hist_doubles; elbo: n_steps doubles; scratch: mf_gen_loop_scratch_bytes.  false: not launched (the device cannot hold the
 // exchanging grid at once): the caller takes the graph of launches
-bool launch_mf_gen_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, double *hist, double *elbo, char *scratch) {
-  return by_dtype(c, [&](auto t) { return mf_gen_loop_impl<decltype(t)>(c, params, l, hist, elbo, scratch); });
+static bool launch_mf_gen_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b) {
+  return by_dtype(c, [&](auto t) { return mf_gen_loop_impl<decltype(t)>(c, params, l, b.area, b.rec, (char *)c->gen_scratch.p); });
 }
+DeviceLoop loop_mf_gen() { return {LOOP_MF_GEN, mf_gen_loop_takes, 2, mf_gen_loop_reserve, mf_loop_hist_doubles, launch_mf_gen_loop}; }
 
 // rule 0 Descent / 1 Adam: n_steps SGD iterations;  rule -1: n_steps estimates at fixed parameters, the last one's gradient
 // into grad_out (what mivi_estimate_gradient_n returns).  elbo[t] of every step / estimate either way.
@@ -799,6 +805,18 @@ void launch_mf_sgd_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx
   by_dtype(c, [&](auto t) {
     mf_sgd_loop_impl<decltype(t)>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, hist, elbo, grad_out, lane_scratch, value_last);
   });
+}
+// the optimisation loop: every workgroup owns four rows of (mu, sigma); no graph, two launches for all n_steps
+static bool launch_mf_sgd_loop_row(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b) {
+  launch_mf_sgd_loop(c, params, l.opt_state_dev, l.estimate_idx0, (long long)l.t0, l.n_steps, l.rule, l.eta, loop_clip_eps(l), b.area, b.rec);
+  return true;
+}
+DeviceLoop loop_mf_sgd() { return {LOOP_MF_SGD, mf_sgd_loop_takes, kExchangesNever, nullptr, mf_loop_hist_doubles, launch_mf_sgd_loop_row}; }
+// the estimates at fixed parameters (rule -1): [elbo: n][hist: mf_loop_hist_doubles][8][lanes: mf_loop_lanes x 2 d elements]
+static size_t mf_lane_bytes(const mivi_ctx *c, int n) { return (size_t)mf_loop_lanes(c, n) * 2 * (size_t)c->cfg.d * c->esize; }
+size_t mf_est_loop_scratch_doubles(const mivi_ctx *c, int n) { return (size_t)n + mf_loop_hist_doubles(c, n) + 8 + (mf_lane_bytes(c, n) + 7) / 8; }
+MfEstScratch mf_est_loop_carve(const mivi_ctx *c, void *base, int n) {
+  return MfEstScratch{(double *)base + n, (double *)base, nullptr, (void *)((double *)base + n + mf_loop_hist_doubles(c, n) + 8), nullptr};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1012,6 +1030,18 @@ static void mf_funnel_loop_impl(mivi_ctx *c, const void *params, uint64_t idx0, 
 void launch_mf_funnel_loop(mivi_ctx *c, const void *params, uint64_t idx0, int n_steps, double *hist, double *elbo, void *scratch,
                            void *value, void *grad, void *lane_scratch, void *e0_tab) {
   by_dtype(c, [&](auto t) { mf_funnel_loop_impl<decltype(t)>(c, params, idx0, n_steps, hist, elbo, scratch, value, grad, lane_scratch, e0_tab); });
+}
+bool mf_funnel_loop_ok(const mivi_ctx *c) { return c->cfg.family == MIVI_MEANFIELD && c->target == TGT_FUNNEL && !c->funnel_constrained && !c->bij_on && c->cfg.n_mc <= 256; }
+// [hist: n x 6 ceil(d/4)][elbo: n][8][sc: n (d + 2) elements][lanes: mf_loop_lanes x 2 d elements][e0: n x n_mc elements], the last three 64 bytes apart
+static size_t round64(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+static size_t mf_funnel_sc_bytes(const mivi_ctx *c, int n) { return round64((size_t)n * ((size_t)c->cfg.d + 2) * c->esize); }
+size_t mf_funnel_loop_scratch_doubles(const mivi_ctx *c, int n) {
+  return (size_t)n * 6 * (size_t)((c->cfg.d + 3) / 4) + (size_t)n + 8 + (mf_funnel_sc_bytes(c, n) + round64(mf_lane_bytes(c, n)) + (size_t)n * (size_t)c->cfg.n_mc * c->esize + 64 + 7) / 8;
+}
+MfEstScratch mf_funnel_loop_carve(const mivi_ctx *c, void *base, int n) {
+  double *hist = (double *)base, *elbo = hist + (size_t)n * 6 * (size_t)((c->cfg.d + 3) / 4);
+  char *sc = (char *)(elbo + n + 8), *lanes = sc + mf_funnel_sc_bytes(c, n);
+  return MfEstScratch{hist, elbo, (void *)sc, (void *)lanes, (void *)(lanes + round64(mf_lane_bytes(c, n)))};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1342,14 +1372,23 @@ static bool mf_funnel_sgd_loop_impl(mivi_ctx *c, void *params, void *opt_state, 
   }
   return true;
 }
-// n_steps optimisation steps of the fused funnel target in ONE launch (n_mc <= 256).  hist: 128-byte aligned, n_steps * roundup(6 * ceil(d/4), 16) doubles; sync: 2 + ceil(d/4) words;
-// pub: 4 elements of T; gtmp: d + 1 elements of T; elbo: n_steps doubles; value: one element of T (the last step's objective value).
-bool launch_mf_funnel_sgd_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta,
-                               double clip_eps, double *hist, unsigned *sync, void *pub, void *gtmp, double *elbo, void *value) {
+static bool mf_funnel_sgd_loop_takes(const mivi_ctx *c, const mivi_loop_t &, bool general) { return !general && mf_funnel_loop_ok(c) && c->cfg.d <= 16384; }
+// The loop's area: six partials per row quad and step, every step's set at addresses of its own (hstride doubles apart), behind up to 15
+// doubles of alignment; then, cut from the end, the tail of ceil(d/4) / 2 + 8 doubles: pub (4 elements of T in 4 doubles), sync (2 + ceil(d/4) words).
+static size_t mf_funnel_sgd_tail_doubles(const mivi_ctx *c) { return (size_t)((c->cfg.d + 3) / 4) / 2 + 8; }
+static size_t mf_funnel_sgd_scratch_doubles(const mivi_ctx *c, int n) { return (size_t)n * ((6 * (size_t)((c->cfg.d + 3) / 4) + 15) / 16 * 16) + 16 + mf_funnel_sgd_tail_doubles(c); }
+// n_steps optimisation steps of the fused funnel target in ONE launch (instead of three launches per step).  hist: 128-byte aligned; gtmp: d + 1
+// elements of T (the gradient scratch); elbo: n_steps doubles; value: one element of T (the last step's objective value).
+static bool launch_mf_funnel_sgd_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b) {
+  double *hist = (double *)(((uintptr_t)b.area + 127) & ~(uintptr_t)127);
+  void *pub = (void *)(b.area + mf_funnel_sgd_scratch_doubles(c, l.n_steps) - mf_funnel_sgd_tail_doubles(c));
+  unsigned *sync = (unsigned *)((double *)pub + 4);
   return by_dtype(c, [&](auto t) {
-    return mf_funnel_sgd_loop_impl<decltype(t)>(c, params, opt_state, idx0, t0, n_steps, rule, eta, clip_eps, hist, sync, pub, gtmp, elbo, value);
+    return mf_funnel_sgd_loop_impl<decltype(t)>(c, params, l.opt_state_dev, l.estimate_idx0, (long long)l.t0, l.n_steps, l.rule, l.eta, loop_clip_eps(l), hist, sync, pub,
+                                                b.grad, b.rec, b.value);
   });
 }
+DeviceLoop loop_mf_funnel_sgd() { return {LOOP_MF_FUNNEL_SGD, mf_funnel_sgd_loop_takes, 0, nullptr, mf_funnel_sgd_scratch_doubles, launch_mf_funnel_sgd_loop}; }
 
 // rand(rng, q::MvLocationScale{<:Diagonal}, M): Z = mu + sigma .* eps  (location_scale.jl:80-87)
 // lanes run along rows => Z / eps stores are fully coalesced.

@@ -558,6 +558,7 @@ struct mivi_ctx : mivi_ctx_streams {
   size_t lds_max = 64 * 1024;    // exchange per step check their grids against (hipOccupancyMaxActiveBlocksPerMultiprocessor x n_cu >= grid)
   bool exchange_lost = false;    // a grid-wide exchange expired once on this context (status bit 8): those loops are not taken again
   int last_status_bits = 0;      // the sticky device flags read_status saw last
+  int last_loop = 0;             // the DeviceLoopId the last mivi_optimize_loop call ran on, 0: the graph of launches (mivi_batch_info what = 7)
   mivi::DevBuf snap;             // parameters / optimiser state / average before a loop with a grid-wide exchange (restored if it is lost)
   mivi_ctx *kids[kMaxKids] = {};
   int n_kids = 0;
@@ -601,28 +602,47 @@ namespace mivi {
 struct ValueJob;
 void launch_mf_main(mivi_ctx *c, const void *params, const RngArgs &rng, int M, int want_grad, const void *G,
                     const ValueIn &vin, const OutArgs &out, const ValueJob *prev = nullptr);
+// ---- the launch-free loops ------------------------------------------------------------------------------------------------------------
+// mivi_optimize_loop walks kDeviceLoops (api_common.h: one row per launch-free optimisation loop, in priority order; first match).  A row
+// is defined beside its kernel; `takes` is the WHOLE condition of the row apart from the two the dispatcher owns (no_device_loops, and
+// allow_exchange for a row that exchanges).
+enum DeviceLoopId : int { LOOP_GRAPH = 0, LOOP_MF_SGD = 1, LOOP_LR_SMALL = 2, LOOP_MF_GEN = 3, LOOP_FR_SMALL = 4, LOOP_FR_ROWS = 5, LOOP_MF_FUNNEL_SGD = 6 };
+struct LoopBufs {       // what the dispatcher owns (c->X)
+  void *value, *grad;   // the value word (8 elements), the gradient scratch (params_len elements)
+  double *rec, *area;   // the f64 ELBO record (n_steps doubles) and, behind it, the hist / partials area: the largest hist_doubles of the table (+ 8)
+};
+constexpr int kExchangesNever = 1 << 30;
+struct DeviceLoop {
+  int id;
+  bool (*takes)(const mivi_ctx *c, const mivi_loop_t &l, bool general);   // pure host predicate
+  int exchanges_from;                                                     // rules >= this exchange grid-wide every step (0: all, 2: DoG / DoWG -- two global norms)
+  mivi_status_t (*reserve)(mivi_ctx *c, const mivi_loop_t &l);            // the loop's own buffers (rows_eps, gen_scratch); nullptr: none
+  size_t (*hist_doubles)(const mivi_ctx *c, int n_steps);                 // what it needs of LoopBufs::area; nullptr: nothing
+  bool (*launch)(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b);   // false: not launched (an exchanging grid not resident, the LDS refused): the next row
+};
+DeviceLoop loop_mf_sgd(), loop_mf_gen(), loop_mf_funnel_sgd(), loop_fr_small(), loop_fr_rows(), loop_lr_small();   // the rows: kernels_meanfield / _fullrank_small / _fullrank_rows / _logreg_small.hip
+// simple: what the fused paths implement (Descent / Adam, at most ClipScale, no averager); general := !simple || (Adam with other betas than
+// their defaults: the general loops take them from the call).  The fast class is exactly !general: simple && (rule == 0 || default Adam).
+inline bool loop_general(const mivi_loop_t &l) {
+  const bool simple = l.rule <= 1 && l.op <= 1 && l.averager == 0;
+  return !simple || (l.rule == 1 && !(l.beta1 == 0.9 && l.beta2 == 0.999 && l.adam_eps == 1e-8));
+}
+inline double loop_clip_eps(const mivi_loop_t &l) { return l.op == 1 ? l.clip_epsilon : (double)NAN; }   // NaN = no ClipScale
+// kernels_meanfield.hip: the launch-free batches of estimates at FIXED parameters (mivi_estimate_gradient_n, mivi_profile_kernel which = 5) --
+// their predicates (the optimisation loops' too) and the layout of their one scratch buffer, `_scratch_doubles` doubles carved from its base
+bool mf_diag_loop_ok(const mivi_ctx *c);     // mean-field, diagonal-Gaussian target, no Stacked bijector, a bounded n_mc
+bool mf_funnel_loop_ok(const mivi_ctx *c);   // mean-field, fused (unconstrained) funnel target, no Stacked bijector, a bounded n_mc
+struct MfEstScratch { double *hist, *elbo; void *sc, *lanes, *e0; };   // sc, e0: the funnel's finishing scratch and eps[0, m] table; lanes: the estimate lanes' gradients
+size_t mf_est_loop_scratch_doubles(const mivi_ctx *c, int n);
+MfEstScratch mf_est_loop_carve(const mivi_ctx *c, void *base, int n);
+size_t mf_funnel_loop_scratch_doubles(const mivi_ctx *c, int n);
+MfEstScratch mf_funnel_loop_carve(const mivi_ctx *c, void *base, int n);
+// rule 0 Descent / 1 Adam: the optimisation loop (loop_mf_sgd); rule -1: n_steps estimates at fixed parameters
 void launch_mf_sgd_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule,
                         double eta, double clip_eps, double *hist, double *elbo, void *grad_out = nullptr, void *lane_scratch = nullptr,
                         void *value_last = nullptr);   // value_last: the last step's objective value as an element of T (written by the value kernel)
-bool fr_rows_loop_ok(const mivi_ctx *c);    // kernels_fullrank_rows.hip: f32, n_mc <= 32, d <= 1024, diagonal-Gaussian target, not STL
-size_t fr_rows_eps_bytes(const mivi_ctx *c, int n_steps);
-size_t fr_rows_part_bytes(const mivi_ctx *c, int n_steps);
-bool launch_fr_rows_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta, double clip_eps,
-                         float *eps_all, double *hist, double *elbo, void *value, const mivi_loop_t *gen = nullptr, double *part = nullptr);
-bool lr_small_loop_ok(const mivi_ctx *c);   // kernels_logreg_small.hip: the logistic-regression target, d <= 64, (d - 1) n_mc <= 256, n (d - 1) n_mc <= 2^20: one workgroup per 2^14 of them
-size_t lr_small_part_bytes(const mivi_ctx *c, int n_steps);   // 0: one workgroup, no exchange
-bool launch_lr_small_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, double *elbo, void *value, double *part);
-bool mf_gen_loop_ok(const mivi_ctx *c, int rule);   // kernels_meanfield.hip: every rule x operator x averager, mean-field + diagonal-Gaussian target
-size_t mf_gen_loop_scratch_bytes(const mivi_ctx *c, int n_steps);
-bool launch_mf_gen_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, double *hist, double *elbo, char *scratch);
-bool fr_small_loop_ok(const mivi_ctx *c);   // kernels_fullrank_small.hip: d <= 32, n_mc <= 64, diagonal-Gaussian target
-void launch_fr_small_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta,
-                          double clip_eps, double *elbo, void *value, const mivi_loop_t *gen = nullptr);
-bool launch_mf_funnel_sgd_loop(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta,
-                               double clip_eps, double *hist, unsigned *sync, void *pub, void *gtmp, double *elbo, void *value);
 void launch_mf_funnel_loop(mivi_ctx *c, const void *params, uint64_t idx0, int n_steps, double *hist, double *elbo, void *scratch,
                            void *value, void *grad, void *lane_scratch, void *e0_tab = nullptr);
-int mf_loop_lanes(const mivi_ctx *c, int n_steps);   // estimate lanes of the launch-free batches (lane_scratch: lanes * 2 d elements)
 void launch_sample_mf(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *Z, void *eps, int ld_eps,
                       double *he_part);
 

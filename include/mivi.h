@@ -735,7 +735,10 @@ int32_t mivi_batch_lanes(const mivi_ctx_t *ctx, int32_t count);
  * counts them): equal before a context's creation and after its mivi_destroy means the context returned every allocation it made;
  * 6: the number of HIP streams, events and graph execs the library holds right now in this process, over all contexts (the caller's stream
  * is not one of them; every one sits in an owner that counts its creation and its destruction): the same equality means the context
- * destroyed every handle it created, the children's, the exchange pipelines' and the cached graph included. */
+ * destroyed every handle it created, the children's, the exchange pipelines' and the cached graph included;
+ * 7: the route the last mivi_optimize_loop / _batches call on this context ran on -- 0: the graph of launches, else the launch-free loop in
+ * the library's priority order (first match): 1 mean-field Descent / default Adam, 2 small logistic regression, 3 mean-field, every other
+ * rule x operator x averager, 4 small full-rank in one workgroup, 5 full-rank row-owning workgroups, 6 mean-field fused funnel. */
 int32_t mivi_batch_info(const mivi_ctx_t *ctx, const void *params_dev, int32_t what);
 
 /* ---- measurement hook (bench.py roofline leg) --------------------------------------------------------- *
