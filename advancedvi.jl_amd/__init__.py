@@ -16,7 +16,7 @@ from . import objectives as _objectives
 from . import optimize as _optimize
 from .optimize import (KLMinRepGradDescent, KLMinRepGradProxDescent, ADVI, KLMinScoreGradDescent, BBVI, ClipScale, IdentityOperator,
                        ProximalLocationScaleEntropy, Descent, Adam, DoG, DoWG, COCOB, NoAveraging,
-                       PolynomialAveraging, optimize, step, output)
+                       PolynomialAveraging, optimize, step, output, optimize_many, many_plan)
 from .measure_space import KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent, FisherMinBatchMatch, KLMinWassFwdBwd
 from . import measure_space as _measure_space
 from .context import MiviContext, NATGRAD_SMALL_D, BAM_MAX_SAMPLES

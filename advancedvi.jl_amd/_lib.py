@@ -39,6 +39,7 @@ SIGNATURES = {
     "mivi_partials_len": (C.c_int64, [C.c_void_p]),
     "mivi_set_base_dist": (C.c_int32, [C.c_void_p, C.c_int32, C.c_double]),
     "mivi_optimize_loop": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mivi_optimize_loop_many": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mivi_logreg_select_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
     "mivi_logreg_set_batch_schedule": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mivi_logreg_seek_batch": (C.c_int32, [C.c_void_p, C.c_int32]),
@@ -182,6 +183,13 @@ class MiviLoop(C.Structure):
                 ("clip_epsilon", C.c_double), ("avg_eta", C.c_double),
                 ("opt_state_dev", C.c_void_p), ("avg_params_dev", C.c_void_p),
                 ("estimate_idx0", C.c_uint64), ("t0", C.c_int64), ("elbo_dev", C.c_void_p)]
+
+
+class MiviMany(C.Structure):
+    """mivi_many_t (include/mivi.h)"""
+    _fields_ = [("n_runs", C.c_int32), ("seed_host", C.c_void_p), ("estimate_idx0_host", C.c_void_p), ("eta_host", C.c_void_p),
+                ("mean_host", C.c_void_p), ("std_host", C.c_void_p), ("y_dev", C.c_void_p), ("X_dev", C.c_void_p),
+                ("X_run_stride", C.c_int64), ("status_host", C.c_void_p)]
 
 
 class MiviBatchSchedule(C.Structure):

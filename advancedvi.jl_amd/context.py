@@ -38,7 +38,8 @@ class MiviContext:
         self.np_dtype = np.dtype(dtype)
         self.family, self.d, self.n_mc, self.entropy = int(family), int(d), int(n_mc), int(entropy)
         self.device = int(device)
-        self.rank = int(rank)   # columns of scale_factors (the low-rank family; not read for the others)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF   # the Philox seed of every draw of this context
+        self.rank = int(rank)  # columns of scale_factors (the low-rank family; not read for the others)
         self.tdtype = torch_dtype(self.np_dtype)
         self.tdevice = torch.device("cuda", self.device)
         if stream is None:
@@ -795,6 +796,74 @@ class MiviContext:
                           self._p(avg_params) if avg_params is not None else None, int(idx0), int(t0),
                           self._p(elbo) if elbo is not None else None)
         self._chk(self.lib.mivi_optimize_loop(self.h, self._p(params), C.byref(l)))
+
+    def last_loop(self):
+        """The route the last optimize_loop / optimize_loop_many call ran on (mivi_batch_info what = 7): 0 the graph of launches, a
+        launch-free loop's id, or 16 | that id after optimize_loop_many."""
+        return int(self.lib.mivi_batch_info(self.h, None, 7))
+
+    def optimize_loop_many(self, params, n_runs, n_steps, idx0, t0, seeds=None, etas=None, means=None, stds=None, y=None, X=None,
+                           x_stride=0, rule=0, op=0, averager=0, eta=0.0, beta=(0.9, 0.999), adam_eps=1e-8, clip_epsilon=0.0, avg_eta=8.0,
+                           opt_state=None, avg_params=None, elbo=None, want_status=True):
+        """mivi_optimize_loop_many: n_runs independent runs of optimize_loop in one launch, workgroup k = run k.  Run-major device arrays:
+        params [K params_len], opt_state K single-run states, avg_params [K params_len], elbo [K n_steps].  idx0: one first estimate
+        index or K of them; seeds / etas: K values or None (the context's seed, `eta`); means / stds: [K, d] host arrays (diagonal-Gaussian
+        target) or None; y: device uint8 [K n], X: device matrix or K of them x_stride elements apart (logistic regression) or None.
+        Returns the runs' status words (int32[K]: bit 1 non-finite objective, bit 2 non-positive scale); want_status=False: None, and a set
+        bit raises as optimize_loop does."""
+        K = int(n_runs)
+        keep = []
+        torch = _torch()
+
+        def host(a, dt, count, name):   # a per-run host array of EXACTLY `count` entries (the library reads that many)
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != count:
+                raise ValueError(f"optimize_loop_many: {name} holds {a.size} entries, {count} are needed for {K} runs")
+            keep.append(a)
+            return a.ctypes.data
+
+        def dev(t, dt, at_least, name, exact=True):   # a device array of the element type and size the kernel indexes
+            if t is None:
+                return
+            if not isinstance(t, torch.Tensor) or t.device != self.tdevice or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"optimize_loop_many: {name} must be a contiguous {dt} tensor on {self.tdevice}")
+            if (t.numel() != at_least) if exact else (t.numel() < at_least):
+                raise ValueError(f"optimize_loop_many: {name} holds {t.numel()} entries, {at_least} are needed for {K} runs")
+
+        if K >= 1:
+            plen = self.params_len
+            dev(params, self.tdtype, K * plen, "params")
+            dev(avg_params, self.tdtype, K * plen, "avg_params")
+            dev(elbo, self.tdtype, K * int(n_steps), "elbo")
+            if opt_state is not None and int(rule) == 1:
+                dev(opt_state, self.tdtype, 2 * K * plen, "opt_state")
+            elif opt_state is not None and int(rule) in (2, 3):
+                dev(opt_state, torch.uint8, K * int(self.lib.mivi_dog_state_bytes(self.h)), "opt_state")
+            lr = getattr(self, "_lr_full", None)
+            if (y is not None or X is not None) and lr is None:
+                raise ValueError("optimize_loop_many: y / X are for a context with a LogRegProblem")
+            if lr is not None:
+                n, p = lr.n_rows(), self.d - 1
+                dev(y, torch.uint8, K * n, "y")
+                if X is not None and int(x_stride) != 0 and int(x_stride) < n * p:
+                    raise ValueError("optimize_loop_many: x_stride must be 0 (one shared X) or at least n (d - 1)")
+                dev(X, self.tdtype, (K - 1) * int(x_stride) + n * p, "X", exact=False)
+
+        idx_arr = None if np.ndim(idx0) == 0 else idx0
+        status = np.zeros(K, dtype=np.int32) if want_status else None
+        m = _lib.MiviMany(K, host(seeds, np.uint64, K, "seeds"), host(idx_arr, np.uint64, K, "idx0"), host(etas, np.float64, K, "etas"),
+                          host(means, self.np_dtype, K * self.d, "means"), host(stds, self.np_dtype, K * self.d, "stds"),
+                          self._p(y) if y is not None else None, self._p(X) if X is not None else None, int(x_stride),
+                          status.ctypes.data if want_status else None)
+        l = _lib.MiviLoop(int(rule), int(op), int(averager), int(n_steps), float(eta), float(beta[0]), float(beta[1]),
+                          float(adam_eps), float(clip_epsilon), float(avg_eta),
+                          self._p(opt_state) if opt_state is not None else None,
+                          self._p(avg_params) if avg_params is not None else None, int(idx0) if idx_arr is None else 0, int(t0),
+                          self._p(elbo) if elbo is not None else None)
+        self._chk(self.lib.mivi_optimize_loop_many(self.h, self._p(params), C.byref(l), C.byref(m)))
+        return status
 
     # -- a schedule of minibatches resident on the device (the built-in logistic regression) ----------
     def set_batch_schedule(self, rows, estimate_idx=None, likeadj=None, kernels=0):

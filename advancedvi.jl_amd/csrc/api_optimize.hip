@@ -240,6 +240,119 @@ mivi_status_t mivi_optimize_loop(mivi_ctx_t *c, void *params, const mivi_loop_t 
   return s;
 }
 
+// ---- mivi_optimize_loop_many: K independent runs of one shape, workgroup k = run k ---------------------------------------------------------
+// c->many_buf, carved once per call: what the host uploads in ONE copy (the runs' table, their zeroed status words, the diagonal-Gaussian
+// targets of the runs that bring their own), then what the kernel leaves (the f64 ELBO records [K][n_steps], the last values [K]).
+struct ManyLayout {
+  size_t off_status, off_mean, off_istd, up_bytes, off_rec, off_value, bytes;
+};
+static ManyLayout many_layout(const mivi_ctx *c, size_t K, int n_steps, bool own_target) {
+  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  ManyLayout L;
+  L.off_status = up16(K * sizeof(ManyRun));
+  L.off_mean = up16(L.off_status + K * sizeof(int));
+  L.off_istd = up16(L.off_mean + (own_target ? K * (size_t)c->cfg.d * c->esize : 0));
+  L.up_bytes = up16(L.off_istd + (own_target ? K * (size_t)c->cfg.d * c->esize : 0));
+  L.off_rec = L.up_bytes;
+  L.off_value = up16(L.off_rec + K * (size_t)n_steps * sizeof(double));
+  L.bytes = up16(L.off_value + (K + 8) * c->esize);
+  return L;
+}
+
+// `optimize` for K independent small problems of one shape (restarts, step-size sweeps, simulated data sets: K calls of src/optimize.jl:42-94
+// whose steps are src/algorithms/common.jl:69-104, at the sizes of bench/benchmarks.jl:43-94) in one launch.  Everything is validated on the
+// host before anything is uploaded; the rows of kDeviceLoops that have a `launch_many` are the configurations it serves.
+mivi_status_t mivi_optimize_loop_many(mivi_ctx_t *c, void *params, const mivi_loop_t *lp, const mivi_many_t *mp) {
+  if (!c || !params || !lp || !mp) return MIVI_ERR_BAD_ARG;
+  const mivi_loop_t &l = *lp;
+  const mivi_many_t &m = *mp;
+  if (m.n_runs < 1) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_many: n_runs must be at least 1");
+  if (l.n_steps > 0 && (long long)m.n_runs * l.n_steps > (1ll << 30)) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_many: n_runs x n_steps must not exceed 2^30 (call it in chunks of steps)");
+  if (l.n_steps <= 0 || l.rule < 0 || l.rule > 4 || l.op < 0 || l.op > 2 || l.averager < 0 || l.averager > 1) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_many: n_steps, rule, op or averager out of range");
+  if (l.op == 2 && l.rule == 1) return fail(c, MIVI_ERR_BAD_ARG, "ProximalLocationScaleEntropy does not support Adam (Descent, DoG, DoWG: proximal_location_scale_entropy.jl:26-42)");
+  if (l.rule == 4) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: COCOB (rule 4) has no launch-free loop");
+  if (l.rule != 0 && !l.opt_state_dev) return fail(c, MIVI_ERR_BAD_ARG, "this optimisation rule needs opt_state_dev");
+  if (l.averager == 1 && !l.avg_params_dev) return fail(c, MIVI_ERR_BAD_ARG, "PolynomialAveraging needs avg_params_dev");
+  if (c->cfg.family == MIVI_LOWRANK) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: the low-rank family has no launch-free loop");
+  if (c->base != MIVI_BASE_NORMAL) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a non-normal base distribution has no launch-free loop");
+  if (c->bij_on) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a Stacked bijector is set");
+  if (c->cfg.m_offset != 0 || c->M_total != c->cfg.n_mc) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a sharded context (m_offset / m_total)");
+  if (c->lr_sched_n > 0) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a batch schedule is set (mivi_logreg_set_batch_schedule)");
+  if (c->idx_src) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: an index source is set (mivi_set_index_source)");
+  if (switches().no_fused_loop) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: MIVI_NO_FUSED_LOOP=1 keeps the graph of launches, which has no many-run form");
+  const DeviceLoop *row = nullptr;
+  for (const DeviceLoop &r : kDeviceLoops)
+    if (r.launch_many && r.takes_many(c, l)) { row = &r; break; }
+  if (!row)
+    return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: neither a small full-rank run on a diagonal-Gaussian target (d <= 32, n_mc <= 64, d n_mc <= 768; "
+                                         "512 with the sticking-the-landing estimators) nor a small logistic regression that fits one workgroup");
+  const bool gauss = c->target == TGT_DIAG_GAUSS;
+  const size_t K = (size_t)m.n_runs, d = (size_t)c->cfg.d;
+  if ((m.mean_host != nullptr) != (m.std_host != nullptr)) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_many: mean_host and std_host come together");
+  if (!gauss && m.mean_host) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_many: mean_host / std_host are for the diagonal-Gaussian target");
+  if (gauss && (m.y_dev || m.X_dev)) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_many: y_dev / X_dev are for the logistic-regression target");
+  if (m.X_dev && m.X_run_stride != 0 && m.X_run_stride < (int64_t)c->lr_n * (int64_t)(d - 1)) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_many: X_run_stride must be 0 (one shared X) or at least n (d - 1) elements");
+  const bool own_target = gauss && m.mean_host;
+  const ManyLayout L = many_layout(c, K, l.n_steps, own_target);
+  std::vector<char> up(L.up_bytes, 0);
+  ManyRun *runs = (ManyRun *)up.data();
+  for (size_t k = 0; k < K; ++k) {
+    runs[k].seed = m.seed_host ? m.seed_host[k] : c->cfg.seed;
+    runs[k].idx0 = m.estimate_idx0_host ? m.estimate_idx0_host[k] : l.estimate_idx0;
+    runs[k].eta = m.eta_host ? m.eta_host[k] : l.eta;
+    double cst = c->t_const;
+    if (own_target) {   // mivi_set_target_diag_gauss's arithmetic, per run
+      cst = -0.5 * (double)d * kLog2Pi;
+      for (size_t i = 0; i < d; ++i) {
+        const double s = host_get(m.std_host, c->cfg.dtype, k * d + i), mu = host_get(m.mean_host, c->cfg.dtype, k * d + i);
+        if (!(s > 0.0)) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_many: std must be positive");
+        cst -= log(s);
+        if (c->cfg.dtype == MIVI_F64) {
+          ((double *)(up.data() + L.off_mean))[k * d + i] = mu;
+          ((double *)(up.data() + L.off_istd))[k * d + i] = 1.0 / s;
+        } else {
+          ((float *)(up.data() + L.off_mean))[k * d + i] = (float)mu;
+          ((float *)(up.data() + L.off_istd))[k * d + i] = (float)(1.0 / s);
+        }
+      }
+    }
+    runs[k].ell_const = cst;
+  }
+  (void)hipSetDevice(c->cfg.device);
+  mivi_status_t s = ensure(c, c->many_buf, L.bytes, false);
+  if (s) return s;
+  char *base = (char *)c->many_buf.p;
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // (whatever read the buffer last is done: the copy below does not run on the stream)
+  HIPCHK(c, hipMemcpy(base, up.data(), L.up_bytes, hipMemcpyHostToDevice));
+  ManyLaunch ml{};
+  ml.n_runs = m.n_runs;
+  ml.runs = (const ManyRun *)base;
+  ml.status = (int *)(base + L.off_status);
+  ml.t_mean = own_target ? base + L.off_mean : nullptr;
+  ml.t_istd = own_target ? base + L.off_istd : nullptr;
+  ml.y = m.y_dev;
+  ml.X = m.X_dev;
+  ml.x_stride = m.X_dev ? (long long)m.X_run_stride : 0;
+  double *rec = (double *)(base + L.off_rec);
+  const LoopBufs b{base + L.off_value, nullptr, rec, nullptr};
+  c->last_loop = LOOP_GRAPH;
+  if (!row->launch_many(c, params, l, b, ml)) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: the device refused the kernel's LDS");
+  c->last_loop = LOOP_MANY | row->id;
+  HIPCHK(c, hipGetLastError());
+  if ((s = deliver_elbo(c, rec, (int)(K * (size_t)l.n_steps), l.elbo_dev))) return s;
+  std::vector<int> st(K, 0);
+  HIPCHK(c, hipMemcpyAsync(st.data(), ml.status, K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int any = 0;
+  for (size_t k = 0; k < K; ++k) {
+    any |= st[k];
+    if (m.status_host) m.status_host[k] = st[k];
+  }
+  if (m.status_host || !any) return MIVI_OK;
+  if (any & 2) return fail(c, MIVI_ERR_NONPOSITIVE_SCALE, "scale diagonal is not positive in at least one run (use ClipScale)");
+  return fail(c, MIVI_ERR_NONFINITE, "the objective value is not finite in at least one run: it diverged");
+}
+
 // Whole steps of a SubsampledObjective (src/algorithms/subsampledobjective.jl:64-90) on the device: the loop above over the batches
 // first_batch, first_batch + 1, ... of the resident schedule.  A scheduled context takes no launch-free loop (lr_small_loop_takes sees the
 // schedule), so this is the graph of launches with the batch of every step baked in (record_steps).

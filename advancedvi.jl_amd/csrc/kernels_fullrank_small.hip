@@ -39,13 +39,39 @@ struct FrSmallLoopArgs {
   T *avg;
   const T *x0;
   double *dog_sc;
+  // mivi_optimize_loop_many: workgroup (0, y) is run run0 + y.  nullptr: the one run described above (grid 1 x 1)
+  const ManyRun *many;
+  int run0;
+  long long state_stride, tgt_stride;   // bytes between the runs' optimiser states; elements between their targets (0: one target)
 };
+
+// The prologue of a run of mivi_optimize_loop_many: every per-run pointer moves to the run's slice and the per-run scalars come from the
+// device table; nothing else of the kernel knows about runs, so run k executes the single run's instructions on the single run's threads.
+template <typename T>
+__device__ __forceinline__ void fr_small_select_run(FrSmallLoopArgs<T> &a) {
+  if (!a.many) return;
+  const size_t run = (size_t)a.run0 + blockIdx.y;
+  const ManyRun r = a.many[run];
+  const size_t plen = (size_t)a.d + (size_t)a.d * a.d;
+  a.params += run * plen;
+  if (a.opt_state) a.opt_state = (T *)((char *)a.opt_state + run * (size_t)a.state_stride);
+  if (a.x0) a.x0 = (const T *)((const char *)a.x0 + run * (size_t)a.state_stride);
+  if (a.dog_sc) a.dog_sc = (double *)((char *)a.dog_sc + run * (size_t)a.state_stride);
+  if (a.avg) a.avg += run * plen;
+  a.t_mean += run * (size_t)a.tgt_stride;
+  a.t_istd += run * (size_t)a.tgt_stride;
+  a.elbo += run * (size_t)a.n_steps;
+  a.value += run;
+  a.status += run;
+  a.seed = r.seed; a.idx0 = r.idx0; a.eta = r.eta; a.ell_const = r.ell_const;
+}
 
 constexpr int kSmallD = 32, kSmallM = 64, kSmallNE = 3;   // (32 + 528 entries over 256 threads)
 
 template <typename T, int RULE>
 __global__ __launch_bounds__(256) void k_fr_small_loop(FrSmallLoopArgs<T> a) {
   constexpr int NT = 256;
+  fr_small_select_run(a);
   __shared__ T Cs[kSmallD * kSmallD];   // C[k d + i]: column k, row i; zero above the diagonal
   __shared__ T mus[kSmallD], tms[kSmallD], tiss[kSmallD];
   __shared__ T E[kSmallM * kSmallD];    // eps[m d + i]
@@ -256,7 +282,7 @@ static bool fr_small_loop_ok(const mivi_ctx *c) {
 
 template <typename T>
 static void fr_small_loop_impl(mivi_ctx *c, void *params, void *opt_state, uint64_t idx0, long long t0, int n_steps, int rule, double eta,
-                               double clip_eps, double *elbo, void *value, const mivi_loop_t *gen) {
+                               double clip_eps, double *elbo, void *value, const mivi_loop_t *gen, const ManyLaunch *many = nullptr) {
   FrSmallLoopArgs<T> a;
   a.d = c->cfg.d; a.M = c->cfg.n_mc; a.n_steps = n_steps; a.rule = rule; a.ent_kind = c->cfg.entropy;
   a.m_offset = c->cfg.m_offset; a.M_total = c->M_total;
@@ -274,10 +300,23 @@ static void fr_small_loop_impl(mivi_ctx *c, void *params, void *opt_state, uint6
       a.dog_sc = (double *)((char *)gen->opt_state_dev + mivi_dog_state_bytes(c) - 16);
     }
   }
-  if (rule == 0) hipLaunchKernelGGL((k_fr_small_loop<T, 0>), dim3(1), dim3(256), 0, c->stream, a);
-  else if (rule == 1) hipLaunchKernelGGL((k_fr_small_loop<T, 1>), dim3(1), dim3(256), 0, c->stream, a);
-  else if (rule == 2) hipLaunchKernelGGL((k_fr_small_loop<T, 2>), dim3(1), dim3(256), 0, c->stream, a);
-  else hipLaunchKernelGGL((k_fr_small_loop<T, 3>), dim3(1), dim3(256), 0, c->stream, a);
+  a.many = nullptr; a.run0 = 0; a.state_stride = 0; a.tgt_stride = 0;
+  int n_runs = 1;
+  if (many) {   // run-major arrays; the table carries seed, first index, eta and ell_const of every run
+    n_runs = many->n_runs;
+    a.many = many->runs;
+    a.status = many->status;
+    a.state_stride = rule == 1 ? (long long)(2 * ((size_t)a.d + (size_t)a.d * a.d) * sizeof(T)) : (rule >= 2 ? (long long)mivi_dog_state_bytes(c) : 0);
+    if (many->t_mean) { a.t_mean = (const T *)many->t_mean; a.t_istd = (const T *)many->t_istd; a.tgt_stride = a.d; }
+  }
+  for (int r0 = 0; r0 < n_runs; r0 += kManyGridY) {
+    a.run0 = r0;
+    const dim3 grid(1, n_runs - r0 < kManyGridY ? n_runs - r0 : kManyGridY);
+    if (rule == 0) hipLaunchKernelGGL((k_fr_small_loop<T, 0>), grid, dim3(256), 0, c->stream, a);
+    else if (rule == 1) hipLaunchKernelGGL((k_fr_small_loop<T, 1>), grid, dim3(256), 0, c->stream, a);
+    else if (rule == 2) hipLaunchKernelGGL((k_fr_small_loop<T, 2>), grid, dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_fr_small_loop<T, 3>), grid, dim3(256), 0, c->stream, a);
+  }
 }
 static bool fr_small_loop_takes(const mivi_ctx *c, const mivi_loop_t &l, bool) { return l.rule <= 3 && fr_small_loop_ok(c); }
 // The whole loop in ONE workgroup (the two norms of DoG / DoWG are block sums there).  The kernel's description of the rule is the call's
@@ -287,6 +326,15 @@ static bool launch_fr_small_loop(mivi_ctx *c, void *params, const mivi_loop_t &l
   by_dtype(c, [&](auto t) { fr_small_loop_impl<decltype(t)>(c, params, l.opt_state_dev, l.estimate_idx0, (long long)l.t0, l.n_steps, l.rule, l.eta, loop_clip_eps(l), b.rec, b.value, gen); });
   return true;
 }
-DeviceLoop loop_fr_small() { return {LOOP_FR_SMALL, fr_small_loop_takes, kExchangesNever, nullptr, nullptr, launch_fr_small_loop}; }
+// mivi_optimize_loop_many: the same kernel, workgroup (0, k) = run k (the row's condition is the single run's: one workgroup either way)
+static bool fr_small_loop_takes_many(const mivi_ctx *c, const mivi_loop_t &l) { return fr_small_loop_takes(c, l, loop_general(l)); }
+static bool launch_fr_small_many(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b, const ManyLaunch &m) {
+  const mivi_loop_t *gen = loop_general(l) ? &l : nullptr;
+  by_dtype(c, [&](auto t) { fr_small_loop_impl<decltype(t)>(c, params, l.opt_state_dev, l.estimate_idx0, (long long)l.t0, l.n_steps, l.rule, l.eta, loop_clip_eps(l), b.rec, b.value, gen, &m); });
+  return true;
+}
+DeviceLoop loop_fr_small() {
+  return {LOOP_FR_SMALL, fr_small_loop_takes, kExchangesNever, nullptr, nullptr, launch_fr_small_loop, fr_small_loop_takes_many, launch_fr_small_many};
+}
 
 }  // namespace mivi

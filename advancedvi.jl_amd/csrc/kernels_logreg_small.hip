@@ -50,7 +50,32 @@ struct LrSmallLoopArgs {
   double *dog_sc;
   double *part;                    // G > 1: [n_steps][G][pstride] partial sums, NaN until delivered
   int pstride, spin;
+  // mivi_optimize_loop_many: workgroup (0, y) is run run0 + y (G = 1: no exchange).  nullptr: the one run described above
+  const ManyRun *many;
+  int run0;
+  long long state_stride, x_stride, y_stride;   // bytes between the runs' optimiser states; elements between their X (0: shared) and y (0: shared)
 };
+
+// The prologue of a run of mivi_optimize_loop_many (as fr_small_select_run, kernels_fullrank_small.hip): pointers to the run's slices, the
+// per-run scalars from the device table, and nothing else of the kernel knows about runs.
+template <typename T>
+__device__ __forceinline__ void lr_small_select_run(LrSmallLoopArgs<T> &a) {
+  if (!a.many) return;
+  const size_t run = (size_t)a.run0 + blockIdx.y;
+  const ManyRun r = a.many[run];
+  const size_t plen = a.family == MIVI_FULLRANK ? (size_t)a.d + (size_t)a.d * a.d : 2 * (size_t)a.d;
+  a.params += run * plen;
+  if (a.opt_state) a.opt_state = (T *)((char *)a.opt_state + run * (size_t)a.state_stride);
+  if (a.x0) a.x0 = (const T *)((const char *)a.x0 + run * (size_t)a.state_stride);
+  if (a.dog_sc) a.dog_sc = (double *)((char *)a.dog_sc + run * (size_t)a.state_stride);
+  if (a.avg) a.avg += run * plen;
+  a.X += run * (size_t)a.x_stride;
+  a.y += run * (size_t)a.y_stride;
+  a.elbo += run * (size_t)a.n_steps;
+  a.value += run;
+  a.status += run;
+  a.seed = r.seed; a.idx0 = r.idx0; a.eta = r.eta;
+}
 
 template <typename T>
 __device__ __forceinline__ T lrs_softplus(T x) { return x > T(0) ? x + log1p(exp(-x)) : log1p(exp(x)); }
@@ -58,6 +83,7 @@ __device__ __forceinline__ T lrs_softplus(T x) { return x > T(0) ? x + log1p(exp
 template <typename T, int RULE, bool XRES>   // XRES: X lives in LDS (no generic pointers: a pointer that may be LDS or global makes every load a flat load)
 __global__ __launch_bounds__(kLrSmallNT) void k_lr_small_loop(LrSmallLoopArgs<T> a) {
   constexpr int NT = kLrSmallNT, NE = kLrSmallNE, GPT = kLrSmallGPT;
+  lr_small_select_run(a);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int d = a.d, p = d - 1, M = a.M, d4 = (d + 3) >> 2, RC = a.rc;
@@ -476,7 +502,8 @@ static size_t lr_small_part_bytes(const mivi_ctx *c, int n_steps) {
   const size_t ps = (((size_t)(c->cfg.d - 1) * c->cfg.n_mc + c->cfg.n_mc) + 15) & ~(size_t)15;
   return (size_t)n_steps * G * ps * sizeof(double);
 }
-static bool lr_small_loop_ok(const mivi_ctx *c) {
+// G: the workgroups of a run -- lr_small_groups(c) for mivi_optimize_loop, ONE for mivi_optimize_loop_many (0: lr_small_groups(c))
+static bool lr_small_loop_ok(const mivi_ctx *c, int G = 0) {
   const int d = c->cfg.d, M = c->cfg.n_mc;
   const bool stl = c->cfg.entropy == MIVI_ENT_STL || c->cfg.entropy == MIVI_ENT_STL_ZERO_GRAD;
   if (!(c->target == TGT_LOGREG && !c->bij_on && !stl && d >= 2 && d <= kLrSmallD && M >= 1 && M <= kLrSmallM && c->cfg.m_offset == 0 && c->M_total == M &&
@@ -492,11 +519,11 @@ static bool lr_small_loop_ok(const mivi_ctx *c) {
   // 4000 x 16 x 4 (sixteen): 17.5 / 33; 208 x 60 x 8 (seven): 28.9 / 36; 1000 x 32 x 16 (32; BASELINE configs[0]): 35.4 / 31 -- a step's fixed
   // work and the exchanged partials grow with (d - 1) n_mc.  Taken where it wins: (d - 1) n_mc <= 256.
   return (long long)(d - 1) * M <= 256 && (long long)c->lr_n * (d - 1) * M <= (1ll << 20) &&
-         lr_small_lds(c, lr_small_groups(c), false, nullptr) <= c->lds_max;
+         lr_small_lds(c, G > 0 ? G : lr_small_groups(c), false, nullptr) <= c->lds_max;
 }
 
 template <typename T>
-static bool lr_small_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, double *elbo, void *value, double *part) {
+static bool lr_small_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, double *elbo, void *value, double *part, const ManyLaunch *many = nullptr) {
   LrSmallLoopArgs<T> a;
   a.family = c->cfg.family; a.d = c->cfg.d; a.M = c->cfg.n_mc; a.n_steps = l.n_steps; a.rule = l.rule; a.ent_kind = c->cfg.entropy;
   a.m_offset = c->cfg.m_offset; a.M_total = c->M_total; a.variant = c->lr_variant; a.n = c->lr_n;
@@ -509,7 +536,17 @@ static bool lr_small_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, 
   a.x0 = l.rule >= 2 ? (const T *)l.opt_state_dev : nullptr;
   a.dog_sc = l.rule >= 2 ? (double *)((char *)l.opt_state_dev + mivi_dog_state_bytes(c) - 16) : nullptr;
   a.rc = lr_small_rc(a.M);
-  const int G = lr_small_groups(c);
+  const int G = many ? 1 : lr_small_groups(c);   // (a run of mivi_optimize_loop_many is one workgroup whatever its size: nothing is exchanged)
+  a.many = nullptr; a.run0 = 0; a.state_stride = 0; a.x_stride = 0; a.y_stride = 0;
+  int n_runs = 1;
+  if (many) {
+    n_runs = many->n_runs;
+    a.many = many->runs;
+    a.status = many->status;
+    a.state_stride = l.rule == 1 ? (long long)(2 * (size_t)mivi_params_len(c) * sizeof(T)) : (l.rule >= 2 ? (long long)mivi_dog_state_bytes(c) : 0);
+    if (many->X) { a.X = (const T *)many->X; a.x_stride = many->x_stride; }
+    if (many->y) { a.y = many->y; a.y_stride = c->lr_n; }
+  }
   a.part = part;
   a.pstride = (int)((((size_t)(a.d - 1) * a.M + a.M) + 15) & ~(size_t)15);
   a.spin = 1 << 20;
@@ -528,7 +565,10 @@ static bool lr_small_loop_impl(mivi_ctx *c, void *params, const mivi_loop_t &l, 
       launched = false;
       return;
     }
-    hipLaunchKernelGGL(kern, dim3(G), dim3(kLrSmallNT), lds, c->stream, a);
+    for (int r0 = 0; r0 < n_runs; r0 += kManyGridY) {
+      a.run0 = r0;
+      hipLaunchKernelGGL(kern, dim3(G, n_runs - r0 < kManyGridY ? n_runs - r0 : kManyGridY), dim3(kLrSmallNT), lds, c->stream, a);
+    }
   };
   if (a.x_resident) {
     switch (l.rule) {
@@ -557,6 +597,14 @@ static mivi_status_t lr_small_loop_reserve(mivi_ctx *c, const mivi_loop_t &l) { 
 static bool launch_lr_small_loop(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b) {
   return by_dtype(c, [&](auto t) { return lr_small_loop_impl<decltype(t)>(c, params, l, b.rec, b.value, (double *)c->gen_scratch.p); });
 }
-DeviceLoop loop_lr_small() { return {LOOP_LR_SMALL, lr_small_loop_takes, 0, lr_small_loop_reserve, nullptr, launch_lr_small_loop}; }
+// mivi_optimize_loop_many: the same kernel with ONE workgroup per run (lr_small_groups is not consulted: X resident in LDS where it fits
+// beside the rest, streamed otherwise -- the rule of G = 1), workgroup (0, k) = run k
+static bool lr_small_loop_takes_many(const mivi_ctx *c, const mivi_loop_t &l) { return l.rule <= 3 && lr_small_loop_ok(c, 1); }
+static bool launch_lr_small_many(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b, const ManyLaunch &m) {
+  return by_dtype(c, [&](auto t) { return lr_small_loop_impl<decltype(t)>(c, params, l, b.rec, b.value, nullptr, &m); });
+}
+DeviceLoop loop_lr_small() {
+  return {LOOP_LR_SMALL, lr_small_loop_takes, 0, lr_small_loop_reserve, nullptr, launch_lr_small_loop, lr_small_loop_takes_many, launch_lr_small_many};
+}
 
 }  // namespace mivi

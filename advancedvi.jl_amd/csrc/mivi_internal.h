@@ -457,6 +457,7 @@ struct mivi_ctx : mivi_ctx_streams {
   bool p2p_opened[8] = {false, false, false, false, false, false, false, false};                   // hipIpcOpenMemHandle'd (to be closed)
   mivi::DevBuf rows_eps;   // kernels_fullrank_rows.hip: eps of all steps of a device-resident loop call
   mivi::DevBuf gen_scratch;  // kernels_meanfield.hip k_mf_gen_loop: DoG / DoWG partial norms of every step, arrival flags
+  mivi::DevBuf many_buf;     // mivi_optimize_loop_many: the runs' table, status words, targets, ELBO records and last values (many_layout, api_optimize.hip)
   mivi::DevBuf p2p_tab, p2p_ctr, p2p_scratch, p2p_direct;   // (p2p_direct: P2PDirectTab, what the partial kernels need to store straight into the owners' staging areas)
   bool p2p_on = false;
   bool p2p_distinct = false;     // the attached exchange areas include one of ANOTHER device (not only this process's own contexts on this device)
@@ -606,11 +607,28 @@ void launch_mf_main(mivi_ctx *c, const void *params, const RngArgs &rng, int M, 
 // mivi_optimize_loop walks kDeviceLoops (api_common.h: one row per launch-free optimisation loop, in priority order; first match).  A row
 // is defined beside its kernel; `takes` is the WHOLE condition of the row apart from the two the dispatcher owns (no_device_loops, and
 // allow_exchange for a row that exchanges).
-enum DeviceLoopId : int { LOOP_GRAPH = 0, LOOP_MF_SGD = 1, LOOP_LR_SMALL = 2, LOOP_MF_GEN = 3, LOOP_FR_SMALL = 4, LOOP_FR_ROWS = 5, LOOP_MF_FUNNEL_SGD = 6 };
+enum DeviceLoopId : int { LOOP_GRAPH = 0, LOOP_MF_SGD = 1, LOOP_LR_SMALL = 2, LOOP_MF_GEN = 3, LOOP_FR_SMALL = 4, LOOP_FR_ROWS = 5, LOOP_MF_FUNNEL_SGD = 6,
+                          LOOP_MANY = 16 };   // LOOP_MANY | row id: mivi_optimize_loop_many ran on that row's kernel, workgroup k = run k
 struct LoopBufs {       // what the dispatcher owns (c->X)
   void *value, *grad;   // the value word (8 elements), the gradient scratch (params_len elements)
   double *rec, *area;   // the f64 ELBO record (n_steps doubles) and, behind it, the hist / partials area: the largest hist_doubles of the table (+ 8)
 };
+// mivi_optimize_loop_many: independent runs of one shape in ONE launch, workgroup (0, k) = run k.  What differs between the runs reaches the
+// kernel through a device table (one ManyRun per run) and run-major arrays; a short prologue of the kernel offsets its pointers by the run.
+struct ManyRun {
+  uint64_t seed, idx0;     // the run's Philox seed and first estimate index
+  double eta, ell_const;   // its step size; the per-sample constant of its diagonal-Gaussian target
+};
+struct ManyLaunch {
+  int n_runs;
+  const ManyRun *runs;             // device, [n_runs]
+  int *status;                     // device, [n_runs]: bit 1 non-finite objective, bit 2 non-positive scale diagonal -- a word per run
+  const void *t_mean, *t_istd;     // diagonal-Gaussian target: device T[n_runs d], or nullptr = the context's target for every run
+  const uint8_t *y;                // logistic regression: device uint8[n_runs n], or nullptr = the context's y for every run
+  const void *X;                   // ... device X (n x p column-major) of run 0, or nullptr = the context's X for every run
+  long long x_stride;              // ... elements between the runs' X (0: one shared matrix)
+};
+constexpr int kManyGridY = 65535;  // runs per launch (gridDim.y); more runs: further launches of the same kernel at a run offset
 constexpr int kExchangesNever = 1 << 30;
 struct DeviceLoop {
   int id;
@@ -619,6 +637,10 @@ struct DeviceLoop {
   mivi_status_t (*reserve)(mivi_ctx *c, const mivi_loop_t &l);            // the loop's own buffers (rows_eps, gen_scratch); nullptr: none
   size_t (*hist_doubles)(const mivi_ctx *c, int n_steps);                 // what it needs of LoopBufs::area; nullptr: nothing
   bool (*launch)(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b);   // false: not launched (an exchanging grid not resident, the LDS refused): the next row
+  // mivi_optimize_loop_many (nullptr: the row has no such form).  takes_many: the row's condition with ONE workgroup per run; launch_many:
+  // every array run-major (params, l.opt_state_dev, l.avg_params_dev; b.rec [n_runs][n_steps], b.value [n_runs]), no exchange of any kind
+  bool (*takes_many)(const mivi_ctx *c, const mivi_loop_t &l) = nullptr;
+  bool (*launch_many)(mivi_ctx *c, void *params, const mivi_loop_t &l, const LoopBufs &b, const ManyLaunch &m) = nullptr;
 };
 DeviceLoop loop_mf_sgd(), loop_mf_gen(), loop_mf_funnel_sgd(), loop_fr_small(), loop_fr_rows(), loop_lr_small();   // the rows: kernels_meanfield / _fullrank_small / _fullrank_rows / _logreg_small.hip
 // simple: what the fused paths implement (Descent / Adam, at most ClipScale, no averager); general := !simple || (Adam with other betas than

@@ -476,3 +476,234 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
             print(f"\rOptimizing {t}/{max_iter} elbo={info['elbo']:.6g}", end="" if t < max_iter else "\n")
         info_total.append(info)
     return output(algorithm, state), info_total, state
+
+
+# --- optimize_many: independent runs of one shape, one workgroup each -------------------------------
+# the shapes mivi_optimize_loop_many serves (include/mivi.h): fr_small_loop_ok / lr_small_loop_ok of the library, restated for the host
+_MANY_FR = dict(d=32, n_mc=64, dm=768, dm_stl=512)
+_MANY_LR = dict(d=64, n_mc=64, pm=256, work=1 << 20)
+
+
+def _many_family(q, state=None):
+    """(family, d, dtype string) of a run, or None when the many-run entry cannot carry it: from `q` (an MvLocationScale with the normal
+    base), or -- a warm start written as `optimize` allows, q_init = None with a state -- from the state's context (a base other than
+    the normal one is then the library's to refuse)."""
+    from .families import FULLRANK, MEANFIELD
+    if q is None and state is not None:
+        ctx = _ctx_of(state["obj_st"])
+        fam, d, dt = ctx.family, ctx.d, np.dtype(ctx.np_dtype).str
+    elif isinstance(q, MvLocationScale) and getattr(getattr(q, "dist", None), "code", 0) == 0:
+        fam, d, dt = q.family, len(q), np.dtype(q.eltype).str
+    else:
+        return None
+    return (fam, d, dt) if fam in (FULLRANK, MEANFIELD) else None
+
+
+def _many_key(alg, prob, q, state=None):
+    """What must agree between runs that share a launch, as a hashable key -- None for a run mivi_optimize_loop_many cannot carry.  Pure
+    host arithmetic on types and shapes: no library call, no device.  The step size (eta, or alpha of DoG / DoWG) is not part of the key:
+    it is what the runs of a sweep differ in."""
+    from . import problems as P
+    from .families import FULLRANK
+    if type(alg) not in (KLMinRepGradDescent, KLMinRepGradProxDescent) or type(alg.objective) is not O.RepGradELBO:
+        return None
+    codes = _device_loop_codes(alg, None, ())
+    fam = _many_family(q, state)
+    if codes is None or codes[0] > 3 or fam is None:
+        return None
+    family, d, dtype_str = fam
+    M, ent = alg.objective.n_samples, alg.objective.entropy
+    stl = isinstance(ent, (O.StickingTheLandingEntropy, O.StickingTheLandingEntropyZeroGradient))
+    if type(prob) is P.DiagNormalProblem:
+        if family != FULLRANK or d > _MANY_FR["d"] or M > _MANY_FR["n_mc"] or d * M > (_MANY_FR["dm_stl"] if stl else _MANY_FR["dm"]):
+            return None
+        if P.dimension(prob) != d:
+            return None
+        shape = ("A", d)
+    elif type(prob) is P.LogRegProblem:
+        if not isinstance(prob.X, np.ndarray) or prob.X.ndim != 2 or P.dimension(prob) != d:
+            return None
+        n, p = prob.X.shape
+        if stl or d < 2 or d > _MANY_LR["d"] or M > _MANY_LR["n_mc"] or p * M > _MANY_LR["pm"] or n * p * M > _MANY_LR["work"]:
+            return None
+        shape = ("B", n, p, prob.variant, prob.likeadj)
+    else:
+        return None
+    opt = alg.optimizer
+    return (type(alg), codes, type(ent), M, getattr(opt, "beta", None), getattr(opt, "epsilon", None),
+            getattr(alg.operator, "epsilon", None), getattr(alg.averager, "eta", None), getattr(alg.adtype, "device", 0),
+            family, dtype_str, shape)
+
+
+def many_plan(algorithms, probs, q_inits, states=None):
+    """The decision "these runs can share a launch" of optimize_many: the common key of the runs (see _many_key) when every run has one and
+    all agree, else None -- the runs are then optimised one after the other.  `states`: the runs' states of a warm start (a run whose
+    q_init is None is described by its state)."""
+    states = [None] * len(algorithms) if states is None else states
+    keys = [_many_key(a, p, q, s) for a, p, q, s in zip(algorithms, probs, q_inits, states)]
+    if not keys or keys[0] is None or any(k != keys[0] for k in keys[1:]):
+        return None
+    return keys[0]
+
+
+def _per_run(x, K, name):
+    """`x` as a list of K: one value for every run, or a list / tuple of exactly K."""
+    if isinstance(x, (list, tuple)):
+        if len(x) != K:
+            raise ValueError(f"optimize_many: {name} holds {len(x)} entries for {K} rngs")
+        return list(x)
+    return [x] * K
+
+
+def _optimize_many_on_device(rngs, algs, max_iter, states, key, show_progress):
+    """The chunks of optimize_many on mivi_optimize_loop_many.  Returns the runs' info lists, or None when the library does not take the
+    group (nothing has been changed then)."""
+    import torch
+    from ._lib import MiviError
+    K = len(rngs)
+    rule, op, avg = key[1]
+    cls = key[-1][0]
+    ctx = _ctx_of(states[0]["obj_st"])
+    ctxs = [_ctx_of(st["obj_st"]) for st in states]
+    probs = [st["prob"] for st in states]
+    infos = [[] for _ in range(K)]
+    active = list(range(K))
+    y_all = X_all = None
+    x_stride = 0
+    if cls == "B":
+        n, p = probs[0].X.shape
+        y_all = torch.as_tensor(np.ascontiguousarray(np.stack([np.asarray(pr.y).reshape(n) for pr in probs]), dtype=np.uint8)).to(ctx.tdevice)
+        shared = all(pr.X is probs[0].X or np.array_equal(pr.X, probs[0].X) for pr in probs[1:])
+        Xs = [probs[0].X] if shared else [pr.X for pr in probs]
+        X_all = torch.as_tensor(np.stack([np.ascontiguousarray(np.asarray(X, dtype=ctx.np_dtype).T).reshape(-1) for X in Xs])).to(ctx.tdevice)
+        x_stride = 0 if shared else n * p
+    done = 0
+    while done < max_iter and active:
+        n_st = min(DEVICE_LOOP_CHUNK, max_iter - done)
+        sts = [states[k] for k in active]
+        Ka = len(active)
+        params = torch.stack([st["params"] for st in sts]).contiguous()
+        opt_state = torch.stack([st["opt_st"] for st in sts]).contiguous() if rule != 0 else None
+        avg_params = torch.stack([st["avg_st"][0] for st in sts]).contiguous() if avg == 1 else None
+        elbo = ctx.empty(Ka * n_st)
+        t0s = {st["iteration"] for st in sts}
+        if len(t0s) != 1:
+            raise ValueError("optimize_many: the runs of one launch must have done the same number of iterations")
+        opt0 = algs[active[0]].optimizer
+        kw = dict(rule=rule, op=op, averager=avg, beta=getattr(opt0, "beta", (0.9, 0.999)), adam_eps=getattr(opt0, "epsilon", 1e-8),
+                  clip_epsilon=getattr(algs[active[0]].operator, "epsilon", 0.0), avg_eta=getattr(algs[active[0]].averager, "eta", 8),
+                  opt_state=opt_state, avg_params=avg_params, elbo=elbo)
+        if cls == "A":
+            d = ctx.d
+            kw.update(means=np.stack([np.asarray(probs[k].mean, dtype=ctx.np_dtype) for k in active]),
+                      stds=np.stack([np.broadcast_to(np.asarray(probs[k].std, dtype=ctx.np_dtype), (d,)) for k in active]))
+        else:
+            sel = torch.as_tensor(active, device=ctx.tdevice)
+            kw.update(y=y_all.index_select(0, sel).contiguous(),
+                      X=X_all if x_stride == 0 else X_all.index_select(0, sel).contiguous(), x_stride=x_stride)
+        try:
+            status = ctx.optimize_loop_many(params, Ka, n_st, [rngs[k].counter for k in active], sts[0]["iteration"],
+                                            seeds=[ctxs[k].seed for k in active], etas=[getattr(algs[k].optimizer, "eta", 0.0) for k in active],
+                                            **kw)
+        except MiviError as e:
+            if e.status == 6 and done == 0:   # MIVI_ERR_UNSUPPORTED: the library does not take this group
+                return None
+            raise
+        vals = elbo.cpu().numpy().reshape(Ka, n_st)
+        still = []
+        # the finished runs' slices back into the runs' own tensors: one batched copy per kind, not one launch per run
+        fine = [j for j in range(Ka) if status[j] == 0]
+        dst, src = [states[active[j]]["params"] for j in fine], [params[j] for j in fine]
+        if rule != 0:
+            dst, src = dst + [states[active[j]]["opt_st"] for j in fine], src + [opt_state[j] for j in fine]
+        if avg == 1:
+            dst, src = dst + [states[active[j]]["avg_st"][0] for j in fine], src + [avg_params[j] for j in fine]
+        if dst:
+            torch._foreach_copy_(dst, src)
+        iters = range(done + 1, done + n_st + 1)
+        for j, k in enumerate(active):
+            st, rng = states[k], rngs[k]
+            if status[j] == 0:
+                if avg == 1:
+                    st["avg_st"] = (st["avg_st"][0], st["avg_st"][1] + n_st)
+                rng.counter += n_st   # (n_st times next_index: one estimate index per step)
+                infos[k] += [{"elbo": e, "iteration": i} for e, i in zip(vals[j].tolist(), iters)]
+                st["iteration"] += n_st
+                st["q"] = None
+                still.append(k)
+                continue
+            # the run diverged inside the chunk: its tensors still hold the chunk's entry state (nothing was copied back), so the host-driven
+            # loop replays it and stops where `optimize` would have raised, the steps before it applied (common.jl:83-94)
+            try:
+                for i in range(n_st):
+                    new_state, _, info = step(rng, algs[k], st, None)
+                    st.update(new_state)
+                    infos[k].append({**info, "iteration": done + i + 1})
+            except (RuntimeError, MiviError) as e:
+                if isinstance(e, MiviError) and e.status not in (2, 3):
+                    raise
+                try:
+                    ctxs[k].synchronize()   # drop the sticky device flag of the failed estimate
+                except MiviError:
+                    pass
+                st["diverged"] = True
+            else:
+                warnings.warn(f"optimize_many: run {k} reported status {int(status[j])} on the device but its host-driven replay completed "
+                              "with finite objectives; continuing from the replayed steps", RuntimeWarning)
+                still.append(k)
+        active = still
+        done += n_st
+        if show_progress:
+            print(f"\rOptimizing {done}/{max_iter} ({len(active)} of {K} runs)", end="" if done < max_iter and active else "\n")
+    return infos
+
+
+def optimize_many(rngs, algorithm, max_iter: int, probs, q_inits, *, states=None, show_progress=False):
+    """K independent `optimize` calls as one: element k of the returned list is what
+    `optimize(rngs[k], algorithm_k, max_iter, probs[k], q_inits[k], state=states[k])` returns -- (output, info, state), with rngs[k]
+    advanced alike.  `algorithm`, `probs` and `q_inits`: one value for every run or K of them; `states`: K states or None (with states,
+    q_inits may be None as for `optimize`).  Bit for bit where `optimize` runs the problem in one workgroup too: every small full-rank run
+    on a DiagNormalProblem, and the regressions that mivi_optimize_loop does not split over workgroups (n p n_samples <= 2^14); for a
+    larger regression `optimize` splits the rows over several workgroups and a run here stays one, so the two agree to the rounding of
+    the row sums (2e-4 relative in float32, 1e-9 in float64: tests/test_gpu_optimize_many.py).
+
+    Runs of one shape whose whole loop fits a workgroup -- small full-rank families on a DiagNormalProblem, small LogRegProblems (see
+    mivi_optimize_loop_many, include/mivi.h) -- with the same rule, operator, averager, estimator and sample count (step sizes may differ)
+    share ONE launch per chunk of DEVICE_LOOP_CHUNK iterations, workgroup k = run k.  Every other configuration runs as K `optimize` calls.
+    A run that diverges does not raise: its state carries `state["diverged"] = True`, its `info` ends at the last finite step and its
+    parameters are those of that step, where `optimize` would have raised; the other runs are not affected."""
+    rngs = list(rngs)
+    K = len(rngs)
+    if K < 1:
+        raise ValueError("optimize_many: at least one rng (one run) is needed")
+    if not all(isinstance(r, O.PhiloxRNG) for r in rngs):
+        raise TypeError("optimize_many: rngs must be PhiloxRNGs, one per run")
+    if len({id(r) for r in rngs}) != K:
+        raise ValueError("optimize_many: every run needs a PhiloxRNG of its own (the same object was passed twice)")
+    if not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+        raise ValueError("optimize_many: max_iter must be a non-negative integer")
+    algs = _per_run(algorithm, K, "algorithm")
+    probs = _per_run(probs, K, "probs")
+    qs = _per_run(q_inits, K, "q_inits")
+    if states is None:
+        states = [None] * K
+    elif isinstance(states, dict) or len(states) != K or not all(isinstance(s, dict) for s in states):
+        raise ValueError(f"optimize_many: states must be a list of {K} states, one per run (a state belongs to one run)")
+    else:
+        states = list(states)
+
+    def sequential(sts):
+        return [optimize(rngs[k], algs[k], max_iter, probs[k], qs[k], show_progress=show_progress, state=sts[k]) for k in range(K)]
+
+    if _measure_space(*algs) is not None:
+        return sequential(states)
+    key = many_plan(algs, [s["prob"] if s is not None else p for s, p in zip(states, probs)], qs, states)
+    if key is None or max_iter == 0:
+        return sequential(states)
+    sts = [dict(s) if s is not None else init(rngs[k], algs[k], qs[k], probs[k]) for k, s in enumerate(states)]
+    if len({st["iteration"] for st in sts}) != 1 or len({id(st["params"]) for st in sts}) != K:
+        return sequential(sts)
+    infos = _optimize_many_on_device(rngs, algs, int(max_iter), sts, key, show_progress)
+    if infos is None:
+        return sequential(sts)
+    return [(output(algs[k], sts[k]), infos[k], sts[k]) for k in range(K)]

@@ -575,6 +575,7 @@ mivi_status_t mivi_prox_scale_entropy(mivi_ctx_t *ctx, void *params_dev, double 
  *   logistic-regression target, (d - 1) n_mc <= 256, d <= 64,  one kernel for the whole loop (the reference README's own example: one workgroup;
  *     n (d - 1) n_mc <= 2^20                                  larger data sets: up to 64 that split the rows and exchange partial sums), to rounding
  *   otherwise                                                 one hipGraph of chained estimates (full-rank f32: update + ClipScale in the VJP epilogue)
+ *   K independent runs of the one-workgroup shapes above       mivi_optimize_loop_many: the same two kernels, workgroup k = run k (below)
  * MIVI_NO_FUSED_LOOP=1 forces the hipGraph everywhere (A/B). */
 mivi_status_t mivi_optimize_steps(mivi_ctx_t *ctx, void *params_dev, void *opt_state_dev, uint64_t estimate_idx0,
                                   int64_t t0, int32_t n_steps, int32_t rule, double eta, double clip_epsilon,
@@ -608,6 +609,51 @@ typedef struct mivi_loop {
   void *elbo_dev;     /* T[n_steps] or NULL: info.elbo of every iteration */
 } mivi_loop_t;
 mivi_status_t mivi_optimize_loop(mivi_ctx_t *ctx, void *params_dev, const mivi_loop_t *loop);
+/* K INDEPENDENT runs of mivi_optimize_loop in ONE launch, workgroup k = run k: `optimize` (src/optimize.jl:42-94) called K times -- restarts
+ * from other seeds and initialisations, a step-size sweep, one fit per simulated data set or bootstrap replicate -- for the small problems
+ * whose whole loop of `step`s (src/algorithms/common.jl:69-104) fits one workgroup, the sizes of the reference's own benchmark
+ * (bench/benchmarks.jl:43-94).  A single such run keeps one compute unit busy; K of them fill the device.  Two classes are served:
+ *   A  full-rank family, diagonal-Gaussian target, d <= 32, n_mc <= 64, d n_mc <= 768 (512 with the sticking-the-landing estimators); every
+ *      entropy estimator.  Per run: seed, first estimate index, eta, parameters, optimiser state, average, and the target's mean / std.
+ *   B  logistic-regression target, both families, both variants, (d - 1) n_mc <= 256, d <= 64, n (d - 1) n_mc <= 2^20, and the run's y fits
+ *      the LDS of ONE workgroup beside the kernel's other arrays (every run is one workgroup whatever mivi_optimize_loop would split; X is
+ *      resident in LDS where it fits and streamed otherwise).  Per run: as A without the target, plus y and optionally X; n, p, variant and
+ *      likeadj are the context's.
+ * Rules 0-3, operators 0-2, averager 0 / 1, f32 and f64.  Every array is run-major: params_dev T[K params_len]; loop->opt_state_dev K times
+ * the single run's state (Adam: 2 params_len elements, DoG / DoWG: mivi_dog_state_bytes bytes); loop->avg_params_dev T[K params_len];
+ * loop->elbo_dev T[K n_steps].  loop->eta, estimate_idx0 hold for every run whose array below is NULL; t0, the betas, clip_epsilon and avg_eta
+ * are common.  Run k executes the instructions of the single-run kernel on the same threads: mivi_optimize_loop on a context with run k's
+ * seed and target gives the same bits where it is one workgroup too (always in class A; in class B where it does not split the rows), and
+ * agrees to the rounding of the row sums elsewhere.  Workgroups never wait for one another, so K may exceed what is resident at once.
+ * A run that diverges finishes its steps carrying NaNs and touches nothing of another run.
+ *   n_runs               K >= 1
+ *   seed_host            uint64[K] or NULL: the context's seed for every run
+ *   estimate_idx0_host   uint64[K] or NULL: loop->estimate_idx0
+ *   eta_host             double[K] or NULL: loop->eta
+ *   mean_host, std_host  class A: T[K d] each (both or neither), or NULL: the context's target for every run
+ *   y_dev                class B: device uint8[K n], or NULL: the context's y for every run
+ *   X_dev, X_run_stride  class B: device X (n x p column-major) of run 0 and the elements between the runs' matrices (0: one matrix for all),
+ *                        or NULL: the context's X.  Device data are borrowed for the call.
+ *   status_host          int32[K] or NULL, written on return: bit 1 a non-finite objective, bit 2 a non-positive scale diagonal, per run
+ * Returns MIVI_OK when the launch ran and status_host is given, whatever the per-run bits say; with status_host NULL a set bit in any run
+ * returns what mivi_optimize_loop returns for it (MIVI_ERR_NONPOSITIVE_SCALE for bit 2, else MIVI_ERR_NONFINITE).  MIVI_ERR_UNSUPPORTED, with
+ * a message naming the reason and before anything is uploaded: a configuration outside A / B, a Stacked bijector, a sharded context, a batch
+ * schedule, an index source, the low-rank family, a non-normal base, rule 4 (COCOB), MIVI_NO_FUSED_LOOP=1.  MIVI_ERR_BAD_ARG: n_runs < 1, a
+ * non-positive std, op = 2 with Adam, a target array of the other class.  The call waits for the runs (it reads their status words).
+ * mivi_batch_info(what = 7) then reports 16 | the id of the loop whose kernel ran. */
+typedef struct mivi_many {
+  int32_t n_runs;
+  const uint64_t *seed_host;
+  const uint64_t *estimate_idx0_host;
+  const double *eta_host;
+  const void *mean_host;
+  const void *std_host;
+  const uint8_t *y_dev;
+  const void *X_dev;
+  int64_t X_run_stride;
+  int32_t *status_host;
+} mivi_many_t;
+mivi_status_t mivi_optimize_loop_many(mivi_ctx_t *ctx, void *params_dev, const mivi_loop_t *loop, const mivi_many_t *many);
 /* mivi_optimize_loop on a scheduled context (mivi_logreg_set_batch_schedule) where step t (0-based) evaluates batch first_batch + t: whole
  * steps of a SubsampledObjective (src/algorithms/subsampledobjective.jl:64-90) on the device.  When the schedule carries estimate indices,
  * step t draws at estimate_idx_host[first_batch + t] (loop->estimate_idx0 is not read), otherwise at estimate_idx0 + t.  Requires
@@ -738,7 +784,8 @@ int32_t mivi_batch_lanes(const mivi_ctx_t *ctx, int32_t count);
  * destroyed every handle it created, the children's, the exchange pipelines' and the cached graph included;
  * 7: the route the last mivi_optimize_loop / _batches call on this context ran on -- 0: the graph of launches, else the launch-free loop in
  * the library's priority order (first match): 1 mean-field Descent / default Adam, 2 small logistic regression, 3 mean-field, every other
- * rule x operator x averager, 4 small full-rank in one workgroup, 5 full-rank row-owning workgroups, 6 mean-field fused funnel. */
+ * rule x operator x averager, 4 small full-rank in one workgroup, 5 full-rank row-owning workgroups, 6 mean-field fused funnel;
+ * after mivi_optimize_loop_many: 16 | the id of the loop whose kernel ran the runs (18 small logistic regressions, 20 small full-rank runs). */
 int32_t mivi_batch_info(const mivi_ctx_t *ctx, const void *params_dev, int32_t what);
 
 /* ---- measurement hook (bench.py roofline leg) --------------------------------------------------------- *
