@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "libmivi.so")
 
 MIVI_OK, ERR_BAD_ARG, ERR_NONFINITE, ERR_NONPOSITIVE_SCALE, ERR_HIP, ERR_NO_TARGET, ERR_UNSUPPORTED = range(7)
 F32, F64 = 0, 1
-MEANFIELD, FULLRANK, LOWRANK = 0, 1, 2
+MEANFIELD, FULLRANK, LOWRANK, REALNVP = 0, 1, 2, 3
 BASE_NORMAL, BASE_LAPLACE, BASE_TDIST = 0, 1, 2
 
 
@@ -23,6 +23,10 @@ class MiviConfig(C.Structure):
     ]
 
 
+class MiviFlow(C.Structure):   # mivi_flow_t: the architecture of a MIVI_REALNVP context (mivi_create_flow)
+    _fields_ = [("n_layers", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3)]
+
+
 LOGDENSITY_AND_GRADIENT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p)
 LOGDENSITY_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)
 LOGDENSITY_GRADIENT_AND_HESSIAN_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -30,6 +34,7 @@ LOGDENSITY_GRADIENT_AND_HESSIAN_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void
 # name -> (restype, argtypes): every symbol include/mivi.h declares
 SIGNATURES = {
     "mivi_create": (C.c_int32, [C.POINTER(MiviConfig), C.POINTER(C.c_void_p)]),
+    "mivi_create_flow": (C.c_int32, [C.POINTER(MiviConfig), C.POINTER(MiviFlow), C.POINTER(C.c_void_p)]),
     "mivi_destroy": (C.c_int32, [C.c_void_p]),
     "mivi_last_error": (C.c_char_p, [C.c_void_p]),
     "mivi_version": (C.c_int32, []),

@@ -30,6 +30,7 @@ mivi_status_t mivi_set_base_dist(mivi_ctx_t *c, int32_t base, double nu) {
   if (base == MIVI_BASE_TDIST && !(nu > 0.0 && isfinite(nu))) return fail(c, MIVI_ERR_BAD_ARG, "mivi_set_base_dist: TDist needs finite degrees of freedom nu > 0");
   if (base != MIVI_BASE_NORMAL) {
     if (c->cfg.family == MIVI_LOWRANK) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_set_base_dist: a non-normal base is not supported on the low-rank family (MIVI_LOWRANK)");
+    if (mivi_status_t rs = refuse_flow(c, "mivi_set_base_dist with a non-normal base (the flow's base is the standard normal)")) return rs;
     if (c->cfg.m_offset != 0 || (c->cfg.m_total != 0 && c->cfg.m_total != c->cfg.n_mc))
       return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_set_base_dist: a non-normal base is not supported on a sharded context");
   }

@@ -236,6 +236,7 @@ mivi_status_t ensure_work(mivi_ctx *c, int M) {
       if (d % 128 == 0 && (s = ensure(c, c->stl_F, mivi::stl_pack_units(d) * 4, false))) return s;   // + developer stamp page (MIVI_STL_STAMPS)
     }
     if (c->cfg.family == MIVI_LOWRANK && (s = ensure_work_lowrank(c, capM))) return s;
+    if (c->cfg.family == MIVI_REALNVP && (s = ensure_work_flow(c, capM))) return s;
     if (c->base != MIVI_BASE_NORMAL && (s = ensure_work_base(c, capM))) return s;
     if ((s = ensure(c, c->Z, (size_t)d * capM * es, false))) return s;
     if ((s = ensure(c, c->W, (size_t)d * capM * es, false))) return s;
@@ -256,19 +257,29 @@ const char *mivi_last_error(const mivi_ctx_t *ctx) { return ctx ? ctx->err.c_str
 int64_t mivi_params_len(const mivi_ctx_t *c) {
   const int64_t d = c->cfg.d;
   if (c->cfg.family == MIVI_LOWRANK) return 2 * d + d * (int64_t)c->cfg.rank;
+  if (c->cfg.family == MIVI_REALNVP) return flow_params_len(c->flow);
   return c->cfg.family == MIVI_MEANFIELD ? 2 * d : d + d * d;
 }
 int64_t mivi_partials_len(const mivi_ctx_t *c) {
   const int64_t d = c->cfg.d;
-  if (c->cfg.family == MIVI_LOWRANK) return 0;   // no sharded estimates
+  if (c->cfg.family == MIVI_LOWRANK || c->cfg.family == MIVI_REALNVP) return 0;   // no sharded estimates
   return (c->cfg.family == MIVI_MEANFIELD ? 2 * d : d + d * (d + 1) / 2) + 2;
 }
 
 mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out) {
+  if (cfg && cfg->family == MIVI_REALNVP) {
+    fprintf(stderr, "libmivi: mivi_create: the RealNVP family (MIVI_REALNVP) takes its architecture through mivi_create_flow\n");
+    return MIVI_ERR_BAD_ARG;
+  }
+  return create_context(cfg, nullptr, out);
+}
+
+// mivi_create, and mivi_create_flow (api_flow.hip) behind its own checks: `flow` is the architecture of a MIVI_REALNVP context
+mivi_status_t create_context(const mivi_config_t *cfg, const mivi::FlowArch *flow, mivi_ctx_t **out) {
   if (!cfg || !out) return MIVI_ERR_BAD_ARG;
   if (cfg->d <= 0 || cfg->n_mc <= 0) return MIVI_ERR_BAD_ARG;
   if (cfg->dtype != MIVI_F32 && cfg->dtype != MIVI_F64) return MIVI_ERR_BAD_ARG;
-  if (cfg->family != MIVI_MEANFIELD && cfg->family != MIVI_FULLRANK && cfg->family != MIVI_LOWRANK) return MIVI_ERR_BAD_ARG;
+  if (cfg->family != MIVI_MEANFIELD && cfg->family != MIVI_FULLRANK && cfg->family != MIVI_LOWRANK && !(cfg->family == MIVI_REALNVP && flow)) return MIVI_ERR_BAD_ARG;
   if (cfg->family == MIVI_LOWRANK) {   // (rank is read for this family only)
     if (cfg->rank < 1 || cfg->rank > MIVI_LOWRANK_MAX_RANK) return MIVI_ERR_BAD_ARG;
     if (cfg->m_offset != 0 || (cfg->m_total != 0 && cfg->m_total != cfg->n_mc)) return MIVI_ERR_UNSUPPORTED;   // no sharded low-rank estimates
@@ -282,6 +293,7 @@ mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out) {
   }
   mivi_ctx *c = new mivi_ctx();
   c->cfg = *cfg;
+  if (flow) c->flow = *flow;
   c->esize = cfg->dtype == MIVI_F32 ? 4 : 8;
   {
     int v = 0;
@@ -503,6 +515,7 @@ mivi_status_t refuse_batch_schedule(mivi_ctx *c, const char *entry) {
 
 mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *c, const mivi_batch_schedule_t *sp) {
   if (!c || !sp) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_flow(c, "mivi_logreg_set_batch_schedule")) return rs;
   if (c->target != TGT_LOGREG || !c->lr_X_full) return fail(c, MIVI_ERR_NO_TARGET, "no logistic-regression target set");
   const mivi_batch_schedule_t &sc = *sp;
   if (sc.n_batches < 0 || sc.kernels < 0 || sc.kernels > 2) return fail(c, MIVI_ERR_BAD_ARG, "batch schedule: n_batches >= 0 and kernels in 0 .. 2");
@@ -545,6 +558,7 @@ mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *c, const mivi_batch_sch
 
 mivi_status_t mivi_logreg_seek_batch(mivi_ctx_t *c, int32_t k) {
   if (!c) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_flow(c, "mivi_logreg_seek_batch")) return rs;
   if (c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "no batch schedule set (mivi_logreg_set_batch_schedule)");
   if (k < 0 || k >= c->lr_sched_n) return fail(c, MIVI_ERR_BAD_ARG, "batch index outside the schedule");
   invalidate_graph(c);

@@ -4,6 +4,7 @@
 #include "api_common.h"
 
 mivi_status_t refuse_lowrank(mivi_ctx *c, const char *entry) {
+  if (mivi_status_t rs = refuse_flow(c, entry)) return rs;
   if (c->cfg.family != MIVI_LOWRANK) return MIVI_OK;
   c->err = std::string(entry) + ": not supported on the low-rank family (MIVI_LOWRANK)";
   return MIVI_ERR_UNSUPPORTED;

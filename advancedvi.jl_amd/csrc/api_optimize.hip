@@ -3,6 +3,7 @@
 
 mivi_status_t mivi_clip_scale(mivi_ctx_t *c, void *params, double epsilon) {
   if (!c || !params) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_flow(c, "mivi_clip_scale (ClipScale has no method for a family without a scale)")) return rs;
   (void)hipSetDevice(c->cfg.device);
   launch_clip(c, params, epsilon);
   HIPCHK(c, hipGetLastError());
@@ -88,6 +89,8 @@ static mivi_status_t optimize_loop_run(mivi_ctx_t *c, void *params, const mivi_l
   if (l.op == 2 && (rule == 1 || rule == 4)) return fail(c, MIVI_ERR_BAD_ARG, "ProximalLocationScaleEntropy does not support Adam / COCOB (Descent, DoG, DoWG: proximal_location_scale_entropy.jl:26-42)");
   if (l.op == 2)
     if (mivi_status_t rs = refuse_lowrank(c, "mivi_optimize_loop with op = 2 (the reference has no ProximalLocationScaleEntropy method for it)")) return rs;
+  if (l.op == 1)
+    if (mivi_status_t rs = refuse_flow(c, "mivi_optimize_loop with op = 1 (ClipScale has no method for a family without a scale; use op = 0)")) return rs;
   const bool dog = rule == 2 || rule == 3;        // the rules with two global norms per step
   if (!graph_capturable(c)) return fail(c, MIVI_ERR_UNSUPPORTED, "device-resident loop needs a built-in target");
   if (c->idx_src) return fail(c, MIVI_ERR_UNSUPPORTED, "an index source is set (mivi_set_index_source): the device-resident loop keeps its own counter");
@@ -274,6 +277,7 @@ mivi_status_t mivi_optimize_loop_many(mivi_ctx_t *c, void *params, const mivi_lo
   if (l.rule != 0 && !l.opt_state_dev) return fail(c, MIVI_ERR_BAD_ARG, "this optimisation rule needs opt_state_dev");
   if (l.averager == 1 && !l.avg_params_dev) return fail(c, MIVI_ERR_BAD_ARG, "PolynomialAveraging needs avg_params_dev");
   if (c->cfg.family == MIVI_LOWRANK) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: the low-rank family has no launch-free loop");
+  if (mivi_status_t rs = refuse_flow(c, "mivi_optimize_loop_many (the family has no launch-free loop)")) return rs;
   if (c->base != MIVI_BASE_NORMAL) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a non-normal base distribution has no launch-free loop");
   if (c->bij_on) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a Stacked bijector is set");
   if (c->cfg.m_offset != 0 || c->M_total != c->cfg.n_mc) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a sharded context (m_offset / m_total)");
@@ -358,6 +362,7 @@ mivi_status_t mivi_optimize_loop_many(mivi_ctx_t *c, void *params, const mivi_lo
 // schedule), so this is the graph of launches with the batch of every step baked in (record_steps).
 mivi_status_t mivi_optimize_loop_batches(mivi_ctx_t *c, void *params, const mivi_loop_t *lp, int32_t first_batch) {
   if (!c || !params || !lp) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_flow(c, "mivi_optimize_loop_batches")) return rs;
   if (c->target != TGT_LOGREG || c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_batches: no batch schedule set (mivi_logreg_set_batch_schedule)");
   if (first_batch < 0 || lp->n_steps <= 0 || (long long)first_batch + lp->n_steps > c->lr_sched_n)
     return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_batches: first_batch + n_steps must lie inside the schedule");

@@ -226,6 +226,20 @@ struct ColTargetArgs {  // standalone per-column targets: Z -> (ell, G)
   int constrained;   // funnel: theta_1 = s itself (no built-in exp bijector / log-Jacobian)
 };
 
+// The RealNVP family's architecture (mivi_flow_t behind mivi_create_flow) as the kernels take it, and the layout of its parameter vector:
+// layers l = 1 .. L, each [s net; t net], a net [vec W_1; b_1; ...; vec W_{H+1}; b_{H+1}] from |B_l| inputs to |A_l| outputs.
+struct FlowArch {
+  int d, L, H;
+  int h[3];
+};
+__host__ __device__ inline int flow_nA(int d, int l) { return (l & 1) ? (d + 1) / 2 : d / 2; }   // |A_l|: the even coordinates for odd l, the odd ones for even l
+__host__ __device__ inline long long flow_net_len(const FlowArch &a, int nin, int nout) {
+  long long n = 0;
+  int prev = nin;
+  for (int j = 0; j < a.H; ++j) { n += (long long)a.h[j] * prev + a.h[j]; prev = a.h[j]; }
+  return n + (long long)nout * prev + nout;
+}
+
 // --------------------------------------------------------------------------------------------
 // Context
 // --------------------------------------------------------------------------------------------
@@ -532,6 +546,10 @@ struct mivi_ctx : mivi_ctx_streams {
   mivi::DevBuf ngd_est, natgrad_host;   // api_measure.hip: [logpi_avg or entropy (16 bytes); grad (d); hess (d x d)] of the _steps loops and the _host updates; [S; Sigma] of mivi_natgrad_update_host / Sigma of mivi_wass_update_host
   mivi::DevBuf h2_acc;             // second-order branch of the logistic-regression / funnel targets: f64 sums (kernels_hess2.hip)
   mivi::DevBuf lowr_E, lowr_V, lowr_prep, lowr_sx, lowr_part;   // low-rank family (kernels_lowrank.hip): the draws (d + r) x cap_M; V = Sigma^-1 (z - m), d x cap_M (t before that); the f64 prep block; f64 [s (r x cap_M); x (r x cap_M); |t|^2 (cap_M); log q (cap_M)]; the VJP's f64 partials, 8 slices x params_len
+  // RealNVP family (kernels_flow.hip): its architecture (L = 0: not a flow context); every layer's input and the last one's output, (L + 1) x cap_M x d;
+  // the f64 log q per sample; the VJP's f64 partials, flow_slices x params_len
+  mivi::FlowArch flow{};
+  mivi::DevBuf flow_X, flow_lq, flow_part;
   // base distribution of the location-scale families (mivi_set_base_dist; base_dist.h, kernels_basedist.hip, api_basedist.hip)
   int base = MIVI_BASE_NORMAL;
   double base_nu = 0.0, base_c0 = 0.0, base_H = 0.0;   // TDist's degrees of freedom; -(constant of log phi); H(phi) -- f64, computed once on the host
@@ -812,6 +830,14 @@ void launch_lowr_sample(mivi_ctx *c, const void *params, int M, void *Z, bool wi
 void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v, const LowrPoints *pts = nullptr);   // t -> s, x, log q (want_v: V over t)
 double *lowr_logq_of(const mivi_ctx *c, const LowrPoints &pts);   // where launch_lowr_woodbury leaves the f64 log q of pts' columns
 void launch_lowr_vjp_finish(mivi_ctx *c, const void *params, int M, int want_grad, const ValueIn &vin, const OutArgs &out);   // W = G (and V, x, the draws) -> out.grad; out.value, the non-finite flag, the elbo record
+
+// kernels_flow.hip: the RealNVP family's estimate, rand and logpdf (api_flow.hip drives them)
+long long flow_params_len(const FlowArch &a);
+int flow_slices(const FlowArch &a, int M);   // slices of the sample axis the VJP leaves partials for (<= 64, and at most 256 MB of them)
+bool flow_prepare(mivi_ctx *c);              // the kernels' LDS attributes, once per context (false: the runtime refused)
+void launch_flow_forward(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *Z, void *eps, bool save);   // draws -> Z (eps: the draws, or nullptr); save: every x^l -> flow_X, log q -> flow_lq
+void launch_flow_inverse(mivi_ctx *c, const void *params, const void *Z, int n, void *logq);   // log q at the caller's points (n <= kSampleChunk per launch)
+void launch_flow_vjp_finish(mivi_ctx *c, const void *params, int M, int want_grad, const ValueIn &vin, const OutArgs &out);   // W = grad ell (and flow_X, flow_lq) -> out.grad; out.value, the non-finite flag, the elbo record
 
 // kernels_logpdf.hip: logpdf(q, z) at the caller's points (api_logpdf.hip drives them); n <= kSampleChunk columns per launch
 void launch_stl_dinv32(mivi_ctx *c, const void *params, void *DinvT);   // kernels_fullrank.hip: k_stl_prep's diagonal workgroups alone

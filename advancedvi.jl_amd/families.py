@@ -10,8 +10,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-MEANFIELD, FULLRANK, LOWRANK = 0, 1, 2
+MEANFIELD, FULLRANK, LOWRANK, REALNVP = 0, 1, 2, 3
 LOWRANK_MAX_RANK = 64   # MIVI_LOWRANK_MAX_RANK (include/mivi.h)
+FLOW_MAX_D, FLOW_MAX_HIDDEN, FLOW_MAX_LAYERS = 128, 64, 32   # MIVI_FLOW_MAX_* (include/mivi.h)
 
 
 # --- univariate base distributions of MvLocationScale (docs/src/families.md:59-101): mivi_base_t codes, host statistics ---------------
@@ -211,17 +212,86 @@ def LowRankGaussian(mu, D, U) -> MvLocationScaleLowRank:
     return MvLocationScaleLowRank(np.asarray(mu), np.asarray(D), np.asarray(U))
 
 
+def flow_layout(d: int, hidden_dims, n_layers: int):
+    """The parameter vector of a RealNVP flow (MIVI_REALNVP, include/mivi.h), block by block: a list of
+    (layer l = 1 .. L, net "s" | "t", j = 1 .. H + 1, "W" | "b", offset, shape).  For l = 1 .. L the s net, then the t net; a net is
+    [vec W_1 (column-major, out x in); b_1; ...; vec W_{H+1}; b_{H+1}] from |B_l| inputs to |A_l| outputs, A_l the even coordinates
+    (0-based) for odd l and the odd ones for even l."""
+    blocks, off = [], 0
+    for l in range(1, n_layers + 1):
+        n_a = (d + 1) // 2 if l % 2 == 1 else d // 2
+        widths = [d - n_a, *hidden_dims, n_a]
+        for net in ("s", "t"):
+            for j in range(1, len(widths)):
+                out, inn = widths[j], widths[j - 1]
+                blocks.append((l, net, j, "W", off, (out, inn)))
+                off += out * inn
+                blocks.append((l, net, j, "b", off, (out,)))
+                off += out
+    return blocks, off
+
+
+class RealNVPFlow:
+    """The RealNVP normalizing flow of docs/src/tutorials/flows.md on a standard-normal base (`@leaf MvNormal`: the base has no
+    parameters): L affine coupling layers x[A] <- x[A] .* exp(s(x[B])) + t(x[B]) with alternating masks, s and t fully connected nets
+    with leakyrelu hidden layers (tanh on s's output).  `params` is the flat vector of `flow_layout`.  Arrays are numpy float32/float64."""
+
+    family = REALNVP
+
+    def __init__(self, d, hidden_dims, n_layers, params):
+        self.d, self.hidden_dims, self.n_layers = int(d), tuple(int(h) for h in hidden_dims), int(n_layers)
+        if not 2 <= self.d <= FLOW_MAX_D:
+            raise ValueError(f"RealNVP: the dimension must be in 2 .. {FLOW_MAX_D}")
+        if not 1 <= len(self.hidden_dims) <= 3 or not all(1 <= h <= FLOW_MAX_HIDDEN for h in self.hidden_dims):
+            raise ValueError(f"RealNVP: one to three hidden layers of width 1 .. {FLOW_MAX_HIDDEN}")
+        if not 1 <= self.n_layers <= FLOW_MAX_LAYERS:
+            raise ValueError(f"RealNVP: n_layers must be in 1 .. {FLOW_MAX_LAYERS}")
+        self.params = np.ascontiguousarray(params)
+        if self.params.dtype not in (np.float32, np.float64):
+            raise TypeError("RealNVP: eltype must be Float32 or Float64")
+        if self.params.shape != (flow_layout(self.d, self.hidden_dims, self.n_layers)[1],):
+            raise ValueError("flat parameter vector has the wrong length")
+
+    def __len__(self):
+        return self.d
+
+    @property
+    def eltype(self):
+        return self.params.dtype
+
+    def blocks(self):
+        """{(l, net, j, "W" | "b"): array view} of the parameter vector (W as an out x in matrix)."""
+        return {(l, net, j, k): self.params[off:off + int(np.prod(shape))].reshape(shape, order="F")
+                for l, net, j, k, off, shape in flow_layout(self.d, self.hidden_dims, self.n_layers)[0]}
+
+
+def RealNVP(d, hidden_dims, n_layers, eltype=np.float64, rng=None) -> RealNVPFlow:
+    """realnvp(MvNormal(zeros(d), I), hidden_dims, n_layers) of docs/src/tutorials/flows.md:199-207: Glorot-uniform weights from a seeded
+    numpy generator (an int seed or a Generator; None: seed 0), zero biases."""
+    gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(0 if rng is None else rng)
+    blocks, n = flow_layout(int(d), tuple(hidden_dims), int(n_layers))
+    flat = np.zeros(n, dtype=np.float64)
+    for _, _, _, kind, off, shape in blocks:
+        if kind == "W":
+            lim = math.sqrt(6.0 / (shape[0] + shape[1]))
+            flat[off:off + shape[0] * shape[1]] = gen.uniform(-lim, lim, size=shape[0] * shape[1])
+    return RealNVPFlow(d, hidden_dims, n_layers, flat.astype(eltype))
+
+
 class Restructure:
     """The `re` closure returned by Optimisers.destructure; RestructureMeanField for the
     Diagonal case (src/families/location_scale.jl:28-37)."""
 
-    def __init__(self, d: int, family: int, dtype, rank: int = 0, dist=None):
+    def __init__(self, d: int, family: int, dtype, rank: int = 0, dist=None, flow=None):
         self.d, self.family, self.dtype, self.rank = d, family, dtype, rank
         self.dist = dist if dist is not None else Normal()   # carried through, as re.model.dist (location_scale.jl:32-37)
+        self.flow = flow   # REALNVP: (hidden_dims, n_layers)
 
     def __call__(self, flat):
         flat = np.asarray(flat, dtype=self.dtype)
         d = self.d
+        if self.family == REALNVP:
+            return RealNVPFlow(d, self.flow[0], self.flow[1], flat.copy())
         if self.family == LOWRANK:
             if flat.shape[0] != 2 * d + d * self.rank:
                 raise ValueError("flat parameter vector has the wrong length")
@@ -240,8 +310,11 @@ def destructure(q):
     mean-field: [location; diag(scale)], length 2d   (src/families/location_scale.jl:39-43)
     full-rank : [location; vec(scale)] column-major, length d + d^2, strict upper triangle zero
     low-rank  : [location; scale_diag; vec(scale_factors)] column-major, length 2d + d r (the functor's field order,
-                src/families/location_scale_low_rank.jl:41)."""
+                src/families/location_scale_low_rank.jl:41).
+    RealNVP   : the nets' weights and biases, layer by layer (flow_layout)."""
     d = len(q)
+    if q.family == REALNVP:   # the flow's own flat vector (flow_layout)
+        return q.params.copy(), Restructure(d, REALNVP, q.eltype, flow=(q.hidden_dims, q.n_layers))
     if q.family == LOWRANK:
         flat = np.concatenate([q.location, q.scale_diag, q.scale_factors.reshape(-1, order="F")])
         return flat.astype(q.eltype, copy=False), Restructure(d, LOWRANK, q.eltype, q.rank)

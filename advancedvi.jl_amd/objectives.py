@@ -18,7 +18,7 @@ import numpy as np
 
 from . import problems as P
 from .context import MiviContext
-from .families import MvLocationScale, MvLocationScaleLowRank, destructure
+from .families import MvLocationScale, MvLocationScaleLowRank, RealNVPFlow, destructure
 
 
 _log = logging.getLogger("advancedvi_jl_amd")
@@ -177,12 +177,24 @@ def _ad_problem(adtype, prob, announce=True):
     return P.ADgradient(kind, prob)
 
 
+_NO_FLOW_ENTROPY = ("a normalizing flow (RealNVP) has no entropy(q): {} cannot be used with it -- use `MonteCarloEntropy()` or "
+                    "`StickingTheLandingEntropy()` (docs/src/tutorials/flows.md:213)")
+
+
+def _flow_arch(q):
+    """the `flow` argument of MiviContext for q (None unless q is a RealNVPFlow)"""
+    return (q.hidden_dims, q.n_layers) if isinstance(q, RealNVPFlow) else None
+
+
 def _make_ctx(rng, obj, adtype, q, prob, n_mc=None, entropy=None):
-    if not isinstance(q, (MvLocationScale, MvLocationScaleLowRank)):
-        raise TypeError("libmivi implements the RepGradELBO path for MvLocationScale and MvLocationScaleLowRank families only")
+    if not isinstance(q, (MvLocationScale, MvLocationScaleLowRank, RealNVPFlow)):
+        raise TypeError("libmivi implements the RepGradELBO path for MvLocationScale, MvLocationScaleLowRank and RealNVP families only")
+    ent = entropy or obj.entropy
+    if isinstance(q, RealNVPFlow) and ent.code not in (MonteCarloEntropy.code, StickingTheLandingEntropy.code):
+        raise TypeError(_NO_FLOW_ENTROPY.format(f"`{type(ent).__name__}`"))
     device = getattr(adtype, "device", 0)
     ctx = MiviContext(q.eltype, q.family, len(q), n_mc or obj.n_samples,
-                      (entropy or obj.entropy).code, rng.seed, device=device, rank=getattr(q, "rank", 0))
+                      ent.code, rng.seed, device=device, rank=getattr(q, "rank", 0), flow=_flow_arch(q))
     try:
         ctx.set_base_dist(getattr(q, "dist", None))   # MvLocationScale(location, scale, dist); the low-rank family: Normal() only
         ctx.set_problem(prob)
@@ -193,6 +205,9 @@ def _make_ctx(rng, obj, adtype, q, prob, n_mc=None, entropy=None):
 
 
 def _make_score_ctx(rng, obj, adtype, q, prob):
+    if isinstance(q, RealNVPFlow):
+        raise TypeError("ScoreGradELBO is not implemented for a normalizing flow (RealNVP): use RepGradELBO (KLMinRepGradDescent) with "
+                        "`MonteCarloEntropy()` or `StickingTheLandingEntropy()`")
     if isinstance(q, MvLocationScaleLowRank):
         raise TypeError("ScoreGradELBO is not implemented for the low-rank family (MvLocationScaleLowRank): use RepGradELBO "
                         "(KLMinRepGradDescent), or a MeanFieldGaussian / FullRankGaussian")
@@ -296,11 +311,17 @@ class TransformedDistribution:
         return len(self.q)
 
 
+def _plain_entropy(q):
+    """the estimator code of a context that only samples or scores q (never read there): a flow context admits no closed-form kind"""
+    return MonteCarloEntropy.code if isinstance(q, RealNVPFlow) else 0
+
+
 def rand(rng, q, num_samples: int, device: int = 0):
     """rand(rng, q, num_samples): d x num_samples samples (location_scale.jl:71-87, location_scale_low_rank.jl:66-100), returned as a
     device tensor (column m = sample m).  q::TransformedDistribution: the draws of q.q pushed through the bijector (constrained)."""
     qt, q = (q, q.q) if isinstance(q, TransformedDistribution) else (None, q)
-    ctx = MiviContext(q.eltype, q.family, len(q), num_samples, 0, rng.seed, device=device, rank=getattr(q, "rank", 0))
+    ctx = MiviContext(q.eltype, q.family, len(q), num_samples, _plain_entropy(q), rng.seed, device=device, rank=getattr(q, "rank", 0),
+                      flow=_flow_arch(q))
     try:
         ctx.set_base_dist(getattr(q, "dist", None))
         params, _ = destructure(q)
@@ -318,7 +339,7 @@ def logpdf(q, z, device: int = 0):
     z of shape (d,): a Python float.  z of shape (d, n), numpy or device tensor: a device tensor of n values in q.eltype.
     q::TransformedDistribution: z are constrained points, the value is log q.q(b(z)) - logabsdetjac(binv, b(z)); -inf outside the support."""
     qt, q = (q, q.q) if isinstance(q, TransformedDistribution) else (None, q)
-    ctx = MiviContext(q.eltype, q.family, len(q), 1, 0, 0, device=device, rank=getattr(q, "rank", 0))
+    ctx = MiviContext(q.eltype, q.family, len(q), 1, _plain_entropy(q), 0, device=device, rank=getattr(q, "rank", 0), flow=_flow_arch(q))
     try:
         ctx.set_base_dist(getattr(q, "dist", None))
         params, _ = destructure(q)

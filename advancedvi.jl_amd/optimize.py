@@ -10,7 +10,7 @@ import numpy as np
 
 from . import objectives as O
 from . import subsampling as S
-from .families import LOWRANK, MvLocationScale, MvLocationScaleLowRank, destructure
+from .families import LOWRANK, REALNVP, MvLocationScale, MvLocationScaleLowRank, RealNVPFlow, destructure
 
 
 # --- operators (src/optimization/clip_scale.jl, src/AdvancedVI.jl:173-204) ------------------------
@@ -26,12 +26,18 @@ class ClipScale:
         self.epsilon = epsilon
 
     def apply(self, ctx, params, optimizer=None, opt_st=None):
+        if ctx.family == REALNVP:
+            raise TypeError(_NO_SCALE_FLOW.format("ClipScale"))
         ctx.clip_scale(params, self.epsilon)
         return params
 
 
 _NO_PROX_LOWRANK = ("`ProximalLocationScaleEntropy` has no method for the low-rank family (MvLocationScaleLowRank), as in the reference "
                     "(proximal_location_scale_entropy.jl:44): use `ClipScale`")
+
+
+_NO_SCALE_FLOW = ("`{}` has no method for a normalizing flow (RealNVP): the family has no scale -- use `IdentityOperator()` "
+                  "(docs/src/tutorials/flows.md:212-215)")
 
 
 class ProximalLocationScaleEntropy:
@@ -42,6 +48,8 @@ class ProximalLocationScaleEntropy:
     def apply(self, ctx, params, optimizer=None, opt_st=None):
         if ctx.family == LOWRANK:
             raise TypeError(_NO_PROX_LOWRANK)
+        if ctx.family == REALNVP:
+            raise TypeError(_NO_SCALE_FLOW.format("ProximalLocationScaleEntropy"))
         if isinstance(optimizer, DoG):            # DoWG is a subclass
             ctx.prox_scale_entropy(params, 0.0, opt_st, optimizer.kind)
         elif isinstance(optimizer, Descent):
@@ -255,6 +263,8 @@ def init(rng, alg, q_init, prob):
         return M.init(rng, alg, q_init, prob)
     if isinstance(q_init, MvLocationScaleLowRank) and isinstance(alg.operator, ProximalLocationScaleEntropy):
         raise TypeError(_NO_PROX_LOWRANK)
+    if isinstance(q_init, RealNVPFlow) and isinstance(alg.operator, (ClipScale, ProximalLocationScaleEntropy)):
+        raise TypeError(_NO_SCALE_FLOW.format(type(alg.operator).__name__))
     if isinstance(q_init, (MvLocationScale, MvLocationScaleLowRank)) and isinstance(alg.operator, IdentityOperator):
         warnings.warn(
             "IdentityOperator is used with a variational family <:MvLocationScale. Optimization can easily fail under "
@@ -462,6 +472,8 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
     if state is None:
         state = init(rng, algorithm, q_init, prob)
     codes = _device_loop_codes(algorithm, callback, objargs, state.get("prob")) if device_loop else None
+    if isinstance(algorithm.objective, S.SubsampledObjective) and _ctx_of(state["obj_st"]).family == REALNVP:
+        codes = None   # the batch schedule has no form for a flow: subsampled steps keep the host loop (mivi_logreg_select_rows per step)
     if codes is not None and max_iter > 0:
         state = dict(state)
         info_dev = _optimize_on_device(rng, algorithm, max_iter, state, codes, show_progress)
@@ -685,6 +697,9 @@ def optimize_many(rngs, algorithm, max_iter: int, probs, q_inits, *, states=None
     algs = _per_run(algorithm, K, "algorithm")
     probs = _per_run(probs, K, "probs")
     qs = _per_run(q_inits, K, "q_inits")
+    if any(isinstance(q, RealNVPFlow) for q in qs):
+        raise TypeError("optimize_many has no method for a normalizing flow (RealNVP): its runs are small Gaussian families, one "
+                        "workgroup each -- call `optimize` once per run")
     if states is None:
         states = [None] * K
     elif isinstance(states, dict) or len(states) != K or not all(isinstance(s, dict) for s in states):

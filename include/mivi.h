@@ -61,8 +61,37 @@ typedef enum { MIVI_F32 = 0, MIVI_F64 = 1 } mivi_dtype_t;
  * the DoG entries, and mivi_optimize_steps / _loop as a graph of launches (op 0 or 1).  Every other entry that reads parameters returns
  * MIVI_ERR_UNSUPPORTED on it (the score-gradient and measure-space entries, partials / finalize / dist / p2p, the profile entries,
  * mivi_prox_scale_entropy and op = 2: the reference has no ProximalLocationScaleEntropy method for the family). */
-typedef enum { MIVI_MEANFIELD = 0, MIVI_FULLRANK = 1, MIVI_LOWRANK = 2 } mivi_family_t;
+typedef enum { MIVI_MEANFIELD = 0, MIVI_FULLRANK = 1, MIVI_LOWRANK = 2, MIVI_REALNVP = 3 } mivi_family_t;
 #define MIVI_LOWRANK_MAX_RANK 64
+
+/* MIVI_REALNVP: the RealNVP normalizing flow of docs/src/tutorials/flows.md (Dinh et al.; the masks and activations of
+ * NormalizingFlows.realnvp), created by mivi_create_flow.  All index sets are 0-based.
+ *   base     eps ~ N(0, I_d): the mean-field family's Philox stream, d rows.  No parameters.
+ *   layers   l = 1 .. n_layers, x^0 = eps, z = x^L.  A_l = {0, 2, 4, ...} for odd l, {1, 3, 5, ...} for even l, B_l the rest;
+ *            c = x^{l-1}[B_l], a = x^{l-1}[A_l];  x^l[B_l] = c,  x^l[A_l] = a .* exp(s_l(c)) + t_l(c)
+ *   nets     each |B_l| -> hidden[0] -> ... -> hidden[n_hidden - 1] -> |A_l|; hidden layers leakyrelu(W_j . + b_j) with slope 0.01, the
+ *            output W . + b; s_l applies tanh to it, t_l nothing
+ *   log q    log q(z) = -1/2 |eps|^2 - d/2 log 2 pi - sum_l 1' s_l(c_l) at eps = T^-1(z); inverse layer: a = (y_A - t(c)) .* exp(-s(c))
+ *   params   for l = 1 .. L: the s net, then the t net; a net is [vec W_1 (column-major, out x in); b_1; ...; vec W_{H+1}; b_{H+1}]
+ *   limits   2 <= d <= 128, 1 <= hidden[j] <= 64, 1 <= n_hidden <= 3, 1 <= n_layers <= 32, any n_mc >= 1
+ *   entropy  MIVI_ENT_MONTE_CARLO and MIVI_ENT_STL: value = mean[-ell(z_m) + log q(z_m)] for both (ell includes the bijector's
+ *            logabsdetjac); the others need entropy(q), which a flow does not have: MIVI_ERR_UNSUPPORTED
+ * What family 3 supports: destroy / synchronize / set_stream / params_len, every mivi_set_target_* and mivi_set_bijector_stacked[_ex],
+ * mivi_sample (eps_dev: T[d * n_mc]) / mivi_sample_constrained, mivi_logpdf[_host] (std NULL) / mivi_logpdf_constrained[_host],
+ * mivi_estimate_gradient[_host / _n / _each] (the batched forms as sequential single calls), mivi_estimate_objective[_host], the update
+ * entries without a scale (descent / adam / cocob / DoG), and mivi_optimize_steps / _loop as a graph of launches with op 0 (op 1 and 2:
+ * MIVI_ERR_UNSUPPORTED -- ClipScale and the proximal operator have no method for a family without a scale; mivi_clip_scale likewise).
+ * mivi_set_base_dist accepts MIVI_BASE_NORMAL, which changes nothing, and refuses every other base.  Every other entry that reads
+ * parameters returns MIVI_ERR_UNSUPPORTED on it with a message naming the entry and the family: what the low-rank family is refused on,
+ * and the batch schedule (mivi_logreg_set_batch_schedule / _seek_batch, mivi_optimize_loop_batches), which the low-rank family has. */
+#define MIVI_FLOW_MAX_D 128
+#define MIVI_FLOW_MAX_HIDDEN 64
+#define MIVI_FLOW_MAX_LAYERS 32
+typedef struct {
+  int32_t n_layers;   /* L, 1 .. MIVI_FLOW_MAX_LAYERS */
+  int32_t n_hidden;   /* H, 1 .. 3 hidden layers per net */
+  int32_t hidden[3];  /* their widths, 1 .. MIVI_FLOW_MAX_HIDDEN (entries from n_hidden on are not read) */
+} mivi_flow_t;
 
 /* src/algorithms/entropy.jl: ClosedFormEntropy :25-29, ClosedFormEntropyZeroGradient :11-15,
  * MonteCarloEntropy :40-46, StickingTheLandingEntropy :57-65, StickingTheLandingEntropyZeroGradient :78-90 */
@@ -98,6 +127,10 @@ typedef struct mivi_ctx mivi_ctx_t;
  * MIVI_LOWRANK: MIVI_ERR_BAD_ARG unless 1 <= rank <= MIVI_LOWRANK_MAX_RANK; MIVI_ERR_UNSUPPORTED for a sharded context (m_offset != 0 or
  * m_total not in {0, n_mc}). */
 mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out);
+/* A MIVI_REALNVP context (cfg->family must be MIVI_REALNVP; mivi_create answers MIVI_ERR_BAD_ARG for that family).  MIVI_ERR_BAD_ARG
+ * outside the limits above; MIVI_ERR_UNSUPPORTED for an entropy kind other than MIVI_ENT_MONTE_CARLO / MIVI_ENT_STL and for a sharded
+ * context (m_offset != 0 or m_total not in {0, n_mc}). */
+mivi_status_t mivi_create_flow(const mivi_config_t *cfg, const mivi_flow_t *flow, mivi_ctx_t **out);
 mivi_status_t mivi_destroy(mivi_ctx_t *ctx);
 const char *mivi_last_error(const mivi_ctx_t *ctx);
 int32_t mivi_version(void);
