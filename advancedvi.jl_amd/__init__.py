@@ -5,7 +5,7 @@ Everything numerical is a hand-written HIP kernel in libmivi.so (csrc/, C ABI in
 this package is the host-side mirror of the reference's operator interface for that path."""
 from ._lib import LIB_PATH, MiviError, load as load_library
 from .families import (MvLocationScale, MeanFieldGaussian, FullRankGaussian, MvLocationScaleLowRank, LowRankGaussian, Restructure, destructure,
-                       MEANFIELD, FULLRANK, LOWRANK, REALNVP, RealNVP, RealNVPFlow, flow_layout, Normal, Laplace, TDist)
+                       MEANFIELD, FULLRANK, LOWRANK, REALNVP, RealNVP, RealNVPFlow, flow_layout, NSF, NeuralSplineFlow, SplineFlow, nsf_layout, Normal, Laplace, TDist)
 from .problems import (LogDensityOrder, DiagNormalProblem, DenseNormalProblem, LogRegProblem, FunnelProblem,
                        dimension, capabilities)
 from .objectives import (RepGradELBO, RepGradELBOState, ScoreGradELBO, ScoreGradELBOState, ClosedFormEntropy, ClosedFormEntropyZeroGradient,

@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "libmivi.so")
 
 MIVI_OK, ERR_BAD_ARG, ERR_NONFINITE, ERR_NONPOSITIVE_SCALE, ERR_HIP, ERR_NO_TARGET, ERR_UNSUPPORTED = range(7)
 F32, F64 = 0, 1
-MEANFIELD, FULLRANK, LOWRANK, REALNVP = 0, 1, 2, 3
+MEANFIELD, FULLRANK, LOWRANK, REALNVP, NSF = 0, 1, 2, 3, 4
 BASE_NORMAL, BASE_LAPLACE, BASE_TDIST = 0, 1, 2
 
 
@@ -27,6 +27,10 @@ class MiviFlow(C.Structure):   # mivi_flow_t: the architecture of a MIVI_REALNVP
     _fields_ = [("n_layers", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3)]
 
 
+class MiviSplineFlow(C.Structure):   # mivi_spline_flow_t: the architecture of a MIVI_NSF context (mivi_create_spline_flow)
+    _fields_ = [("n_layers", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3), ("n_bins", C.c_int32), ("bound", C.c_double)]
+
+
 LOGDENSITY_AND_GRADIENT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p)
 LOGDENSITY_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)
 LOGDENSITY_GRADIENT_AND_HESSIAN_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -35,6 +39,7 @@ LOGDENSITY_GRADIENT_AND_HESSIAN_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void
 SIGNATURES = {
     "mivi_create": (C.c_int32, [C.POINTER(MiviConfig), C.POINTER(C.c_void_p)]),
     "mivi_create_flow": (C.c_int32, [C.POINTER(MiviConfig), C.POINTER(MiviFlow), C.POINTER(C.c_void_p)]),
+    "mivi_create_spline_flow": (C.c_int32, [C.POINTER(MiviConfig), C.POINTER(MiviSplineFlow), C.POINTER(C.c_void_p)]),
     "mivi_destroy": (C.c_int32, [C.c_void_p]),
     "mivi_last_error": (C.c_char_p, [C.c_void_p]),
     "mivi_version": (C.c_int32, []),

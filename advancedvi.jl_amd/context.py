@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .families import FULLRANK, LOWRANK, MEANFIELD, REALNVP
+from .families import FULLRANK, LOWRANK, MEANFIELD, NSF, REALNVP
 from . import problems as P
 
 NATGRAD_SMALL_D = 44   # MIVI_NATGRAD_SMALL_D (include/mivi.h): up to this d mivi_natgrad_update is the one-workgroup kernel, above it the tile path
@@ -33,7 +33,8 @@ class MiviContext:
     """One RepGradELBO estimator instance on one GPU (mivi_create ... mivi_destroy)."""
 
     def __init__(self, dtype, family, d, n_mc, entropy, seed, device=0, m_offset=0, m_total=0, stream=None, rank=0, flow=None):
-        """flow: (hidden_dims, n_layers) of a REALNVP context (mivi_create_flow); not read for the other families."""
+        """flow: (hidden_dims, n_layers) of a REALNVP context (mivi_create_flow), (hidden_dims, n_layers, n_bins, bound) of an NSF
+        context (mivi_create_spline_flow); not read for the other families."""
         torch = _torch()
         self.lib = _lib.load()
         self.np_dtype = np.dtype(dtype)
@@ -61,6 +62,20 @@ class MiviContext:
                 sharded = int(m_offset) != 0 or int(m_total) not in (0, self.n_mc)
                 raise _lib.MiviError(st, "mivi_create_flow: the RealNVP family has no sharded form (m_offset / m_total)" if sharded else
                                          "mivi_create_flow: a flow has no entropy(q) -- the estimators that work on it are MonteCarloEntropy "
+                                         "and StickingTheLandingEntropy")
+        elif self.family == NSF:
+            if flow is None or len(flow) != 4:
+                raise ValueError("an NSF context needs flow = (hidden_dims, n_layers, n_bins, bound)")
+            hidden = [int(w) for w in flow[0]]
+            if not 1 <= len(hidden) <= 3:
+                raise ValueError("NeuralSplineFlow: one to three hidden layers")
+            self.flow = (tuple(hidden), int(flow[1]), int(flow[2]), float(flow[3]))
+            arch = _lib.MiviSplineFlow(int(flow[1]), len(hidden), (C.c_int32 * 3)(*(hidden + [0] * (3 - len(hidden)))), int(flow[2]), float(flow[3]))
+            st = self.lib.mivi_create_spline_flow(C.byref(cfg), C.byref(arch), C.byref(h))
+            if st == 6:   # MIVI_ERR_UNSUPPORTED before a context exists to carry the message
+                sharded = int(m_offset) != 0 or int(m_total) not in (0, self.n_mc)
+                raise _lib.MiviError(st, "mivi_create_spline_flow: the neural spline flow family has no sharded form (m_offset / m_total)" if sharded else
+                                         "mivi_create_spline_flow: a flow has no entropy(q) -- the estimators that work on it are MonteCarloEntropy "
                                          "and StickingTheLandingEntropy")
         else:
             st = self.lib.mivi_create(C.byref(cfg), C.byref(h))

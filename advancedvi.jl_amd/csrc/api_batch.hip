@@ -471,7 +471,7 @@ static mivi_status_t record_lane_branch(mivi_ctx *c, mivi_ctx *const *ctxs, int 
 mivi_status_t mivi_estimate_gradient_n(mivi_ctx_t *c, const void *params, uint64_t idx0, int32_t count, void *value, void *grad) {
   if (!c || !params || !value || !grad || count <= 0) return MIVI_ERR_BAD_ARG;
   (void)hipSetDevice(c->cfg.device);
-  if (c->cfg.family == MIVI_LOWRANK || c->cfg.family == MIVI_REALNVP || c->base != MIVI_BASE_NORMAL) {   // the single calls, one after the other: no lanes, no child contexts, no engine, no graph
+  if (c->cfg.family == MIVI_LOWRANK || is_flow(c) || c->base != MIVI_BASE_NORMAL) {   // the single calls, one after the other: no lanes, no child contexts, no engine, no graph
     mivi_status_t sl = MIVI_OK;
     for (int i = 0; i < count && sl == MIVI_OK; ++i) sl = run_estimate(c, params, rng_of(c, idx0 + (uint64_t)i), c->cfg.n_mc, 1, final_out(c, value, grad));
     return sl;

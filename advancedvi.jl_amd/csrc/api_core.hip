@@ -236,7 +236,7 @@ mivi_status_t ensure_work(mivi_ctx *c, int M) {
       if (d % 128 == 0 && (s = ensure(c, c->stl_F, mivi::stl_pack_units(d) * 4, false))) return s;   // + developer stamp page (MIVI_STL_STAMPS)
     }
     if (c->cfg.family == MIVI_LOWRANK && (s = ensure_work_lowrank(c, capM))) return s;
-    if (c->cfg.family == MIVI_REALNVP && (s = ensure_work_flow(c, capM))) return s;
+    if (is_flow(c) && (s = ensure_work_flow(c, capM))) return s;
     if (c->base != MIVI_BASE_NORMAL && (s = ensure_work_base(c, capM))) return s;
     if ((s = ensure(c, c->Z, (size_t)d * capM * es, false))) return s;
     if ((s = ensure(c, c->W, (size_t)d * capM * es, false))) return s;
@@ -257,18 +257,22 @@ const char *mivi_last_error(const mivi_ctx_t *ctx) { return ctx ? ctx->err.c_str
 int64_t mivi_params_len(const mivi_ctx_t *c) {
   const int64_t d = c->cfg.d;
   if (c->cfg.family == MIVI_LOWRANK) return 2 * d + d * (int64_t)c->cfg.rank;
-  if (c->cfg.family == MIVI_REALNVP) return flow_params_len(c->flow);
+  if (is_flow(c)) return flow_params_len(c->flow);
   return c->cfg.family == MIVI_MEANFIELD ? 2 * d : d + d * d;
 }
 int64_t mivi_partials_len(const mivi_ctx_t *c) {
   const int64_t d = c->cfg.d;
-  if (c->cfg.family == MIVI_LOWRANK || c->cfg.family == MIVI_REALNVP) return 0;   // no sharded estimates
+  if (c->cfg.family == MIVI_LOWRANK || is_flow(c)) return 0;   // no sharded estimates
   return (c->cfg.family == MIVI_MEANFIELD ? 2 * d : d + d * (d + 1) / 2) + 2;
 }
 
 mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out) {
   if (cfg && cfg->family == MIVI_REALNVP) {
     fprintf(stderr, "libmivi: mivi_create: the RealNVP family (MIVI_REALNVP) takes its architecture through mivi_create_flow\n");
+    return MIVI_ERR_BAD_ARG;
+  }
+  if (cfg && cfg->family == MIVI_NSF) {
+    fprintf(stderr, "libmivi: mivi_create: the neural spline flow family (MIVI_NSF) takes its architecture through mivi_create_spline_flow\n");
     return MIVI_ERR_BAD_ARG;
   }
   return create_context(cfg, nullptr, out);
@@ -279,7 +283,7 @@ mivi_status_t create_context(const mivi_config_t *cfg, const mivi::FlowArch *flo
   if (!cfg || !out) return MIVI_ERR_BAD_ARG;
   if (cfg->d <= 0 || cfg->n_mc <= 0) return MIVI_ERR_BAD_ARG;
   if (cfg->dtype != MIVI_F32 && cfg->dtype != MIVI_F64) return MIVI_ERR_BAD_ARG;
-  if (cfg->family != MIVI_MEANFIELD && cfg->family != MIVI_FULLRANK && cfg->family != MIVI_LOWRANK && !(cfg->family == MIVI_REALNVP && flow)) return MIVI_ERR_BAD_ARG;
+  if (cfg->family != MIVI_MEANFIELD && cfg->family != MIVI_FULLRANK && cfg->family != MIVI_LOWRANK && !((cfg->family == MIVI_REALNVP || cfg->family == MIVI_NSF) && flow)) return MIVI_ERR_BAD_ARG;
   if (cfg->family == MIVI_LOWRANK) {   // (rank is read for this family only)
     if (cfg->rank < 1 || cfg->rank > MIVI_LOWRANK_MAX_RANK) return MIVI_ERR_BAD_ARG;
     if (cfg->m_offset != 0 || (cfg->m_total != 0 && cfg->m_total != cfg->n_mc)) return MIVI_ERR_UNSUPPORTED;   // no sharded low-rank estimates

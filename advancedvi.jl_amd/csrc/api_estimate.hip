@@ -224,7 +224,7 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
   const bool gen2 = c->cfg.family == MIVI_FULLRANK && c->base == MIVI_BASE_NORMAL && lds_route(c, params, M, want_grad, out);
   if (!gen2 && !fr_prepare(c, M)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");   // (cached: a compare per estimate)
   if (c->cfg.family == MIVI_LOWRANK) return run_estimate_lowrank(c, params, rng, M, want_grad, out);   // (its own kernels; nothing below knows the family)
-  if (c->cfg.family == MIVI_REALNVP) return run_estimate_flow(c, params, rng, M, want_grad, out);
+  if (is_flow(c)) return run_estimate_flow(c, params, rng, M, want_grad, out);
   if (c->base != MIVI_BASE_NORMAL) return run_estimate_base(c, params, rng, M, want_grad, out);   // (everything below draws its own normals)
   if (gen2) return run_estimate_lds(c, params, rng, M, want_grad, out, ch, upd, stop_after_target);
   ValueIn vin{};
@@ -357,7 +357,7 @@ mivi_status_t mivi_sample(mivi_ctx_t *c, const void *params, uint64_t idx, void 
   if (s) return s;
   if (c->cfg.family == MIVI_FULLRANK && !fr_prepare(c, M)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
   if (c->cfg.family == MIVI_LOWRANK) return sample_lowrank(c, params, idx, Z, eps);
-  if (c->cfg.family == MIVI_REALNVP) return sample_flow(c, params, idx, Z, eps);
+  if (is_flow(c)) return sample_flow(c, params, idx, Z, eps);
   if (c->base != MIVI_BASE_NORMAL) return sample_base(c, params, idx, Z, eps);
   if (c->cfg.family == MIVI_MEANFIELD) {
     launch_sample_mf(c, params, rng_of(c, idx), M, Z, eps, d, nullptr);

@@ -25,7 +25,7 @@ mivi_status_t logpdf_launches(mivi_ctx *c, const void *params, const char *Z, in
   const size_t d = c->cfg.d, es = c->esize;
   const int cap = n < kSampleChunk ? n : kSampleChunk;
   mivi_status_t s;
-  if (c->cfg.family == MIVI_REALNVP)   // eps = T^-1(z) through the inverse layers, log q beside it: no parameter-only stage, no scratch
+  if (is_flow(c))   // eps = T^-1(z) through the inverse layers, log q beside it: no parameter-only stage, no scratch
     return for_each_chunk(c, 0, n, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
       launch_flow_inverse(c, params, chunk_points(c, k, Z, bij), k.Mc, logq + (size_t)k.off * es);
       chunk_finish(c, k, logq, bij);

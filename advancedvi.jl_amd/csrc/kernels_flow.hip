@@ -14,19 +14,16 @@
 //                    code as the forward pass: bitwise the same activations); the parameter gradients of its tiles are summed, tile after
 //                    tile, into the slice's own f64 partial vector -- no atomics
 //   k_flow_finish    gradient = the slices' partials summed in slice order; value = mean[-ell + log q]
-#include "mivi_internal.h"
-#include "device_common.h"
+#include "flow_tile.h"
 
 namespace mivi {
 
-// (the forward pass saves ALL 16 columns of a tile to flow_X and the VJP reads them back: the planes hold cap_M columns, and ensure_work
-//  rounds cap_M up to a multiple of 64, so a launch's last tile ends inside its own plane -- launch_flow_forward checks it)
-constexpr int kFlowTile = 16;            // samples per tile
-constexpr int kFlowBlk = 64 * kFlowTile;   // elements of one [64][16] block
-constexpr int kFlowMaxSlices = 64;
-
 long long flow_params_len(const FlowArch &a) {
   long long n = 0;
+  if (a.K) {   // the neural spline flow: one net per layer, 3K - 1 outputs per transformed coordinate
+    for (int l = 1; l <= a.L; ++l) n += flow_net_len(a, a.d - flow_nA(a.d, l), flow_nA(a.d, l) * nsf_rows(a));
+    return n;
+  }
   for (int l = 1; l <= a.L; ++l) n += 2 * flow_net_len(a, a.d - flow_nA(a.d, l), flow_nA(a.d, l));
   return n;
 }
@@ -37,28 +34,10 @@ int flow_slices(const FlowArch &a, int M) {
   return ns < 1 ? 1 : (int)ns;
 }
 
-template <typename T>
-struct FlowArgs {
-  FlowArch a;
-  int M, capM;         // samples of this launch; columns of X's planes
-  const T *params;
-  RngArgs rng;
-  T *X;                // [L + 1][capM][d]: x^0 = eps ... x^L = z (or nullptr: not saved)
-  T *Z, *eps;          // d x M outputs, ld = d (or nullptr)
-  const T *Zin;        // k_flow_inverse: the points, d x M
-  T *logq;             // k_flow_inverse: log q per point
-  const T *Wg;         // k_flow_vjp: grad_z ell, d x M (ld = d)
-  double *lq;          // f64 log q per sample
-  double *part;        // [n_slices][params_len] f64
-  int kind;            // MIVI_ENT_MONTE_CARLO or MIVI_ENT_STL
-  double invM;
-};
-
 __device__ __forceinline__ float flow_exp(float x) { return expf(x); }
 __device__ __forceinline__ double flow_exp(double x) { return exp(x); }
 __device__ __forceinline__ float flow_tanh(float x) { return tanhf(x); }
 __device__ __forceinline__ double flow_tanh(double x) { return tanh(x); }
-__device__ __forceinline__ int round16(int x) { return (x + 15) & ~15; }
 // where layer l's parameters start: the layers before it are l / 2 odd ones and (l - 1) / 2 even ones
 __device__ __forceinline__ long long flow_layer_off(const FlowArch &a, int l) {
   const int nA1 = flow_nA(a.d, 1), nA2 = flow_nA(a.d, 2);
@@ -173,34 +152,6 @@ __device__ T *flow_net_backward(const FlowArch &a, const T *np, int nin, int nou
   return dcur;
 }
 
-// c = x[B_l] -> H0 (zero rows up to a multiple of 16) from a [d][16] block
-template <typename T>
-__device__ __forceinline__ void flow_take_c(const T *XC, T *H0, int nB, int pa) {
-  for (int e = threadIdx.x; e < round16(nB) * 16; e += 64) {
-    const int j = e >> 4, m = e & 15;
-    H0[e] = j < nB ? XC[(2 * j + 1 - pa) * 16 + m] : T(0);
-  }
-  __syncthreads();
-}
-// a tile of a d x * plane (ld = d) <-> a [d][16] block; columns from n_ok on read as zero / are not stored
-template <typename T>
-__device__ __forceinline__ void flow_load_tile(const T *src, T *blk, int d, int n_ok, T scale = T(1)) {
-  for (int e = threadIdx.x; e < 16 * d; e += 64) {
-    const int m = e / d, i = e - m * d;
-    blk[i * 16 + m] = m < n_ok ? scale * src[(size_t)m * d + i] : T(0);
-  }
-  __syncthreads();
-}
-template <typename T>
-__device__ __forceinline__ void flow_store_tile(T *dst, const T *blk, int d, int n_ok) {
-  for (int e = threadIdx.x; e < 16 * d; e += 64) {
-    const int m = e / d, i = e - m * d;
-    if (m < n_ok) dst[(size_t)m * d + i] = blk[i * 16 + m];
-  }
-}
-
-extern __shared__ double flow_lds[];
-
 // LDS: XC [128][16] | H [4][64][16] | S [64][16] | TT [64][16]
 constexpr int kFlowFwdElems = 128 * 16 + 6 * kFlowBlk;
 template <typename T, bool INVERSE>
@@ -213,17 +164,7 @@ __global__ __launch_bounds__(64) void k_flow_forward(FlowArgs<T> g) {
   if (INVERSE) {
     flow_load_tile(g.Zin + (size_t)m0 * d, XC, d, n_ok);
   } else {
-    const int d4 = (d + 3) >> 2;
-    const uint64_t idx = rng_index(g.rng);
-    for (int e = lane; e < 16 * d4; e += 64) {
-      const int m = e / d4, rq = e - m * d4;
-      T ev[4] = {T(0), T(0), T(0), T(0)};
-      if (m < n_ok) eps_block<T>(g.rng.seed, idx, (uint64_t)(g.rng.m_offset + m0 + m) * (uint64_t)d4 + (uint64_t)rq, ev);
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (4 * rq + r < d) XC[(4 * rq + r) * 16 + m] = ev[r];
-    }
-    __syncthreads();
+    flow_draw_tile(g.rng, XC, d, m0, n_ok);
     if (g.eps) flow_store_tile(g.eps + (size_t)m0 * d, XC, d, n_ok);
     if (g.X) flow_store_tile(g.X + (size_t)m0 * d, XC, d, 16);
   }
@@ -396,31 +337,17 @@ __global__ __launch_bounds__(256) void k_flow_finish(long long plen, int n_slice
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------
-template <typename T, typename K>
-static bool flow_lds_attr(mivi_ctx *c, K kern, int elems) {
-  const size_t bytes = (size_t)elems * sizeof(T);
-  if (bytes <= 48 * 1024) return true;
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-}
 bool flow_prepare(mivi_ctx *c) {
+  if (c->flow.K) return nsf_prepare(c);
   return by_dtype(c, [&](auto t) {
     using T = decltype(t);
-    return flow_lds_attr<T>(c, &k_flow_forward<T, false>, kFlowFwdElems) && flow_lds_attr<T>(c, &k_flow_forward<T, true>, kFlowFwdElems) &&
-           flow_lds_attr<T>(c, &k_flow_vjp<T>, kFlowVjpElems);
+    return flow_lds_attr<T>(&k_flow_forward<T, false>, kFlowFwdElems) && flow_lds_attr<T>(&k_flow_forward<T, true>, kFlowFwdElems) &&
+           flow_lds_attr<T>(&k_flow_vjp<T>, kFlowVjpElems);
   });
 }
 
-template <typename T>
-static FlowArgs<T> flow_args(mivi_ctx *c, const void *params, int M) {
-  FlowArgs<T> g{};
-  g.a = c->flow;
-  g.M = M;
-  g.capM = c->cap_M;
-  g.params = (const T *)params;
-  return g;
-}
-
 void launch_flow_forward(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *Z, void *eps, bool save) {
+  if (c->flow.K) return launch_nsf_forward(c, params, rng, M, Z, eps, save);
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
     FlowArgs<T> g = flow_args<T>(c, params, M);
@@ -435,6 +362,7 @@ void launch_flow_forward(mivi_ctx *c, const void *params, const RngArgs &rng, in
 }
 
 void launch_flow_inverse(mivi_ctx *c, const void *params, const void *Z, int n, void *logq) {
+  if (c->flow.K) return launch_nsf_inverse(c, params, Z, n, logq);
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
     FlowArgs<T> g = flow_args<T>(c, params, n);
@@ -456,7 +384,8 @@ void launch_flow_vjp_finish(mivi_ctx *c, const void *params, int M, int want_gra
       g.part = (double *)c->flow_part.p;
       g.kind = out.ent_kind;
       g.invM = 1.0 / (double)out.M_total;
-      hipLaunchKernelGGL(k_flow_vjp<T>, dim3(ns), dim3(64), kFlowVjpElems * sizeof(T), c->stream, g, plen);
+      if (c->flow.K) launch_nsf_vjp<T>(c, g, ns, plen);
+      else hipLaunchKernelGGL(k_flow_vjp<T>, dim3(ns), dim3(64), kFlowVjpElems * sizeof(T), c->stream, g, plen);
     }
     hipLaunchKernelGGL(k_flow_finish<T>, dim3(ngb + 1), dim3(256), 0, c->stream, plen, ns, ngb, (const double *)c->flow_part.p, (const double *)c->flow_lq.p, vin, out);
   });

@@ -228,10 +228,15 @@ struct ColTargetArgs {  // standalone per-column targets: Z -> (ell, G)
 
 // The RealNVP family's architecture (mivi_flow_t behind mivi_create_flow) as the kernels take it, and the layout of its parameter vector:
 // layers l = 1 .. L, each [s net; t net], a net [vec W_1; b_1; ...; vec W_{H+1}; b_{H+1}] from |B_l| inputs to |A_l| outputs.
+// The neural spline flow (MIVI_NSF, mivi_spline_flow_t behind mivi_create_spline_flow) is the same architecture with K > 0 bins on
+// [-B, B]: ONE net per layer from |B_l| inputs to |A_l| (3K - 1) outputs, coordinate-major.  K = 0: RealNVP.
 struct FlowArch {
   int d, L, H;
   int h[3];
+  int K;
+  double B;
 };
+__host__ __device__ inline int nsf_rows(const FlowArch &a) { return 3 * a.K - 1; }   // output rows per transformed coordinate: u^w (K), u^h (K), u^d (K - 1)
 __host__ __device__ inline int flow_nA(int d, int l) { return (l & 1) ? (d + 1) / 2 : d / 2; }   // |A_l|: the even coordinates for odd l, the odd ones for even l
 __host__ __device__ inline long long flow_net_len(const FlowArch &a, int nin, int nout) {
   long long n = 0;
@@ -831,6 +836,11 @@ void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v, c
 double *lowr_logq_of(const mivi_ctx *c, const LowrPoints &pts);   // where launch_lowr_woodbury leaves the f64 log q of pts' columns
 void launch_lowr_vjp_finish(mivi_ctx *c, const void *params, int M, int want_grad, const ValueIn &vin, const OutArgs &out);   // W = G (and V, x, the draws) -> out.grad; out.value, the non-finite flag, the elbo record
 
+// kernels_nsf.hip: the neural spline flow's kernels; the launchers below branch to them on a context whose flow.K > 0 (launch_nsf_vjp,
+// which takes the typed argument block, is declared beside FlowArgs in flow_tile.h)
+bool nsf_prepare(mivi_ctx *c);
+void launch_nsf_forward(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *Z, void *eps, bool save);
+void launch_nsf_inverse(mivi_ctx *c, const void *params, const void *Z, int n, void *logq);
 // kernels_flow.hip: the RealNVP family's estimate, rand and logpdf (api_flow.hip drives them)
 long long flow_params_len(const FlowArch &a);
 int flow_slices(const FlowArch &a, int M);   // slices of the sample axis the VJP leaves partials for (<= 64, and at most 256 MB of them)

@@ -10,7 +10,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-MEANFIELD, FULLRANK, LOWRANK, REALNVP = 0, 1, 2, 3
+MEANFIELD, FULLRANK, LOWRANK, REALNVP, NSF = 0, 1, 2, 3, 4
+FLOW_FAMILIES = (REALNVP, NSF)   # the coupling flows: one surface, one set of refusals
+FLOW_NAMES = {REALNVP: "RealNVP", NSF: "NeuralSplineFlow"}
 LOWRANK_MAX_RANK = 64   # MIVI_LOWRANK_MAX_RANK (include/mivi.h)
 FLOW_MAX_D, FLOW_MAX_HIDDEN, FLOW_MAX_LAYERS = 128, 64, 32   # MIVI_FLOW_MAX_* (include/mivi.h)
 
@@ -278,6 +280,89 @@ def RealNVP(d, hidden_dims, n_layers, eltype=np.float64, rng=None) -> RealNVPFlo
     return RealNVPFlow(d, hidden_dims, n_layers, flat.astype(eltype))
 
 
+NSF_MAX_BINS = 16   # MIVI_NSF_MAX_BINS (include/mivi.h)
+
+
+def nsf_layout(d: int, hidden_dims, n_layers: int, n_bins: int):
+    """The parameter vector of a neural spline flow (MIVI_NSF, include/mivi.h), block by block: a list of
+    (layer l = 1 .. L, j = 1 .. H + 1, "W" | "b", offset, shape).  ONE net per layer, [vec W_1 (column-major, out x in); b_1; ...;
+    vec W_{H+1}; b_{H+1}] from |B_l| inputs to |A_l| (3K - 1) outputs: coordinate i of A_l owns the output rows i (3K - 1) ...,
+    in the order u^w_1..K, u^h_1..K, u^d_1..K-1."""
+    blocks, off = [], 0
+    for l in range(1, n_layers + 1):
+        n_a = (d + 1) // 2 if l % 2 == 1 else d // 2
+        widths = [d - n_a, *hidden_dims, n_a * (3 * n_bins - 1)]
+        for j in range(1, len(widths)):
+            out, inn = widths[j], widths[j - 1]
+            blocks.append((l, j, "W", off, (out, inn)))
+            off += out * inn
+            blocks.append((l, j, "b", off, (out,)))
+            off += out
+    return blocks, off
+
+
+class SplineFlow:
+    """The neural spline flow (Durkan et al., 2019; `nsf` of NormalizingFlows.jl) on a standard-normal base: RealNVP's masks and layer
+    order, the affine map of each coupling layer replaced by a monotone rational-quadratic spline with `n_bins` bins on [-bound, bound]
+    (the identity outside), whose widths, heights and slopes one net per layer gives.  `params` is the flat vector of `nsf_layout`."""
+
+    family = NSF
+
+    def __init__(self, d, hidden_dims, n_layers, n_bins, bound, params):
+        self.d, self.hidden_dims, self.n_layers = int(d), tuple(int(h) for h in hidden_dims), int(n_layers)
+        self.n_bins, self.bound = int(n_bins), float(bound)
+        if not 2 <= self.d <= FLOW_MAX_D:
+            raise ValueError(f"NeuralSplineFlow: the dimension must be in 2 .. {FLOW_MAX_D}")
+        if not 1 <= len(self.hidden_dims) <= 3 or not all(1 <= h <= FLOW_MAX_HIDDEN for h in self.hidden_dims):
+            raise ValueError(f"NeuralSplineFlow: one to three hidden layers of width 1 .. {FLOW_MAX_HIDDEN}")
+        if not 1 <= self.n_layers <= FLOW_MAX_LAYERS:
+            raise ValueError(f"NeuralSplineFlow: n_layers must be in 1 .. {FLOW_MAX_LAYERS}")
+        if not 2 <= self.n_bins <= NSF_MAX_BINS:
+            raise ValueError(f"NeuralSplineFlow: n_bins must be in 2 .. {NSF_MAX_BINS}")
+        if not (self.bound > 0 and math.isfinite(self.bound)):
+            raise ValueError("NeuralSplineFlow: bound must be positive and finite")
+        self.params = np.ascontiguousarray(params)
+        if self.params.dtype not in (np.float32, np.float64):
+            raise TypeError("NeuralSplineFlow: eltype must be Float32 or Float64")
+        if self.params.shape != (nsf_layout(self.d, self.hidden_dims, self.n_layers, self.n_bins)[1],):
+            raise ValueError("flat parameter vector has the wrong length")
+
+    def __len__(self):
+        return self.d
+
+    @property
+    def eltype(self):
+        return self.params.dtype
+
+    def blocks(self):
+        """{(l, j, "W" | "b"): array view} of the parameter vector (W as an out x in matrix)."""
+        return {(l, j, k): self.params[off:off + int(np.prod(shape))].reshape(shape, order="F")
+                for l, j, k, off, shape in nsf_layout(self.d, self.hidden_dims, self.n_layers, self.n_bins)[0]}
+
+
+def NeuralSplineFlow(d, hidden_dims, n_bins, bound, n_layers, eltype=np.float64, rng=None) -> SplineFlow:
+    """nsf(MvNormal(zeros(d), I); hidden_dims, K = n_bins, B = bound, n_layers): Glorot-uniform weights from a seeded numpy generator
+    (an int seed or a Generator; None: seed 0), zero biases."""
+    gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(0 if rng is None else rng)
+    blocks, n = nsf_layout(int(d), tuple(hidden_dims), int(n_layers), int(n_bins))
+    flat = np.zeros(n, dtype=np.float64)
+    for _, _, kind, off, shape in blocks:
+        if kind == "W":
+            lim = math.sqrt(6.0 / (shape[0] + shape[1]))
+            flat[off:off + shape[0] * shape[1]] = gen.uniform(-lim, lim, size=shape[0] * shape[1])
+    return SplineFlow(d, hidden_dims, n_layers, n_bins, bound, flat.astype(eltype))
+
+
+COUPLING_FLOWS = (RealNVPFlow, SplineFlow)
+
+
+def flow_arch(q):
+    """the `flow` argument of MiviContext for q (None unless q is a coupling flow)"""
+    if isinstance(q, SplineFlow):
+        return (q.hidden_dims, q.n_layers, q.n_bins, q.bound)
+    return (q.hidden_dims, q.n_layers) if isinstance(q, RealNVPFlow) else None
+
+
 class Restructure:
     """The `re` closure returned by Optimisers.destructure; RestructureMeanField for the
     Diagonal case (src/families/location_scale.jl:28-37)."""
@@ -285,13 +370,15 @@ class Restructure:
     def __init__(self, d: int, family: int, dtype, rank: int = 0, dist=None, flow=None):
         self.d, self.family, self.dtype, self.rank = d, family, dtype, rank
         self.dist = dist if dist is not None else Normal()   # carried through, as re.model.dist (location_scale.jl:32-37)
-        self.flow = flow   # REALNVP: (hidden_dims, n_layers)
+        self.flow = flow   # REALNVP: (hidden_dims, n_layers); NSF: (hidden_dims, n_layers, n_bins, bound)
 
     def __call__(self, flat):
         flat = np.asarray(flat, dtype=self.dtype)
         d = self.d
         if self.family == REALNVP:
             return RealNVPFlow(d, self.flow[0], self.flow[1], flat.copy())
+        if self.family == NSF:
+            return SplineFlow(d, *self.flow, flat.copy())
         if self.family == LOWRANK:
             if flat.shape[0] != 2 * d + d * self.rank:
                 raise ValueError("flat parameter vector has the wrong length")
@@ -311,10 +398,12 @@ def destructure(q):
     full-rank : [location; vec(scale)] column-major, length d + d^2, strict upper triangle zero
     low-rank  : [location; scale_diag; vec(scale_factors)] column-major, length 2d + d r (the functor's field order,
                 src/families/location_scale_low_rank.jl:41).
-    RealNVP   : the nets' weights and biases, layer by layer (flow_layout)."""
+    RealNVP   : the nets' weights and biases, layer by layer (flow_layout); NeuralSplineFlow likewise (nsf_layout)."""
     d = len(q)
     if q.family == REALNVP:   # the flow's own flat vector (flow_layout)
         return q.params.copy(), Restructure(d, REALNVP, q.eltype, flow=(q.hidden_dims, q.n_layers))
+    if q.family == NSF:
+        return q.params.copy(), Restructure(d, NSF, q.eltype, flow=flow_arch(q))
     if q.family == LOWRANK:
         flat = np.concatenate([q.location, q.scale_diag, q.scale_factors.reshape(-1, order="F")])
         return flat.astype(q.eltype, copy=False), Restructure(d, LOWRANK, q.eltype, q.rank)

@@ -38,7 +38,7 @@ from . import objectives as O
 from . import problems as P
 from . import subsampling as S
 from .context import BAM_MAX_SAMPLES, MiviContext
-from .families import FULLRANK, REALNVP, MvLocationScale, destructure
+from .families import FLOW_FAMILIES, FLOW_NAMES, FULLRANK, MvLocationScale, destructure
 
 
 class KLMinSqrtNaturalGradDescent:
@@ -157,8 +157,8 @@ def _own_buffers(state):
 def init(rng, alg, q_init, prob):
     """klminsqrtnaturalgraddescent.jl:55-75 / klminnaturalgraddescent.jl:64-91 / fisherminbatchmatch.jl:56-77 / klminwassfwdbwd.jl:56-76."""
     name = type(alg).__name__
-    if getattr(q_init, "family", None) == REALNVP:
-        raise TypeError(f"`{name}` updates a Gaussian's location and scale: it has no method for a normalizing flow (RealNVP) -- use "
+    if getattr(q_init, "family", None) in FLOW_FAMILIES:
+        raise TypeError(f"`{name}` updates a Gaussian's location and scale: it has no method for a normalizing flow ({FLOW_NAMES[q_init.family]}) -- use "
                         "`KLMinRepGradDescent` with `StickingTheLandingEntropy()` and `IdentityOperator()`")
     if not isinstance(q_init, MvLocationScale) or q_init.family != FULLRANK:
         raise TypeError(f"`{name}` expects a Gaussian with a lower-triangular scale (FullRankGaussian) as q_init")

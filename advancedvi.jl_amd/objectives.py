@@ -18,7 +18,7 @@ import numpy as np
 
 from . import problems as P
 from .context import MiviContext
-from .families import MvLocationScale, MvLocationScaleLowRank, RealNVPFlow, destructure
+from .families import COUPLING_FLOWS, FLOW_NAMES, MvLocationScale, MvLocationScaleLowRank, destructure, flow_arch as _flow_arch
 
 
 _log = logging.getLogger("advancedvi_jl_amd")
@@ -177,21 +177,16 @@ def _ad_problem(adtype, prob, announce=True):
     return P.ADgradient(kind, prob)
 
 
-_NO_FLOW_ENTROPY = ("a normalizing flow (RealNVP) has no entropy(q): {} cannot be used with it -- use `MonteCarloEntropy()` or "
+_NO_FLOW_ENTROPY = ("a normalizing flow ({}) has no entropy(q): {} cannot be used with it -- use `MonteCarloEntropy()` or "
                     "`StickingTheLandingEntropy()` (docs/src/tutorials/flows.md:213)")
 
 
-def _flow_arch(q):
-    """the `flow` argument of MiviContext for q (None unless q is a RealNVPFlow)"""
-    return (q.hidden_dims, q.n_layers) if isinstance(q, RealNVPFlow) else None
-
-
 def _make_ctx(rng, obj, adtype, q, prob, n_mc=None, entropy=None):
-    if not isinstance(q, (MvLocationScale, MvLocationScaleLowRank, RealNVPFlow)):
-        raise TypeError("libmivi implements the RepGradELBO path for MvLocationScale, MvLocationScaleLowRank and RealNVP families only")
+    if not isinstance(q, (MvLocationScale, MvLocationScaleLowRank) + COUPLING_FLOWS):
+        raise TypeError("libmivi implements the RepGradELBO path for MvLocationScale, MvLocationScaleLowRank, RealNVP and NeuralSplineFlow families only")
     ent = entropy or obj.entropy
-    if isinstance(q, RealNVPFlow) and ent.code not in (MonteCarloEntropy.code, StickingTheLandingEntropy.code):
-        raise TypeError(_NO_FLOW_ENTROPY.format(f"`{type(ent).__name__}`"))
+    if isinstance(q, COUPLING_FLOWS) and ent.code not in (MonteCarloEntropy.code, StickingTheLandingEntropy.code):
+        raise TypeError(_NO_FLOW_ENTROPY.format(FLOW_NAMES[q.family], f"`{type(ent).__name__}`"))
     device = getattr(adtype, "device", 0)
     ctx = MiviContext(q.eltype, q.family, len(q), n_mc or obj.n_samples,
                       ent.code, rng.seed, device=device, rank=getattr(q, "rank", 0), flow=_flow_arch(q))
@@ -205,8 +200,8 @@ def _make_ctx(rng, obj, adtype, q, prob, n_mc=None, entropy=None):
 
 
 def _make_score_ctx(rng, obj, adtype, q, prob):
-    if isinstance(q, RealNVPFlow):
-        raise TypeError("ScoreGradELBO is not implemented for a normalizing flow (RealNVP): use RepGradELBO (KLMinRepGradDescent) with "
+    if isinstance(q, COUPLING_FLOWS):
+        raise TypeError(f"ScoreGradELBO is not implemented for a normalizing flow ({FLOW_NAMES[q.family]}): use RepGradELBO (KLMinRepGradDescent) with "
                         "`MonteCarloEntropy()` or `StickingTheLandingEntropy()`")
     if isinstance(q, MvLocationScaleLowRank):
         raise TypeError("ScoreGradELBO is not implemented for the low-rank family (MvLocationScaleLowRank): use RepGradELBO "
@@ -313,7 +308,7 @@ class TransformedDistribution:
 
 def _plain_entropy(q):
     """the estimator code of a context that only samples or scores q (never read there): a flow context admits no closed-form kind"""
-    return MonteCarloEntropy.code if isinstance(q, RealNVPFlow) else 0
+    return MonteCarloEntropy.code if isinstance(q, COUPLING_FLOWS) else 0
 
 
 def rand(rng, q, num_samples: int, device: int = 0):

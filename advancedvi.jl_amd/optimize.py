@@ -10,7 +10,7 @@ import numpy as np
 
 from . import objectives as O
 from . import subsampling as S
-from .families import LOWRANK, REALNVP, MvLocationScale, MvLocationScaleLowRank, RealNVPFlow, destructure
+from .families import COUPLING_FLOWS, FLOW_FAMILIES, FLOW_NAMES, LOWRANK, MvLocationScale, MvLocationScaleLowRank, destructure
 
 
 # --- operators (src/optimization/clip_scale.jl, src/AdvancedVI.jl:173-204) ------------------------
@@ -26,8 +26,8 @@ class ClipScale:
         self.epsilon = epsilon
 
     def apply(self, ctx, params, optimizer=None, opt_st=None):
-        if ctx.family == REALNVP:
-            raise TypeError(_NO_SCALE_FLOW.format("ClipScale"))
+        if ctx.family in FLOW_FAMILIES:
+            raise TypeError(_NO_SCALE_FLOW.format("ClipScale", FLOW_NAMES[ctx.family]))
         ctx.clip_scale(params, self.epsilon)
         return params
 
@@ -36,7 +36,7 @@ _NO_PROX_LOWRANK = ("`ProximalLocationScaleEntropy` has no method for the low-ra
                     "(proximal_location_scale_entropy.jl:44): use `ClipScale`")
 
 
-_NO_SCALE_FLOW = ("`{}` has no method for a normalizing flow (RealNVP): the family has no scale -- use `IdentityOperator()` "
+_NO_SCALE_FLOW = ("`{}` has no method for a normalizing flow ({}): the family has no scale -- use `IdentityOperator()` "
                   "(docs/src/tutorials/flows.md:212-215)")
 
 
@@ -48,8 +48,8 @@ class ProximalLocationScaleEntropy:
     def apply(self, ctx, params, optimizer=None, opt_st=None):
         if ctx.family == LOWRANK:
             raise TypeError(_NO_PROX_LOWRANK)
-        if ctx.family == REALNVP:
-            raise TypeError(_NO_SCALE_FLOW.format("ProximalLocationScaleEntropy"))
+        if ctx.family in FLOW_FAMILIES:
+            raise TypeError(_NO_SCALE_FLOW.format("ProximalLocationScaleEntropy", FLOW_NAMES[ctx.family]))
         if isinstance(optimizer, DoG):            # DoWG is a subclass
             ctx.prox_scale_entropy(params, 0.0, opt_st, optimizer.kind)
         elif isinstance(optimizer, Descent):
@@ -263,8 +263,8 @@ def init(rng, alg, q_init, prob):
         return M.init(rng, alg, q_init, prob)
     if isinstance(q_init, MvLocationScaleLowRank) and isinstance(alg.operator, ProximalLocationScaleEntropy):
         raise TypeError(_NO_PROX_LOWRANK)
-    if isinstance(q_init, RealNVPFlow) and isinstance(alg.operator, (ClipScale, ProximalLocationScaleEntropy)):
-        raise TypeError(_NO_SCALE_FLOW.format(type(alg.operator).__name__))
+    if isinstance(q_init, COUPLING_FLOWS) and isinstance(alg.operator, (ClipScale, ProximalLocationScaleEntropy)):
+        raise TypeError(_NO_SCALE_FLOW.format(type(alg.operator).__name__, FLOW_NAMES[q_init.family]))
     if isinstance(q_init, (MvLocationScale, MvLocationScaleLowRank)) and isinstance(alg.operator, IdentityOperator):
         warnings.warn(
             "IdentityOperator is used with a variational family <:MvLocationScale. Optimization can easily fail under "
@@ -472,7 +472,7 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
     if state is None:
         state = init(rng, algorithm, q_init, prob)
     codes = _device_loop_codes(algorithm, callback, objargs, state.get("prob")) if device_loop else None
-    if isinstance(algorithm.objective, S.SubsampledObjective) and _ctx_of(state["obj_st"]).family == REALNVP:
+    if isinstance(algorithm.objective, S.SubsampledObjective) and _ctx_of(state["obj_st"]).family in FLOW_FAMILIES:
         codes = None   # the batch schedule has no form for a flow: subsampled steps keep the host loop (mivi_logreg_select_rows per step)
     if codes is not None and max_iter > 0:
         state = dict(state)
@@ -697,8 +697,9 @@ def optimize_many(rngs, algorithm, max_iter: int, probs, q_inits, *, states=None
     algs = _per_run(algorithm, K, "algorithm")
     probs = _per_run(probs, K, "probs")
     qs = _per_run(q_inits, K, "q_inits")
-    if any(isinstance(q, RealNVPFlow) for q in qs):
-        raise TypeError("optimize_many has no method for a normalizing flow (RealNVP): its runs are small Gaussian families, one "
+    flow = next((q for q in qs if isinstance(q, COUPLING_FLOWS)), None)
+    if flow is not None:
+        raise TypeError(f"optimize_many has no method for a normalizing flow ({FLOW_NAMES[flow.family]}): its runs are small Gaussian families, one "
                         "workgroup each -- call `optimize` once per run")
     if states is None:
         states = [None] * K

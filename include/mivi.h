@@ -61,7 +61,7 @@ typedef enum { MIVI_F32 = 0, MIVI_F64 = 1 } mivi_dtype_t;
  * the DoG entries, and mivi_optimize_steps / _loop as a graph of launches (op 0 or 1).  Every other entry that reads parameters returns
  * MIVI_ERR_UNSUPPORTED on it (the score-gradient and measure-space entries, partials / finalize / dist / p2p, the profile entries,
  * mivi_prox_scale_entropy and op = 2: the reference has no ProximalLocationScaleEntropy method for the family). */
-typedef enum { MIVI_MEANFIELD = 0, MIVI_FULLRANK = 1, MIVI_LOWRANK = 2, MIVI_REALNVP = 3 } mivi_family_t;
+typedef enum { MIVI_MEANFIELD = 0, MIVI_FULLRANK = 1, MIVI_LOWRANK = 2, MIVI_REALNVP = 3, MIVI_NSF = 4 } mivi_family_t;
 #define MIVI_LOWRANK_MAX_RANK 64
 
 /* MIVI_REALNVP: the RealNVP normalizing flow of docs/src/tutorials/flows.md (Dinh et al.; the masks and activations of
@@ -92,6 +92,43 @@ typedef struct {
   int32_t n_hidden;   /* H, 1 .. 3 hidden layers per net */
   int32_t hidden[3];  /* their widths, 1 .. MIVI_FLOW_MAX_HIDDEN (entries from n_hidden on are not read) */
 } mivi_flow_t;
+
+/* MIVI_NSF: the neural spline flow (Durkan et al., 2019; the coupling flow `nsf` of NormalizingFlows.jl beside `realnvp`), created by
+ * mivi_create_spline_flow.  RealNVP's affine map of each coupling layer is replaced by a monotone rational-quadratic spline on [-B, B]
+ * with K bins, in the form Bijectors.RationalQuadraticSpline documents (no minimum bin size or slope).  All index sets are 0-based.
+ *   base     eps ~ N(0, I_d): the mean-field family's Philox stream, d rows.  No parameters.
+ *   layers   l = 1 .. n_layers, x^0 = eps, z = x^L.  A_l = {0, 2, 4, ...} for odd l, {1, 3, 5, ...} for even l, B_l the rest (RealNVP's);
+ *            c = x^{l-1}[B_l] passes through, x^l[A_l][i] = f(a_i; theta_i(c)) with a = x^{l-1}[A_l]
+ *   net      ONE per layer, |B_l| -> hidden[0] -> ... -> hidden[n_hidden - 1] -> |A_l| (3K - 1); hidden layers leakyrelu(W_j . + b_j) with
+ *            slope 0.01, the output layer W . + b (nothing applied).  Output rows are coordinate-major: coordinate i of A_l (its i-th
+ *            member) owns the rows i (3K - 1) ... i (3K - 1) + 3K - 2 = theta_i, in the order u^w_1..K, u^h_1..K, u^d_1..K-1
+ *   spline   of one coordinate, from theta = (u^w, u^h, u^d):  w = 2B softmax(u^w), h = 2B softmax(u^h); knots X_0 = -B,
+ *            X_k = X_{k-1} + w_k, Y_0 = -B, Y_k = Y_{k-1} + h_k; slopes delta_0 = delta_K = 1, delta_k = softplus(u^d_k) = log(1 + exp u^d_k).
+ *            a <= -B or a >= B:  f(a) = a, log f'(a) = 0 (the identity tails).
+ *            otherwise bin k is the one with X_{k-1} <= a < X_k (a >= X_{K-1}: bin K), and with xi = (a - X_{k-1}) / w_k, s = h_k / w_k,
+ *            D = s + (delta_k + delta_{k-1} - 2s) xi (1 - xi):
+ *              f(a)      = Y_{k-1} + h_k (s xi^2 + delta_{k-1} xi (1 - xi)) / D
+ *              log f'(a) = 2 log s + log(delta_k xi^2 + 2 s xi (1 - xi) + delta_{k-1} (1 - xi)^2) - 2 log D
+ *   inverse  y <= -B or y >= B: a = y.  Otherwise bin k with Y_{k-1} <= y < Y_k, dy = y - Y_{k-1}, t = delta_k + delta_{k-1} - 2s,
+ *            qa = h_k (s - delta_{k-1}) + dy t, qb = h_k delta_{k-1} - dy t, qc = -s dy, xi = 2 qc / (-qb - sqrt(qb^2 - 4 qa qc)),
+ *            a = X_{k-1} + xi w_k
+ *   log q    log q(z) = -1/2 |eps|^2 - d/2 log 2 pi - sum_l sum_{i in A_l} log f'_{l,i}(a_{l,i}) at eps = T^-1(z)
+ *   params   for l = 1 .. L the layer's net [vec W_1 (column-major, out x in); b_1; ...; vec W_{H+1}; b_{H+1}], as a RealNVP net lies
+ *   limits   2 <= d <= 128, 1 <= hidden[j] <= 64, 1 <= n_hidden <= 3, 1 <= n_layers <= 32, 2 <= n_bins <= 16, bound > 0 and finite,
+ *            any n_mc >= 1, f32 and f64
+ *   entropy  as MIVI_REALNVP: MIVI_ENT_MONTE_CARLO and MIVI_ENT_STL
+ * Family 4 supports exactly the entries family 3 supports (the list above) and is refused, with a message naming the entry and "neural
+ * spline flow family (MIVI_NSF)", on exactly the entries family 3 is refused on.
+ * NormalizingFlows.nsf's own parameter order (its Flux conditioner's layout and its minimum bin sizes, if it sets any) is NOT what this
+ * header fixes: binding it belongs to julia/MIVI.jl, is not part of the library and has not been checked against that package. */
+#define MIVI_NSF_MAX_BINS 16
+typedef struct {
+  int32_t n_layers;   /* L, 1 .. MIVI_FLOW_MAX_LAYERS */
+  int32_t n_hidden;   /* H, 1 .. 3 hidden layers of the conditioner */
+  int32_t hidden[3];  /* their widths, 1 .. MIVI_FLOW_MAX_HIDDEN (entries from n_hidden on are not read) */
+  int32_t n_bins;     /* K, 2 .. MIVI_NSF_MAX_BINS */
+  double bound;       /* B > 0, finite */
+} mivi_spline_flow_t;
 
 /* src/algorithms/entropy.jl: ClosedFormEntropy :25-29, ClosedFormEntropyZeroGradient :11-15,
  * MonteCarloEntropy :40-46, StickingTheLandingEntropy :57-65, StickingTheLandingEntropyZeroGradient :78-90 */
@@ -131,6 +168,9 @@ mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out);
  * outside the limits above; MIVI_ERR_UNSUPPORTED for an entropy kind other than MIVI_ENT_MONTE_CARLO / MIVI_ENT_STL and for a sharded
  * context (m_offset != 0 or m_total not in {0, n_mc}). */
 mivi_status_t mivi_create_flow(const mivi_config_t *cfg, const mivi_flow_t *flow, mivi_ctx_t **out);
+/* A MIVI_NSF context (cfg->family must be MIVI_NSF; mivi_create and mivi_create_flow answer MIVI_ERR_BAD_ARG for that family).  The
+ * same answers as mivi_create_flow: MIVI_ERR_BAD_ARG outside the limits above, MIVI_ERR_UNSUPPORTED for the entropy kind and the shard. */
+mivi_status_t mivi_create_spline_flow(const mivi_config_t *cfg, const mivi_spline_flow_t *flow, mivi_ctx_t **out);
 mivi_status_t mivi_destroy(mivi_ctx_t *ctx);
 const char *mivi_last_error(const mivi_ctx_t *ctx);
 int32_t mivi_version(void);
