@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .families import FULLRANK, LOWRANK, MEANFIELD, NSF, REALNVP
+from .families import BLOCKDIAG, FULLRANK, LOWRANK, MEANFIELD, NSF, REALNVP
 from . import problems as P
 
 NATGRAD_SMALL_D = 44   # MIVI_NATGRAD_SMALL_D (include/mivi.h): up to this d mivi_natgrad_update is the one-workgroup kernel, above it the tile path
@@ -32,8 +32,8 @@ def torch_dtype(np_dtype):
 class MiviContext:
     """One RepGradELBO estimator instance on one GPU (mivi_create ... mivi_destroy)."""
 
-    def __init__(self, dtype, family, d, n_mc, entropy, seed, device=0, m_offset=0, m_total=0, stream=None, rank=0, flow=None):
-        """flow: (hidden_dims, n_layers) of a REALNVP context (mivi_create_flow), (hidden_dims, n_layers, n_bins, bound) of an NSF
+    def __init__(self, dtype, family, d, n_mc, entropy, seed, device=0, m_offset=0, m_total=0, stream=None, rank=0, flow=None, block=0):
+        """block: the block size of a BLOCKDIAG context (mivi_create_blockdiag).  flow: (hidden_dims, n_layers) of a REALNVP context (mivi_create_flow), (hidden_dims, n_layers, n_bins, bound) of an NSF
         context (mivi_create_spline_flow); not read for the other families."""
         torch = _torch()
         self.lib = _lib.load()
@@ -41,6 +41,7 @@ class MiviContext:
         self.family, self.d, self.n_mc, self.entropy = int(family), int(d), int(n_mc), int(entropy)
         self.device = int(device)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF   # the Philox seed of every draw of this context
+        self.block = int(block)  # rows of a scale block (the block-diagonal family; not read for the others)
         self.rank = int(rank)  # columns of scale_factors (the low-rank family; not read for the others)
         self.tdtype = torch_dtype(self.np_dtype)
         self.tdevice = torch.device("cuda", self.device)
@@ -77,6 +78,10 @@ class MiviContext:
                 raise _lib.MiviError(st, "mivi_create_spline_flow: the neural spline flow family has no sharded form (m_offset / m_total)" if sharded else
                                          "mivi_create_spline_flow: a flow has no entropy(q) -- the estimators that work on it are MonteCarloEntropy "
                                          "and StickingTheLandingEntropy")
+        elif self.family == BLOCKDIAG:
+            st = self.lib.mivi_create_blockdiag(C.byref(cfg), C.byref(_lib.MiviBlockDiag(self.block)), C.byref(h))
+            if st == 6:   # MIVI_ERR_UNSUPPORTED before a context exists to carry the message
+                raise _lib.MiviError(st, "mivi_create_blockdiag: the block-diagonal family has no sharded form (m_offset / m_total)")
         else:
             st = self.lib.mivi_create(C.byref(cfg), C.byref(h))
         _lib.check(self.lib, None, st)

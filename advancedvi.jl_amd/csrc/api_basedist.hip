@@ -8,6 +8,7 @@
 static const char *base_name(const mivi_ctx *c) { return c->base == MIVI_BASE_LAPLACE ? "Laplace" : "TDist"; }
 
 mivi_status_t refuse_non_gaussian(mivi_ctx *c, const char *entry) {
+  if (mivi_status_t rs = refuse_blockdiag(c, entry)) return rs;
   if (mivi_status_t rs = refuse_lowrank(c, entry)) return rs;
   if (mivi_status_t rs = refuse_batch_schedule(c, entry)) return rs;   // (these entries are also the ones that read a logistic regression's data set themselves)
   if (c->base == MIVI_BASE_NORMAL) return MIVI_OK;
@@ -30,6 +31,7 @@ mivi_status_t mivi_set_base_dist(mivi_ctx_t *c, int32_t base, double nu) {
   if (base == MIVI_BASE_TDIST && !(nu > 0.0 && isfinite(nu))) return fail(c, MIVI_ERR_BAD_ARG, "mivi_set_base_dist: TDist needs finite degrees of freedom nu > 0");
   if (base != MIVI_BASE_NORMAL) {
     if (c->cfg.family == MIVI_LOWRANK) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_set_base_dist: a non-normal base is not supported on the low-rank family (MIVI_LOWRANK)");
+    if (mivi_status_t rs = refuse_blockdiag(c, "mivi_set_base_dist with a non-normal base")) return rs;
     if (mivi_status_t rs = refuse_flow(c, "mivi_set_base_dist with a non-normal base (the flow's base is the standard normal)")) return rs;
     if (c->cfg.m_offset != 0 || (c->cfg.m_total != 0 && c->cfg.m_total != c->cfg.n_mc))
       return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_set_base_dist: a non-normal base is not supported on a sharded context");

@@ -237,6 +237,7 @@ mivi_status_t ensure_work(mivi_ctx *c, int M) {
     }
     if (c->cfg.family == MIVI_LOWRANK && (s = ensure_work_lowrank(c, capM))) return s;
     if (is_flow(c) && (s = ensure_work_flow(c, capM))) return s;
+    if (c->cfg.family == MIVI_BLOCKDIAG && (s = ensure_work_blockdiag(c, capM))) return s;
     if (c->base != MIVI_BASE_NORMAL && (s = ensure_work_base(c, capM))) return s;
     if ((s = ensure(c, c->Z, (size_t)d * capM * es, false))) return s;
     if ((s = ensure(c, c->W, (size_t)d * capM * es, false))) return s;
@@ -258,11 +259,12 @@ int64_t mivi_params_len(const mivi_ctx_t *c) {
   const int64_t d = c->cfg.d;
   if (c->cfg.family == MIVI_LOWRANK) return 2 * d + d * (int64_t)c->cfg.rank;
   if (is_flow(c)) return flow_params_len(c->flow);
+  if (c->cfg.family == MIVI_BLOCKDIAG) return c->bd.plen;
   return c->cfg.family == MIVI_MEANFIELD ? 2 * d : d + d * d;
 }
 int64_t mivi_partials_len(const mivi_ctx_t *c) {
   const int64_t d = c->cfg.d;
-  if (c->cfg.family == MIVI_LOWRANK || is_flow(c)) return 0;   // no sharded estimates
+  if (c->cfg.family == MIVI_LOWRANK || c->cfg.family == MIVI_BLOCKDIAG || is_flow(c)) return 0;   // no sharded estimates
   return (c->cfg.family == MIVI_MEANFIELD ? 2 * d : d + d * (d + 1) / 2) + 2;
 }
 
@@ -275,15 +277,19 @@ mivi_status_t mivi_create(const mivi_config_t *cfg, mivi_ctx_t **out) {
     fprintf(stderr, "libmivi: mivi_create: the neural spline flow family (MIVI_NSF) takes its architecture through mivi_create_spline_flow\n");
     return MIVI_ERR_BAD_ARG;
   }
+  if (cfg && cfg->family == MIVI_BLOCKDIAG) {
+    fprintf(stderr, "libmivi: mivi_create: the block-diagonal family (MIVI_BLOCKDIAG) takes its block size through mivi_create_blockdiag\n");
+    return MIVI_ERR_BAD_ARG;
+  }
   return create_context(cfg, nullptr, out);
 }
 
 // mivi_create, and mivi_create_flow (api_flow.hip) behind its own checks: `flow` is the architecture of a MIVI_REALNVP context
-mivi_status_t create_context(const mivi_config_t *cfg, const mivi::FlowArch *flow, mivi_ctx_t **out) {
+mivi_status_t create_context(const mivi_config_t *cfg, const mivi::FlowArch *flow, mivi_ctx_t **out, int block) {
   if (!cfg || !out) return MIVI_ERR_BAD_ARG;
   if (cfg->d <= 0 || cfg->n_mc <= 0) return MIVI_ERR_BAD_ARG;
   if (cfg->dtype != MIVI_F32 && cfg->dtype != MIVI_F64) return MIVI_ERR_BAD_ARG;
-  if (cfg->family != MIVI_MEANFIELD && cfg->family != MIVI_FULLRANK && cfg->family != MIVI_LOWRANK && !((cfg->family == MIVI_REALNVP || cfg->family == MIVI_NSF) && flow)) return MIVI_ERR_BAD_ARG;
+  if (cfg->family != MIVI_MEANFIELD && cfg->family != MIVI_FULLRANK && cfg->family != MIVI_LOWRANK && !((cfg->family == MIVI_REALNVP || cfg->family == MIVI_NSF) && flow) && !(cfg->family == MIVI_BLOCKDIAG && block > 0)) return MIVI_ERR_BAD_ARG;
   if (cfg->family == MIVI_LOWRANK) {   // (rank is read for this family only)
     if (cfg->rank < 1 || cfg->rank > MIVI_LOWRANK_MAX_RANK) return MIVI_ERR_BAD_ARG;
     if (cfg->m_offset != 0 || (cfg->m_total != 0 && cfg->m_total != cfg->n_mc)) return MIVI_ERR_UNSUPPORTED;   // no sharded low-rank estimates
@@ -298,6 +304,7 @@ mivi_status_t create_context(const mivi_config_t *cfg, const mivi::FlowArch *flo
   mivi_ctx *c = new mivi_ctx();
   c->cfg = *cfg;
   if (flow) c->flow = *flow;
+  if (block > 0) c->bd = bd_shape(cfg->d, block);
   c->esize = cfg->dtype == MIVI_F32 ? 4 : 8;
   {
     int v = 0;
@@ -519,6 +526,7 @@ mivi_status_t refuse_batch_schedule(mivi_ctx *c, const char *entry) {
 
 mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *c, const mivi_batch_schedule_t *sp) {
   if (!c || !sp) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_blockdiag(c, "mivi_logreg_set_batch_schedule")) return rs;
   if (mivi_status_t rs = refuse_flow(c, "mivi_logreg_set_batch_schedule")) return rs;
   if (c->target != TGT_LOGREG || !c->lr_X_full) return fail(c, MIVI_ERR_NO_TARGET, "no logistic-regression target set");
   const mivi_batch_schedule_t &sc = *sp;
@@ -562,6 +570,7 @@ mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *c, const mivi_batch_sch
 
 mivi_status_t mivi_logreg_seek_batch(mivi_ctx_t *c, int32_t k) {
   if (!c) return MIVI_ERR_BAD_ARG;
+  if (mivi_status_t rs = refuse_blockdiag(c, "mivi_logreg_seek_batch")) return rs;
   if (mivi_status_t rs = refuse_flow(c, "mivi_logreg_seek_batch")) return rs;
   if (c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "no batch schedule set (mivi_logreg_set_batch_schedule)");
   if (k < 0 || k >= c->lr_sched_n) return fail(c, MIVI_ERR_BAD_ARG, "batch index outside the schedule");

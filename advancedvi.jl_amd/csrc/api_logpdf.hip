@@ -3,6 +3,7 @@
 // The estimators only ever form log q at their own draws, where u = C^-1 (z - mu) is known; here it has to be solved for:
 //   mean-field : u = (z - mu) / sigma, one streaming kernel
 //   full-rank  : the forward block substitution C X = Z - mu (k_lp_fwd16, kernels_logpdf.hip) on the inverted diagonal blocks of k_stl_prep
+//   block-diag : the forward substitution C_k X_k = Z_k - mu_k per unit in LDS (k_bd_logpdf, kernels_blockdiag.hip), f64 X and sums
 //   low-rank   : t = D^-1 (z - m), then the estimators' own parameter preparation and Woodbury stage (kernels_lowrank.hip) on t
 // The call works in scratch of its own (mivi_ctx::lp_*), launches on the context's stream and touches neither the estimate buffers, the
 // eps speculation, the buffer parity nor a cached graph: estimates around it are bitwise what they are without it.
@@ -31,6 +32,14 @@ mivi_status_t logpdf_launches(mivi_ctx *c, const void *params, const char *Z, in
       chunk_finish(c, k, logq, bij);
       return MIVI_OK;
     });
+  if (c->cfg.family == MIVI_BLOCKDIAG) {   // the forward substitution per unit; the unit chunks' f64 partials per column, then their sum
+    if ((s = ensure(c, c->lp_work, (size_t)bd_logpdf_chunks(c->bd) * cap * sizeof(double), false))) return s;
+    return for_each_chunk(c, 0, n, 0, 1, [&](const SampleChunk &k) -> mivi_status_t {
+      launch_bd_logpdf(c, params, chunk_points(c, k, Z, bij), k.Mc, logq + (size_t)k.off * es, std ? std + (size_t)k.off * d * es : nullptr, (double *)c->lp_work.p);
+      chunk_finish(c, k, logq, bij);
+      return MIVI_OK;
+    });
+  }
   if (c->cfg.family == MIVI_LOWRANK) {
     const size_t r = c->cfg.rank, t_bytes = (d * cap * es + 15) / 16 * 16;
     if ((s = ensure(c, c->lp_scal, lowr_prep_doubles((int)d, (int)r) * sizeof(double), false)) ||

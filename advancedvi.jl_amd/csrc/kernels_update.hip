@@ -265,11 +265,23 @@ void launch_value_only(mivi_ctx *c, const void *params, const ValueIn &vin, cons
   });
 }
 
+// The kernels below take the family as one int: the family itself, and for the block-diagonal family its block size above bit 8
+// (family_code; every other family's code is its mivi_family_t, so their launches are what they were).
+static int family_code(const mivi_ctx *c) { return c->cfg.family == MIVI_BLOCKDIAG ? MIVI_BLOCKDIAG | (c->bd.b << 8) : c->cfg.family; }
+// where C_ii lies in the parameter vector; block-diagonal: block k = i / b of b_k = min(b, d - k b) rows at d + k b^2, column-major
+__device__ __forceinline__ size_t scale_diag_offset(int i, int d, int family) {
+  if ((family & 0xff) == MIVI_BLOCKDIAG) {
+    const int b = family >> 8, k = i / b, j = i - k * b, bk = d - k * b < b ? d - k * b : b;
+    return (size_t)d + (size_t)k * b * b + (size_t)j * bk + j;
+  }
+  return family == MIVI_FULLRANK ? (size_t)d + (size_t)i * d + i : (size_t)d + i;
+}
+
 template <typename T>
 __global__ void k_clip(int d, int family, T *params, T epsilon) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < d) {
-    const size_t o = family != MIVI_FULLRANK ? (size_t)d + i : (size_t)d + (size_t)i * d + i;   // (low-rank: scale_diag = params[d .. 2d))
+    const size_t o = scale_diag_offset(i, d, family);   // (low-rank: scale_diag = params[d .. 2d))
     params[o] = clip_step(params[o], epsilon);
   }
 }
@@ -277,7 +289,7 @@ void launch_clip(mivi_ctx *c, void *params, double epsilon) {
   const int d = c->cfg.d;
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_clip<T>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, c->cfg.family, (T *)params, (T)epsilon);
+    hipLaunchKernelGGL(k_clip<T>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, family_code(c), (T *)params, (T)epsilon);
   });
 }
 
@@ -292,7 +304,7 @@ __global__ void k_prox(int d, int family, T *params, double stepsize, const doub
       const double v = dog_sc[0], r = dog_sc[1];
       g = (dog_kind == 1 ? r * r : r) / sqrt(v);
     }
-    const size_t o = family == MIVI_MEANFIELD ? (size_t)d + i : (size_t)d + (size_t)i * d + i;
+    const size_t o = family == MIVI_MEANFIELD ? (size_t)d + i : scale_diag_offset(i, d, family);
     params[o] = prox_entropy_step(params[o], (T)g);
   }
 }
@@ -301,7 +313,7 @@ void launch_prox(mivi_ctx *c, void *params, double stepsize, const void *dog_sta
   const double *sc = dog_state ? (const double *)((const char *)dog_state + mivi_dog_state_bytes(c) - 16) : nullptr;
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_prox<T>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, c->cfg.family, (T *)params, stepsize, sc, dog_kind);
+    hipLaunchKernelGGL(k_prox<T>, dim3((d + 255) / 256), dim3(256), 0, c->stream, d, family_code(c), (T *)params, stepsize, sc, dog_kind);
   });
 }
 
@@ -310,6 +322,11 @@ __device__ __forceinline__ bool is_scale_diag(int64_t i, int d, int family) {
   if (i < d) return false;
   if (family == MIVI_MEANFIELD) return true;
   if (family == MIVI_LOWRANK) return i < 2 * (int64_t)d;   // [m; D; vec U]
+  if ((family & 0xff) == MIVI_BLOCKDIAG) {                 // [m; C_0; C_1; ...]: every block before the last holds b^2 entries
+    const int64_t b = family >> 8, nb = (d + b - 1) / b, e = i - d;
+    const int64_t k = e / (b * b) < nb - 1 ? e / (b * b) : nb - 1, r = e - k * b * b, bk = d - k * b < b ? d - k * b : b;
+    return r / bk == r % bk;
+  }
   const int64_t e = i - d;
   return (e / d) == (e % d);
 }
@@ -326,7 +343,7 @@ void launch_descent(mivi_ctx *c, void *params, const void *grad, double eta, dou
   const int64_t n = mivi_params_len(c);
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_descent<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, (T)eta, c->cfg.d, c->cfg.family,
+    hipLaunchKernelGGL(k_descent<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, (T)eta, c->cfg.d, family_code(c),
                        (T)clip_eps);
   });
 }
@@ -354,7 +371,7 @@ void launch_adam(mivi_ctx *c, void *params, const void *grad, void *state, const
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(k_adam<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, (T *)state, t_ptr, t_base, eta, b1, b2,
-                       eps, c->cfg.d, c->cfg.family, (T)clip_eps);
+                       eps, c->cfg.d, family_code(c), (T)clip_eps);
   });
 }
 
@@ -377,7 +394,7 @@ void launch_cocob(mivi_ctx *c, void *params, const void *grad, void *state, doub
   by_dtype(c, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(k_cocob<T>, dim3(grid256(n)), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, (T *)state, (T)alpha, c->cfg.d,
-                       c->cfg.family, (T)clip_eps);
+                       family_code(c), (T)clip_eps);
   });
 }
 
@@ -579,7 +596,7 @@ bool launch_dog_update_fused(mivi_ctx *c, void *params, const void *grad, void *
     return by_dtype(c, [&](auto t) {
       using T = decltype(t);
       hipLaunchKernelGGL((k_dog_update<T, true>), dim3(1), dim3(1024), 0, c->stream, n, (T *)params, (const T *)grad, (const T *)state, sc, kind,
-                         c->cfg.d, c->cfg.family, (T)clip_eps, (T *)avg, avg_eta, t_ptr, t_base);
+                         c->cfg.d, family_code(c), (T)clip_eps, (T *)avg, avg_eta, t_ptr, t_base);
       return true;
     });
   }
@@ -589,7 +606,7 @@ bool launch_dog_update_fused(mivi_ctx *c, void *params, const void *grad, void *
     using T = decltype(t);
     hipLaunchKernelGGL(k_dog_norms<T>, dim3(nb), dim3(256), 0, c->stream, n, (const T *)params, (const T *)grad, (const T *)state, part);
     hipLaunchKernelGGL(k_dog_eta, dim3(1), dim3(256), 0, c->stream, nb, part, sc, eta, kind);
-    hipLaunchKernelGGL(k_dog_apply_fused<T>, dim3(2048), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, eta, c->cfg.d, c->cfg.family,
+    hipLaunchKernelGGL(k_dog_apply_fused<T>, dim3(2048), dim3(256), 0, c->stream, n, (T *)params, (const T *)grad, eta, c->cfg.d, family_code(c),
                        (T)clip_eps, (T *)avg, avg_eta, t_ptr, t_base);
     return true;
   });

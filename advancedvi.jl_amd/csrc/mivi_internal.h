@@ -245,6 +245,14 @@ __host__ __device__ inline long long flow_net_len(const FlowArch &a, int nin, in
   return n + (long long)nout * prev + nout;
 }
 
+// The block-diagonal family's layout (MIVI_BLOCKDIAG, mivi_blockdiag_t behind mivi_create_blockdiag) as the kernels take it: blocks of b rows
+// (the last one shorter), worked on in UNITS of g consecutive blocks = R rows (kernels_blockdiag.hip: g = 16 / b for b <= 8, else 1).
+struct BdShape {
+  int d, b, g, R, n_units;
+  int ns_max;        // the most slices of the sample axis a launch takes (1: the units alone fill the chip)
+  long long plen;    // d + sum b_k^2
+};
+
 // --------------------------------------------------------------------------------------------
 // Context
 // --------------------------------------------------------------------------------------------
@@ -555,6 +563,10 @@ struct mivi_ctx : mivi_ctx_streams {
   // the f64 log q per sample; the VJP's f64 partials, flow_slices x params_len
   mivi::FlowArch flow{};
   mivi::DevBuf flow_X, flow_lq, flow_part;
+  // block-diagonal family (kernels_blockdiag.hip): its layout (b = 0: not such a context); f64 [sum 0.5 eps^2 | sum ell (n_units x ns_max each) |
+  // sum log C_ii, non-positive counts (2 x n_units)]; the VJP's f64 partials, slices x params_len (only where a launch takes slices)
+  mivi::BdShape bd{};
+  mivi::DevBuf bd_sc, bd_part;
   // base distribution of the location-scale families (mivi_set_base_dist; base_dist.h, kernels_basedist.hip, api_basedist.hip)
   int base = MIVI_BASE_NORMAL;
   double base_nu = 0.0, base_c0 = 0.0, base_H = 0.0;   // TDist's degrees of freedom; -(constant of log phi); H(phi) -- f64, computed once on the host
@@ -835,6 +847,17 @@ void launch_lowr_sample(mivi_ctx *c, const void *params, int M, void *Z, bool wi
 void launch_lowr_woodbury(mivi_ctx *c, const void *params, int M, bool want_v, const LowrPoints *pts = nullptr);   // t -> s, x, log q (want_v: V over t)
 double *lowr_logq_of(const mivi_ctx *c, const LowrPoints &pts);   // where launch_lowr_woodbury leaves the f64 log q of pts' columns
 void launch_lowr_vjp_finish(mivi_ctx *c, const void *params, int M, int want_grad, const ValueIn &vin, const OutArgs &out);   // W = G (and V, x, the draws) -> out.grad; out.value, the non-finite flag, the elbo record
+
+// kernels_blockdiag.hip: the block-diagonal family's estimate and rand (api_blockdiag.hip drives them)
+BdShape bd_shape(int d, int b);
+int bd_slices(const BdShape &s, int M);      // slices of the sample axis a launch over M samples takes (<= ns_max, and at most 256 MB of partials)
+size_t bd_sc_bytes(const BdShape &s);        // of c->bd_sc
+bool bd_prepare(mivi_ctx *c);                // the kernels' LDS attributes, once per context (false: the runtime refused)
+void launch_bd_forward(mivi_ctx *c, const void *params, const RngArgs &rng, int M, void *Z, void *eps, bool stats);   // draws -> Z (eps: the draws, or nullptr); stats: the value's partials -> bd_sc
+int bd_logpdf_chunks(const BdShape &s);      // chunks of units a logpdf launch leaves per-column partials for (<= 64)
+void launch_bd_logpdf(mivi_ctx *c, const void *params, const void *Z, int n, void *logq, void *std, double *part);   // log q (and std = C^-1 (z - mu)) at n <= kSampleChunk points; part: chunks x n f64
+void bd_wire_value(const mivi_ctx *c, int M, bool fused, ValueIn &vin);   // bd_sc's partials of a launch over M samples into vin
+void launch_bd_grad(mivi_ctx *c, const void *params, const RngArgs &rng, int M, bool fused, ValueIn &vin, const OutArgs &out);   // W = grad ell (fused: the draws alone) -> out.grad; wires vin
 
 // kernels_nsf.hip: the neural spline flow's kernels; the launchers below branch to them on a context whose flow.K > 0 (launch_nsf_vjp,
 // which takes the typed argument block, is declared beside FlowArgs in flow_tile.h)

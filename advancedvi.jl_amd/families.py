@@ -10,9 +10,10 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-MEANFIELD, FULLRANK, LOWRANK, REALNVP, NSF = 0, 1, 2, 3, 4
+MEANFIELD, FULLRANK, LOWRANK, REALNVP, NSF, BLOCKDIAG = 0, 1, 2, 3, 4, 5
 FLOW_FAMILIES = (REALNVP, NSF)   # the coupling flows: one surface, one set of refusals
 FLOW_NAMES = {REALNVP: "RealNVP", NSF: "NeuralSplineFlow"}
+BLOCKDIAG_MAX_BLOCK = 64   # MIVI_BLOCKDIAG_MAX_BLOCK (include/mivi.h)
 LOWRANK_MAX_RANK = 64   # MIVI_LOWRANK_MAX_RANK (include/mivi.h)
 FLOW_MAX_D, FLOW_MAX_HIDDEN, FLOW_MAX_LAYERS = 128, 64, 32   # MIVI_FLOW_MAX_* (include/mivi.h)
 
@@ -214,6 +215,76 @@ def LowRankGaussian(mu, D, U) -> MvLocationScaleLowRank:
     return MvLocationScaleLowRank(np.asarray(mu), np.asarray(D), np.asarray(U))
 
 
+def blockdiag_layout(d: int, block: int):
+    """The parameter vector of the block-diagonal family (MIVI_BLOCKDIAG, include/mivi.h): ([(first coordinate, rows b_k, offset of C_k)],
+    params_len).  [mu (d); C_0; C_1; ...], C_k column-major b_k x b_k, every block `block` rows but the last."""
+    blocks, off = [], d
+    for lo in range(0, d, block):
+        bk = min(block, d - lo)
+        blocks.append((lo, bk, off))
+        off += bk * bk
+    return blocks, off
+
+
+class BlockDiagGaussian:
+    """MvLocationScale(location, scale, Normal()) with a block-diagonal lower-triangular scale (src/families/location_scale.jl:12-108 is
+    generic in `scale`): z[block k] = location[block k] + tril(blocks[k]) u[block k].  `blocks`: square arrays of one size b, only the last
+    may be smaller.  Arrays are numpy (host) float32/float64."""
+
+    family = BLOCKDIAG
+
+    def __init__(self, location, blocks):
+        self.location = np.ascontiguousarray(location)
+        if self.location.dtype not in (np.float32, np.float64):
+            raise TypeError("BlockDiagGaussian: eltype must be Float32 or Float64")
+        self.blocks = [np.tril(np.asarray(B, dtype=self.location.dtype)) for B in blocks]
+        if not self.blocks or any(B.ndim != 2 or B.shape[0] != B.shape[1] for B in self.blocks):
+            raise ValueError("blocks must be a non-empty list of square lower-triangular matrices")
+        self.block = self.blocks[0].shape[0]
+        if not 1 <= self.block <= BLOCKDIAG_MAX_BLOCK:
+            raise ValueError(f"the block size must be in 1 .. {BLOCKDIAG_MAX_BLOCK}")
+        sizes = [B.shape[0] for B in self.blocks]
+        if any(s != self.block for s in sizes[:-1]) or not 1 <= sizes[-1] <= self.block:
+            raise ValueError("every block but the last must have the same size, and the last must not be larger")
+        if self.location.ndim != 1 or self.location.shape[0] != sum(sizes):
+            raise ValueError("location must have one entry per row of the blocks")
+
+    def __len__(self):
+        return self.location.shape[0]
+
+    @property
+    def eltype(self):
+        return self.location.dtype
+
+    def dense_scale(self):
+        """the d x d lower-triangular scale with the blocks on its diagonal"""
+        C = np.zeros((len(self), len(self)), dtype=self.eltype)
+        for (lo, bk, _), B in zip(blockdiag_layout(len(self), self.block)[0], self.blocks):
+            C[lo:lo + bk, lo:lo + bk] = B
+        return C
+
+    def entropy(self):   # d H(Normal) + logdet(scale), location_scale.jl:52-57
+        ld = sum(np.log(np.diagonal(B)).sum() for B in self.blocks)
+        return self.eltype.type(len(self) * self.eltype.type(Normal().entropy()) + ld)
+
+    def logpdf(self, z, want_std=False):   # host statistic like entropy / cov (the device entry is avi.logpdf(q, z)): z of shape (d,) or (d, n)
+        r = (np.asarray(z, dtype=self.eltype).T - self.location).T
+        x = np.concatenate([np.linalg.solve(B, r[lo:lo + bk]) for (lo, bk, _), B in zip(blockdiag_layout(len(self), self.block)[0], self.blocks)])
+        ld = sum(np.log(np.diagonal(B)).sum() for B in self.blocks)
+        lq = -0.5 * (x * x).sum(axis=0) - 0.5 * len(self) * math.log(2.0 * math.pi) - ld
+        return (lq, x) if want_std else lq   # x = scale^-1 (z - location), the standardised points
+
+    def mean(self):
+        return self.location.copy()
+
+    def var(self):
+        return np.concatenate([(B * B).sum(axis=1) for B in self.blocks])
+
+    def cov(self):
+        C = self.dense_scale()
+        return C @ C.T
+
+
 def flow_layout(d: int, hidden_dims, n_layers: int):
     """The parameter vector of a RealNVP flow (MIVI_REALNVP, include/mivi.h), block by block: a list of
     (layer l = 1 .. L, net "s" | "t", j = 1 .. H + 1, "W" | "b", offset, shape).  For l = 1 .. L the s net, then the t net; a net is
@@ -367,8 +438,8 @@ class Restructure:
     """The `re` closure returned by Optimisers.destructure; RestructureMeanField for the
     Diagonal case (src/families/location_scale.jl:28-37)."""
 
-    def __init__(self, d: int, family: int, dtype, rank: int = 0, dist=None, flow=None):
-        self.d, self.family, self.dtype, self.rank = d, family, dtype, rank
+    def __init__(self, d: int, family: int, dtype, rank: int = 0, dist=None, flow=None, block: int = 0):
+        self.d, self.family, self.dtype, self.rank, self.block = d, family, dtype, rank, block
         self.dist = dist if dist is not None else Normal()   # carried through, as re.model.dist (location_scale.jl:32-37)
         self.flow = flow   # REALNVP: (hidden_dims, n_layers); NSF: (hidden_dims, n_layers, n_bins, bound)
 
@@ -379,6 +450,11 @@ class Restructure:
             return RealNVPFlow(d, self.flow[0], self.flow[1], flat.copy())
         if self.family == NSF:
             return SplineFlow(d, *self.flow, flat.copy())
+        if self.family == BLOCKDIAG:
+            layout, n = blockdiag_layout(d, self.block)
+            if flat.shape[0] != n:
+                raise ValueError("flat parameter vector has the wrong length")
+            return BlockDiagGaussian(flat[:d].copy(), [flat[off:off + bk * bk].reshape(bk, bk, order="F") for _, bk, off in layout])
         if self.family == LOWRANK:
             if flat.shape[0] != 2 * d + d * self.rank:
                 raise ValueError("flat parameter vector has the wrong length")
@@ -398,12 +474,16 @@ def destructure(q):
     full-rank : [location; vec(scale)] column-major, length d + d^2, strict upper triangle zero
     low-rank  : [location; scale_diag; vec(scale_factors)] column-major, length 2d + d r (the functor's field order,
                 src/families/location_scale_low_rank.jl:41).
+    block-diag: [location; vec(C_0); vec(C_1); ...] column-major per block, length d + sum b_k^2 (blockdiag_layout)
     RealNVP   : the nets' weights and biases, layer by layer (flow_layout); NeuralSplineFlow likewise (nsf_layout)."""
     d = len(q)
     if q.family == REALNVP:   # the flow's own flat vector (flow_layout)
         return q.params.copy(), Restructure(d, REALNVP, q.eltype, flow=(q.hidden_dims, q.n_layers))
     if q.family == NSF:
         return q.params.copy(), Restructure(d, NSF, q.eltype, flow=flow_arch(q))
+    if q.family == BLOCKDIAG:
+        flat = np.concatenate([q.location] + [B.reshape(-1, order="F") for B in q.blocks])
+        return flat.astype(q.eltype, copy=False), Restructure(d, BLOCKDIAG, q.eltype, block=q.block)
     if q.family == LOWRANK:
         flat = np.concatenate([q.location, q.scale_diag, q.scale_factors.reshape(-1, order="F")])
         return flat.astype(q.eltype, copy=False), Restructure(d, LOWRANK, q.eltype, q.rank)

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import objectives as O
 from . import subsampling as S
-from .families import COUPLING_FLOWS, FLOW_FAMILIES, FLOW_NAMES, LOWRANK, MvLocationScale, MvLocationScaleLowRank, destructure
+from .families import BlockDiagGaussian, COUPLING_FLOWS, FLOW_FAMILIES, FLOW_NAMES, LOWRANK, MvLocationScale, MvLocationScaleLowRank, destructure
 
 
 # --- operators (src/optimization/clip_scale.jl, src/AdvancedVI.jl:173-204) ------------------------
@@ -261,11 +261,14 @@ def init(rng, alg, q_init, prob):
     M = _measure_space(alg)
     if M is not None:
         return M.init(rng, alg, q_init, prob)
+    if isinstance(q_init, BlockDiagGaussian) and isinstance(alg.objective, S.SubsampledObjective):
+        raise TypeError("a SubsampledObjective is not implemented for the block-diagonal family (BlockDiagGaussian): the batch schedule "
+                        "(mivi_logreg_set_batch_schedule) refuses it -- drop `subsampling`, or use a MeanFieldGaussian / FullRankGaussian")
     if isinstance(q_init, MvLocationScaleLowRank) and isinstance(alg.operator, ProximalLocationScaleEntropy):
         raise TypeError(_NO_PROX_LOWRANK)
     if isinstance(q_init, COUPLING_FLOWS) and isinstance(alg.operator, (ClipScale, ProximalLocationScaleEntropy)):
         raise TypeError(_NO_SCALE_FLOW.format(type(alg.operator).__name__, FLOW_NAMES[q_init.family]))
-    if isinstance(q_init, (MvLocationScale, MvLocationScaleLowRank)) and isinstance(alg.operator, IdentityOperator):
+    if isinstance(q_init, (MvLocationScale, MvLocationScaleLowRank, BlockDiagGaussian)) and isinstance(alg.operator, IdentityOperator):
         warnings.warn(
             "IdentityOperator is used with a variational family <:MvLocationScale. Optimization can easily fail under "
             "this combination due to singular scale matrices. Consider using the operator `ClipScale` in the algorithm "
@@ -701,6 +704,9 @@ def optimize_many(rngs, algorithm, max_iter: int, probs, q_inits, *, states=None
     if flow is not None:
         raise TypeError(f"optimize_many has no method for a normalizing flow ({FLOW_NAMES[flow.family]}): its runs are small Gaussian families, one "
                         "workgroup each -- call `optimize` once per run")
+    if any(isinstance(q, BlockDiagGaussian) for q in qs):
+        raise TypeError("optimize_many has no method for the block-diagonal family (BlockDiagGaussian): it has no launch-free loop -- call "
+                        "`optimize` once per run")
     if states is None:
         states = [None] * K
     elif isinstance(states, dict) or len(states) != K or not all(isinstance(s, dict) for s in states):

@@ -61,7 +61,7 @@ typedef enum { MIVI_F32 = 0, MIVI_F64 = 1 } mivi_dtype_t;
  * the DoG entries, and mivi_optimize_steps / _loop as a graph of launches (op 0 or 1).  Every other entry that reads parameters returns
  * MIVI_ERR_UNSUPPORTED on it (the score-gradient and measure-space entries, partials / finalize / dist / p2p, the profile entries,
  * mivi_prox_scale_entropy and op = 2: the reference has no ProximalLocationScaleEntropy method for the family). */
-typedef enum { MIVI_MEANFIELD = 0, MIVI_FULLRANK = 1, MIVI_LOWRANK = 2, MIVI_REALNVP = 3, MIVI_NSF = 4 } mivi_family_t;
+typedef enum { MIVI_MEANFIELD = 0, MIVI_FULLRANK = 1, MIVI_LOWRANK = 2, MIVI_REALNVP = 3, MIVI_NSF = 4, MIVI_BLOCKDIAG = 5 } mivi_family_t;
 #define MIVI_LOWRANK_MAX_RANK 64
 
 /* MIVI_REALNVP: the RealNVP normalizing flow of docs/src/tutorials/flows.md (Dinh et al.; the masks and activations of
@@ -130,6 +130,38 @@ typedef struct {
   double bound;       /* B > 0, finite */
 } mivi_spline_flow_t;
 
+/* MIVI_BLOCKDIAG: MvLocationScale(location, scale, Normal()) (src/families/location_scale.jl:12-108, generic in `scale`) with a BLOCK-DIAGONAL
+ * lower-triangular scale: a full covariance inside each group of consecutive coordinates and none across groups.  Created by
+ * mivi_create_blockdiag.  All indices are 0-based.
+ *   blocks   block size b = mivi_blockdiag_t.block, 1 <= b <= MIVI_BLOCKDIAG_MAX_BLOCK, uniform; nb = ceil(d / b) blocks, block k covers the
+ *            coordinates [k b, min(d, (k + 1) b)) and has b_k = min(b, d - k b) rows (only the last block can be shorter)
+ *   params   [mu (d); C_0; C_1; ...; C_{nb-1}], C_k a dense column-major b_k x b_k matrix read as tril(C_k) -- entry (i, j) of block k at
+ *            d + k b^2 + j b_k + i.  Entries above a block's diagonal are never read and their gradient is exactly 0 (the full-rank
+ *            layout d + d^2, per block).  params_len = d + sum_k b_k^2
+ *   rand     z[block k] = mu[block k] + tril(C_k) eps[block k], eps ~ N(0, I_d): the mean-field family's Philox stream, d rows (eps of an
+ *            estimate index is bit for bit what a MIVI_MEANFIELD context of the same d, n_mc and seed draws)
+ *   entropy  d/2 (1 + log 2 pi) + sum_i log C_ii (the closed forms), or the Monte-Carlo mean of 1/2 |eps_m|^2 + d/2 log 2 pi + sum_i log C_ii
+ *   gradient with W = grad log pi(z) (d x n_mc, M = m_total): d mu = -(1/M) W 1, dC_k = -(1/M) tril(W_k eps_k') - c diag(1 / C_ii), c the
+ *            estimator's direct coefficient (closed form 1, closed form zero-gradient 0, Monte-Carlo 1, sticking the landing 0, its
+ *            zero-gradient form -1); the sticking-the-landing kinds use W + C_k^-T eps_k in place of W_k.  b = 1 is the mean-field family
+ *   limits   any d >= 1 and n_mc >= 1 with d * (n_mc rounded up to 64) <= MIVI_BLOCKDIAG_MAX_PLANE (the d x n_mc work planes; d is
+ *            indexed in 64 bits throughout), f32 and f64, all five entropy kinds, the standard-normal base only
+ * What family 5 supports: destroy / synchronize / set_stream / params_len, every mivi_set_target_* and mivi_set_bijector_stacked[_ex],
+ * mivi_sample (eps_dev: T[d * n_mc]) / mivi_sample_constrained, mivi_logpdf[_host] (std served: the scale is square; X = C^-1 (z - mu) by
+ * forward substitution per block, X and every sum in f64) / mivi_logpdf_constrained[_host], mivi_estimate_gradient[_host / _n / _each] (the batched forms as sequential
+ * single calls), mivi_estimate_objective[_host], every update entry (clip, descent, adam, cocob, DoG / DoWG, mivi_prox_scale_entropy --
+ * ClipScale and ProximalLocationScaleEntropy touch diagind(scale) only, which the reference defines for any square scale -- mivi_axpby)
+ * and mivi_optimize_steps / _loop as a graph of launches with every rule, operator and averager.  mivi_set_base_dist accepts
+ * MIVI_BASE_NORMAL and refuses every other base.  Every other entry that reads parameters returns MIVI_ERR_UNSUPPORTED with a message
+ * naming the entry and "block-diagonal family (MIVI_BLOCKDIAG)": partials / finalize / dist / comm / p2p and sharded contexts, the batch
+ * schedule (mivi_logreg_set_batch_schedule / _seek_batch, mivi_optimize_loop_batches), mivi_optimize_loop_many, the score-gradient
+ * entries, mivi_gauss_expected_grad_hess* and the four measure-space algorithms, and the profile entries. */
+#define MIVI_BLOCKDIAG_MAX_BLOCK 64
+#define MIVI_BLOCKDIAG_MAX_PLANE ((int64_t)1 << 31)
+typedef struct {
+  int32_t block;      /* b, 1 .. MIVI_BLOCKDIAG_MAX_BLOCK */
+} mivi_blockdiag_t;
+
 /* src/algorithms/entropy.jl: ClosedFormEntropy :25-29, ClosedFormEntropyZeroGradient :11-15,
  * MonteCarloEntropy :40-46, StickingTheLandingEntropy :57-65, StickingTheLandingEntropyZeroGradient :78-90 */
 typedef enum {
@@ -171,6 +203,9 @@ mivi_status_t mivi_create_flow(const mivi_config_t *cfg, const mivi_flow_t *flow
 /* A MIVI_NSF context (cfg->family must be MIVI_NSF; mivi_create and mivi_create_flow answer MIVI_ERR_BAD_ARG for that family).  The
  * same answers as mivi_create_flow: MIVI_ERR_BAD_ARG outside the limits above, MIVI_ERR_UNSUPPORTED for the entropy kind and the shard. */
 mivi_status_t mivi_create_spline_flow(const mivi_config_t *cfg, const mivi_spline_flow_t *flow, mivi_ctx_t **out);
+/* A MIVI_BLOCKDIAG context (cfg->family must be MIVI_BLOCKDIAG; mivi_create answers MIVI_ERR_BAD_ARG for that family).  MIVI_ERR_BAD_ARG
+ * outside the limits above; MIVI_ERR_UNSUPPORTED for a sharded context (m_offset != 0 or m_total not in {0, n_mc}). */
+mivi_status_t mivi_create_blockdiag(const mivi_config_t *cfg, const mivi_blockdiag_t *bd, mivi_ctx_t **out);
 mivi_status_t mivi_destroy(mivi_ctx_t *ctx);
 const char *mivi_last_error(const mivi_ctx_t *ctx);
 int32_t mivi_version(void);
@@ -180,7 +215,7 @@ mivi_status_t mivi_set_stream(mivi_ctx_t *ctx, void *hip_stream);
  * clears, returning MIVI_ERR_NONFINITE / MIVI_ERR_NONPOSITIVE_SCALE -- the once-per-step isfinite check of
  * src/algorithms/common.jl:83-89. */
 mivi_status_t mivi_synchronize(mivi_ctx_t *ctx);
-/* length of `params` / gradient: 2d or d + d*d  (test/families/location_scale.jl:146-155); low-rank: 2d + d*rank */
+/* length of `params` / gradient: 2d or d + d*d  (test/families/location_scale.jl:146-155); low-rank: 2d + d*rank; block-diagonal: d + sum b_k^2 */
 int64_t mivi_params_len(const mivi_ctx_t *ctx);
 /* length of the shard-additive partials buffer ([sum_m W (d); sum_m W (x) eps; sum ell; sum 0.5|eps|^2]):
  * mean-field 2d + 2; full-rank d + d(d+1)/2 + 2 -- only the lower triangle travels, packed column by column
