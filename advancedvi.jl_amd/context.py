@@ -29,6 +29,15 @@ def torch_dtype(np_dtype):
     return torch.float32 if np.dtype(np_dtype) == np.float32 else torch.float64
 
 
+# The families with a creating entry of their own (mivi_create creates the others): the entry, the family's name in the message of a status
+# that arrives before a context exists, and -- the coupling flows -- what `flow` has to be
+_CREATORS = {REALNVP: ("mivi_create_flow", "RealNVP family", "a REALNVP context needs flow = (hidden_dims, n_layers)"),
+             NSF: ("mivi_create_spline_flow", "neural spline flow family", "an NSF context needs flow = (hidden_dims, n_layers, n_bins, bound)"),
+             BLOCKDIAG: ("mivi_create_blockdiag", "block-diagonal family", None)}
+# ... and the flows' architecture: the name in its validation messages, the ABI struct, the casts of what follows (hidden_dims, n_layers)
+_FLOW_FIELDS = {REALNVP: ("RealNVP", _lib.MiviFlow, ()), NSF: ("NeuralSplineFlow", _lib.MiviSplineFlow, (int, float))}
+
+
 class MiviContext:
     """One RepGradELBO estimator instance on one GPU (mivi_create ... mivi_destroy)."""
 
@@ -50,45 +59,36 @@ class MiviContext:
         cfg = _lib.MiviConfig(_NP2MIVI[self.np_dtype], self.family, self.d, self.n_mc, self.entropy, self.device,
                               C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(m_offset), int(m_total), C.c_void_p(stream), 0, self.rank)
         h = C.c_void_p()
-        if self.family == REALNVP:
-            if flow is None:
-                raise ValueError("a REALNVP context needs flow = (hidden_dims, n_layers)")
+        entry, name, arch = _CREATORS.get(self.family, ("mivi_create", None, None))
+        args = ()
+        if self.family in _FLOW_FIELDS:
+            what, struct, tail = _FLOW_FIELDS[self.family]
+            if flow is None or len(flow) != 2 + len(tail):
+                raise ValueError(arch)
             hidden = [int(w) for w in flow[0]]
             if not 1 <= len(hidden) <= 3:
-                raise ValueError("RealNVP: one to three hidden layers")
-            self.flow = (tuple(hidden), int(flow[1]))
-            arch = _lib.MiviFlow(int(flow[1]), len(hidden), (C.c_int32 * 3)(*(hidden + [0] * (3 - len(hidden)))))
-            st = self.lib.mivi_create_flow(C.byref(cfg), C.byref(arch), C.byref(h))
-            if st == 6:   # MIVI_ERR_UNSUPPORTED before a context exists to carry the message
-                sharded = int(m_offset) != 0 or int(m_total) not in (0, self.n_mc)
-                raise _lib.MiviError(st, "mivi_create_flow: the RealNVP family has no sharded form (m_offset / m_total)" if sharded else
-                                         "mivi_create_flow: a flow has no entropy(q) -- the estimators that work on it are MonteCarloEntropy "
-                                         "and StickingTheLandingEntropy")
-        elif self.family == NSF:
-            if flow is None or len(flow) != 4:
-                raise ValueError("an NSF context needs flow = (hidden_dims, n_layers, n_bins, bound)")
-            hidden = [int(w) for w in flow[0]]
-            if not 1 <= len(hidden) <= 3:
-                raise ValueError("NeuralSplineFlow: one to three hidden layers")
-            self.flow = (tuple(hidden), int(flow[1]), int(flow[2]), float(flow[3]))
-            arch = _lib.MiviSplineFlow(int(flow[1]), len(hidden), (C.c_int32 * 3)(*(hidden + [0] * (3 - len(hidden)))), int(flow[2]), float(flow[3]))
-            st = self.lib.mivi_create_spline_flow(C.byref(cfg), C.byref(arch), C.byref(h))
-            if st == 6:   # MIVI_ERR_UNSUPPORTED before a context exists to carry the message
-                sharded = int(m_offset) != 0 or int(m_total) not in (0, self.n_mc)
-                raise _lib.MiviError(st, "mivi_create_spline_flow: the neural spline flow family has no sharded form (m_offset / m_total)" if sharded else
-                                         "mivi_create_spline_flow: a flow has no entropy(q) -- the estimators that work on it are MonteCarloEntropy "
-                                         "and StickingTheLandingEntropy")
+                raise ValueError(f"{what}: one to three hidden layers")
+            self.flow = (tuple(hidden), int(flow[1]), *(cast(v) for cast, v in zip(tail, flow[2:])))
+            args = (struct(self.flow[1], len(hidden), (C.c_int32 * 3)(*(hidden + [0] * (3 - len(hidden)))), *self.flow[2:]),)
         elif self.family == BLOCKDIAG:
-            st = self.lib.mivi_create_blockdiag(C.byref(cfg), C.byref(_lib.MiviBlockDiag(self.block)), C.byref(h))
-            if st == 6:   # MIVI_ERR_UNSUPPORTED before a context exists to carry the message
-                raise _lib.MiviError(st, "mivi_create_blockdiag: the block-diagonal family has no sharded form (m_offset / m_total)")
-        else:
-            st = self.lib.mivi_create(C.byref(cfg), C.byref(h))
+            args = (_lib.MiviBlockDiag(self.block),)
+        st = getattr(self.lib, entry)(C.byref(cfg), *(C.byref(a) for a in args), C.byref(h))
+        if st == 6 and name:   # MIVI_ERR_UNSUPPORTED before a context exists to carry the message
+            sharded = int(m_offset) != 0 or int(m_total) not in (0, self.n_mc)
+            raise _lib.MiviError(st, f"{entry}: the {name} has no sharded form (m_offset / m_total)" if sharded or self.family == BLOCKDIAG else
+                                     f"{entry}: a flow has no entropy(q) -- the estimators that work on it are MonteCarloEntropy "
+                                     "and StickingTheLandingEntropy")
         _lib.check(self.lib, None, st)
         self.h = h
         self.m_total = int(m_total) if m_total else self.n_mc
         self._keep = []      # keep-alive for callbacks / borrowed device arrays
         self.problem = None
+
+    @classmethod
+    def for_family(cls, q, n_mc, entropy, seed, device=0):
+        """A context for the variational family q: what its family needs beside the dimension (rank, flow, block) is read off q."""
+        return cls(q.eltype, q.family, len(q), n_mc, entropy, seed, device=device, rank=getattr(q, "rank", 0), flow=getattr(q, "arch", None),
+                   block=getattr(q, "block", 0))
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):

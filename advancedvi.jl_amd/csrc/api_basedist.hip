@@ -8,8 +8,7 @@
 static const char *base_name(const mivi_ctx *c) { return c->base == MIVI_BASE_LAPLACE ? "Laplace" : "TDist"; }
 
 mivi_status_t refuse_non_gaussian(mivi_ctx *c, const char *entry) {
-  if (mivi_status_t rs = refuse_blockdiag(c, entry)) return rs;
-  if (mivi_status_t rs = refuse_lowrank(c, entry)) return rs;
+  if (mivi_status_t rs = refuse(c, LACKS_GAUSSIAN_ONLY, entry)) return rs;
   if (mivi_status_t rs = refuse_batch_schedule(c, entry)) return rs;   // (these entries are also the ones that read a logistic regression's data set themselves)
   if (c->base == MIVI_BASE_NORMAL) return MIVI_OK;
   c->err = std::string(entry) + ": not supported with the non-normal base distribution " + base_name(c) + " (mivi_set_base_dist)";
@@ -30,9 +29,10 @@ mivi_status_t mivi_set_base_dist(mivi_ctx_t *c, int32_t base, double nu) {
   if (base != MIVI_BASE_NORMAL && base != MIVI_BASE_LAPLACE && base != MIVI_BASE_TDIST) return fail(c, MIVI_ERR_BAD_ARG, "mivi_set_base_dist: unknown base distribution");
   if (base == MIVI_BASE_TDIST && !(nu > 0.0 && isfinite(nu))) return fail(c, MIVI_ERR_BAD_ARG, "mivi_set_base_dist: TDist needs finite degrees of freedom nu > 0");
   if (base != MIVI_BASE_NORMAL) {
-    if (c->cfg.family == MIVI_LOWRANK) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_set_base_dist: a non-normal base is not supported on the low-rank family (MIVI_LOWRANK)");
-    if (mivi_status_t rs = refuse_blockdiag(c, "mivi_set_base_dist with a non-normal base")) return rs;
-    if (mivi_status_t rs = refuse_flow(c, "mivi_set_base_dist with a non-normal base (the flow's base is the standard normal)")) return rs;
+    // (a family without a scale is a flow, not an MvLocationScale(location, scale, dist): its message says whose base that is)
+    if (mivi_status_t rs = refuse(c, LACKS_BASE_DIST, family_lacks(c, LACKS_CLIP_SCALE) ? "mivi_set_base_dist with a non-normal base (the flow's base is the standard normal)"
+                                                                                        : "mivi_set_base_dist with a non-normal base"))
+      return rs;
     if (c->cfg.m_offset != 0 || (c->cfg.m_total != 0 && c->cfg.m_total != c->cfg.n_mc))
       return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_set_base_dist: a non-normal base is not supported on a sharded context");
   }
@@ -96,10 +96,7 @@ mivi_status_t run_estimate_base(mivi_ctx *c, const void *params, const RngArgs &
   vin.n_he_part = eps_blocks(c, M);
   if (full) launch_fr_sample(c, params, M, TGT_NONE, c->Z.p);
   else launch_bd_mf_sample(c, params, M, U, c->Z.p);
-  if (c->bij_on) launch_bij_forward(c, M);   // the target sees binv(z)
-  mivi_status_t s = target_on_z(c, M, want_grad, p, vin);
-  if (s) return s;
-  if (c->bij_on) launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
+  if (mivi_status_t s = target_behind_bijector(c, M, want_grad, p, vin)) return s;
   if (want_grad) {
     if (full) {
       if (stl) {   // W += C^-T (-psi(U)): the solves of the Gaussian route (stl_term, api_estimate.hip) with the base's right-hand side

@@ -1,14 +1,7 @@
 // libmivi C ABI, the block-diagonal Gaussian family (MIVI_BLOCKDIAG; MvLocationScale with a block-diagonal LowerTriangular scale, defined
-// in include/mivi.h): creation, one RepGradELBO estimate as launches of kernels_blockdiag.hip, and rand.  run_estimate (api_estimate.hip)
-// branches here before anything that means "full-rank"; every entry the family does not support refuses it through refuse_blockdiag
-// (api_common.h; refuse_non_gaussian begins with it).
+// in include/mivi.h): creation, one RepGradELBO estimate as launches of kernels_blockdiag.hip, rand and logpdf.  The host layer reaches
+// them through the family's row of kFamilies (api_common.h), which also says which groups of entries refuse the family.
 #include "api_common.h"
-
-mivi_status_t refuse_blockdiag(mivi_ctx *c, const char *entry) {
-  if (c->cfg.family != MIVI_BLOCKDIAG) return MIVI_OK;
-  c->err = std::string(entry) + ": not supported on the block-diagonal family (MIVI_BLOCKDIAG)";
-  return MIVI_ERR_UNSUPPORTED;
-}
 
 mivi_status_t mivi_create_blockdiag(const mivi_config_t *cfg, const mivi_blockdiag_t *bd, mivi_ctx_t **out) {
   if (!cfg || !bd || !out) return MIVI_ERR_BAD_ARG;
@@ -29,6 +22,8 @@ mivi_status_t mivi_create_blockdiag(const mivi_config_t *cfg, const mivi_blockdi
   return MIVI_OK;
 }
 
+int64_t params_len_blockdiag(const mivi_ctx *c) { return c->bd.plen; }
+
 // the family's scratch (ensure_work): the value's partials, and the VJP's f64 partials where a launch takes slices of the sample axis
 mivi_status_t ensure_work_blockdiag(mivi_ctx *c, int cap) {
   const int ns = bd_slices(c->bd, cap);
@@ -41,20 +36,12 @@ mivi_status_t ensure_work_blockdiag(mivi_ctx *c, int cap) {
 // One estimate over M samples (no allocation, no host synchronisation with a built-in target: capturable).
 //   diagonal-Gaussian target, no bijector, a gradient wanted:  ONE kernel (draws, Z, target, VJP)  [-> finish]  -> value
 //   otherwise:  forward (draws, Z) [-> bijector] -> target [-> bijector] [-> VJP on the redrawn tiles [-> finish]] -> value
-mivi_status_t run_estimate_blockdiag(mivi_ctx *c, const void *params, const RngArgs &rng, int M, int want_grad, const OutArgs &out) {
-  if (out.partials_mode) return fail(c, MIVI_ERR_UNSUPPORTED, "shard partials: not supported on the block-diagonal family (MIVI_BLOCKDIAG)");
-  c->pre.clear();
-  const int p = c->cur;
-  ValueIn vin{};
-  vin.ell_const = c->t_const;
+mivi_status_t run_estimate_blockdiag(mivi_ctx *c, const void *params, const RngArgs &rng, int M, int want_grad, const OutArgs &out, ValueIn &vin) {
   if (want_grad && c->target == TGT_DIAG_GAUSS && !c->bij_on) {
     launch_bd_grad(c, params, rng, M, true, vin, out);
   } else {
     launch_bd_forward(c, params, rng, M, c->Z.p, nullptr, true);
-    if (c->bij_on) launch_bij_forward(c, M);   // the target sees binv(z)
-    mivi_status_t s = target_on_z(c, M, want_grad, p, vin);
-    if (s) return s;
-    if (c->bij_on) launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
+    if (mivi_status_t s = target_behind_bijector(c, M, want_grad, c->cur, vin)) return s;
     if (want_grad) launch_bd_grad(c, params, rng, M, false, vin, out);
     else bd_wire_value(c, M, false, vin);
   }
@@ -68,4 +55,15 @@ mivi_status_t sample_blockdiag(mivi_ctx *c, const void *params, uint64_t idx, vo
   launch_bd_forward(c, params, rng_of(c, idx), c->cfg.n_mc, Z, eps, false);
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
+}
+
+// logpdf(q, z) (logpdf_launches): the forward substitution C_k X_k = Z_k - mu_k per unit in LDS (k_bd_logpdf, kernels_blockdiag.hip), f64 X
+// and sums; the unit chunks' f64 partials per column, then their sum
+mivi_status_t logpdf_blockdiag(mivi_ctx *c, const void *params, const char *Z, int n, char *logq, char *std, const LogpdfBij *bij) {
+  const size_t d = c->cfg.d, es = c->esize;
+  const int cap = n < kSampleChunk ? n : kSampleChunk;
+  if (mivi_status_t s = ensure(c, c->lp_work, (size_t)bd_logpdf_chunks(c->bd) * cap * sizeof(double), false)) return s;
+  return logpdf_chunks(c, Z, n, logq, bij, [&](const SampleChunk &k, const char *z, char *lq) {
+    launch_bd_logpdf(c, params, z, k.Mc, lq, std ? std + (size_t)k.off * d * es : nullptr, (double *)c->lp_work.p);
+  });
 }

@@ -120,6 +120,12 @@ mivi_status_t target_on_z(mivi_ctx *c, int M, int want_grad, int p, ValueIn &vin
   vin.n_ell = M;
   return MIVI_OK;
 }
+mivi_status_t target_behind_bijector(mivi_ctx *c, int M, int want_grad, int p, ValueIn &vin) {
+  if (c->bij_on) launch_bij_forward(c, M);   // the target sees binv(z)
+  if (mivi_status_t s = target_on_z(c, M, want_grad, p, vin)) return s;
+  if (c->bij_on) launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
+  return MIVI_OK;
+}
 
 // The sticking-the-landing term W += C^-T eps of a full-rank gradient estimate (nothing for the other estimators).
 // dinv_done: the product kernel's riders have already inverted the diagonal blocks of C.
@@ -223,9 +229,13 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
   if (!out.status) out.status = (int *)c->status.p;
   const bool gen2 = c->cfg.family == MIVI_FULLRANK && c->base == MIVI_BASE_NORMAL && lds_route(c, params, M, want_grad, out);
   if (!gen2 && !fr_prepare(c, M)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");   // (cached: a compare per estimate)
-  if (c->cfg.family == MIVI_LOWRANK) return run_estimate_lowrank(c, params, rng, M, want_grad, out);   // (its own kernels; nothing below knows the family)
-  if (is_flow(c)) return run_estimate_flow(c, params, rng, M, want_grad, out);
-  if (c->cfg.family == MIVI_BLOCKDIAG) return run_estimate_blockdiag(c, params, rng, M, want_grad, out);
+  if (const FamilyRow *row = family_row(c)) {   // (its own kernels; nothing below knows the family)
+    if (out.partials_mode && (s = refuse(c, LACKS_GAUSSIAN_ONLY, "shard partials"))) return s;
+    c->pre.clear();
+    ValueIn vin{};
+    vin.ell_const = c->t_const;
+    return row->run_estimate(c, params, rng, M, want_grad, out, vin);
+  }
   if (c->base != MIVI_BASE_NORMAL) return run_estimate_base(c, params, rng, M, want_grad, out);   // (everything below draws its own normals)
   if (gen2) return run_estimate_lds(c, params, rng, M, want_grad, out, ch, upd, stop_after_target);
   ValueIn vin{};
@@ -257,9 +267,7 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
       wire_mf_partials(c, p, vin);
     } else {
       launch_sample_mf(c, params, rng, M, c->Z.p, nullptr, 0, want_grad ? nullptr : (double *)c->he_part[p].p);
-      if (bij) launch_bij_forward(c, M);   // the target sees binv(z)
-      if ((s = target_on_z(c, M, want_grad, p, vin))) return s;
-      if (bij) launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
+      if ((s = target_behind_bijector(c, M, want_grad, p, vin))) return s;
       if (want_grad) {
         launch_mf_main(c, params, rng, M, 1, c->W.p, vin, out);
         wire_mf_partials(c, p, vin);   // (ell_part2: zeros for the non-fused target; he / logdet live here)
@@ -274,9 +282,7 @@ mivi_status_t run_estimate(mivi_ctx *c, const void *params, const RngArgs &rng, 
     vin.n_he_part = eps_blocks(c, M);   // (not he_n: on this route every producer of eps leaves eps_blocks partials)
     if (c->bij_on) {   // Stacked bijector: explicit samples, transformed in place around whatever target is set
       launch_fr_sample(c, params, M, TGT_NONE, c->Z.p);
-      launch_bij_forward(c, M);
-      if ((s = target_on_z(c, M, want_grad, p, vin))) return s;
-      launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
+      if ((s = target_behind_bijector(c, M, want_grad, p, vin))) return s;
     } else if (c->target == TGT_DIAG_GAUSS) {
       launch_fr_sample(c, params, M, TGT_DIAG_GAUSS, nullptr, prev);
       vin.ell_part = (const double *)c->ell_part[p].p;
@@ -357,9 +363,7 @@ mivi_status_t mivi_sample(mivi_ctx_t *c, const void *params, uint64_t idx, void 
   mivi_status_t s = ensure_work(c, M);
   if (s) return s;
   if (c->cfg.family == MIVI_FULLRANK && !fr_prepare(c, M)) return fail(c, MIVI_ERR_HIP, "full-rank work tables: allocation or upload failed");
-  if (c->cfg.family == MIVI_LOWRANK) return sample_lowrank(c, params, idx, Z, eps);
-  if (is_flow(c)) return sample_flow(c, params, idx, Z, eps);
-  if (c->cfg.family == MIVI_BLOCKDIAG) return sample_blockdiag(c, params, idx, Z, eps);
+  if (const FamilyRow *row = family_row(c)) return row->sample(c, params, idx, Z, eps);
   if (c->base != MIVI_BASE_NORMAL) return sample_base(c, params, idx, Z, eps);
   if (c->cfg.family == MIVI_MEANFIELD) {
     launch_sample_mf(c, params, rng_of(c, idx), M, Z, eps, d, nullptr);

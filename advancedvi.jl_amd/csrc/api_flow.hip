@@ -1,15 +1,9 @@
-// libmivi C ABI, the RealNVP normalizing-flow family (MIVI_REALNVP; docs/src/tutorials/flows.md, defined in include/mivi.h): creation, one
-// RepGradELBO estimate as a sequence of launches of kernels_flow.hip, and rand.  run_estimate (api_estimate.hip) branches here before
-// anything that means "location-scale"; every entry the family does not support refuses it through refuse_flow (api_common.h; refuse_lowrank begins with it).
-// The neural spline flow family (MIVI_NSF, mivi_create_spline_flow) is the other coupling flow: the same context with bins in its FlowArch,
-// the same routes and the same refusals (is_flow), its own kernels behind the launchers (kernels_nsf.hip).
+// libmivi C ABI, the coupling flows: the RealNVP normalizing-flow family (MIVI_REALNVP; docs/src/tutorials/flows.md, defined in
+// include/mivi.h) and the neural spline flow family (MIVI_NSF, mivi_create_spline_flow) -- the same context with bins in its FlowArch, its
+// own kernels behind the launchers (kernels_nsf.hip).  Creation, one RepGradELBO estimate as a sequence of launches of kernels_flow.hip,
+// rand and logpdf.  The host layer reaches them through the families' two rows of kFamilies (api_common.h), which share every route and
+// every refusal and differ in name and creating entry.
 #include "api_common.h"
-
-mivi_status_t refuse_flow(mivi_ctx *c, const char *entry) {
-  if (!is_flow(c)) return MIVI_OK;
-  c->err = std::string(entry) + ": not supported on the " + flow_family_name(c);
-  return MIVI_ERR_UNSUPPORTED;
-}
 
 // what mivi_create_flow and mivi_create_spline_flow share: the limits of the conditioner, the estimators, no shards; K = 0: RealNVP
 static mivi_status_t create_coupling_flow(const char *entry, const mivi_config_t *cfg, const mivi_flow_t *flow, int K, double B, mivi_ctx_t **out) {
@@ -58,6 +52,8 @@ mivi_status_t mivi_create_spline_flow(const mivi_config_t *cfg, const mivi_splin
   return create_coupling_flow("mivi_create_spline_flow", cfg, &net, flow->n_bins, flow->bound, out);
 }
 
+int64_t params_len_flow(const mivi_ctx *c) { return flow_params_len(c->flow); }
+
 // the family's scratch for cap samples per launch (ensure_work): every x^l, the f64 log q per sample, the VJP's f64 partials
 mivi_status_t ensure_work_flow(mivi_ctx *c, int cap) {
   const size_t d = c->cfg.d, L = c->flow.L;
@@ -70,19 +66,11 @@ mivi_status_t ensure_work_flow(mivi_ctx *c, int cap) {
 
 // One estimate over M samples (no allocation, no host synchronisation with a built-in target: capturable):
 //   draws + forward (z, every x^l, log q) [-> bijector] -> target [-> bijector] [-> VJP partials: the STL sweep, the parameter sweep] -> finish
-mivi_status_t run_estimate_flow(mivi_ctx *c, const void *params, const RngArgs &rng, int M, int want_grad, const OutArgs &out) {
-  if (out.partials_mode) return fail(c, MIVI_ERR_UNSUPPORTED, (std::string("shard partials: not supported on the ") + flow_family_name(c)).c_str());
+mivi_status_t run_estimate_flow(mivi_ctx *c, const void *params, const RngArgs &rng, int M, int want_grad, const OutArgs &out, ValueIn &vin) {
   if (out.ent_kind != MIVI_ENT_MONTE_CARLO && out.ent_kind != MIVI_ENT_STL)
     return fail(c, MIVI_ERR_UNSUPPORTED, "a flow has no entropy(q): use MonteCarloEntropy (2) or StickingTheLandingEntropy (3)");
-  c->pre.clear();
-  const int p = c->cur;
-  ValueIn vin{};
-  vin.ell_const = c->t_const;
   launch_flow_forward(c, params, rng, M, c->Z.p, nullptr, true);
-  if (c->bij_on) launch_bij_forward(c, M);   // the target sees binv(z)
-  mivi_status_t s = target_on_z(c, M, want_grad, p, vin);
-  if (s) return s;
-  if (c->bij_on) launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
+  if (mivi_status_t s = target_behind_bijector(c, M, want_grad, c->cur, vin)) return s;
   launch_flow_vjp_finish(c, params, M, want_grad, vin, out);
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
@@ -93,4 +81,9 @@ mivi_status_t sample_flow(mivi_ctx *c, const void *params, uint64_t idx, void *Z
   launch_flow_forward(c, params, rng_of(c, idx), c->cfg.n_mc, Z, eps, false);
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
+}
+
+// logpdf(q, z) (logpdf_launches): eps = T^-1(z) through the inverse layers, log q beside it: no parameter-only stage, no scratch
+mivi_status_t logpdf_flow(mivi_ctx *c, const void *params, const char *Z, int n, char *logq, char *, const LogpdfBij *bij) {
+  return logpdf_chunks(c, Z, n, logq, bij, [&](const SampleChunk &k, const char *z, char *lq) { launch_flow_inverse(c, params, z, k.Mc, lq); });
 }

@@ -1,14 +1,16 @@
 // libmivi C ABI, the low-rank Gaussian family (MIVI_LOWRANK; src/families/location_scale_low_rank.jl): one RepGradELBO estimate as a
-// sequence of launches of kernels_lowrank.hip, and rand.  run_estimate (api_estimate.hip) branches here before anything that means
-// "full-rank"; every entry the family does not support refuses it through refuse_lowrank (api_common.h).
+// sequence of launches of kernels_lowrank.hip, rand and logpdf.  The host layer reaches them through the family's row of kFamilies
+// (api_common.h), which also says which groups of entries refuse the family.
 #include "api_common.h"
 
-mivi_status_t refuse_lowrank(mivi_ctx *c, const char *entry) {
-  if (mivi_status_t rs = refuse_flow(c, entry)) return rs;
-  if (c->cfg.family != MIVI_LOWRANK) return MIVI_OK;
-  c->err = std::string(entry) + ": not supported on the low-rank family (MIVI_LOWRANK)";
-  return MIVI_ERR_UNSUPPORTED;
+mivi_status_t lowrank_check_config(const mivi_config_t *cfg) {
+  if (cfg->family != MIVI_LOWRANK) return MIVI_OK;   // (rank is read for this family only)
+  if (cfg->rank < 1 || cfg->rank > MIVI_LOWRANK_MAX_RANK) return MIVI_ERR_BAD_ARG;
+  if (cfg->m_offset != 0 || (cfg->m_total != 0 && cfg->m_total != cfg->n_mc)) return MIVI_ERR_UNSUPPORTED;   // no sharded low-rank estimates
+  return MIVI_OK;
 }
+
+int64_t params_len_lowrank(const mivi_ctx *c) { return 2 * (int64_t)c->cfg.d + (int64_t)c->cfg.d * (int64_t)c->cfg.rank; }
 
 // the family's scratch for cap samples per launch (ensure_work): the draws, V = Sigma^-1 (z - m), the prep block, f64 [s; x; |t|^2; log q]
 mivi_status_t ensure_work_lowrank(mivi_ctx *c, int cap) {
@@ -24,20 +26,12 @@ mivi_status_t ensure_work_lowrank(mivi_ctx *c, int cap) {
 
 // One estimate over M samples (no allocation, no host synchronisation with a built-in target: capturable):
 //   [gram ->] draws + prep -> sample [-> bijector] -> target [-> bijector] [-> Woodbury: s; x, log q, V] [-> VJP partials] -> finish (gradient, value)
-mivi_status_t run_estimate_lowrank(mivi_ctx *c, const void *params, const RngArgs &rng, int M, int want_grad, const OutArgs &out) {
-  if (out.partials_mode) return fail(c, MIVI_ERR_UNSUPPORTED, "shard partials: not supported on the low-rank family (MIVI_LOWRANK)");
+mivi_status_t run_estimate_lowrank(mivi_ctx *c, const void *params, const RngArgs &rng, int M, int want_grad, const OutArgs &out, ValueIn &vin) {
   const int ek = out.ent_kind;
   const bool closed = ek == MIVI_ENT_CLOSED_FORM || ek == MIVI_ENT_CLOSED_FORM_ZERO_GRAD;
-  c->pre.clear();
-  const int p = c->cur;
-  ValueIn vin{};
-  vin.ell_const = c->t_const;
   launch_lowr_draw_prep(c, rng, M, params);
   launch_lowr_sample(c, params, M, c->Z.p, !closed);
-  if (c->bij_on) launch_bij_forward(c, M);   // the target sees binv(z)
-  mivi_status_t s = target_on_z(c, M, want_grad, p, vin);
-  if (s) return s;
-  if (c->bij_on) launch_bij_backward(c, M, want_grad, c->target != TGT_DENSE_GAUSS);
+  if (mivi_status_t s = target_behind_bijector(c, M, want_grad, c->cur, vin)) return s;
   if (!closed) launch_lowr_woodbury(c, params, M, want_grad != 0);
   launch_lowr_vjp_finish(c, params, M, want_grad, vin, out);
   HIPCHK(c, hipGetLastError());
@@ -53,4 +47,22 @@ mivi_status_t sample_lowrank(mivi_ctx *c, const void *params, uint64_t idx, void
     HIPCHK(c, hipMemcpyAsync(eps, c->lowr_E.p, (size_t)(c->cfg.d + c->cfg.rank) * M * c->esize, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipGetLastError());
   return MIVI_OK;
+}
+
+// logpdf(q, z) (logpdf_launches): t = D^-1 (z - m), then the estimators' own parameter preparation and Woodbury stage on t
+mivi_status_t logpdf_lowrank(mivi_ctx *c, const void *params, const char *Z, int n, char *logq, char *, const LogpdfBij *bij) {
+  const size_t d = c->cfg.d, es = c->esize;
+  const int cap = n < kSampleChunk ? n : kSampleChunk;
+  const size_t r = c->cfg.rank, t_bytes = (d * cap * es + 15) / 16 * 16;
+  mivi_status_t s;
+  if ((s = ensure(c, c->lp_scal, lowr_prep_doubles((int)d, (int)r) * sizeof(double), false)) ||
+      (s = ensure(c, c->lp_work, t_bytes + (2 * r + 2) * cap * sizeof(double), false)))
+    return s;
+  const LowrPoints pts{c->lp_work.p, (double *)c->lp_scal.p, (double *)((char *)c->lp_work.p + t_bytes), (size_t)cap};
+  launch_lowr_draw_prep(c, rng_of(c, 0), 0, params, pts.prep);   // the parameter half alone: A^-1, sum log D, 1/2 logdet A, the scale flag
+  return logpdf_chunks(c, Z, n, logq, bij, [&](const SampleChunk &k, const char *z, char *lq) {
+    launch_lp_lowr_t(c, params, z, k.Mc, pts.t);
+    launch_lowr_woodbury(c, params, k.Mc, false, &pts);
+    launch_lp_store(c, k.Mc, lowr_logq_of(c, pts), lq);
+  });
 }

@@ -124,6 +124,18 @@ class MvLocationScale:
     def eltype(self):  # Base.eltype, location_scale.jl:49
         return self.location.dtype
 
+    def _flatten(self):   # -> (flat, what the Restructure keeps beside d, family and eltype); location_scale.jl:39-43
+        scale = self.scale if self.scale.ndim == 1 else np.tril(self.scale).reshape(-1, order="F")
+        return np.concatenate([self.location, scale]), {"dist": self.dist}
+
+    @classmethod
+    def _from_flat(cls, re, flat):
+        d = re.d
+        if flat.shape[0] != (2 * d if re.family == MEANFIELD else d + d * d):
+            raise ValueError("flat parameter vector has the wrong length")
+        scale = flat[d:].copy() if re.family == MEANFIELD else np.tril(flat[d:].reshape(d, d, order="F"))
+        return cls(flat[:d].copy(), scale, re.dist)
+
     # host statistics (numpy): location_scale.jl:52-57, 98-113
     def _dense_scale(self):
         return np.diag(self.scale) if self.scale.ndim == 1 else self.scale
@@ -193,6 +205,16 @@ class MvLocationScaleLowRank:
     def eltype(self):  # Base.eltype, location_scale_low_rank.jl:45
         return self.location.dtype
 
+    def _flatten(self):   # the functor's field order, location_scale_low_rank.jl:41
+        return np.concatenate([self.location, self.scale_diag, self.scale_factors.reshape(-1, order="F")]), {"rank": self.rank}
+
+    @classmethod
+    def _from_flat(cls, re, flat):
+        d = re.d
+        if flat.shape[0] != 2 * d + d * re.rank:
+            raise ValueError("flat parameter vector has the wrong length")
+        return cls(flat[:d].copy(), flat[d:2 * d].copy(), flat[2 * d:].reshape(d, re.rank, order="F").copy())
+
     # host statistics with the base distribution Normal(0, 1): location_scale_low_rank.jl:102-121
     def entropy(self):   # location_scale_low_rank.jl:35-43: d H(Normal) + (2 sum log D + logdet(I + U' D^-2 U)) / 2
         D, U = self.scale_diag, self.scale_factors
@@ -255,6 +277,16 @@ class BlockDiagGaussian:
     @property
     def eltype(self):
         return self.location.dtype
+
+    def _flatten(self):
+        return np.concatenate([self.location] + [B.reshape(-1, order="F") for B in self.blocks]), {"block": self.block}
+
+    @classmethod
+    def _from_flat(cls, re, flat):
+        layout, n = blockdiag_layout(re.d, re.block)
+        if flat.shape[0] != n:
+            raise ValueError("flat parameter vector has the wrong length")
+        return cls(flat[:re.d].copy(), [flat[off:off + bk * bk].reshape(bk, bk, order="F") for _, bk, off in layout])
 
     def dense_scale(self):
         """the d x d lower-triangular scale with the blocks on its diagonal"""
@@ -332,6 +364,18 @@ class RealNVPFlow:
     def eltype(self):
         return self.params.dtype
 
+    @property
+    def arch(self):
+        """the `flow` argument of MiviContext and of Restructure"""
+        return (self.hidden_dims, self.n_layers)
+
+    def _flatten(self):   # the flow's own flat vector (flow_layout)
+        return self.params.copy(), {"flow": self.arch}
+
+    @classmethod
+    def _from_flat(cls, re, flat):
+        return cls(re.d, re.flow[0], re.flow[1], flat.copy())
+
     def blocks(self):
         """{(l, net, j, "W" | "b"): array view} of the parameter vector (W as an out x in matrix)."""
         return {(l, net, j, k): self.params[off:off + int(np.prod(shape))].reshape(shape, order="F")
@@ -405,6 +449,18 @@ class SplineFlow:
     def eltype(self):
         return self.params.dtype
 
+    @property
+    def arch(self):
+        """the `flow` argument of MiviContext and of Restructure"""
+        return (self.hidden_dims, self.n_layers, self.n_bins, self.bound)
+
+    def _flatten(self):   # the flow's own flat vector (nsf_layout)
+        return self.params.copy(), {"flow": self.arch}
+
+    @classmethod
+    def _from_flat(cls, re, flat):
+        return cls(re.d, *re.flow, flat.copy())
+
     def blocks(self):
         """{(l, j, "W" | "b"): array view} of the parameter vector (W as an out x in matrix)."""
         return {(l, j, k): self.params[off:off + int(np.prod(shape))].reshape(shape, order="F")
@@ -425,13 +481,9 @@ def NeuralSplineFlow(d, hidden_dims, n_bins, bound, n_layers, eltype=np.float64,
 
 
 COUPLING_FLOWS = (RealNVPFlow, SplineFlow)
-
-
-def flow_arch(q):
-    """the `flow` argument of MiviContext for q (None unless q is a coupling flow)"""
-    if isinstance(q, SplineFlow):
-        return (q.hidden_dims, q.n_layers, q.n_bins, q.bound)
-    return (q.hidden_dims, q.n_layers) if isinstance(q, RealNVPFlow) else None
+# family code -> the class that flattens it (_flatten) and is rebuilt from a flat vector (_from_flat)
+FAMILY_CLASSES = {MEANFIELD: MvLocationScale, FULLRANK: MvLocationScale, LOWRANK: MvLocationScaleLowRank, REALNVP: RealNVPFlow, NSF: SplineFlow,
+                  BLOCKDIAG: BlockDiagGaussian}
 
 
 class Restructure:
@@ -444,28 +496,7 @@ class Restructure:
         self.flow = flow   # REALNVP: (hidden_dims, n_layers); NSF: (hidden_dims, n_layers, n_bins, bound)
 
     def __call__(self, flat):
-        flat = np.asarray(flat, dtype=self.dtype)
-        d = self.d
-        if self.family == REALNVP:
-            return RealNVPFlow(d, self.flow[0], self.flow[1], flat.copy())
-        if self.family == NSF:
-            return SplineFlow(d, *self.flow, flat.copy())
-        if self.family == BLOCKDIAG:
-            layout, n = blockdiag_layout(d, self.block)
-            if flat.shape[0] != n:
-                raise ValueError("flat parameter vector has the wrong length")
-            return BlockDiagGaussian(flat[:d].copy(), [flat[off:off + bk * bk].reshape(bk, bk, order="F") for _, bk, off in layout])
-        if self.family == LOWRANK:
-            if flat.shape[0] != 2 * d + d * self.rank:
-                raise ValueError("flat parameter vector has the wrong length")
-            return MvLocationScaleLowRank(flat[:d].copy(), flat[d:2 * d].copy(), flat[2 * d:].reshape(d, self.rank, order="F").copy())
-        if self.family == MEANFIELD:
-            if flat.shape[0] != 2 * d:
-                raise ValueError("flat parameter vector has the wrong length")
-            return MvLocationScale(flat[:d].copy(), flat[d:].copy(), self.dist)
-        if flat.shape[0] != d + d * d:
-            raise ValueError("flat parameter vector has the wrong length")
-        return MvLocationScale(flat[:d].copy(), np.tril(flat[d:].reshape(d, d, order="F")), self.dist)
+        return FAMILY_CLASSES[self.family]._from_flat(self, np.asarray(flat, dtype=self.dtype))
 
 
 def destructure(q):
@@ -476,19 +507,5 @@ def destructure(q):
                 src/families/location_scale_low_rank.jl:41).
     block-diag: [location; vec(C_0); vec(C_1); ...] column-major per block, length d + sum b_k^2 (blockdiag_layout)
     RealNVP   : the nets' weights and biases, layer by layer (flow_layout); NeuralSplineFlow likewise (nsf_layout)."""
-    d = len(q)
-    if q.family == REALNVP:   # the flow's own flat vector (flow_layout)
-        return q.params.copy(), Restructure(d, REALNVP, q.eltype, flow=(q.hidden_dims, q.n_layers))
-    if q.family == NSF:
-        return q.params.copy(), Restructure(d, NSF, q.eltype, flow=flow_arch(q))
-    if q.family == BLOCKDIAG:
-        flat = np.concatenate([q.location] + [B.reshape(-1, order="F") for B in q.blocks])
-        return flat.astype(q.eltype, copy=False), Restructure(d, BLOCKDIAG, q.eltype, block=q.block)
-    if q.family == LOWRANK:
-        flat = np.concatenate([q.location, q.scale_diag, q.scale_factors.reshape(-1, order="F")])
-        return flat.astype(q.eltype, copy=False), Restructure(d, LOWRANK, q.eltype, q.rank)
-    if q.family == MEANFIELD:
-        flat = np.concatenate([q.location, q.scale])
-    else:
-        flat = np.concatenate([q.location, np.tril(q.scale).reshape(-1, order="F")])
-    return flat.astype(q.eltype, copy=False), Restructure(d, q.family, q.eltype, dist=q.dist)
+    flat, kept = q._flatten()
+    return flat.astype(q.eltype, copy=False), Restructure(len(q), q.family, q.eltype, **kept)

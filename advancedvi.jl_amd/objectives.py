@@ -18,7 +18,7 @@ import numpy as np
 
 from . import problems as P
 from .context import MiviContext
-from .families import COUPLING_FLOWS, FLOW_NAMES, BlockDiagGaussian, MvLocationScale, MvLocationScaleLowRank, destructure, flow_arch as _flow_arch
+from .families import COUPLING_FLOWS, FLOW_NAMES, BlockDiagGaussian, MvLocationScale, MvLocationScaleLowRank, destructure
 
 
 _log = logging.getLogger("advancedvi_jl_amd")
@@ -188,8 +188,7 @@ def _make_ctx(rng, obj, adtype, q, prob, n_mc=None, entropy=None):
     if isinstance(q, COUPLING_FLOWS) and ent.code not in (MonteCarloEntropy.code, StickingTheLandingEntropy.code):
         raise TypeError(_NO_FLOW_ENTROPY.format(FLOW_NAMES[q.family], f"`{type(ent).__name__}`"))
     device = getattr(adtype, "device", 0)
-    ctx = MiviContext(q.eltype, q.family, len(q), n_mc or obj.n_samples,
-                      ent.code, rng.seed, device=device, rank=getattr(q, "rank", 0), flow=_flow_arch(q), block=getattr(q, "block", 0))
+    ctx = MiviContext.for_family(q, n_mc or obj.n_samples, ent.code, rng.seed, device=device)
     try:
         ctx.set_base_dist(getattr(q, "dist", None))   # MvLocationScale(location, scale, dist); the low-rank family: Normal() only
         ctx.set_problem(prob)
@@ -318,8 +317,7 @@ def rand(rng, q, num_samples: int, device: int = 0):
     """rand(rng, q, num_samples): d x num_samples samples (location_scale.jl:71-87, location_scale_low_rank.jl:66-100), returned as a
     device tensor (column m = sample m).  q::TransformedDistribution: the draws of q.q pushed through the bijector (constrained)."""
     qt, q = (q, q.q) if isinstance(q, TransformedDistribution) else (None, q)
-    ctx = MiviContext(q.eltype, q.family, len(q), num_samples, _plain_entropy(q), rng.seed, device=device, rank=getattr(q, "rank", 0),
-                      flow=_flow_arch(q), block=getattr(q, "block", 0))
+    ctx = MiviContext.for_family(q, num_samples, _plain_entropy(q), rng.seed, device=device)
     try:
         ctx.set_base_dist(getattr(q, "dist", None))
         params, _ = destructure(q)
@@ -337,8 +335,7 @@ def logpdf(q, z, device: int = 0):
     z of shape (d,): a Python float.  z of shape (d, n), numpy or device tensor: a device tensor of n values in q.eltype.
     q::TransformedDistribution: z are constrained points, the value is log q.q(b(z)) - logabsdetjac(binv, b(z)); -inf outside the support."""
     qt, q = (q, q.q) if isinstance(q, TransformedDistribution) else (None, q)
-    ctx = MiviContext(q.eltype, q.family, len(q), 1, _plain_entropy(q), 0, device=device, rank=getattr(q, "rank", 0), flow=_flow_arch(q),
-                      block=getattr(q, "block", 0))
+    ctx = MiviContext.for_family(q, 1, _plain_entropy(q), 0, device=device)
     try:
         ctx.set_base_dist(getattr(q, "dist", None))
         params, _ = destructure(q)

@@ -218,6 +218,39 @@ def test_environment_switches_have_one_table():
         assert not [n for n in retired if n in txt], path
 
 
+def test_family_dispatch_has_one_table():
+    """The families that run their own kernels are rows of ONE table (csrc/api_common.h: kFamilies behind family_row, refuse).  With
+    comments stripped, a family code is named only there, in the family's own api_*.hip unit and in kernels_update.hip (device code with
+    the family baked into its launches); the guards and predicates the table replaced are named nowhere; and the capability matrix of
+    DESIGN.md ("The family table") names the families of the table's rows."""
+    csrc = os.path.join(ROOT, "advancedvi.jl_amd", "csrc")
+    raw = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    code = {f: re.sub(r"//[^\n]*|/\*.*?\*/", "", txt, flags=re.S) for f, txt in raw.items()}
+    may_name = {"MIVI_LOWRANK": {"api_lowrank.hip"}, "MIVI_REALNVP": {"api_flow.hip"}, "MIVI_NSF": {"api_flow.hip"}, "MIVI_BLOCKDIAG": {"api_blockdiag.hip"}}
+    for name, own in may_name.items():
+        named_in = {f for f, txt in code.items() if re.search(rf"\b{name}\b", txt)}
+        assert "api_common.h" in named_in and named_in <= own | {"api_common.h", "kernels_update.hip"}, (name, sorted(named_in))
+    for gone in ("refuse_lowrank", "refuse_flow", "refuse_blockdiag", "is_flow", "flow_family_name"):
+        assert not [f for f, txt in raw.items() if re.search(rf"\b{gone}\b", txt)], gone
+    table = re.search(r"inline const FamilyRow kFamilies\[\] = \{\n(.*?)\n\};", code["api_common.h"], flags=re.S).group(1)
+    rows = re.findall(r'\{(MIVI_\w+), "([^"]+ family \((MIVI_\w+)\))", ', table)
+    assert len(rows) == table.count('{MIVI_') == 4 and all(fam == in_name for fam, _, in_name in rows), table
+    assert {fam for fam, _, _ in rows} == set(may_name)
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = re.search(r"### The family table.*?(?=\n## )", design, flags=re.S).group(0)
+    assert set(re.findall(r"`([^`]+ family \(MIVI_\w+\))`", section)) == {name for _, name, _ in rows}
+    header = re.search(r"\| group \(`FamilyLacks`\) \|([^\n]*)\|\n", section).group(1)
+    assert [c.strip() for c in header.split("|")] == ["mean-field / full-rank", "low-rank", "RealNVP / NSF", "block-diagonal"]
+    lacks = dict(re.findall(r"\{(MIVI_\w+), \"[^\"]+\", [^,]+, ([^\n]+?),?\n", table))
+    lacks = {fam: code["api_common.h"].split("constexpr unsigned kFlowLacks = ")[1].split(";")[0] if expr == "kFlowLacks" else expr for fam, expr in lacks.items()}
+    assert lacks["MIVI_REALNVP"] == lacks["MIVI_NSF"]
+    matrix = re.findall(r"\| `(LACKS_\w+)`[^|]*\| – \| ([R–]) \| ([R–]) \| ([R–]) \|", section)
+    assert len(matrix) == 7 == len(re.findall(r"\bLACKS_\w+ = 1u << \d", code["api_common.h"]))
+    for group, *cells in matrix:   # the matrix IS the rows' bit sets
+        for fam, cell in zip(("MIVI_LOWRANK", "MIVI_REALNVP", "MIVI_BLOCKDIAG"), cells):
+            assert (group in re.findall(r"LACKS_\w+", lacks[fam])) == (cell == "R"), (group, fam)
+
+
 def test_stream_and_event_handles_have_one_owner():
     """Streams and events are created and destroyed in ONE translation unit (csrc/api_core.hip: make_stream, make_event, handle_destroy),
     a hipGraphExec is destroyed in the graph unit only; every other unit holds them in a Stream / Event / GraphExec (csrc/mivi_internal.h).
