@@ -63,6 +63,9 @@ SIGNATURES = {
     "mivi_set_target_diag_gauss": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mivi_set_target_dense_gauss": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mivi_set_target_logreg": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int32]),
+    "mivi_set_target_softmax": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
+    "mivi_softmax_select_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
+    "mivi_softmax_set_plane_cap": (C.c_int32, [C.c_void_p, C.c_int64]),
     "mivi_set_target_funnel": (C.c_int32, [C.c_void_p, C.c_double]),
     "mivi_set_target_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_AND_GRADIENT_FN, LOGDENSITY_FN, C.c_void_p]),
     "mivi_set_target_value_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_FN, C.c_void_p]),

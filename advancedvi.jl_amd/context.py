@@ -147,7 +147,30 @@ class MiviContext:
         self.set_bijector(None)
         if not isinstance(prob, (P.LogRegProblem, P.LogRegSubset)):
             self._lr_full = None   # another target kind replaces the resident data set
-        if isinstance(prob, P.DiagNormalProblem):
+        if not isinstance(prob, (P.SoftmaxRegProblem, P.SoftmaxRegSubset)):
+            self._sm_full = None
+        if isinstance(prob, P.SoftmaxRegProblem) and getattr(self, "_sm_full", None) is prob:
+            self._chk(self.lib.mivi_softmax_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
+        elif isinstance(prob, P.SoftmaxRegProblem):
+            if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor of the context's dtype, y uint8
+                if prob.X.dtype != self.tdtype or not prob.X.is_contiguous() or prob.y.dtype != _torch().uint8:
+                    raise TypeError("SoftmaxRegProblem on the device: X is a contiguous (p, n) tensor of the context's dtype, y a uint8 tensor")
+                self._keep += [prob.X, prob.y]
+                self._chk(self.lib.mivi_set_target_softmax(self.h, self._p(prob.X), self._p(prob.y), prob.n, prob.n_classes,
+                                                           P.SoftmaxRegProblem.VARIANTS[prob.variant], prob.likeadj, 1))
+            else:
+                Xf = np.asfortranarray(prob.X, dtype=dt)
+                y = np.ascontiguousarray(prob.y, dtype=np.uint8)
+                if y.size and int(np.max(np.asarray(prob.y))) > 255:
+                    raise ValueError("SoftmaxRegProblem: labels are bytes in {0, ..., n_classes - 1}")
+                self._chk(self.lib.mivi_set_target_softmax(self.h, Xf.ctypes.data, y.ctypes.data, Xf.shape[0], prob.n_classes,
+                                                           P.SoftmaxRegProblem.VARIANTS[prob.variant], prob.likeadj, 0))
+            self._sm_full = prob
+        elif isinstance(prob, P.SoftmaxRegSubset):
+            if getattr(self, "_sm_full", None) is not prob.parent:   # upload the full data set once, then only select rows
+                self.set_problem(prob.parent)
+            self._chk(self.lib.mivi_softmax_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
+        elif isinstance(prob, P.DiagNormalProblem):
             m = np.ascontiguousarray(prob.mean, dtype=dt)
             s = np.ascontiguousarray(np.broadcast_to(prob.std, m.shape), dtype=dt)
             self._chk(self.lib.mivi_set_target_diag_gauss(self.h, m.ctypes.data, s.ctypes.data))
@@ -633,6 +656,11 @@ class MiviContext:
     def set_logreg_route(self, route):
         """0 = by problem size, 1 = matrix-core kernels, 2 = VALU kernels (built-in logistic regression, f32)."""
         self._chk(self.lib.mivi_set_logreg_route(self.h, int(route)))
+
+    def softmax_set_plane_cap(self, nbytes):
+        """Internal (tests): the byte cap of the softmax regression target's residual plane, which decides how many samples one chunk
+        of its launches takes; 0 restores the default.  Results do not depend on it (mivi_softmax_set_plane_cap)."""
+        self._chk(self.lib.mivi_softmax_set_plane_cap(self.h, int(nbytes)))
 
     def set_index_source(self, idx_tensor):
         """idx_tensor: 1-element int64/uint64 device tensor added to every estimate index (None to unset)."""

@@ -19,6 +19,9 @@ mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
     case TGT_LOGREG:
       if (!launch_logreg_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "logistic regression: scratch allocation failed");
       return MIVI_OK;
+    case TGT_SOFTMAX:
+      if (!launch_sm_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "softmax regression: scratch allocation failed");
+      return MIVI_OK;
     case TGT_CALLBACK: {
       if (want_grad && !c->cb_grad) return fail(c, MIVI_ERR_UNSUPPORTED, kValueOnlyTarget);
       const size_t es = c->esize, d = c->cfg.d;

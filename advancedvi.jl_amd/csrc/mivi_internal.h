@@ -32,7 +32,8 @@ enum TargetKind : int {
   TGT_DENSE_GAUSS = 2,
   TGT_LOGREG = 3,
   TGT_FUNNEL = 4,
-  TGT_CALLBACK = 5
+  TGT_CALLBACK = 5,
+  TGT_SOFTMAX = 6     // softmax (multinomial logistic) regression: kernels_softmax.hip, a generic target like the callback's
 };
 
 // What the Stacked bijector does to one coordinate (kernels_bijector.hip).  The legacy mask of mivi_set_bijector_stacked holds 0 / 1:
@@ -517,6 +518,18 @@ struct mivi_ctx : mivi_ctx_streams {
   int lr_sched_kernels = 0;                // 0 by size | 1 the fused minibatch kernel | 2 device gather + the resident-data kernels
   bool lr_sched_has_idx = false;
   int lr_loop_first = -1;                  // >= 0 while mivi_optimize_loop_batches runs: step t of the loop evaluates batch lr_loop_first + t
+  // softmax regression (api_softmax.hip, kernels_softmax.hip): theta = [vec B (p x C); s].  The data set stays resident; a row selection
+  // (mivi_softmax_select_rows) is the index vector sm_idx, which the kernels read the rows THROUGH -- no gathered copy of X.
+  // sm_R: the residual plane Y - P of one chunk of samples; sm_part: the f64 partials of X'R per row slice; sm_ell: those of the
+  // log-likelihood per (row tile, sample).  sm_cap: the byte cap of sm_R (0: kSmPlaneCap; mivi_softmax_set_plane_cap)
+  const void *sm_X = nullptr;
+  const uint8_t *sm_y = nullptr;
+  mivi::DevBuf sm_X_own, sm_y_own, sm_idx, sm_R, sm_part, sm_ell;
+  int64_t sm_n = 0, sm_nr = 0;             // rows of the data set; rows of the selection (= sm_n without one)
+  bool sm_sel = false;                     // a row selection is in force
+  int sm_C = 0, sm_variant = 0;
+  double sm_likeadj = 1.0, sm_likeadj_full = 1.0;
+  size_t sm_cap = 0;
   // callback
   mivi_logdensity_and_gradient_fn cb_grad = nullptr;
   mivi_logdensity_fn cb_value = nullptr;
@@ -793,6 +806,13 @@ int logreg_kernel_bits(const mivi_ctx *c, int M);         // mivi_logreg_kernels
 bool logreg_uses_mfma(const mivi_ctx *c, int M);          // the matrix-core route (needs Z^T staged in RT)
 bool logreg_reserve(mivi_ctx *c, int M);                        // size the scratch ahead of a graph capture
 bool logreg_prepare_f32(mivi_ctx *c);   // row-major padded copy of X for the MFMA route (false: allocation failed)
+
+// kernels_softmax.hip: the softmax regression target (api_softmax.hip sets it; eval_generic_target evaluates it)
+constexpr size_t kSmPlaneCap = 64u << 20;          // bytes of the residual plane a chunk of samples may take (at least one sample per chunk)
+constexpr size_t kSmPartCap = 128u << 20;          // ... and of the f64 partials of X'R
+int sm_chunk_samples(const mivi_ctx *c, int M);    // samples per chunk under the two caps
+bool sm_reserve(mivi_ctx *c, int M);               // size sm_R / sm_part / sm_ell for M samples per estimate (ahead of a graph capture)
+bool launch_sm_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation failed
 
 // kernels_score.hip: the score-gradient (VarGrad) estimator's own kernels (api_score.hip drives them)
 void launch_sg_dense_ell(mivi_ctx *c, int M);                          // sg_d[cap + m] = 0.5 r_m' g_m from Z and W = G = -P R (dense-Gaussian target)

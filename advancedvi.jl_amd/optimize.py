@@ -344,6 +344,19 @@ def _scheduled_logreg(obj, prob):
             isinstance(obj.subsampling, S.ReshufflingBatchSubsampling) and type(inner) is P.LogRegProblem)
 
 
+NO_SCHEDULE_SOFTMAX = ("SoftmaxRegProblem: the scheduled minibatch device loop (mivi_logreg_set_batch_schedule / mivi_optimize_loop_batches) is "
+                       "built for the logistic regression only; subsampled steps take the host-driven loop with mivi_softmax_select_rows per step")
+
+
+def subsampled_route_note(obj, prob):
+    """Why a SubsampledObjective over `prob` does not take the scheduled device loop, by name -- None where it does, or where nothing is subsampled."""
+    from . import problems as P
+    inner = prob.prob if isinstance(prob, P.TransformedProblem) else prob
+    if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.SoftmaxRegProblem, P.SoftmaxRegSubset)):
+        return NO_SCHEDULE_SOFTMAX
+    return None
+
+
 def _device_loop_codes(alg, callback, objargs, prob=None):
     """(rule, op, averager) when a whole `step` can run inside mivi_optimize_loop, else None: no callback (it needs the
     parameters on the host every iteration), a plain RepGradELBO -- or a SubsampledObjective around one over the built-in
@@ -477,6 +490,9 @@ def optimize(rng, algorithm, max_iter: int, prob=None, q_init=None, *objargs, sh
     codes = _device_loop_codes(algorithm, callback, objargs, state.get("prob")) if device_loop else None
     if isinstance(algorithm.objective, S.SubsampledObjective) and _ctx_of(state["obj_st"]).family in FLOW_FAMILIES:
         codes = None   # the batch schedule has no form for a flow: subsampled steps keep the host loop (mivi_logreg_select_rows per step)
+    note = subsampled_route_note(algorithm.objective, state.get("prob"))
+    if note is not None:   # (codes is None: _scheduled_logreg takes the logistic regression alone)
+        state = dict(state, route_note=note)
     if codes is not None and max_iter > 0:
         state = dict(state)
         info_dev = _optimize_on_device(rng, algorithm, max_iter, state, codes, show_progress)

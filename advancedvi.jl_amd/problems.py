@@ -148,6 +148,61 @@ class LogRegSubset:
         return LogRegSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
+class SoftmaxRegProblem:
+    """Softmax (multinomial logistic) regression over theta = [vec B (p x n_classes, column-major); s], d = p n_classes + 1:
+    B[k, c] ~ Normal(0, sigma^2), sigma = exp(s), y_r ~ Categorical(softmax(X[r] B)); the prior on sigma, the Jacobian term and
+    likeadj are those of LogRegProblem's variants (mivi_set_target_softmax).  X is n x p, y in {0, ..., n_classes - 1}."""
+
+    VARIANTS = LogRegProblem.VARIANTS
+    MAX_CLASSES = 64
+
+    def __init__(self, X, y, n_classes, variant="logsigma_normal", likeadj=1.0):
+        # device-resident data: a contiguous (p, n) tensor -- n x p column-major, as the kernels read it -- and a uint8 tensor of labels
+        self.on_device = hasattr(X, "data_ptr")
+        self.X = X if self.on_device else np.asarray(X)
+        self.y = y if self.on_device else np.asarray(y)
+        self.p, self.n = (int(X.shape[0]), int(X.shape[1])) if self.on_device else (self.X.shape[1], self.X.shape[0])
+        self.n_classes = int(n_classes)
+        if variant not in self.VARIANTS:
+            raise ValueError(f"unknown variant {variant}")
+        self.variant = variant
+        self.likeadj = float(likeadj)
+
+    def dimension(self):
+        return self.p * self.n_classes + 1
+
+    def capabilities(self):
+        return LogDensityOrder(1)
+
+    def n_rows(self):
+        return self.n
+
+    def subsample(self, batch):
+        """AdvancedVI.subsample(prob, batch): the rows `batch` (0-based) with the likelihood scaled by n_data / n.  The data stay on
+        the device and the kernels read the rows through the index vector; see mivi_softmax_select_rows."""
+        return SoftmaxRegSubset(self, batch)
+
+
+class SoftmaxRegSubset:
+    """A minibatch view of a SoftmaxRegProblem (what `subsample` returns); never copies X."""
+
+    def __init__(self, parent: SoftmaxRegProblem, batch):
+        self.parent = parent
+        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
+        if self.batch.size == 0:
+            raise ValueError("empty batch")
+        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
+
+    def dimension(self):
+        return self.parent.dimension()
+
+    def capabilities(self):
+        return self.parent.capabilities()
+
+    def subsample(self, batch):
+        return SoftmaxRegSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
+
+
 def subsample(model, batch):
     """AdvancedVI.subsample(model, batch): models that do not specialise it are returned unchanged
     (src/AdvancedVI.jl:313; the tutorial's warning at docs/src/tutorials/subsampling.md:106-110)."""
@@ -248,4 +303,5 @@ class TransformedProblem:
         return TransformedProblem(subsample(self.prob, batch), self.bijector)
 
 
-BUILTIN = (DiagNormalProblem, DenseNormalProblem, LogRegProblem, LogRegSubset, FunnelProblem, FunnelConstrainedProblem)
+BUILTIN = (DiagNormalProblem, DenseNormalProblem, LogRegProblem, LogRegSubset, FunnelProblem, FunnelConstrainedProblem, SoftmaxRegProblem,
+           SoftmaxRegSubset)

@@ -297,6 +297,31 @@ mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *ctx, const mivi_batch_s
  * selection: no device work, no synchronisation; captured graphs are invalidated as by mivi_logreg_select_rows. */
 mivi_status_t mivi_logreg_seek_batch(mivi_ctx_t *ctx, int32_t k);
 
+/* Softmax (multinomial logistic) regression over theta = [vec B (p x C, column-major: B[k + p c]); s], d = p C + 1, sigma = e^s:
+ *   Lambda = X B (n x C),  loglike = sum_r (Lambda[r, y_r] - logsumexp_c Lambda[r, c]),  B[k, c] ~ Normal(0, sigma^2) i.i.d.,
+ *   log pi = likeadj loglike - pC/2 log 2 pi - pC s - |B|_F^2 / (2 sigma^2) + logprior_sigma(s) + jac(s)
+ * with logprior_sigma, jac, the integer codes of `variant` and the meaning of `likeadj` those of mivi_set_target_logreg.
+ * X: n x p COLUMN-major T (X[r + k*n]), y: n bytes in {0, ..., n_classes - 1}; x_on_device != 0 => X, y are device ptrs (borrowed, must
+ * outlive the ctx; the labels are then NOT checked), otherwise host ptrs, copied.  The target runs on the device on kernels of its own
+ * (Lambda and X'(Y - P) on the matrix cores in the element type, the softmax, every sum and the prior in f64) and is served by every
+ * entry that serves a callback target by explicit samples -- all families, entropy estimators, bijectors and bases, the score-gradient
+ * and Stein (order-1) entries, mivi_estimate_objective -- without a host round trip, and by the graph-recorded routes
+ * (mivi_estimate_gradient_n, mivi_optimize_steps / _loop as the graph of launches).  MIVI_ERR_UNSUPPORTED with a message naming the entry
+ * and "softmax regression target": mivi_optimize_loop_many, the batch schedule entries, mivi_gauss_expected_grad_hess2*, the mivi_logreg_*
+ * entries.  MIVI_ERR_BAD_ARG with a message: n < 1, n_classes outside [2, MIVI_SOFTMAX_MAX_CLASSES], d - 1 not a positive multiple of
+ * n_classes, a label >= n_classes (host data), an unknown variant, likeadj <= 0; the target that was set stays. */
+#define MIVI_SOFTMAX_MAX_CLASSES 64
+mivi_status_t mivi_set_target_softmax(mivi_ctx_t *ctx, const void *X, const uint8_t *y, int64_t n, int32_t n_classes,
+                                      int32_t variant, double likeadj, int32_t x_on_device);
+/* AdvancedVI.subsample for the softmax regression, the contract of mivi_logreg_select_rows: the target becomes the rows idx_host[0..b)
+ * (0-based, repeats allowed) of the resident data set with the likelihood scaled by `likeadj`; b = 0 restores the full data set and the
+ * likeadj it was set with.  Every index is checked before anything is uploaded; a failed call leaves the selection unchanged.  The
+ * kernels read the selected rows THROUGH the uploaded index vector: nothing is gathered.  Synchronises the stream. */
+mivi_status_t mivi_softmax_select_rows(mivi_ctx_t *ctx, const int64_t *idx_host, int64_t b, double likeadj);
+/* Internal (tests): the byte cap of the residual plane Y - P, which decides how many samples a chunk of the target's launches takes
+ * (at least one).  0 restores the default (64 MiB).  Results do not depend on it, bit for bit. */
+mivi_status_t mivi_softmax_set_plane_cap(mivi_ctx_t *ctx, int64_t bytes);
+
 /* Neal's funnel on the constrained scale + Stacked([log, identity]) bijector (README.md:76-82,102-106):
  * theta_1 = exp(eta_1) ~ LogNormal(0, sigma_v), theta_i ~ Normal(0, theta_1), log|det J| = eta_1. */
 mivi_status_t mivi_set_target_funnel(mivi_ctx_t *ctx, double sigma_v);
