@@ -31,6 +31,11 @@ class MiviBlockDiag(C.Structure):   # mivi_blockdiag_t: the block size of a MIVI
     _fields_ = [("block", C.c_int32)]
 
 
+class MiviBnn(C.Structure):   # mivi_bnn_t: the network, likelihood and prior of mivi_set_target_bnn
+    _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3), ("likelihood", C.c_int32), ("noise", C.c_double), ("prior_std", C.c_double),
+                ("likeadj", C.c_double)]
+
+
 class MiviSplineFlow(C.Structure):   # mivi_spline_flow_t: the architecture of a MIVI_NSF context (mivi_create_spline_flow)
     _fields_ = [("n_layers", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3), ("n_bins", C.c_int32), ("bound", C.c_double)]
 
@@ -66,6 +71,10 @@ SIGNATURES = {
     "mivi_set_target_softmax": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
     "mivi_softmax_select_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
     "mivi_softmax_set_plane_cap": (C.c_int32, [C.c_void_p, C.c_int64]),
+    "mivi_set_target_bnn": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "mivi_bnn_select_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
+    "mivi_bnn_forward": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mivi_bnn_set_part_cap": (C.c_int32, [C.c_void_p, C.c_int64]),
     "mivi_set_target_funnel": (C.c_int32, [C.c_void_p, C.c_double]),
     "mivi_set_target_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_AND_GRADIENT_FN, LOGDENSITY_FN, C.c_void_p]),
     "mivi_set_target_value_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_FN, C.c_void_p]),

@@ -149,6 +149,8 @@ class MiviContext:
             self._lr_full = None   # another target kind replaces the resident data set
         if not isinstance(prob, (P.SoftmaxRegProblem, P.SoftmaxRegSubset)):
             self._sm_full = None
+        if not isinstance(prob, (P.BNNProblem, P.BNNSubset)):
+            self._bnn_full = None
         if isinstance(prob, P.SoftmaxRegProblem) and getattr(self, "_sm_full", None) is prob:
             self._chk(self.lib.mivi_softmax_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
         elif isinstance(prob, P.SoftmaxRegProblem):
@@ -170,6 +172,27 @@ class MiviContext:
             if getattr(self, "_sm_full", None) is not prob.parent:   # upload the full data set once, then only select rows
                 self.set_problem(prob.parent)
             self._chk(self.lib.mivi_softmax_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
+        elif isinstance(prob, P.BNNProblem) and getattr(self, "_bnn_full", None) is prob:
+            self._chk(self.lib.mivi_bnn_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
+        elif isinstance(prob, P.BNNProblem):
+            hidden = list(prob.hidden_dims)
+            if not 1 <= len(hidden) <= 3:
+                raise ValueError("BNNProblem: one to three hidden layers")
+            net = _lib.MiviBnn(len(hidden), (C.c_int32 * 3)(*(hidden + [0] * (3 - len(hidden)))), P.BNNProblem.LIKELIHOODS[prob.likelihood],
+                               prob.noise, prob.prior_std, prob.likeadj)
+            if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor, y a tensor of n entries, both of the context's dtype
+                if prob.X.dtype != self.tdtype or not prob.X.is_contiguous() or prob.y.dtype != self.tdtype or not prob.y.is_contiguous():
+                    raise TypeError("BNNProblem on the device: X is a contiguous (p, n) tensor and y a contiguous tensor of the context's dtype")
+                self._keep += [prob.X, prob.y]
+                self._chk(self.lib.mivi_set_target_bnn(self.h, C.byref(net), self._p(prob.X), self._p(prob.y), prob.n, prob.p, 1))
+            else:
+                Xf, y = np.asfortranarray(prob.X, dtype=dt), np.ascontiguousarray(prob.y, dtype=dt)
+                self._chk(self.lib.mivi_set_target_bnn(self.h, C.byref(net), Xf.ctypes.data, y.ctypes.data, Xf.shape[0], prob.p, 0))
+            self._bnn_full = prob
+        elif isinstance(prob, P.BNNSubset):
+            if getattr(self, "_bnn_full", None) is not prob.parent:   # upload the full data set once, then only select rows
+                self.set_problem(prob.parent)
+            self._chk(self.lib.mivi_bnn_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
         elif isinstance(prob, P.DiagNormalProblem):
             m = np.ascontiguousarray(prob.mean, dtype=dt)
             s = np.ascontiguousarray(np.broadcast_to(prob.std, m.shape), dtype=dt)
@@ -661,6 +684,27 @@ class MiviContext:
         """Internal (tests): the byte cap of the softmax regression target's residual plane, which decides how many samples one chunk
         of its launches takes; 0 restores the default.  Results do not depend on it (mivi_softmax_set_plane_cap)."""
         self._chk(self.lib.mivi_softmax_set_plane_cap(self.h, int(nbytes)))
+
+    def bnn_set_part_cap(self, nbytes):
+        """Internal (tests): the byte cap of the Bayesian neural network target's f64 partial planes, which decides how many samples one
+        chunk of its launches takes; 0 restores the default.  Results do not depend on it (mivi_bnn_set_part_cap)."""
+        self._chk(self.lib.mivi_bnn_set_part_cap(self.h, int(nbytes)))
+
+    def bnn_forward(self, theta, Xnew):
+        """mivi_bnn_forward: f (M, n_new) of the M networks in theta (d x M: a (d, M) array or tensor) on the rows of Xnew (n_new x p), with
+        the architecture of the BNNProblem that is set."""
+        torch = _torch()
+        th = (theta if isinstance(theta, torch.Tensor) else torch.as_tensor(np.asarray(theta))).reshape(self.d, -1)
+        th = th.to(device=self.tdevice, dtype=self.tdtype).t().contiguous()            # (M, d): d x M column-major
+        Xn = torch.as_tensor(np.asarray(Xnew)) if not isinstance(Xnew, torch.Tensor) else Xnew
+        Xn = Xn.to(device=self.tdevice, dtype=self.tdtype).t().contiguous()            # (p, n_new): n_new x p column-major
+        if getattr(self, "_bnn_full", None) is None or Xn.dim() != 2 or Xn.shape[0] != self._bnn_full.p:
+            raise ValueError("bnn_forward: a BNNProblem must be set and Xnew be n_new x p with the problem's p")
+        f = torch.empty((th.shape[0], Xn.shape[1]), dtype=self.tdtype, device=self.tdevice)
+        torch.cuda.current_stream(self.tdevice).synchronize()   # (th, Xn and f were made on torch's stream; the kernel runs on the context's)
+        self._chk(self.lib.mivi_bnn_forward(self.h, self._p(th), th.shape[0], self._p(Xn), Xn.shape[1], self._p(f)))
+        self.synchronize()
+        return f
 
     def set_index_source(self, idx_tensor):
         """idx_tensor: 1-element int64/uint64 device tensor added to every estimate index (None to unset)."""

@@ -1,0 +1,95 @@
+// libmivi C ABI, the Bayesian neural network target (include/mivi.h): mivi_set_target_bnn, the row selection mivi_bnn_select_rows
+// (AdvancedVI.subsample), the posterior predictive mivi_bnn_forward and the partial planes' cap.  The target is a GENERIC one:
+// eval_generic_target (api_estimate.hip) evaluates it on explicit samples through launch_bnn_target (kernels_bnn.hip), so every route that
+// serves a callback target by explicit samples serves it, on the device; the entries that cannot are guarded by refuse_bnn (api_common.h).
+#include <cmath>
+
+#include "api_common.h"
+
+static bool bnn_positive(double v) { return std::isfinite(v) && v > 0.0; }
+
+mivi_status_t mivi_set_target_bnn(mivi_ctx_t *c, const mivi_bnn_t *np, const void *X, const void *y, int64_t n, int32_t p, int32_t on_device) {
+  if (!c || !np || !X || !y) return MIVI_ERR_BAD_ARG;
+  const mivi_bnn_t net = *np;
+  if (n < 1) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: n must be at least 1");
+  if (p < 1 || p > MIVI_BNN_MAX_IN) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: p must lie in [1, 64]");
+  if (net.n_hidden < 1 || net.n_hidden > 3) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: n_hidden must lie in [1, 3]");
+  long long d = 0;
+  int prev = p;
+  for (int l = 0; l < net.n_hidden; ++l) {
+    if (net.hidden[l] < 1 || net.hidden[l] > MIVI_BNN_MAX_HIDDEN) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: a hidden width must lie in [1, 64]");
+    d += (long long)net.hidden[l] * (prev + 1);
+    prev = net.hidden[l];
+  }
+  d += prev + 1;
+  if (c->cfg.d != d)
+    return fail(c, MIVI_ERR_BAD_ARG, ("Bayesian neural network: the context's d must be the network's parameter count, " + std::to_string(d)).c_str());
+  if (net.likelihood != 0 && net.likelihood != 1) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: unknown likelihood (0 Bernoulli-logit, 1 Normal)");
+  if (!bnn_positive(net.noise)) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: noise must be positive and finite");
+  if (!bnn_positive(net.prior_std)) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: prior_std must be positive and finite");
+  if (!bnn_positive(net.likeadj)) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: likelihood adjustment must be positive and finite");
+  if (!on_device && net.likelihood == 0)
+    for (int64_t r = 0; r < n; ++r) {
+      const double v = c->cfg.dtype == MIVI_F32 ? (double)((const float *)y)[r] : ((const double *)y)[r];
+      if (v != 0.0 && v != 1.0) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: a Bernoulli label is not 0 or 1");
+    }
+  (void)hipSetDevice(c->cfg.device);
+  invalidate_graph(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // an estimate in flight may still read the previous data set
+  if (on_device) {
+    c->bnn_X = X;
+    c->bnn_y = y;
+  } else {
+    mivi_status_t s;
+    if ((s = upload(c, c->bnn_X_own, X, (size_t)n * p * c->esize)) || (s = upload(c, c->bnn_y_own, y, (size_t)n * c->esize))) return s;
+    c->bnn_X = c->bnn_X_own.p;
+    c->bnn_y = c->bnn_y_own.p;
+  }
+  c->bnn = net;
+  c->bnn_p = p;
+  c->bnn_n = c->bnn_nr = n;
+  c->bnn_sel = false;
+  c->bnn_likeadj = net.likeadj;
+  c->lr_sched_n = c->lr_sched_k = 0;   // (a logistic regression's schedule of batches goes with its target)
+  c->t_const = 0.0;
+  c->target = TGT_BNN;
+  return MIVI_OK;
+}
+
+mivi_status_t mivi_bnn_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t b, double likeadj) {
+  if (!c || b < 0 || (b > 0 && !idx)) return MIVI_ERR_BAD_ARG;
+  if (c->target != TGT_BNN) return fail(c, MIVI_ERR_NO_TARGET, "no Bayesian neural network target set");
+  (void)hipSetDevice(c->cfg.device);
+  if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection in force)
+    if (!bnn_positive(likeadj)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive and finite");
+    for (int64_t j = 0; j < b; ++j)
+      if (idx[j] < 0 || idx[j] >= c->bnn_n) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
+  }
+  invalidate_graph(c);
+  mivi_status_t s = MIVI_OK;
+  if (b > 0) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the previous estimate may still be reading the index vector
+    s = upload(c, c->bnn_idx, idx, (size_t)b * sizeof(int64_t));   // (a grown vector is a new one: on failure the old selection is gone)
+  }
+  c->bnn_sel = b > 0 && s == MIVI_OK;
+  c->bnn_nr = c->bnn_sel ? b : c->bnn_n;
+  c->bnn_likeadj = c->bnn_sel ? likeadj : c->bnn.likeadj;
+  return s;
+}
+
+mivi_status_t mivi_bnn_forward(mivi_ctx_t *c, const void *theta, int32_t M, const void *Xnew, int64_t n_new, void *f) {
+  if (!c || !theta || !Xnew || !f) return MIVI_ERR_BAD_ARG;
+  if (c->target != TGT_BNN) return fail(c, MIVI_ERR_NO_TARGET, "no Bayesian neural network target set");
+  if (M < 1 || n_new < 1) return fail(c, MIVI_ERR_BAD_ARG, "mivi_bnn_forward: M and n_new must be at least 1");
+  (void)hipSetDevice(c->cfg.device);
+  if (!launch_bnn_forward(c, theta, M, Xnew, n_new, f)) return fail(c, MIVI_ERR_HIP, "mivi_bnn_forward: the runtime refused the kernel's LDS size");
+  HIPCHK(c, hipGetLastError());
+  return MIVI_OK;
+}
+
+mivi_status_t mivi_bnn_set_part_cap(mivi_ctx_t *c, int64_t bytes) {
+  if (!c || bytes < 0) return MIVI_ERR_BAD_ARG;
+  invalidate_graph(c);   // (a recorded graph holds the chunks of the cap it was recorded under)
+  c->bnn_cap = (size_t)bytes;
+  return MIVI_OK;
+}

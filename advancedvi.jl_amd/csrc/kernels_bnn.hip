@@ -1,0 +1,433 @@
+// The Bayesian neural network target (include/mivi.h, mivi_set_target_bnn): theta = [vec W_1; b_1; ...; vec W_{H+1}; b_{H+1}] per sample
+// column of Z -- every Monte-Carlo sample is a DIFFERENT network, so the work is M independent small MLP forward and backward passes over
+// the same rows, each returning its own parameter gradient.  api_bnn.hip sets the target; eval_generic_target reaches launch_bnn_target.
+//
+//   k_bnn_rows     grid (sample of the chunk, row slice), 256 threads.  The workgroup stages ITS network into LDS once -- the hidden
+//                  layers' weights as [in][out + 1] planes with every width padded to a multiple of 16 by zero rows and columns, the
+//                  biases, the output row -- and walks its slice of the rows in tiles of 16 (through the row index vector, if a selection
+//                  is set).  A tile's activations are [width][16] blocks (stride 17: both operand orders of a block read 64 banks).
+//                  Every hidden product runs on the 16 x 16 x 4 matrix-core form of the element type (Mfma16): forward W_l (A) times
+//                  a_{l-1} (B), wave w owning output rows 16 w ..; the output row as an A operand whose rows 1 .. 15 are zero; backward
+//                  W_l' (A, the same plane read the other way) times delta_l (B); dW_l += delta_l a_{l-1}' with the tile's 16 rows as
+//                  the K axis, its at most 48 output tiles dealt round-robin to the four waves and kept in registers across the slice.
+//                  f, softplus, the residual and the log-likelihood terms are f64; tanh' comes from the saved a_l.  The f32 accumulators
+//                  are flushed into the slice's f64 partial every kBnnFlush rows; bias and output-row gradients are f64 sums per thread.
+//   k_bnn_finish   one workgroup per sample: the slices in slice order, likeadj, the prior, the Normal likelihood's constants -- all
+//                  f64, rounded once into ell (M) and G (d x M) where eval_generic_target leaves them for the other generic targets.
+//   k_bnn_forward  the same forward sweep on new rows, storing f (mivi_bnn_forward).
+// Nothing is accumulated atomically and no geometry depends on the chunking of the samples: results are bitwise reproducible and the
+// same for every partial cap.
+#include "flow_tile.h"
+
+namespace mivi {
+
+constexpr int kBnnLda = kFlowTile + 1;   // stride of a [width][16] activation block
+constexpr int kBnnFlush = 128;           // rows between two flushes of the f32 dW accumulators into the f64 partial
+constexpr int kBnnWaveTiles = 12;        // dW output tiles per wave: 3 layers x 16 tiles over 4 waves
+constexpr long long kBnnSliceRows = 256; // rows a slice aims at (slices: ceil(rows / 256) clamped to 1 .. 32)
+
+// layer l = 1 .. H + 1 maps n[l - 1] -> n[l]; P: the hidden-side widths padded to 16.  Offsets into theta (woff, boff) and into LDS
+struct BnnNet {
+  int H, d;
+  int n[5], P[4];
+  int woff[4], boff[4];      // theta: W_l, b_l at index l - 1
+  int lw[3], lb[3], lwo;     // LDS: hidden W_l ([P[l-1]][P[l] + 1]), b_l, the output row (P[H])
+  int la[4], ldl[2];         // LDS: a_0 .. a_H, the two delta blocks
+  int toff[4];               // dW tiles of hidden layer l: [toff[l - 1], toff[l])
+  int lds_elems;
+};
+
+template <typename T>
+struct BnnArgs {
+  BnnNet net;
+  int M, m0;                 // samples of this chunk; the chunk's first sample column in Z / ell / G
+  long long n, nr;           // X's leading dimension; rows evaluated
+  const T *X, *y;
+  const long long *rows;     // the row selection (nr entries) or nullptr: rows 0 .. nr - 1
+  const T *Z;                // d x M_total, ld d
+  double *part;              // [n_sl][M][d]
+  double *llp;               // [n_sl][M]
+  int n_sl;
+  long long rps;             // rows per slice, a multiple of 16
+  T *G, *ell;                // d x M_total; M_total
+  T *f;                      // k_bnn_forward: nr x M
+  int likelihood, want_grad;
+  double noise, prior_std, likeadj;
+};
+
+__device__ __forceinline__ float bnn_tanh(float x) { return tanhf(x); }
+__device__ __forceinline__ double bnn_tanh(double x) { return tanh(x); }
+
+template <typename T>
+__device__ __forceinline__ void bnn_stage_net(const BnnNet &nt, const T *th, T *S) {
+  const int tid = threadIdx.x;
+  for (int l = 1; l <= nt.H; ++l) {
+    const int no = nt.n[l], ni = nt.n[l - 1], ldw = nt.P[l] + 1;
+    T *W = S + nt.lw[l - 1], *b = S + nt.lb[l - 1];
+    for (int e = tid; e < nt.P[l - 1] * ldw; e += 256) {
+      const int i = e / ldw, o = e - i * ldw;
+      W[e] = (o < no && i < ni) ? th[nt.woff[l - 1] + o + no * i] : T(0);
+    }
+    for (int e = tid; e < nt.P[l]; e += 256) b[e] = e < no ? th[nt.boff[l - 1] + e] : T(0);
+  }
+  for (int e = tid; e < nt.P[nt.H]; e += 256) S[nt.lwo + e] = e < nt.n[nt.H] ? th[nt.woff[nt.H] + e] : T(0);
+  __syncthreads();
+}
+
+// the 16 rows at rr of the slice ending at rend -> rowi (or -1) and a_0 (zero rows up to P[0], zero columns past the slice)
+template <typename T>
+__device__ __forceinline__ void bnn_load_x(const BnnArgs<T> &a, T *S, long long *rowi, long long rr, long long rend) {
+  const int tid = threadIdx.x;
+  if (tid < kFlowTile) rowi[tid] = rr + tid < rend ? (a.rows ? a.rows[rr + tid] : rr + tid) : -1;
+  __syncthreads();
+  T *a0 = S + a.net.la[0];
+  for (int e = tid; e < a.net.P[0] * kFlowTile; e += 256) {
+    const int r = e & 15, k = e >> 4;
+    const long long ri = rowi[r];
+    a0[k * kBnnLda + r] = (ri >= 0 && k < a.net.n[0]) ? a.X[ri + (long long)k * a.n] : T(0);
+  }
+  __syncthreads();
+}
+
+// a_0 -> a_1 .. a_H in LDS; f of tile row `tid` in threads 0 .. 15 (f64, the output bias added), 0 elsewhere
+template <typename T>
+__device__ __forceinline__ double bnn_forward_tile(const BnnNet &nt, T *S, double bout) {
+  using acc_t = typename Mfma16<T>::acc_t;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
+  for (int l = 1; l <= nt.H; ++l) {
+    const T *W = S + nt.lw[l - 1], *b = S + nt.lb[l - 1], *ain = S + nt.la[l - 1];
+    T *aout = S + nt.la[l];
+    const int ldw = nt.P[l] + 1, K = nt.P[l - 1];
+    for (int ot = w; ot < nt.P[l] / 16; ot += 4) {
+      acc_t acc = acc_t{0, 0, 0, 0};
+      for (int kk = 0; kk < K; kk += 4) acc = Mfma16<T>::mma(W[(kk + kq) * ldw + 16 * ot + col], ain[(kk + kq) * kBnnLda + col], acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * ot + Mfma16<T>::row(kq, r);
+        aout[row * kBnnLda + col] = bnn_tanh(acc[r] + b[row]);   // (a padded row has zero weights and bias: tanh(0) = 0)
+      }
+    }
+    __syncthreads();
+  }
+  double f = 0.0;
+  if (w == 0) {   // the output row as a 16-row A operand whose rows 1 .. 15 are zero: C[0][col] is register 0 of lanes 0 .. 15
+    const T *wo = S + nt.lwo, *aH = S + nt.la[nt.H];
+    acc_t acc = acc_t{0, 0, 0, 0};
+    for (int kk = 0; kk < nt.P[nt.H]; kk += 4) acc = Mfma16<T>::mma(col == 0 ? wo[kk + kq] : T(0), aH[(kk + kq) * kBnnLda + col], acc);
+    if (kq == 0) f = (double)acc[0] + bout;
+  }
+  return f;
+}
+
+// the wave's dW tiles -> the slice's f64 partial (added to it after the first flush); the accumulators restart at zero
+template <typename T>
+__device__ __forceinline__ void bnn_flush(const BnnNet &nt, typename Mfma16<T>::acc_t (&acc)[kBnnWaveTiles], double *part, bool add) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
+#pragma unroll
+  for (int t = 0; t < kBnnWaveTiles; ++t) {
+    int g = w + 4 * t;
+    if (g < nt.toff[nt.H]) {
+      int l = 1;
+      while (g >= nt.toff[l]) ++l;
+      g -= nt.toff[l - 1];
+      const int itn = nt.P[l - 1] / 16, ot = g / itn, it = g - ot * itn, i = 16 * it + col;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = 16 * ot + Mfma16<T>::row(kq, r);
+        if (o < nt.n[l] && i < nt.n[l - 1]) {
+          double *dst = part + nt.woff[l - 1] + o + nt.n[l] * i;
+          *dst = add ? *dst + (double)acc[t][r] : (double)acc[t][r];
+        }
+        acc[t][r] = T(0);
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bnn_rows(BnnArgs<T> a) {
+  using acc_t = typename Mfma16<T>::acc_t;
+  T *S = reinterpret_cast<T *>(flow_lds);
+  __shared__ long long rowi[kFlowTile];
+  __shared__ T res[kFlowTile];
+  const BnnNet &nt = a.net;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 15, kq = lane >> 4;
+  const int ml = blockIdx.x, sl = blockIdx.y;
+  const T *th = a.Z + (size_t)(a.m0 + ml) * nt.d;
+  bnn_stage_net(nt, th, S);
+  const double bout = (double)th[nt.d - 1], in2 = 1.0 / (a.noise * a.noise);
+  const long long rbeg = (long long)sl * a.rps, rend = rbeg + a.rps < a.nr ? rbeg + a.rps : a.nr;
+  double *part = a.part + ((size_t)sl * a.M + ml) * nt.d;
+  acc_t acc[kBnnWaveTiles];
+#pragma unroll
+  for (int t = 0; t < kBnnWaveTiles; ++t) acc[t] = acc_t{0, 0, 0, 0};
+  double gb[3] = {0.0, 0.0, 0.0}, gwo = 0.0, gbo = 0.0, ll = 0.0;
+  bool flushed = false;
+  int since = 0;
+  const T *wo = S + nt.lwo, *aH = S + nt.la[nt.H];
+  for (long long rr = rbeg; rr < rend; rr += kFlowTile) {
+    bnn_load_x(a, S, rowi, rr, rend);
+    const double f = bnn_forward_tile(nt, S, bout);
+    if (tid < kFlowTile) {   // the likelihood of tile row tid, in f64
+      double rs = 0.0;
+      if (rowi[tid] >= 0) {
+        const double y = (double)a.y[rowi[tid]];
+        if (a.likelihood == 0) {
+          const double e = exp(-fabs(f));
+          ll += y * f - (fmax(f, 0.0) + log1p(e));
+          rs = y - (f >= 0.0 ? 1.0 : e) / (1.0 + e);
+        } else {
+          const double u = y - f;
+          ll -= 0.5 * u * u * in2;
+          rs = u * in2;
+        }
+      }
+      gbo += rs;
+      res[tid] = (T)rs;
+    }
+    if (!a.want_grad) continue;
+    __syncthreads();
+    T *D = S + nt.ldl[0], *Dn = S + nt.ldl[1];
+    if (tid < nt.P[nt.H]) {   // the output row's gradient; delta_H = w_out res (1 - a_H^2)
+      double s = 0.0;
+#pragma unroll
+      for (int r = 0; r < kFlowTile; ++r) s += (double)aH[tid * kBnnLda + r] * (double)res[r];
+      gwo += s;
+    }
+    for (int e = tid; e < nt.P[nt.H] * kFlowTile; e += 256) {
+      const int j = e >> 4, r = e & 15;
+      const T av = aH[j * kBnnLda + r];
+      D[j * kBnnLda + r] = wo[j] * res[r] * (T(1) - av * av);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int l = 3; l >= 1; --l) {
+      if (l <= nt.H) {
+        const T *ain = S + nt.la[l - 1];
+        if (tid < nt.P[l]) {   // db_l: the row sums of delta_l
+          double s = 0.0;
+#pragma unroll
+          for (int r = 0; r < kFlowTile; ++r) s += (double)D[tid * kBnnLda + r];
+          gb[l - 1] += s;
+        }
+        const int t0 = nt.toff[l - 1], tn = nt.toff[l] - t0, itn = nt.P[l - 1] / 16;
+#pragma unroll
+        for (int t = 0; t < kBnnWaveTiles; ++t) {   // dW_l += delta_l a_{l-1}': K is the tile's 16 rows
+          const int g = w + 4 * t - t0;
+          if (g >= 0 && g < tn) {
+            const int ot = g / itn, it = g - ot * itn;
+#pragma unroll
+            for (int kk = 0; kk < kFlowTile; kk += 4)
+              acc[t] = Mfma16<T>::mma(D[(16 * ot + col) * kBnnLda + kk + kq], ain[(16 * it + col) * kBnnLda + kk + kq], acc[t]);
+          }
+        }
+        if (l > 1) {   // delta_{l-1} = (W_l' delta_l) (1 - a_{l-1}^2), from the saved activations
+          const T *W = S + nt.lw[l - 1];
+          const int ldw = nt.P[l] + 1;
+          for (int it = w; it < itn; it += 4) {
+            acc_t c = acc_t{0, 0, 0, 0};
+            for (int kk = 0; kk < nt.P[l]; kk += 4) c = Mfma16<T>::mma(W[(16 * it + col) * ldw + kk + kq], D[(kk + kq) * kBnnLda + col], c);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int i = 16 * it + Mfma16<T>::row(kq, r);
+              const T av = ain[i * kBnnLda + col];
+              Dn[i * kBnnLda + col] = c[r] * (T(1) - av * av);
+            }
+          }
+        }
+        __syncthreads();
+        T *sw = D;
+        D = Dn;
+        Dn = sw;
+      }
+    }
+    if constexpr (sizeof(T) == 4) {
+      since += kFlowTile;
+      if (since >= kBnnFlush) {
+        bnn_flush<T>(nt, acc, part, flushed);
+        flushed = true;
+        since = 0;
+      }
+    }
+  }
+  ll = wave_sum(ll);     // (threads 0 .. 15 of wave 0 hold the terms)
+  gbo = wave_sum(gbo);
+  if (tid == 0) a.llp[(size_t)sl * a.M + ml] = ll;
+  if (!a.want_grad) return;
+  bnn_flush<T>(nt, acc, part, flushed);
+#pragma unroll
+  for (int l = 1; l <= 3; ++l)
+    if (l <= nt.H && tid < nt.n[l]) part[nt.boff[l - 1] + tid] = gb[l - 1];
+  if (tid < nt.n[nt.H]) part[nt.woff[nt.H] + tid] = gwo;
+  if (tid == 0) part[nt.d - 1] = gbo;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bnn_forward(BnnArgs<T> a) {
+  T *S = reinterpret_cast<T *>(flow_lds);
+  __shared__ long long rowi[kFlowTile];
+  const BnnNet &nt = a.net;
+  const int tid = threadIdx.x, m = blockIdx.x, sl = blockIdx.y;
+  const T *th = a.Z + (size_t)m * nt.d;
+  bnn_stage_net(nt, th, S);
+  const double bout = (double)th[nt.d - 1];
+  const long long rbeg = (long long)sl * a.rps, rend = rbeg + a.rps < a.nr ? rbeg + a.rps : a.nr;
+  for (long long rr = rbeg; rr < rend; rr += kFlowTile) {
+    bnn_load_x(a, S, rowi, rr, rend);
+    const double f = bnn_forward_tile(nt, S, bout);
+    if (tid < kFlowTile && rowi[tid] >= 0) a.f[rr + tid + a.nr * (long long)m] = (T)f;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bnn_finish(BnnArgs<T> a) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x, ml = blockIdx.x, d = a.net.d;
+  const T *z = a.Z + (size_t)(a.m0 + ml) * d;
+  const double ip2 = 1.0 / (a.prior_std * a.prior_std);
+  double tt = 0.0;
+  for (int i = tid; i < d; i += 256) {
+    const double zi = (double)z[i];
+    tt += zi * zi;
+    if (a.want_grad) {
+      double x = 0.0;
+      for (int sl = 0; sl < a.n_sl; ++sl) x += a.part[((size_t)sl * a.M + ml) * d + i];
+      a.G[(size_t)(a.m0 + ml) * d + i] = (T)(a.likeadj * x - zi * ip2);
+    }
+  }
+  tt = block_sum<double, 256>(tt, red);
+  if (tid == 0) {
+    double ll = 0.0;
+    for (int sl = 0; sl < a.n_sl; ++sl) ll += a.llp[(size_t)sl * a.M + ml];
+    if (a.likelihood == 1) ll -= (double)a.nr * (log(a.noise) + 0.5 * kLog2Pi);
+    a.ell[a.m0 + ml] = (T)(a.likeadj * ll - 0.5 * tt * ip2 - (double)d * (log(a.prior_std) + 0.5 * kLog2Pi));
+  }
+}
+
+// ---- the launches' geometry: a function of the architecture, the rows and the cap alone ------------------------------------------------
+static BnnNet bnn_net(const mivi_ctx *c) {
+  BnnNet nt{};
+  nt.H = c->bnn.n_hidden;
+  nt.n[0] = c->bnn_p;
+  for (int l = 1; l <= nt.H; ++l) nt.n[l] = c->bnn.hidden[l - 1];
+  nt.n[nt.H + 1] = 1;
+  int off = 0, lds = 0;
+  for (int l = 0; l <= nt.H; ++l) nt.P[l] = (nt.n[l] + 15) & ~15;
+  for (int l = 1; l <= nt.H + 1; ++l) {
+    nt.woff[l - 1] = off;
+    off += nt.n[l] * nt.n[l - 1];
+    nt.boff[l - 1] = off;
+    off += nt.n[l];
+  }
+  nt.d = off;
+  for (int l = 1; l <= nt.H; ++l) {
+    nt.lw[l - 1] = lds;
+    lds += nt.P[l - 1] * (nt.P[l] + 1);
+    nt.lb[l - 1] = lds;
+    lds += nt.P[l];
+    nt.toff[l] = nt.toff[l - 1] + (nt.P[l] / 16) * (nt.P[l - 1] / 16);
+  }
+  nt.lwo = lds;
+  lds += nt.P[nt.H];
+  int widest = 0;
+  for (int l = 0; l <= nt.H; ++l) {
+    nt.la[l] = lds;
+    lds += nt.P[l] * kBnnLda;
+    widest = nt.P[l] > widest ? nt.P[l] : widest;
+  }
+  for (int k = 0; k < 2; ++k) {
+    nt.ldl[k] = lds;
+    lds += widest * kBnnLda;
+  }
+  nt.lds_elems = lds;
+  return nt;
+}
+
+struct BnnGeom {
+  int n_sl, Mc;
+  long long rps;
+};
+static BnnGeom bnn_geom(const mivi_ctx *c, long long nr, int M) {
+  BnnGeom g;
+  long long ns = (nr + kBnnSliceRows - 1) / kBnnSliceRows;
+  ns = ns < 1 ? 1 : (ns > 32 ? 32 : ns);
+  g.rps = ((nr + ns - 1) / ns + kFlowTile - 1) / kFlowTile * kFlowTile;
+  g.n_sl = (int)((nr + g.rps - 1) / g.rps);
+  const size_t cap = c->bnn_cap ? c->bnn_cap : kBnnPartCap;
+  size_t mc = cap / ((size_t)g.n_sl * c->cfg.d * sizeof(double));
+  if (mc > (size_t)M) mc = (size_t)M;
+  g.Mc = mc < 1 ? 1 : (int)mc;
+  return g;
+}
+
+bool bnn_reserve(mivi_ctx *c, int M) {
+  const BnnGeom g = bnn_geom(c, c->bnn_nr, M);
+  return !ensure(c, c->bnn_part, (size_t)g.n_sl * g.Mc * c->cfg.d * sizeof(double), false) &&
+         !ensure(c, c->bnn_ll, (size_t)g.n_sl * g.Mc * sizeof(double), false);
+}
+
+template <typename T>
+static BnnArgs<T> bnn_args(const mivi_ctx *c) {
+  BnnArgs<T> a{};
+  a.net = bnn_net(c);
+  a.likelihood = c->bnn.likelihood;
+  a.noise = c->bnn.noise;
+  a.prior_std = c->bnn.prior_std;
+  return a;
+}
+
+template <typename T>
+static bool bnn_impl(mivi_ctx *c, int M, int want_grad) {
+  const BnnGeom g = bnn_geom(c, c->bnn_nr, M);
+  BnnArgs<T> a = bnn_args<T>(c);
+  if (!flow_lds_attr<T>(k_bnn_rows<T>, a.net.lds_elems)) return false;
+  a.n = c->bnn_n;
+  a.nr = c->bnn_nr;
+  a.X = (const T *)c->bnn_X;
+  a.y = (const T *)c->bnn_y;
+  a.rows = c->bnn_sel ? (const long long *)c->bnn_idx.p : nullptr;
+  a.Z = (const T *)c->Z.p;
+  a.part = (double *)c->bnn_part.p;
+  a.llp = (double *)c->bnn_ll.p;
+  a.n_sl = g.n_sl;
+  a.rps = g.rps;
+  a.G = (T *)c->W.p;
+  a.ell = (T *)c->ell.p;
+  a.want_grad = want_grad;
+  a.likeadj = c->bnn_likeadj;
+  const size_t lds = (size_t)a.net.lds_elems * sizeof(T);
+  for (int m0 = 0; m0 < M; m0 += g.Mc) {   // chunks of samples: the f64 partials stay under their cap
+    a.m0 = m0;
+    a.M = M - m0 < g.Mc ? M - m0 : g.Mc;
+    hipLaunchKernelGGL(k_bnn_rows<T>, dim3(a.M, g.n_sl), dim3(256), lds, c->stream, a);
+    hipLaunchKernelGGL(k_bnn_finish<T>, dim3(a.M), dim3(256), 0, c->stream, a);
+  }
+  return true;
+}
+
+// false: device allocation of the partials failed, or the runtime refused the kernel its LDS
+bool launch_bnn_target(mivi_ctx *c, int M, int want_grad) {
+  if (!bnn_reserve(c, M)) return false;
+  return by_dtype(c, [&](auto t) { return bnn_impl<decltype(t)>(c, M, want_grad); });
+}
+
+template <typename T>
+static bool bnn_forward_impl(mivi_ctx *c, const void *theta, int M, const void *Xnew, long long n_new, void *f) {
+  const BnnGeom g = bnn_geom(c, n_new, M);
+  BnnArgs<T> a = bnn_args<T>(c);
+  if (!flow_lds_attr<T>(k_bnn_forward<T>, a.net.lds_elems)) return false;
+  a.n = a.nr = n_new;
+  a.X = (const T *)Xnew;
+  a.Z = (const T *)theta;
+  a.f = (T *)f;
+  a.n_sl = g.n_sl;
+  a.rps = g.rps;
+  hipLaunchKernelGGL(k_bnn_forward<T>, dim3(M, g.n_sl), dim3(256), (size_t)a.net.lds_elems * sizeof(T), c->stream, a);
+  return true;
+}
+
+bool launch_bnn_forward(mivi_ctx *c, const void *theta, int M, const void *Xnew, long long n_new, void *f) {
+  return by_dtype(c, [&](auto t) { return bnn_forward_impl<decltype(t)>(c, theta, M, Xnew, n_new, f); });
+}
+
+}  // namespace mivi

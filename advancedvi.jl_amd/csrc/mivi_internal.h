@@ -33,7 +33,8 @@ enum TargetKind : int {
   TGT_LOGREG = 3,
   TGT_FUNNEL = 4,
   TGT_CALLBACK = 5,
-  TGT_SOFTMAX = 6     // softmax (multinomial logistic) regression: kernels_softmax.hip, a generic target like the callback's
+  TGT_SOFTMAX = 6,    // softmax (multinomial logistic) regression: kernels_softmax.hip, a generic target like the callback's
+  TGT_BNN = 7         // Bayesian neural network: kernels_bnn.hip, a generic target too
 };
 
 // What the Stacked bijector does to one coordinate (kernels_bijector.hip).  The legacy mask of mivi_set_bijector_stacked holds 0 / 1:
@@ -530,6 +531,17 @@ struct mivi_ctx : mivi_ctx_streams {
   int sm_C = 0, sm_variant = 0;
   double sm_likeadj = 1.0, sm_likeadj_full = 1.0;
   size_t sm_cap = 0;
+  // Bayesian neural network (api_bnn.hip, kernels_bnn.hip): theta = [vec W_1; b_1; ...; vec W_{H+1}; b_{H+1}].  The data set stays resident; a
+  // row selection (mivi_bnn_select_rows) is the index vector bnn_idx, which the kernel reads the rows THROUGH.  bnn_part: the f64 partial
+  // gradients per (row slice, sample of a chunk); bnn_ll: those of the log-likelihood.  bnn_cap: the byte cap of bnn_part (0: kBnnPartCap)
+  mivi_bnn_t bnn = {};
+  const void *bnn_X = nullptr, *bnn_y = nullptr;
+  mivi::DevBuf bnn_X_own, bnn_y_own, bnn_idx, bnn_part, bnn_ll;
+  int64_t bnn_n = 0, bnn_nr = 0;           // rows of the data set; rows of the selection (= bnn_n without one)
+  bool bnn_sel = false;                    // a row selection is in force
+  int bnn_p = 0;
+  double bnn_likeadj = 1.0;                // the likeadj in force (bnn.likeadj: the full data set's)
+  size_t bnn_cap = 0;
   // callback
   mivi_logdensity_and_gradient_fn cb_grad = nullptr;
   mivi_logdensity_fn cb_value = nullptr;
@@ -813,6 +825,12 @@ constexpr size_t kSmPartCap = 128u << 20;          // ... and of the f64 partial
 int sm_chunk_samples(const mivi_ctx *c, int M);    // samples per chunk under the two caps
 bool sm_reserve(mivi_ctx *c, int M);               // size sm_R / sm_part / sm_ell for M samples per estimate (ahead of a graph capture)
 bool launch_sm_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation failed
+
+// kernels_bnn.hip: the Bayesian neural network target (api_bnn.hip sets it; eval_generic_target evaluates it)
+constexpr size_t kBnnPartCap = 128u << 20;         // bytes of the f64 partial planes a chunk of samples may take (at least one sample per chunk)
+bool bnn_reserve(mivi_ctx *c, int M);              // size bnn_part / bnn_ll for M samples per estimate (ahead of a graph capture)
+bool launch_bnn_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation or the LDS size failed
+bool launch_bnn_forward(mivi_ctx *c, const void *theta, int M, const void *Xnew, long long n_new, void *f);   // f[r + n_new m]
 
 // kernels_score.hip: the score-gradient (VarGrad) estimator's own kernels (api_score.hip drives them)
 void launch_sg_dense_ell(mivi_ctx *c, int M);                          // sg_d[cap + m] = 0.5 r_m' g_m from Z and W = G = -P R (dense-Gaussian target)

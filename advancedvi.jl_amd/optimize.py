@@ -348,12 +348,17 @@ NO_SCHEDULE_SOFTMAX = ("SoftmaxRegProblem: the scheduled minibatch device loop (
                        "built for the logistic regression only; subsampled steps take the host-driven loop with mivi_softmax_select_rows per step")
 
 
+NO_SCHEDULE_BNN = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "BNNProblem").replace("mivi_softmax_select_rows", "mivi_bnn_select_rows")
+
+
 def subsampled_route_note(obj, prob):
     """Why a SubsampledObjective over `prob` does not take the scheduled device loop, by name -- None where it does, or where nothing is subsampled."""
     from . import problems as P
     inner = prob.prob if isinstance(prob, P.TransformedProblem) else prob
     if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.SoftmaxRegProblem, P.SoftmaxRegSubset)):
         return NO_SCHEDULE_SOFTMAX
+    if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.BNNProblem, P.BNNSubset)):
+        return NO_SCHEDULE_BNN
     return None
 
 

@@ -203,6 +203,91 @@ class SoftmaxRegSubset:
         return SoftmaxRegSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
+class BNNProblem:
+    """A Bayesian neural network (mivi_set_target_bnn): the MLP p -> hidden_dims -> 1 with tanh hidden layers over
+    theta = [vec W_1 (column-major, out x in); b_1; ...; vec W_{H+1}; b_{H+1}], theta_i ~ Normal(0, prior_std^2), and a Bernoulli (logit link,
+    y in {0, 1}) or Normal(f, noise) likelihood scaled by likeadj.  X is n x p, y has n entries; one to three hidden layers of width <= 64."""
+
+    LIKELIHOODS = {"bernoulli": 0, "normal": 1}
+
+    def __init__(self, X, y, hidden_dims, likelihood="bernoulli", noise=1.0, prior_std=1.0, likeadj=1.0):
+        # device-resident data: a contiguous (p, n) tensor -- n x p column-major, as the kernel reads it -- and a tensor of n labels, both of
+        # the context's dtype
+        self.on_device = hasattr(X, "data_ptr")
+        self.X = X if self.on_device else np.asarray(X)
+        self.y = y if self.on_device else np.asarray(y)
+        self.p, self.n = (int(X.shape[0]), int(X.shape[1])) if self.on_device else (self.X.shape[1], self.X.shape[0])
+        self.hidden_dims = tuple(int(h) for h in hidden_dims)
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError(f"unknown likelihood {likelihood}")
+        self.likelihood = likelihood
+        self.noise, self.prior_std, self.likeadj = float(noise), float(prior_std), float(likeadj)
+
+    def layers(self):
+        """[(out, in)] of W_1 .. W_{H+1}"""
+        widths = (self.p,) + self.hidden_dims + (1,)
+        return [(widths[l + 1], widths[l]) for l in range(len(widths) - 1)]
+
+    def dimension(self):
+        return sum(o * (i + 1) for o, i in self.layers())
+
+    def capabilities(self):
+        return LogDensityOrder(1)
+
+    def n_rows(self):
+        return self.n
+
+    def subsample(self, batch):
+        """AdvancedVI.subsample(prob, batch): the rows `batch` (0-based) with the likelihood scaled by n_data / n.  The data stay on
+        the device and the kernel reads the rows through the index vector; see mivi_bnn_select_rows."""
+        return BNNSubset(self, batch)
+
+    def unpack(self, theta):
+        """theta (d,) -> [(W_l (out, in), b_l (out,))], views where theta is contiguous"""
+        theta, out, off = np.asarray(theta), [], 0
+        for o, i in self.layers():
+            out.append((theta[off:off + o * i].reshape(o, i, order="F"), theta[off + o * i:off + o * (i + 1)]))
+            off += o * (i + 1)
+        return out
+
+    def predict(self, theta, Xnew, ctx=None):
+        """Posterior predictive f of the M networks in theta (d x M: the samples `MiviContext.sample` returns, or a (d, M) array) on the
+        rows of Xnew (n_new x p): a device tensor (M, n_new), by mivi_bnn_forward.  ctx: a context that has this problem set; without one
+        a context of theta's precision is made for the call."""
+        from . import context as K
+        own = ctx is None
+        if own:
+            f64 = (theta.dtype == K._torch().float64) if hasattr(theta, "data_ptr") else (np.asarray(theta).dtype == np.float64)
+            ctx = K.MiviContext(np.float64 if f64 else np.float32, K.MEANFIELD, self.dimension(), 1, 0, 0)
+            ctx.set_problem(self)
+        try:
+            return ctx.bnn_forward(theta, Xnew)
+        finally:
+            if own:
+                ctx.synchronize()
+                ctx.close()
+
+
+class BNNSubset:
+    """A minibatch view of a BNNProblem (what `subsample` returns); never copies X."""
+
+    def __init__(self, parent: BNNProblem, batch):
+        self.parent = parent
+        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
+        if self.batch.size == 0:
+            raise ValueError("empty batch")
+        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
+
+    def dimension(self):
+        return self.parent.dimension()
+
+    def capabilities(self):
+        return self.parent.capabilities()
+
+    def subsample(self, batch):
+        return BNNSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
+
+
 def subsample(model, batch):
     """AdvancedVI.subsample(model, batch): models that do not specialise it are returned unchanged
     (src/AdvancedVI.jl:313; the tutorial's warning at docs/src/tutorials/subsampling.md:106-110)."""
@@ -304,4 +389,4 @@ class TransformedProblem:
 
 
 BUILTIN = (DiagNormalProblem, DenseNormalProblem, LogRegProblem, LogRegSubset, FunnelProblem, FunnelConstrainedProblem, SoftmaxRegProblem,
-           SoftmaxRegSubset)
+           SoftmaxRegSubset, BNNProblem, BNNSubset)

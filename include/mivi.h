@@ -322,6 +322,44 @@ mivi_status_t mivi_softmax_select_rows(mivi_ctx_t *ctx, const int64_t *idx_host,
  * (at least one).  0 restores the default (64 MiB).  Results do not depend on it, bit for bit. */
 mivi_status_t mivi_softmax_set_plane_cap(mivi_ctx_t *ctx, int64_t bytes);
 
+/* A Bayesian neural network: the MLP p -> h_1 -> ... -> h_H -> 1 with tanh hidden layers, a_0 = x, a_j = tanh(W_j a_{j-1} + b_j),
+ * f = W_{H+1} a_H + b_{H+1} (a scalar per row), over theta = [vec W_1 (column-major, out x in: W[o + out*i]); b_1; ...; vec W_{H+1}; b_{H+1}]
+ * -- the layout of a net of the flow families -- so d = sum_l n_l (n_{l-1} + 1) with n_0 = p, n_{H+1} = 1 (at most 12 545):
+ *   likelihood 0 (Bernoulli, logit link, y in {0, 1}):  loglike = sum_r [y_r f_r - softplus(f_r)]
+ *   likelihood 1 (Normal, fixed std `noise`):           loglike = -1/2 sum_r ((y_r - f_r) / noise)^2 - n log noise - n/2 log 2 pi
+ *   theta_i ~ Normal(0, prior_std^2) i.i.d.,            log pi(theta) = likeadj loglike + logprior(theta)
+ * X: n x p COLUMN-major T (X[r + k*n]), y: n values of T; x_on_device != 0 => X, y are device ptrs (borrowed, must outlive the ctx; the
+ * labels are then NOT checked), otherwise host ptrs, copied.  Every Monte-Carlo sample is a different network: the target runs M
+ * independent forward and backward passes on the device on a kernel of its own (every layer product on the matrix cores in the element
+ * type, the likelihood, every sum over rows and the prior in f64), and is served by every entry that serves a callback target by explicit
+ * samples -- all families, entropy estimators, bijectors and bases, the score-gradient and Stein (order-1) entries,
+ * mivi_estimate_objective -- without a host round trip, and by the graph-recorded routes (mivi_estimate_gradient_n,
+ * mivi_optimize_steps / _loop as the graph of launches).  MIVI_ERR_UNSUPPORTED with a message naming the entry and "Bayesian neural
+ * network target": mivi_optimize_loop_many, the batch schedule entries, mivi_gauss_expected_grad_hess2*, mivi_logreg_select_rows,
+ * mivi_softmax_select_rows.  MIVI_ERR_BAD_ARG with a message: n < 1; p, n_hidden or a width outside its limits; d of the context not the
+ * network's (the message gives the expected d); an unknown likelihood; noise, prior_std or likeadj <= 0 or not finite; a Bernoulli label
+ * outside {0, 1} (host data); the target that was set stays. */
+#define MIVI_BNN_MAX_IN 64
+#define MIVI_BNN_MAX_HIDDEN 64
+typedef struct {
+  int32_t n_hidden;     /* H, 1 .. 3 */
+  int32_t hidden[3];    /* widths, 1 .. MIVI_BNN_MAX_HIDDEN */
+  int32_t likelihood;   /* 0 Bernoulli-logit, 1 Normal(f, noise) */
+  double  noise, prior_std, likeadj;
+} mivi_bnn_t;
+mivi_status_t mivi_set_target_bnn(mivi_ctx_t *ctx, const mivi_bnn_t *net, const void *X, const void *y, int64_t n, int32_t p,
+                                  int32_t x_on_device);
+/* AdvancedVI.subsample for the network, the contract of mivi_softmax_select_rows: rows idx_host[0..b) (0-based, repeats allowed) with the
+ * likelihood scaled by `likeadj`; b = 0 restores the full data set and its likeadj.  Every index is checked before anything is uploaded; a
+ * failed call leaves the selection unchanged.  The kernel reads the rows THROUGH the index vector: nothing is gathered. */
+mivi_status_t mivi_bnn_select_rows(mivi_ctx_t *ctx, const int64_t *idx_host, int64_t b, double likeadj);
+/* Posterior predictive: f_dev[r + n_new*m] = f(Xnew[r]; theta[:, m]) for the M networks in theta_dev (d x M, ld d) on the rows of Xnew_dev
+ * (n_new x p column-major, device), with the architecture of the target that is set.  Asynchronous on the context's stream. */
+mivi_status_t mivi_bnn_forward(mivi_ctx_t *ctx, const void *theta_dev, int32_t M, const void *Xnew_dev, int64_t n_new, void *f_dev);
+/* Internal (tests): the byte cap of the f64 partial-gradient planes, which decides how many samples a chunk of the target's launches
+ * takes (at least one).  0 restores the default (128 MiB).  Results do not depend on it, bit for bit. */
+mivi_status_t mivi_bnn_set_part_cap(mivi_ctx_t *ctx, int64_t bytes);
+
 /* Neal's funnel on the constrained scale + Stacked([log, identity]) bijector (README.md:76-82,102-106):
  * theta_1 = exp(eta_1) ~ LogNormal(0, sigma_v), theta_i ~ Normal(0, theta_1), log|det J| = eta_1. */
 mivi_status_t mivi_set_target_funnel(mivi_ctx_t *ctx, double sigma_v);
