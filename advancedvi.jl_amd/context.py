@@ -151,6 +151,8 @@ class MiviContext:
             self._sm_full = None
         if not isinstance(prob, (P.BNNProblem, P.BNNSubset)):
             self._bnn_full = None
+        if not isinstance(prob, (P.HierGLMProblem, P.HierGLMSubset)):
+            self._hglm_full = None
         if isinstance(prob, P.SoftmaxRegProblem) and getattr(self, "_sm_full", None) is prob:
             self._chk(self.lib.mivi_softmax_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
         elif isinstance(prob, P.SoftmaxRegProblem):
@@ -193,6 +195,28 @@ class MiviContext:
             if getattr(self, "_bnn_full", None) is not prob.parent:   # upload the full data set once, then only select rows
                 self.set_problem(prob.parent)
             self._chk(self.lib.mivi_bnn_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
+        elif isinstance(prob, P.HierGLMProblem) and getattr(self, "_hglm_full", None) is prob:
+            self._chk(self.lib.mivi_hglm_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
+        elif isinstance(prob, P.HierGLMProblem):
+            model = _lib.MiviHglm(P.HierGLMProblem.LIKELIHOODS[prob.likelihood], prob.n_groups, prob.prior_std, prob.tau_scale, prob.likeadj)
+            groups = np.ascontiguousarray(prob.groups, dtype=np.int32)   # (always on the host: the row order is built there)
+            if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor, y and the offset tensors of n entries, all of the context's dtype
+                held = [prob.X, prob.y] + ([] if prob.offset is None else [prob.offset])
+                if any(t.dtype != self.tdtype or not t.is_contiguous() for t in held):
+                    raise TypeError("HierGLMProblem on the device: X is a contiguous (p, n) tensor, y and offset contiguous tensors of the context's dtype")
+                self._keep += held
+                self._chk(self.lib.mivi_set_target_hglm(self.h, C.byref(model), self._p(prob.X), self._p(prob.y),
+                                                        None if prob.offset is None else self._p(prob.offset), groups.ctypes.data, prob.n, prob.p, 1))
+            else:
+                Xf, y = np.asfortranarray(prob.X, dtype=dt), np.ascontiguousarray(prob.y, dtype=dt)
+                off = None if prob.offset is None else np.ascontiguousarray(prob.offset, dtype=dt)
+                self._chk(self.lib.mivi_set_target_hglm(self.h, C.byref(model), Xf.ctypes.data, y.ctypes.data, None if off is None else off.ctypes.data,
+                                                        groups.ctypes.data, Xf.shape[0], prob.p, 0))
+            self._hglm_full = prob
+        elif isinstance(prob, P.HierGLMSubset):
+            if getattr(self, "_hglm_full", None) is not prob.parent:   # upload the full data set once, then only select rows
+                self.set_problem(prob.parent)
+            self._chk(self.lib.mivi_hglm_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
         elif isinstance(prob, P.DiagNormalProblem):
             m = np.ascontiguousarray(prob.mean, dtype=dt)
             s = np.ascontiguousarray(np.broadcast_to(prob.std, m.shape), dtype=dt)
@@ -689,6 +713,11 @@ class MiviContext:
         """Internal (tests): the byte cap of the Bayesian neural network target's f64 partial planes, which decides how many samples one
         chunk of its launches takes; 0 restores the default.  Results do not depend on it (mivi_bnn_set_part_cap)."""
         self._chk(self.lib.mivi_bnn_set_part_cap(self.h, int(nbytes)))
+
+    def hglm_set_part_cap(self, nbytes):
+        """Internal (tests): the byte cap of the hierarchical GLM target's f64 partial planes, which decides how many samples one chunk of
+        its launches takes; 0 restores the default.  Results do not depend on it (mivi_hglm_set_part_cap)."""
+        self._chk(self.lib.mivi_hglm_set_part_cap(self.h, int(nbytes)))
 
     def bnn_forward(self, theta, Xnew):
         """mivi_bnn_forward: f (M, n_new) of the M networks in theta (d x M: a (d, M) array or tensor) on the rows of Xnew (n_new x p), with

@@ -34,7 +34,8 @@ enum TargetKind : int {
   TGT_FUNNEL = 4,
   TGT_CALLBACK = 5,
   TGT_SOFTMAX = 6,    // softmax (multinomial logistic) regression: kernels_softmax.hip, a generic target like the callback's
-  TGT_BNN = 7         // Bayesian neural network: kernels_bnn.hip, a generic target too
+  TGT_BNN = 7,        // Bayesian neural network: kernels_bnn.hip, a generic target too
+  TGT_HGLM = 8        // hierarchical GLM (varying intercepts): kernels_hglm.hip, a generic target too
 };
 
 // What the Stacked bijector does to one coordinate (kernels_bijector.hip).  The legacy mask of mivi_set_bijector_stacked holds 0 / 1:
@@ -542,6 +543,22 @@ struct mivi_ctx : mivi_ctx_streams {
   int bnn_p = 0;
   double bnn_likeadj = 1.0;                // the likeadj in force (bnn.likeadj: the full data set's)
   size_t bnn_cap = 0;
+  // hierarchical GLM (api_hglm.hip, kernels_hglm.hip): theta = [beta (p); u (J); s].  The rows are evaluated in GROUP order: host data is
+  // stored in that order (hg_rows_on = false for the full set), borrowed device data and every row selection are read THROUGH hg_rows.
+  // hg_grp: the group of every evaluated row, hg_gstart: the segment table (J + 1), hg_sltab: first and last group of every row slice.
+  // hg_group / hg_pos / hg_lg (host): every row's group, its place in the stored data (empty: its own index) and lgamma(y + 1) (Poisson).
+  // hg_bpart [slice][sample][p], hg_gplane [J][sample], hg_edge [slice][2][sample], hg_ll [slice][sample]: the f64 partials of a chunk
+  mivi_hglm_t hg = {};
+  const void *hg_X = nullptr, *hg_y = nullptr, *hg_off = nullptr;
+  mivi::DevBuf hg_X_own, hg_y_own, hg_off_own, hg_rows, hg_grp, hg_gstart, hg_sltab, hg_bpart, hg_gplane, hg_edge, hg_ll;
+  std::vector<int32_t> hg_group;
+  std::vector<int64_t> hg_pos;
+  std::vector<double> hg_lg;
+  int64_t hg_n = 0, hg_nr = 0;             // rows of the data set; rows evaluated (= hg_n without a selection)
+  bool hg_rows_on = false;                 // the kernel reads its rows through hg_rows
+  int hg_p = 0;
+  double hg_likeadj = 1.0, hg_lgam = 0.0;  // the likeadj in force (hg.likeadj: the full data set's); sum lgamma(y_r + 1) over the evaluated rows
+  size_t hg_cap = 0;
   // callback
   mivi_logdensity_and_gradient_fn cb_grad = nullptr;
   mivi_logdensity_fn cb_value = nullptr;
@@ -831,6 +848,15 @@ constexpr size_t kBnnPartCap = 128u << 20;         // bytes of the f64 partial p
 bool bnn_reserve(mivi_ctx *c, int M);              // size bnn_part / bnn_ll for M samples per estimate (ahead of a graph capture)
 bool launch_bnn_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation or the LDS size failed
 bool launch_bnn_forward(mivi_ctx *c, const void *theta, int M, const void *Xnew, long long n_new, void *f);   // f[r + n_new m]
+
+// kernels_hglm.hip: the hierarchical GLM target (api_hglm.hip sets it; eval_generic_target evaluates it)
+constexpr size_t kHglmPartCap = 256u << 20;        // bytes of the f64 partial planes a chunk of samples may take (at least one sample per chunk)
+constexpr long long kHglmSliceRows = 256;          // rows a slice aims at; slices: ceil(rows / 256) clamped to 1 .. kHglmMaxSlices
+constexpr long long kHglmMaxSlices = 1024;
+struct HglmGeom { int n_sl; long long rps; };      // row slices and rows per slice (a multiple of 16): a function of the evaluated rows alone
+HglmGeom hglm_geom(long long nr);
+bool hglm_reserve(mivi_ctx *c, int M);             // size the partial planes for M samples per estimate (ahead of a graph capture)
+bool launch_hglm_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation or the LDS size failed
 
 // kernels_score.hip: the score-gradient (VarGrad) estimator's own kernels (api_score.hip drives them)
 void launch_sg_dense_ell(mivi_ctx *c, int M);                          // sg_d[cap + m] = 0.5 r_m' g_m from Z and W = G = -P R (dense-Gaussian target)

@@ -351,6 +351,9 @@ NO_SCHEDULE_SOFTMAX = ("SoftmaxRegProblem: the scheduled minibatch device loop (
 NO_SCHEDULE_BNN = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "BNNProblem").replace("mivi_softmax_select_rows", "mivi_bnn_select_rows")
 
 
+NO_SCHEDULE_HGLM = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "HierGLMProblem").replace("mivi_softmax_select_rows", "mivi_hglm_select_rows")
+
+
 def subsampled_route_note(obj, prob):
     """Why a SubsampledObjective over `prob` does not take the scheduled device loop, by name -- None where it does, or where nothing is subsampled."""
     from . import problems as P
@@ -359,6 +362,8 @@ def subsampled_route_note(obj, prob):
         return NO_SCHEDULE_SOFTMAX
     if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.BNNProblem, P.BNNSubset)):
         return NO_SCHEDULE_BNN
+    if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.HierGLMProblem, P.HierGLMSubset)):
+        return NO_SCHEDULE_HGLM
     return None
 
 

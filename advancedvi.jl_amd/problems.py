@@ -288,6 +288,71 @@ class BNNSubset:
         return BNNSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
+class HierGLMProblem:
+    """A hierarchical GLM with varying intercepts (mivi_set_target_hglm): theta = [beta (p); u (n_groups); s], eta_r = x_r . beta +
+    u[groups[r]] + offset[r], beta_k ~ Normal(0, prior_std^2), u_g ~ Normal(0, tau^2), tau = exp(s) ~ HalfNormal(tau_scale), and a Bernoulli
+    (logit link, y in {0, 1}) or Poisson (log link, y in {0, 1, 2, ...}) likelihood scaled by likeadj.  X is n x p (p <= 256), y and the
+    optional offset have n entries, groups holds n ids in {0, ..., n_groups - 1} in any order; a group may have no rows."""
+
+    LIKELIHOODS = {"bernoulli": 0, "poisson": 1}
+
+    def __init__(self, X, y, groups, n_groups, likelihood="bernoulli", offset=None, prior_std=1.0, tau_scale=1.0, likeadj=1.0):
+        # device-resident data: a contiguous (p, n) tensor -- n x p column-major, as the kernel reads it -- and tensors of n responses and
+        # offsets, all of the context's dtype.  The group ids are host data in either case: the row order is built on the host
+        self.on_device = hasattr(X, "data_ptr")
+        self.X = X if self.on_device else np.asarray(X)
+        self.y = y if self.on_device else np.asarray(y)
+        self.offset = offset if offset is None or self.on_device else np.asarray(offset)
+        self.groups = np.asarray(groups.cpu() if hasattr(groups, "data_ptr") else groups).reshape(-1)
+        self.p, self.n = (int(X.shape[0]), int(X.shape[1])) if self.on_device else (self.X.shape[1], self.X.shape[0])
+        if self.groups.size != self.n:
+            raise ValueError("HierGLMProblem: one group id per row")
+        self.n_groups = int(n_groups)
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError(f"unknown likelihood {likelihood}")
+        self.likelihood = likelihood
+        self.prior_std, self.tau_scale, self.likeadj = float(prior_std), float(tau_scale), float(likeadj)
+
+    def dimension(self):
+        return self.p + self.n_groups + 1
+
+    def capabilities(self):
+        return LogDensityOrder(1)
+
+    def n_rows(self):
+        return self.n
+
+    def subsample(self, batch):
+        """AdvancedVI.subsample(prob, batch): the rows `batch` (0-based) with the likelihood scaled by n_data / n.  The data stay on
+        the device; the selection is put into group order and the kernel reads the rows through it; see mivi_hglm_select_rows."""
+        return HierGLMSubset(self, batch)
+
+    def unpack(self, theta):
+        """theta (d,) -> (beta (p,), u (n_groups,), s), views where theta is contiguous"""
+        theta = np.asarray(theta)
+        return theta[:self.p], theta[self.p:self.p + self.n_groups], theta[self.p + self.n_groups]
+
+
+class HierGLMSubset:
+    """A minibatch view of a HierGLMProblem (what `subsample` returns); never copies X."""
+
+    def __init__(self, parent: HierGLMProblem, batch):
+        self.parent = parent
+        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
+        if self.batch.size == 0:
+            raise ValueError("empty batch")
+        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
+
+    def dimension(self):
+        return self.parent.dimension()
+
+    def capabilities(self):
+        return self.parent.capabilities()
+
+    def subsample(self, batch):
+        return HierGLMSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
+
+
 def subsample(model, batch):
     """AdvancedVI.subsample(model, batch): models that do not specialise it are returned unchanged
     (src/AdvancedVI.jl:313; the tutorial's warning at docs/src/tutorials/subsampling.md:106-110)."""
@@ -389,4 +454,4 @@ class TransformedProblem:
 
 
 BUILTIN = (DiagNormalProblem, DenseNormalProblem, LogRegProblem, LogRegSubset, FunnelProblem, FunnelConstrainedProblem, SoftmaxRegProblem,
-           SoftmaxRegSubset, BNNProblem, BNNSubset)
+           SoftmaxRegSubset, BNNProblem, BNNSubset, HierGLMProblem, HierGLMSubset)

@@ -360,6 +360,44 @@ mivi_status_t mivi_bnn_forward(mivi_ctx_t *ctx, const void *theta_dev, int32_t M
  * takes (at least one).  0 restores the default (128 MiB).  Results do not depend on it, bit for bit. */
 mivi_status_t mivi_bnn_set_part_cap(mivi_ctx_t *ctx, int64_t bytes);
 
+/* A hierarchical GLM with varying intercepts ("mixed effects"): theta = [beta (p); u (J); s], d = p + J + 1, tau = e^s.  Row r has the
+ * features x_r, the group g_r in {0 .. J-1}, the response y_r and an optional offset o_r (0 without one):
+ *   eta_r = x_r . beta + u[g_r] + o_r
+ *   likelihood 0 (Bernoulli, logit link, y in {0, 1}):     ll_r = y_r eta_r - softplus(eta_r)
+ *   likelihood 1 (Poisson, log link, y in {0, 1, 2, ...}): ll_r = y_r eta_r - exp(eta_r) - lgamma(y_r + 1)
+ *   log pi(theta) = likeadj sum_r ll_r + sum_k logNormal(beta_k; 0, prior_std^2) + sum_g logNormal(u_g; 0, e^{2s})
+ *                 + [log 2 - 1/2 log(2 pi) - log tau_scale - e^{2s} / (2 tau_scale^2) + s]
+ * (tau ~ HalfNormal(tau_scale), the Jacobian of s = log tau included).  With res_r = y_r - sigma(eta_r) (Bernoulli) or y_r - e^{eta_r}
+ * (Poisson): d/dbeta = likeadj X' res - beta / prior_std^2, d/du_g = likeadj sum_{r: g_r = g} res_r - u_g e^{-2s},
+ * d/ds = -J + |u|^2 e^{-2s} - e^{2s} / tau_scale^2 + 1.  A group without rows is legal: its gradient is the prior term alone.
+ * X: n x p COLUMN-major T (X[r + k*n]), y and offset_or_null: n values of T; x_on_device != 0 => X, y and the offset are device ptrs
+ * (borrowed, must outlive the ctx; y is then NOT checked), otherwise host ptrs, copied.  group_host: n group ids in any order, ALWAYS a
+ * host pointer, copied.  The rows are evaluated in group order (a stable ordering built on the host; host data is stored in it, borrowed
+ * data and row selections are read through it), so the sum over a group's rows is a segmented reduction inside the same pass over X that
+ * forms X beta and X' res on the matrix cores; the likelihood and every sum are f64, sum_r lgamma(y_r + 1) is taken once per data set or
+ * selection on the host.  Served, like the softmax and Bayesian-network targets, by every entry that serves a callback target by explicit
+ * samples and by the graph-recorded routes.  MIVI_ERR_UNSUPPORTED with a message naming the entry and "hierarchical GLM target":
+ * mivi_optimize_loop_many, the batch schedule entries, mivi_gauss_expected_grad_hess2*, the other targets' *_select_rows.
+ * MIVI_ERR_BAD_ARG with a message: n < 1; p outside [1, MIVI_HGLM_MAX_P]; n_groups < 1; d of the context not p + J + 1 (the message gives
+ * the expected d); a group id outside [0, J); an unknown likelihood; prior_std, tau_scale or likeadj <= 0 or not finite; a Bernoulli label
+ * outside {0, 1} or a Poisson response that is negative or not an integer (host data); the target that was set stays. */
+#define MIVI_HGLM_MAX_P 256
+typedef struct {
+  int32_t likelihood;   /* 0 Bernoulli-logit, 1 Poisson-log */
+  int32_t n_groups;     /* J */
+  double  prior_std, tau_scale, likeadj;
+} mivi_hglm_t;
+mivi_status_t mivi_set_target_hglm(mivi_ctx_t *ctx, const mivi_hglm_t *model, const void *X, const void *y, const void *offset_or_null,
+                                   const int32_t *group_host, int64_t n, int32_t p, int32_t x_on_device);
+/* AdvancedVI.subsample for the model, the contract of mivi_softmax_select_rows: rows idx_host[0..b) (0-based, repeats allowed) with the
+ * likelihood scaled by `likeadj`; b = 0 restores the full data set and its likeadj.  Every index is checked before anything changes; a
+ * failed call leaves the selection unchanged.  Nothing is gathered: the selection is put into group order on the host and the kernel reads
+ * the rows through that index vector.  MIVI_ERR_UNSUPPORTED, by name, on a context whose target is the softmax or Bayesian-network one. */
+mivi_status_t mivi_hglm_select_rows(mivi_ctx_t *ctx, const int64_t *idx_host, int64_t b, double likeadj);
+/* Internal (tests): the byte cap of the f64 partial planes, which decides how many samples a chunk of the target's launches takes (at
+ * least one).  0 restores the default (256 MiB).  Results do not depend on it, bit for bit. */
+mivi_status_t mivi_hglm_set_part_cap(mivi_ctx_t *ctx, int64_t bytes);
+
 /* Neal's funnel on the constrained scale + Stacked([log, identity]) bijector (README.md:76-82,102-106):
  * theta_1 = exp(eta_1) ~ LogNormal(0, sigma_v), theta_i ~ Normal(0, theta_1), log|det J| = eta_1. */
 mivi_status_t mivi_set_target_funnel(mivi_ctx_t *ctx, double sigma_v);
