@@ -20,7 +20,7 @@ from .optimize import (KLMinRepGradDescent, KLMinRepGradProxDescent, ADVI, KLMin
 from .measure_space import KLMinSqrtNaturalGradDescent, KLMinNaturalGradDescent, FisherMinBatchMatch, KLMinWassFwdBwd
 from . import measure_space as _measure_space
 from .context import MiviContext, NATGRAD_SMALL_D, BAM_MAX_SAMPLES
-from .problems import SoftmaxRegProblem, SoftmaxRegSubset, BNNProblem, BNNSubset, HierGLMProblem, HierGLMSubset
+from .problems import SoftmaxRegProblem, SoftmaxRegSubset, BNNProblem, BNNSubset, HierGLMProblem, HierGLMSubset, PPCAProblem, PPCASubset
 from .problems import subsample, LogRegSubset, FunnelConstrainedProblem, StackedBijector, TransformedProblem, ADgradient
 from . import forwarddiff
 from .subsampling import (ReshufflingBatchSubsampling, ReshufflingBatchSubsamplingState, SubsampledObjective,

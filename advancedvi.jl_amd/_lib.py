@@ -40,6 +40,10 @@ class MiviHglm(C.Structure):   # mivi_hglm_t: the likelihood, group count and pr
     _fields_ = [("likelihood", C.c_int32), ("n_groups", C.c_int32), ("prior_std", C.c_double), ("tau_scale", C.c_double), ("likeadj", C.c_double)]
 
 
+class MiviPpca(C.Structure):   # mivi_ppca_t: the latent dimension, the ARD switch and the priors of mivi_set_target_ppca
+    _fields_ = [("k", C.c_int32), ("ard", C.c_int32), ("prior_std", C.c_double), ("mean_std", C.c_double), ("noise_scale", C.c_double), ("likeadj", C.c_double)]
+
+
 class MiviSplineFlow(C.Structure):   # mivi_spline_flow_t: the architecture of a MIVI_NSF context (mivi_create_spline_flow)
     _fields_ = [("n_layers", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3), ("n_bins", C.c_int32), ("bound", C.c_double)]
 
@@ -82,6 +86,9 @@ SIGNATURES = {
     "mivi_set_target_hglm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "mivi_hglm_select_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
     "mivi_hglm_set_part_cap": (C.c_int32, [C.c_void_p, C.c_int64]),
+    "mivi_set_target_ppca": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "mivi_ppca_select_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
+    "mivi_ppca_set_part_cap": (C.c_int32, [C.c_void_p, C.c_int64]),
     "mivi_set_target_funnel": (C.c_int32, [C.c_void_p, C.c_double]),
     "mivi_set_target_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_AND_GRADIENT_FN, LOGDENSITY_FN, C.c_void_p]),
     "mivi_set_target_value_callback": (C.c_int32, [C.c_void_p, LOGDENSITY_FN, C.c_void_p]),

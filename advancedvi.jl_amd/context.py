@@ -153,6 +153,8 @@ class MiviContext:
             self._bnn_full = None
         if not isinstance(prob, (P.HierGLMProblem, P.HierGLMSubset)):
             self._hglm_full = None
+        if not isinstance(prob, (P.PPCAProblem, P.PPCASubset)):
+            self._ppca_full = None
         if isinstance(prob, P.SoftmaxRegProblem) and getattr(self, "_sm_full", None) is prob:
             self._chk(self.lib.mivi_softmax_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
         elif isinstance(prob, P.SoftmaxRegProblem):
@@ -217,6 +219,26 @@ class MiviContext:
             if getattr(self, "_hglm_full", None) is not prob.parent:   # upload the full data set once, then only select rows
                 self.set_problem(prob.parent)
             self._chk(self.lib.mivi_hglm_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
+        elif isinstance(prob, P.PPCAProblem) and getattr(self, "_ppca_full", None) is prob:
+            self._chk(self.lib.mivi_ppca_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
+        elif isinstance(prob, P.PPCAProblem):
+            model = _lib.MiviPpca(prob.k, int(prob.ard), prob.prior_std, prob.mean_std, prob.noise_scale, prob.likeadj)
+            if prob.on_device:   # column-major n x D as a (D, n) contiguous tensor of the context's dtype, the mask a uint8 tensor of that shape
+                if prob.Y.dtype != self.tdtype or not prob.Y.is_contiguous() or (
+                        prob.mask is not None and (prob.mask.dtype != _torch().uint8 or not prob.mask.is_contiguous() or prob.mask.shape != prob.Y.shape)):
+                    raise TypeError("PPCAProblem on the device: Y is a contiguous (D, n) tensor of the context's dtype, mask a contiguous uint8 tensor of that shape")
+                self._keep += [prob.Y] + ([] if prob.mask is None else [prob.mask])
+                self._chk(self.lib.mivi_set_target_ppca(self.h, C.byref(model), self._p(prob.Y), None if prob.mask is None else self._p(prob.mask),
+                                                        prob.n, prob.D, 1))
+            else:
+                Yf = np.asfortranarray(prob.Y, dtype=dt)
+                mask = None if prob.mask is None else np.asfortranarray(prob.mask, dtype=np.uint8)
+                self._chk(self.lib.mivi_set_target_ppca(self.h, C.byref(model), Yf.ctypes.data, None if mask is None else mask.ctypes.data, prob.n, prob.D, 0))
+            self._ppca_full = prob
+        elif isinstance(prob, P.PPCASubset):
+            if getattr(self, "_ppca_full", None) is not prob.parent:   # upload the full data set once, then only select rows
+                self.set_problem(prob.parent)
+            self._chk(self.lib.mivi_ppca_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
         elif isinstance(prob, P.DiagNormalProblem):
             m = np.ascontiguousarray(prob.mean, dtype=dt)
             s = np.ascontiguousarray(np.broadcast_to(prob.std, m.shape), dtype=dt)
@@ -718,6 +740,11 @@ class MiviContext:
         """Internal (tests): the byte cap of the hierarchical GLM target's f64 partial planes, which decides how many samples one chunk of
         its launches takes; 0 restores the default.  Results do not depend on it (mivi_hglm_set_part_cap)."""
         self._chk(self.lib.mivi_hglm_set_part_cap(self.h, int(nbytes)))
+
+    def ppca_set_part_cap(self, nbytes):
+        """Internal (tests): the byte cap of the probabilistic PCA target's f64 partial planes, which decides how many samples one chunk of
+        its launches takes; 0 restores the default.  Results do not depend on it (mivi_ppca_set_part_cap)."""
+        self._chk(self.lib.mivi_ppca_set_part_cap(self.h, int(nbytes)))
 
     def bnn_forward(self, theta, Xnew):
         """mivi_bnn_forward: f (M, n_new) of the M networks in theta (d x M: a (d, M) array or tensor) on the rows of Xnew (n_new x p), with

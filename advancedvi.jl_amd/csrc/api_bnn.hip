@@ -59,6 +59,7 @@ mivi_status_t mivi_set_target_bnn(mivi_ctx_t *c, const mivi_bnn_t *np, const voi
 mivi_status_t mivi_bnn_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t b, double likeadj) {
   if (!c || b < 0 || (b > 0 && !idx)) return MIVI_ERR_BAD_ARG;
   if (mivi_status_t rs = refuse_hglm(c, "mivi_bnn_select_rows (its rows are selected by mivi_hglm_select_rows)")) return rs;
+  if (mivi_status_t rs = refuse_ppca(c, "mivi_bnn_select_rows (its rows are selected by mivi_ppca_select_rows)")) return rs;
   if (c->target != TGT_BNN) return fail(c, MIVI_ERR_NO_TARGET, "no Bayesian neural network target set");
   (void)hipSetDevice(c->cfg.device);
   if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection in force)

@@ -478,6 +478,7 @@ mivi_status_t mivi_logreg_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t
   if (mivi_status_t rs = refuse_softmax(c, "mivi_logreg_select_rows (its rows are selected by mivi_softmax_select_rows)")) return rs;
   if (mivi_status_t rs = refuse_bnn(c, "mivi_logreg_select_rows (its rows are selected by mivi_bnn_select_rows)")) return rs;
   if (mivi_status_t rs = refuse_hglm(c, "mivi_logreg_select_rows (its rows are selected by mivi_hglm_select_rows)")) return rs;
+  if (mivi_status_t rs = refuse_ppca(c, "mivi_logreg_select_rows (its rows are selected by mivi_ppca_select_rows)")) return rs;
   if (c->target != TGT_LOGREG || !c->lr_X_full) return fail(c, MIVI_ERR_NO_TARGET, "no logistic-regression target set");
   (void)hipSetDevice(c->cfg.device);
   if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection -- rows or a schedule -- in force)
@@ -522,6 +523,7 @@ mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *c, const mivi_batch_sch
   if (mivi_status_t rs = refuse_softmax(c, "mivi_logreg_set_batch_schedule")) return rs;
   if (mivi_status_t rs = refuse_bnn(c, "mivi_logreg_set_batch_schedule")) return rs;
   if (mivi_status_t rs = refuse_hglm(c, "mivi_logreg_set_batch_schedule")) return rs;
+  if (mivi_status_t rs = refuse_ppca(c, "mivi_logreg_set_batch_schedule")) return rs;
   if (c->target != TGT_LOGREG || !c->lr_X_full) return fail(c, MIVI_ERR_NO_TARGET, "no logistic-regression target set");
   const mivi_batch_schedule_t &sc = *sp;
   if (sc.n_batches < 0 || sc.kernels < 0 || sc.kernels > 2) return fail(c, MIVI_ERR_BAD_ARG, "batch schedule: n_batches >= 0 and kernels in 0 .. 2");
@@ -568,6 +570,7 @@ mivi_status_t mivi_logreg_seek_batch(mivi_ctx_t *c, int32_t k) {
   if (mivi_status_t rs = refuse_softmax(c, "mivi_logreg_seek_batch")) return rs;
   if (mivi_status_t rs = refuse_bnn(c, "mivi_logreg_seek_batch")) return rs;
   if (mivi_status_t rs = refuse_hglm(c, "mivi_logreg_seek_batch")) return rs;
+  if (mivi_status_t rs = refuse_ppca(c, "mivi_logreg_seek_batch")) return rs;
   if (c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "no batch schedule set (mivi_logreg_set_batch_schedule)");
   if (k < 0 || k >= c->lr_sched_n) return fail(c, MIVI_ERR_BAD_ARG, "batch index outside the schedule");
   invalidate_graph(c);

@@ -28,6 +28,9 @@ mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
     case TGT_HGLM:
       if (!launch_hglm_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "hierarchical GLM: scratch allocation or the kernel's LDS size failed");
       return MIVI_OK;
+    case TGT_PPCA:
+      if (!launch_ppca_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "probabilistic PCA: scratch allocation or the kernel's LDS size failed");
+      return MIVI_OK;
     case TGT_CALLBACK: {
       if (want_grad && !c->cb_grad) return fail(c, MIVI_ERR_UNSUPPORTED, kValueOnlyTarget);
       const size_t es = c->esize, d = c->cfg.d;

@@ -280,6 +280,7 @@ mivi_status_t mivi_optimize_loop_many(mivi_ctx_t *c, void *params, const mivi_lo
   if (mivi_status_t rs = refuse_softmax(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
   if (mivi_status_t rs = refuse_bnn(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
   if (mivi_status_t rs = refuse_hglm(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
+  if (mivi_status_t rs = refuse_ppca(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
   if (c->base != MIVI_BASE_NORMAL) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a non-normal base distribution has no launch-free loop");
   if (c->bij_on) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a Stacked bijector is set");
   if (c->cfg.m_offset != 0 || c->M_total != c->cfg.n_mc) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a sharded context (m_offset / m_total)");
@@ -368,6 +369,7 @@ mivi_status_t mivi_optimize_loop_batches(mivi_ctx_t *c, void *params, const mivi
   if (mivi_status_t rs = refuse_softmax(c, "mivi_optimize_loop_batches")) return rs;
   if (mivi_status_t rs = refuse_bnn(c, "mivi_optimize_loop_batches")) return rs;
   if (mivi_status_t rs = refuse_hglm(c, "mivi_optimize_loop_batches")) return rs;
+  if (mivi_status_t rs = refuse_ppca(c, "mivi_optimize_loop_batches")) return rs;
   if (c->target != TGT_LOGREG || c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_batches: no batch schedule set (mivi_logreg_set_batch_schedule)");
   if (first_batch < 0 || lp->n_steps <= 0 || (long long)first_batch + lp->n_steps > c->lr_sched_n)
     return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_batches: first_batch + n_steps must lie inside the schedule");

@@ -35,7 +35,8 @@ enum TargetKind : int {
   TGT_CALLBACK = 5,
   TGT_SOFTMAX = 6,    // softmax (multinomial logistic) regression: kernels_softmax.hip, a generic target like the callback's
   TGT_BNN = 7,        // Bayesian neural network: kernels_bnn.hip, a generic target too
-  TGT_HGLM = 8        // hierarchical GLM (varying intercepts): kernels_hglm.hip, a generic target too
+  TGT_HGLM = 8,       // hierarchical GLM (varying intercepts): kernels_hglm.hip, a generic target too
+  TGT_PPCA = 9        // probabilistic PCA / Bayesian factor model (local latents z_r): kernels_ppca.hip, a generic target too
 };
 
 // What the Stacked bijector does to one coordinate (kernels_bijector.hip).  The legacy mask of mivi_set_bijector_stacked holds 0 / 1:
@@ -559,6 +560,18 @@ struct mivi_ctx : mivi_ctx_streams {
   int hg_p = 0;
   double hg_likeadj = 1.0, hg_lgam = 0.0;  // the likeadj in force (hg.likeadj: the full data set's); sum lgamma(y_r + 1) over the evaluated rows
   size_t hg_cap = 0;
+  // probabilistic PCA (api_ppca.hip, kernels_ppca.hip): theta = [vec W (D x k); Z (k x N); mu (D); a (k, ARD); s].  pp_Y: N x D column-major,
+  // pp_mask: uint8 in the same layout or nullptr (all observed); own copies of host data, borrowed device data.  A row selection
+  // (mivi_ppca_select_rows, no repeats) is the index vector pp_idx, which the kernel reads the rows THROUGH; z_r keeps its original row id.
+  // pp_part: the f64 partials per (row slice, sample of a chunk); pp_cap: its byte cap (0: kPpcaPartCap)
+  mivi_ppca_t pp = {};
+  const void *pp_Y = nullptr, *pp_mask = nullptr;
+  mivi::DevBuf pp_Y_own, pp_mask_own, pp_idx, pp_part;
+  int64_t pp_n = 0, pp_nr = 0;             // rows of the data set; rows of the selection (= pp_n without one)
+  bool pp_sel = false;                     // a row selection is in force
+  int pp_D = 0;
+  double pp_likeadj = 1.0;                 // the likeadj in force (pp.likeadj: the full data set's)
+  size_t pp_cap = 0;
   // callback
   mivi_logdensity_and_gradient_fn cb_grad = nullptr;
   mivi_logdensity_fn cb_value = nullptr;
@@ -857,6 +870,11 @@ struct HglmGeom { int n_sl; long long rps; };      // row slices and rows per sl
 HglmGeom hglm_geom(long long nr);
 bool hglm_reserve(mivi_ctx *c, int M);             // size the partial planes for M samples per estimate (ahead of a graph capture)
 bool launch_hglm_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation or the LDS size failed
+
+// kernels_ppca.hip: the probabilistic PCA target (api_ppca.hip sets it; eval_generic_target evaluates it); its row slices are hglm_geom's
+constexpr size_t kPpcaPartCap = 256u << 20;        // bytes of the f64 partial planes a chunk of samples may take (at least one sample per chunk)
+bool ppca_reserve(mivi_ctx *c, int M);             // size the partial planes for M samples per estimate (ahead of a graph capture)
+bool launch_ppca_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation or the LDS size failed
 
 // kernels_score.hip: the score-gradient (VarGrad) estimator's own kernels (api_score.hip drives them)
 void launch_sg_dense_ell(mivi_ctx *c, int M);                          // sg_d[cap + m] = 0.5 r_m' g_m from Z and W = G = -P R (dense-Gaussian target)

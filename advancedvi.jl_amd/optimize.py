@@ -354,6 +354,9 @@ NO_SCHEDULE_BNN = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "BNNProblem")
 NO_SCHEDULE_HGLM = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "HierGLMProblem").replace("mivi_softmax_select_rows", "mivi_hglm_select_rows")
 
 
+NO_SCHEDULE_PPCA = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "PPCAProblem").replace("mivi_softmax_select_rows", "mivi_ppca_select_rows")
+
+
 def subsampled_route_note(obj, prob):
     """Why a SubsampledObjective over `prob` does not take the scheduled device loop, by name -- None where it does, or where nothing is subsampled."""
     from . import problems as P
@@ -364,6 +367,8 @@ def subsampled_route_note(obj, prob):
         return NO_SCHEDULE_BNN
     if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.HierGLMProblem, P.HierGLMSubset)):
         return NO_SCHEDULE_HGLM
+    if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.PPCAProblem, P.PPCASubset)):
+        return NO_SCHEDULE_PPCA
     return None
 
 

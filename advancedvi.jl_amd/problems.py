@@ -353,6 +353,69 @@ class HierGLMSubset:
         return HierGLMSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
+class PPCAProblem:
+    """Probabilistic PCA / a Bayesian factor model (mivi_set_target_ppca): y_rj ~ Normal(mu_j + W_j. . z_r, sigma^2) on the observed entries
+    of Y (n x D, D <= 512; `mask` n x D of 0 / 1, None: all observed), z_r ~ Normal(0, I_k) for every row (k <= 32), mu_j ~ Normal(0,
+    mean_std^2), sigma = exp(s) ~ HalfNormal(noise_scale) and W_jc ~ Normal(0, prior_std^2) or, with ard, W_jc ~ Normal(0, exp(2 a_c)),
+    exp(a_c) ~ HalfNormal(prior_std).  theta = [vec W (D x k, column-major); Z (k x n, z_r contiguous); mu (D); a (k, with ard); s]: every
+    row owns k coordinates, which start on a multiple of k -- BlockDiagGaussian blocks of k give each z_r a full covariance.  likeadj scales
+    the rows' terms, each row's z_r prior included."""
+
+    def __init__(self, Y, k, mask=None, ard=False, prior_std=1.0, mean_std=10.0, noise_scale=1.0, likeadj=1.0):
+        # device-resident data: a contiguous (D, n) tensor of the context's dtype -- n x D column-major, as the kernel reads it -- and a
+        # uint8 mask tensor of the same shape
+        self.on_device = hasattr(Y, "data_ptr")
+        self.Y = Y if self.on_device else np.asarray(Y)
+        self.mask = mask if mask is None or self.on_device else np.asarray(mask)
+        self.D, self.n = (int(Y.shape[0]), int(Y.shape[1])) if self.on_device else (self.Y.shape[1], self.Y.shape[0])
+        if self.mask is not None and tuple(self.mask.shape) != tuple(self.Y.shape):
+            raise ValueError("PPCAProblem: the mask has the shape of Y")
+        self.k, self.ard = int(k), bool(ard)
+        self.prior_std, self.mean_std, self.noise_scale, self.likeadj = float(prior_std), float(mean_std), float(noise_scale), float(likeadj)
+
+    def dimension(self):
+        return self.D * self.k + self.n * self.k + self.D + (self.k if self.ard else 0) + 1
+
+    def capabilities(self):
+        return LogDensityOrder(1)
+
+    def n_rows(self):
+        return self.n
+
+    def subsample(self, batch):
+        """AdvancedVI.subsample(prob, batch): the rows `batch` (0-based, no repeats) with their terms -- likelihood and z_r prior -- scaled
+        by n_data / n.  The data stay on the device; the kernel reads the rows through the index vector; see mivi_ppca_select_rows."""
+        return PPCASubset(self, batch)
+
+    def unpack(self, theta):
+        """theta (d,) -> (W (D, k), Z (n, k), mu (D,), a (k,) or None, s), views where theta is contiguous"""
+        theta = np.asarray(theta)
+        D, k, n = self.D, self.k, self.n
+        oz, om = D * k, D * k + n * k
+        return (theta[:oz].reshape(k, D).T, theta[oz:om].reshape(n, k), theta[om:om + D], theta[om + D:om + D + k] if self.ard else None,
+                theta[-1])
+
+
+class PPCASubset:
+    """A minibatch view of a PPCAProblem (what `subsample` returns); never copies Y."""
+
+    def __init__(self, parent: PPCAProblem, batch):
+        self.parent = parent
+        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
+        if self.batch.size == 0:
+            raise ValueError("empty batch")
+        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
+
+    def dimension(self):
+        return self.parent.dimension()
+
+    def capabilities(self):
+        return self.parent.capabilities()
+
+    def subsample(self, batch):
+        return PPCASubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
+
+
 def subsample(model, batch):
     """AdvancedVI.subsample(model, batch): models that do not specialise it are returned unchanged
     (src/AdvancedVI.jl:313; the tutorial's warning at docs/src/tutorials/subsampling.md:106-110)."""
@@ -454,4 +517,4 @@ class TransformedProblem:
 
 
 BUILTIN = (DiagNormalProblem, DenseNormalProblem, LogRegProblem, LogRegSubset, FunnelProblem, FunnelConstrainedProblem, SoftmaxRegProblem,
-           SoftmaxRegSubset, BNNProblem, BNNSubset, HierGLMProblem, HierGLMSubset)
+           SoftmaxRegSubset, BNNProblem, BNNSubset, HierGLMProblem, HierGLMSubset, PPCAProblem, PPCASubset)

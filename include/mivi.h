@@ -398,6 +398,50 @@ mivi_status_t mivi_hglm_select_rows(mivi_ctx_t *ctx, const int64_t *idx_host, in
  * least one).  0 restores the default (256 MiB).  Results do not depend on it, bit for bit. */
 mivi_status_t mivi_hglm_set_part_cap(mivi_ctx_t *ctx, int64_t bytes);
 
+/* Probabilistic PCA / Bayesian factor model (Bishop's Bayesian PCA with an optional ARD prior on the loading columns; with a mask, dense
+ * probabilistic matrix factorisation).  Y is n x D, m in {0,1}^{n x D} marks the observed entries (no mask: all), k is the latent dimension:
+ *   theta = [vec W (D x k, column c contiguous: W[j + c*D]); Z (k x n, z_r contiguous); mu (D); a (k, only with ard); s],  sigma = e^s
+ *   d = D k + n k + D + (ard ? k : 0) + 1 -- every data row r OWNS its latent z_r, so d grows with the data; z_r starts on a multiple of k
+ *   pred_rj = mu_j + sum_c W_jc z_rc
+ *   log pi(theta) = likeadj sum_{r selected} [ sum_j m_rj (-1/2 (y_rj - pred_rj)^2 e^{-2s} - s - 1/2 log 2pi) - 1/2 |z_r|^2 - k/2 log 2pi ]
+ *                 + sum_j logNormal(mu_j; 0, mean_std^2)
+ *                 + (ard == 0: sum_jc logNormal(W_jc; 0, prior_std^2)
+ *                    ard != 0: sum_jc logNormal(W_jc; 0, e^{2 a_c}) + sum_c [log 2 - 1/2 log 2pi - log prior_std - e^{2 a_c} / (2 prior_std^2) + a_c])
+ *                 + [log 2 - 1/2 log 2pi - log noise_scale - e^{2s} / (2 noise_scale^2) + s]
+ * (e^{a_c} ~ HalfNormal(prior_std) and sigma ~ HalfNormal(noise_scale), the Jacobians of the logs included).  likeadj multiplies the whole
+ * bracket of a row, its z_r prior too.  With e_rj = m_rj (y_rj - pred_rj) e^{-2s}: d/dz_r = likeadj (sum_j e_rj W_j. - z_r) on a selected
+ * row and EXACTLY 0 on any other, d/dW_jc = likeadj sum_r e_rj z_rc - W_jc / prior_std^2 (ard: - W_jc e^{-2 a_c}),
+ * d/dmu_j = likeadj sum_r e_rj - mu_j / mean_std^2, d/da_c = -D + |W_.c|^2 e^{-2 a_c} - e^{2 a_c} / prior_std^2 + 1,
+ * d/ds = likeadj sum_rj m_rj ((y_rj - pred_rj)^2 e^{-2s} - 1) - e^{2s} / noise_scale^2 + 1.
+ * Y: n x D COLUMN-major T (Y[r + j*n]), mask_or_null: uint8 in the same layout; y_on_device != 0 => device ptrs (borrowed, must outlive
+ * the ctx, NOT checked; a contiguous (D, n) tensor), otherwise host ptrs, checked and copied.  One launch per chunk of samples does the
+ * likelihood and every gradient in one pass over Y on the 16 x 16 x 4 matrix cores (kernels_ppca.hip); residuals and every sum over rows
+ * are f64.  Served, like the softmax, Bayesian-network and hierarchical GLM targets, by every entry that serves a callback target by
+ * explicit samples and by the graph-recorded routes.  MIVI_ERR_UNSUPPORTED with a message naming the entry and "probabilistic PCA target":
+ * mivi_optimize_loop_many, the batch schedule entries, mivi_gauss_expected_grad_hess2*, the other targets' *_select_rows.
+ * MIVI_ERR_BAD_ARG with a message: n < 1; D outside [1, MIVI_PPCA_MAX_D]; k outside [1, MIVI_PPCA_MAX_K]; d of the context not the count
+ * above (the message gives it); prior_std, mean_std, noise_scale or likeadj <= 0 or not finite; a mask entry other than 0 or 1, a
+ * non-finite observed y (host data); the target that was set stays.  The limits keep one sample's W in one workgroup's LDS (f64 at both
+ * limits: 153 KB of gfx950's 160). */
+#define MIVI_PPCA_MAX_D 512
+#define MIVI_PPCA_MAX_K 32
+typedef struct {
+  int32_t k;      /* latent dimension */
+  int32_t ard;    /* != 0: automatic-relevance prior, theta holds a (k) */
+  double  prior_std, mean_std, noise_scale, likeadj;
+} mivi_ppca_t;
+mivi_status_t mivi_set_target_ppca(mivi_ctx_t *ctx, const mivi_ppca_t *model, const void *Y, const uint8_t *mask_or_null, int64_t n, int32_t D,
+                                   int32_t y_on_device);
+/* AdvancedVI.subsample for the model: rows idx_host[0..b) (0-based, in any order, NO repeats: two row slices would both own d/dz_r) with
+ * the rows' brackets scaled by `likeadj`; b = 0 restores the full data set and its likeadj.  Every index is checked before anything
+ * changes; a failed call leaves the selection unchanged.  Nothing is gathered: the kernel reads Y, the mask and z_r through the index
+ * vector, and d/dz_r of the rows outside the selection is written as zero.  MIVI_ERR_UNSUPPORTED, by name, on a context whose target is
+ * the softmax, Bayesian-network or hierarchical GLM one. */
+mivi_status_t mivi_ppca_select_rows(mivi_ctx_t *ctx, const int64_t *idx_host, int64_t b, double likeadj);
+/* Internal (tests): the byte cap of the f64 partial planes, which decides how many samples a chunk of the target's launches takes (at
+ * least one).  0 restores the default (256 MiB).  Results do not depend on it, bit for bit. */
+mivi_status_t mivi_ppca_set_part_cap(mivi_ctx_t *ctx, int64_t bytes);
+
 /* Neal's funnel on the constrained scale + Stacked([log, identity]) bijector (README.md:76-82,102-106):
  * theta_1 = exp(eta_1) ~ LogNormal(0, sigma_v), theta_i ~ Normal(0, theta_1), log|det J| = eta_1. */
 mivi_status_t mivi_set_target_funnel(mivi_ctx_t *ctx, double sigma_v);
