@@ -38,6 +38,16 @@ _CREATORS = {REALNVP: ("mivi_create_flow", "RealNVP family", "a REALNVP context 
 _FLOW_FIELDS = {REALNVP: ("RealNVP", _lib.MiviFlow, ()), NSF: ("NeuralSplineFlow", _lib.MiviSplineFlow, (int, float))}
 
 
+# The targets whose data set stays resident on the device (the logistic regression and the rows of kTargets, csrc/api_common.h): the
+# full-data problem class -> (the entry that selects its rows, the MiviContext method that uploads the data set).  A _RowSubset of such a
+# problem is its parent plus a row selection; optimize.subsampled_route_note names the same entries
+_RESIDENT = {P.LogRegProblem: ("mivi_logreg_select_rows", "_upload_logreg"),
+             P.SoftmaxRegProblem: ("mivi_softmax_select_rows", "_upload_softmax"),
+             P.BNNProblem: ("mivi_bnn_select_rows", "_upload_bnn"),
+             P.HierGLMProblem: ("mivi_hglm_select_rows", "_upload_hglm"),
+             P.PPCAProblem: ("mivi_ppca_select_rows", "_upload_ppca")}
+
+
 class MiviContext:
     """One RepGradELBO estimator instance on one GPU (mivi_create ... mivi_destroy)."""
 
@@ -82,6 +92,7 @@ class MiviContext:
         self.h = h
         self.m_total = int(m_total) if m_total else self.n_mc
         self._keep = []      # keep-alive for callbacks / borrowed device arrays
+        self._resident = None   # the full-data problem of _RESIDENT whose data set is on the device
         self.problem = None
 
     @classmethod
@@ -145,100 +156,20 @@ class MiviContext:
             self.problem = prob
             return
         self.set_bijector(None)
-        if not isinstance(prob, (P.LogRegProblem, P.LogRegSubset)):
-            self._lr_full = None   # another target kind replaces the resident data set
-        if not isinstance(prob, (P.SoftmaxRegProblem, P.SoftmaxRegSubset)):
-            self._sm_full = None
-        if not isinstance(prob, (P.BNNProblem, P.BNNSubset)):
-            self._bnn_full = None
-        if not isinstance(prob, (P.HierGLMProblem, P.HierGLMSubset)):
-            self._hglm_full = None
-        if not isinstance(prob, (P.PPCAProblem, P.PPCASubset)):
-            self._ppca_full = None
-        if isinstance(prob, P.SoftmaxRegProblem) and getattr(self, "_sm_full", None) is prob:
-            self._chk(self.lib.mivi_softmax_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
-        elif isinstance(prob, P.SoftmaxRegProblem):
-            if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor of the context's dtype, y uint8
-                if prob.X.dtype != self.tdtype or not prob.X.is_contiguous() or prob.y.dtype != _torch().uint8:
-                    raise TypeError("SoftmaxRegProblem on the device: X is a contiguous (p, n) tensor of the context's dtype, y a uint8 tensor")
-                self._keep += [prob.X, prob.y]
-                self._chk(self.lib.mivi_set_target_softmax(self.h, self._p(prob.X), self._p(prob.y), prob.n, prob.n_classes,
-                                                           P.SoftmaxRegProblem.VARIANTS[prob.variant], prob.likeadj, 1))
-            else:
-                Xf = np.asfortranarray(prob.X, dtype=dt)
-                y = np.ascontiguousarray(prob.y, dtype=np.uint8)
-                if y.size and int(np.max(np.asarray(prob.y))) > 255:
-                    raise ValueError("SoftmaxRegProblem: labels are bytes in {0, ..., n_classes - 1}")
-                self._chk(self.lib.mivi_set_target_softmax(self.h, Xf.ctypes.data, y.ctypes.data, Xf.shape[0], prob.n_classes,
-                                                           P.SoftmaxRegProblem.VARIANTS[prob.variant], prob.likeadj, 0))
-            self._sm_full = prob
-        elif isinstance(prob, P.SoftmaxRegSubset):
-            if getattr(self, "_sm_full", None) is not prob.parent:   # upload the full data set once, then only select rows
-                self.set_problem(prob.parent)
-            self._chk(self.lib.mivi_softmax_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
-        elif isinstance(prob, P.BNNProblem) and getattr(self, "_bnn_full", None) is prob:
-            self._chk(self.lib.mivi_bnn_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
-        elif isinstance(prob, P.BNNProblem):
-            hidden = list(prob.hidden_dims)
-            if not 1 <= len(hidden) <= 3:
-                raise ValueError("BNNProblem: one to three hidden layers")
-            net = _lib.MiviBnn(len(hidden), (C.c_int32 * 3)(*(hidden + [0] * (3 - len(hidden)))), P.BNNProblem.LIKELIHOODS[prob.likelihood],
-                               prob.noise, prob.prior_std, prob.likeadj)
-            if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor, y a tensor of n entries, both of the context's dtype
-                if prob.X.dtype != self.tdtype or not prob.X.is_contiguous() or prob.y.dtype != self.tdtype or not prob.y.is_contiguous():
-                    raise TypeError("BNNProblem on the device: X is a contiguous (p, n) tensor and y a contiguous tensor of the context's dtype")
-                self._keep += [prob.X, prob.y]
-                self._chk(self.lib.mivi_set_target_bnn(self.h, C.byref(net), self._p(prob.X), self._p(prob.y), prob.n, prob.p, 1))
-            else:
-                Xf, y = np.asfortranarray(prob.X, dtype=dt), np.ascontiguousarray(prob.y, dtype=dt)
-                self._chk(self.lib.mivi_set_target_bnn(self.h, C.byref(net), Xf.ctypes.data, y.ctypes.data, Xf.shape[0], prob.p, 0))
-            self._bnn_full = prob
-        elif isinstance(prob, P.BNNSubset):
-            if getattr(self, "_bnn_full", None) is not prob.parent:   # upload the full data set once, then only select rows
-                self.set_problem(prob.parent)
-            self._chk(self.lib.mivi_bnn_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
-        elif isinstance(prob, P.HierGLMProblem) and getattr(self, "_hglm_full", None) is prob:
-            self._chk(self.lib.mivi_hglm_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
-        elif isinstance(prob, P.HierGLMProblem):
-            model = _lib.MiviHglm(P.HierGLMProblem.LIKELIHOODS[prob.likelihood], prob.n_groups, prob.prior_std, prob.tau_scale, prob.likeadj)
-            groups = np.ascontiguousarray(prob.groups, dtype=np.int32)   # (always on the host: the row order is built there)
-            if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor, y and the offset tensors of n entries, all of the context's dtype
-                held = [prob.X, prob.y] + ([] if prob.offset is None else [prob.offset])
-                if any(t.dtype != self.tdtype or not t.is_contiguous() for t in held):
-                    raise TypeError("HierGLMProblem on the device: X is a contiguous (p, n) tensor, y and offset contiguous tensors of the context's dtype")
-                self._keep += held
-                self._chk(self.lib.mivi_set_target_hglm(self.h, C.byref(model), self._p(prob.X), self._p(prob.y),
-                                                        None if prob.offset is None else self._p(prob.offset), groups.ctypes.data, prob.n, prob.p, 1))
-            else:
-                Xf, y = np.asfortranarray(prob.X, dtype=dt), np.ascontiguousarray(prob.y, dtype=dt)
-                off = None if prob.offset is None else np.ascontiguousarray(prob.offset, dtype=dt)
-                self._chk(self.lib.mivi_set_target_hglm(self.h, C.byref(model), Xf.ctypes.data, y.ctypes.data, None if off is None else off.ctypes.data,
-                                                        groups.ctypes.data, Xf.shape[0], prob.p, 0))
-            self._hglm_full = prob
-        elif isinstance(prob, P.HierGLMSubset):
-            if getattr(self, "_hglm_full", None) is not prob.parent:   # upload the full data set once, then only select rows
-                self.set_problem(prob.parent)
-            self._chk(self.lib.mivi_hglm_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
-        elif isinstance(prob, P.PPCAProblem) and getattr(self, "_ppca_full", None) is prob:
-            self._chk(self.lib.mivi_ppca_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
-        elif isinstance(prob, P.PPCAProblem):
-            model = _lib.MiviPpca(prob.k, int(prob.ard), prob.prior_std, prob.mean_std, prob.noise_scale, prob.likeadj)
-            if prob.on_device:   # column-major n x D as a (D, n) contiguous tensor of the context's dtype, the mask a uint8 tensor of that shape
-                if prob.Y.dtype != self.tdtype or not prob.Y.is_contiguous() or (
-                        prob.mask is not None and (prob.mask.dtype != _torch().uint8 or not prob.mask.is_contiguous() or prob.mask.shape != prob.Y.shape)):
-                    raise TypeError("PPCAProblem on the device: Y is a contiguous (D, n) tensor of the context's dtype, mask a contiguous uint8 tensor of that shape")
-                self._keep += [prob.Y] + ([] if prob.mask is None else [prob.mask])
-                self._chk(self.lib.mivi_set_target_ppca(self.h, C.byref(model), self._p(prob.Y), None if prob.mask is None else self._p(prob.mask),
-                                                        prob.n, prob.D, 1))
-            else:
-                Yf = np.asfortranarray(prob.Y, dtype=dt)
-                mask = None if prob.mask is None else np.asfortranarray(prob.mask, dtype=np.uint8)
-                self._chk(self.lib.mivi_set_target_ppca(self.h, C.byref(model), Yf.ctypes.data, None if mask is None else mask.ctypes.data, prob.n, prob.D, 0))
-            self._ppca_full = prob
-        elif isinstance(prob, P.PPCASubset):
-            if getattr(self, "_ppca_full", None) is not prob.parent:   # upload the full data set once, then only select rows
-                self.set_problem(prob.parent)
-            self._chk(self.lib.mivi_ppca_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
+        full = prob.parent if isinstance(prob, P._RowSubset) else prob
+        row = next((r for cls, r in _RESIDENT.items() if isinstance(full, cls)), None)
+        if row is None or self._resident is not full:
+            self._resident = None   # another data set, another target kind: it replaces the resident data set
+        if row is not None:
+            select_rows, upload = getattr(self.lib, row[0]), getattr(self, row[1])
+            fresh = self._resident is None
+            if fresh:   # upload the full data set once, then only select rows
+                upload(full)
+                self._resident = full
+            if prob is not full:
+                self._chk(select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
+            elif not fresh:
+                self._chk(select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
         elif isinstance(prob, P.DiagNormalProblem):
             m = np.ascontiguousarray(prob.mean, dtype=dt)
             s = np.ascontiguousarray(np.broadcast_to(prob.std, m.shape), dtype=dt)
@@ -247,27 +178,6 @@ class MiviContext:
             m = np.ascontiguousarray(prob.mean, dtype=dt)
             L = np.asfortranarray(prob.L, dtype=dt)
             self._chk(self.lib.mivi_set_target_dense_gauss(self.h, m.ctypes.data, L.ctypes.data))
-        elif isinstance(prob, P.LogRegProblem) and getattr(self, "_lr_full", None) is prob:
-            self._chk(self.lib.mivi_logreg_select_rows(self.h, None, 0, 1.0))   # already resident: back to all rows
-        elif isinstance(prob, P.LogRegProblem):
-            self._lr_full = prob
-            torch = _torch()
-            X = prob.X
-            if isinstance(X, torch.Tensor):   # device-resident, column-major n x p expected
-                Xd, yd = X, prob.y
-                n = X.shape[1] if getattr(prob, "x_is_colmajor_tensor", False) else X.shape[0]
-                self._keep += [Xd, yd]
-                self._chk(self.lib.mivi_set_target_logreg(self.h, self._p(Xd), self._p(yd), n,
-                                                          P.LogRegProblem.VARIANTS[prob.variant], prob.likeadj, 1))
-            else:
-                Xf = np.asfortranarray(X, dtype=dt)
-                y = np.ascontiguousarray(prob.y, dtype=np.uint8)
-                self._chk(self.lib.mivi_set_target_logreg(self.h, Xf.ctypes.data, y.ctypes.data, Xf.shape[0],
-                                                          P.LogRegProblem.VARIANTS[prob.variant], prob.likeadj, 0))
-        elif isinstance(prob, P.LogRegSubset):
-            if getattr(self, "_lr_full", None) is not prob.parent:   # upload the full data set once, then only select rows
-                self.set_problem(prob.parent)
-            self._chk(self.lib.mivi_logreg_select_rows(self.h, prob.batch.ctypes.data, prob.batch.size, prob.likeadj))
         elif isinstance(prob, P.FunnelProblem):
             self._chk(self.lib.mivi_set_target_funnel(self.h, prob.sigma_v))
         elif isinstance(prob, P.FunnelConstrainedProblem):
@@ -275,6 +185,87 @@ class MiviContext:
         else:
             self._set_callback(prob, values_only=values_only)
         self.problem = prob
+
+    # the full data set of a target of _RESIDENT -> the device (set_problem calls them through the table)
+    def _upload_logreg(self, prob):
+        dt = self.np_dtype
+        torch = _torch()
+        X = prob.X
+        if isinstance(X, torch.Tensor):   # device-resident, column-major n x p expected
+            Xd, yd = X, prob.y
+            n = X.shape[1] if getattr(prob, "x_is_colmajor_tensor", False) else X.shape[0]
+            self._keep += [Xd, yd]
+            self._chk(self.lib.mivi_set_target_logreg(self.h, self._p(Xd), self._p(yd), n,
+                                                      P.LogRegProblem.VARIANTS[prob.variant], prob.likeadj, 1))
+        else:
+            Xf = np.asfortranarray(X, dtype=dt)
+            y = np.ascontiguousarray(prob.y, dtype=np.uint8)
+            self._chk(self.lib.mivi_set_target_logreg(self.h, Xf.ctypes.data, y.ctypes.data, Xf.shape[0],
+                                                      P.LogRegProblem.VARIANTS[prob.variant], prob.likeadj, 0))
+
+    def _upload_softmax(self, prob):
+        dt = self.np_dtype
+        if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor of the context's dtype, y uint8
+            if prob.X.dtype != self.tdtype or not prob.X.is_contiguous() or prob.y.dtype != _torch().uint8:
+                raise TypeError("SoftmaxRegProblem on the device: X is a contiguous (p, n) tensor of the context's dtype, y a uint8 tensor")
+            self._keep += [prob.X, prob.y]
+            self._chk(self.lib.mivi_set_target_softmax(self.h, self._p(prob.X), self._p(prob.y), prob.n, prob.n_classes,
+                                                       P.SoftmaxRegProblem.VARIANTS[prob.variant], prob.likeadj, 1))
+        else:
+            Xf = np.asfortranarray(prob.X, dtype=dt)
+            y = np.ascontiguousarray(prob.y, dtype=np.uint8)
+            if y.size and int(np.max(np.asarray(prob.y))) > 255:
+                raise ValueError("SoftmaxRegProblem: labels are bytes in {0, ..., n_classes - 1}")
+            self._chk(self.lib.mivi_set_target_softmax(self.h, Xf.ctypes.data, y.ctypes.data, Xf.shape[0], prob.n_classes,
+                                                       P.SoftmaxRegProblem.VARIANTS[prob.variant], prob.likeadj, 0))
+
+    def _upload_bnn(self, prob):
+        dt = self.np_dtype
+        hidden = list(prob.hidden_dims)
+        if not 1 <= len(hidden) <= 3:
+            raise ValueError("BNNProblem: one to three hidden layers")
+        net = _lib.MiviBnn(len(hidden), (C.c_int32 * 3)(*(hidden + [0] * (3 - len(hidden)))), P.BNNProblem.LIKELIHOODS[prob.likelihood],
+                           prob.noise, prob.prior_std, prob.likeadj)
+        if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor, y a tensor of n entries, both of the context's dtype
+            if prob.X.dtype != self.tdtype or not prob.X.is_contiguous() or prob.y.dtype != self.tdtype or not prob.y.is_contiguous():
+                raise TypeError("BNNProblem on the device: X is a contiguous (p, n) tensor and y a contiguous tensor of the context's dtype")
+            self._keep += [prob.X, prob.y]
+            self._chk(self.lib.mivi_set_target_bnn(self.h, C.byref(net), self._p(prob.X), self._p(prob.y), prob.n, prob.p, 1))
+        else:
+            Xf, y = np.asfortranarray(prob.X, dtype=dt), np.ascontiguousarray(prob.y, dtype=dt)
+            self._chk(self.lib.mivi_set_target_bnn(self.h, C.byref(net), Xf.ctypes.data, y.ctypes.data, Xf.shape[0], prob.p, 0))
+
+    def _upload_hglm(self, prob):
+        dt = self.np_dtype
+        model = _lib.MiviHglm(P.HierGLMProblem.LIKELIHOODS[prob.likelihood], prob.n_groups, prob.prior_std, prob.tau_scale, prob.likeadj)
+        groups = np.ascontiguousarray(prob.groups, dtype=np.int32)   # (always on the host: the row order is built there)
+        if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor, y and the offset tensors of n entries, all of the context's dtype
+            held = [prob.X, prob.y] + ([] if prob.offset is None else [prob.offset])
+            if any(t.dtype != self.tdtype or not t.is_contiguous() for t in held):
+                raise TypeError("HierGLMProblem on the device: X is a contiguous (p, n) tensor, y and offset contiguous tensors of the context's dtype")
+            self._keep += held
+            self._chk(self.lib.mivi_set_target_hglm(self.h, C.byref(model), self._p(prob.X), self._p(prob.y),
+                                                    None if prob.offset is None else self._p(prob.offset), groups.ctypes.data, prob.n, prob.p, 1))
+        else:
+            Xf, y = np.asfortranarray(prob.X, dtype=dt), np.ascontiguousarray(prob.y, dtype=dt)
+            off = None if prob.offset is None else np.ascontiguousarray(prob.offset, dtype=dt)
+            self._chk(self.lib.mivi_set_target_hglm(self.h, C.byref(model), Xf.ctypes.data, y.ctypes.data, None if off is None else off.ctypes.data,
+                                                    groups.ctypes.data, Xf.shape[0], prob.p, 0))
+
+    def _upload_ppca(self, prob):
+        dt = self.np_dtype
+        model = _lib.MiviPpca(prob.k, int(prob.ard), prob.prior_std, prob.mean_std, prob.noise_scale, prob.likeadj)
+        if prob.on_device:   # column-major n x D as a (D, n) contiguous tensor of the context's dtype, the mask a uint8 tensor of that shape
+            if prob.Y.dtype != self.tdtype or not prob.Y.is_contiguous() or (
+                    prob.mask is not None and (prob.mask.dtype != _torch().uint8 or not prob.mask.is_contiguous() or prob.mask.shape != prob.Y.shape)):
+                raise TypeError("PPCAProblem on the device: Y is a contiguous (D, n) tensor of the context's dtype, mask a contiguous uint8 tensor of that shape")
+            self._keep += [prob.Y] + ([] if prob.mask is None else [prob.mask])
+            self._chk(self.lib.mivi_set_target_ppca(self.h, C.byref(model), self._p(prob.Y), None if prob.mask is None else self._p(prob.mask),
+                                                    prob.n, prob.D, 1))
+        else:
+            Yf = np.asfortranarray(prob.Y, dtype=dt)
+            mask = None if prob.mask is None else np.asfortranarray(prob.mask, dtype=np.uint8)
+            self._chk(self.lib.mivi_set_target_ppca(self.h, C.byref(model), Yf.ctypes.data, None if mask is None else mask.ctypes.data, prob.n, prob.D, 0))
 
     def set_base_dist(self, dist):
         """mivi_set_base_dist: the base distribution of the location-scale family -- families.Normal() (None: the same), Laplace() or
@@ -754,7 +745,7 @@ class MiviContext:
         th = th.to(device=self.tdevice, dtype=self.tdtype).t().contiguous()            # (M, d): d x M column-major
         Xn = torch.as_tensor(np.asarray(Xnew)) if not isinstance(Xnew, torch.Tensor) else Xnew
         Xn = Xn.to(device=self.tdevice, dtype=self.tdtype).t().contiguous()            # (p, n_new): n_new x p column-major
-        if getattr(self, "_bnn_full", None) is None or Xn.dim() != 2 or Xn.shape[0] != self._bnn_full.p:
+        if not isinstance(self._resident, P.BNNProblem) or Xn.dim() != 2 or Xn.shape[0] != self._resident.p:
             raise ValueError("bnn_forward: a BNNProblem must be set and Xnew be n_new x p with the problem's p")
         f = torch.empty((th.shape[0], Xn.shape[1]), dtype=self.tdtype, device=self.tdevice)
         torch.cuda.current_stream(self.tdevice).synchronize()   # (th, Xn and f were made on torch's stream; the kernel runs on the context's)
@@ -1005,7 +996,7 @@ class MiviContext:
                 dev(opt_state, self.tdtype, 2 * K * plen, "opt_state")
             elif opt_state is not None and int(rule) in (2, 3):
                 dev(opt_state, torch.uint8, K * int(self.lib.mivi_dog_state_bytes(self.h)), "opt_state")
-            lr = getattr(self, "_lr_full", None)
+            lr = self._resident if isinstance(self._resident, P.LogRegProblem) else None
             if (y is not None or X is not None) and lr is None:
                 raise ValueError("optimize_loop_many: y / X are for a context with a LogRegProblem")
             if lr is not None:
@@ -1048,7 +1039,7 @@ class MiviContext:
             if idx.shape != (n_batches,):
                 raise ValueError("estimate_idx must hold one index per batch")
         if likeadj is None:
-            full = getattr(self, "_lr_full", None)
+            full = self._resident if isinstance(self._resident, P.LogRegProblem) else None
             if full is None:
                 raise ValueError("likeadj is needed: the context holds no LogRegProblem to take n_data from")
             likeadj = full.likeadj * full.n_rows() / batch   # (what LogRegSubset gives a batch of that size)

@@ -3,16 +3,13 @@
 #include "api_common.h"
 
 bool graph_capturable(const mivi_ctx *c) {   // every device-resident target (the host callback is not)
-  return c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS || c->target == TGT_FUNNEL || c->target == TGT_LOGREG || c->target == TGT_SOFTMAX ||
-         c->target == TGT_BNN || c->target == TGT_HGLM || c->target == TGT_PPCA;
+  return c->target == TGT_DIAG_GAUSS || c->target == TGT_DENSE_GAUSS || c->target == TGT_FUNNEL || c->target == TGT_LOGREG || target_row(c);
 }
 // allocations are not allowed inside a capture: size whatever the target's launchers would otherwise grow lazily
 mivi_status_t reserve_target(mivi_ctx *c, int M) {
   if (c->target == TGT_LOGREG && !logreg_reserve(c, M)) return fail(c, MIVI_ERR_HIP, "logistic regression: scratch allocation failed");
-  if (c->target == TGT_SOFTMAX && !sm_reserve(c, M)) return fail(c, MIVI_ERR_HIP, "softmax regression: scratch allocation failed");
-  if (c->target == TGT_BNN && !bnn_reserve(c, M)) return fail(c, MIVI_ERR_HIP, "Bayesian neural network: scratch allocation failed");
-  if (c->target == TGT_HGLM && !hglm_reserve(c, M)) return fail(c, MIVI_ERR_HIP, "hierarchical GLM: scratch allocation failed");
-  if (c->target == TGT_PPCA && !ppca_reserve(c, M)) return fail(c, MIVI_ERR_HIP, "probabilistic PCA: scratch allocation failed");
+  const TargetRow *row = target_row(c);
+  if (row && !row->reserve(c, M)) return fail(c, MIVI_ERR_HIP, (std::string(row->short_name) + ": scratch allocation failed").c_str());
   return MIVI_OK;
 }
 

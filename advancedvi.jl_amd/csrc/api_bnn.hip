@@ -1,7 +1,8 @@
 // libmivi C ABI, the Bayesian neural network target (include/mivi.h): mivi_set_target_bnn, the row selection mivi_bnn_select_rows
 // (AdvancedVI.subsample), the posterior predictive mivi_bnn_forward and the partial planes' cap.  The target is a GENERIC one:
 // eval_generic_target (api_estimate.hip) evaluates it on explicit samples through launch_bnn_target (kernels_bnn.hip), so every route that
-// serves a callback target by explicit samples serves it, on the device; the entries that cannot are guarded by refuse_bnn (api_common.h).
+// serves a callback target by explicit samples serves it, on the device; the target is a row of kTargets (api_common.h), whose refuse_target
+// guards the entries that cannot.
 #include <cmath>
 
 #include "api_common.h"
@@ -47,9 +48,7 @@ mivi_status_t mivi_set_target_bnn(mivi_ctx_t *c, const mivi_bnn_t *np, const voi
   }
   c->bnn = net;
   c->bnn_p = p;
-  c->bnn_n = c->bnn_nr = n;
-  c->bnn_sel = false;
-  c->bnn_likeadj = net.likeadj;
+  c->bnn_rows.set_full(n, net.likeadj);
   c->lr_sched_n = c->lr_sched_k = 0;   // (a logistic regression's schedule of batches goes with its target)
   c->t_const = 0.0;
   c->target = TGT_BNN;
@@ -58,25 +57,11 @@ mivi_status_t mivi_set_target_bnn(mivi_ctx_t *c, const mivi_bnn_t *np, const voi
 
 mivi_status_t mivi_bnn_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t b, double likeadj) {
   if (!c || b < 0 || (b > 0 && !idx)) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_bnn_select_rows (its rows are selected by mivi_hglm_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_bnn_select_rows (its rows are selected by mivi_ppca_select_rows)")) return rs;
+  if (mivi_status_t rs = refuse_rows_of_other_target(c, "mivi_bnn_select_rows", TGT_BNN)) return rs;
   if (c->target != TGT_BNN) return fail(c, MIVI_ERR_NO_TARGET, "no Bayesian neural network target set");
   (void)hipSetDevice(c->cfg.device);
-  if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection in force)
-    if (!bnn_positive(likeadj)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive and finite");
-    for (int64_t j = 0; j < b; ++j)
-      if (idx[j] < 0 || idx[j] >= c->bnn_n) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
-  }
-  invalidate_graph(c);
-  mivi_status_t s = MIVI_OK;
-  if (b > 0) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the previous estimate may still be reading the index vector
-    s = upload(c, c->bnn_idx, idx, (size_t)b * sizeof(int64_t));   // (a grown vector is a new one: on failure the old selection is gone)
-  }
-  c->bnn_sel = b > 0 && s == MIVI_OK;
-  c->bnn_nr = c->bnn_sel ? b : c->bnn_n;
-  c->bnn_likeadj = c->bnn_sel ? likeadj : c->bnn.likeadj;
-  return s;
+  if (b > 0 && !bnn_positive(likeadj)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive and finite");
+  return select_rows(c, c->bnn_rows, idx, b, likeadj, false);
 }
 
 mivi_status_t mivi_bnn_forward(mivi_ctx_t *c, const void *theta, int32_t M, const void *Xnew, int64_t n_new, void *f) {
@@ -89,9 +74,4 @@ mivi_status_t mivi_bnn_forward(mivi_ctx_t *c, const void *theta, int32_t M, cons
   return MIVI_OK;
 }
 
-mivi_status_t mivi_bnn_set_part_cap(mivi_ctx_t *c, int64_t bytes) {
-  if (!c || bytes < 0) return MIVI_ERR_BAD_ARG;
-  invalidate_graph(c);   // (a recorded graph holds the chunks of the cap it was recorded under)
-  c->bnn_cap = (size_t)bytes;
-  return MIVI_OK;
-}
+mivi_status_t mivi_bnn_set_part_cap(mivi_ctx_t *c, int64_t bytes) { return set_rows_cap(c, &mivi_ctx::bnn_rows, bytes); }

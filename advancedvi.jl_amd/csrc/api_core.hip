@@ -475,10 +475,7 @@ static void point_at_batch_copy(mivi_ctx *c, int64_t b, double likeadj) {
 
 mivi_status_t mivi_logreg_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t b, double likeadj) {
   if (!c || b < 0 || (b > 0 && !idx)) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_softmax(c, "mivi_logreg_select_rows (its rows are selected by mivi_softmax_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_logreg_select_rows (its rows are selected by mivi_bnn_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_logreg_select_rows (its rows are selected by mivi_hglm_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_logreg_select_rows (its rows are selected by mivi_ppca_select_rows)")) return rs;
+  if (mivi_status_t rs = refuse_rows_of_other_target(c, "mivi_logreg_select_rows", TGT_LOGREG)) return rs;
   if (c->target != TGT_LOGREG || !c->lr_X_full) return fail(c, MIVI_ERR_NO_TARGET, "no logistic-regression target set");
   (void)hipSetDevice(c->cfg.device);
   if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection -- rows or a schedule -- in force)
@@ -507,6 +504,36 @@ mivi_status_t mivi_logreg_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t
   return MIVI_OK;
 }
 
+// ---- the row selection of the targets of kTargets (RowSelection, mivi_internal.h): what their mivi_<t>_select_rows entries share ----
+// The entry has checked its target and likeadj.  b = 0: back to the full data set.  The indices are checked before anything changes (a
+// failed check leaves the previous selection in force); a failed upload leaves NO selection (a grown vector is a new one: the old is gone).
+mivi_status_t select_rows(mivi_ctx *c, RowSelection &rows, const int64_t *idx, int64_t b, double likeadj, bool no_repeats) {
+  std::vector<bool> seen(no_repeats && b > 0 ? (size_t)rows.n : 0, false);
+  for (int64_t j = 0; j < b; ++j) {
+    if (idx[j] < 0 || idx[j] >= rows.n) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
+    if (!no_repeats) continue;
+    if (seen[(size_t)idx[j]]) return fail(c, MIVI_ERR_BAD_ARG, "batch row index repeated (every row owns its latent z_r: a batch names it once)");
+    seen[(size_t)idx[j]] = true;
+  }
+  invalidate_graph(c);
+  mivi_status_t s = MIVI_OK;
+  if (b > 0) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the previous estimate may still be reading the index vector
+    s = upload(c, rows.idx, idx, (size_t)b * sizeof(int64_t));
+  }
+  rows.sel = b > 0 && s == MIVI_OK;
+  rows.nr = rows.sel ? b : rows.n;
+  rows.likeadj = rows.sel ? likeadj : rows.likeadj_full;
+  return s;
+}
+
+mivi_status_t set_rows_cap(mivi_ctx *c, RowSelection mivi_ctx::*rows, int64_t bytes) {
+  if (!c || bytes < 0) return MIVI_ERR_BAD_ARG;
+  invalidate_graph(c);   // (a recorded graph holds the chunks of the cap it was recorded under)
+  (c->*rows).cap = (size_t)bytes;
+  return MIVI_OK;
+}
+
 // ---- a schedule of minibatches resident on the device (include/mivi.h) ----
 // THE guard of every entry that reads the logistic regression's data set outside launch_logreg_target (the Hessian, measure-space, score,
 // partials / sharded / peer-to-peer and profile entries: refuse_non_gaussian reaches it for them): on a scheduled context the active
@@ -520,10 +547,7 @@ mivi_status_t refuse_batch_schedule(mivi_ctx *c, const char *entry) {
 mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *c, const mivi_batch_schedule_t *sp) {
   if (!c || !sp) return MIVI_ERR_BAD_ARG;
   if (mivi_status_t rs = refuse(c, LACKS_BATCH_SCHEDULE, "mivi_logreg_set_batch_schedule")) return rs;
-  if (mivi_status_t rs = refuse_softmax(c, "mivi_logreg_set_batch_schedule")) return rs;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_logreg_set_batch_schedule")) return rs;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_logreg_set_batch_schedule")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_logreg_set_batch_schedule")) return rs;
+  if (mivi_status_t rs = refuse_target(c, "mivi_logreg_set_batch_schedule")) return rs;
   if (c->target != TGT_LOGREG || !c->lr_X_full) return fail(c, MIVI_ERR_NO_TARGET, "no logistic-regression target set");
   const mivi_batch_schedule_t &sc = *sp;
   if (sc.n_batches < 0 || sc.kernels < 0 || sc.kernels > 2) return fail(c, MIVI_ERR_BAD_ARG, "batch schedule: n_batches >= 0 and kernels in 0 .. 2");
@@ -567,10 +591,7 @@ mivi_status_t mivi_logreg_set_batch_schedule(mivi_ctx_t *c, const mivi_batch_sch
 mivi_status_t mivi_logreg_seek_batch(mivi_ctx_t *c, int32_t k) {
   if (!c) return MIVI_ERR_BAD_ARG;
   if (mivi_status_t rs = refuse(c, LACKS_BATCH_SCHEDULE, "mivi_logreg_seek_batch")) return rs;
-  if (mivi_status_t rs = refuse_softmax(c, "mivi_logreg_seek_batch")) return rs;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_logreg_seek_batch")) return rs;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_logreg_seek_batch")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_logreg_seek_batch")) return rs;
+  if (mivi_status_t rs = refuse_target(c, "mivi_logreg_seek_batch")) return rs;
   if (c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "no batch schedule set (mivi_logreg_set_batch_schedule)");
   if (k < 0 || k >= c->lr_sched_n) return fail(c, MIVI_ERR_BAD_ARG, "batch index outside the schedule");
   invalidate_graph(c);

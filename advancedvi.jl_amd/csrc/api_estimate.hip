@@ -19,18 +19,6 @@ mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
     case TGT_LOGREG:
       if (!launch_logreg_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "logistic regression: scratch allocation failed");
       return MIVI_OK;
-    case TGT_SOFTMAX:
-      if (!launch_sm_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "softmax regression: scratch allocation failed");
-      return MIVI_OK;
-    case TGT_BNN:
-      if (!launch_bnn_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "Bayesian neural network: scratch allocation or the kernel's LDS size failed");
-      return MIVI_OK;
-    case TGT_HGLM:
-      if (!launch_hglm_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "hierarchical GLM: scratch allocation or the kernel's LDS size failed");
-      return MIVI_OK;
-    case TGT_PPCA:
-      if (!launch_ppca_target(c, M, want_grad)) return fail(c, MIVI_ERR_HIP, "probabilistic PCA: scratch allocation or the kernel's LDS size failed");
-      return MIVI_OK;
     case TGT_CALLBACK: {
       if (want_grad && !c->cb_grad) return fail(c, MIVI_ERR_UNSUPPORTED, kValueOnlyTarget);
       const size_t es = c->esize, d = c->cfg.d;
@@ -49,7 +37,8 @@ mivi_status_t eval_generic_target(mivi_ctx *c, int M, int want_grad) {
       if (want_grad) HIPCHK(c, hipMemcpyAsync(c->W.p, c->h_G.data(), d * M * es, hipMemcpyHostToDevice, c->stream));
       return MIVI_OK;
     }
-    default:
+    default:   // a target of kTargets, or none
+      if (const TargetRow *row = target_row(c)) return row->launch(c, M, want_grad) ? MIVI_OK : fail(c, MIVI_ERR_HIP, row->launch_failed);
       return fail(c, MIVI_ERR_NO_TARGET, "no target set");
   }
 }

@@ -1,6 +1,7 @@
 // libmivi C ABI, the hierarchical GLM target (include/mivi.h): mivi_set_target_hglm, the row selection mivi_hglm_select_rows
 // (AdvancedVI.subsample) and the partial planes' cap.  The target is a GENERIC one: eval_generic_target (api_estimate.hip) evaluates it on
-// explicit samples through launch_hglm_target (kernels_hglm.hip); the entries that cannot serve it are guarded by refuse_hglm (api_common.h).
+// explicit samples through launch_hglm_target (kernels_hglm.hip); the target is a row of kTargets (api_common.h), whose refuse_target guards
+// the entries that cannot serve it.
 // What is built here, on the host, is the ORDER the kernel walks the rows in: a stable ordering by group id, the segment table of the
 // groups and the first and last group of every row slice -- once per data set or selection.
 #include <cmath>
@@ -9,7 +10,7 @@
 
 static bool hglm_positive(double v) { return std::isfinite(v) && v > 0.0; }
 
-// The rows `idx[0 .. nr)` of the data set (idx == nullptr: all of them, nr = hg_n) in group order -> hg_rows, hg_grp, hg_gstart, hg_sltab
+// The rows `idx[0 .. nr)` of the data set (idx == nullptr: all of them, nr = hg_rows.n) in group order -> hg_rows.idx, hg_grp, hg_gstart, hg_sltab
 // and the lgamma constant.  A counting sort: stable, so repeats and the rows of a group keep the order they came in.
 static mivi_status_t hglm_install_rows(mivi_ctx *c, const int64_t *idx, int64_t nr) {
   const int J = c->hg.n_groups;
@@ -29,7 +30,7 @@ static mivi_status_t hglm_install_rows(mivi_ctx *c, const int64_t *idx, int64_t 
   }
   if (c->hg.likelihood == 1)   // (in the evaluated order: one fixed sum per data set or selection)
     for (int64_t j = 0; j < nr; ++j) lgam += c->hg_lg[idx ? idx[j] : j];
-  const mivi::HglmGeom geo = mivi::hglm_geom(nr);
+  const mivi::RowSlices geo = mivi::row_slices(nr, mivi::kHglmSliceRows, mivi::kHglmMaxSlices);
   std::vector<int32_t> sltab(2 * (size_t)geo.n_sl);
   for (int s = 0; s < geo.n_sl; ++s) {
     const int64_t rend = (s + 1) * geo.rps < nr ? (s + 1) * geo.rps : nr;
@@ -40,9 +41,9 @@ static mivi_status_t hglm_install_rows(mivi_ctx *c, const int64_t *idx, int64_t 
   if ((s = upload(c, c->hg_grp, grp.data(), (size_t)nr * sizeof(int32_t))) || (s = upload(c, c->hg_gstart, gstart.data(), ((size_t)J + 1) * sizeof(int64_t))) ||
       (s = upload(c, c->hg_sltab, sltab.data(), sltab.size() * sizeof(int32_t))))
     return s;
-  if (!stored_in_order && (s = upload(c, c->hg_rows, rows.data(), (size_t)nr * sizeof(int64_t)))) return s;
-  c->hg_rows_on = !stored_in_order;
-  c->hg_nr = nr;
+  if (!stored_in_order && (s = upload(c, c->hg_rows.idx, rows.data(), (size_t)nr * sizeof(int64_t)))) return s;
+  c->hg_rows.sel = !stored_in_order;
+  c->hg_rows.nr = nr;
   c->hg_lgam = lgam;
   return MIVI_OK;
 }
@@ -117,11 +118,10 @@ mivi_status_t mivi_set_target_hglm(mivi_ctx_t *c, const mivi_hglm_t *mp, const v
   }
   c->hg = m;
   c->hg_p = p;
-  c->hg_n = n;
+  c->hg_rows.set_full(n, m.likeadj);
   c->hg_group.assign(group, group + n);
   c->hg_pos.swap(pos);
   c->hg_lg.swap(lg);
-  c->hg_likeadj = m.likeadj;
   if (mivi_status_t st = hglm_install_rows(c, nullptr, n)) return st;
   c->lr_sched_n = c->lr_sched_k = 0;   // (a logistic regression's schedule of batches goes with its target)
   c->t_const = 0.0;
@@ -131,29 +131,22 @@ mivi_status_t mivi_set_target_hglm(mivi_ctx_t *c, const mivi_hglm_t *mp, const v
 
 mivi_status_t mivi_hglm_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t b, double likeadj) {
   if (!c || b < 0 || (b > 0 && !idx)) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_softmax(c, "mivi_hglm_select_rows (its rows are selected by mivi_softmax_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_hglm_select_rows (its rows are selected by mivi_bnn_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_hglm_select_rows (its rows are selected by mivi_ppca_select_rows)")) return rs;
+  if (mivi_status_t rs = refuse_rows_of_other_target(c, "mivi_hglm_select_rows", TGT_HGLM)) return rs;
   if (c->target != TGT_HGLM) return fail(c, MIVI_ERR_NO_TARGET, "no hierarchical GLM target set");
   (void)hipSetDevice(c->cfg.device);
   if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection in force)
     if (!hglm_positive(likeadj)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive and finite");
     for (int64_t j = 0; j < b; ++j)
-      if (idx[j] < 0 || idx[j] >= c->hg_n) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
+      if (idx[j] < 0 || idx[j] >= c->hg_rows.n) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
   }
   invalidate_graph(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));   // the previous estimate may still be reading the row order
-  if (mivi_status_t s = hglm_install_rows(c, b > 0 ? idx : nullptr, b > 0 ? b : c->hg_n)) {
+  if (mivi_status_t s = hglm_install_rows(c, b > 0 ? idx : nullptr, b > 0 ? b : c->hg_rows.n)) {
     c->target = TGT_NONE;   // (an upload failed half way: the row order on the device is no selection's)
     return s;
   }
-  c->hg_likeadj = b > 0 ? likeadj : c->hg.likeadj;
+  c->hg_rows.likeadj = b > 0 ? likeadj : c->hg_rows.likeadj_full;
   return MIVI_OK;
 }
 
-mivi_status_t mivi_hglm_set_part_cap(mivi_ctx_t *c, int64_t bytes) {
-  if (!c || bytes < 0) return MIVI_ERR_BAD_ARG;
-  invalidate_graph(c);   // (a recorded graph holds the chunks of the cap it was recorded under)
-  c->hg_cap = (size_t)bytes;
-  return MIVI_OK;
-}
+mivi_status_t mivi_hglm_set_part_cap(mivi_ctx_t *c, int64_t bytes) { return set_rows_cap(c, &mivi_ctx::hg_rows, bytes); }

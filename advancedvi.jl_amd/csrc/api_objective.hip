@@ -183,10 +183,7 @@ mivi_status_t mivi_gauss_expected_grad_hess2(mivi_ctx_t *c, const void *params, 
                                              void *logpi_avg, void *grad, void *hess) {
   if (!c || !params || !logpi_avg || !grad || !hess) return MIVI_ERR_BAD_ARG;
   if (mivi_status_t rs = refuse_non_gaussian(c, "mivi_gauss_expected_grad_hess2")) return rs;
-  if (mivi_status_t rs = refuse_softmax(c, "mivi_gauss_expected_grad_hess2 (second-order branch: the target has no Hessian kernel; use mivi_gauss_expected_grad_hess)")) return rs;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_gauss_expected_grad_hess2 (second-order branch: the target has no Hessian kernel; use mivi_gauss_expected_grad_hess)")) return rs;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_gauss_expected_grad_hess2 (second-order branch: the target has no Hessian kernel; use mivi_gauss_expected_grad_hess)")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_gauss_expected_grad_hess2 (second-order branch: the target has no Hessian kernel; use mivi_gauss_expected_grad_hess)")) return rs;
+  if (mivi_status_t rs = refuse_target(c, "mivi_gauss_expected_grad_hess2 (second-order branch: the target has no Hessian kernel; use mivi_gauss_expected_grad_hess)")) return rs;
   if (c->cfg.family != MIVI_FULLRANK)
     return fail(c, MIVI_ERR_UNSUPPORTED, "gauss_expected_grad_hess takes a triangular scale (full-rank family)");
   const bool sampled = target_has_hess2(c);   // logistic regression / funnel: the Hessian depends on z -- linear in per-sample statistics (kernels_hess2.hip)

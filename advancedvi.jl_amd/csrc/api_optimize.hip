@@ -277,10 +277,7 @@ mivi_status_t mivi_optimize_loop_many(mivi_ctx_t *c, void *params, const mivi_lo
   if (l.rule != 0 && !l.opt_state_dev) return fail(c, MIVI_ERR_BAD_ARG, "this optimisation rule needs opt_state_dev");
   if (l.averager == 1 && !l.avg_params_dev) return fail(c, MIVI_ERR_BAD_ARG, "PolynomialAveraging needs avg_params_dev");
   if (mivi_status_t rs = refuse(c, LACKS_LOOP_MANY, "mivi_optimize_loop_many (the family has no launch-free loop)")) return rs;
-  if (mivi_status_t rs = refuse_softmax(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
+  if (mivi_status_t rs = refuse_target(c, "mivi_optimize_loop_many (the target has no launch-free loop)")) return rs;
   if (c->base != MIVI_BASE_NORMAL) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a non-normal base distribution has no launch-free loop");
   if (c->bij_on) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a Stacked bijector is set");
   if (c->cfg.m_offset != 0 || c->M_total != c->cfg.n_mc) return fail(c, MIVI_ERR_UNSUPPORTED, "mivi_optimize_loop_many: a sharded context (m_offset / m_total)");
@@ -366,10 +363,7 @@ mivi_status_t mivi_optimize_loop_many(mivi_ctx_t *c, void *params, const mivi_lo
 mivi_status_t mivi_optimize_loop_batches(mivi_ctx_t *c, void *params, const mivi_loop_t *lp, int32_t first_batch) {
   if (!c || !params || !lp) return MIVI_ERR_BAD_ARG;
   if (mivi_status_t rs = refuse(c, LACKS_BATCH_SCHEDULE, "mivi_optimize_loop_batches")) return rs;
-  if (mivi_status_t rs = refuse_softmax(c, "mivi_optimize_loop_batches")) return rs;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_optimize_loop_batches")) return rs;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_optimize_loop_batches")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_optimize_loop_batches")) return rs;
+  if (mivi_status_t rs = refuse_target(c, "mivi_optimize_loop_batches")) return rs;
   if (c->target != TGT_LOGREG || c->lr_sched_n <= 0) return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_batches: no batch schedule set (mivi_logreg_set_batch_schedule)");
   if (first_batch < 0 || lp->n_steps <= 0 || (long long)first_batch + lp->n_steps > c->lr_sched_n)
     return fail(c, MIVI_ERR_BAD_ARG, "mivi_optimize_loop_batches: first_batch + n_steps must lie inside the schedule");

@@ -1,7 +1,7 @@
 // libmivi C ABI, the probabilistic PCA / Bayesian factor model target (include/mivi.h): mivi_set_target_ppca, the row selection
 // mivi_ppca_select_rows (AdvancedVI.subsample) and the partial planes' cap.  The target is a GENERIC one: eval_generic_target
-// (api_estimate.hip) evaluates it on explicit samples through launch_ppca_target (kernels_ppca.hip); the entries that cannot serve it are
-// guarded by refuse_ppca (api_common.h).
+// (api_estimate.hip) evaluates it on explicit samples through launch_ppca_target (kernels_ppca.hip); the target is a row of kTargets
+// (api_common.h), whose refuse_target guards the entries that cannot serve it.
 #include <cmath>
 
 #include "api_common.h"
@@ -44,9 +44,7 @@ mivi_status_t mivi_set_target_ppca(mivi_ctx_t *c, const mivi_ppca_t *mp, const v
   }
   c->pp = m;
   c->pp_D = D;
-  c->pp_n = c->pp_nr = n;
-  c->pp_sel = false;
-  c->pp_likeadj = m.likeadj;
+  c->pp_rows.set_full(n, m.likeadj);
   c->lr_sched_n = c->lr_sched_k = 0;   // (a logistic regression's schedule of batches goes with its target)
   c->t_const = 0.0;
   c->target = TGT_PPCA;
@@ -55,35 +53,11 @@ mivi_status_t mivi_set_target_ppca(mivi_ctx_t *c, const mivi_ppca_t *mp, const v
 
 mivi_status_t mivi_ppca_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t b, double likeadj) {
   if (!c || b < 0 || (b > 0 && !idx)) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_softmax(c, "mivi_ppca_select_rows (its rows are selected by mivi_softmax_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_ppca_select_rows (its rows are selected by mivi_bnn_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_ppca_select_rows (its rows are selected by mivi_hglm_select_rows)")) return rs;
+  if (mivi_status_t rs = refuse_rows_of_other_target(c, "mivi_ppca_select_rows", TGT_PPCA)) return rs;
   if (c->target != TGT_PPCA) return fail(c, MIVI_ERR_NO_TARGET, "no probabilistic PCA target set");
   (void)hipSetDevice(c->cfg.device);
-  if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection in force)
-    if (!ppca_positive(likeadj)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive and finite");
-    std::vector<bool> seen((size_t)c->pp_n, false);
-    for (int64_t j = 0; j < b; ++j) {
-      if (idx[j] < 0 || idx[j] >= c->pp_n) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
-      if (seen[(size_t)idx[j]]) return fail(c, MIVI_ERR_BAD_ARG, "batch row index repeated (every row owns its latent z_r: a batch names it once)");
-      seen[(size_t)idx[j]] = true;
-    }
-  }
-  invalidate_graph(c);
-  mivi_status_t s = MIVI_OK;
-  if (b > 0) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the previous estimate may still be reading the index vector
-    s = upload(c, c->pp_idx, idx, (size_t)b * sizeof(int64_t));   // (a grown vector is a new one: on failure the old selection is gone)
-  }
-  c->pp_sel = b > 0 && s == MIVI_OK;
-  c->pp_nr = c->pp_sel ? b : c->pp_n;
-  c->pp_likeadj = c->pp_sel ? likeadj : c->pp.likeadj;
-  return s;
+  if (b > 0 && !ppca_positive(likeadj)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive and finite");
+  return select_rows(c, c->pp_rows, idx, b, likeadj, true);   // (every row owns its latent z_r: no repeats)
 }
 
-mivi_status_t mivi_ppca_set_part_cap(mivi_ctx_t *c, int64_t bytes) {
-  if (!c || bytes < 0) return MIVI_ERR_BAD_ARG;
-  invalidate_graph(c);   // (a recorded graph holds the chunks of the cap it was recorded under)
-  c->pp_cap = (size_t)bytes;
-  return MIVI_OK;
-}
+mivi_status_t mivi_ppca_set_part_cap(mivi_ctx_t *c, int64_t bytes) { return set_rows_cap(c, &mivi_ctx::pp_rows, bytes); }

@@ -1,7 +1,7 @@
 // libmivi C ABI, the softmax (multinomial logistic) regression target (include/mivi.h): mivi_set_target_softmax, the row selection
 // mivi_softmax_select_rows (AdvancedVI.subsample) and the residual plane's cap.  The target is a GENERIC one: eval_generic_target
 // (api_estimate.hip) evaluates it on explicit samples through launch_sm_target (kernels_softmax.hip), so every route that serves a callback
-// target by explicit samples serves it, on the device; the entries that cannot are guarded by refuse_softmax (api_common.h).
+// target by explicit samples serves it, on the device; the target is a row of kTargets (api_common.h), whose refuse_target guards the entries that cannot.
 #include "api_common.h"
 
 mivi_status_t mivi_set_target_softmax(mivi_ctx_t *c, const void *X, const uint8_t *y, int64_t n, int32_t n_classes, int32_t variant,
@@ -31,11 +31,9 @@ mivi_status_t mivi_set_target_softmax(mivi_ctx_t *c, const void *X, const uint8_
     c->sm_X = c->sm_X_own.p;
     c->sm_y = (const uint8_t *)c->sm_y_own.p;
   }
-  c->sm_n = c->sm_nr = n;
-  c->sm_sel = false;
+  c->sm_rows.set_full(n, likeadj);
   c->sm_C = n_classes;
   c->sm_variant = variant;
-  c->sm_likeadj = c->sm_likeadj_full = likeadj;
   c->lr_sched_n = c->lr_sched_k = 0;   // (a logistic regression's schedule of batches goes with its target)
   c->t_const = 0.0;
   c->target = TGT_SOFTMAX;
@@ -44,39 +42,11 @@ mivi_status_t mivi_set_target_softmax(mivi_ctx_t *c, const void *X, const uint8_
 
 mivi_status_t mivi_softmax_select_rows(mivi_ctx_t *c, const int64_t *idx, int64_t b, double likeadj) {
   if (!c || b < 0 || (b > 0 && !idx)) return MIVI_ERR_BAD_ARG;
-  if (mivi_status_t rs = refuse_bnn(c, "mivi_softmax_select_rows (its rows are selected by mivi_bnn_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_hglm(c, "mivi_softmax_select_rows (its rows are selected by mivi_hglm_select_rows)")) return rs;
-  if (mivi_status_t rs = refuse_ppca(c, "mivi_softmax_select_rows (its rows are selected by mivi_ppca_select_rows)")) return rs;
+  if (mivi_status_t rs = refuse_rows_of_other_target(c, "mivi_softmax_select_rows", TGT_SOFTMAX)) return rs;
   if (c->target != TGT_SOFTMAX) return fail(c, MIVI_ERR_NO_TARGET, "no softmax regression target set");
   (void)hipSetDevice(c->cfg.device);
-  if (b > 0) {   // (checked before anything changes: a failed call leaves the previous selection in force)
-    if (!(likeadj > 0.0)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive");
-    for (int64_t j = 0; j < b; ++j)
-      if (idx[j] < 0 || idx[j] >= c->sm_n) return fail(c, MIVI_ERR_BAD_ARG, "batch row index out of range");
-  }
-  invalidate_graph(c);
-  if (b == 0) {   // back to the full data set
-    c->sm_sel = false;
-    c->sm_nr = c->sm_n;
-    c->sm_likeadj = c->sm_likeadj_full;
-    return MIVI_OK;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // the previous estimate may still be reading the index vector
-  if (mivi_status_t s = upload(c, c->sm_idx, idx, (size_t)b * sizeof(int64_t))) {   // (a grown vector is a new one: the old selection is gone)
-    c->sm_sel = false;
-    c->sm_nr = c->sm_n;
-    c->sm_likeadj = c->sm_likeadj_full;
-    return s;
-  }
-  c->sm_sel = true;
-  c->sm_nr = b;
-  c->sm_likeadj = likeadj;
-  return MIVI_OK;
+  if (b > 0 && !(likeadj > 0.0)) return fail(c, MIVI_ERR_BAD_ARG, "likelihood adjustment must be positive");
+  return select_rows(c, c->sm_rows, idx, b, likeadj, false);
 }
 
-mivi_status_t mivi_softmax_set_plane_cap(mivi_ctx_t *c, int64_t bytes) {
-  if (!c || bytes < 0) return MIVI_ERR_BAD_ARG;
-  invalidate_graph(c);   // (a recorded graph holds the chunks of the cap it was recorded under)
-  c->sm_cap = (size_t)bytes;
-  return MIVI_OK;
-}
+mivi_status_t mivi_softmax_set_plane_cap(mivi_ctx_t *c, int64_t bytes) { return set_rows_cap(c, &mivi_ctx::sm_rows, bytes); }

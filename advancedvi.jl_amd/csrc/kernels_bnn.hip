@@ -343,27 +343,16 @@ static BnnNet bnn_net(const mivi_ctx *c) {
   return nt;
 }
 
-struct BnnGeom {
-  int n_sl, Mc;
-  long long rps;
-};
-static BnnGeom bnn_geom(const mivi_ctx *c, long long nr, int M) {
-  BnnGeom g;
-  long long ns = (nr + kBnnSliceRows - 1) / kBnnSliceRows;
-  ns = ns < 1 ? 1 : (ns > 32 ? 32 : ns);
-  g.rps = ((nr + ns - 1) / ns + kFlowTile - 1) / kFlowTile * kFlowTile;
-  g.n_sl = (int)((nr + g.rps - 1) / g.rps);
-  const size_t cap = c->bnn_cap ? c->bnn_cap : kBnnPartCap;
-  size_t mc = cap / ((size_t)g.n_sl * c->cfg.d * sizeof(double));
-  if (mc > (size_t)M) mc = (size_t)M;
-  g.Mc = mc < 1 ? 1 : (int)mc;
-  return g;
+static RowSlices bnn_slices(long long nr) { return row_slices(nr, kBnnSliceRows, 32); }
+static int bnn_chunk(const mivi_ctx *c, const RowSlices &g, int M) {   // samples per chunk under the cap
+  return samples_under_cap(c->bnn_rows.cap ? c->bnn_rows.cap : kBnnPartCap, (size_t)g.n_sl * c->cfg.d * sizeof(double), M);
 }
 
 bool bnn_reserve(mivi_ctx *c, int M) {
-  const BnnGeom g = bnn_geom(c, c->bnn_nr, M);
-  return !ensure(c, c->bnn_part, (size_t)g.n_sl * g.Mc * c->cfg.d * sizeof(double), false) &&
-         !ensure(c, c->bnn_ll, (size_t)g.n_sl * g.Mc * sizeof(double), false);
+  const RowSlices g = bnn_slices(c->bnn_rows.nr);
+  const size_t mc = (size_t)bnn_chunk(c, g, M);
+  return !ensure(c, c->bnn_part, (size_t)g.n_sl * mc * c->cfg.d * sizeof(double), false) &&
+         !ensure(c, c->bnn_ll, (size_t)g.n_sl * mc * sizeof(double), false);
 }
 
 template <typename T>
@@ -378,14 +367,15 @@ static BnnArgs<T> bnn_args(const mivi_ctx *c) {
 
 template <typename T>
 static bool bnn_impl(mivi_ctx *c, int M, int want_grad) {
-  const BnnGeom g = bnn_geom(c, c->bnn_nr, M);
+  const RowSlices g = bnn_slices(c->bnn_rows.nr);
+  const int Mc = bnn_chunk(c, g, M);
   BnnArgs<T> a = bnn_args<T>(c);
   if (!flow_lds_attr<T>(k_bnn_rows<T>, a.net.lds_elems)) return false;
-  a.n = c->bnn_n;
-  a.nr = c->bnn_nr;
+  a.n = c->bnn_rows.n;
+  a.nr = c->bnn_rows.nr;
   a.X = (const T *)c->bnn_X;
   a.y = (const T *)c->bnn_y;
-  a.rows = c->bnn_sel ? (const long long *)c->bnn_idx.p : nullptr;
+  a.rows = c->bnn_rows.sel ? (const long long *)c->bnn_rows.idx.p : nullptr;
   a.Z = (const T *)c->Z.p;
   a.part = (double *)c->bnn_part.p;
   a.llp = (double *)c->bnn_ll.p;
@@ -394,11 +384,11 @@ static bool bnn_impl(mivi_ctx *c, int M, int want_grad) {
   a.G = (T *)c->W.p;
   a.ell = (T *)c->ell.p;
   a.want_grad = want_grad;
-  a.likeadj = c->bnn_likeadj;
+  a.likeadj = c->bnn_rows.likeadj;
   const size_t lds = (size_t)a.net.lds_elems * sizeof(T);
-  for (int m0 = 0; m0 < M; m0 += g.Mc) {   // chunks of samples: the f64 partials stay under their cap
+  for (int m0 = 0; m0 < M; m0 += Mc) {   // chunks of samples: the f64 partials stay under their cap
     a.m0 = m0;
-    a.M = M - m0 < g.Mc ? M - m0 : g.Mc;
+    a.M = M - m0 < Mc ? M - m0 : Mc;
     hipLaunchKernelGGL(k_bnn_rows<T>, dim3(a.M, g.n_sl), dim3(256), lds, c->stream, a);
     hipLaunchKernelGGL(k_bnn_finish<T>, dim3(a.M), dim3(256), 0, c->stream, a);
   }
@@ -413,7 +403,7 @@ bool launch_bnn_target(mivi_ctx *c, int M, int want_grad) {
 
 template <typename T>
 static bool bnn_forward_impl(mivi_ctx *c, const void *theta, int M, const void *Xnew, long long n_new, void *f) {
-  const BnnGeom g = bnn_geom(c, n_new, M);
+  const RowSlices g = bnn_slices(n_new);
   BnnArgs<T> a = bnn_args<T>(c);
   if (!flow_lds_attr<T>(k_bnn_forward<T>, a.net.lds_elems)) return false;
   a.n = a.nr = n_new;

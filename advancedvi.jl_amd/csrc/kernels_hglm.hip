@@ -247,25 +247,12 @@ __global__ __launch_bounds__(256) void k_hglm_finish(HglmArgs<T> a) {
 }
 
 // ---- the launches' geometry: a function of the evaluated rows, p, the precision and the cap alone --------------------------------------
-HglmGeom hglm_geom(long long nr) {
-  HglmGeom g;
-  long long ns = (nr + kHglmSliceRows - 1) / kHglmSliceRows;
-  ns = ns < 1 ? 1 : (ns > kHglmMaxSlices ? kHglmMaxSlices : ns);
-  g.rps = ((nr + ns - 1) / ns + kFlowTile - 1) / kFlowTile * kFlowTile;
-  g.n_sl = (int)((nr + g.rps - 1) / g.rps);
-  return g;
-}
-
-static int hglm_chunk(const mivi_ctx *c, const HglmGeom &g, int M) {   // samples per chunk under the cap
-  const size_t cap = c->hg_cap ? c->hg_cap : kHglmPartCap;
-  const size_t per = ((size_t)g.n_sl * (c->hg_p + 3) + (size_t)c->hg.n_groups) * sizeof(double);
-  size_t mc = cap / per;
-  if (mc > (size_t)M) mc = (size_t)M;
-  return mc < 1 ? 1 : (int)mc;
+static int hglm_chunk(const mivi_ctx *c, const RowSlices &g, int M) {   // samples per chunk under the cap
+  return samples_under_cap(c->hg_rows.cap ? c->hg_rows.cap : kHglmPartCap, ((size_t)g.n_sl * (c->hg_p + 3) + (size_t)c->hg.n_groups) * sizeof(double), M);
 }
 
 bool hglm_reserve(mivi_ctx *c, int M) {
-  const HglmGeom g = hglm_geom(c->hg_nr);
+  const RowSlices g = row_slices(c->hg_rows.nr, kHglmSliceRows, kHglmMaxSlices);
   const size_t mc = (size_t)hglm_chunk(c, g, M), D = sizeof(double);
   return !ensure(c, c->hg_bpart, (size_t)g.n_sl * mc * c->hg_p * D, false) && !ensure(c, c->hg_gplane, (size_t)c->hg.n_groups * mc * D, false) &&
          !ensure(c, c->hg_edge, (size_t)g.n_sl * 2 * mc * D, false) && !ensure(c, c->hg_ll, (size_t)g.n_sl * mc * D, false);
@@ -290,19 +277,19 @@ static bool hglm_rows_launch(mivi_ctx *c, const HglmArgs<T> &a, int n_sl) {
 
 template <typename T>
 static bool hglm_impl(mivi_ctx *c, int M, int want_grad) {
-  const HglmGeom g = hglm_geom(c->hg_nr);
+  const RowSlices g = row_slices(c->hg_rows.nr, kHglmSliceRows, kHglmMaxSlices);
   const int Mc = hglm_chunk(c, g, M);
   HglmArgs<T> a{};
   a.p = c->hg_p;
   a.P = (a.p + 15) & ~15;
   a.J = c->hg.n_groups;
   a.d = c->cfg.d;
-  a.n = c->hg_n;
-  a.nr = c->hg_nr;
+  a.n = c->hg_rows.n;
+  a.nr = c->hg_rows.nr;
   a.X = (const T *)c->hg_X;
   a.y = (const T *)c->hg_y;
   a.off = (const T *)c->hg_off;
-  a.rows = c->hg_rows_on ? (const long long *)c->hg_rows.p : nullptr;
+  a.rows = c->hg_rows.sel ? (const long long *)c->hg_rows.idx.p : nullptr;
   a.grp = (const int *)c->hg_grp.p;
   a.gstart = (const long long *)c->hg_gstart.p;
   a.sltab = (const int *)c->hg_sltab.p;
@@ -319,7 +306,7 @@ static bool hglm_impl(mivi_ctx *c, int M, int want_grad) {
   a.want_grad = want_grad;
   a.prior_std = c->hg.prior_std;
   a.tau_scale = c->hg.tau_scale;
-  a.likeadj = c->hg_likeadj;
+  a.likeadj = c->hg_rows.likeadj;
   a.lgam = c->hg_lgam;
   const int nt = a.P / 16;
   for (int m0 = 0; m0 < M; m0 += Mc) {   // chunks of samples: the f64 partials stay under their cap

@@ -311,15 +311,15 @@ __global__ __launch_bounds__(256) void k_ppca_finish(PpcaArgs<T> a) {
 // ---- the launches' geometry: a function of the evaluated rows, D, k and the precision alone ---------------------------------------------
 static long long ppca_plen(const mivi_ctx *c) { return (long long)c->pp_D * c->pp.k + c->pp_D + 3; }
 
-static int ppca_chunk(const mivi_ctx *c, const HglmGeom &g, int M) {   // samples per chunk under the cap
-  const size_t cap = c->pp_cap ? c->pp_cap : kPpcaPartCap;
-  size_t mc = cap / ((size_t)g.n_sl * ppca_plen(c) * sizeof(double));
-  if (mc > (size_t)M) mc = (size_t)M;
-  return mc < 1 ? 1 : (int)mc;
+static RowSlices ppca_slices(const mivi_ctx *c) {   // (the row slices of the hierarchical GLM target: 256 rows, at most 1024 slices)
+  return row_slices(c->pp_rows.nr, kHglmSliceRows, kHglmMaxSlices);
+}
+static int ppca_chunk(const mivi_ctx *c, const RowSlices &g, int M) {   // samples per chunk under the cap
+  return samples_under_cap(c->pp_rows.cap ? c->pp_rows.cap : kPpcaPartCap, (size_t)g.n_sl * ppca_plen(c) * sizeof(double), M);
 }
 
 bool ppca_reserve(mivi_ctx *c, int M) {
-  const HglmGeom g = hglm_geom(c->pp_nr);   // (the row slices of the hierarchical GLM target: 256 rows, at most 1024 slices)
+  const RowSlices g = ppca_slices(c);
   return !ensure(c, c->pp_part, (size_t)g.n_sl * ppca_chunk(c, g, M) * ppca_plen(c) * sizeof(double), false);
 }
 
@@ -341,18 +341,18 @@ static bool ppca_rows_nc(mivi_ctx *c, const PpcaArgs<T> &a, int waves) {
 
 template <typename T>
 static bool ppca_impl(mivi_ctx *c, int M, int want_grad) {
-  const HglmGeom g = hglm_geom(c->pp_nr);
+  const RowSlices g = ppca_slices(c);
   const int Mc = ppca_chunk(c, g, M);
   PpcaArgs<T> a{};
   a.D = c->pp_D;
   a.k = c->pp.k;
   a.d = c->cfg.d;
   a.ldw = ((a.D + 63) & ~63) + 17;   // (the forward product reads 16 consecutive columns of 4 rows, dZ's 4 consecutive columns of 16 rows)
-  a.n = c->pp_n;
-  a.nr = c->pp_nr;
+  a.n = c->pp_rows.n;
+  a.nr = c->pp_rows.nr;
   a.Y = (const T *)c->pp_Y;
   a.mask = (const unsigned char *)c->pp_mask;
-  a.rows = c->pp_sel ? (const long long *)c->pp_idx.p : nullptr;
+  a.rows = c->pp_rows.sel ? (const long long *)c->pp_rows.idx.p : nullptr;
   a.Z = (const T *)c->Z.p;
   a.part = (double *)c->pp_part.p;
   a.plen = ppca_plen(c);
@@ -365,7 +365,7 @@ static bool ppca_impl(mivi_ctx *c, int M, int want_grad) {
   a.prior_std = c->pp.prior_std;
   a.mean_std = c->pp.mean_std;
   a.noise_scale = c->pp.noise_scale;
-  a.likeadj = c->pp_likeadj;
+  a.likeadj = c->pp_rows.likeadj;
   const int nblk = (a.D + 15) / 16, waves = nblk < 4 ? nblk : 4, nb = (nblk + waves - 1) / waves;   // nb <= 8 at D <= 512
   const size_t nz = (size_t)a.n * a.k;
   for (int m0 = 0; m0 < M; m0 += Mc) {   // chunks of samples: the f64 partials stay under their cap

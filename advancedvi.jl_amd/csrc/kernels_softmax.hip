@@ -245,13 +245,13 @@ static SmGeom sm_geom(const mivi_ctx *c, int M) {
   g.p = (c->cfg.d - 1) / g.C;
   g.CT = (g.C + 15) / 16;
   g.SG = 4 / g.CT;
-  const long long nr = c->sm_nr;
+  const long long nr = c->sm_rows.nr;
   g.n_rt = (int)((nr + 63) / 64);
   long long ns = (nr + 127) / 128;
   ns = ns < 1 ? 1 : (ns > 32 ? 32 : ns);
   g.rps = ((nr + ns - 1) / ns + kSmKC - 1) / kSmKC * kSmKC;
   g.n_sl = (int)((nr + g.rps - 1) / g.rps);
-  const size_t cap = c->sm_cap ? c->sm_cap : kSmPlaneCap;
+  const size_t cap = c->sm_rows.cap ? c->sm_rows.cap : kSmPlaneCap;
   const size_t by_R = cap / ((size_t)nr * g.C * c->esize), by_P = kSmPartCap / ((size_t)g.n_sl * g.p * g.C * sizeof(double));
   size_t mc = by_R < by_P ? by_R : by_P;
   if (mc > (size_t)M) mc = (size_t)M;
@@ -264,7 +264,7 @@ int sm_chunk_samples(const mivi_ctx *c, int M) { return sm_geom(c, M).Mc; }
 bool sm_reserve(mivi_ctx *c, int M) {
   const SmGeom g = sm_geom(c, M);
   const size_t pC = (size_t)g.p * g.C;
-  return !ensure(c, c->sm_R, (size_t)c->sm_nr * g.Mc * g.C * c->esize, false) &&
+  return !ensure(c, c->sm_R, (size_t)c->sm_rows.nr * g.Mc * g.C * c->esize, false) &&
          !ensure(c, c->sm_part, (size_t)g.n_sl * g.Mc * pC * sizeof(double), false) &&
          !ensure(c, c->sm_ell, (size_t)g.n_rt * g.Mc * sizeof(double), false);
 }
@@ -278,11 +278,11 @@ static bool sm_impl(mivi_ctx *c, int M, int want_grad) {
   a.C = g.C;
   a.CT = g.CT;
   a.SG = g.SG;
-  a.n = c->sm_n;
-  a.nr = c->sm_nr;
+  a.n = c->sm_rows.n;
+  a.nr = c->sm_rows.nr;
   a.X = (const T *)c->sm_X;
   a.y = c->sm_y;
-  a.rows = c->sm_sel ? (const long long *)c->sm_idx.p : nullptr;
+  a.rows = c->sm_rows.sel ? (const long long *)c->sm_rows.idx.p : nullptr;
   a.Z = (const T *)c->Z.p;
   a.R = (T *)c->sm_R.p;
   a.ldR = (long long)g.Mc * g.C;
@@ -294,7 +294,7 @@ static bool sm_impl(mivi_ctx *c, int M, int want_grad) {
   a.ell = (T *)c->ell.p;
   a.variant = c->sm_variant;
   a.want_grad = want_grad;
-  a.likeadj = c->sm_likeadj;
+  a.likeadj = c->sm_rows.likeadj;
   for (int m0 = 0; m0 < M; m0 += g.Mc) {   // chunks of samples: the residual plane and the partials stay under their caps
     a.m0 = m0;
     a.M = M - m0 < g.Mc ? M - m0 : g.Mc;

@@ -429,6 +429,21 @@ struct LaneRecorder {
   }
 };
 
+// The rows of a resident data set that a target of kTargets (api_common.h) evaluates: all n of them, or the selection of its
+// mivi_<t>_select_rows (AdvancedVI.subsample), which is the index vector idx that the kernels read the rows THROUGH -- no gathered copy.
+struct RowSelection {
+  DevBuf idx;
+  int64_t n = 0, nr = 0;                       // rows of the data set; rows evaluated (= n without a selection)
+  bool sel = false;                            // the kernels read their rows through idx
+  double likeadj = 1.0, likeadj_full = 1.0;    // the likelihood adjustment in force; the full data set's
+  size_t cap = 0;                              // byte cap of the target's scratch planes (0: the target's default; mivi_<t>_set_*_cap)
+  void set_full(int64_t rows, double adj) {    // a new data set: every row, no selection
+    n = nr = rows;
+    sel = false;
+    likeadj = likeadj_full = adj;
+  }
+};
+
 }  // namespace mivi
 
 // The streams and events a context created, every one in its owner.  A base of mivi_ctx, so that they are destroyed AFTER the context's
@@ -522,56 +537,44 @@ struct mivi_ctx : mivi_ctx_streams {
   bool lr_sched_has_idx = false;
   int lr_loop_first = -1;                  // >= 0 while mivi_optimize_loop_batches runs: step t of the loop evaluates batch lr_loop_first + t
   // softmax regression (api_softmax.hip, kernels_softmax.hip): theta = [vec B (p x C); s].  The data set stays resident; a row selection
-  // (mivi_softmax_select_rows) is the index vector sm_idx, which the kernels read the rows THROUGH -- no gathered copy of X.
-  // sm_R: the residual plane Y - P of one chunk of samples; sm_part: the f64 partials of X'R per row slice; sm_ell: those of the
-  // log-likelihood per (row tile, sample).  sm_cap: the byte cap of sm_R (0: kSmPlaneCap; mivi_softmax_set_plane_cap)
+  // (mivi_softmax_select_rows) is sm_rows.  sm_R: the residual plane Y - P of one chunk of samples; sm_part: the f64 partials of X'R per
+  // row slice; sm_ell: those of the log-likelihood per (row tile, sample).  sm_rows.cap: the byte cap of sm_R (0: kSmPlaneCap)
   const void *sm_X = nullptr;
   const uint8_t *sm_y = nullptr;
-  mivi::DevBuf sm_X_own, sm_y_own, sm_idx, sm_R, sm_part, sm_ell;
-  int64_t sm_n = 0, sm_nr = 0;             // rows of the data set; rows of the selection (= sm_n without one)
-  bool sm_sel = false;                     // a row selection is in force
+  mivi::DevBuf sm_X_own, sm_y_own, sm_R, sm_part, sm_ell;
+  mivi::RowSelection sm_rows;
   int sm_C = 0, sm_variant = 0;
-  double sm_likeadj = 1.0, sm_likeadj_full = 1.0;
-  size_t sm_cap = 0;
   // Bayesian neural network (api_bnn.hip, kernels_bnn.hip): theta = [vec W_1; b_1; ...; vec W_{H+1}; b_{H+1}].  The data set stays resident; a
-  // row selection (mivi_bnn_select_rows) is the index vector bnn_idx, which the kernel reads the rows THROUGH.  bnn_part: the f64 partial
-  // gradients per (row slice, sample of a chunk); bnn_ll: those of the log-likelihood.  bnn_cap: the byte cap of bnn_part (0: kBnnPartCap)
+  // row selection (mivi_bnn_select_rows) is bnn_rows.  bnn_part: the f64 partial gradients per (row slice, sample of a chunk); bnn_ll:
+  // those of the log-likelihood.  bnn_rows.cap: the byte cap of bnn_part (0: kBnnPartCap)
   mivi_bnn_t bnn = {};
   const void *bnn_X = nullptr, *bnn_y = nullptr;
-  mivi::DevBuf bnn_X_own, bnn_y_own, bnn_idx, bnn_part, bnn_ll;
-  int64_t bnn_n = 0, bnn_nr = 0;           // rows of the data set; rows of the selection (= bnn_n without one)
-  bool bnn_sel = false;                    // a row selection is in force
+  mivi::DevBuf bnn_X_own, bnn_y_own, bnn_part, bnn_ll;
+  mivi::RowSelection bnn_rows;
   int bnn_p = 0;
-  double bnn_likeadj = 1.0;                // the likeadj in force (bnn.likeadj: the full data set's)
-  size_t bnn_cap = 0;
   // hierarchical GLM (api_hglm.hip, kernels_hglm.hip): theta = [beta (p); u (J); s].  The rows are evaluated in GROUP order: host data is
-  // stored in that order (hg_rows_on = false for the full set), borrowed device data and every row selection are read THROUGH hg_rows.
+  // stored in that order (hg_rows.sel = false for the full set), borrowed device data and every row selection are read THROUGH hg_rows.idx.
   // hg_grp: the group of every evaluated row, hg_gstart: the segment table (J + 1), hg_sltab: first and last group of every row slice.
   // hg_group / hg_pos / hg_lg (host): every row's group, its place in the stored data (empty: its own index) and lgamma(y + 1) (Poisson).
   // hg_bpart [slice][sample][p], hg_gplane [J][sample], hg_edge [slice][2][sample], hg_ll [slice][sample]: the f64 partials of a chunk
   mivi_hglm_t hg = {};
   const void *hg_X = nullptr, *hg_y = nullptr, *hg_off = nullptr;
-  mivi::DevBuf hg_X_own, hg_y_own, hg_off_own, hg_rows, hg_grp, hg_gstart, hg_sltab, hg_bpart, hg_gplane, hg_edge, hg_ll;
+  mivi::DevBuf hg_X_own, hg_y_own, hg_off_own, hg_grp, hg_gstart, hg_sltab, hg_bpart, hg_gplane, hg_edge, hg_ll;
   std::vector<int32_t> hg_group;
   std::vector<int64_t> hg_pos;
   std::vector<double> hg_lg;
-  int64_t hg_n = 0, hg_nr = 0;             // rows of the data set; rows evaluated (= hg_n without a selection)
-  bool hg_rows_on = false;                 // the kernel reads its rows through hg_rows
+  mivi::RowSelection hg_rows;              // (idx: the evaluated rows in group order, built by api_hglm.hip; cap: of the partial planes, 0: kHglmPartCap)
   int hg_p = 0;
-  double hg_likeadj = 1.0, hg_lgam = 0.0;  // the likeadj in force (hg.likeadj: the full data set's); sum lgamma(y_r + 1) over the evaluated rows
-  size_t hg_cap = 0;
+  double hg_lgam = 0.0;                    // sum lgamma(y_r + 1) over the evaluated rows
   // probabilistic PCA (api_ppca.hip, kernels_ppca.hip): theta = [vec W (D x k); Z (k x N); mu (D); a (k, ARD); s].  pp_Y: N x D column-major,
   // pp_mask: uint8 in the same layout or nullptr (all observed); own copies of host data, borrowed device data.  A row selection
-  // (mivi_ppca_select_rows, no repeats) is the index vector pp_idx, which the kernel reads the rows THROUGH; z_r keeps its original row id.
-  // pp_part: the f64 partials per (row slice, sample of a chunk); pp_cap: its byte cap (0: kPpcaPartCap)
+  // (mivi_ppca_select_rows, no repeats) is pp_rows; z_r keeps its original row id.
+  // pp_part: the f64 partials per (row slice, sample of a chunk); pp_rows.cap: its byte cap (0: kPpcaPartCap)
   mivi_ppca_t pp = {};
   const void *pp_Y = nullptr, *pp_mask = nullptr;
-  mivi::DevBuf pp_Y_own, pp_mask_own, pp_idx, pp_part;
-  int64_t pp_n = 0, pp_nr = 0;             // rows of the data set; rows of the selection (= pp_n without one)
-  bool pp_sel = false;                     // a row selection is in force
+  mivi::DevBuf pp_Y_own, pp_mask_own, pp_part;
+  mivi::RowSelection pp_rows;
   int pp_D = 0;
-  double pp_likeadj = 1.0;                 // the likeadj in force (pp.likeadj: the full data set's)
-  size_t pp_cap = 0;
   // callback
   mivi_logdensity_and_gradient_fn cb_grad = nullptr;
   mivi_logdensity_fn cb_value = nullptr;
@@ -849,6 +852,23 @@ bool logreg_uses_mfma(const mivi_ctx *c, int M);          // the matrix-core rou
 bool logreg_reserve(mivi_ctx *c, int M);                        // size the scratch ahead of a graph capture
 bool logreg_prepare_f32(mivi_ctx *c);   // row-major padded copy of X for the MFMA route (false: allocation failed)
 
+// The launch geometry the Bayesian neural network, hierarchical GLM and probabilistic PCA targets share.  row_slices: `nr` evaluated rows
+// as ceil(nr / slice_rows) slices, clamped to 1 .. max_slices, of rps rows each (a multiple of the kernels' 16-row tile): a function of the
+// evaluated rows alone.  samples_under_cap: the samples of a chunk whose scratch, bytes_per_sample each, stays under cap: 1 .. M
+struct RowSlices { int n_sl; long long rps; };
+inline RowSlices row_slices(long long nr, int slice_rows, int max_slices) {
+  long long ns = (nr + slice_rows - 1) / slice_rows;
+  ns = ns < 1 ? 1 : (ns > max_slices ? max_slices : ns);
+  RowSlices g;
+  g.rps = ((nr + ns - 1) / ns + 15) / 16 * 16;
+  g.n_sl = (int)((nr + g.rps - 1) / g.rps);
+  return g;
+}
+inline int samples_under_cap(size_t cap, size_t bytes_per_sample, int M) {
+  const size_t mc = cap / bytes_per_sample;
+  return mc > (size_t)M ? M : mc < 1 ? 1 : (int)mc;
+}
+
 // kernels_softmax.hip: the softmax regression target (api_softmax.hip sets it; eval_generic_target evaluates it)
 constexpr size_t kSmPlaneCap = 64u << 20;          // bytes of the residual plane a chunk of samples may take (at least one sample per chunk)
 constexpr size_t kSmPartCap = 128u << 20;          // ... and of the f64 partials of X'R
@@ -866,12 +886,10 @@ bool launch_bnn_forward(mivi_ctx *c, const void *theta, int M, const void *Xnew,
 constexpr size_t kHglmPartCap = 256u << 20;        // bytes of the f64 partial planes a chunk of samples may take (at least one sample per chunk)
 constexpr long long kHglmSliceRows = 256;          // rows a slice aims at; slices: ceil(rows / 256) clamped to 1 .. kHglmMaxSlices
 constexpr long long kHglmMaxSlices = 1024;
-struct HglmGeom { int n_sl; long long rps; };      // row slices and rows per slice (a multiple of 16): a function of the evaluated rows alone
-HglmGeom hglm_geom(long long nr);
 bool hglm_reserve(mivi_ctx *c, int M);             // size the partial planes for M samples per estimate (ahead of a graph capture)
 bool launch_hglm_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation or the LDS size failed
 
-// kernels_ppca.hip: the probabilistic PCA target (api_ppca.hip sets it; eval_generic_target evaluates it); its row slices are hglm_geom's
+// kernels_ppca.hip: the probabilistic PCA target (api_ppca.hip sets it; eval_generic_target evaluates it); its row slices are the hierarchical GLM's
 constexpr size_t kPpcaPartCap = 256u << 20;        // bytes of the f64 partial planes a chunk of samples may take (at least one sample per chunk)
 bool ppca_reserve(mivi_ctx *c, int M);             // size the partial planes for M samples per estimate (ahead of a graph capture)
 bool launch_ppca_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation or the LDS size failed

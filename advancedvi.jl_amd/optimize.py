@@ -344,31 +344,20 @@ def _scheduled_logreg(obj, prob):
             isinstance(obj.subsampling, S.ReshufflingBatchSubsampling) and type(inner) is P.LogRegProblem)
 
 
-NO_SCHEDULE_SOFTMAX = ("SoftmaxRegProblem: the scheduled minibatch device loop (mivi_logreg_set_batch_schedule / mivi_optimize_loop_batches) is "
-                       "built for the logistic regression only; subsampled steps take the host-driven loop with mivi_softmax_select_rows per step")
-
-
-NO_SCHEDULE_BNN = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "BNNProblem").replace("mivi_softmax_select_rows", "mivi_bnn_select_rows")
-
-
-NO_SCHEDULE_HGLM = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "HierGLMProblem").replace("mivi_softmax_select_rows", "mivi_hglm_select_rows")
-
-
-NO_SCHEDULE_PPCA = NO_SCHEDULE_SOFTMAX.replace("SoftmaxRegProblem", "PPCAProblem").replace("mivi_softmax_select_rows", "mivi_ppca_select_rows")
+NO_SCHEDULE = ("{problem}: the scheduled minibatch device loop (mivi_logreg_set_batch_schedule / mivi_optimize_loop_batches) is "
+               "built for the logistic regression only; subsampled steps take the host-driven loop with {select_rows} per step")
 
 
 def subsampled_route_note(obj, prob):
     """Why a SubsampledObjective over `prob` does not take the scheduled device loop, by name -- None where it does, or where nothing is subsampled."""
     from . import problems as P
+    from .context import _RESIDENT
     inner = prob.prob if isinstance(prob, P.TransformedProblem) else prob
-    if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.SoftmaxRegProblem, P.SoftmaxRegSubset)):
-        return NO_SCHEDULE_SOFTMAX
-    if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.BNNProblem, P.BNNSubset)):
-        return NO_SCHEDULE_BNN
-    if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.HierGLMProblem, P.HierGLMSubset)):
-        return NO_SCHEDULE_HGLM
-    if isinstance(obj, S.SubsampledObjective) and isinstance(inner, (P.PPCAProblem, P.PPCASubset)):
-        return NO_SCHEDULE_PPCA
+    full = inner.parent if isinstance(inner, P._RowSubset) else inner
+    if isinstance(obj, S.SubsampledObjective):
+        for cls, (select_rows, _) in _RESIDENT.items():
+            if cls is not P.LogRegProblem and isinstance(full, cls):
+                return NO_SCHEDULE.format(problem=cls.__name__, select_rows=select_rows)
     return None
 
 

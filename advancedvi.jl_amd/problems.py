@@ -95,6 +95,27 @@ class DenseNormalProblem:
         return LogDensityOrder(self.order)
 
 
+class _RowSubset:
+    """A minibatch view of a data-set problem (what its `subsample` returns): the rows `batch` (0-based) of `parent`, with the likelihood
+    scaled by n_data / n.  The data stay where the parent keeps them; the device reads the rows through mivi_<t>_select_rows."""
+
+    def __init__(self, parent, batch):
+        self.parent = parent
+        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
+        if self.batch.size == 0:
+            raise ValueError("empty batch")
+        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
+
+    def dimension(self):
+        return self.parent.dimension()
+
+    def capabilities(self):
+        return self.parent.capabilities()
+
+    def subsample(self, batch):
+        return type(self)(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
+
+
 class LogRegProblem:
     """Hierarchical logistic regression over theta = [beta; s].
     variant "logsigma_normal": docs/src/tutorials/subsampling.md:26-38
@@ -128,24 +149,8 @@ class LogRegProblem:
         return LogRegSubset(self, batch)
 
 
-class LogRegSubset:
+class LogRegSubset(_RowSubset):
     """A minibatch view of a LogRegProblem (what `subsample` returns); never copies X on the host."""
-
-    def __init__(self, parent: LogRegProblem, batch):
-        self.parent = parent
-        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
-        if self.batch.size == 0:
-            raise ValueError("empty batch")
-        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
-
-    def dimension(self):
-        return self.parent.dimension()
-
-    def capabilities(self):
-        return self.parent.capabilities()
-
-    def subsample(self, batch):
-        return LogRegSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
 class SoftmaxRegProblem:
@@ -183,24 +188,8 @@ class SoftmaxRegProblem:
         return SoftmaxRegSubset(self, batch)
 
 
-class SoftmaxRegSubset:
+class SoftmaxRegSubset(_RowSubset):
     """A minibatch view of a SoftmaxRegProblem (what `subsample` returns); never copies X."""
-
-    def __init__(self, parent: SoftmaxRegProblem, batch):
-        self.parent = parent
-        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
-        if self.batch.size == 0:
-            raise ValueError("empty batch")
-        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
-
-    def dimension(self):
-        return self.parent.dimension()
-
-    def capabilities(self):
-        return self.parent.capabilities()
-
-    def subsample(self, batch):
-        return SoftmaxRegSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
 class BNNProblem:
@@ -268,24 +257,8 @@ class BNNProblem:
                 ctx.close()
 
 
-class BNNSubset:
+class BNNSubset(_RowSubset):
     """A minibatch view of a BNNProblem (what `subsample` returns); never copies X."""
-
-    def __init__(self, parent: BNNProblem, batch):
-        self.parent = parent
-        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
-        if self.batch.size == 0:
-            raise ValueError("empty batch")
-        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
-
-    def dimension(self):
-        return self.parent.dimension()
-
-    def capabilities(self):
-        return self.parent.capabilities()
-
-    def subsample(self, batch):
-        return BNNSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
 class HierGLMProblem:
@@ -333,24 +306,8 @@ class HierGLMProblem:
         return theta[:self.p], theta[self.p:self.p + self.n_groups], theta[self.p + self.n_groups]
 
 
-class HierGLMSubset:
+class HierGLMSubset(_RowSubset):
     """A minibatch view of a HierGLMProblem (what `subsample` returns); never copies X."""
-
-    def __init__(self, parent: HierGLMProblem, batch):
-        self.parent = parent
-        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
-        if self.batch.size == 0:
-            raise ValueError("empty batch")
-        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
-
-    def dimension(self):
-        return self.parent.dimension()
-
-    def capabilities(self):
-        return self.parent.capabilities()
-
-    def subsample(self, batch):
-        return HierGLMSubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
 class PPCAProblem:
@@ -396,24 +353,8 @@ class PPCAProblem:
                 theta[-1])
 
 
-class PPCASubset:
+class PPCASubset(_RowSubset):
     """A minibatch view of a PPCAProblem (what `subsample` returns); never copies Y."""
-
-    def __init__(self, parent: PPCAProblem, batch):
-        self.parent = parent
-        self.batch = np.ascontiguousarray(np.asarray(batch, dtype=np.int64).reshape(-1))
-        if self.batch.size == 0:
-            raise ValueError("empty batch")
-        self.likeadj = parent.likeadj * parent.n_rows() / self.batch.size
-
-    def dimension(self):
-        return self.parent.dimension()
-
-    def capabilities(self):
-        return self.parent.capabilities()
-
-    def subsample(self, batch):
-        return PPCASubset(self.parent, self.batch[np.asarray(batch, dtype=np.int64)])
 
 
 def subsample(model, batch):

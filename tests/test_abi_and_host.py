@@ -251,6 +251,35 @@ def test_family_dispatch_has_one_table():
             assert (group in re.findall(r"LACKS_\w+", lacks[fam])) == (cell == "R"), (group, fam)
 
 
+def test_target_dispatch_has_one_table():
+    """The data-set targets that run their own kernels are rows of ONE table (csrc/api_common.h: kTargets behind target_row, refuse_target).
+    With comments stripped, a target code is named only in mivi_internal.h (the enum), there and in the target's own api_*.hip unit; the
+    guards and the geometry function the table and row_slices replaced are named nowhere; and the matrix of DESIGN.md ("The target
+    table") names the targets of the table's rows."""
+    csrc = os.path.join(ROOT, "advancedvi.jl_amd", "csrc")
+    raw = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    code = {f: re.sub(r"//[^\n]*|/\*.*?\*/", "", txt, flags=re.S) for f, txt in raw.items()}
+    may_name = {"TGT_SOFTMAX": "api_softmax.hip", "TGT_BNN": "api_bnn.hip", "TGT_HGLM": "api_hglm.hip", "TGT_PPCA": "api_ppca.hip"}
+    for name, own in may_name.items():
+        named_in = {f for f, txt in code.items() if re.search(rf"\b{name}\b", txt)}
+        assert named_in == {"mivi_internal.h", "api_common.h", own}, (name, sorted(named_in))
+    for gone in ("refuse_softmax", "refuse_bnn", "refuse_hglm", "refuse_ppca", "hglm_geom"):
+        assert not [f for f, txt in raw.items() if re.search(rf"\b{gone}\b", txt)], gone
+    table = re.search(r"inline const TargetRow kTargets\[\] = \{\n(.*?)\n\};", code["api_common.h"], flags=re.S).group(1)
+    rows = re.findall(r'\{(TGT_\w+), "([^"]+ target \(mivi_set_target_(\w+)\))", "[^"]+", "mivi_(\w+)_select_rows",', table)
+    assert len(rows) == table.count("{TGT_") == 4 and all(setter == selector for _, _, setter, selector in rows), table
+    assert [kind for kind, _, _, _ in rows] == list(may_name)
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = re.search(r"### The target table.*?(?=\n###? )", design, flags=re.S).group(0)
+    assert set(re.findall(r"`([^`]+ target \(mivi_set_target_\w+\))`", section)) == {name for _, name, _, _ in rows}
+    header = re.search(r"\| entry \|([^\n]*)\|\n", section).group(1)
+    assert [c.strip() for c in header.split("|")] == ["softmax", "BNN", "hierarchical GLM", "PPCA"]
+    matrix = dict(re.findall(r"\| `(mivi_\w+)` \| ([RN–] \| [RN–] \| [RN–] \| [RN–]) \|", section))
+    assert len(matrix) == 10
+    for col, (_, _, _, selector) in enumerate(rows):   # every row's own select_rows entry is its column's one open cell
+        assert [entry for entry, cells in matrix.items() if cells.split(" | ")[col] == "–"] == [f"mivi_{selector}_select_rows"]
+
+
 def test_stream_and_event_handles_have_one_owner():
     """Streams and events are created and destroyed in ONE translation unit (csrc/api_core.hip: make_stream, make_event, handle_destroy),
     a hipGraphExec is destroyed in the graph unit only; every other unit holds them in a Stream / Event / GraphExec (csrc/mivi_internal.h).
