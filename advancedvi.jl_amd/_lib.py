@@ -33,7 +33,7 @@ class MiviBlockDiag(C.Structure):   # mivi_blockdiag_t: the block size of a MIVI
 
 class MiviBnn(C.Structure):   # mivi_bnn_t: the network, likelihood and prior of mivi_set_target_bnn
     _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3), ("likelihood", C.c_int32), ("noise", C.c_double), ("prior_std", C.c_double),
-                ("likeadj", C.c_double)]
+                ("likeadj", C.c_double), ("n_out", C.c_int32)]   # (n_out last: six positional values leave it 0, the one-output network)
 
 
 class MiviHglm(C.Structure):   # mivi_hglm_t: the likelihood, group count and priors of mivi_set_target_hglm

@@ -225,14 +225,14 @@ class MiviContext:
         if not 1 <= len(hidden) <= 3:
             raise ValueError("BNNProblem: one to three hidden layers")
         net = _lib.MiviBnn(len(hidden), (C.c_int32 * 3)(*(hidden + [0] * (3 - len(hidden)))), P.BNNProblem.LIKELIHOODS[prob.likelihood],
-                           prob.noise, prob.prior_std, prob.likeadj)
-        if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor, y a tensor of n entries, both of the context's dtype
+                           prob.noise, prob.prior_std, prob.likeadj, prob.n_out)
+        if prob.on_device:   # column-major n x p as a (p, n) contiguous tensor, y a tensor of n entries ((k, n): a Normal with k outputs), both of the context's dtype
             if prob.X.dtype != self.tdtype or not prob.X.is_contiguous() or prob.y.dtype != self.tdtype or not prob.y.is_contiguous():
                 raise TypeError("BNNProblem on the device: X is a contiguous (p, n) tensor and y a contiguous tensor of the context's dtype")
             self._keep += [prob.X, prob.y]
             self._chk(self.lib.mivi_set_target_bnn(self.h, C.byref(net), self._p(prob.X), self._p(prob.y), prob.n, prob.p, 1))
         else:
-            Xf, y = np.asfortranarray(prob.X, dtype=dt), np.ascontiguousarray(prob.y, dtype=dt)
+            Xf, y = np.asfortranarray(prob.X, dtype=dt), np.ascontiguousarray(np.asarray(prob.y).T, dtype=dt)   # ((n, k): n x k column-major)
             self._chk(self.lib.mivi_set_target_bnn(self.h, C.byref(net), Xf.ctypes.data, y.ctypes.data, Xf.shape[0], prob.p, 0))
 
     def _upload_hglm(self, prob):
@@ -747,7 +747,8 @@ class MiviContext:
         Xn = Xn.to(device=self.tdevice, dtype=self.tdtype).t().contiguous()            # (p, n_new): n_new x p column-major
         if not isinstance(self._resident, P.BNNProblem) or Xn.dim() != 2 or Xn.shape[0] != self._resident.p:
             raise ValueError("bnn_forward: a BNNProblem must be set and Xnew be n_new x p with the problem's p")
-        f = torch.empty((th.shape[0], Xn.shape[1]), dtype=self.tdtype, device=self.tdevice)
+        k = self._resident.n_out
+        f = torch.empty((th.shape[0], Xn.shape[1]) + ((k,) if k >= 2 else ()), dtype=self.tdtype, device=self.tdevice)
         torch.cuda.current_stream(self.tdevice).synchronize()   # (th, Xn and f were made on torch's stream; the kernel runs on the context's)
         self._chk(self.lib.mivi_bnn_forward(self.h, self._p(th), th.shape[0], self._p(Xn), Xn.shape[1], self._p(f)))
         self.synchronize()

@@ -15,6 +15,8 @@ mivi_status_t mivi_set_target_bnn(mivi_ctx_t *c, const mivi_bnn_t *np, const voi
   if (n < 1) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: n must be at least 1");
   if (p < 1 || p > MIVI_BNN_MAX_IN) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: p must lie in [1, 64]");
   if (net.n_hidden < 1 || net.n_hidden > 3) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: n_hidden must lie in [1, 3]");
+  if (net.n_out < 0 || net.n_out > MIVI_BNN_MAX_OUT) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: n_out must lie in [0, 64] (0 and 1: one output)");
+  const int n_out = net.n_out >= 2 ? net.n_out : 1;
   long long d = 0;
   int prev = p;
   for (int l = 0; l < net.n_hidden; ++l) {
@@ -22,17 +24,25 @@ mivi_status_t mivi_set_target_bnn(mivi_ctx_t *c, const mivi_bnn_t *np, const voi
     d += (long long)net.hidden[l] * (prev + 1);
     prev = net.hidden[l];
   }
-  d += prev + 1;
+  d += (long long)n_out * (prev + 1);
   if (c->cfg.d != d)
     return fail(c, MIVI_ERR_BAD_ARG, ("Bayesian neural network: the context's d must be the network's parameter count, " + std::to_string(d)).c_str());
   if (net.likelihood != 0 && net.likelihood != 1) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: unknown likelihood (0 Bernoulli-logit, 1 Normal)");
   if (!bnn_positive(net.noise)) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: noise must be positive and finite");
   if (!bnn_positive(net.prior_std)) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: prior_std must be positive and finite");
   if (!bnn_positive(net.likeadj)) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: likelihood adjustment must be positive and finite");
+  if (n_out >= 2) {   // the head kernels keep the output layer in LDS as one more plane: the largest f64 networks do not fit
+    const size_t need = mivi::bnn_head_lds_bytes(net, p, c->esize);
+    if (need > MIVI_BNN_LDS_LIMIT)
+      return fail(c, MIVI_ERR_BAD_ARG, ("Bayesian neural network: the multi-output network needs " + std::to_string(need) + " bytes of LDS, the limit is " +
+                                        std::to_string(MIVI_BNN_LDS_LIMIT) + " (narrower layers, fewer of them, or f32)").c_str());
+  }
   if (!on_device && net.likelihood == 0)
     for (int64_t r = 0; r < n; ++r) {
       const double v = c->cfg.dtype == MIVI_F32 ? (double)((const float *)y)[r] : ((const double *)y)[r];
-      if (v != 0.0 && v != 1.0) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: a Bernoulli label is not 0 or 1");
+      if (n_out == 1 && v != 0.0 && v != 1.0) return fail(c, MIVI_ERR_BAD_ARG, "Bayesian neural network: a Bernoulli label is not 0 or 1");
+      if (n_out >= 2 && !(v >= 0.0 && v < (double)n_out && v == std::floor(v)))
+        return fail(c, MIVI_ERR_BAD_ARG, ("Bayesian neural network: a categorical label is not an integer in [0, " + std::to_string(n_out) + ")").c_str());
     }
   (void)hipSetDevice(c->cfg.device);
   invalidate_graph(c);
@@ -42,7 +52,7 @@ mivi_status_t mivi_set_target_bnn(mivi_ctx_t *c, const mivi_bnn_t *np, const voi
     c->bnn_y = y;
   } else {
     mivi_status_t s;
-    if ((s = upload(c, c->bnn_X_own, X, (size_t)n * p * c->esize)) || (s = upload(c, c->bnn_y_own, y, (size_t)n * c->esize))) return s;
+    if ((s = upload(c, c->bnn_X_own, X, (size_t)n * p * c->esize)) || (s = upload(c, c->bnn_y_own, y, (size_t)n * (net.likelihood == 1 ? n_out : 1) * c->esize))) return s;
     c->bnn_X = c->bnn_X_own.p;
     c->bnn_y = c->bnn_y_own.p;
   }

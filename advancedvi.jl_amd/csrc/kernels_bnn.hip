@@ -15,6 +15,14 @@
 //   k_bnn_finish   one workgroup per sample: the slices in slice order, likeadj, the prior, the Normal likelihood's constants -- all
 //                  f64, rounded once into ell (M) and G (d x M) where eval_generic_target leaves them for the other generic targets.
 //   k_bnn_forward  the same forward sweep on new rows, storing f (mivi_bnn_forward).
+//   k_bnn_rows_head, k_bnn_forward_head   the same two for a network with n_out = 2 .. 64 outputs (a categorical likelihood with a softmax
+//                  link, or independent Normals).  The output layer is then one more [in][out + 1] plane, padded to Pc = round16(n_out)
+//                  like the hidden ones, and layer H + 1 of every sweep: the logits W_{H+1} a_H + b on the matrix cores (wave w owns output
+//                  tile w) into one of the two delta blocks; the likelihood in f64 -- wave w takes tile rows 4 w .. 4 w + 3 with 16 lanes
+//                  per row striding over the REAL classes, the row maximum and sum of exponentials by 16-lane shuffles, the label only ever
+//                  COMPARED with the class index -- which overwrites the logits by delta_out in place; then dW_out += delta_out a_H' (its
+//                  at most 16 tiles join the round-robin deal: up to 64 tiles, kBnnHeadWaveTiles = 16 per wave, in registers across the
+//                  slice), db_out and delta_H = (W_out' delta_out)(1 - a_H^2) by the code of the hidden layers.
 // Nothing is accumulated atomically and no geometry depends on the chunking of the samples: results are bitwise reproducible and the
 // same for every partial cap.
 #include "flow_tile.h"
@@ -24,16 +32,17 @@ namespace mivi {
 constexpr int kBnnLda = kFlowTile + 1;   // stride of a [width][16] activation block
 constexpr int kBnnFlush = 128;           // rows between two flushes of the f32 dW accumulators into the f64 partial
 constexpr int kBnnWaveTiles = 12;        // dW output tiles per wave: 3 layers x 16 tiles over 4 waves
+constexpr int kBnnHeadWaveTiles = 16;    // ... of the head kernel: the output layer's 16 tiles more
 constexpr long long kBnnSliceRows = 256; // rows a slice aims at (slices: ceil(rows / 256) clamped to 1 .. 32)
 
 // layer l = 1 .. H + 1 maps n[l - 1] -> n[l]; P: the hidden-side widths padded to 16.  Offsets into theta (woff, boff) and into LDS
 struct BnnNet {
   int H, d;
-  int n[5], P[4];
+  int n[5], P[5];            // (P[H + 1] = Pc, the padded width of the head: set when n[H + 1] >= 2 only)
   int woff[4], boff[4];      // theta: W_l, b_l at index l - 1
-  int lw[3], lb[3], lwo;     // LDS: hidden W_l ([P[l-1]][P[l] + 1]), b_l, the output row (P[H])
+  int lw[4], lb[4], lwo;     // LDS: W_l ([P[l-1]][P[l] + 1]), b_l of the hidden layers (and of the head), the output row (P[H]; one output)
   int la[4], ldl[2];         // LDS: a_0 .. a_H, the two delta blocks
-  int toff[4];               // dW tiles of hidden layer l: [toff[l - 1], toff[l])
+  int toff[5];               // dW tiles of layer l: [toff[l - 1], toff[l]) (the hidden layers; the head as layer H + 1)
   int lds_elems;
 };
 
@@ -50,7 +59,7 @@ struct BnnArgs {
   int n_sl;
   long long rps;             // rows per slice, a multiple of 16
   T *G, *ell;                // d x M_total; M_total
-  T *f;                      // k_bnn_forward: nr x M
+  T *f;                      // k_bnn_forward: nr x M; k_bnn_forward_head: n_out x nr x M
   int likelihood, want_grad;
   double noise, prior_std, likeadj;
 };
@@ -58,10 +67,11 @@ struct BnnArgs {
 __device__ __forceinline__ float bnn_tanh(float x) { return tanhf(x); }
 __device__ __forceinline__ double bnn_tanh(double x) { return tanh(x); }
 
+// layers 1 .. nl as zero-padded planes and biases (no barrier)
 template <typename T>
-__device__ __forceinline__ void bnn_stage_net(const BnnNet &nt, const T *th, T *S) {
+__device__ __forceinline__ void bnn_stage_planes(const BnnNet &nt, const T *th, T *S, int nl) {
   const int tid = threadIdx.x;
-  for (int l = 1; l <= nt.H; ++l) {
+  for (int l = 1; l <= nl; ++l) {
     const int no = nt.n[l], ni = nt.n[l - 1], ldw = nt.P[l] + 1;
     T *W = S + nt.lw[l - 1], *b = S + nt.lb[l - 1];
     for (int e = tid; e < nt.P[l - 1] * ldw; e += 256) {
@@ -70,6 +80,12 @@ __device__ __forceinline__ void bnn_stage_net(const BnnNet &nt, const T *th, T *
     }
     for (int e = tid; e < nt.P[l]; e += 256) b[e] = e < no ? th[nt.boff[l - 1] + e] : T(0);
   }
+}
+
+template <typename T>
+__device__ __forceinline__ void bnn_stage_net(const BnnNet &nt, const T *th, T *S) {
+  const int tid = threadIdx.x;
+  bnn_stage_planes(nt, th, S, nt.H);
   for (int e = tid; e < nt.P[nt.H]; e += 256) S[nt.lwo + e] = e < nt.n[nt.H] ? th[nt.woff[nt.H] + e] : T(0);
   __syncthreads();
 }
@@ -89,9 +105,9 @@ __device__ __forceinline__ void bnn_load_x(const BnnArgs<T> &a, T *S, long long 
   __syncthreads();
 }
 
-// a_0 -> a_1 .. a_H in LDS; f of tile row `tid` in threads 0 .. 15 (f64, the output bias added), 0 elsewhere
+// a_0 -> a_1 .. a_H in LDS
 template <typename T>
-__device__ __forceinline__ double bnn_forward_tile(const BnnNet &nt, T *S, double bout) {
+__device__ __forceinline__ void bnn_hidden_tile(const BnnNet &nt, T *S) {
   using acc_t = typename Mfma16<T>::acc_t;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
   for (int l = 1; l <= nt.H; ++l) {
@@ -109,6 +125,14 @@ __device__ __forceinline__ double bnn_forward_tile(const BnnNet &nt, T *S, doubl
     }
     __syncthreads();
   }
+}
+
+// a_0 -> a_1 .. a_H in LDS; f of tile row `tid` in threads 0 .. 15 (f64, the output bias added), 0 elsewhere
+template <typename T>
+__device__ __forceinline__ double bnn_forward_tile(const BnnNet &nt, T *S, double bout) {
+  using acc_t = typename Mfma16<T>::acc_t;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
+  bnn_hidden_tile(nt, S);
   double f = 0.0;
   if (w == 0) {   // the output row as a 16-row A operand whose rows 1 .. 15 are zero: C[0][col] is register 0 of lanes 0 .. 15
     const T *wo = S + nt.lwo, *aH = S + nt.la[nt.H];
@@ -119,14 +143,14 @@ __device__ __forceinline__ double bnn_forward_tile(const BnnNet &nt, T *S, doubl
   return f;
 }
 
-// the wave's dW tiles -> the slice's f64 partial (added to it after the first flush); the accumulators restart at zero
-template <typename T>
-__device__ __forceinline__ void bnn_flush(const BnnNet &nt, typename Mfma16<T>::acc_t (&acc)[kBnnWaveTiles], double *part, bool add) {
+// the wave's dW tiles of layers 1 .. nl -> the slice's f64 partial (added to it after the first flush); the accumulators restart at zero
+template <typename T, int NT>
+__device__ __forceinline__ void bnn_flush(const BnnNet &nt, typename Mfma16<T>::acc_t (&acc)[NT], double *part, bool add, int nl) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
 #pragma unroll
-  for (int t = 0; t < kBnnWaveTiles; ++t) {
+  for (int t = 0; t < NT; ++t) {
     int g = w + 4 * t;
-    if (g < nt.toff[nt.H]) {
+    if (g < nt.toff[nl]) {
       int l = 1;
       while (g >= nt.toff[l]) ++l;
       g -= nt.toff[l - 1];
@@ -244,7 +268,7 @@ __global__ __launch_bounds__(256) void k_bnn_rows(BnnArgs<T> a) {
     if constexpr (sizeof(T) == 4) {
       since += kFlowTile;
       if (since >= kBnnFlush) {
-        bnn_flush<T>(nt, acc, part, flushed);
+        bnn_flush<T>(nt, acc, part, flushed, nt.H);
         flushed = true;
         since = 0;
       }
@@ -254,7 +278,7 @@ __global__ __launch_bounds__(256) void k_bnn_rows(BnnArgs<T> a) {
   gbo = wave_sum(gbo);
   if (tid == 0) a.llp[(size_t)sl * a.M + ml] = ll;
   if (!a.want_grad) return;
-  bnn_flush<T>(nt, acc, part, flushed);
+  bnn_flush<T>(nt, acc, part, flushed, nt.H);
 #pragma unroll
   for (int l = 1; l <= 3; ++l)
     if (l <= nt.H && tid < nt.n[l]) part[nt.boff[l - 1] + tid] = gb[l - 1];
@@ -279,6 +303,179 @@ __global__ __launch_bounds__(256) void k_bnn_forward(BnnArgs<T> a) {
   }
 }
 
+// ---- the multi-output head (n_out >= 2): layer H + 1 is a plane like the hidden ones -------------------------------------------------------
+// logits = W_{H+1} a_H + b_{H+1} of the tile -> the [Pc][16] block L (a padded class: 0); wave w owns output tile w
+template <typename T>
+__device__ __forceinline__ void bnn_head_logits(const BnnNet &nt, T *S, T *L) {
+  using acc_t = typename Mfma16<T>::acc_t;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
+  const T *W = S + nt.lw[nt.H], *b = S + nt.lb[nt.H], *aH = S + nt.la[nt.H];
+  const int ldw = nt.P[nt.H + 1] + 1, K = nt.P[nt.H];
+  for (int ot = w; ot < nt.P[nt.H + 1] / 16; ot += 4) {
+    acc_t acc = acc_t{0, 0, 0, 0};
+    for (int kk = 0; kk < K; kk += 4) acc = Mfma16<T>::mma(W[(kk + kq) * ldw + 16 * ot + col], aH[(kk + kq) * kBnnLda + col], acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * ot + Mfma16<T>::row(kq, r);
+      L[row * kBnnLda + col] = acc[r] + b[row];
+    }
+  }
+  __syncthreads();
+}
+
+// The likelihood of the tile in f64: the logits in L are overwritten by delta_out (0 in rows past the slice and in padded classes); returns
+// this lane's log-likelihood terms.  Wave w takes tile rows 4 w .. 4 w + 3, 16 lanes per row, the lanes striding over the classes: the
+// maximum and the sum of exponentials of a row are over its n_out REAL classes.  The label is compared with the class index and never
+// used as one, so a label outside 0 .. n_out - 1 (device-resident data are not checked) matches no class and addresses nothing.
+template <typename T>
+__device__ __forceinline__ double bnn_head_delta(const BnnArgs<T> &a, T *L, const long long *rowi, double in2) {
+  const int lane = threadIdx.x & 63, c0 = lane & 15, r = 4 * (threadIdx.x >> 6) + (lane >> 4);
+  const int C = a.net.n[a.net.H + 1], Pc = a.net.P[a.net.H + 1];
+  const long long ri = rowi[r];
+  double ll = 0.0;
+  if (a.likelihood == 0) {
+    double mx = -INFINITY, se = 0.0;
+    for (int c = c0; c < C; c += 16) mx = fmax(mx, (double)L[c * kBnnLda + r]);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 16));
+    for (int c = c0; c < C; c += 16) se += exp((double)L[c * kBnnLda + r] - mx);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o, 16);
+    const double lse = mx + log(se), yv = ri >= 0 ? (double)a.y[ri] : -1.0;
+    for (int c = c0; c < Pc; c += 16) {
+      double dl = 0.0;
+      if (ri >= 0 && c < C) {
+        const double lg = (double)L[c * kBnnLda + r];
+        const bool hit = (double)c == yv;
+        if (hit) ll += lg - lse;
+        dl = (hit ? 1.0 : 0.0) - exp(lg - lse);
+      }
+      L[c * kBnnLda + r] = (T)dl;
+    }
+  } else {
+    for (int c = c0; c < Pc; c += 16) {
+      double dl = 0.0;
+      if (ri >= 0 && c < C) {
+        const double u = (double)a.y[ri + a.n * (long long)c] - (double)L[c * kBnnLda + r];
+        ll -= 0.5 * u * u * in2;
+        dl = u * in2;
+      }
+      L[c * kBnnLda + r] = (T)dl;
+    }
+  }
+  __syncthreads();
+  return ll;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bnn_rows_head(BnnArgs<T> a) {
+  using acc_t = typename Mfma16<T>::acc_t;
+  T *S = reinterpret_cast<T *>(flow_lds);
+  __shared__ long long rowi[kFlowTile];
+  __shared__ double red[4];
+  const BnnNet &nt = a.net;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 15, kq = lane >> 4;
+  const int ml = blockIdx.x, sl = blockIdx.y, nl = nt.H + 1;
+  const T *th = a.Z + (size_t)(a.m0 + ml) * nt.d;
+  bnn_stage_planes(nt, th, S, nl);
+  __syncthreads();
+  const double in2 = 1.0 / (a.noise * a.noise);
+  const long long rbeg = (long long)sl * a.rps, rend = rbeg + a.rps < a.nr ? rbeg + a.rps : a.nr;
+  double *part = a.part + ((size_t)sl * a.M + ml) * nt.d;
+  acc_t acc[kBnnHeadWaveTiles];
+#pragma unroll
+  for (int t = 0; t < kBnnHeadWaveTiles; ++t) acc[t] = acc_t{0, 0, 0, 0};
+  double gb[4] = {0.0, 0.0, 0.0, 0.0}, ll = 0.0;
+  bool flushed = false;
+  int since = 0;
+  for (long long rr = rbeg; rr < rend; rr += kFlowTile) {
+    bnn_load_x(a, S, rowi, rr, rend);
+    bnn_hidden_tile(nt, S);
+    T *D = S + nt.ldl[0], *Dn = S + nt.ldl[1];
+    bnn_head_logits(nt, S, D);
+    ll += bnn_head_delta(a, D, rowi, in2);
+    if (!a.want_grad) continue;
+#pragma unroll
+    for (int l = 4; l >= 1; --l) {   // the head is layer H + 1 of the sweep
+      if (l <= nl) {
+        const T *ain = S + nt.la[l - 1];
+        if (tid < nt.P[l]) {   // db_l: the row sums of delta_l
+          double s = 0.0;
+#pragma unroll
+          for (int r = 0; r < kFlowTile; ++r) s += (double)D[tid * kBnnLda + r];
+          gb[l - 1] += s;
+        }
+        const int t0 = nt.toff[l - 1], tn = nt.toff[l] - t0, itn = nt.P[l - 1] / 16;
+#pragma unroll
+        for (int t = 0; t < kBnnHeadWaveTiles; ++t) {   // dW_l += delta_l a_{l-1}': K is the tile's 16 rows
+          const int g = w + 4 * t - t0;
+          if (g >= 0 && g < tn) {
+            const int ot = g / itn, it = g - ot * itn;
+#pragma unroll
+            for (int kk = 0; kk < kFlowTile; kk += 4)
+              acc[t] = Mfma16<T>::mma(D[(16 * ot + col) * kBnnLda + kk + kq], ain[(16 * it + col) * kBnnLda + kk + kq], acc[t]);
+          }
+        }
+        if (l > 1) {   // delta_{l-1} = (W_l' delta_l) (1 - a_{l-1}^2), from the saved activations
+          const T *W = S + nt.lw[l - 1];
+          const int ldw = nt.P[l] + 1;
+          for (int it = w; it < itn; it += 4) {
+            acc_t c = acc_t{0, 0, 0, 0};
+            for (int kk = 0; kk < nt.P[l]; kk += 4) c = Mfma16<T>::mma(W[(16 * it + col) * ldw + kk + kq], D[(kk + kq) * kBnnLda + col], c);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int i = 16 * it + Mfma16<T>::row(kq, r);
+              const T av = ain[i * kBnnLda + col];
+              Dn[i * kBnnLda + col] = c[r] * (T(1) - av * av);
+            }
+          }
+        }
+        __syncthreads();
+        T *sw = D;
+        D = Dn;
+        Dn = sw;
+      }
+    }
+    if constexpr (sizeof(T) == 4) {
+      since += kFlowTile;
+      if (since >= kBnnFlush) {
+        bnn_flush<T>(nt, acc, part, flushed, nl);
+        flushed = true;
+        since = 0;
+      }
+    }
+  }
+  ll = block_sum<double, 256>(ll, red);
+  if (tid == 0) a.llp[(size_t)sl * a.M + ml] = ll;
+  if (!a.want_grad) return;
+  bnn_flush<T>(nt, acc, part, flushed, nl);
+#pragma unroll
+  for (int l = 1; l <= 4; ++l)
+    if (l <= nl && tid < nt.n[l]) part[nt.boff[l - 1] + tid] = gb[l - 1];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bnn_forward_head(BnnArgs<T> a) {
+  T *S = reinterpret_cast<T *>(flow_lds);
+  __shared__ long long rowi[kFlowTile];
+  const BnnNet &nt = a.net;
+  const int tid = threadIdx.x, m = blockIdx.x, sl = blockIdx.y, C = nt.n[nt.H + 1];
+  bnn_stage_planes(nt, a.Z + (size_t)m * nt.d, S, nt.H + 1);
+  __syncthreads();
+  T *L = S + nt.ldl[0];
+  const long long rbeg = (long long)sl * a.rps, rend = rbeg + a.rps < a.nr ? rbeg + a.rps : a.nr;
+  for (long long rr = rbeg; rr < rend; rr += kFlowTile) {
+    bnn_load_x(a, S, rowi, rr, rend);
+    bnn_hidden_tile(nt, S);
+    bnn_head_logits(nt, S, L);
+    for (int e = tid; e < C * kFlowTile; e += 256) {
+      const int r = e / C, c = e - r * C;
+      if (rowi[r] >= 0) a.f[c + (long long)C * (rr + r + a.nr * (long long)m)] = L[c * kBnnLda + r];
+    }
+    __syncthreads();   // (the next tile's bnn_load_x writes rowi)
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_bnn_finish(BnnArgs<T> a) {
   __shared__ double red[4];
@@ -299,20 +496,23 @@ __global__ __launch_bounds__(256) void k_bnn_finish(BnnArgs<T> a) {
   if (tid == 0) {
     double ll = 0.0;
     for (int sl = 0; sl < a.n_sl; ++sl) ll += a.llp[(size_t)sl * a.M + ml];
-    if (a.likelihood == 1) ll -= (double)a.nr * (log(a.noise) + 0.5 * kLog2Pi);
+    if (a.likelihood == 1) ll -= (double)a.nr * (double)a.net.n[a.net.H + 1] * (log(a.noise) + 0.5 * kLog2Pi);
     a.ell[a.m0 + ml] = (T)(a.likeadj * ll - 0.5 * tt * ip2 - (double)d * (log(a.prior_std) + 0.5 * kLog2Pi));
   }
 }
 
 // ---- the launches' geometry: a function of the architecture, the rows and the cap alone ------------------------------------------------
-static BnnNet bnn_net(const mivi_ctx *c) {
+// (one output: the layout the one-output kernels have always had; n_out >= 2: the head as layer H + 1, no output row)
+static BnnNet bnn_net(const mivi_bnn_t &b, int p) {
   BnnNet nt{};
-  nt.H = c->bnn.n_hidden;
-  nt.n[0] = c->bnn_p;
-  for (int l = 1; l <= nt.H; ++l) nt.n[l] = c->bnn.hidden[l - 1];
-  nt.n[nt.H + 1] = 1;
+  nt.H = b.n_hidden;
+  nt.n[0] = p;
+  for (int l = 1; l <= nt.H; ++l) nt.n[l] = b.hidden[l - 1];
+  nt.n[nt.H + 1] = b.n_out >= 2 ? b.n_out : 1;
+  const bool head = nt.n[nt.H + 1] >= 2;
+  const int nl = head ? nt.H + 1 : nt.H;   // layers staged as planes
   int off = 0, lds = 0;
-  for (int l = 0; l <= nt.H; ++l) nt.P[l] = (nt.n[l] + 15) & ~15;
+  for (int l = 0; l <= nl; ++l) nt.P[l] = (nt.n[l] + 15) & ~15;
   for (int l = 1; l <= nt.H + 1; ++l) {
     nt.woff[l - 1] = off;
     off += nt.n[l] * nt.n[l - 1];
@@ -320,16 +520,18 @@ static BnnNet bnn_net(const mivi_ctx *c) {
     off += nt.n[l];
   }
   nt.d = off;
-  for (int l = 1; l <= nt.H; ++l) {
+  for (int l = 1; l <= nl; ++l) {
     nt.lw[l - 1] = lds;
     lds += nt.P[l - 1] * (nt.P[l] + 1);
     nt.lb[l - 1] = lds;
     lds += nt.P[l];
     nt.toff[l] = nt.toff[l - 1] + (nt.P[l] / 16) * (nt.P[l - 1] / 16);
   }
-  nt.lwo = lds;
-  lds += nt.P[nt.H];
-  int widest = 0;
+  if (!head) {
+    nt.lwo = lds;
+    lds += nt.P[nt.H];
+  }
+  int widest = head ? nt.P[nl] : 0;   // (the logits and delta_out live in a delta block)
   for (int l = 0; l <= nt.H; ++l) {
     nt.la[l] = lds;
     lds += nt.P[l] * kBnnLda;
@@ -341,6 +543,11 @@ static BnnNet bnn_net(const mivi_ctx *c) {
   }
   nt.lds_elems = lds;
   return nt;
+}
+
+// the LDS of a workgroup of the head kernels: the dynamic block and k_bnn_rows_head's static arrays (rowi, red)
+size_t bnn_head_lds_bytes(const mivi_bnn_t &b, int p, size_t esize) {
+  return (size_t)bnn_net(b, p).lds_elems * esize + kFlowTile * sizeof(long long) + 4 * sizeof(double);
 }
 
 static RowSlices bnn_slices(long long nr) { return row_slices(nr, kBnnSliceRows, 32); }
@@ -358,7 +565,7 @@ bool bnn_reserve(mivi_ctx *c, int M) {
 template <typename T>
 static BnnArgs<T> bnn_args(const mivi_ctx *c) {
   BnnArgs<T> a{};
-  a.net = bnn_net(c);
+  a.net = bnn_net(c->bnn, c->bnn_p);
   a.likelihood = c->bnn.likelihood;
   a.noise = c->bnn.noise;
   a.prior_std = c->bnn.prior_std;
@@ -370,7 +577,8 @@ static bool bnn_impl(mivi_ctx *c, int M, int want_grad) {
   const RowSlices g = bnn_slices(c->bnn_rows.nr);
   const int Mc = bnn_chunk(c, g, M);
   BnnArgs<T> a = bnn_args<T>(c);
-  if (!flow_lds_attr<T>(k_bnn_rows<T>, a.net.lds_elems)) return false;
+  const auto rows_kernel = a.net.n[a.net.H + 1] >= 2 ? k_bnn_rows_head<T> : k_bnn_rows<T>;
+  if (!flow_lds_attr<T>(rows_kernel, a.net.lds_elems)) return false;
   a.n = c->bnn_rows.n;
   a.nr = c->bnn_rows.nr;
   a.X = (const T *)c->bnn_X;
@@ -389,7 +597,7 @@ static bool bnn_impl(mivi_ctx *c, int M, int want_grad) {
   for (int m0 = 0; m0 < M; m0 += Mc) {   // chunks of samples: the f64 partials stay under their cap
     a.m0 = m0;
     a.M = M - m0 < Mc ? M - m0 : Mc;
-    hipLaunchKernelGGL(k_bnn_rows<T>, dim3(a.M, g.n_sl), dim3(256), lds, c->stream, a);
+    hipLaunchKernelGGL(rows_kernel, dim3(a.M, g.n_sl), dim3(256), lds, c->stream, a);
     hipLaunchKernelGGL(k_bnn_finish<T>, dim3(a.M), dim3(256), 0, c->stream, a);
   }
   return true;
@@ -405,14 +613,15 @@ template <typename T>
 static bool bnn_forward_impl(mivi_ctx *c, const void *theta, int M, const void *Xnew, long long n_new, void *f) {
   const RowSlices g = bnn_slices(n_new);
   BnnArgs<T> a = bnn_args<T>(c);
-  if (!flow_lds_attr<T>(k_bnn_forward<T>, a.net.lds_elems)) return false;
+  const auto forward_kernel = a.net.n[a.net.H + 1] >= 2 ? k_bnn_forward_head<T> : k_bnn_forward<T>;
+  if (!flow_lds_attr<T>(forward_kernel, a.net.lds_elems)) return false;
   a.n = a.nr = n_new;
   a.X = (const T *)Xnew;
   a.Z = (const T *)theta;
   a.f = (T *)f;
   a.n_sl = g.n_sl;
   a.rps = g.rps;
-  hipLaunchKernelGGL(k_bnn_forward<T>, dim3(M, g.n_sl), dim3(256), (size_t)a.net.lds_elems * sizeof(T), c->stream, a);
+  hipLaunchKernelGGL(forward_kernel, dim3(M, g.n_sl), dim3(256), (size_t)a.net.lds_elems * sizeof(T), c->stream, a);
   return true;
 }
 

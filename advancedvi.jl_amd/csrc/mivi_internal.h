@@ -880,7 +880,8 @@ bool launch_sm_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W =
 constexpr size_t kBnnPartCap = 128u << 20;         // bytes of the f64 partial planes a chunk of samples may take (at least one sample per chunk)
 bool bnn_reserve(mivi_ctx *c, int M);              // size bnn_part / bnn_ll for M samples per estimate (ahead of a graph capture)
 bool launch_bnn_target(mivi_ctx *c, int M, int want_grad);   // Z -> ell (and W = G); false: scratch allocation or the LDS size failed
-bool launch_bnn_forward(mivi_ctx *c, const void *theta, int M, const void *Xnew, long long n_new, void *f);   // f[r + n_new m]
+bool launch_bnn_forward(mivi_ctx *c, const void *theta, int M, const void *Xnew, long long n_new, void *f);   // f[r + n_new m]; n_out >= 2: f[c + n_out (r + n_new m)]
+size_t bnn_head_lds_bytes(const mivi_bnn_t &net, int p, size_t esize);   // LDS bytes of a workgroup of the head kernels (n_out >= 2)
 
 // kernels_hglm.hip: the hierarchical GLM target (api_hglm.hip sets it; eval_generic_target evaluates it)
 constexpr size_t kHglmPartCap = 256u << 20;        // bytes of the f64 partial planes a chunk of samples may take (at least one sample per chunk)

@@ -195,13 +195,15 @@ class SoftmaxRegSubset(_RowSubset):
 class BNNProblem:
     """A Bayesian neural network (mivi_set_target_bnn): the MLP p -> hidden_dims -> 1 with tanh hidden layers over
     theta = [vec W_1 (column-major, out x in); b_1; ...; vec W_{H+1}; b_{H+1}], theta_i ~ Normal(0, prior_std^2), and a Bernoulli (logit link,
-    y in {0, 1}) or Normal(f, noise) likelihood scaled by likeadj.  X is n x p, y has n entries; one to three hidden layers of width <= 64."""
+    y in {0, 1}) or Normal(f, noise) likelihood scaled by likeadj.  X is n x p, y has n entries; one to three hidden layers of width <= 64.
+    The multi-output head, p -> hidden_dims -> n_out with n_out <= 64: likelihood="categorical" with n_classes=C (a softmax link, y holds
+    the class labels 0 .. C - 1), or likelihood="normal" with a two-dimensional y of shape (n, k), k >= 2 (independent Normal(f_c, noise))."""
 
-    LIKELIHOODS = {"bernoulli": 0, "normal": 1}
+    LIKELIHOODS = {"bernoulli": 0, "normal": 1, "categorical": 0}   # (the logit family is code 0 at every number of outputs)
 
-    def __init__(self, X, y, hidden_dims, likelihood="bernoulli", noise=1.0, prior_std=1.0, likeadj=1.0):
+    def __init__(self, X, y, hidden_dims, likelihood="bernoulli", noise=1.0, prior_std=1.0, likeadj=1.0, n_classes=None):
         # device-resident data: a contiguous (p, n) tensor -- n x p column-major, as the kernel reads it -- and a tensor of n labels, both of
-        # the context's dtype
+        # the context's dtype; the responses of a multi-output Normal are then a contiguous (k, n) tensor, as X is (p, n)
         self.on_device = hasattr(X, "data_ptr")
         self.X = X if self.on_device else np.asarray(X)
         self.y = y if self.on_device else np.asarray(y)
@@ -209,12 +211,19 @@ class BNNProblem:
         self.hidden_dims = tuple(int(h) for h in hidden_dims)
         if likelihood not in self.LIKELIHOODS:
             raise ValueError(f"unknown likelihood {likelihood}")
+        if (likelihood == "categorical") != (n_classes is not None) or (n_classes is not None and int(n_classes) < 2):
+            raise ValueError('likelihood="categorical" takes n_classes >= 2, and no other likelihood takes n_classes')
         self.likelihood = likelihood
+        self.n_out = 1
+        if likelihood == "categorical":
+            self.n_out = int(n_classes)
+        elif likelihood == "normal" and len(self.y.shape) == 2:
+            self.n_out = int(self.y.shape[0] if self.on_device else self.y.shape[1])
         self.noise, self.prior_std, self.likeadj = float(noise), float(prior_std), float(likeadj)
 
     def layers(self):
         """[(out, in)] of W_1 .. W_{H+1}"""
-        widths = (self.p,) + self.hidden_dims + (1,)
+        widths = (self.p,) + self.hidden_dims + (self.n_out,)
         return [(widths[l + 1], widths[l]) for l in range(len(widths) - 1)]
 
     def dimension(self):
@@ -241,8 +250,9 @@ class BNNProblem:
 
     def predict(self, theta, Xnew, ctx=None):
         """Posterior predictive f of the M networks in theta (d x M: the samples `MiviContext.sample` returns, or a (d, M) array) on the
-        rows of Xnew (n_new x p): a device tensor (M, n_new), by mivi_bnn_forward.  ctx: a context that has this problem set; without one
-        a context of theta's precision is made for the call."""
+        rows of Xnew (n_new x p): a device tensor (M, n_new) -- (M, n_new, n_out) of logits, or of the Normal's means, for a multi-output
+        head -- by mivi_bnn_forward.  ctx: a context that has this problem set; without one a context of theta's precision is made for
+        the call."""
         from . import context as K
         own = ctx is None
         if own:

@@ -338,14 +338,28 @@ mivi_status_t mivi_softmax_set_plane_cap(mivi_ctx_t *ctx, int64_t bytes);
  * network target": mivi_optimize_loop_many, the batch schedule entries, mivi_gauss_expected_grad_hess2*, mivi_logreg_select_rows,
  * mivi_softmax_select_rows.  MIVI_ERR_BAD_ARG with a message: n < 1; p, n_hidden or a width outside its limits; d of the context not the
  * network's (the message gives the expected d); an unknown likelihood; noise, prior_std or likeadj <= 0 or not finite; a Bernoulli label
- * outside {0, 1} (host data); the target that was set stays. */
+ * outside {0, 1} (host data); the target that was set stays.
+ *
+ * The multi-output head, n_out = 2 .. MIVI_BNN_MAX_OUT (n_out 0 or 1: the one-output network above, unchanged): p -> h_1 .. h_H -> n_out,
+ * W_{H+1} is n_out x n_H column-major and b_{H+1} has n_out entries, f_r = W_{H+1} a_H + b_{H+1} is a vector.
+ *   likelihood 0: y_r ~ Categorical(softmax(f_r)),       ll_r = f_r[y_r] - logsumexp(f_r); y: n class labels 0 .. n_out - 1 stored as values
+ *                                                        of T (as the Bernoulli labels are)
+ *   likelihood 1: y_rc ~ Normal(f_rc, noise) independent, ll_r = sum_c [-1/2 (y_rc - f_rc)^2 / noise^2 - log noise - 1/2 log 2 pi];
+ *                                                        y: n x n_out COLUMN-major T (y[r + c*n])
+ * It runs on kernels of its own that keep the output layer in LDS beside the hidden ones; a workgroup may have MIVI_BNN_LDS_LIMIT bytes.
+ * In f32 every admitted network fits; in f64 the largest do not (64 -> 64, 64, 64 -> 64 does not; 64 -> 64, 64 -> 64 and
+ * 16 -> 64, 64, 64 -> 64 do).  More MIVI_ERR_BAD_ARG messages: n_out outside [0, 64]; a network over the LDS limit (the message gives the
+ * bytes it needs and the limit); a categorical label that is not an integer in [0, n_out) (host data; a Normal's y is any number). */
 #define MIVI_BNN_MAX_IN 64
 #define MIVI_BNN_MAX_HIDDEN 64
+#define MIVI_BNN_MAX_OUT 64
+#define MIVI_BNN_LDS_LIMIT 163840
 typedef struct {
   int32_t n_hidden;     /* H, 1 .. 3 */
   int32_t hidden[3];    /* widths, 1 .. MIVI_BNN_MAX_HIDDEN */
-  int32_t likelihood;   /* 0 Bernoulli-logit, 1 Normal(f, noise) */
+  int32_t likelihood;   /* 0 logit family (Bernoulli; categorical with a softmax link at n_out >= 2), 1 Normal(f, noise) */
   double  noise, prior_std, likeadj;
+  int32_t n_out;        /* outputs: 0 or 1 one output, 2 .. MIVI_BNN_MAX_OUT the multi-output head */
 } mivi_bnn_t;
 mivi_status_t mivi_set_target_bnn(mivi_ctx_t *ctx, const mivi_bnn_t *net, const void *X, const void *y, int64_t n, int32_t p,
                                   int32_t x_on_device);
@@ -354,7 +368,8 @@ mivi_status_t mivi_set_target_bnn(mivi_ctx_t *ctx, const mivi_bnn_t *net, const 
  * failed call leaves the selection unchanged.  The kernel reads the rows THROUGH the index vector: nothing is gathered. */
 mivi_status_t mivi_bnn_select_rows(mivi_ctx_t *ctx, const int64_t *idx_host, int64_t b, double likeadj);
 /* Posterior predictive: f_dev[r + n_new*m] = f(Xnew[r]; theta[:, m]) for the M networks in theta_dev (d x M, ld d) on the rows of Xnew_dev
- * (n_new x p column-major, device), with the architecture of the target that is set.  Asynchronous on the context's stream. */
+ * (n_new x p column-major, device), with the architecture of the target that is set; with n_out >= 2 outputs f_dev holds n_out n_new M
+ * values, f_dev[c + n_out*(r + n_new*m)] = f_c (the logits, or the Normal's means).  Asynchronous on the context's stream. */
 mivi_status_t mivi_bnn_forward(mivi_ctx_t *ctx, const void *theta_dev, int32_t M, const void *Xnew_dev, int64_t n_new, void *f_dev);
 /* Internal (tests): the byte cap of the f64 partial-gradient planes, which decides how many samples a chunk of the target's launches
  * takes (at least one).  0 restores the default (128 MiB).  Results do not depend on it, bit for bit. */
